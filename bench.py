@@ -18,6 +18,18 @@ gather to rank (step mod N) -- all three are printed under `modes` with the wire
 (`sharding.gather_model`) and the speed-up over one of this run's own ranks that each implies.  `--no-gather` /
 `--gather-dst 0|rotate` restrict the run to one mode.
 
+A plain run does what the headline needs and no more: set-up, `--warmup` steps, ONE block of exactly `--steps` timed
+steps (`ms_per_step` = that block / `--steps`), the outputs of the last timed step if `--dump-outputs DIR` is given, and the
+line.  `--full` adds everything else this script measures or checks: the median of >= 5 blocks covering >= 1 s (the
+defaults of `--blocks` / `--min-seconds` under `--full`), the SHA-256 check of the timed frames against an eagerly launched
+one, the one-context loop beside two frames in flight, per-stage times (an eager pass of its own), the roofline figures, the
+device-copy bandwidth and the CPU baseline.
+
+`--dump-outputs DIR` writes, from the frame of the last timed step (rank 0), `DIR/<name>.npy` in float32 / float64: the
+RGBA image (`image`, H x W x 4, when it has at most 2^20 pixels; else `image_sample` = 2^20 of its pixels at fixed, seeded
+flat indices, `image_sample_index`), `image_row_sum` (the f64 sum of every row, per channel: every pixel of the frame) and
+`bump` (the 8 bump allocator words, BUMP_NAMES).  The scenes are seeded, so the same arguments give the same inputs.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -32,6 +44,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~4.8 TB/s is what a device copy reaches
 BUMP_NAMES = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]
+DUMP_PIXELS = 1 << 20  # --dump-outputs: a larger image is sampled at this many pixels (16 MiB of f32 RGBA + 8 MiB of indices)
+DUMP_SEED = 0x64756D70  # "dump"
+DUMP_STRIDE = 2654435761  # a prime above any pixel count: i -> (i * DUMP_STRIDE + DUMP_SEED) mod pixels is one to one
 
 
 def parse_args(argv=None):
@@ -48,19 +63,25 @@ def parse_args(argv=None):
     ap.add_argument("--paths", type=int, default=0, help="default: 100000 (c3) / 30000 (c4)")
     ap.add_argument("--size", type=int, default=0, help="default: 4096 (c3) / 2048 (c4)")
     ap.add_argument("--aa", choices=["area", "msaa8", "msaa16"], default="area", help="coverage mode of the fine stage (the headline is area)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (see the module docstring): block statistics, the "
+                         "timed-frame SHA-256 check, the one-context loop, per-stage times, roofline, copy bandwidth, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32 / f64, < 30 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: time only the independent renders, no image gather")
     ap.add_argument("--gather-dst", choices=["all", "0", "rotate"], default="all",
                     help="N > 1: where the finished frames are collected: on rank 0 (C5 as written: one compositor GPU; its inbound "
                          "links bound the job) or on rank (step mod N) -- consecutive gathers then use disjoint inbound links and, "
                          "being double-buffered on two communicators, overlap each other as well as the next render; "
                          "all (default) = time both, after the gather-free loop, in one run")
-    ap.add_argument("--blocks", type=int, default=5,
-                    help="timed blocks of --steps steps each; the line reports the median block.  More blocks are added (up to 101) until "
-                         "the timed region of a mode covers >= 1 s, so that a short --steps still keeps the GPU busy long enough to be seen")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="blocks are added until a mode's timed region covers this long (0: exactly --blocks blocks; the counter passes "
-                         "of tools/pmc*.sh use that -- every extra frame is rows in their CSVs)")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of --steps steps each; the line reports the median block.  Default 1 (exactly --steps timed steps); "
+                         "5 with --full, where more blocks are added (up to 101) until the timed region of a mode covers >= 1 s, so that a "
+                         "short --steps still keeps the GPU busy long enough to be seen")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="blocks are added until a mode's timed region covers this long (default 0 = exactly --blocks blocks; 1.0 with "
+                         "--full; the counter passes of tools/pmc*.sh pass 0 -- every extra frame is rows in their CSVs)")
     ap.add_argument("--bands", action="store_true",
                     help="N > 1: ONE scene, every rank runs the element stages on it and coarse+fine for its band of bin rows "
                          "(strong scaling of one frame; SURVEY 8e) instead of one independent scene per rank")
@@ -70,12 +91,16 @@ def parse_args(argv=None):
     ap.add_argument("--in-flight", type=int, choices=[1, 2], default=2,
                     help="frames in flight per GPU: 2 (default) = two engine contexts (own stream, buffers, scratch, graph) take the steps "
                          "in turn, so the kernels of frame i + 1 fill the launch gaps and tails of frame i; 1 = one context, one "
-                         "frame after the other (every round before round 4; also timed beside the default for comparison)")
+                         "frame after the other (every round before round 4; --full also times it beside the default for comparison)")
     args = ap.parse_args(argv)
     if args.paths <= 0:
         args.paths = {"c3": 100_000, "c2": 300, "c1": 2}.get(args.scene, 30_000)
     if args.size <= 0:
         args.size = {"c3": 4096, "c2": 1024, "c1": 512}.get(args.scene, 2048)
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
+    if args.min_seconds is None:
+        args.min_seconds = 1.0 if args.full else 0.0
     return args
 
 
@@ -207,7 +232,7 @@ def run_rank(args, world):
         h.update(eng_of[k].download(rec.buffer("bumpBuf")[0], dtype=np.uint32)[:8].tobytes())
         h.update(outs[k].cpu().numpy().tobytes())
         return h.hexdigest()
-    eager_digest = frame_digest(0)  # an eagerly launched frame; every timed frame must reproduce it
+    eager_digest = frame_digest(0) if args.full else None  # an eagerly launched frame; every timed frame must reproduce it
 
     # One frame is ~45 short launches, so the dispatch-only replay of the recording is captured once into a hipGraph
     # per output buffer and the timed steps replay it.
@@ -216,8 +241,10 @@ def run_rank(args, world):
     pipe = sharding.GatherPipeline(dist, rank, world, outs, gathered, gather_groups, streams=streams if n_ctx == 2 else None,
                                    alternate=n_ctx == 2)
     pipe_one = sharding.GatherPipeline(dist, rank, world, outs[:1], None, None)  # one context, one frame after the other
+    last_k = [0]  # the output buffer of the most recent step (--dump-outputs)
 
     def render(k):
+        last_k[0] = k
         if use_graph:
             eng_of[k].replay(graphs[k])
         else:
@@ -259,8 +286,8 @@ def run_rank(args, world):
         return sorted(blocks)
 
     blocks_plain = timed(None)
-    # (two frames in flight: the one-context loop of the earlier rounds timed beside it, three blocks)
-    blocks_one = timed(None, pipe_one, 3) if n_ctx == 2 else None
+    # (--full, two frames in flight: the one-context loop of the earlier rounds timed beside it, three blocks)
+    blocks_one = timed(None, pipe_one, 3) if (args.full and n_ctx == 2) else None
     # Each gather mode on its own: one that raises (the first contact of this path with RCCL on real hardware has not
     # happened yet) is reported as {"error": ...} under `modes`; the gather-free measurement above and the line survive,
     # and the process exits non-zero.  The ranks agree on a mode's fate through the default group (gloo-free: a MIN
@@ -281,52 +308,59 @@ def run_rank(args, world):
     blocks = blocks_by_mode[head_mode] if gather else blocks_plain
     elapsed_plain = blocks_plain[len(blocks_plain) // 2]
     elapsed = blocks[len(blocks) // 2]  # the median block
-    # The frames that were timed are the frame that was checked: replayed (or re-run) frames must be bit-identical to the
-    # eager one -- image and bump allocators -- or the number describes something else.
-    for k, o in enumerate(outs):
-        d = frame_digest(k)
-        if d != eager_digest:
-            raise RuntimeError("rank %d: the timed frame in output buffer %d differs from the eagerly launched frame (SHA-256 %s vs %s)"
-                               % (rank, k, d[:16], eager_digest[:16]))
+    if args.dump_outputs and rank == 0:  # the frame of the last timed step, before anything else renders into its buffer
+        torch.cuda.synchronize(dev)
+        k = last_k[0]
+        dump_outputs(args.dump_outputs, outs[k].cpu().numpy(),
+                     eng_of[k].download(rec.buffer("bumpBuf")[0], dtype=np.uint32)[:len(BUMP_NAMES)])
+    if args.full:
+        # The frames that were timed are the frame that was checked: replayed (or re-run) frames must be bit-identical to the
+        # eager one -- image and bump allocators -- or the number describes something else.
+        for k, o in enumerate(outs):
+            d = frame_digest(k)
+            if d != eager_digest:
+                raise RuntimeError("rank %d: the timed frame in output buffer %d differs from the eagerly launched frame (SHA-256 %s vs %s)"
+                                   % (rank, k, d[:16], eager_digest[:16]))
 
-    # Per-stage device times: the same K steps once more, eagerly, with a hipEvent pair around every stage on the
-    # launch stream (events cannot be read back from inside a replayed graph).
-    eng.profile(True)
-    for i in range(args.steps):
-        eng.run(rec, RUN_DISPATCHES, outs[0].data_ptr())
-    torch.cuda.synchronize(dev)
-    prof = eng.profile_collect(1 << 16)
-    eng.profile(False)
-    stage_ms = {}
-    for name, ms in prof:
-        stage_ms[name] = stage_ms.get(name, 0.0) + ms
-    stage_ms = {k: v / args.steps for k, v in stage_ms.items()}
-    fine_ms = stage_ms.get(fine_stage, float("nan"))
+        # Per-stage device times: the same K steps once more, eagerly, with a hipEvent pair around every stage on the
+        # launch stream (events cannot be read back from inside a replayed graph).
+        eng.profile(True)
+        for i in range(args.steps):
+            eng.run(rec, RUN_DISPATCHES, outs[0].data_ptr())
+        torch.cuda.synchronize(dev)
+        prof = eng.profile_collect(1 << 16)
+        eng.profile(False)
+        stage_ms = {}
+        for name, ms in prof:
+            stage_ms[name] = stage_ms.get(name, 0.0) + ms
+        stage_ms = {k: v / args.steps for k, v in stage_ms.items()}
+        fine_ms = stage_ms.get(fine_stage, float("nan"))
 
     result = None
     if rank == 0:
-        # ---- algorithmic bytes of the fine stage, from the PTCL this run produced ----
-        ptcl_id, _ = rec.buffer("ptclBuf")
-        ptcl = eng.download(ptcl_id, dtype=np.uint32)
-        st = (ctypes.c_uint64 * 8)()
-        if eng._L.jl_ptcl_stats(ptcl.ctypes.data, ptcl.size, cfg["width_in_tiles"], cfg["height_in_tiles"], st) != 0:
-            raise RuntimeError("malformed PTCL")
-        words, segs, info_words, texels, spill_px = st[0], st[1], st[2], st[3], st[4]
-        b_fine = 4 * words + 24 * segs + 4 * info_words + 8 * texels + 32 * spill_px + 8 * W * H
-        achieved = b_fine / (fine_ms * 1e-3) / 1e9
         bump_now = dict(zip(BUMP_NAMES, [int(v) for v in eng.download(rec.buffer("bumpBuf")[0], dtype=np.uint32)[:8]]))
-        copy_gbs = measured_copy_gbs(torch, dev)
-        kname = "k_fine_area" if args.aa == "area" else "k_fine_area<%s>" % args.aa
-        roofline = {"kernel": kname, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None, "algorithmic_bytes": int(b_fine), "avg_ms": round(fine_ms, 4),
-                    "segment_pixel_evals": int(segs) * 256,
-                    "peak_measured_copy": None if copy_gbs is None else round(copy_gbs, 1)}
-        roofline.update(committed_counters(args, fine_ms))
-        if args.bands and (world > 1 or args.emulate_band_of > 1):  # one band only: the whole-target byte count does not apply
-            roofline = None
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(host, args)
+        roofline = cpu = None
+        if args.full:
+            # ---- algorithmic bytes of the fine stage, from the PTCL this run produced ----
+            ptcl_id, _ = rec.buffer("ptclBuf")
+            ptcl = eng.download(ptcl_id, dtype=np.uint32)
+            st = (ctypes.c_uint64 * 8)()
+            if eng._L.jl_ptcl_stats(ptcl.ctypes.data, ptcl.size, cfg["width_in_tiles"], cfg["height_in_tiles"], st) != 0:
+                raise RuntimeError("malformed PTCL")
+            words, segs, info_words, texels, spill_px = st[0], st[1], st[2], st[3], st[4]
+            b_fine = 4 * words + 24 * segs + 4 * info_words + 8 * texels + 32 * spill_px + 8 * W * H
+            achieved = b_fine / (fine_ms * 1e-3) / 1e9
+            copy_gbs = measured_copy_gbs(torch, dev)
+            kname = "k_fine_area" if args.aa == "area" else "k_fine_area<%s>" % args.aa
+            roofline = {"kernel": kname, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None, "algorithmic_bytes": int(b_fine), "avg_ms": round(fine_ms, 4),
+                        "segment_pixel_evals": int(segs) * 256,
+                        "peak_measured_copy": None if copy_gbs is None else round(copy_gbs, 1)}
+            roofline.update(committed_counters(args, fine_ms))
+            if args.bands and (world > 1 or args.emulate_band_of > 1):  # one band only: the whole-target byte count does not apply
+                roofline = None
+            if world == 1 and not args.no_cpu_baseline:
+                cpu = cpu_baseline(host, args)
         units = 1 if args.bands else world  # frames finished per step by the whole job
         per = elapsed / args.steps
         mode = ("bin-row bands of one scene x%d" % world) if args.bands else \
@@ -340,9 +374,9 @@ def run_rank(args, world):
         result = {
             "metric": metric, "value": round(W * H * units / per / 1e6, 2), "unit": "Mpixels/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(per * 1e3, 4), "higher_is_better": True,
+            "full": bool(args.full),
             "blocks": len(blocks), "block_ms_per_step": [round(b / args.steps * 1e3, 4) for b in blocks],
             "block_spread": round((blocks[-1] - blocks[0]) / elapsed, 4),
-            "timed_frames_verified": "SHA-256 of image + bump allocators equals an eagerly launched frame (%s...)" % eager_digest[:16],
             "scaling": "strong" if args.bands else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s, %dx%d RGBA16F target, %s AA, %s" % (what, W, H, args.aa,
                                    "one scene split into bin-row bands" if args.bands else "one independent scene per GPU"),
@@ -351,27 +385,31 @@ def run_rank(args, world):
                                  "%d frame(s) in flight per GPU%s" % (n_ctx, "" if world == 1 else ", %d GPUs, one scene each" % world)),
             "paths_per_s": round(args.paths * units / per, 1),
             "paths_per_s_definition": "a RATE (user paths of the frames finished per second), not SURVEY 8(d)'s scene-resident -> image-complete "
-                                      "time of one frame: that is paths_per_s_latency",
-            "paths_per_s_latency": None if blocks_one is None else round(args.paths / (blocks_one[len(blocks_one) // 2] / args.steps), 1),
-            "fine_mpixels_per_s": round(W * H / (fine_ms * 1e-3) / 1e6, 2),
+                                      "time of one frame: that is paths_per_s_latency (--full)",
             "frames_in_flight": n_ctx,
-            "one_frame_at_a_time": None if blocks_one is None else {
-                "ms_per_step": round(blocks_one[len(blocks_one) // 2] / args.steps * 1e3, 4),
-                "value": round(W * H * units / (blocks_one[len(blocks_one) // 2] / args.steps) / 1e6, 2),
-                "note": "the gather-free loop on ONE context (no overlap between consecutive frames), as every round before round 4 timed it"},
             "launch": "hipGraph replay" if use_graph else "eager",
             "launches_per_frame": None if not use_graph else dict(zip(("kernels", "fills_and_copies"), eng.graph_node_counts(graphs[0]))),
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
-            "stage_ms_source": "eager replay of the same %d steps with a hipEvent pair per stage" % args.steps,
-            "stage_ms_regime": "one context, eager (a stage's duration is its own: the sum is a frame alone, not ms_per_step with %d frames in flight)" % n_ctx,
             "bump": bump_now, "scratch_bytes_per_context": eng.scratch_bytes(), "sizing_attempts": attempts, "bump_estimate_clamped": scene.bump_sizes_clamped(W, H),
-            "stage_roofline": stage_roofline(cfg, bump_now, stage_ms, rec),
-            "roofline": roofline,
-            "cpu_baseline": cpu,
             "device": eng.device_info()["name"],
         }
+        if args.full:
+            result.update({
+                "timed_frames_verified": "SHA-256 of image + bump allocators equals an eagerly launched frame (%s...)" % eager_digest[:16],
+                "paths_per_s_latency": None if blocks_one is None else round(args.paths / (blocks_one[len(blocks_one) // 2] / args.steps), 1),
+                "fine_mpixels_per_s": round(W * H / (fine_ms * 1e-3) / 1e6, 2),
+                "one_frame_at_a_time": None if blocks_one is None else {
+                    "ms_per_step": round(blocks_one[len(blocks_one) // 2] / args.steps * 1e3, 4),
+                    "value": round(W * H * units / (blocks_one[len(blocks_one) // 2] / args.steps) / 1e6, 2),
+                    "note": "the gather-free loop on ONE context (no overlap between consecutive frames), as every round before round 4 timed it"},
+                "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+                "stage_ms_source": "eager replay of the same %d steps with a hipEvent pair per stage" % args.steps,
+                "stage_ms_regime": "one context, eager (a stage's duration is its own: the sum is a frame alone, not ms_per_step with %d frames in flight)" % n_ctx,
+                "stage_roofline": stage_roofline(cfg, bump_now, stage_ms, rec),
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+            })
         if world == 1:
-            result["value_mode"] = "%d frame(s) in flight on one GPU%s" % (n_ctx, "" if n_ctx == 1 else " (the one-context figure of rounds 1-3 is one_frame_at_a_time.value)")
+            result["value_mode"] = "%d frame(s) in flight on one GPU%s" % (n_ctx, "" if n_ctx == 1 else " (the one-context figure of rounds 1-3 is one_frame_at_a_time.value, --full)")
         if world > 1 and not args.bands:
             # Every mode of this run side by side.  `render` = the gather-free step of THIS run (every rank finishes one frame
             # per step), so N * render / step is the speed-up over one of this run's own ranks that a mode delivers.
@@ -423,6 +461,25 @@ def run_rank(args, world):
         print(json.dumps(result))
     if mode_errors:  # the line is out; a gather mode that failed still fails the run
         sys.exit(3)
+
+
+def dump_outputs(path, image, bump_words):
+    """--dump-outputs: the finished frame (H x W x 4 float16 RGBA on the host) and its bump allocator words as DIR/<name>.npy.
+    An image of more than DUMP_PIXELS pixels is sampled at DUMP_PIXELS distinct flat pixel indices, (i * DUMP_STRIDE + DUMP_SEED)
+    mod pixels for i < DUMP_PIXELS, sorted (fixed for a given size); its per-row sums cover every pixel."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = image.astype(np.float32)  # (exact: every float16 is a float32)
+    h, w = img.shape[:2]
+    arrays = {"bump": np.asarray(bump_words, dtype=np.float64), "image_row_sum": img.sum(axis=1, dtype=np.float64)}
+    if h * w <= DUMP_PIXELS:
+        arrays["image"] = img
+    else:
+        idx = np.sort((np.arange(DUMP_PIXELS, dtype=np.int64) * DUMP_STRIDE + DUMP_SEED) % (h * w))
+        arrays["image_sample"] = img.reshape(-1, 4)[idx]
+        arrays["image_sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def measured_copy_gbs(torch, dev):

@@ -21,11 +21,11 @@ cp gpurun_out/fine_counters*.json profiles/ 2>/dev/null
 for S in c3 c4 c4n; do
   bash tools/kprof.sh col_$S --scene $S > "$O/${S}_summary.txt" 2>&1 || exit 1
   cp gpurun_out/kprof_col_$S/kernel_stats.csv "$O/${S}_kernel_stats.csv"
-  timeout -k 10 300 python3 bench.py --scene $S > "$O/${S}_bench.json" 2> "$O/${S}_bench.err" || exit 1
+  timeout -k 10 300 python3 bench.py --full --scene $S > "$O/${S}_bench.json" 2> "$O/${S}_bench.err" || exit 1
   echo "bench $S done"
 done
-timeout -k 10 300 python3 bench.py --aa msaa8 --no-cpu-baseline > "$O/c3_msaa8_bench.json" 2>/dev/null
-timeout -k 10 300 python3 bench.py --aa msaa16 --no-cpu-baseline > "$O/c3_msaa16_bench.json" 2>/dev/null
+timeout -k 10 300 python3 bench.py --full --aa msaa8 --no-cpu-baseline > "$O/c3_msaa8_bench.json" 2>/dev/null
+timeout -k 10 300 python3 bench.py --full --aa msaa16 --no-cpu-baseline > "$O/c3_msaa16_bench.json" 2>/dev/null
 fi
 [ "$PART" = 1 ] && exit 0
 bash tools/fine_split.sh "$COMMIT" > "$O/fine_split.log" 2>&1 && cp gpurun_out/fine_split.json "$O/" && echo "fine split done"
@@ -35,7 +35,7 @@ echo "ptcl stats done"
 ( timeout -k 10 300 python3 tools/time_configs.py; timeout -k 10 300 python3 tools/time_shapes.py ) > "$O/other_scenes.txt" 2>&1
 echo "other scenes done"
 # round 4: the small configurations as bench lines, the counters of the flatten and tile-stage kernels, the split of k_flatten_items
-for S in c1 c2; do timeout -k 10 300 python3 bench.py --scene $S --no-cpu-baseline > "$O/${S}_bench.json" 2>/dev/null; done
+for S in c1 c2; do timeout -k 10 300 python3 bench.py --full --scene $S --no-cpu-baseline > "$O/${S}_bench.json" 2>/dev/null; done
 bash tools/pmc_flatten.sh > "$O/pmc_flatten_tile_kernels.txt" 2>&1 && echo "pmc flatten / tile kernels done"
 bash tools/flatten_split.sh > "$O/flatten_split.txt" 2>&1 && echo "flatten split done"
 # round 5: k_flatten_lines split, frames in flight, and -- if the round-5 library was built next to the product one

@@ -8,7 +8,7 @@ TAG=${1:-run}; shift
 OUT=$R/gpurun_out/kprof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/raw" -- python3 "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --in-flight 1 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/raw" -- python3 "$R/bench.py" --full --steps 20 --warmup 3 --no-cpu-baseline --in-flight 1 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
 F=$(ls "$OUT"/raw/*/*kernel_stats.csv | head -1)
 cp "$F" "$OUT/kernel_stats.csv"
 rm -rf "$OUT/raw"

@@ -14,7 +14,7 @@ for r in rows:
     name = col(r, "Kernel_Name").replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
     ev.append((s, e, q, name))
 ev.sort()
-# bench.py --steps K --blocks 1 launches the fine kernel, from the end of the run backwards: K times in the eager per-stage pass, 3 (K + 1)
+# bench.py --full --steps K --blocks 1 launches the fine kernel, from the end of the run backwards: K times in the eager per-stage pass, 3 (K + 1)
 # times one frame at a time (warm-up 3 + three blocks ... with --warmup 3: 3 + 3 K), K times in the timed block with two frames in
 # flight -- the block this report is about.
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 60

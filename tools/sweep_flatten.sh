@@ -8,5 +8,5 @@ for cfg in "${FL_CFGS[@]}"; do
   set -- $cfg
   make -s -C jello_amd/csrc EXTRA="-DFL_REFILL_LANES=${1}u -DFL_WAVES_PER_EU=$2 -DFL_BLOCKS_PER_CU=$3" > /dev/null 2>&1
   echo -n "refill=$1 waves/eu=$2 blocks/cu=$3  "
-  timeout -k 10 200 python3 bench.py --steps 20 --warmup 2 --blocks 3 --no-cpu-baseline --no-graph 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['ms_per_step'], d['stage_ms'].get('flatten'))"
+  timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 2 --blocks 3 --no-cpu-baseline --no-graph 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['ms_per_step'], d['stage_ms'].get('flatten'))"
 done

@@ -6,5 +6,5 @@ trap 'make -s -C jello_amd/csrc > /dev/null 2>&1' EXIT
 for e in ${PC_THRESH:-64 128 256 1024}; do
   make -s -C jello_amd/csrc EXTRA="-DPC_BIG_PATH=${e}u" > /dev/null 2>&1
   echo -n "PC_BIG_PATH=$e  "
-  timeout -k 10 200 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['ms_per_step'], d['stage_ms'].get('path_count'))"
+  timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print(d['ms_per_step'], d['stage_ms'].get('path_count'))"
 done
