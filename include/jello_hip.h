@@ -17,6 +17,7 @@
  *   jh_profile_group_begin/end    Profiler.Start / Nest / End          profiler.go:49-65, 113-158
  *   jh_profile_collect_tree       Profiler.Collect (nested results)    profiler.go:304-385
  *   jh_stage                      renderer.FullShaders field order     renderer/render.go:17-43
+ *   jh_blit                       RenderToSurface's blit pass          engine/wgpu_engine/lib.go:109-198, 266-333
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -187,6 +188,38 @@ int jh_graph_launch(jh_ctx* ctx, void* graph_exec);
 /* What the capture recorded: kernel launches and other nodes (fills, copies) of one replay -- the launches per frame. */
 int jh_graph_node_counts(jh_ctx* ctx, void* graph_exec, uint32_t* kernel_nodes, uint32_t* other_nodes);
 int jh_graph_destroy(jh_ctx* ctx, void* graph_exec);
+
+/* ---- surface blit (RenderToSurface, engine/wgpu_engine/lib.go:266-333) ----
+ * The reference renders into an RGBA16F target and then draws it into the surface with a blit pass that premultiplies
+ * (vec4(rgb * a, a), lib.go:109-198) and writes RendererOptions.SurfaceFormat (lib.go:19-22).  jh_surface_format is that
+ * choice; it is separate from JlImageFormat, which mirrors renderer.ImageFormat.
+ *
+ * Conversion rule (the hardware's float -> unorm and linear -> sRGB conversions are implementation-defined; this is the
+ * project's definition, DESIGN.md "Surface blit"):  c = a colour channel, a = alpha, both the stored f16 widened to f32.
+ *   premultiply   p = c * a in f32 (exact: an f16 x f16 product needs at most 22 significand bits); alpha passes as a
+ *   clamp         v = min(max(p, 0), 1); NaN (inf * 0 included) -> 0, +inf -> 1
+ *   unorm         u8 = rint_f32(v * 255.0f)  (the product rounded to nearest-even in f32, then ties to even) -- also alpha in
+ *                 every format
+ *   sRGB colour   u8 = rint_f64(255 enc(v)), enc(v) = 12.92 v for v <= 0.0031308, 1.055 v^(1/2.4) - 0.055 otherwise, in
+ *                 binary64 on the f32 value; alpha stays linear.  The kernel uses a table of 255 f32 thresholds
+ *                 (jello_amd/csrc/srgb_encode_lut.h, tools/gen_srgb_encode_table.py): u8 = #{k : t[k] <= v}
+ *   channel order BGRA formats swap bytes 0 and 2 */
+typedef enum jh_surface_format {
+    JH_SURFACE_RGBA8_UNORM = 0,
+    JH_SURFACE_BGRA8_UNORM = 1,
+    JH_SURFACE_RGBA8_SRGB = 2,
+    JH_SURFACE_BGRA8_SRGB = 3
+} jh_surface_format;
+/* Converts the RGBA16F image src_image_id (width x height, JL_RGBA16_FLOAT) into caller-owned device memory: height rows of
+ * 4 * width bytes, dst_pitch_bytes apart; the bytes between 4 * width and the pitch are never written.  Stream-ordered on the
+ * context's stream, one kernel launch, may be captured between jh_graph_begin and jh_graph_end (the graph then holds
+ * dst_device_ptr).  A source that was never written (created only, or uploaded as all zero bytes) blits as transparent black.
+ * In band mode (jh_set_band) only the pixel rows of the active bin rows are written, so the bands of several contexts compose
+ * into one surface.  With profiling on it is a query labelled "blit" with stage = -1 in jh_profile_collect_tree (not a
+ * jh_profile_collect record).  JH_ERR_INVALID, with nothing enqueued, for an unknown or non-RGBA16F source, a size that differs
+ * from the source's, a pitch below 4 * width, a null dst or an unknown format. */
+int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t dst_pitch_bytes, uint32_t width, uint32_t height,
+            int surface_format);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

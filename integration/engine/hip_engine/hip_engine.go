@@ -37,6 +37,29 @@ type Engine struct {
 	resolver    *renderer.Resolver
 	fullShaders *renderer.FullShaders
 	downloads   map[renderer.ResourceID][]byte
+	target      *targetTexture // RenderToSurface's RGBA16F target (eng.target, lib.go:279-284)
+}
+
+// SurfaceFormat is RendererOptions.SurfaceFormat (lib.go:19-22): the 8-bit format RenderToSurface writes
+// (jh_surface_format; the conversion rule is in include/jello_hip.h).
+type SurfaceFormat int
+
+const (
+	SurfaceRGBA8Unorm SurfaceFormat = C.JH_SURFACE_RGBA8_UNORM
+	SurfaceBGRA8Unorm SurfaceFormat = C.JH_SURFACE_BGRA8_UNORM
+	SurfaceRGBA8Srgb  SurfaceFormat = C.JH_SURFACE_RGBA8_SRGB
+	SurfaceBGRA8Srgb  SurfaceFormat = C.JH_SURFACE_BGRA8_SRGB
+)
+
+// surfaceTargetID names the target's buffer on the context: recordings take their ResourceIDs from a counter that starts at 1
+// (recording.go:15-19) and never reaches the top bit.
+const surfaceTargetID renderer.ResourceID = 1<<63 | 0x7461726765740000
+
+// targetTexture: a context buffer of Width*Height RGBA16F pixels (lib.go:200-226 newTargetTexture).
+type targetTexture struct {
+	id            renderer.ResourceID
+	ptr           unsafe.Pointer
+	Width, Height uint32
 }
 
 // New mirrors wgpu_engine.New (wgpu.go:157-178).  device is the HIP device ordinal; one Engine per
@@ -252,10 +275,19 @@ func maxClipDepth(enc *encoding.Encoding) uint32 {
 // target is device memory for Width*Height RGBA16F pixels.  Returns the attempts it took.
 func (e *Engine) RenderToTexture(arena *mem.Arena, enc *encoding.Encoding, target unsafe.Pointer,
 	params *renderer.RenderParams, pgroup profiler.ProfilerGroup) int {
+	return e.renderToTexture(arena, enc, target, params, pgroup, nil)
+}
+
+// renderToTexture is RenderToTexture; outImage, if not nil, receives the target's ImageProxy of the final attempt.
+func (e *Engine) renderToTexture(arena *mem.Arena, enc *encoding.Encoding, target unsafe.Pointer,
+	params *renderer.RenderParams, pgroup profiler.ProfilerGroup, outImage *renderer.ImageProxy) int {
 	for attempt := 1; ; attempt++ {
 		var render renderer.Render
 		recording := e.renderer.RenderEncodingCoarse(arena, &render, enc, e.resolver, e.fullShaders, params, true, pgroup)
 		out := render.OutImage()
+		if outImage != nil {
+			*outImage = out
+		}
 		bumpID := render.BumpBuf().ID // (accessor added by the patch; the proxy of the "bumpBuf" buffer)
 		recording = e.renderer.RecordFine(arena, &render, e.fullShaders, recording, pgroup)
 		// fine's blend-stack scratch is sized from the nesting depth of the clip layers (include/jello_hip.h,
@@ -299,6 +331,34 @@ func (e *Engine) RenderToTexture(arena *mem.Arena, enc *encoding.Encoding, targe
 			return attempt // nothing left to grow
 		}
 	}
+}
+
+// RenderToSurface mirrors lib.go:266-333: RenderToTexture into the engine's own RGBA16F target (kept while the size stays
+// the same, lib.go:279-284), then the blit pass (lib.go:109-198) -- premultiply, convert to format -- into surface: device
+// memory of params.Height rows of 4*params.Width bytes, pitch bytes apart (bytes past 4*Width are not written).  The blit is
+// stream-ordered behind the frame; the surface is ready once the context's stream is (the regrow loop of RenderToTexture
+// already waited for the frame).  Returns the attempts RenderToTexture took.
+func (e *Engine) RenderToSurface(arena *mem.Arena, enc *encoding.Encoding, surface unsafe.Pointer, pitch uint64,
+	format SurfaceFormat, params *renderer.RenderParams, pgroup profiler.ProfilerGroup) int {
+	label := C.CString("RenderToSurface")
+	defer C.free(unsafe.Pointer(label))
+	e.check(C.jh_profile_group_begin(e.ctx, label), "profile_group_begin")
+	defer C.jh_profile_group_end(e.ctx)
+	if e.target == nil || e.target.Width != params.Width || e.target.Height != params.Height {
+		if e.target != nil {
+			e.check(C.jh_free(e.ctx, C.uint64_t(e.target.id)), "free")
+		}
+		id := surfaceTargetID
+		e.check(C.jh_buffer_create(e.ctx, C.uint64_t(id), C.uint64_t(uint64(params.Width)*uint64(params.Height)*8)), "buffer_create")
+		e.target = &targetTexture{id: id, ptr: C.jh_buffer_device_ptr(e.ctx, C.uint64_t(id)), Width: params.Width, Height: params.Height}
+	}
+	var out renderer.ImageProxy
+	attempts := e.renderToTexture(arena, enc, e.target.ptr, params, pgroup, &out)
+	e.check(C.jh_blit(e.ctx, C.uint64_t(out.ID), surface, C.uint64_t(pitch), C.uint32_t(params.Width), C.uint32_t(params.Height),
+		C.int(format)), "blit")
+	// the target image of this frame is an import over e.target: forgetting it frees nothing
+	e.check(C.jh_image_free(e.ctx, C.uint64_t(out.ID)), "image_free")
+	return attempts
 }
 
 // TrimScratch gives the context's internal scratch arrays back (the count / offset arrays of the deterministic allocators,

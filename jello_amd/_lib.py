@@ -164,6 +164,10 @@ def _declare(L):
     L.jl_engine_release.argtypes = [vp, vp]
     L.jl_engine_render.restype = vp
     L.jl_engine_render.argtypes = [vp, vp, ctypes.POINTER(CRenderParams), vp, ci, ci, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ci)]
+    L.jl_engine_render_to_surface.restype = vp
+    L.jl_engine_render_to_surface.argtypes = [vp, vp, ctypes.POINTER(CRenderParams), vp, ctypes.c_uint64, ci, ci,
+                                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ci)]
+    L.jl_engine_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
     L.hip = hip
@@ -189,6 +193,9 @@ def _declare(L):
     hip.jh_profile_group_end.argtypes = [vp]
     hip.jh_profile_collect_tree.argtypes = [vp, vp, ci]
     hip.jh_image_create.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
+    hip.jh_image_upload.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci, vp, ctypes.c_uint64]
+    hip.jh_image_free.argtypes = [vp, ctypes.c_uint64]
+    hip.jh_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]
     hip.jh_graph_begin.argtypes = [vp]

@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstdio>
@@ -39,6 +40,7 @@ struct Alloc {
     int format = 0;
     bool pending_clear = false;
     bool written = false;   // images: has content (uploaded / imported); a created-only image reads as zero like a new wgpu texture
+    bool stored = false;    // images: bound as a dispatch's storage image (fine's target) -- has content for jh_blit, not for sampling
 };
 
 // One node of the profile tree (engine/wgpu_engine/profiler.go:96-158): a group (Start/Nest ... End: CPU interval and
@@ -912,6 +914,11 @@ static int dispatch_common(jh_ctx* ctx, int stage, uint32_t gx, uint32_t gy, uin
     if (rc) return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + jh_stage_name(stage));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, jh_stage_name(stage));
+    for (int i = 0; i < n_bindings; i++)
+        if (bindings[i].kind == JH_BIND_IMAGE) {
+            auto it = ctx->images.find(bindings[i].id);
+            if (it != ctx->images.end()) it->second.stored = true;
+        }
     return JH_OK;
 }
 
@@ -1058,7 +1065,7 @@ int jh_profile_collect(jh_ctx* ctx, jh_profile_record* out, int max) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     int n = 0;
     for (auto& p : ctx->prof) {
-        if (p.kind != JH_PROF_QUERY) continue;
+        if (p.kind != JH_PROF_QUERY || p.stage < 0) continue;  // (the blit is a query of the tree, not a stage record)
         float ms = 0.0f;
         (void)hipEventElapsedTime(&ms, p.start, p.stop);
         if (out && n < max) {
@@ -1119,6 +1126,57 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     }
     prof_recycle(ctx);
     return n;
+}
+
+// ---- surface blit (RenderToSurface's blit pass, engine/wgpu_engine/lib.go:109-198, 266-333) ----
+int jh_blit_launch(hipStream_t stream, const void* src, void* dst, uint64_t pitch, uint32_t width, uint32_t row0, uint32_t row1, int format,
+                   int num_cus);
+
+int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t dst_pitch_bytes, uint32_t width, uint32_t height,
+            int surface_format) {
+    if (!ctx) return JH_ERR_INVALID;
+    // every check comes before anything is enqueued: a refused call touches no memory
+    auto it = ctx->images.find(src_image_id);
+    if (it == ctx->images.end()) return fail(ctx, JH_ERR_INVALID, "jh_blit: unknown source image id");
+    const Alloc& a = it->second;
+    if (a.format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_blit: the source is not an RGBA16F image");
+    if (a.width != width || a.height != height) return fail(ctx, JH_ERR_INVALID, "jh_blit: size differs from the source image");
+    if (!dst_device_ptr) return fail(ctx, JH_ERR_INVALID, "jh_blit: null destination");
+    if (dst_pitch_bytes < 4ull * width) return fail(ctx, JH_ERR_INVALID, "jh_blit: pitch below 4 * width");
+    if (surface_format < JH_SURFACE_RGBA8_UNORM || surface_format > JH_SURFACE_BGRA8_SRGB)
+        return fail(ctx, JH_ERR_INVALID, "jh_blit: unknown surface format");
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // band mode: the pixel rows of the active bin rows only (a bin row = 256 pixel rows), so that bands of several ranks compose
+    const uint64_t h = height;
+    const uint32_t row0 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row0 * 256u, h);
+    const uint32_t row1 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row1 * 256u, h);
+    ProfEntry pe;
+    if (ctx->profiling) {  // a query of its own (the reference's pgroup.Render(arena, "blit")), not a stage: stage = -1
+        auto get_event = [&](hipEvent_t* e) {
+            if (!ctx->free_events.empty()) { *e = ctx->free_events.back(); ctx->free_events.pop_back(); return hipSuccess; }
+            return hipEventCreate(e);
+        };
+        HIP_TRY(ctx, get_event(&pe.start));
+        HIP_TRY(ctx, get_event(&pe.stop));
+        pe.kind = JH_PROF_QUERY;
+        pe.parent = ctx->prof_stack.empty() ? -1 : ctx->prof_stack.back();
+        pe.stage = -1;
+        pe.label = "blit";
+        pe.cpu_start_ms = now_ms();
+        HIP_TRY(ctx, hipEventRecord(pe.start, ctx->stream));
+    }
+    // a source that was never written reads as transparent black, like a fresh texture
+    const int rc = jh_blit_launch(ctx->stream, (a.written || a.stored) ? a.ptr : nullptr, dst_device_ptr, dst_pitch_bytes, width, row0,
+                                  row1 > row0 ? row1 : row0, surface_format, ctx->num_cus);
+    if (ctx->profiling) {
+        HIP_TRY(ctx, hipEventRecord(pe.stop, ctx->stream));
+        pe.cpu_end_ms = now_ms();
+        ctx->prof.push_back(pe);
+    }
+    if (rc == -1) return fail(ctx, JH_ERR_INVALID, "jh_blit: image too large for one launch");
+    if (rc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_blit: launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return JH_OK;
 }
 
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);

@@ -4,6 +4,7 @@
 ``Engine``      = engine/hip_engine: replays a Recording on the MI355X through the C ABI.
 """
 import ctypes
+import enum
 
 import numpy as np
 
@@ -13,6 +14,18 @@ from ._lib import CConfig
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
                "flatten", "draw_reduce", "draw_leaf", "clip_reduce", "clip_leaf", "binning", "tile_alloc", "backdrop_dyn",
                "path_count_setup", "path_count", "coarse", "path_tiling_setup", "path_tiling", "fine_area", "fine_msaa8", "fine_msaa16"]
+
+
+class Surface(enum.IntEnum):
+    """jh_surface_format (include/jello_hip.h): RendererOptions.SurfaceFormat of the reference (lib.go:19-22)."""
+    RGBA8_UNORM = 0
+    BGRA8_UNORM = 1
+    RGBA8_SRGB = 2
+    BGRA8_SRGB = 3
+
+
+# a context buffer that blit / render_to_surface convert into when the caller passes no device pointer (it only grows)
+_SURFACE_BUFFER_ID = 0x5355524641434500
 
 
 class CMD:
@@ -154,12 +167,55 @@ class Engine:
         names = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]
         return Recording(self._L, h), dict(zip(names, bump)), attempts.value
 
-    def capture(self, recording, out_device_ptr=None):
+    def _surface(self, width, height, fmt, out_device_ptr, pitch):
+        """(device pointer, pitch) to convert into: the caller's, or the engine's own buffer (tightly packed rows)."""
+        if out_device_ptr is not None:
+            return out_device_ptr, (4 * width if pitch is None else pitch)
+        pitch = 4 * width
+        self._check(self.hip.jh_buffer_create(self.ctx, _SURFACE_BUFFER_ID, max(pitch * height, 16)), "buffer_create")
+        return self.hip.jh_buffer_device_ptr(self.ctx, _SURFACE_BUFFER_ID), pitch
+
+    def _download_surface(self, width, height):
+        out = np.empty((height, width, 4), dtype=np.uint8)
+        if out.nbytes:
+            self._check(self.hip.jh_download(self.ctx, _SURFACE_BUFFER_ID, out.ctypes.data, 0, out.nbytes), "download")
+        return out
+
+    def blit(self, src_image_id, width, height, fmt, out_device_ptr=None, pitch=None):
+        """The blit pass of RenderToSurface (jh_blit): the RGBA16F image `src_image_id` premultiplied and converted to the
+        Surface format `fmt`.  Into `out_device_ptr` (rows `pitch` bytes apart, default 4 * width; returns None) or, without
+        a pointer, returned as an (height, width, 4) uint8 array."""
+        ptr, pitch = self._surface(width, height, fmt, out_device_ptr, pitch)
+        self._check(self._L.jl_engine_blit(self._h, src_image_id, ptr, pitch, width, height, int(fmt)), "blit")
+        return None if out_device_ptr is not None else self._download_surface(width, height)
+
+    def render_to_surface(self, scene, params, fmt, out_device_ptr=None, pitch=None, robust=True):
+        """RenderToSurface (lib.go:266-333): RenderToTexture into the engine's own RGBA16F target, then the blit.
+        Returns (surface, Recording, bump dict, attempts); surface is an (H, W, 4) uint8 array without `out_device_ptr`,
+        None with it.  The Recording's target image is the engine's target until the next render_to_surface."""
+        ptr, pitch = self._surface(params.width, params.height, fmt, out_device_ptr, pitch)
+        p = params._c()
+        bump = (ctypes.c_uint32 * 8)()
+        attempts = ctypes.c_int()
+        h = self._L.jl_engine_render_to_surface(self._h, scene._h, ctypes.byref(p), ptr, pitch, int(fmt), 1 if robust else 0, bump,
+                                                ctypes.byref(attempts))
+        if not h:
+            raise RuntimeError("render_to_surface: " + self._L.jl_last_error().decode())
+        names = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]
+        surface = None if out_device_ptr is not None else self._download_surface(params.width, params.height)
+        return surface, Recording(self._L, h), dict(zip(names, bump)), attempts.value
+
+    def capture(self, recording, out_device_ptr=None, surface=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
-        The recording must have been run once (buffers + scratch exist)."""
+        The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
+        appends the blit of the frame's target into that surface (one more kernel launch)."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
+            if surface is not None:
+                ptr, pitch, fmt = surface
+                t = recording.target
+                self._check(self._L.jl_engine_blit(self._h, t["id"], ptr, pitch, t["width"], t["height"], int(fmt)), "blit")
         finally:
             g = ctypes.c_void_p()
             rc = self.hip.jh_graph_end(self.ctx, ctypes.byref(g))

@@ -381,4 +381,27 @@ void* jl_engine_render(void* e, void* scene, const jl_render_params* params, voi
     return h.release();
 }
 
+// RenderToSurface (lib.go:266-333): RenderToTexture into the engine's own RGBA16F target, then the blit into `surface`
+// (jh_surface_format `format`, `pitch` bytes per row).  Returns the final attempt's recording handle like jl_engine_render;
+// its target image is the engine's target until the next call.
+void* jl_engine_render_to_surface(void* e, void* scene, const jl_render_params* params, void* surface, uint64_t pitch, int format,
+                                  int robust, uint32_t* bump_out, int* attempts) {
+    Engine* eng = (Engine*)e;
+    std::unique_ptr<RecHandle> h(new RecHandle());
+    Engine::Frame f;
+    GUARD(f = eng->render_to_surface(((Scene*)scene)->encoding(), to_params(params), surface, pitch, format, robust != 0), nullptr);
+    h->result.recording = std::move(f.recording);
+    h->result.config = f.config;
+    h->result.out_image = ResourceProxy::of(f.target);
+    h->buffers = f.buffers;
+    if (bump_out) std::memcpy(bump_out, &f.bump, sizeof(JlBump));
+    if (attempts) *attempts = f.attempts;
+    flatten_recording(h.get());
+    return h.release();
+}
+int jl_engine_blit(void* e, uint64_t src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format) {
+    GUARD(((Engine*)e)->blit(src_image_id, surface, pitch, width, height, format), -1);
+    return 0;
+}
+
 }  // extern "C"

@@ -174,6 +174,32 @@ Engine::Frame Engine::render_to_texture(const Encoding& enc, RenderParams params
     return f;
 }
 
+Engine::Frame Engine::render_to_surface(const Encoding& enc, RenderParams params, void* surface, uint64_t pitch, int format, bool robust) {
+    // pgroup = pgroup.Nest("RenderToSurface"); defer pgroup.End()  (lib.go:274-275)
+    check(jh_profile_group_begin(ctx_, "RenderToSurface"), "profile_group_begin");
+    struct GroupEnd { jh_ctx* c; ~GroupEnd() { (void)jh_profile_group_end(c); } } group_end{ctx_};
+    SurfaceTarget& t = surface_target_;
+    if (t.image) {  // the previous frame's image over the target: an import, forgetting it frees nothing
+        check(jh_image_free(ctx_, t.image), "image_free");
+        t.image = 0;
+    }
+    if (t.buffer == 0 || t.width != params.width || t.height != params.height) {  // lib.go:279-284
+        if (t.buffer) check(jh_free(ctx_, t.buffer), "free");
+        t.buffer = next_resource_id();
+        t.width = params.width;
+        t.height = params.height;
+        check(jh_buffer_create(ctx_, t.buffer, (uint64_t)t.width * t.height * 8u), "buffer_create");
+    }
+    Frame f = render_to_texture(enc, params, jh_buffer_device_ptr(ctx_, t.buffer), robust, false);
+    t.image = f.target.id;
+    blit(f.target.id, surface, pitch, params.width, params.height, format);
+    return f;
+}
+
+void Engine::blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format) {
+    check(jh_blit(ctx_, src_image_id, surface, pitch, width, height, format), "blit");
+}
+
 void Engine::download_target(const Frame& f, void* dst, size_t bytes) { check(jh_image_download(ctx_, f.target.id, dst, bytes), "image_download"); }
 
 void Engine::release(const Frame& f) {

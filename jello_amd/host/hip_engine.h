@@ -62,6 +62,14 @@ class Engine {
     void download_target(const Frame& f, void* dst, size_t bytes);
     void release(const Frame& f);  // frees whatever a retain=true frame kept
 
+    // RenderToSurface (lib.go:266-333): render_to_texture into an engine-owned RGBA16F target -- kept while width and height
+    // stay the same (eng.target, lib.go:279-284) -- then jh_blit into `surface`: device memory of height rows of 4 * width
+    // bytes, `pitch` bytes apart, in the jh_surface_format `format`.  The frame's target image stays readable under
+    // Frame::target.id until the next render_to_surface.
+    Frame render_to_surface(const Encoding& enc, RenderParams params, void* surface, uint64_t pitch, int format, bool robust = true);
+    // The blit pass alone: the RGBA16F image src_image_id into a surface (jh_blit).
+    void blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format);
+
     Resolver& resolver() { return resolver_; }
     Renderer& renderer() { return renderer_; }
 
@@ -72,6 +80,8 @@ class Engine {
     Resolver resolver_;
     FullShaders shaders_;
     std::map<ResourceID, std::vector<uint8_t>> downloads_;
+    struct SurfaceTarget { ResourceID buffer = 0, image = 0; uint32_t width = 0, height = 0; };
+    SurfaceTarget surface_target_;  // render_to_surface's RGBA16F target (a context buffer) and the last frame's image over it
 
    public:
     const std::vector<uint8_t>* get_download(ResourceID id) const {
