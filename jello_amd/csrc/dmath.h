@@ -47,7 +47,7 @@ JD float mix_(float a, float b, float t) { return a * (1.0f - t) + b * t; }
 // both to the table of edge cases.  (Round 6: five instructions each as compare + select chains before; line_setup of path_count /
 // path_tiling and the multisampled fine kernel convert per line / per touched pixel.)
 JD uint32_t to_u32(float f) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(JD_NO_ASM_CVT)
+#if defined(__HIP_DEVICE_COMPILE__)
     uint32_t r;
     asm("v_cvt_u32_f32_e32 %0, %1" : "=v"(r) : "v"(f));
     return r;
@@ -58,7 +58,7 @@ JD uint32_t to_u32(float f) {
 #endif
 }
 JD int32_t to_i32(float f) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(JD_NO_ASM_CVT)
+#if defined(__HIP_DEVICE_COMPILE__)
     int32_t r;
     asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(r) : "v"(f));
     return r;

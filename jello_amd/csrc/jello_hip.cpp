@@ -299,11 +299,9 @@ int jh_create(jh_ctx** out, int device) {
     // (zeroed on the context's OWN stream: a hipMemset here would be the process's first use of the legacy default stream, and
     // from then on the frames of two contexts no longer overlapped at all -- bench.py's two frames in flight fell from 0.91 to
     // 1.05 ms per frame, found by bisection in round 5)
-#ifndef JH_NO_HINT_COUNTER
     if (hipMalloc((void**)&ctx->hint_overflow, 256) != hipSuccess || hipMemsetAsync(ctx->hint_overflow, 0, 256, ctx->own_stream) != hipSuccess ||
         hipStreamSynchronize(ctx->own_stream) != hipSuccess)
         ctx->hint_overflow = nullptr;
-#endif
     *out = ctx;
     return JH_OK;
 }
@@ -1257,7 +1255,7 @@ int jh_debug_clip_hint_overflows(jh_ctx* ctx, uint32_t* count, int reset) {
     }
     return JH_OK;
 }
-#if defined(FINE_TIMING) || defined(FINE_EB_STATS)
+#ifdef FINE_TIMING
 extern "C" int jh_debug_fine_timing(jh_ctx* ctx, unsigned long long* out6, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

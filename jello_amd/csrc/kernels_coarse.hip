@@ -35,15 +35,6 @@ struct Cmd {
     uint32_t chunk_base;   // word offset (relative to dyn_start) of this tile's first chunk
     uint32_t chunk_words;  // PTCL words of dynamic chunks taken so far
     uint32_t seg_base, seg_used;
-    // MODE 2 (one walk + relocation): `ptcl` is the scratch copy of the PTCL, chunks come from an arena in walk order
-    uint32_t* arena_ctr;            // words of the arena handed out so far
-    uint2* owner;                   // per arena chunk: (tile slot, ordinal of the chunk in its tile's stream)
-    unsigned long long* masks;      // per 64 words of the scratch PTCL: [0] seg_ix words of FILL commands, [1] JUMP target words
-    uint32_t* aux;                  // per 4 words (FILL commands are at least four words apart): the Tile of the FILL whose seg_ix lies there
-    uint32_t slot;
-    uint32_t* pool;                 // LDS, two words per wave: [next, end) of the wave's share of the arena.  (Not registers: the walk
-                                    // loop runs once per window of elements, a lane that left one early would come back with a stale copy --
-                                    // and, as the first active lane, hand out chunks a second time.)
 };
 
 // PTCL words leave as 16-byte stores (dword-aligned addresses: gfx950 runs in unaligned-access mode; a 4-byte store
@@ -63,6 +54,7 @@ JD void ptcl_wr4(const Buf<uint32_t>& ptcl, uint32_t i, uint32_t a, uint32_t b, 
 #endif
 // MODE 0: count only.  1: write at the canonical addresses (bases known).  2: write into the scratch PTCL, chunks from the
 // arena; what depends on the canonical allocation (chunk addresses, JUMP targets, seg_ix) is left tile-relative and marked.
+// MODE 2 walks with the lanes and takes its chunks itself (k_coarse): alloc_cmd serves the one-lane walk of MODE 0 and 1.
 template <int MODE>
 JD void alloc_cmd(Cmd& c, uint32_t size) {  // coarse.wgsl:70-88
     const bool need = c.cmd_offset + size >= c.cmd_limit;
@@ -75,50 +67,6 @@ JD void alloc_cmd(Cmd& c, uint32_t size) {  // coarse.wgsl:70-88
             }
             c.ptcl.wr(c.cmd_offset, JL_CMD_JUMP);
             c.ptcl.wr(c.cmd_offset + 1u, new_cmd);
-        }
-    }
-    if (MODE == 2) {
-        // Chunks come out of the WAVE's share of the arena, COARSE_POOL_CHUNKS at a time: a returning atomic in this loop waits for
-        // every PTCL store the wave has in flight (loads, stores and atomics share one in-order counter) -- with one atomic per
-        // chunk the walk took 803 us instead of 478 on C4.  The lanes that need a chunk in this trip take consecutive ones.
-        const uint64_t nm = __builtin_amdgcn_ballot_w64(need);
-        if (nm != 0ull) {  // uniform
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(nm) * JL_PTCL_INCREMENT;
-            uint32_t pn = (uint32_t)__builtin_amdgcn_readfirstlane((int)c.pool[0]), pe = (uint32_t)__builtin_amdgcn_readfirstlane((int)c.pool[1]);
-            if (pe - pn < cnt) {  // (what is left of the old share is given up: the arena has room for that, see jh_launch_coarse)
-                const uint32_t grab = umax_(cnt, COARSE_POOL_CHUNKS * JL_PTCL_INCREMENT);
-                uint32_t base = 0u;
-                if (lane_id() == (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) {  // the first lane still walking
-                    base = atomicAdd(c.arena_ctr, grab);
-                    // the chunks of the share that are not handed out right now have no owner yet -- and may never get one (the
-                    // tail of the wave's last share, a share given up early): the relocation must not take what an earlier frame
-                    // left in their records for one of its chunks
-                    for (uint32_t i = cnt; i < grab; i += JL_PTCL_INCREMENT)
-                        if (c.dyn_start + base + i + JL_PTCL_INCREMENT <= c.ptcl.n) c.owner[(base + i) / JL_PTCL_INCREMENT] = make_uint2(0xffffffffu, 0u);
-                }
-                pn = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                pe = pn + grab;
-            }
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(nm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)nm, 0u));
-            const uint32_t off = pn + rank * JL_PTCL_INCREMENT;
-            wave_sync();  // (every lane has read the pool)
-            if (lane_id() == (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(true))) { c.pool[0] = pn + cnt; c.pool[1] = pe; }
-            wave_sync();
-            if (need) {
-                new_cmd = c.dyn_start + off;
-                // (an arena that overflows: k_coarse_bases raises the flag -- the canonical PTCL may or may not have overflowed too)
-                if (new_cmd + JL_PTCL_INCREMENT > c.ptcl.n || new_cmd + JL_PTCL_INCREMENT < new_cmd) {
-                    new_cmd = 0u;
-                } else {
-                    c.owner[off / JL_PTCL_INCREMENT] = make_uint2(c.slot, c.chunk_words / JL_PTCL_INCREMENT);
-                    ulonglong2* m = (ulonglong2*)(c.masks + (size_t)(new_cmd >> 6) * 2u);
-#pragma unroll
-                    for (int i = 0; i < 4; i++) m[i] = make_ulonglong2(0ull, 0ull);  // the chunk's four 64-word blocks: nothing marked yet
-                }
-                c.ptcl.wr(c.cmd_offset, JL_CMD_JUMP);
-                c.ptcl.wr(c.cmd_offset + 1u, new_cmd);  // (provisional: the relocation writes the canonical address over it)
-                if (c.cmd_offset + 1u < c.ptcl.n) atomicOr(c.masks + (size_t)((c.cmd_offset + 1u) >> 6) * 2u + 1u, 1ull << ((c.cmd_offset + 1u) & 63u));
-            }
         }
     }
     c.chunk_words += need ? JL_PTCL_INCREMENT : 0u;
@@ -138,18 +86,11 @@ JD void alloc_cmd(Cmd& c, uint32_t size) {  // coarse.wgsl:70-88
 #ifndef COARSE_WG_PER_CU
 #define COARSE_WG_PER_CU 2u
 #endif
-#ifndef COARSE_RELOCATE
-#define COARSE_RELOCATE 1  // scenes with clip layers walk once and relocate (0: the two-pass route for every scene)
-#endif
 #ifndef COARSE_MAX_SPLIT
 #define COARSE_MAX_SPLIT 16u
 #endif
-// The one-walk route of scenes with clip layers walks a tile's elements with the LANES of a wave (round 6, see the walk below);
-// 0: one lane per tile, as the scenes without clips and rounds 1-5.
-#ifndef COARSE_PAR_WALK
-#define COARSE_PAR_WALK 1
-#endif
-// ... and splits the bins for this many workgroups per CU: every wave of a workgroup walks, so more workgroups are more walkers
+// The one-walk route of scenes with clip layers walks a tile's elements with the LANES of a wave (see the walk below) and splits
+// the bins for this many workgroups per CU: every wave of a workgroup walks, so more workgroups are more walkers
 // (C4 k_coarse<2>: 554 / 328 / 245 us with 1 / 2 / 4; nested C4 1061 / 616 / 423; the LDS of one allows four)
 #ifndef COARSE_PAR_WG_PER_CU
 #define COARSE_PAR_WG_PER_CU 4u
@@ -185,16 +126,17 @@ struct Walk {
     JlTile tile;
 };
 
-// CLIPS = false: instantiation for scenes without clip layers (ConfigUniform.n_clip == 0): no BEGIN/END_CLIP draw
-// objects can occur, which removes the clip-depth state and half of the divergent control flow of the command walk.
-struct CoarseReloc {  // MODE 2 only (see Cmd)
-    uint32_t* arena_ctr;
-    uint2* owner;
-    unsigned long long* masks;
-    uint32_t* aux;
-    uint32_t* end_pos;  // per tile slot: index of the stream's END word in the scratch PTCL
+// MODE 2 only (one walk + relocation): `ptcl` is the scratch copy of the PTCL, chunks come from an arena in walk order.
+struct CoarseReloc {
+    uint32_t* arena_ctr;        // words of the arena handed out so far
+    uint2* owner;               // per arena chunk: (tile slot, ordinal of the chunk in its tile's stream)
+    unsigned long long* masks;  // per 64 words of the scratch PTCL: [0] seg_ix words of FILL commands, [1] JUMP target words
+    uint32_t* aux;              // per 4 words (FILL commands are at least four words apart): the Tile of the FILL whose seg_ix lies there
+    uint32_t* end_pos;          // per tile slot: index of the stream's END word in the scratch PTCL
 };
 
+// CLIPS = false: instantiation for scenes without clip layers (ConfigUniform.n_clip == 0): no BEGIN/END_CLIP draw
+// objects can occur, which removes the clip-depth state and half of the divergent control flow of the command walk.
 template <int MODE, bool CLIPS>
 __global__ __launch_bounds__(JL_WG) void k_coarse(const JlConfig* __restrict__ cfg, Buf<uint32_t> scene, Buf<JlDrawMonoid> draw_monoids,
                                                   Buf<JlBinHeader> bin_headers, Buf<uint32_t> info_bin_data, Buf<JlPath> paths, Buf<JlTile> tiles,
@@ -229,14 +171,14 @@ __global__ __launch_bounds__(JL_WG) void k_coarse(const JlConfig* __restrict__ c
     // (backdrop, segment count) of the (draw, tile) pairs of the current window of elements.  The command walk reads Tiles
     // from here ONLY: a global load inside its loop makes every trip wait for the PTCL stores of the trip before
     // (vmcnt counts loads and stores in one order) -- 1 us per trip in the write pass.
-    constexpr bool PAR = MODE == 2 && CLIPS && COARSE_PAR_WALK != 0;  // lanes = the elements of ONE tile (see the walk)
+    constexpr bool PAR = MODE == 2;  // lanes = the elements of ONE tile (see the walk; MODE 2 serves scenes with clip layers only)
     __shared__ uint2 sh_tile_cache[PAR ? 1u : COARSE_TILE_CACHE];
     // PAR: the walk state of the workgroup's tiles (write position and limit, chunk words, segments, clip state: Walk / Cmd below) and,
     // per wave, two lists of the elements that include the tile it works on / the one it prepares
     __shared__ uint32_t sh_st[8][PAR ? JL_N_TILE : 1u];
     __shared__ uint8_t sh_list[JL_WG / 64][2][PAR ? JL_N_TILE : 1u];
-    __shared__ uint32_t sh_pool[JL_WG / 64][2];  // MODE 2: the waves' shares of the chunk arena (alloc_cmd)
-    if (MODE == 2 && threadIdx.x < JL_WG / 64) { sh_pool[threadIdx.x][0] = 0u; sh_pool[threadIdx.x][1] = 0u; }  // (barriers follow before any walk)
+    __shared__ uint32_t sh_pool[JL_WG / 64][2];  // PAR: the waves' shares of the chunk arena, [next, end)
+    if (PAR && threadIdx.x < JL_WG / 64) { sh_pool[threadIdx.x][0] = 0u; sh_pool[threadIdx.x][1] = 0u; }  // (barriers follow before any walk)
 
     const uint32_t lid = threadIdx.x;
     const uint32_t width_in_bins = (cfg->width_in_tiles + JL_N_TILE_X - 1u) / JL_N_TILE_X;
@@ -323,8 +265,6 @@ __global__ __launch_bounds__(JL_WG) void k_coarse(const JlConfig* __restrict__ c
         w.c.chunk_words = 0u;
         w.c.seg_base = my_base_seg;
         w.c.seg_used = 0u;
-        w.c.arena_ctr = R.arena_ctr; w.c.owner = R.owner; w.c.masks = R.masks; w.c.aux = R.aux; w.c.slot = w.slot;
-        w.c.pool = &sh_pool[lid >> 6][0];
         // (only a tile of the target owns its head: the index of one beyond the right edge is another tile's)
         if (MODE == 2 && w.has_tile && bin_tile_x + w.tile_x < cfg->width_in_tiles && bin_tile_y + w.tile_y < cfg->height_in_tiles &&
             (size_t)this_tile_ix * JL_PTCL_INITIAL_ALLOC + JL_PTCL_INITIAL_ALLOC <= ptcl.n) {  // the head's 64-word block: nothing marked yet
@@ -673,7 +613,8 @@ __global__ __launch_bounds__(JL_WG) void k_coarse(const JlConfig* __restrict__ c
                         const uint32_t l1 = m1 != 0ull ? (uint32_t)__builtin_ctzll(m1) : 64u, l2 = m2 != 0ull ? (uint32_t)__builtin_ctzll(m2) : 64u;
                         const uint32_t bl = l1 <= l2 ? l1 : l2, bslot = l1 <= l2 ? 0u : 1u;
                         const uint32_t bo = (uint32_t)__builtin_amdgcn_readlane((int)(bslot == 0u ? o1 : o2), (int)bl);
-                        // a chunk from the wave's share of the arena (alloc_cmd<2>, one chunk at a time)
+                        // a chunk from the wave's share of the arena, taken COARSE_POOL_CHUNKS at a time: a returning atomic waits for
+                        // every PTCL store the wave has in flight
                         uint32_t pn = uni(sh_pool[wv][0]), pe = uni(sh_pool[wv][1]);
                         if (pe - pn < JL_PTCL_INCREMENT) {
                             const uint32_t grab = COARSE_POOL_CHUNKS * JL_PTCL_INCREMENT;
@@ -827,13 +768,7 @@ __global__ __launch_bounds__(JL_WG) void k_coarse(const JlConfig* __restrict__ c
                     const uint32_t rule = (n_segs << 1) | ((meta / CM_EVENODD_FILL) & 1u);
                     if (s1 == 4u) {
                         const uint32_t tile_ix = q0.z + q0.w * w.tile_y + w.tile_x;
-                        if (MODE == 1) {
-                            if (tiles.ok(tile_ix)) tiles.p[tile_ix].segment_count_or_ix = ~seg_ix;
-                        } else if (c.cmd_offset + 2u < c.ptcl.n) {  // seg_ix is tile-relative here: marked, the relocation adds the tile's base and writes the Tile
-                            const uint32_t at = c.cmd_offset + 2u;
-                            atomicOr(c.masks + (size_t)(at >> 6) * 2u, 1ull << (at & 63u));
-                            c.aux[at >> 2] = tile_ix;
-                        }
+                        if (tiles.ok(tile_ix)) tiles.p[tile_ix].segment_count_or_ix = ~seg_ix;
                     }
                     if (s1 != 0u) {
                         PtclQuad q; q.a = has_segs ? JL_CMD_FILL : JL_CMD_SOLID; q.b = rule; q.c = seg_ix; q.d = (uint32_t)tile.backdrop;
@@ -1107,9 +1042,9 @@ int jh_launch_coarse(const JhLaunch& L) {
     auto tiles = mkbuf<JlTile>(L.b[6].ptr, L.b[6].size);
     JlBump* bump = (JlBump*)L.b[7].ptr;
     auto ptcl = mkbuf<uint32_t>(L.b[8].ptr, L.b[8].size);
+    const bool clips = !(L.cfg_host && L.cfg_host->layout.n_clip == 0u);  // host shadow of the uploaded ConfigUniform
     // workgroups per bin: enough to give every CU COARSE_WG_PER_CU workgroups (the LDS of one allows four per CU)
-    const bool clips_early = !(L.cfg_host && L.cfg_host->layout.n_clip == 0u);
-    const uint32_t want = (clips_early && COARSE_RELOCATE && COARSE_PAR_WALK ? COARSE_PAR_WG_PER_CU : COARSE_WG_PER_CU) * (uint32_t)(L.num_cus > 0 ? L.num_cus : 256);
+    const uint32_t want = (clips ? COARSE_PAR_WG_PER_CU : COARSE_WG_PER_CU) * (uint32_t)(L.num_cus > 0 ? L.num_cus : 256);
     uint32_t split = 1u;
     while (split < COARSE_MAX_SPLIT && L.gx * L.gy * split < want) split *= 2u;
     const uint32_t n_wg = L.gx * L.gy * split;
@@ -1119,17 +1054,15 @@ int jh_launch_coarse(const JhLaunch& L) {
     dim3 grid(L.gx, L.gy, split), blk(JL_WG);
     const uint32_t row0 = L.band_row0 < L.gy ? L.band_row0 : L.gy, row1 = L.band_row1 < L.gy ? L.band_row1 : L.gy;
     dim3 grid_w(L.gx, row1 > row0 ? row1 - row0 : 0u, split);
-    const bool clips = !(L.cfg_host && L.cfg_host->layout.n_clip == 0u);  // host shadow of the uploaded ConfigUniform
     CoarseReloc R;
     std::memset(&R, 0, sizeof R);
 #define JH_COARSE(W, C, G, ROW0, P) hipLaunchKernelGGL((k_coarse<W, C>), G, blk, 0, L.stream, cfg, scene, dm, bh, ibd, paths, tiles, bump, P, cnt_seg, cnt_chunk, cnt_blend, wg_tot, n_wg, ROW0, split, R)
-#if COARSE_RELOCATE
     // Scenes with clip layers: ONE walk into a scratch copy of the PTCL, then the relocation (the walk of such a scene is long --
     // C4: ~640 trips per tile -- and the counting pass repeated all of it; for a scene without clips the relocation's traffic
     // eats what it saves).
-    if ((clips || COARSE_RELOCATE == 2) && ptcl.n != 0u) {
-        // the scratch PTCL: the real one's size + what the waves' arena shares can leave unused (a share given up early, the tail of
-        // the last one): 2 x COARSE_POOL_CHUNKS chunks per walking wave
+    if (clips && ptcl.n != 0u) {
+        // the scratch PTCL: the real one's size + what the waves' arena shares can leave unused: 2 x COARSE_POOL_CHUNKS chunks per
+        // walking wave, kept conservatively for the lane walk, whose only loss is the tail of its last share
         const uint64_t slack = (uint64_t)n_wg * 4u * 2u * COARSE_POOL_CHUNKS * JL_PTCL_INCREMENT;
         const uint64_t words = (uint64_t)ptcl.n + slack > 0xfffffff0ull ? 0xfffffff0ull : (uint64_t)ptcl.n + slack;
         uint32_t* tmp = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_B, words * 4);
@@ -1150,7 +1083,7 @@ int jh_launch_coarse(const JhLaunch& L) {
         const uint64_t cfg_dyn = L.cfg_host ? (uint64_t)L.cfg_host->width_in_tiles * L.cfg_host->height_in_tiles * JL_PTCL_INITIAL_ALLOC : 0u;
         // (owner records of chunks no tile took this frame must not look like one of the band's: slot ~0)
         auto tmpbuf = mkbuf<uint32_t>(tmp, words * 4);
-        if (clips) JH_COARSE(2, true, grid, 0u, tmpbuf); else JH_COARSE(2, false, grid, 0u, tmpbuf);
+        JH_COARSE(2, true, grid, 0u, tmpbuf);
         hipLaunchKernelGGL(k_coarse_bases, dim3(n_wg), blk, 0, L.stream, cfg, bump, (const uint32_t*)cnt_seg, (const uint32_t*)cnt_chunk, (const uint32_t*)cnt_blend,
                            (const uint32_t*)wg_tot, n_wg, split, base_seg, base_chunk, base_blend, R.arena_ctr, arena_used,
                            (uint32_t)(words > (uint64_t)cfg_dyn ? words - cfg_dyn : 0u));
@@ -1162,7 +1095,6 @@ int jh_launch_coarse(const JhLaunch& L) {
         }
         return 0;
     }
-#endif
     if (clips) JH_COARSE(0, true, grid, 0u, ptcl); else JH_COARSE(0, false, grid, 0u, ptcl);
     if (grid_w.y == 0u) {  // an empty band: nobody to report the totals (otherwise the write pass's first workgroup does)
         hipLaunchKernelGGL(k_coarse_totals, dim3(1), blk, 0, L.stream, (const uint32_t*)wg_tot, n_wg, bump);

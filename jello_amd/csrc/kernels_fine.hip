@@ -37,10 +37,6 @@ using namespace jd;
 
 namespace {
 
-#ifndef FINE_BLEND_UNIFORM_DISPATCH
-#define FINE_BLEND_UNIFORM_DISPATCH 1
-#endif
-
 struct V4 {
     float x, y, z, w;
 };
@@ -148,13 +144,11 @@ JD V4 blend_compose(V3 cb, V3 cs, float ab, float as_, uint32_t mode) {  // blen
 // formula is the rare case.
 __device__ __attribute__((noinline)) V4 blend_mix_compose(V4 backdrop, V4 src, uint32_t mode) {  // blend.wgsl:288-310
     const float EPSILON = 1e-15f;
-#if FINE_BLEND_UNIFORM_DISPATCH
     // `mode` is a PTCL word: the same in every lane.  As a function argument it arrives in a vector register, and the two switches
     // below became trees of v_cmp / s_and_saveexec / s_cbranch_execz -- ~25 vector + scalar instructions per call in front of the
     // arithmetic (round 6: nested C4 spends 55 % of its fine kernel in here, 85 calls x 4 pixels per tile).  As a scalar the switches
     // are compare-and-branch on the scalar pipe.
     mode = (uint32_t)__builtin_amdgcn_readfirstlane((int)mode);
-#endif
     if ((mode & 0x7fffu) == 0u) {
         float k = 1.0f - src.w;
         return v4(backdrop.x * k + src.x, backdrop.y * k + src.y, backdrop.z * k + src.z, backdrop.w * k + src.w);
@@ -262,21 +256,6 @@ JD V4 over(V4 bg, V4 fg, float area) {
 #define FINE_WAVES 1  // tile-waves per workgroup (round 3, C3: 0.405 ms with 1, 0.421 with 2, 0.428 with 4)
 #endif
 #define FB_PLANE 65
-#ifndef FINE_FINAL_ASM
-#define FINE_FINAL_ASM 1  // (C3 fine 351.3 -> 347.0 us on the same box)
-#endif
-#ifndef FINE_COLOR_BPERM
-#define FINE_COLOR_BPERM 1  // (C3 fine 346.0 -> 340.7 / 346.9 -> 343.5 us on one box, two rounds)
-#endif
-#ifndef FINE_LAYER_FILL
-#define FINE_LAYER_FILL 1
-#endif
-#ifndef FINE_VECTOR_LAYERS
-#define FINE_VECTOR_LAYERS 1  // (0: the scalar counting loop of round 4)
-#endif
-#ifndef FINE_CROSS_INLANE
-#define FINE_CROSS_INLANE 1  // (0: every crossing pixel through the lane = crossing pixel passes, as up to round 4: C3 fine 362.6 -> 354.5 us with 1)
-#endif
 // FINE_SKIP (differential builds, `make VARIANT=... EXTRA=-DFINE_SKIP=n`; results are WRONG, only counters and times of
 // such a library are of interest -- tools/fine_split.sh): 1 no crossing-pixel formula (stage 3), 2 no row walk / y_edge
 // terms (stage 4), 3 no pair evaluation (stages 2 + 3), 4 no batches at all, 5 no compositing of solid colours,
@@ -286,27 +265,10 @@ JD V4 over(V4 bg, V4 fg, float area) {
 // own `area += a * dy`), finalisation, composite, store -- and none of what moves it between lanes (pair -> segment mapping,
 // row sort, entries, marks, owner scan, row walk).  What stage 1 and the classification cost is in it: without them the
 // number of pairs and crossing pixels is not known.
-// 7 (round 6, timing only) stage 4 TRANSPOSED: a lane = (fill slot, pixel row) of the batch -- four slots of equal shares of the batch's
-// segments stand in for its fills, the real row masks give the trip counts -- walks its row's entries of its slot with all sixteen
-// pixels in registers (four 16-byte reads and eight packed adds per entry), the areas go back through the entry planes, and a FILL
-// reads its four with one 16-byte load: what VERDICT r05 asked to be measured instead of estimated.
 #ifndef FINE_SKIP
 #define FINE_SKIP 0
 #endif
-// FINE_WHATIF (timing-only variant builds, results WRONG; round 6: what do the LDS bank conflicts cost?): bit 0 the row walk reads
-// its entries at conflict-free linear addresses (same trips, same instructions), bit 1 stage 2 writes its entries at [quad][lane]
-// instead of [quad][row-sorted position], bit 2 the crossing pixels' single floats go to [quad][lane] as well.
-#ifndef FINE_WHATIF
-#define FINE_WHATIF 0
-#endif
-#if FINE_WHATIF & 1
-#define FINE_WALK_RD "%[rd]"
-#define FINE_WALK_RD_OPERAND , [rd] "v"(lds_addr(&F.ent[0][0]) + lane * 16u)
-#else
-#define FINE_WALK_RD "%[cur]"
-#define FINE_WALK_RD_OPERAND
-#endif
-#if (FINE_SKIP != 0 || FINE_WHATIF != 0) && !defined(JH_VARIANT_BUILD)
+#if FINE_SKIP != 0 && !defined(JH_VARIANT_BUILD)
 #error "FINE_SKIP changes results: build it as a variant library (make VARIANT=name EXTRA='-DJH_VARIANT_BUILD -DFINE_SKIP=n')"
 #endif
 #define RK_NONEG 1u
@@ -398,14 +360,6 @@ JD void load_segraw_clamped(const float* __restrict__ segments, uint32_t segment
 // (their index is formed with the WGSL's own u32 arithmetic first), segments behind the buffer read as zeros -- and a zero
 // segment touches the tile corner: it does count.
 // ------------------------------------------------------------------------------------------------
-// FINE_MS_SKIP (timing-only variant builds, results WRONG): bit 0 no entries are applied at the fills, bit 1 no resolve arithmetic,
-// bit 2 no touched-pixel passes in the batch build, bit 3 no clearing of the accumulators
-#ifndef FINE_MS_SKIP
-#define FINE_MS_SKIP 0
-#endif
-#if FINE_MS_SKIP != 0 && !defined(JH_VARIANT_BUILD)
-#error "FINE_MS_SKIP changes results: build it as a variant library"
-#endif
 // Touched pixels per batch (a sane segment has at most 31; one with more is walked at the fill: MsState::direct).  192 with 8
 // samples: 4 944 bytes of LDS per tile-wave then -- LDS is handed out in blocks of 1 280 bytes on this part (two what-if sweeps found
 // the steps, profiles/r06_fine_lds_sweep.txt / r06_fine_clip_lds.txt), so 5 120 is the line between 25 and 32 tile-waves per CU.
@@ -633,7 +587,7 @@ JD void ms_build(MsLds<SAMPLES>& T, MsState& B, uint32_t lane, uint32_t so, cons
 #pragma unroll
     for (uint32_t p = 0u; p < PASSES; p++) {
         word[p] = 0u;
-        if (p * 64u < B.total && !(FINE_MS_SKIP & 4)) {  // uniform
+        if (p * 64u < B.total) {  // uniform
             T.mark[lane] = 0u;
             wave_sync();
             if (starts && first - p * 64u < 64u) T.mark[first - p * 64u] = lane + 1u;
@@ -685,7 +639,7 @@ JD void ms_fill(MsLds<SAMPLES>& T, MsState& B, uint32_t lane, uint32_t size_and_
     {
         const uint4 z4 = make_uint4(cleared, cleared, cleared, cleared);
         uint4* s = (uint4*)&T.samples[0];
-        if (B.clean != (even_odd ? 1u : 0u) && !(FINE_MS_SKIP & 8)) {  // uniform
+        if (B.clean != (even_odd ? 1u : 0u)) {  // uniform
             if (even_odd) s[lane] = z4;
             else {
 #pragma unroll
@@ -732,7 +686,7 @@ JD void ms_fill(MsLds<SAMPLES>& T, MsState& B, uint32_t lane, uint32_t size_and_
         } else {
             const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)B.first, (int)(r0 & 63u));
             const uint32_t e1 = r0 + take >= 64u ? B.total : (uint32_t)__builtin_amdgcn_readlane((int)B.first, (int)((r0 + take) & 63u));
-            for (uint32_t eb = e0; eb < e1 && !(FINE_MS_SKIP & 1); eb += 64u)  // uniform
+            for (uint32_t eb = e0; eb < e1; eb += 64u)  // uniform
                 if (eb + lane < e1) ms_apply<SAMPLES>(T, T.ent[eb + lane], even_odd);
             piece_e0 = e0; piece_e1 = e1;
         }
@@ -809,9 +763,7 @@ JD void ms_fill(MsLds<SAMPLES>& T, MsState& B, uint32_t lane, uint32_t size_and_
     for (uint32_t i = 0u; i < 4u; i++) {
         // the winding number every sample of the pixel starts from; a sample is covered when its counter differs from "zero"
         const uint32_t zero = (((wx >> (i * 8u)) + wy) & 0xffu) - (uint32_t)backdrop;
-        if (FINE_MS_SKIP & 2) {
-            area[i] = u2f((sw[i * WORDS] & 0x7fffffu) | 0x3f000000u);
-        } else if (zero >= 256u) {
+        if (zero >= 256u) {
             area[i] = 1.0f;
         } else if (SAMPLES == 8) {
             const uint32_t d0 = (zero * 0x1010101u) ^ sw[i * 2u], d1 = (zero * 0x1010101u) ^ sw[i * 2u + 1u];
@@ -869,8 +821,7 @@ template <> struct FineStackSel<false> { struct type { float4 lvl[1][1][1]; }; }
 
 // Pixel ownership = the WGSL's: lane = ly*4 + lx (workgroup (4,16)), pixel i = 0..3 at column 4*lx + i.
 // AA = 0: analytic area coverage (fine_area); 8 / 16: fine_msaa8 / fine_msaa16.
-// Tile-waves per workgroup: two where LDS is small (the CU runs at most 16 workgroups, so single-wave workgroups would cap
-// the occupancy at 4 waves per SIMD); one for the clip instantiations (a history note of round 2: their LDS is 10 KB per wave now).
+// Tile-waves per workgroup: one (FINE_WAVES, see there; always one for the clip instantiations).
 #define FINE_WG_WAVES(CLIPS) ((CLIPS) ? 1 : FINE_WAVES)
 #ifndef FINE_LEAN_MS_WAVES_PER_EU
 #define FINE_LEAN_MS_WAVES_PER_EU 7  // (C3 msaa8: 580 / 522 / 490 us at 4 / 5 / 6 waves per SIMD; 7 -- 72 registers, four spilled -- once the LDS allows 28 tile-waves: 440 -> 429)
@@ -888,8 +839,7 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                                                   uint32_t scr_levels,                 // levels per tile in clip_scratch (0 ... FINE_SCR_LEVELS, from the scene's clip depth)
                                                   uint32_t* __restrict__ hint_overflow) {  // counts the saves dropped for want of a level (a clip-depth hint that was too small)
     const uint32_t tile_y = blockIdx.y + tile_row0;
-    // FINE_WAVES independent waves (= tiles, side by side in x) per workgroup: the CU runs at most 16 workgroups, so
-    // single-wave workgroups would cap the occupancy at 4 waves per SIMD.  The waves never synchronise with each other.
+    // FINE_WG_WAVES independent waves (= tiles, side by side in x) per workgroup.  The waves never synchronise with each other.
     constexpr uint32_t WV = FINE_WG_WAVES(CLIPS);
     __shared__ typename FineLdsSel<AA, CLIPS>::type F_all[WV];
     __shared__ typename FineStackSel<CLIPS>::type S_all[WV];
@@ -1112,10 +1062,9 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
 #pragma unroll
             for (int q = 0; q < 16; q++) cv[q] = clamp_((float)(q + 1) - c1f, 0.0f, 1.0f) * s2_dy;
 #pragma unroll
-            for (int q = 0; q < 4; q++) F.ent[q][(FINE_WHATIF & 2) ? lane : pos] = make_float4(cv[4 * q], cv[4 * q + 1], cv[4 * q + 2], cv[4 * q + 3]);
+            for (int q = 0; q < 4; q++) F.ent[q][pos] = make_float4(cv[4 * q], cv[4 * q + 1], cv[4 * q + 2], cv[4 * q + 3]);
         }
-#if FINE_CROSS_INLANE
-        // The pair's own lane evaluates its FIRST crossing pixel (round 5): all operands are in its registers, so the pixel
+        // The pair's own lane evaluates its FIRST crossing pixel: all operands are in its registers, so the pixel
         // costs the formula and one store -- not a mark, a share of the owner scan and five lane shuffles.  Only the
         // pixels behind it (0.8 per pair on C3 instead of 1.8) go through the lane = crossing pixel passes below.
         if (ncross != 0u) {
@@ -1130,14 +1079,10 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
             float c = fmax_(b, 0.0f);
             float d = fmax_(xmin, 0.0f);
             float a = (b + 0.5f * (d * d - c * c) - xmin) / (xmax - xmin);
-            ((float*)&F.ent[X >> 2][(FINE_WHATIF & 4) ? lane : pos])[X & 3u] = a * s2_dy;
+            ((float*)&F.ent[X >> 2][pos])[X & 3u] = a * s2_dy;
         }
         const uint32_t nrest = ncross != 0u ? ncross - 1u : 0u;
         const int32_t n0r = n0 + 1;
-#else
-        const uint32_t nrest = ncross;
-        const int32_t n0r = n0;
-#endif
         const uint32_t sincl = wave_incl_scan_u32(nrest);
         const uint32_t spos = sincl - nrest;
         const uint32_t nspec = (FINE_SKIP == 1 || FINE_SKIP == 3) ? 0u : (uint32_t)__builtin_amdgcn_readlane((int)sincl, 63);
@@ -1178,49 +1123,11 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                     float c = fmax_(b, 0.0f);
                     float d = fmax_(xmin, 0.0f);
                     float a = (b + 0.5f * (d * d - c * c) - xmin) / (xmax - xmin);
-                    ((float*)&F.ent[(FINE_WHATIF & 4) ? (lane >> 4) : (X >> 2)][(FINE_WHATIF & 4) ? lane : epos])[(FINE_WHATIF & 4) ? (lane & 3u) : (X & 3u)] = a * dy;
+                    ((float*)&F.ent[X >> 2][epos])[X & 3u] = a * dy;
                 }
             }
         }
         wave_sync();
-#if FINE_SKIP == 7
-        {
-            const uint32_t f = lane >> 4, r = lane & 15u;
-            const uint32_t per = (e_rel + 3u) / 4u;
-            const uint32_t s_lo = umin_(f * per, e_rel), s_hi = umin_(s_lo + per, e_rel);
-            const uint32_t firstv = lane < e_rel ? first : n_pairs;
-            const uint32_t p_lo = __shfl(firstv, (int)(s_lo & 63u), 64), p_hi = s_hi < 64u ? __shfl(firstv, (int)(s_hi & 63u), 64) : n_pairs;
-            const uint64_t rm = F.rowmask[r];
-            auto below = [](uint32_t P) -> uint64_t { return (1ull << (P & 63u)) - 1ull; };
-            const uint32_t before = (uint32_t)__builtin_popcountll(rm & below(p_lo));
-            const uint32_t cnt = (uint32_t)__builtin_popcountll(rm & below(p_hi)) - before;
-            uint32_t addr = lds_addr(&F.ent[0][0]) + (__shfl(excl16, (int)r, 64) + before) * 16u;
-            jk_v2f a[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) a[q] = {lyf, lyf};
-            for (uint32_t trip = 0u; __builtin_amdgcn_ballot_w64(trip < cnt) != 0ull; trip++) {
-                if (trip < cnt) {
-#pragma unroll
-                    for (uint32_t q = 0u; q < 4u; q++) {
-                        const float4 v = lds_ld_f4(addr + q * (uint32_t)sizeof(F.ent[0]));
-                        a[2 * q] += jk_v2f{v.x, v.y}; a[2 * q + 1] += jk_v2f{v.z, v.w};
-                    }
-                    addr += 16u;
-                }
-            }
-            {   // one y_edge term per lane stands in for the slot's edge segments
-                float2 ed;
-                if constexpr (CLIPS) ed = make_float2(F.edge_y[s_lo & 63u], 1.0f); else ed = F.edge[s_lo & 63u];
-                const float ye = ed.y * clamp_((float)r - ed.x + 1.0f, 0.0f, 1.0f);
-#pragma unroll
-                for (int q = 0; q < 8; q++) a[q] += jk_v2f{ye, ye};
-            }
-            wave_sync();
-#pragma unroll
-            for (uint32_t q = 0u; q < 4u; q++) F.ent[q][lane] = make_float4(a[2 * q].x, a[2 * q].y, a[2 * q + 1].x, a[2 * q + 1].y);
-            wave_sync();
-        }
-#endif
       } else {
         (void)so;
       }
@@ -1384,13 +1291,7 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                 area[0] = a01.x; area[1] = a01.y; area[2] = a23.x; area[3] = a23.y;
             }
 #endif
-#if FINE_SKIP == 7
-            {
-                const float4 v = lds_ld_f4(lds_addr(&F.ent[lx][((r0 & 3u) * 16u + ly) & 63u]));
-                area[0] += v.x; area[1] += v.y; area[2] += v.z; area[3] += v.w;
-            }
-#endif
-            for (; FINE_SKIP != 2 && FINE_SKIP != 4 && FINE_SKIP != 6 && FINE_SKIP != 7;) {  // uniform
+            for (; FINE_SKIP != 2 && FINE_SKIP != 4 && FINE_SKIP != 6;) {  // uniform
                 const uint32_t e_sl = em != 0ull ? (uint32_t)__builtin_ctzll(em) : 0u;
                 const uint32_t seg_end = em != 0ull ? e_sl + 1u : r0 + take;  // the run covers window segments < seg_end
                 done = (uint32_t)__builtin_popcountll(my_rowmask & below(first_of(seg_end)));
@@ -1408,12 +1309,12 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                         "1:\n"
                         "v_cmpx_lt_u32_e32 vcc, %[cur], %[hi]\n"
                         "s_cbranch_execz 3f\n"
-                        "ds_read_b128 v[64:67], " FINE_WALK_RD "\n"
+                        "ds_read_b128 v[64:67], %[cur]\n"
                         "v_add_u32_e32 %[t], 16, %[cur]\n"
                         "v_cmp_lt_u32_e32 vcc, %[t], %[hi]\n"
                         "s_mov_b64 %[s1], exec\n"
                         "s_and_b64 exec, exec, vcc\n"
-                        "ds_read_b128 v[68:71], " FINE_WALK_RD " offset:16\n"
+                        "ds_read_b128 v[68:71], %[cur] offset:16\n"
                         "s_mov_b64 exec, %[s1]\n"
                         "v_add_u32_e32 %[cur], 32, %[cur]\n"
                         "s_waitcnt lgkmcnt(1)\n"
@@ -1428,7 +1329,7 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                         "3:\n"
                         "s_mov_b64 exec, %[sv]\n"
                         : [cur] "+v"(cur), [a01] "+v"(a01), [a23] "+v"(a23), [sv] "=&s"(sv), [s1] "=&s"(s1), [t] "=&v"(t)
-                        : [hi] "v"(hi) FINE_WALK_RD_OPERAND
+                        : [hi] "v"(hi)
                         : "vcc", "memory", "v64", "v65", "v66", "v67", "v68", "v69", "v70", "v71");
                     area[0] = a01.x; area[1] = a01.y; area[2] = a23.x; area[3] = a23.y;
                 }
@@ -1456,7 +1357,7 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
         } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-#if FINE_FINAL_ASM && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
                 // min(|a|, 1) as ONE instruction: the compiler puts a canonicalising v_max |a|, |a| in front of its v_min because the sum
                 // comes out of inline assembly (it cannot know that an addition's result is never a signalling NaN).
                 asm("v_min_f32_e64 %0, |%1|, 1.0" : "=v"(area[k]) : "v"(area[k]));
@@ -1494,14 +1395,10 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
             // (as an arm of the general decoder below the pair carried that decoder's flag variables, state copies and branch chain).
             for (uint32_t hot = 0; hot < (1u << 24) && tag == JL_CMD_FILL && W(4) == JL_CMD_COLOR; hot++) {  // uniform
                 do_fill(W(1), W(2), (int32_t)W(3));
-#if FINE_COLOR_BPERM
                 // (the colour through the LDS crossbar into vector registers instead of four v_readlane with a scalar lane select, 8 cycles
                 // of the vector pipe each: the kernel is bound by vector issue, the LDS pipe is a third busy)
                 auto WB = [&](uint32_t k) -> float { return u2f((uint32_t)__builtin_amdgcn_ds_bpermute((int)((woff + k) << 2), (int)wcur)); };
                 const V4 fgc = v4(WB(5), WB(6), WB(7), WB(8));
-#else
-                const V4 fgc = v4(u2f(W(5)), u2f(W(6)), u2f(W(7)), u2f(W(8)));
-#endif
                 pc += 9u;
                 materialize();
 #pragma unroll
@@ -1519,15 +1416,14 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
             // far accounted for (exactly what its own folding of BEGIN_CLIP / SOLID does).
             // Inside the loop nothing but the plain arm's `+ 0.0` touches rgba and nothing but SOLID touches the area, so what one
             // layer's tests established holds for the layers behind it: once the area is 1 and the backdrop's tests have passed, the
-            // commands of an empty layer need NOTHING but counting -- the scalar loop at the head of every trip.  (Round 4.  The C4
-            // tile is bound by the CU's one scalar pipe: 118 scalar instructions per empty layer before, the compiler's boolean
-            // bookkeeping around the decoder; the counting loop is one compare-and-branch per condition.)
+            // commands of an empty layer need NOTHING but counting -- the loop at the head of every trip.  (The C4 tile is bound by
+            // the CU's one scalar pipe: through the decoder an empty layer cost 118 scalar instructions, the compiler's boolean
+            // bookkeeping around it.)
             uint32_t rgba_known = 0u;  // (of this run of empty layers: see end_clip_fast)
             bool area_one = false;
             for (uint32_t hot = 0; hot < (1u << 24); hot++) {  // uniform
                 if (area_one) {
-                    // The counting loop, by hand: one compare-and-branch per condition, ~47 scalar instructions per BEGIN_CLIP SOLID END_CLIP
-                    // (as C++ the structuriser turned the chain of exits into state codes and mask bookkeeping, no better than before).
+                    // The counting loop:
                     //   BEGIN_CLIP: depth + 1.   SOLID: nothing (the area is 1).   END_CLIP blend alpha: closes an EMPTY layer (one that
                     //   was never materialised: pushed_depth < depth) if 0 <= alpha < inf (bit pattern), the compose operator is src-over
                     //   and what end_clip_fast would test for the mix mode -- plain / clip: RK_NONEG, modes 1..11: + RK_RANGE, hue /
@@ -1535,9 +1431,8 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                     //   in the register window: out (the window is re-based and the loop entered again, or the trip below takes over).
                     for (uint32_t sk = 0; sk < (1u << 24); sk++) {  // uniform
                         ensure_window();
-#if FINE_VECTOR_LAYERS
-                        // Round 5: the same counting, but by ALL 64 LANES AT ONCE on the register window instead of one scalar
-                        // branch chain per command (47 scalar instructions per BEGIN_CLIP SOLID END_CLIP, 10 k of the C4 tile's 19 k).
+                        // Counted by ALL 64 LANES AT ONCE on the register window (a scalar branch chain per command was 47 scalar
+                        // instructions per BEGIN_CLIP SOLID END_CLIP, 10 k of the C4 tile's 19 k).
                         // Lane k looks at word k of the window and at its two predecessors (DPP wave shifts) and decides whether
                         // the stream is still countable THERE, given that it was up to there: a word behind an END_CLIP tag is its
                         // blend (low byte 0 = src-over, mix class covered by rgba_known), the word behind that its alpha
@@ -1580,86 +1475,23 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                                 pc += end - wo;
                             }
                         }
-#else
-#if defined(__HIP_DEVICE_COMPILE__)
-                        uint32_t t_i, t_t, t_b;
-                        asm volatile(
-                            "1:\n"
-                            "  s_sub_u32 %[i], %[pc], %[wb]\n"
-                            "  s_cmp_gt_u32 %[i], %[lim]\n"
-                            "  s_cbranch_scc1 9f\n"
-                            "  v_readlane_b32 %[t], %[w], %[i]\n"
-                            "  s_cmp_eq_u32 %[t], 10\n"
-                            "  s_cbranch_scc0 2f\n"
-                            "  s_add_u32 %[d], %[d], 1\n"
-                            "  s_add_u32 %[pc], %[pc], 1\n"
-                            "  s_branch 1b\n"
-                            "2:\n"
-                            "  s_cmp_eq_u32 %[t], 3\n"
-                            "  s_cbranch_scc0 3f\n"
-                            "  s_add_u32 %[pc], %[pc], 1\n"
-                            "  s_branch 1b\n"
-                            "3:\n"
-                            "  s_cmp_eq_u32 %[t], 11\n"
-                            "  s_cbranch_scc0 9f\n"
-                            "  s_cmp_eq_u32 %[d], 0\n"
-                            "  s_cbranch_scc1 9f\n"
-                            "  s_cmp_ge_u32 %[pd], %[d]\n"
-                            "  s_cbranch_scc1 9f\n"
-                            "  s_add_u32 %[t], %[i], 1\n"
-                            "  s_add_u32 %[i], %[i], 2\n"
-                            "  v_readlane_b32 %[b], %[w], %[t]\n"
-                            "  v_readlane_b32 %[i], %[w], %[i]\n"
-                            "  s_cmp_gt_u32 %[i], 0x7f7fffff\n"
-                            "  s_cbranch_scc1 9f\n"
-                            "  s_and_b32 %[t], %[b], 0xff\n"
-                            "  s_cbranch_scc1 9f\n"
-                            "  s_mov_b32 %[t], 1\n"
-                            "  s_and_b32 %[i], %[b], 0x7fff\n"
-                            "  s_cbranch_scc0 4f\n"
-                            "  s_mov_b32 %[t], 3\n"
-                            "  s_cmp_lt_u32 %[b], 0xc00\n"
-                            "  s_cbranch_scc1 4f\n"
-                            "  s_mov_b32 %[t], 7\n"
-                            "  s_cmp_lt_u32 %[b], 0xf00\n"
-                            "  s_cbranch_scc0 9f\n"
-                            "4:\n"
-                            "  s_andn2_b32 %[t], %[t], %[kn]\n"
-                            "  s_cbranch_scc1 9f\n"
-                            "  s_sub_u32 %[d], %[d], 1\n"
-                            "  s_add_u32 %[pc], %[pc], 3\n"
-                            "  s_branch 1b\n"
-                            "9:\n"
-                            : [pc] "+s"(pc), [d] "+s"(clip_depth), [i] "=&s"(t_i), [t] "=&s"(t_t), [b] "=&s"(t_b)
-                            : [wb] "s"(wbase), [pd] "s"(pushed_depth), [kn] "s"(rgba_known), [w] "v"(wcur), [lim] "n"(64 - (int)FINE_TRIP_WORDS)
-                            : "scc");
-#endif
-#endif
                         if (pc - wbase <= 64u - FINE_TRIP_WORDS) break;  // (else: the window ran out, not the commands)
                     }
                     woff = pc - wbase;
                     tag = W(0);  // (what the decoder below sees if this trip leaves the loop)
                 }
-#ifdef FINE_NO_COUNTING_LOOP  // (A/B builds only: every layer is tested and decoded by the trip below, as before round 4)
-                area_one = false; rgba_known = 0u;
-#endif
                 // (a JUMP followed inside this loop -- so that area_one / rgba_known would survive the chunk boundary -- measured 8 % SLOWER on
                 // C4 and 7 % on the nested variant: the window registers redefined inside the loop cost more than the five trips per tile save)
                 uint32_t k = 0u, nb = 0u;
                 while (nb < 3u && W(k) == JL_CMD_BEGIN_CLIP) { nb++; k++; }
                 const bool solid = W(k) == JL_CMD_SOLID;
                 if (solid) k++;
-#if FINE_LAYER_FILL
-                // (round 5) BEGIN_CLIP ... FILL END_CLIP: the layer of a tile that the clip path covers only in part -- 25 per tile in
+                // BEGIN_CLIP ... FILL END_CLIP: the layer of a tile that the clip path covers only in part -- 25 per tile in
                 // the C4 scene -- stays in this loop as well: its coverage is evaluated, and the END_CLIP that closes a layer with
                 // nothing drawn in it takes the shortcut with the area tested (a trip through the general decoder is ~250 scalar
                 // instructions).  Up to 3 + 4 + 3 = 10 of the trip's FINE_TRIP_WORDS words.
                 const bool filled = !solid && W(k) == JL_CMD_FILL && W(k + 4u) == JL_CMD_END_CLIP;
                 if (!filled && W(k) != JL_CMD_END_CLIP) break;
-#else
-                const bool filled = false;
-                if (W(k) != JL_CMD_END_CLIP) break;
-#endif
                 // (the decoder's order: BEGIN_CLIPs, then SOLID, then the command)
                 clip_depth += nb;
                 if (solid && !area_one) {
@@ -1766,13 +1598,9 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                         bg = blend_spill.rd(spill_base + pix_spill(k));
                     }
                     V4 src = v4(rgba[k].x * area[k] * alpha, rgba[k].y * area[k] * alpha, rgba[k].z * area[k] * alpha, rgba[k].w * area[k] * alpha);
-#if defined(FINE_DIFF_BLEND) && defined(JH_VARIANT_BUILD)  // (differential build: every full END_CLIP blends plain src-over)
-                    rgba[k] = blend_mix_compose(bg, src, 0u);
-#else
                     // (the plain / clip case inlined here instead of behind the call -- two of three full blends of a nest of clips -- measured
                     // SLOWER, 2928 -> 3095 us on nested C4: the instantiation has no register to spare, ten more spills)
                     rgba[k] = blend_mix_compose(bg, src, blend);
-#endif
                 }
                 pushed_depth = level;
             }
@@ -1802,11 +1630,6 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                 int32_t x = to_i32(round_(extend_mode(my_d, ext) * 511.0f));
                 rgba[k] = over(rgba[k], load_grad(x, index), area[k]);
             }
-#if defined(FINE_DIFF_GRAD) && defined(JH_VARIANT_BUILD)  // (differential build: a radial gradient composites like a transparent colour)
-        } else if (PAINTS && tag == JL_CMD_RAD_GRAD) {
-            have_fg = true;
-            pc += 3u;
-#endif
         } else if (PAINTS && tag == JL_CMD_RAD_GRAD) {
             materialize();
             pc += 3u;

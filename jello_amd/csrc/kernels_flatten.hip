@@ -129,12 +129,8 @@ struct Out {
         cursor += n;
         if (EMIT) {
             a_first = first;
-#if defined(FL_ISPLIT) && FL_ISPLIT == 2  // (measurement builds only: direct lines allocate nothing -- results are wrong)
-            a_spos = a_rpos = FL_INVALID;
-#else
             a_spos = fl_grab<0>(T, home_s, n, failed_s);
             a_rpos = fl_grab<1>(T, home_r, n, failed_r);
-#endif
         }
         return first;
     }
@@ -395,9 +391,7 @@ JD void piece_record_write(uint4* __restrict__ rec, V2 es_p0, V2 es_p1, float th
 }
 // slot_info of the n lines of a piece whose first line has slot tpos
 JD void piece_slots_write(uint2* __restrict__ sinfo, uint32_t tpos, uint32_t n_u, uint32_t r) {
-#if !(defined(FL_ISPLIT) && FL_ISPLIT == 1)  // (measurement builds only: no slot_info of pieces -- results are wrong)
     for (uint32_t i = 0u; i < n_u; i++) sinfo[tpos + i] = make_uint2(r, FL_INFO_PIECE | (n_u << 8) | i);
-#endif
 }
 
 struct EulerJob {
@@ -1317,11 +1311,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
         const bool bail = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.bail) != 0u;
         const uint32_t nl = bail ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_leaves);
         uint32_t rec_base = 0u;
-#if defined(FL_ISPLIT) && FL_ISPLIT == 3  // (measurement builds only: the batches allocate nothing -- results are wrong)
-        if (nl != 0u && lane == 0u) rec_base = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 640u % (T.K * T.R - 640u);
-#else
         if (nl != 0u && lane == 0u) rec_base = fl_grab<1>(T, o.home_r, nl, o.failed_r);
-#endif
         rec_base = (uint32_t)__builtin_amdgcn_readlane((int)rec_base, 0);
 #ifdef FL_SPLIT_NO_B  // (measurement builds only: no piece is written)
         for (uint32_t lbase = nl; lbase < nl; lbase += 64u) {
@@ -1364,11 +1354,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             const bool together = batch_total <= ((debug & 4u) != 0u ? 48u : FL_MAX_GRAB);  // uniform (jh_debug_flatten_regions bit 2: tests)
             uint32_t grab = 0u;
             if (together) {
-#if defined(FL_ISPLIT) && FL_ISPLIT == 3
-                if (lane == 0u) grab = FL_INVALID;
-#else
                 if (lane == 0u) grab = fl_grab<0>(T, o.home_s, batch_total, o.failed_s);
-#endif
             } else if (active && total != 0u) {
                 grab = fl_grab<0>(T, o.home_s, total, o.failed_s);
             }
