@@ -22,13 +22,23 @@
 #ifndef JH_SCR_SKEW
 #define JH_SCR_SKEW 1280u
 #endif
+// Self-cleaned slots and their "left clean by its kernels" flags (kcommon.h): the one place that pairs them.
+enum { JH_CLEAN_FL_CTR = 1u, JH_CLEAN_BD_CTR = 2u, JH_CLEAN_SCAN = 8u, JH_CLEAN_PC_TOT = 16u };
+static const struct { int slot; uint32_t flag; } kSelfCleaned[] = {
+    {JH_SCR_FL_CTR, JH_CLEAN_FL_CTR}, {JH_SCR_BD_CTR, JH_CLEAN_BD_CTR}, {JH_SCR_SCAN_TMP, JH_CLEAN_SCAN}, {JH_SCR_PC_TOT, JH_CLEAN_PC_TOT}};
+static uint32_t clean_flag_of(int slot) {
+    for (const auto& k : kSelfCleaned)
+        if (k.slot == slot) return k.flag;
+    return 0u;  // (the other arrays are written before they are read in every frame)
+}
+
 struct JhScratch {
-    void* ptr[JH_SCR_COUNT];
-    void* base[JH_SCR_COUNT];  // what hipMalloc returned (ptr may be offset into it)
-    uint64_t cap[JH_SCR_COUNT];
+    void* ptr[JH_SCR_COUNT] = {};
+    void* base[JH_SCR_COUNT] = {};  // what hipMalloc returned (ptr may be offset into it)
+    uint64_t cap[JH_SCR_COUNT] = {};
     std::vector<void*> retired;  // old allocations kept until the next sync (kernels may still use them)
-    uint32_t clean_flags;        // JH_CLEAN_*: see kcommon.h
-    jh_ctx* ctx;
+    uint32_t clean_flags = 0u;   // JH_CLEAN_*
+    jh_ctx* ctx = nullptr;
 };
 
 struct Alloc {
@@ -54,20 +64,13 @@ struct ProfEntry {
     hipEvent_t start = nullptr, stop = nullptr;  // query only
 };
 
-// A recorded command that has not been launched yet.  Five of the recording's commands are 1-thread or trivially small
-// kernels in front of a stage that can do their work in passing (the last pathtag scan, bbox_clear and Clear(bump) in front of flatten,
-// path_count_setup / path_tiling_setup in front of their indirect dispatches, pathtag_reduce2 in front of pathtag_scan1;
-// render.go:186-197,230-237,369-374,415-420): the
-// engine holds them back until the next command and lets that stage absorb them when it is the one they were waiting for
-// (same buffers) -- or launches them as recorded before anything else happens (any other command, a download, a sync, the
-// end of a graph capture).  What every buffer holds after each command is what the recording says.
-struct Deferred {
-    bool is_clear = false;
-    int stage = -1;
-    uint32_t gx = 0, gy = 0, gz = 0;
-    std::vector<JhBound> b;
-    void* clear_ptr = nullptr;
-    uint64_t clear_bytes = 0;
+// A recorded command that has not been launched yet: see "held-back commands" below.
+enum HeldKind { HELD_NONE = -1, HELD_BUMP_CLEAR, HELD_BBOX_CLEAR, HELD_LAST_SCAN, HELD_REDUCE2, HELD_COUNT_SETUP, HELD_TILING_SETUP };
+struct Held {
+    HeldKind kind;
+    int stage;  // jh_stage; -1 for HELD_BUMP_CLEAR, the recording's Clear command
+    uint32_t gx, gy, gz;
+    std::vector<JhBound> b;  // the command's bindings; HELD_BUMP_CLEAR: b[0] = the range to clear
 };
 
 struct JhGraph {  // a captured frame plus the resource generation it was captured against
@@ -118,13 +121,13 @@ struct jh_ctx {
     uint64_t image_table_cap = 0;
     uint32_t* hint_overflow = nullptr;  // device word: blend-stack saves fine had to drop because the clip-depth hint was too small
     std::vector<JhImageDesc> image_table_host;
-    std::vector<Deferred> deferred;  // held-back commands, in recording order
+    std::vector<Held> held;  // held-back commands, in recording order
 };
 
-static int flush_deferred(jh_ctx* ctx);
+static int flush_held(jh_ctx* ctx);
 #define JH_FLUSH(ctx)                              \
     do {                                           \
-        int frc__ = flush_deferred(ctx);           \
+        int frc__ = flush_held(ctx);               \
         if (frc__ != JH_OK) return frc__;          \
     } while (0)
 
@@ -197,20 +200,22 @@ void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes) {
     // new memory holds anything: the slot's "left clean by its kernels" flag goes down (the other slots keep theirs -- with one
     // flag word for all, a frame that grew ANY array late made the next frame fill every counter again, and a graph captured
     // from that frame kept the fills)
-    switch (slot) {
-        case JH_SCR_SCAN_TMP: s->clean_flags &= ~(uint32_t)JH_CLEAN_SCAN; break;
-        case JH_SCR_FL_CTR: s->clean_flags &= ~(uint32_t)JH_CLEAN_FL_CTR; break;
-        case JH_SCR_BD_CTR: s->clean_flags &= ~(uint32_t)JH_CLEAN_BD_CTR; break;
-        case JH_SCR_PC_TOT: s->clean_flags &= ~(uint32_t)JH_CLEAN_PC_TOT; break;
-        default: break;  // (the other arrays are written before they are read in every frame)
-    }
+    s->clean_flags &= ~clean_flag_of(slot);
     p = (char*)p + (uint64_t)slot * JH_SCR_SKEW;
     s->ptr[slot] = p;
     s->cap[slot] = cap;
     return p;
 }
 
-uint32_t* jh_scratch_flags(JhScratch* s) { return &s->clean_flags; }
+void* jh_scratch_acquire(JhScratch* s, int slot, uint64_t bytes, uint64_t fill_bytes, hipStream_t stream) {
+    void* p = jh_scratch_get(s, slot, bytes);
+    if (!p) return nullptr;
+    const uint32_t flag = clean_flag_of(slot);
+    if ((s->clean_flags & flag) == 0u) (void)hipMemsetAsync(p, 0, std::min(fill_bytes, s->cap[slot]), stream);
+    s->clean_flags &= ~flag;
+    return p;
+}
+void jh_scratch_left_clean(JhScratch* s, int slot) { s->clean_flags |= clean_flag_of(slot); }
 uint64_t jh_scratch_cap(JhScratch* s, int slot) { return (slot >= 0 && slot < JH_SCR_COUNT) ? s->cap[slot] : 0; }
 
 static void scratch_release_retired(JhScratch* s) {
@@ -248,28 +253,152 @@ static void* stage_copy(jh_ctx* ctx, const void* data, uint64_t size) {
     return dst;
 }
 
-// Per-stage binding contract (SURVEY Appendix C = renderer/render.go dispatch order): minimum binding count and the
-// slots whose contents the launchers dereference as fixed structs -- checked before every launch so that a buffer that
-// is too small yields JH_ERR_INVALID instead of an out-of-bounds read.
-struct StageContract { int n_min, cfg, bump, indirect; };
-static const StageContract kContract[JH_STAGE_COUNT] = {
-    /* pathtag_reduce */ {3, 0, -1, -1}, /* pathtag_reduce2 */ {2, -1, -1, -1}, /* pathtag_scan1 */ {3, -1, -1, -1},
-    /* pathtag_scan_small */ {4, 0, -1, -1}, /* pathtag_scan_large */ {4, 0, -1, -1}, /* bbox_clear */ {2, 0, -1, -1},
-    /* flatten */ {6, 0, 4, -1}, /* draw_reduce */ {3, 0, -1, -1}, /* draw_leaf */ {7, 0, -1, -1}, /* clip_reduce */ {4, -1, -1, -1},
-    /* clip_leaf */ {7, 0, -1, -1}, /* binning */ {8, 0, 5, -1}, /* tile_alloc */ {6, 0, 3, -1}, /* backdrop_dyn */ {4, 0, 1, -1},
-    /* path_count_setup */ {2, -1, 0, 1}, /* path_count */ {6, 0, 1, -1}, /* coarse */ {9, 0, 7, -1},
-    /* path_tiling_setup */ {3, -1, 0, 1}, /* path_tiling */ {6, -1, 0, -1}, /* fine_area */ {7, 0, -1, -1},
-    /* fine_msaa8 */ {9, 0, -1, -1}, /* fine_msaa16 */ {9, 0, -1, -1}};
+// The stage table, indexed by jh_stage: name, binding contract and launcher, from the list in kcommon.h.
+struct StageInfo {
+    const char* name;
+    int n_min, cfg, bump, indirect;
+    bool indirect_only;
+    JhResult (*launch)(const JhLaunch&);
+};
+#define JH_STAGE_ENTRY(name, ...) {#name, __VA_ARGS__, jh_launch_##name},
+static const StageInfo kStages[JH_STAGE_COUNT] = {JH_STAGE_LIST(JH_STAGE_ENTRY)};
+#undef JH_STAGE_ENTRY
+
+// What every launch gets from the context (the dispatcher adds the command's own: images, indirect count, config shadow, ...)
+static JhLaunch make_launch(jh_ctx* ctx, uint32_t gx, uint32_t gy, uint32_t gz, const std::vector<JhBound>& b) {
+    JhLaunch L = {};
+    L.stream = ctx->stream;
+    L.scratch = &ctx->scratch;
+    L.gx = gx; L.gy = gy; L.gz = gz;
+    L.b = b.data();
+    L.nb = (int)b.size();
+    L.num_cus = ctx->num_cus;
+    L.band_row0 = ctx->band_row0;
+    L.band_row1 = ctx->band_row1;
+    L.clip_depth_hint = ctx->clip_depth_hint;
+    L.hint_overflow = ctx->hint_overflow;
+    L.debug_flatten = ctx->debug_flatten;
+    return L;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Held-back commands
+// ------------------------------------------------------------------------------------------------
+// Six of the recording's commands are 1-thread or trivially small kernels (or a fill) in front of a stage that can do their
+// work in passing (render.go:186-197,230-237,369-374,415-420).  The engine holds them back until the next command and lets
+// that command absorb them when it is the consumer they were waiting for (same buffers) -- or launches them as recorded before
+// anything else happens (any other command, a download, a sync, a buffer that moves, the end of a graph capture: JH_FLUSH).
+// What every buffer holds after each command is what the recording says.  The rules, each stated once below:
+//   which command may be held         held_kind_of_dispatch, clear_may_be_held
+//   what may wait together            hold_back
+//   for which consumer, on which of
+//   its bindings, what it is told     absorb_one
+// Not while profiling: a held-back stage's query would bracket nothing and its work would be charged to the stage that
+// absorbs it -- with the profiler on every command is launched as recorded and every query times its own stage.
+static HeldKind held_kind_of_dispatch(const jh_ctx* ctx, int stage, uint32_t gx) {
+    if (ctx->profiling) return HELD_NONE;
+    switch (stage) {
+        case JH_BBOX_CLEAR: return HELD_BBOX_CLEAR;
+        case JH_PATH_COUNT_SETUP: return HELD_COUNT_SETUP;
+        case JH_PATH_TILING_SETUP: return HELD_TILING_SETUP;
+        // (the reference always dispatches reduce2 with 256 workgroups, one thread of its consumer per entry of reduced2)
+        case JH_PATHTAG_REDUCE2: return gx > 0u && gx <= 256u ? HELD_REDUCE2 : HELD_NONE;
+        case JH_PATHTAG_SCAN_SMALL: case JH_PATHTAG_SCAN_LARGE: return gx > 0u ? HELD_LAST_SCAN : HELD_NONE;
+        default: return HELD_NONE;
+    }
+}
+// (the recording's Clear(bump) in front of flatten, render.go:237: the whole of a buffer that is a BumpAllocators)
+static bool clear_may_be_held(const jh_ctx* ctx, const Alloc& a, uint64_t offset, uint64_t n) {
+    return !ctx->profiling && n && offset == 0 && n == a.size && a.size == sizeof(JlBump);
+}
+
+// Only one kind of thing waits at a time, except what waits for flatten: the last pathtag scan, bbox_clear and Clear(bump), one of
+// each.  Whatever else is waiting is launched first.
+static bool waits_for_flatten(HeldKind k) { return k == HELD_BUMP_CLEAR || k == HELD_BBOX_CLEAR || k == HELD_LAST_SCAN; }
+static int hold_back(jh_ctx* ctx, Held&& h) {
+    for (const Held& d : ctx->held)
+        if (!(waits_for_flatten(h.kind) && waits_for_flatten(d.kind) && d.kind != h.kind)) { JH_FLUSH(ctx); break; }
+    ctx->held.push_back(std::move(h));
+    return JH_OK;
+}
+
+static bool same_buffer(const JhBound& x, const JhBound& y) { return x.ptr == y.ptr && x.size == y.size; }
+// Is the command being dispatched (stage, gx, indirect count, bindings b) the consumer the held-back command `d` waits for?  If
+// so, notes in `a` what its launcher has to do in passing.
+static bool absorb_one(int stage, uint32_t gx, const uint32_t* indirect, const std::vector<JhBound>& b, const Held& d, JhAbsorbed& a) {
+    // (a dispatch with no workgroups launches nothing that could do the held-back work in passing -- an empty scene's flatten,
+    // renderer.cpp: flatten_wgs = 0 -- so what waits for it runs as recorded: ADVICE r03)
+    const bool flatten = stage == JH_FLATTEN && gx > 0u;
+    switch (d.kind) {
+        case HELD_BUMP_CLEAR:  // flatten's first kernel zeroes the bump allocators
+            if (!(flatten && same_buffer(d.b[0], b[FL_BUMP]) && b[FL_BUMP].size == sizeof(JlBump))) return false;
+            a.bump_clear = true;
+            return true;
+        case HELD_BBOX_CLEAR:  // ... and resets the path bboxes
+            if (!(flatten && d.b[BC_CFG].ptr == b[FL_CFG].ptr && same_buffer(d.b[BC_BBOX], b[FL_BBOX]))) return false;
+            a.bbox_clear = true;
+            return true;
+        case HELD_LAST_SCAN:
+            // flatten's classification kernel, which reads every tag word and its monoid back, produces the monoids in passing
+            // (k_pathtag_scan_classify): same config and scene, the scan's output is the tag monoids flatten reads, and its
+            // threads (one per tag word = four tag bytes) cover flatten's (one per tag byte)
+            if (!(flatten && d.b[PSC_CFG].ptr == b[FL_CFG].ptr && same_buffer(d.b[PSC_SCENE], b[FL_SCENE]) && same_buffer(d.b[PSC_TM], b[FL_TM]) &&
+                  (uint64_t)d.gx * 4u >= (uint64_t)gx && d.gy <= 1u && d.gz <= 1u))
+                return false;
+            a.pathtag_scan = true;
+            a.scan_reduced = d.b[PSC_REDUCED];
+            a.scan_wgs = d.gx;
+            a.scan_small = d.stage == JH_PATHTAG_SCAN_SMALL;
+            return true;
+        case HELD_REDUCE2:
+            // pathtag_scan1 redoes reduce2's sums in passing if it runs at most PT_ABSORB_MAX workgroups itself
+            if (!(stage == JH_PATHTAG_SCAN1 && gx > 0u && gx <= PT_ABSORB_MAX && gx <= d.gx && same_buffer(d.b[PR2_REDUCED], b[PS1_REDUCED]) &&
+                  same_buffer(d.b[PR2_REDUCED2], b[PS1_REDUCED2])))
+                return false;
+            a.reduce2 = true;
+            a.reduce2_entries = d.gx;
+            return true;
+        case HELD_COUNT_SETUP:  // k_pc_count writes the indirect count it is dispatched with
+            if (!(stage == JH_PATH_COUNT && indirect && d.b[PCS_BUMP].ptr == b[PC_BUMP].ptr && d.b[PCS_INDIRECT].ptr == (void*)indirect)) return false;
+            a.write_indirect = true;
+            return true;
+        case HELD_TILING_SETUP:  // k_path_tiling likewise, and marks the ptcl on failure
+            if (!(stage == JH_PATH_TILING && indirect && d.b[PTS_BUMP].ptr == b[PT_BUMP].ptr && d.b[PTS_INDIRECT].ptr == (void*)indirect)) return false;
+            a.write_indirect = true;
+            a.tiling_ptcl = d.b[PTS_PTCL];
+            return true;
+        default: return false;
+    }
+}
+// Does this command absorb EVERYTHING that is waiting?  Then *out says with what, and nothing waits any more.
+static bool absorb_all(jh_ctx* ctx, int stage, uint32_t gx, const uint32_t* indirect, const std::vector<JhBound>& b, JhAbsorbed* out) {
+    JhAbsorbed a = {};
+    for (const Held& d : ctx->held)
+        if (!absorb_one(stage, gx, indirect, b, d, a)) return false;
+    *out = a;
+    ctx->held.clear();
+    return true;
+}
+
+// Launches every held-back command as recorded.
+static int flush_held(jh_ctx* ctx) {
+    if (ctx->held.empty()) return JH_OK;
+    std::vector<Held> pending;
+    pending.swap(ctx->held);
+    for (const Held& d : pending) {
+        if (d.kind == HELD_BUMP_CLEAR) {
+            HIP_TRY(ctx, hipMemsetAsync(d.b[0].ptr, 0, d.b[0].size, ctx->stream));
+            continue;
+        }
+        if (kStages[d.stage].launch(make_launch(ctx, d.gx, d.gy, d.gz, d.b)) != JH_L_OK)
+            return fail(ctx, JH_ERR_INVALID, std::string("deferred stage failed: ") + jh_stage_name(d.stage));
+    }
+    return JH_OK;
+}
 
 extern "C" {
 
-const char* jh_stage_name(int stage) {
-    static const char* names[JH_STAGE_COUNT] = {
-        "pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear", "flatten",
-        "draw_reduce", "draw_leaf", "clip_reduce", "clip_leaf", "binning", "tile_alloc", "backdrop_dyn", "path_count_setup", "path_count",
-        "coarse", "path_tiling_setup", "path_tiling", "fine_area", "fine_msaa8", "fine_msaa16"};
-    return (stage >= 0 && stage < JH_STAGE_COUNT) ? names[stage] : "?";
-}
+const char* jh_stage_name(int stage) { return (stage >= 0 && stage < JH_STAGE_COUNT) ? kStages[stage].name : "?"; }
 
 int jh_create(jh_ctx** out, int device) {
     if (!out) return JH_ERR_INVALID;
@@ -291,10 +420,6 @@ int jh_create(jh_ctx** out, int device) {
         return JH_ERR_DEVICE;
     }
     ctx->stream = ctx->own_stream;
-    std::memset(&ctx->scratch.ptr, 0, sizeof ctx->scratch.ptr);
-    std::memset(&ctx->scratch.cap, 0, sizeof ctx->scratch.cap);
-    std::memset(&ctx->scratch.base, 0, sizeof ctx->scratch.base);
-    ctx->scratch.clean_flags = 0u;
     ctx->scratch.ctx = ctx;
     // (zeroed on the context's OWN stream: a hipMemset here would be the process's first use of the legacy default stream, and
     // from then on the frames of two contexts no longer overlapped at all -- bench.py's two frames in flight fell from 0.91 to
@@ -379,19 +504,30 @@ int jh_sync(jh_ctx* ctx) {
 }
 
 // ---- buffers ----
+static Alloc* find_alloc(std::unordered_map<uint64_t, Alloc>& map, uint64_t id) {
+    auto it = map.find(id);
+    return it == map.end() ? nullptr : &it->second;
+}
+// The allocation behind an id goes away (the caller erases or overwrites the entry).  Memory the context owns goes back to the
+// pool and into circulation, so captured graphs that may point to it become stale.  Caller-owned memory stays valid for as long
+// as its owner keeps it -- a graph captured while it was bound keeps using it, e.g. double-buffered output images -- unless
+// the caller asks for staleness anyway (`stale_if_imported`).
+static void retire_alloc(jh_ctx* ctx, const Alloc& a, bool stale_if_imported = false) {
+    if (a.owned) ctx->pool.insert({a.capacity, a.ptr});
+    if (a.owned || stale_if_imported) ctx->generation++;
+}
+
 static int buffer_get_or_create(jh_ctx* ctx, uint64_t id, uint64_t size, Alloc** out) {
-    auto it = ctx->buffers.find(id);
-    if (it != ctx->buffers.end()) {
-        if (it->second.size >= size) {
-            *out = &it->second;
+    if (Alloc* old = find_alloc(ctx->buffers, id)) {
+        if (old->size >= size) {
+            *out = old;
             return 0;
         }
-        if (!it->second.owned) return fail(ctx, JH_ERR_INVALID, "imported buffer is smaller than the requested size (the caller owns it: cannot grow)");
+        if (!old->owned) return fail(ctx, JH_ERR_INVALID, "imported buffer is smaller than the requested size (the caller owns it: cannot grow)");
         // grow: return the old allocation to the pool (a held-back command may still refer to it: launch those first)
         JH_FLUSH(ctx);
-        ctx->pool.insert({it->second.capacity, it->second.ptr});
-        ctx->buffers.erase(it);
-        ctx->generation++;
+        retire_alloc(ctx, *old);
+        ctx->buffers.erase(id);
     }
     Alloc a;
     int rc = pool_get(ctx, size, &a.ptr, &a.capacity);
@@ -413,13 +549,7 @@ int jh_buffer_create(jh_ctx* ctx, uint64_t id, uint64_t size) {
 int jh_buffer_import(jh_ctx* ctx, uint64_t id, void* device_ptr, uint64_t size) {
     if (!ctx || !device_ptr) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
-    auto it = ctx->buffers.find(id);
-    if (it != ctx->buffers.end() && it->second.owned) {
-        ctx->pool.insert({it->second.capacity, it->second.ptr});
-        ctx->generation++;  // pool memory a graph may point to goes back into circulation
-    }
-    // (Re-importing caller-owned memory does not invalidate graphs: a graph captured while another pointer was bound keeps
-    // using that pointer, which stays valid for as long as its owner keeps it -- e.g. double-buffered output images.)
+    if (const Alloc* old = find_alloc(ctx->buffers, id)) retire_alloc(ctx, *old);  // (re-importing caller-owned memory leaves graphs valid)
     Alloc a;
     a.ptr = device_ptr;
     a.size = size;
@@ -467,22 +597,17 @@ int jh_upload(jh_ctx* ctx, uint64_t id, const void* data, uint64_t size) {
 int jh_clear(jh_ctx* ctx, uint64_t id, uint64_t offset, int64_t size) {
     if (!ctx) return JH_ERR_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto it = ctx->buffers.find(id);
-    if (it == ctx->buffers.end()) return fail(ctx, JH_ERR_INVALID, "jh_clear: unknown buffer id (create it first)");
-    Alloc& a = it->second;
-    if (offset > a.size) return fail(ctx, JH_ERR_INVALID, "jh_clear: offset out of range");
-    uint64_t n = size < 0 ? a.size - offset : (uint64_t)size;
-    if (offset + n > a.size) n = a.size - offset;
-    const bool bump_like = !ctx->profiling && n && offset == 0 && n == a.size && a.size == sizeof(JlBump);  // (profiling: as recorded)
-    for (const Deferred& d : ctx->deferred)
-        if (!(bump_like && !d.is_clear && (d.stage == JH_BBOX_CLEAR || d.stage == JH_PATHTAG_SCAN_SMALL || d.stage == JH_PATHTAG_SCAN_LARGE))) { JH_FLUSH(ctx); break; }
-    if (bump_like) {
-        // (the recording's Clear(bump) in front of flatten, render.go:237: flatten's first kernel does it in passing)
-        Deferred d;
-        d.is_clear = true; d.clear_ptr = a.ptr; d.clear_bytes = n;
-        ctx->deferred.push_back(d);
-    } else if (n) {
-        HIP_TRY(ctx, hipMemsetAsync((char*)a.ptr + offset, 0, n, ctx->stream));
+    Alloc* a = find_alloc(ctx->buffers, id);
+    if (!a) return fail(ctx, JH_ERR_INVALID, "jh_clear: unknown buffer id (create it first)");
+    if (offset > a->size) return fail(ctx, JH_ERR_INVALID, "jh_clear: offset out of range");
+    uint64_t n = size < 0 ? a->size - offset : (uint64_t)size;
+    if (offset + n > a->size) n = a->size - offset;
+    if (clear_may_be_held(ctx, *a, offset, n)) {
+        int rc = hold_back(ctx, Held{HELD_BUMP_CLEAR, -1, 0, 0, 0, {JhBound{a->ptr, n, 0, 0, 0}}});
+        if (rc) return rc;
+    } else {
+        JH_FLUSH(ctx);
+        if (n) HIP_TRY(ctx, hipMemsetAsync((char*)a->ptr + offset, 0, n, ctx->stream));
     }
     if (n && offset < sizeof(JlConfig) && ctx->config_shadow.erase(id)) ctx->generation++;  // the shadow no longer describes the device copy
     return JH_OK;
@@ -492,10 +617,10 @@ int jh_download(jh_ctx* ctx, uint64_t id, void* dst, uint64_t offset, uint64_t s
     if (!ctx || !dst) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto it = ctx->buffers.find(id);
-    if (it == ctx->buffers.end()) return fail(ctx, JH_ERR_INVALID, "jh_download: unknown buffer id");
-    if (offset + size > it->second.size) return fail(ctx, JH_ERR_INVALID, "jh_download: range out of bounds");
-    HIP_TRY(ctx, hipMemcpyAsync(dst, (char*)it->second.ptr + offset, size, hipMemcpyDeviceToHost, ctx->stream));
+    const Alloc* a = find_alloc(ctx->buffers, id);
+    if (!a) return fail(ctx, JH_ERR_INVALID, "jh_download: unknown buffer id");
+    if (offset + size > a->size) return fail(ctx, JH_ERR_INVALID, "jh_download: range out of bounds");
+    HIP_TRY(ctx, hipMemcpyAsync(dst, (char*)a->ptr + offset, size, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return JH_OK;
 }
@@ -503,26 +628,21 @@ int jh_download(jh_ctx* ctx, uint64_t id, void* dst, uint64_t offset, uint64_t s
 int jh_free(jh_ctx* ctx, uint64_t id) {
     if (!ctx) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
-    auto it = ctx->buffers.find(id);
-    if (it == ctx->buffers.end()) return JH_OK;  // the reference ignores frees of unknown ids (wgpu.go:601-603)
-    if (it->second.owned) {
-        ctx->pool.insert({it->second.capacity, it->second.ptr});
-        ctx->generation++;
-    }
-    ctx->buffers.erase(it);
+    const Alloc* a = find_alloc(ctx->buffers, id);
+    if (!a) return JH_OK;  // the reference ignores frees of unknown ids (wgpu.go:601-603)
+    retire_alloc(ctx, *a);
+    ctx->buffers.erase(id);
     ctx->config_shadow.erase(id);
     return JH_OK;
 }
 
 void* jh_buffer_device_ptr(jh_ctx* ctx, uint64_t id) {
-    if (!ctx) return nullptr;
-    auto it = ctx->buffers.find(id);
-    return it == ctx->buffers.end() ? nullptr : it->second.ptr;
+    const Alloc* a = ctx ? find_alloc(ctx->buffers, id) : nullptr;
+    return a ? a->ptr : nullptr;
 }
 uint64_t jh_buffer_size(jh_ctx* ctx, uint64_t id) {
-    if (!ctx) return 0;
-    auto it = ctx->buffers.find(id);
-    return it == ctx->buffers.end() ? 0 : it->second.size;
+    const Alloc* a = ctx ? find_alloc(ctx->buffers, id) : nullptr;
+    return a ? a->size : 0;
 }
 
 // ---- images ----
@@ -540,13 +660,11 @@ int jh_image_create(jh_ctx* ctx, uint64_t id, uint32_t width, uint32_t height, i
     if (!bpp) return fail(ctx, JH_ERR_INVALID, "jh_image_create: bad format");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint64_t size = (uint64_t)width * height * bpp;
-    auto it = ctx->images.find(id);
-    if (it != ctx->images.end()) {
-        if (it->second.width == width && it->second.height == height && it->second.format == format) return JH_OK;
+    if (const Alloc* old = find_alloc(ctx->images, id)) {
+        if (old->width == width && old->height == height && old->format == format) return JH_OK;
         JH_FLUSH(ctx);
-        if (it->second.owned) ctx->pool.insert({it->second.capacity, it->second.ptr});
-        ctx->images.erase(it);
-        ctx->generation++;
+        retire_alloc(ctx, *old, /*stale_if_imported=*/true);  // (the image changes shape under the id: a graph that binds it is stale either way)
+        ctx->images.erase(id);
     }
     Alloc a;
     int rc = pool_get(ctx, size ? size : 8, &a.ptr, &a.capacity);
@@ -561,11 +679,7 @@ int jh_image_import(jh_ctx* ctx, uint64_t id, void* device_ptr, uint32_t width, 
     JH_FLUSH(ctx);
     uint64_t bpp = format_bpp(format);
     if (!bpp) return fail(ctx, JH_ERR_INVALID, "jh_image_import: bad format");
-    auto it = ctx->images.find(id);
-    if (it != ctx->images.end() && it->second.owned) {
-        ctx->pool.insert({it->second.capacity, it->second.ptr});
-        ctx->generation++;
-    }
+    if (const Alloc* old = find_alloc(ctx->images, id)) retire_alloc(ctx, *old);
     Alloc a;
     a.ptr = device_ptr; a.size = (uint64_t)width * height * bpp; a.capacity = a.size; a.owned = false;
     a.width = width; a.height = height; a.format = format; a.written = true;
@@ -600,9 +714,9 @@ int jh_image_write(jh_ctx* ctx, uint64_t id, uint32_t x, uint32_t y, uint32_t wi
     if (!ctx || (!data && size)) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto it = ctx->images.find(id);
-    if (it == ctx->images.end()) return fail(ctx, JH_ERR_INVALID, "jh_image_write: unknown image id (create it first)");
-    Alloc& a = it->second;
+    Alloc* found = find_alloc(ctx->images, id);
+    if (!found) return fail(ctx, JH_ERR_INVALID, "jh_image_write: unknown image id (create it first)");
+    Alloc& a = *found;
     const uint64_t bpp = format_bpp(a.format);
     if ((uint64_t)x + width > a.width || (uint64_t)y + height > a.height) return fail(ctx, JH_ERR_INVALID, "jh_image_write: rectangle outside the image");
     const uint64_t row = (uint64_t)width * bpp;
@@ -620,10 +734,10 @@ int jh_image_download(jh_ctx* ctx, uint64_t id, void* dst, uint64_t size) {
     if (!ctx || !dst) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto it = ctx->images.find(id);
-    if (it == ctx->images.end()) return fail(ctx, JH_ERR_INVALID, "jh_image_download: unknown image id");
-    if (size > it->second.size) size = it->second.size;
-    HIP_TRY(ctx, hipMemcpyAsync(dst, it->second.ptr, size, hipMemcpyDeviceToHost, ctx->stream));
+    const Alloc* a = find_alloc(ctx->images, id);
+    if (!a) return fail(ctx, JH_ERR_INVALID, "jh_image_download: unknown image id");
+    if (size > a->size) size = a->size;
+    HIP_TRY(ctx, hipMemcpyAsync(dst, a->ptr, size, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return JH_OK;
 }
@@ -631,20 +745,16 @@ int jh_image_download(jh_ctx* ctx, uint64_t id, void* dst, uint64_t size) {
 int jh_image_free(jh_ctx* ctx, uint64_t id) {
     if (!ctx) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
-    auto it = ctx->images.find(id);
-    if (it == ctx->images.end()) return JH_OK;
-    if (it->second.owned) {
-        ctx->pool.insert({it->second.capacity, it->second.ptr});
-        ctx->generation++;
-    }
-    ctx->images.erase(it);
+    const Alloc* a = find_alloc(ctx->images, id);
+    if (!a) return JH_OK;
+    retire_alloc(ctx, *a);
+    ctx->images.erase(id);
     return JH_OK;
 }
 
 void* jh_image_device_ptr(jh_ctx* ctx, uint64_t id) {
-    if (!ctx) return nullptr;
-    auto it = ctx->images.find(id);
-    return it == ctx->images.end() ? nullptr : it->second.ptr;
+    const Alloc* a = ctx ? find_alloc(ctx->images, id) : nullptr;
+    return a ? a->ptr : nullptr;
 }
 
 // ---- dispatch ----
@@ -656,24 +766,24 @@ static int resolve_bindings(jh_ctx* ctx, const jh_binding* bindings, int n, std:
         JhBound r;
         std::memset(&r, 0, sizeof r);
         if (b.kind == JH_BIND_BUFFER) {
-            auto it = ctx->buffers.find(b.id);
-            if (it == ctx->buffers.end()) return fail(ctx, JH_ERR_INVALID, "dispatch: unknown buffer id in binding " + std::to_string(i));
-            r.ptr = it->second.ptr;
-            r.size = it->second.size;
+            const Alloc* a = find_alloc(ctx->buffers, b.id);
+            if (!a) return fail(ctx, JH_ERR_INVALID, "dispatch: unknown buffer id in binding " + std::to_string(i));
+            r.ptr = a->ptr;
+            r.size = a->size;
             out.push_back(r);
         } else if (b.kind == JH_BIND_IMAGE) {
-            auto it = ctx->images.find(b.id);
-            if (it == ctx->images.end()) return fail(ctx, JH_ERR_INVALID, "dispatch: unknown image id in binding " + std::to_string(i));
-            r.ptr = it->second.ptr; r.size = it->second.size; r.width = it->second.width; r.height = it->second.height; r.format = it->second.format;
+            const Alloc* a = find_alloc(ctx->images, b.id);
+            if (!a) return fail(ctx, JH_ERR_INVALID, "dispatch: unknown image id in binding " + std::to_string(i));
+            r.ptr = a->ptr; r.size = a->size; r.width = a->width; r.height = a->height; r.format = a->format;
             out.push_back(r);
         } else if (b.kind == JH_BIND_IMAGE_ARRAY) {
             for (uint32_t k = 0; k < b.count; k++) {
-                auto it = ctx->images.find(b.ids[k]);
-                if (it == ctx->images.end()) return fail(ctx, JH_ERR_INVALID, "dispatch: unknown image id in image array");
+                const Alloc* a = find_alloc(ctx->images, b.ids[k]);
+                if (!a) return fail(ctx, JH_ERR_INVALID, "dispatch: unknown image id in image array");
                 JhBound im;
                 std::memset(&im, 0, sizeof im);
                 // a never-written image samples as transparent black: no pointer, the texel fetch returns zero
-                im.ptr = it->second.written ? it->second.ptr : nullptr; im.size = it->second.size; im.width = it->second.width; im.height = it->second.height; im.format = it->second.format;
+                im.ptr = a->written ? a->ptr : nullptr; im.size = a->size; im.width = a->width; im.height = a->height; im.format = a->format;
                 images.push_back(im);
             }
             out.push_back(r);  // placeholder keeps binding indices aligned with the WGSL @binding order
@@ -684,55 +794,92 @@ static int resolve_bindings(jh_ctx* ctx, const jh_binding* bindings, int n, std:
     return 0;
 }
 
-static int launch_stage(int stage, const JhLaunch& L) {
-    switch (stage) {
-        case JH_PATHTAG_REDUCE: case JH_PATHTAG_REDUCE2: case JH_PATHTAG_SCAN1: case JH_PATHTAG_SCAN_SMALL: case JH_PATHTAG_SCAN_LARGE:
-            return jh_launch_pathtag(L, stage);
-        case JH_BBOX_CLEAR: return jh_launch_bbox_clear(L);
-        case JH_FLATTEN: return jh_launch_flatten(L);
-        case JH_DRAW_REDUCE: return jh_launch_draw_reduce(L);
-        case JH_DRAW_LEAF: return jh_launch_draw_leaf(L);
-        case JH_CLIP_REDUCE: return jh_launch_clip_reduce(L);
-        case JH_CLIP_LEAF: return jh_launch_clip_leaf(L);
-        case JH_BINNING: return jh_launch_binning(L);
-        case JH_TILE_ALLOC: return jh_launch_tile_alloc(L);
-        case JH_BACKDROP_DYN: return jh_launch_backdrop_dyn(L);
-        case JH_PATH_COUNT_SETUP: return jh_launch_path_count_setup(L);
-        case JH_PATH_COUNT: return jh_launch_path_count(L);
-        case JH_COARSE: return jh_launch_coarse(L);
-        case JH_PATH_TILING_SETUP: return jh_launch_path_tiling_setup(L);
-        case JH_PATH_TILING: return jh_launch_path_tiling(L);
-        case JH_FINE_AREA: return jh_launch_fine_area(L);
-        case JH_FINE_MSAA8: return jh_launch_fine_msaa(L, 8);
-        case JH_FINE_MSAA16: return jh_launch_fine_msaa(L, 16);
-        default: return -9;
-    }
+// The launchers read these slots as fixed structs: refuses binding lists that are too short and buffers that cannot hold them.
+static int check_contract(jh_ctx* ctx, int stage, const std::vector<JhBound>& b, const uint32_t* indirect) {
+    const StageInfo& S = kStages[stage];
+    if ((int)b.size() < S.n_min) return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + S.name + ": too few");
+    auto too_small = [&](int slot, uint64_t need) { return slot >= 0 && (b[slot].ptr == nullptr || b[slot].size < need); };
+    if (too_small(S.cfg, sizeof(JlConfig)) || too_small(S.bump, sizeof(JlBump)) || too_small(S.indirect, 12))
+        return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + S.name + ": config / bump / indirect buffer too small");
+    if (S.indirect_only && !indirect) return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + S.name);
+    return JH_OK;
 }
 
-// Launches every held-back command as recorded (see Deferred).
-static int flush_deferred(jh_ctx* ctx) {
-    if (ctx->deferred.empty()) return JH_OK;
-    std::vector<Deferred> pending;
-    pending.swap(ctx->deferred);
-    for (const Deferred& d : pending) {
-        if (d.is_clear) {
-            HIP_TRY(ctx, hipMemsetAsync(d.clear_ptr, 0, d.clear_bytes, ctx->stream));
-            continue;
-        }
-        JhLaunch L;
-        std::memset(&L, 0, sizeof L);
-        L.stream = ctx->stream;
-        L.scratch = &ctx->scratch;
-        L.gx = d.gx; L.gy = d.gy; L.gz = d.gz;
-        L.b = d.b.data();
-        L.nb = (int)d.b.size();
-        L.num_cus = ctx->num_cus;
-        L.band_row0 = ctx->band_row0;
-        L.band_row1 = ctx->band_row1;
-        int rc = launch_stage(d.stage, L);
-        if (rc) return fail(ctx, JH_ERR_INVALID, std::string("deferred stage failed: ") + jh_stage_name(d.stage));
+// More images than fit in the kernel arguments: fine indexes a device table of descriptors (the reference binds an array of up
+// to 2048 textures, wgpu.go:278).  The table is re-uploaded only when the bound set changes.
+static int bind_image_table(jh_ctx* ctx, const std::vector<JhBound>& images, const JhImageDesc** out) {
+    std::vector<JhImageDesc> t(images.size());
+    for (size_t i = 0; i < images.size(); i++) {
+        t[i].ptr = images[i].ptr; t[i].width = images[i].width; t[i].height = images[i].height;
+        t[i].srgb = images[i].format == JL_RGBA8_SRGB ? 1u : 0u; t[i].pad = 0u;
     }
+    const bool same = t.size() == ctx->image_table_host.size() &&
+                      std::memcmp(t.data(), ctx->image_table_host.data(), t.size() * sizeof(JhImageDesc)) == 0;
+    if (!same) {
+        if (ctx->capturing) return fail(ctx, JH_ERR_INVALID, "fine: the image table changed during graph capture (run the recording once eagerly first)");
+        const uint64_t bytes = t.size() * sizeof(JhImageDesc);
+        if (bytes > ctx->image_table_cap) {
+            void* np = nullptr;
+            if (hipMalloc(&np, pool_size_class(bytes)) != hipSuccess) return fail(ctx, JH_ERR_OOM, "fine: image table allocation failed");
+            if (ctx->image_table) ctx->scratch.retired.push_back(ctx->image_table);
+            ctx->image_table = np;
+            ctx->image_table_cap = pool_size_class(bytes);
+            ctx->generation++;
+        }
+        void* src = stage_copy(ctx, t.data(), bytes);
+        if (!src) return fail(ctx, JH_ERR_OOM, "fine: pinned staging allocation failed");
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->image_table, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        ctx->image_table_host = t;
+    }
+    *out = (const JhImageDesc*)ctx->image_table;
     return JH_OK;
+}
+
+// binning and coarse address a bin by its index in a 256-entry table (one per lane of the 256-thread workgroup:
+// binning.wgsl:52,131; coarse.wgsl:153-176): a target of more than 256 bins of 256 x 256 px -- beyond 4096 px in a
+// direction -- silently loses the bins past the 256th in the reference.  Here the dispatch is refused instead.
+static int check_bin_limit(jh_ctx* ctx, int stage, const JlConfig* cfg_host) {
+    if ((stage != JH_BINNING && stage != JH_COARSE) || !cfg_host) return JH_OK;
+    const uint64_t wb = (cfg_host->width_in_tiles + 15u) / 16u, hb = (cfg_host->height_in_tiles + 15u) / 16u;
+    if (wb * hb > 256u)
+        return fail(ctx, JH_ERR_INVALID, std::string(jh_stage_name(stage)) + ": the target has " + std::to_string(wb * hb) +
+                                             " bins of 256 x 256 px, the pipeline addresses 256 (at most 4096 x 4096 px or any shape of <= 256 bins)");
+    return JH_OK;
+}
+
+// One GPU query of the profile tree around whatever is enqueued between begin and end; both do nothing with the profiler off.
+// stage = -1: a query that is no stage record (the blit).
+static int prof_query_begin(jh_ctx* ctx, ProfEntry& pe, int stage, const char* label) {
+    if (!ctx->profiling) return JH_OK;
+    for (hipEvent_t* e : {&pe.start, &pe.stop}) {
+        if (ctx->free_events.empty()) { HIP_TRY(ctx, hipEventCreate(e)); continue; }
+        *e = ctx->free_events.back();
+        ctx->free_events.pop_back();
+    }
+    pe.kind = JH_PROF_QUERY;
+    pe.parent = ctx->prof_stack.empty() ? -1 : ctx->prof_stack.back();
+    pe.stage = stage;
+    pe.label = label;
+    pe.cpu_start_ms = now_ms();
+    HIP_TRY(ctx, hipEventRecord(pe.start, ctx->stream));
+    return JH_OK;
+}
+static int prof_query_end(jh_ctx* ctx, ProfEntry& pe) {
+    if (!ctx->profiling) return JH_OK;
+    HIP_TRY(ctx, hipEventRecord(pe.stop, ctx->stream));
+    pe.cpu_end_ms = now_ms();
+    ctx->prof.push_back(pe);
+    return JH_OK;
+}
+
+static int launch_result(jh_ctx* ctx, int stage, JhResult r) {
+    switch (r) {
+        case JH_L_OK: return JH_OK;
+        case JH_L_SCRATCH:
+            return fail(ctx, JH_ERR_OOM, ctx->capturing ? "a scratch array would have to grow during graph capture: run the recording once eagerly first"
+                                                        : "scratch allocation failed");
+        default: return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + jh_stage_name(stage));
+    }
 }
 
 static int dispatch_common(jh_ctx* ctx, int stage, uint32_t gx, uint32_t gy, uint32_t gz, const uint32_t* indirect, const jh_binding* bindings,
@@ -742,181 +889,39 @@ static int dispatch_common(jh_ctx* ctx, int stage, uint32_t gx, uint32_t gy, uin
     std::vector<JhBound> b, images;
     int rc = resolve_bindings(ctx, bindings, n_bindings, b, images);
     if (rc) return rc;
-    {   // the launchers read these slots as fixed structs: refuse buffers that cannot hold them
-        const StageContract& sc = kContract[stage];
-        if ((int)b.size() < sc.n_min) return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + jh_stage_name(stage) + ": too few");
-        auto too_small = [&](int slot, uint64_t need) { return slot >= 0 && (b[slot].ptr == nullptr || b[slot].size < need); };
-        if (too_small(sc.cfg, sizeof(JlConfig)) || too_small(sc.bump, sizeof(JlBump)) || too_small(sc.indirect, 12))
-            return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + jh_stage_name(stage) + ": config / bump / indirect buffer too small");
-    }
-    // Hold back the small stages a following stage can absorb (see Deferred); absorb or launch what is being held.
-    // (not while profiling: a held-back stage's query would bracket nothing and its work would be charged to the stage that absorbs
-    // it -- with the profiler on every command is launched as recorded and every query times its own stage)
-    // (pathtag_reduce2: its consumer pathtag_scan1 redoes its sums in passing if it runs at most 16 workgroups itself --
-    // PT_ABSORB_MAX in kernels_scan.hip; the reference always dispatches reduce2 with 256, one thread per entry of reduced2)
-    // (the last pathtag scan: flatten's classification kernel, which reads every tag word and its monoid back, produces the monoids
-    // in passing instead -- k_pathtag_scan_classify)
-    const bool is_last_scan = (stage == JH_PATHTAG_SCAN_SMALL || stage == JH_PATHTAG_SCAN_LARGE) && gx > 0u && b.size() >= 4;
-    const bool deferrable = !ctx->profiling && (stage == JH_BBOX_CLEAR || stage == JH_PATH_COUNT_SETUP || stage == JH_PATH_TILING_SETUP ||
-                                                (stage == JH_PATHTAG_REDUCE2 && gx > 0u && gx <= 256u && b.size() >= 2) || is_last_scan);
-    uint32_t absorb = 0u;
-    JhBound extra;
-    std::memset(&extra, 0, sizeof extra);
-    if (deferrable) {
-        // (only one kind of thing waits at a time, except what waits for flatten: the last pathtag scan, bbox_clear, Clear(bump) --
-        // one of each)
-        for (const Deferred& d : ctx->deferred) {
-            const bool d_scan = !d.is_clear && (d.stage == JH_PATHTAG_SCAN_SMALL || d.stage == JH_PATHTAG_SCAN_LARGE);
-            const bool joins = (stage == JH_BBOX_CLEAR && (d.is_clear || d_scan)) || (is_last_scan && (d.is_clear || d.stage == JH_BBOX_CLEAR));
-            if (!joins) { JH_FLUSH(ctx); break; }
-        }
-    } else if (!ctx->deferred.empty()) {
-        bool all = true;
-        for (const Deferred& d : ctx->deferred) {
-            bool ok = false;
-            // (a dispatch with no workgroups launches nothing that could do the held-back work in passing -- an empty scene's
-            // flatten, renderer.cpp: flatten_wgs = 0 -- so bbox_clear and Clear(bump) run as recorded: ADVICE r03)
-            if (stage == JH_FLATTEN && b.size() >= 6 && gx > 0u) {
-                if (d.is_clear) ok = d.clear_ptr == b[4].ptr && d.clear_bytes == b[4].size && b[4].size == sizeof(JlBump);
-                else if (d.stage == JH_BBOX_CLEAR) ok = d.b[0].ptr == b[0].ptr && d.b[1].ptr == b[3].ptr && d.b[1].size == b[3].size;
-                else  // the last pathtag scan: same config and scene, its output is the tag monoids flatten reads, and its threads
-                      // (one per tag word = four tag bytes) cover flatten's (one per tag byte)
-                    ok = (d.stage == JH_PATHTAG_SCAN_SMALL || d.stage == JH_PATHTAG_SCAN_LARGE) && d.b.size() >= 4 && d.b[0].ptr == b[0].ptr &&
-                         d.b[1].ptr == b[1].ptr && d.b[1].size == b[1].size && d.b[3].ptr == b[2].ptr && d.b[3].size == b[2].size &&
-                         (uint64_t)d.gx * 4u >= (uint64_t)gx && d.gy <= 1u && d.gz <= 1u;
-            } else if (stage == JH_PATHTAG_SCAN1 && b.size() >= 3) {
-                ok = !d.is_clear && d.stage == JH_PATHTAG_REDUCE2 && gx > 0u && gx <= 16u && gx <= d.gx && d.b[0].ptr == b[0].ptr &&
-                     d.b[0].size == b[0].size && d.b[1].ptr == b[1].ptr && d.b[1].size == b[1].size;
-            } else if (stage == JH_PATH_COUNT && indirect && b.size() >= 6) {
-                ok = !d.is_clear && d.stage == JH_PATH_COUNT_SETUP && d.b[0].ptr == b[1].ptr && d.b[1].ptr == (void*)indirect;
-            } else if (stage == JH_PATH_TILING && indirect && b.size() >= 6) {
-                ok = !d.is_clear && d.stage == JH_PATH_TILING_SETUP && d.b[0].ptr == b[0].ptr && d.b[1].ptr == (void*)indirect;
-            }
-            all = all && ok;
-        }
-        if (all) {
-            for (const Deferred& d : ctx->deferred) {
-                if (d.is_clear) absorb |= JH_ABSORB_BUMP_CLEAR;
-                else if (d.stage == JH_BBOX_CLEAR) absorb |= JH_ABSORB_BBOX_CLEAR;
-                else if (d.stage == JH_PATHTAG_SCAN_SMALL || d.stage == JH_PATHTAG_SCAN_LARGE) {
-                    absorb |= JH_ABSORB_PATHTAG_SCAN;
-                    extra = d.b[2];
-                    extra.width = d.gx;
-                    extra.height = d.stage == JH_PATHTAG_SCAN_SMALL ? 1u : 0u;
-                } else {
-                    absorb |= JH_ABSORB_SETUP;
-                    if (d.stage == JH_PATH_TILING_SETUP) extra = d.b[2];
-                    if (d.stage == JH_PATHTAG_REDUCE2) extra.size = d.gx;  // (entries of reduced2 the held-back dispatch writes)
-                }
-            }
-            ctx->deferred.clear();
-        } else {
-            JH_FLUSH(ctx);
-        }
-    }
-    JhLaunch L;
-    L.stream = ctx->stream;
-    L.scratch = &ctx->scratch;
-    L.gx = gx; L.gy = gy; L.gz = gz;
-    L.absorb = absorb;
-    L.extra = extra;
-    L.b = b.data();
-    L.nb = (int)b.size();
+    rc = check_contract(ctx, stage, b, indirect);
+    if (rc) return rc;
+    // held back: launched by the stage it waits for, or as recorded by the next flush
+    const HeldKind kind = held_kind_of_dispatch(ctx, stage, gx);
+    if (kind != HELD_NONE) return hold_back(ctx, Held{kind, stage, gx, gy, gz, std::move(b)});
+    JhLaunch L = make_launch(ctx, gx, gy, gz, b);
+    if (!absorb_all(ctx, stage, gx, indirect, b, &L.absorbed)) JH_FLUSH(ctx);
     L.images = images.data();
     L.n_images = (int)images.size();
     L.indirect = indirect;
-    L.num_cus = ctx->num_cus;
-    L.cfg_host = nullptr;
-    L.band_row0 = ctx->band_row0;
-    L.band_row1 = ctx->band_row1;
-    L.clip_depth_hint = ctx->clip_depth_hint;
-    L.hint_overflow = ctx->hint_overflow;
-    L.debug_flatten = ctx->debug_flatten;
-    L.image_table = nullptr;
     if ((int)images.size() > JH_FINE_INLINE_IMAGES && stage >= JH_FINE_AREA) {
-        // More images than fit in the kernel arguments: fine indexes a device table of descriptors (the reference binds
-        // an array of up to 2048 textures, wgpu.go:278).  The table is re-uploaded only when the bound set changes.
-        std::vector<JhImageDesc> t(images.size());
-        for (size_t i = 0; i < images.size(); i++) {
-            t[i].ptr = images[i].ptr; t[i].width = images[i].width; t[i].height = images[i].height;
-            t[i].srgb = images[i].format == JL_RGBA8_SRGB ? 1u : 0u; t[i].pad = 0u;
-        }
-        const bool same = t.size() == ctx->image_table_host.size() &&
-                          std::memcmp(t.data(), ctx->image_table_host.data(), t.size() * sizeof(JhImageDesc)) == 0;
-        if (!same) {
-            if (ctx->capturing) return fail(ctx, JH_ERR_INVALID, "fine: the image table changed during graph capture (run the recording once eagerly first)");
-            const uint64_t bytes = t.size() * sizeof(JhImageDesc);
-            if (bytes > ctx->image_table_cap) {
-                void* np = nullptr;
-                if (hipMalloc(&np, pool_size_class(bytes)) != hipSuccess) return fail(ctx, JH_ERR_OOM, "fine: image table allocation failed");
-                if (ctx->image_table) ctx->scratch.retired.push_back(ctx->image_table);
-                ctx->image_table = np;
-                ctx->image_table_cap = pool_size_class(bytes);
-                ctx->generation++;
-            }
-            void* src = stage_copy(ctx, t.data(), bytes);
-            if (!src) return fail(ctx, JH_ERR_OOM, "fine: pinned staging allocation failed");
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->image_table, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-            ctx->image_table_host = t;
-        }
-        L.image_table = (const JhImageDesc*)ctx->image_table;
+        rc = bind_image_table(ctx, images, &L.image_table);
+        if (rc) return rc;
     }
     if (n_bindings > 0 && bindings[0].kind == JH_BIND_BUFFER) {
         auto sh = ctx->config_shadow.find(bindings[0].id);
         if (sh != ctx->config_shadow.end()) L.cfg_host = &sh->second;
     }
-    // binning and coarse address a bin by its index in a 256-entry table (one per lane of the 256-thread workgroup:
-    // binning.wgsl:52,131; coarse.wgsl:153-176): a target of more than 256 bins of 256 x 256 px -- beyond 4096 px in a
-    // direction -- silently loses the bins past the 256th in the reference.  Here the dispatch is refused instead.
-    if ((stage == JH_BINNING || stage == JH_COARSE) && L.cfg_host) {
-        const uint64_t wb = (L.cfg_host->width_in_tiles + 15u) / 16u, hb = (L.cfg_host->height_in_tiles + 15u) / 16u;
-        if (wb * hb > 256u)
-            return fail(ctx, JH_ERR_INVALID, std::string(jh_stage_name(stage)) + ": the target has " + std::to_string(wb * hb) +
-                                                 " bins of 256 x 256 px, the pipeline addresses 256 (at most 4096 x 4096 px or any shape of <= 256 bins)");
-    }
+    rc = check_bin_limit(ctx, stage, L.cfg_host);
+    if (rc) return rc;
     ProfEntry pe;
-    if (ctx->profiling) {
-        auto get_event = [&](hipEvent_t* e) {
-            if (!ctx->free_events.empty()) { *e = ctx->free_events.back(); ctx->free_events.pop_back(); return hipSuccess; }
-            return hipEventCreate(e);
-        };
-        HIP_TRY(ctx, get_event(&pe.start));
-        HIP_TRY(ctx, get_event(&pe.stop));
-        pe.kind = JH_PROF_QUERY;
-        pe.parent = ctx->prof_stack.empty() ? -1 : ctx->prof_stack.back();
-        pe.stage = stage;
-        pe.label = jh_stage_name(stage);  // ProfilerGroup.Compute(arena, shader.Label), wgpu.go:486,537
-        pe.cpu_start_ms = now_ms();
-        HIP_TRY(ctx, hipEventRecord(pe.start, ctx->stream));
-    }
-    if (deferrable) {  // held back: launched by the stage it waits for, or as recorded by the next flush
-        Deferred d;
-        d.stage = stage; d.gx = gx; d.gy = gy; d.gz = gz; d.b = b;
-        ctx->deferred.push_back(d);
-        rc = 0;
-    } else {
-        rc = launch_stage(stage, L);
-        if (rc == -9) {
-            if (ctx->profiling) { ctx->free_events.push_back(pe.start); ctx->free_events.push_back(pe.stop); }
-            return fail(ctx, JH_ERR_UNSUPPORTED, std::string("stage not implemented: ") + jh_stage_name(stage));
-        }
-    }
-    if (ctx->profiling) {
-        HIP_TRY(ctx, hipEventRecord(pe.stop, ctx->stream));
-        pe.cpu_end_ms = now_ms();
-        ctx->prof.push_back(pe);
-    }
-    if (rc == -5)
-        return fail(ctx, JH_ERR_OOM, ctx->capturing ? "a scratch array would have to grow during graph capture: run the recording once eagerly first"
-                                                    : "scratch allocation failed");
-    if (rc) return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + jh_stage_name(stage));
+    rc = prof_query_begin(ctx, pe, stage, jh_stage_name(stage));  // ProfilerGroup.Compute(arena, shader.Label), wgpu.go:486,537
+    if (rc) return rc;
+    const JhResult res = kStages[stage].launch(L);
+    rc = prof_query_end(ctx, pe);
+    if (rc) return rc;
+    rc = launch_result(ctx, stage, res);
+    if (rc) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, jh_stage_name(stage));
     for (int i = 0; i < n_bindings; i++)
-        if (bindings[i].kind == JH_BIND_IMAGE) {
-            auto it = ctx->images.find(bindings[i].id);
-            if (it != ctx->images.end()) it->second.stored = true;
-        }
+        if (bindings[i].kind == JH_BIND_IMAGE)
+            if (Alloc* im = find_alloc(ctx->images, bindings[i].id)) im->stored = true;
     return JH_OK;
 }
 
@@ -926,10 +931,10 @@ int jh_dispatch(jh_ctx* ctx, int stage, uint32_t gx, uint32_t gy, uint32_t gz, c
 
 int jh_dispatch_indirect(jh_ctx* ctx, int stage, uint64_t indirect_buffer_id, uint64_t offset, const jh_binding* bindings, int n_bindings) {
     if (!ctx) return JH_ERR_INVALID;
-    auto it = ctx->buffers.find(indirect_buffer_id);
-    if (it == ctx->buffers.end()) return fail(ctx, JH_ERR_INVALID, "dispatch_indirect: unknown indirect buffer");
-    if (offset + 12 > it->second.size || (offset & 3)) return fail(ctx, JH_ERR_INVALID, "dispatch_indirect: bad offset");
-    return dispatch_common(ctx, stage, 0, 1, 1, (const uint32_t*)((char*)it->second.ptr + offset), bindings, n_bindings);
+    const Alloc* a = find_alloc(ctx->buffers, indirect_buffer_id);
+    if (!a) return fail(ctx, JH_ERR_INVALID, "dispatch_indirect: unknown indirect buffer");
+    if (offset + 12 > a->size || (offset & 3)) return fail(ctx, JH_ERR_INVALID, "dispatch_indirect: bad offset");
+    return dispatch_common(ctx, stage, 0, 1, 1, (const uint32_t*)((char*)a->ptr + offset), bindings, n_bindings);
 }
 
 // ---- hipGraph capture ----
@@ -947,7 +952,7 @@ int jh_graph_end(jh_ctx* ctx, void** graph_exec) {
     if (!ctx || !graph_exec) return JH_ERR_INVALID;
     *graph_exec = nullptr;
     hipGraph_t graph = nullptr;
-    const int frc = flush_deferred(ctx);  // held-back commands belong to the captured frame
+    const int frc = flush_held(ctx);  // held-back commands belong to the captured frame
     ctx->capturing = false;
     // Nothing ran: the device holds what it held when the capture began, and so must the host's picture of it (a launcher that
     // found a flag down recorded its fill INTO the graph and raised the flag -- the fill has not happened).
@@ -997,9 +1002,7 @@ int jh_graph_launch(jh_ctx* ctx, void* graph_exec) {
     // (a stage failed half-way) or the scratch was poisoned.  Zero them here -- the eager path's own remedy -- then replay.
     const uint32_t dirty = g->assumes_clean & ~ctx->scratch.clean_flags;
     if (dirty) {
-        static const struct { uint32_t flag; int slot; } kSlots[] = {
-            {JH_CLEAN_FL_CTR, JH_SCR_FL_CTR}, {JH_CLEAN_BD_CTR, JH_SCR_BD_CTR}, {JH_CLEAN_SCAN, JH_SCR_SCAN_TMP}, {JH_CLEAN_PC_TOT, JH_SCR_PC_TOT}};
-        for (const auto& k : kSlots)
+        for (const auto& k : kSelfCleaned)
             if ((dirty & k.flag) && ctx->scratch.ptr[k.slot] && ctx->scratch.cap[k.slot])
                 HIP_TRY(ctx, hipMemsetAsync(ctx->scratch.ptr[k.slot], 0, ctx->scratch.cap[k.slot], ctx->stream));
         ctx->scratch.clean_flags |= dirty;
@@ -1134,9 +1137,9 @@ int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t d
             int surface_format) {
     if (!ctx) return JH_ERR_INVALID;
     // every check comes before anything is enqueued: a refused call touches no memory
-    auto it = ctx->images.find(src_image_id);
-    if (it == ctx->images.end()) return fail(ctx, JH_ERR_INVALID, "jh_blit: unknown source image id");
-    const Alloc& a = it->second;
+    const Alloc* src = find_alloc(ctx->images, src_image_id);
+    if (!src) return fail(ctx, JH_ERR_INVALID, "jh_blit: unknown source image id");
+    const Alloc& a = *src;
     if (a.format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_blit: the source is not an RGBA16F image");
     if (a.width != width || a.height != height) return fail(ctx, JH_ERR_INVALID, "jh_blit: size differs from the source image");
     if (!dst_device_ptr) return fail(ctx, JH_ERR_INVALID, "jh_blit: null destination");
@@ -1149,29 +1152,14 @@ int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t d
     const uint64_t h = height;
     const uint32_t row0 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row0 * 256u, h);
     const uint32_t row1 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row1 * 256u, h);
-    ProfEntry pe;
-    if (ctx->profiling) {  // a query of its own (the reference's pgroup.Render(arena, "blit")), not a stage: stage = -1
-        auto get_event = [&](hipEvent_t* e) {
-            if (!ctx->free_events.empty()) { *e = ctx->free_events.back(); ctx->free_events.pop_back(); return hipSuccess; }
-            return hipEventCreate(e);
-        };
-        HIP_TRY(ctx, get_event(&pe.start));
-        HIP_TRY(ctx, get_event(&pe.stop));
-        pe.kind = JH_PROF_QUERY;
-        pe.parent = ctx->prof_stack.empty() ? -1 : ctx->prof_stack.back();
-        pe.stage = -1;
-        pe.label = "blit";
-        pe.cpu_start_ms = now_ms();
-        HIP_TRY(ctx, hipEventRecord(pe.start, ctx->stream));
-    }
+    ProfEntry pe;  // a query of its own (the reference's pgroup.Render(arena, "blit")), not a stage
+    int prc = prof_query_begin(ctx, pe, -1, "blit");
+    if (prc) return prc;
     // a source that was never written reads as transparent black, like a fresh texture
     const int rc = jh_blit_launch(ctx->stream, (a.written || a.stored) ? a.ptr : nullptr, dst_device_ptr, dst_pitch_bytes, width, row0,
                                   row1 > row0 ? row1 : row0, surface_format, ctx->num_cus);
-    if (ctx->profiling) {
-        HIP_TRY(ctx, hipEventRecord(pe.stop, ctx->stream));
-        pe.cpu_end_ms = now_ms();
-        ctx->prof.push_back(pe);
-    }
+    prc = prof_query_end(ctx, pe);
+    if (prc) return prc;
     if (rc == -1) return fail(ctx, JH_ERR_INVALID, "jh_blit: image too large for one launch");
     if (rc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_blit: launch failed: ") + hipGetErrorString(hipGetLastError()));
     return JH_OK;

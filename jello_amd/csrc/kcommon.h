@@ -236,14 +236,82 @@ struct JhImageDesc {
     uint32_t pad;
 };
 
+// ---- scratch arrays ----
+// Per-context device arrays the launchers keep between kernels of a stage.  The slot NUMBERS are fixed: every slot's array
+// starts slot * JH_SCR_SKEW bytes into its allocation, a measured tuning of k_flatten_lines (jh_scratch_get).  A..J are
+// shared between stages on purpose -- a stage is done with its arrays when the next one starts, and the big ones of
+// flatten sit where path_count's do, so a frame allocates them once:
+//
+//   slot      flatten           binning     tile_alloc  backdrop_dyn  path_count                 coarse               fine
+//   SCAN_TMP  (jh_scan_u32's control words and tile descriptors, whichever stage scans: flatten, path_count)   self-cleaned
+//   A         counts / slot     wg totals   counts      wide list     counts / line              counts + wg totals
+//   B         bases / slot                  wg totals                 bases / line               scratch PTCL (clips)
+//   C         FlTemp.sinfo                                            tile_of / crossing         relocation side arrays
+//   D         FlTemp.recs                                             list / crossing                                 clip levels
+//   E                                                                 list_base / tile
+//   F         item list                                               keys / crossing
+//   G                                                                 dense tiles
+//   H         -- unused --
+//   I                                                                 path ranges + gate
+//   J         -- unused --
+//   FL_CTR    list counters / chunk fills                                                                            self-cleaned
+//   BD_CTR                                              wide counter  (zeroed by k_pc_count)                         self-cleaned
+//   PC_TOT                                                            crossings per path                             self-cleaned
+enum {
+    JH_SCR_SCAN_TMP = 0,
+    JH_SCR_A = 1,
+    JH_SCR_B = 2,
+    JH_SCR_C = 3,
+    JH_SCR_D = 4,
+    JH_SCR_E = 5,
+    JH_SCR_F = 6,
+    JH_SCR_G = 7,
+    JH_SCR_H = 8,  // unused
+    JH_SCR_I = 9,
+    JH_SCR_J = 10,  // unused
+    JH_SCR_FL_CTR = 11,  // flatten's list counters / chunk fills: NOT shared with other stages (they survive between frames)
+    JH_SCR_BD_CTR = 12,  // backdrop's wide-row counter: likewise
+    JH_SCR_PC_TOT = 13,  // path_count's crossings per path (atomic sums): likewise, zeroed by the stage's last kernel
+    JH_SCR_COUNT = 14
+};
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
+uint64_t jh_scratch_cap(JhScratch* s, int slot);               // bytes the slot holds (>= what was last asked for)
+// Self-cleaned counters (SCAN_TMP, FL_CTR, BD_CTR, PC_TOT): counters a stage needs zeroed when it starts are zeroed by the
+// LAST kernel that runs before without using them (the stage's own last kernel of the frame before, or a kernel of the
+// stage in front) instead of by a fill launch of ~4.4 us; a host-side flag per counter says whether that has happened since
+// the counter was last used.  A stage that finds its flag down (first frame, an aborted frame, a stage run on its own, a
+// scratch reallocation) fills as before.
+// The slot <-> flag table (JH_CLEAN_*) is the allocator's, in jello_hip.cpp; launchers see the two calls below.
+//   jh_scratch_acquire: jh_scratch_get + zero the first min(fill_bytes, capacity) bytes on `stream` if the flag is down;
+//                       lowers the flag (the counters are in use).  nullptr, and nothing else done, on OOM.
+//   jh_scratch_left_clean: a kernel that zeroes the counters again has been enqueued -- raises the flag.
+#define JH_FILL_CAPACITY (~0ull)
+void* jh_scratch_acquire(JhScratch* s, int slot, uint64_t bytes, uint64_t fill_bytes, hipStream_t stream);
+void jh_scratch_left_clean(JhScratch* s, int slot);
+
+// What the dispatcher held back in front of this command and the launcher does in passing (jello_hip.cpp, "held-back
+// commands").  All false / zero when nothing was.
+struct JhAbsorbed {
+    bool bbox_clear;    // flatten: bbox_clear
+    bool bump_clear;    // flatten: the recording's Clear(bump)
+    bool pathtag_scan;  // flatten: the last pathtag scan -- the classification kernel produces the tag monoids in passing
+    JhBound scan_reduced;    //   ... its `reduced` binding,
+    uint32_t scan_wgs;       //   its workgroup count,
+    bool scan_small;         //   pathtag_scan_small (else _large)
+    bool reduce2;              // pathtag_scan1: pathtag_reduce2
+    uint32_t reduce2_entries;  //   ... its workgroup count = the entries of reduced2 it would have written
+    bool write_indirect;   // path_count / path_tiling: their setup command -- the kernel writes the indirect count itself
+    JhBound tiling_ptcl;   // path_tiling: path_tiling_setup's ptcl binding (ptcl[0] = ~0 on failure)
+};
+// The same for flatten as the flag word k_flatten_classify takes as a kernel argument (device-visible: the values stay)
+enum { JH_ABSORB_BBOX_CLEAR = 1u, JH_ABSORB_BUMP_CLEAR = 2u, JH_ABSORB_PATHTAG_SCAN = 8u };
 
 struct JhLaunch {
     hipStream_t stream;
     JhScratch* scratch;
     uint32_t gx, gy, gz;
-    const JhBound* b;
+    const JhBound* b;  // at least the stage's minimum binding count (checked by the dispatcher against the stage table)
     int nb;
     const JhBound* images;  // JH_BIND_IMAGE_ARRAY contents for fine
     int n_images;
@@ -255,60 +323,62 @@ struct JhLaunch {
     uint32_t clip_depth_hint;  // jh_set_clip_depth_hint: upper bound of the clip layers' nesting depth, 0 = unknown
     uint32_t* hint_overflow;   // device counter of the blend-stack saves dropped because that hint was too small (or nullptr)
     uint32_t debug_flatten;    // jh_debug_flatten_regions (tests): bit 0 = every wave of k_flatten_items starts in region 0 of the temporary, bit 1 = always 8 regions, bit 2 = batches allocate job by job
-    uint32_t absorb;  // JH_ABSORB_*: held-back commands this stage performs in passing (jello_hip.cpp, Deferred)
-    JhBound extra;    // JH_ABSORB_SETUP of path_tiling: the ptcl buffer of path_tiling_setup (ptcl[0] = ~0 on failure); JH_ABSORB_PATHTAG_SCAN: see there
-};
-enum { JH_ABSORB_BBOX_CLEAR = 1u, JH_ABSORB_BUMP_CLEAR = 2u, JH_ABSORB_SETUP = 4u,
-       // flatten: the last pathtag scan (pathtag_scan_small / _large) was held back; flatten's classification kernel produces the tag
-       // monoids in passing.  L.extra = the scan's `reduced` binding, extra.width = its workgroup count, extra.height = 1: the small variant
-       JH_ABSORB_PATHTAG_SCAN = 8u };
+    JhAbsorbed absorbed;
 
-enum {  // scratch slots
-    JH_SCR_SCAN_TMP = 0,
-    JH_SCR_A = 1,
-    JH_SCR_B = 2,
-    JH_SCR_C = 3,
-    JH_SCR_D = 4,
-    JH_SCR_E = 5,
-    JH_SCR_F = 6,
-    JH_SCR_G = 7,
-    JH_SCR_H = 8,
-    JH_SCR_I = 9,
-    JH_SCR_J = 10,
-    JH_SCR_FL_CTR = 11,  // flatten's list counters / chunk fills: NOT shared with other stages (they survive between frames)
-    JH_SCR_BD_CTR = 12,  // backdrop's wide-row counter: likewise
-    JH_SCR_PC_TOT = 13,  // path_count's crossings per path (atomic sums): likewise, zeroed by the stage's last kernel
-    JH_SCR_COUNT = 14
+    template <typename T> jk::Buf<T> buf(int slot) const { return jk::mkbuf<T>(b[slot].ptr, b[slot].size); }
+    template <typename T> T* ptr(int slot) const { return (T*)b[slot].ptr; }
+    uint32_t cus() const { return (uint32_t)(num_cus > 0 ? num_cus : 256); }
 };
-// Counters a stage needs zeroed when it starts are zeroed by the LAST kernel that runs before without using them (the
-// stage's own last kernel of the frame before, or a kernel of the stage in front) instead of by a fill launch of
-// ~4.4 us; a host-side flag per counter says whether that has happened since the counter was last used.  A stage that
-// finds its flag down (first frame, an aborted frame, a stage run on its own, a scratch reallocation) fills as before.
-enum { JH_CLEAN_FL_CTR = 1u, JH_CLEAN_BD_CTR = 2u, JH_CLEAN_SCAN = 8u, JH_CLEAN_PC_TOT = 16u };
-uint32_t* jh_scratch_flags(JhScratch* s);
-uint64_t jh_scratch_cap(JhScratch* s, int slot);  // bytes the slot holds (>= what was last asked for)
+
+enum JhResult { JH_L_OK = 0, JH_L_BAD_BINDINGS, JH_L_SCRATCH };  // mapped to JH_ERR_* and a message by the dispatcher
 
 // Generic device-side exclusive scan of u32 (stride in words between consecutive inputs).
 // n is read from *n_dev when n_dev != nullptr (clamped to n_max), else n_max.  Writes out[0..n) and
-// *total_dev (if non-null).  Three launches, no inter-workgroup spinning.
-int jh_scan_u32(const JhLaunch& L, const uint32_t* in, uint32_t in_stride, uint32_t* out, uint32_t n_max, const uint32_t* n_dev,
-                uint32_t* total_dev);
+// *total_dev (if non-null).  One launch (decoupled look-back).
+JhResult jh_scan_u32(const JhLaunch& L, const uint32_t* in, uint32_t in_stride, uint32_t* out, uint32_t n_max, const uint32_t* n_dev,
+                     uint32_t* total_dev);
 
+// Binding slots (the WGSL @binding order) of the stages whose bindings the held-back rules compare; the other stages name
+// theirs next to their launcher.
+enum { PR2_REDUCED, PR2_REDUCED2 };                            // pathtag_reduce2
+enum { PS1_REDUCED, PS1_REDUCED2, PS1_OUT };                   // pathtag_scan1
+#define PT_ABSORB_MAX 16u  // the largest grid of pathtag_scan1 that redoes a held-back pathtag_reduce2 in passing (kernels_scan.hip)
+enum { PSC_CFG, PSC_SCENE, PSC_REDUCED, PSC_TM };              // pathtag_scan_small / _large
+enum { BC_CFG, BC_BBOX };                                      // bbox_clear
+enum { FL_CFG, FL_SCENE, FL_TM, FL_BBOX, FL_BUMP, FL_LINES };  // flatten
+enum { PCS_BUMP, PCS_INDIRECT };                               // path_count_setup
+enum { PC_CFG, PC_BUMP, PC_LINES, PC_PATHS, PC_TILES, PC_SEGC };  // path_count
+enum { PTS_BUMP, PTS_INDIRECT, PTS_PTCL };                     // path_tiling_setup
+enum { PT_BUMP, PT_SEGC, PT_LINES, PT_PATHS, PT_TILES, PT_SEGMENTS };  // path_tiling
 
-int jh_launch_pathtag(const JhLaunch& L, int stage);
-int jh_launch_bbox_clear(const JhLaunch& L);
-int jh_launch_flatten(const JhLaunch& L);
-int jh_launch_draw_reduce(const JhLaunch& L);
-int jh_launch_draw_leaf(const JhLaunch& L);
-int jh_launch_clip_reduce(const JhLaunch& L);
-int jh_launch_clip_leaf(const JhLaunch& L);
-int jh_launch_binning(const JhLaunch& L);
-int jh_launch_tile_alloc(const JhLaunch& L);
-int jh_launch_path_count_setup(const JhLaunch& L);
-int jh_launch_path_count(const JhLaunch& L);
-int jh_launch_backdrop_dyn(const JhLaunch& L);
-int jh_launch_coarse(const JhLaunch& L);
-int jh_launch_path_tiling_setup(const JhLaunch& L);
-int jh_launch_path_tiling(const JhLaunch& L);
-int jh_launch_fine_area(const JhLaunch& L);
-int jh_launch_fine_msaa(const JhLaunch& L, int samples);  // 8 or 16
+// The stages in jh_stage order (SURVEY Appendix C = renderer/render.go dispatch order), each named here and nowhere else:
+//   X(name, minimum binding count, slot read as JlConfig, slot read as JlBump, slot written as IndirectCount (-1: none), indirect only)
+// The contract is what the launchers rely on instead of checking themselves (jello_hip.cpp, check_contract); "indirect only": the
+// stage's grid comes from an IndirectCount, jh_dispatch is refused.  jello_hip.cpp builds its stage table -- name, contract,
+// launcher -- from this list, its only caller of the launchers jh_launch_<name>.
+#define JH_STAGE_LIST(X)                          \
+    X(pathtag_reduce, 3, 0, -1, -1, false)        \
+    X(pathtag_reduce2, 2, -1, -1, -1, false)      \
+    X(pathtag_scan1, 3, -1, -1, -1, false)        \
+    X(pathtag_scan_small, 4, 0, -1, -1, false)    \
+    X(pathtag_scan_large, 4, 0, -1, -1, false)    \
+    X(bbox_clear, 2, 0, -1, -1, false)            \
+    X(flatten, 6, 0, 4, -1, false)                \
+    X(draw_reduce, 3, 0, -1, -1, false)           \
+    X(draw_leaf, 7, 0, -1, -1, false)             \
+    X(clip_reduce, 4, -1, -1, -1, false)          \
+    X(clip_leaf, 7, 0, -1, -1, false)             \
+    X(binning, 8, 0, 5, -1, false)                \
+    X(tile_alloc, 6, 0, 3, -1, false)             \
+    X(backdrop_dyn, 4, 0, 1, -1, false)           \
+    X(path_count_setup, 2, -1, 0, 1, false)       \
+    X(path_count, 6, 0, 1, -1, true)              \
+    X(coarse, 9, 0, 7, -1, false)                 \
+    X(path_tiling_setup, 3, -1, 0, 1, false)      \
+    X(path_tiling, 6, -1, 0, -1, true)            \
+    X(fine_area, 7, 0, -1, -1, false)             \
+    X(fine_msaa8, 9, 0, -1, -1, false)            \
+    X(fine_msaa16, 9, 0, -1, -1, false)
+#define JH_DECLARE_LAUNCHER(name, ...) JhResult jh_launch_##name(const JhLaunch& L);
+JH_STAGE_LIST(JH_DECLARE_LAUNCHER)
+#undef JH_DECLARE_LAUNCHER

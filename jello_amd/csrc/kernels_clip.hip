@@ -341,22 +341,18 @@ __global__ __launch_bounds__(BLOCK) void k_clip_leaf(const JlConfig* __restrict_
 
 }  // namespace
 
-// [clip_inp, path_bboxes, reduced(bics), clip_out(els)]
-int jh_launch_clip_reduce(const JhLaunch& L) {
-    if (L.nb < 4) return -1;
-    if (L.gx == 0) return 0;
-    hipLaunchKernelGGL(k_clip_reduce, dim3(L.gx), dim3(BLOCK), 0, L.stream, mkbuf<JlClipInp>(L.b[0].ptr, L.b[0].size),
-                       mkbuf<JlPathBbox>(L.b[1].ptr, L.b[1].size), mkbuf<JlClipBic>(L.b[2].ptr, L.b[2].size),
-                       mkbuf<JlClipEl>(L.b[3].ptr, L.b[3].size));
-    return 0;
+enum { CR_CLIP_INP, CR_PATH_BBOX, CR_BICS, CR_ELS };  // clip_reduce
+JhResult jh_launch_clip_reduce(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    hipLaunchKernelGGL(k_clip_reduce, dim3(L.gx), dim3(BLOCK), 0, L.stream, L.buf<JlClipInp>(CR_CLIP_INP), L.buf<JlPathBbox>(CR_PATH_BBOX),
+                       L.buf<JlClipBic>(CR_BICS), L.buf<JlClipEl>(CR_ELS));
+    return JH_L_OK;
 }
-// [config, clip_inp, path_bboxes, reduced, clip_els, draw_monoids, clip_bboxes]
-int jh_launch_clip_leaf(const JhLaunch& L) {
-    if (L.nb < 7) return -1;
-    if (L.gx == 0) return 0;
-    hipLaunchKernelGGL(k_clip_leaf, dim3(L.gx), dim3(BLOCK), 0, L.stream, (const JlConfig*)L.b[0].ptr, mkbuf<JlClipInp>(L.b[1].ptr, L.b[1].size),
-                       mkbuf<JlPathBbox>(L.b[2].ptr, L.b[2].size), mkbuf<JlClipBic>(L.b[3].ptr, L.b[3].size),
-                       mkbuf<JlClipEl>(L.b[4].ptr, L.b[4].size), mkbuf<JlDrawMonoid>(L.b[5].ptr, L.b[5].size),
-                       mkbuf<Box>(L.b[6].ptr, L.b[6].size));
-    return 0;
+enum { CL_CFG, CL_CLIP_INP, CL_PATH_BBOX, CL_BICS, CL_ELS, CL_DRAW_MONOID, CL_CLIP_BBOX };  // clip_leaf
+JhResult jh_launch_clip_leaf(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    hipLaunchKernelGGL(k_clip_leaf, dim3(L.gx), dim3(BLOCK), 0, L.stream, L.ptr<const JlConfig>(CL_CFG), L.buf<JlClipInp>(CL_CLIP_INP),
+                       L.buf<JlPathBbox>(CL_PATH_BBOX), L.buf<JlClipBic>(CL_BICS), L.buf<JlClipEl>(CL_ELS), L.buf<JlDrawMonoid>(CL_DRAW_MONOID),
+                       L.buf<Box>(CL_CLIP_BBOX));
+    return JH_L_OK;
 }

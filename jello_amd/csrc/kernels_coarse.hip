@@ -1028,28 +1028,27 @@ __global__ __launch_bounds__(JL_WG) void k_coarse_totals(const uint32_t* __restr
 
 }  // namespace
 
-// [config, scene, draw_monoids, bin_headers, info_bin_data, paths, tiles, bump, ptcl]
-int jh_launch_coarse(const JhLaunch& L) {
-    if (L.nb < 9) return -1;
-    if (L.gx == 0 || L.gy == 0) return 0;
+enum { CO_CFG, CO_SCENE, CO_DRAW_MONOID, CO_BIN_HEADER, CO_INFO_BIN_DATA, CO_PATHS, CO_TILES, CO_BUMP, CO_PTCL };  // coarse
+JhResult jh_launch_coarse(const JhLaunch& L) {
+    if (L.gx == 0 || L.gy == 0) return JH_L_OK;
     uint32_t n = L.gx * L.gy * JL_N_TILE;
-    auto cfg = (const JlConfig*)L.b[0].ptr;
-    auto scene = mkbuf<uint32_t>(L.b[1].ptr, L.b[1].size);
-    auto dm = mkbuf<JlDrawMonoid>(L.b[2].ptr, L.b[2].size);
-    auto bh = mkbuf<JlBinHeader>(L.b[3].ptr, L.b[3].size);
-    auto ibd = mkbuf<uint32_t>(L.b[4].ptr, L.b[4].size);
-    auto paths = mkbuf<JlPath>(L.b[5].ptr, L.b[5].size);
-    auto tiles = mkbuf<JlTile>(L.b[6].ptr, L.b[6].size);
-    JlBump* bump = (JlBump*)L.b[7].ptr;
-    auto ptcl = mkbuf<uint32_t>(L.b[8].ptr, L.b[8].size);
+    auto cfg = L.ptr<const JlConfig>(CO_CFG);
+    auto scene = L.buf<uint32_t>(CO_SCENE);
+    auto dm = L.buf<JlDrawMonoid>(CO_DRAW_MONOID);
+    auto bh = L.buf<JlBinHeader>(CO_BIN_HEADER);
+    auto ibd = L.buf<uint32_t>(CO_INFO_BIN_DATA);
+    auto paths = L.buf<JlPath>(CO_PATHS);
+    auto tiles = L.buf<JlTile>(CO_TILES);
+    JlBump* bump = L.ptr<JlBump>(CO_BUMP);
+    auto ptcl = L.buf<uint32_t>(CO_PTCL);
     const bool clips = !(L.cfg_host && L.cfg_host->layout.n_clip == 0u);  // host shadow of the uploaded ConfigUniform
     // workgroups per bin: enough to give every CU COARSE_WG_PER_CU workgroups (the LDS of one allows four per CU)
-    const uint32_t want = (clips ? COARSE_PAR_WG_PER_CU : COARSE_WG_PER_CU) * (uint32_t)(L.num_cus > 0 ? L.num_cus : 256);
+    const uint32_t want = (clips ? COARSE_PAR_WG_PER_CU : COARSE_WG_PER_CU) * L.cus();
     uint32_t split = 1u;
     while (split < COARSE_MAX_SPLIT && L.gx * L.gy * split < want) split *= 2u;
     const uint32_t n_wg = L.gx * L.gy * split;
     uint32_t* scr = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_A, ((uint64_t)n + n_wg) * 4 * 3);
-    if (!scr) return -5;
+    if (!scr) return JH_L_SCRATCH;
     uint32_t *cnt_seg = scr, *cnt_chunk = scr + n, *cnt_blend = scr + 2 * (size_t)n, *wg_tot = scr + 3 * (size_t)n;
     dim3 grid(L.gx, L.gy, split), blk(JL_WG);
     const uint32_t row0 = L.band_row0 < L.gy ? L.band_row0 : L.gy, row1 = L.band_row1 < L.gy ? L.band_row1 : L.gy;
@@ -1070,7 +1069,7 @@ int jh_launch_coarse(const JhLaunch& L) {
         const uint64_t n_blocks = (words + 63u) / 64u, n_aux = (words + 3u) / 4u, n_own = words / JL_PTCL_INCREMENT + 1u;
         const uint64_t bytes = n_blocks * 16u + n_aux * 4u + n_own * 8u + (uint64_t)n * 16u + 256u;
         uint8_t* side = (uint8_t*)jh_scratch_get(L.scratch, JH_SCR_C, bytes);
-        if (!tmp || !side) return -5;
+        if (!tmp || !side) return JH_L_SCRATCH;
         R.masks = (unsigned long long*)side;
         R.owner = (uint2*)(side + n_blocks * 16u);
         R.aux = (uint32_t*)(side + n_blocks * 16u + n_own * 8u);
@@ -1088,19 +1087,19 @@ int jh_launch_coarse(const JhLaunch& L) {
                            (const uint32_t*)wg_tot, n_wg, split, base_seg, base_chunk, base_blend, R.arena_ctr, arena_used,
                            (uint32_t)(words > (uint64_t)cfg_dyn ? words - cfg_dyn : 0u));
         if (grid_w.y != 0u) {
-            const uint32_t rg = (uint32_t)(L.num_cus > 0 ? L.num_cus : 256) * 8u;
+            const uint32_t rg = L.cus() * 8u;
             hipLaunchKernelGGL(k_coarse_relocate, dim3(rg), blk, 0, L.stream, cfg, bump, tmpbuf, ptcl, tiles, (const uint32_t*)cnt_chunk, (const uint32_t*)cnt_blend,
                                (const uint32_t*)base_seg, (const uint32_t*)base_chunk, (const uint32_t*)base_blend, (const uint32_t*)R.end_pos,
                                (const uint2*)R.owner, (const unsigned long long*)R.masks, (const uint32_t*)R.aux, (const uint32_t*)arena_used, row0, row1, n);
         }
-        return 0;
+        return JH_L_OK;
     }
     if (clips) JH_COARSE(0, true, grid, 0u, ptcl); else JH_COARSE(0, false, grid, 0u, ptcl);
     if (grid_w.y == 0u) {  // an empty band: nobody to report the totals (otherwise the write pass's first workgroup does)
         hipLaunchKernelGGL(k_coarse_totals, dim3(1), blk, 0, L.stream, (const uint32_t*)wg_tot, n_wg, bump);
-        return 0;
+        return JH_L_OK;
     }
     if (clips) JH_COARSE(1, true, grid_w, row0, ptcl); else JH_COARSE(1, false, grid_w, row0, ptcl);
 #undef JH_COARSE
-    return 0;
+    return JH_L_OK;
 }

@@ -1805,29 +1805,29 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
 
 }  // namespace
 
-// [config, segments, ptcl, info, blend_spill, output image, gradients image, images[] (, mask_lut for MSAA)]
+// (FN_IMAGES: the placeholder of the image array, whose contents travel in L.images; FN_MASK_LUT: the MSAA stages only)
+enum { FN_CFG, FN_SEGMENTS, FN_PTCL, FN_INFO, FN_BLEND_SPILL, FN_OUTPUT, FN_GRADIENTS, FN_IMAGES, FN_MASK_LUT };
 // aa = 0: fine_area, 8: fine_msaa8, 16: fine_msaa16
-static int launch_fine(const JhLaunch& L, int aa) {
-    if (L.nb < (aa ? 9 : 7)) return -1;
-    if (L.gx == 0 || L.gy == 0) return 0;
-    const uint32_t* mask_lut = aa ? (const uint32_t*)L.b[8].ptr : nullptr;
-    uint32_t mask_lut_n = aa ? (uint32_t)(L.b[8].size / 4) : 0u;
+static JhResult launch_fine(const JhLaunch& L, int aa) {
+    if (L.gx == 0 || L.gy == 0) return JH_L_OK;
+    const uint32_t* mask_lut = aa ? L.ptr<const uint32_t>(FN_MASK_LUT) : nullptr;
+    uint32_t mask_lut_n = aa ? (uint32_t)(L.b[FN_MASK_LUT].size / 4) : 0u;
     if (!mask_lut) mask_lut_n = 0u;
-    auto cfg = (const JlConfig*)L.b[0].ptr;
-    uint32_t segments_n = (uint32_t)(L.b[1].size / sizeof(JlSegment));
-    uint32_t ptcl_n = (uint32_t)(L.b[2].size / 4);
-    uint32_t info_n = (uint32_t)(L.b[3].size / 4);
-    auto spill = mkbuf<V4>(L.b[4].ptr, L.b[4].size);
-    const JhBound& out = L.b[5];
-    const JhBound& grad = L.b[6];
-    if (out.format != JL_RGBA16_FLOAT || !out.ptr) return -1;
+    auto cfg = L.ptr<const JlConfig>(FN_CFG);
+    uint32_t segments_n = (uint32_t)(L.b[FN_SEGMENTS].size / sizeof(JlSegment));
+    uint32_t ptcl_n = (uint32_t)(L.b[FN_PTCL].size / 4);
+    uint32_t info_n = (uint32_t)(L.b[FN_INFO].size / 4);
+    auto spill = L.buf<V4>(FN_BLEND_SPILL);
+    const JhBound& out = L.b[FN_OUTPUT];
+    const JhBound& grad = L.b[FN_GRADIENTS];
+    if (out.format != JL_RGBA16_FLOAT || !out.ptr) return JH_L_BAD_BINDINGS;
     FineImages imgs;
     imgs.n = 0;
     imgs.srgb_mask = 0u;
     imgs.table = nullptr;
     for (int i = 0; i < FINE_MAX_IMAGES; i++) { imgs.px[i] = nullptr; imgs.w[i] = 0; imgs.h[i] = 0; }
     if (L.n_images > FINE_MAX_IMAGES) {
-        if (!L.image_table) return -1;  // the dispatcher builds the table for arrays that do not fit in the arguments
+        if (!L.image_table) return JH_L_BAD_BINDINGS;  // the dispatcher builds the table for arrays that do not fit in the arguments
         imgs.table = L.image_table;
         imgs.n = L.n_images;
     } else {
@@ -1850,8 +1850,8 @@ static int launch_fine(const JhLaunch& L, int aa) {
     // band mode: tile rows of the context's bin rows (a bin row = JL_N_TILE_Y tile rows)
     const uint64_t tr0 = (uint64_t)L.band_row0 * JL_N_TILE_Y, tr1 = (uint64_t)L.band_row1 * JL_N_TILE_Y;
     const uint32_t trow0 = tr0 < L.gy ? (uint32_t)tr0 : L.gy, trow1 = tr1 < L.gy ? (uint32_t)tr1 : L.gy;
-    if (trow1 <= trow0) return 0;
-    const float* seg_ptr = (segments_n != 0u && L.b[1].ptr) ? (const float*)L.b[1].ptr : (const float*)cfg;  // see load_segraw_clamped
+    if (trow1 <= trow0) return JH_L_OK;
+    const float* seg_ptr = (segments_n != 0u && L.b[FN_SEGMENTS].ptr) ? L.ptr<const float>(FN_SEGMENTS) : (const float*)cfg;  // see load_segraw_clamped
     if (seg_ptr == (const float*)cfg) segments_n = 0u;
     FineCfg fc;
     std::memset(&fc, 0, sizeof fc);
@@ -1870,11 +1870,11 @@ static int launch_fine(const JhLaunch& L, int aa) {
         scr_levels = FINE_SCR_LEVELS;
         if (L.clip_depth_hint != 0u) scr_levels = L.clip_depth_hint > FINE_LDS_LEVELS ? std::min<uint32_t>(L.clip_depth_hint - FINE_LDS_LEVELS, FINE_SCR_LEVELS) : 0u;
         clip_scratch = (float4*)jh_scratch_get(L.scratch, JH_SCR_D, (uint64_t)L.gx * (trow1 - trow0) * scr_levels * 4096u);
-        if (!clip_scratch) return -5;
+        if (!clip_scratch) return JH_L_SCRATCH;
     }
 #define JH_FINE_LAUNCH(A, C, P)                                                                                                          \
     hipLaunchKernelGGL((k_fine_area<A, C, P>), dim3((L.gx + FINE_WG_WAVES(C) - 1) / FINE_WG_WAVES(C), trow1 - trow0), dim3(64 * FINE_WG_WAVES(C)), 0, L.stream, cfg, fc, seg_ptr, \
-                       segments_n, (const uint32_t*)L.b[2].ptr, ptcl_n, (const uint32_t*)L.b[3].ptr, info_n, spill, (uint16_t*)out.ptr,         \
+                       segments_n, L.ptr<const uint32_t>(FN_PTCL), ptcl_n, L.ptr<const uint32_t>(FN_INFO), info_n, spill, (uint16_t*)out.ptr,         \
                        out.width, out.height, (const uint16_t*)grad.ptr, grad_h, imgs, L.gx, mask_lut, mask_lut_n, trow0, clip_scratch, scr_levels, L.hint_overflow)
 #define JH_FINE_PICK(A)                                  \
     do {                                                 \
@@ -1888,8 +1888,9 @@ static int launch_fine(const JhLaunch& L, int aa) {
     else JH_FINE_PICK(0);
 #undef JH_FINE_PICK
 #undef JH_FINE_LAUNCH
-    return 0;
+    return JH_L_OK;
 }
 
-int jh_launch_fine_area(const JhLaunch& L) { return launch_fine(L, 0); }
-int jh_launch_fine_msaa(const JhLaunch& L, int samples) { return launch_fine(L, samples); }
+JhResult jh_launch_fine_area(const JhLaunch& L) { return launch_fine(L, 0); }
+JhResult jh_launch_fine_msaa8(const JhLaunch& L) { return launch_fine(L, 8); }
+JhResult jh_launch_fine_msaa16(const JhLaunch& L) { return launch_fine(L, 16); }

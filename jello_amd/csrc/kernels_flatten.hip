@@ -763,7 +763,7 @@ JD Seg load_seg(const Scene& s, uint32_t ix) {
 // The classification: one thread per tag WORD (four tag bytes: the word and its monoid are read once, the bytes' monoids follow from
 // them; up to round 5 a thread took eight tag bytes and fetched word and monoid for each).  SCAN != 0: as an epilogue of the LAST
 // pathtag scan (pathtag_scan.wgsl:24-64 / pathtag_scan_large; the engine holds that dispatch back when flatten follows it,
-// jello_hip.cpp Deferred) -- the thread then HAS the word and its prefix monoid in registers instead of reading them back: one
+// jello_hip.cpp, held-back commands) -- the thread then HAS the word and its prefix monoid in registers instead of reading them back: one
 // launch, 20 us, where pathtag_scan took 4 and the classification 23.  What the scan writes (tag_monoids) and what the
 // classification writes (lists, counters, counts, draw_flags / trans_ix of the path boxes) are the same words either way.
 #ifndef PSC_BLOCKS
@@ -778,7 +778,7 @@ __global__ __launch_bounds__(JL_WG) void k_flatten_classify(const JlConfig* __re
                                                                  uint32_t* __restrict__ bump_words) {
     __shared__ uint32_t sh[20];
     __shared__ uint32_t sh_base[2];
-    // Commands the engine held back for this stage (jello_hip.cpp, Deferred): bbox_clear (bbox_clear.wgsl:13-24; this kernel
+    // Commands the engine held back for this stage (jello_hip.cpp, held-back commands): bbox_clear (bbox_clear.wgsl:13-24; this kernel
     // writes only the draw_flags / trans_ix words of the boxes, the min / max words are first used by k_flatten_bbox) and
     // the recording's Clear(bump) (render.go:237; nothing of flatten touches bump before k_flatten_items).
     if (absorb & JH_ABSORB_BBOX_CLEAR) {
@@ -1734,21 +1734,19 @@ extern "C" int jh_debug_flatten_fast_stats(uint32_t* out8, int reset) {
 }
 #endif
 
-// [config, scene, tag_monoids, path_bboxes, bump, lines]
-int jh_launch_flatten(const JhLaunch& L) {
-    if (L.nb < 6) return -1;
-    if (L.gx == 0) return 0;
+JhResult jh_launch_flatten(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
     uint32_t n_tags = L.gx * JL_WG;
     uint64_t n_slots64 = (uint64_t)n_tags * 3;
-    if (n_slots64 > 0xfffffff0ull) return -1;
+    if (n_slots64 > 0xfffffff0ull) return JH_L_BAD_BINDINGS;
     uint32_t n_slots = (uint32_t)n_slots64;
-    auto cfg = (const JlConfig*)L.b[0].ptr;
-    auto scene = mkbuf<uint32_t>(L.b[1].ptr, L.b[1].size);
-    auto tm = mkbuf<JlTagMonoid>(L.b[2].ptr, L.b[2].size);
-    auto pb = mkbuf<JlPathBbox>(L.b[3].ptr, L.b[3].size);
-    JlBump* bump = (JlBump*)L.b[4].ptr;
-    auto lines = mkbuf<JlLineSoup>(L.b[5].ptr, L.b[5].size);
-    uint32_t cap_blocks = (uint32_t)(L.num_cus > 0 ? L.num_cus : 256) * FL_BLOCKS_PER_CU;
+    auto cfg = L.ptr<const JlConfig>(FL_CFG);
+    auto scene = L.buf<uint32_t>(FL_SCENE);
+    auto tm = L.buf<JlTagMonoid>(FL_TM);
+    auto pb = L.buf<JlPathBbox>(FL_BBOX);
+    JlBump* bump = L.ptr<JlBump>(FL_BUMP);
+    auto lines = L.buf<JlLineSoup>(FL_LINES);
+    uint32_t cap_blocks = L.cus() * FL_BLOCKS_PER_CU;
     uint32_t g = (n_slots + JL_WG - 1) / JL_WG;
     if (g > cap_blocks) g = cap_blocks;
     // The temporary (FlTemp): a slot per line and at most a record per line, K regions of R each; K * R = the line buffer's
@@ -1764,50 +1762,50 @@ int jh_launch_flatten(const JhLaunch& L) {
 #endif
     T.R = (uint32_t)((line_cap + T.K - 1) / T.K) + FL_MAX_GRAB;
     const uint64_t tcap = (uint64_t)T.K * T.R;
-    if (tcap > 0xfffffff0ull) return -1;
+    if (tcap > 0xfffffff0ull) return JH_L_BAD_BINDINGS;
     // (scratch slots are shared with the later stages: the two large arrays sit where path_count keeps its largest ones)
     uint32_t* counts = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_A, (uint64_t)n_slots * 4);
     uint32_t* bases = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_B, (uint64_t)n_slots * 4);
     uint32_t* list = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_F, (uint64_t)n_slots * 4);
     T.sinfo = (uint2*)jh_scratch_get(L.scratch, JH_SCR_C, tcap * sizeof(uint2));
     T.recs = (uint4*)jh_scratch_get(L.scratch, JH_SCR_D, tcap * 64);
-    uint32_t* counters = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_FL_CTR, FL_CTR_WORDS * 4);
-    if (!counts || !bases || !list || !counters || !T.sinfo || !T.recs) return -5;
+    if (!counts || !bases || !list || !T.sinfo || !T.recs) return JH_L_SCRATCH;
+    uint32_t* counters = (uint32_t*)jh_scratch_acquire(L.scratch, JH_SCR_FL_CTR, FL_CTR_WORDS * 4, FL_CTR_WORDS * 4, L.stream);
+    if (!counters) return JH_L_SCRATCH;
     T.ctr = counters;
-    uint32_t* clean = jh_scratch_flags(L.scratch);
-    if ((*clean & JH_CLEAN_FL_CTR) == 0u) (void)hipMemsetAsync(counters, 0, FL_CTR_WORDS * 4, L.stream);
-    *clean &= ~(uint32_t)JH_CLEAN_FL_CTR;
+    // the held-back commands the classification kernel performs in passing, as the flag word it takes (kcommon.h)
+    const JhAbsorbed& A = L.absorbed;
+    const uint32_t absorb = (A.bbox_clear ? JH_ABSORB_BBOX_CLEAR : 0u) | (A.bump_clear ? JH_ABSORB_BUMP_CLEAR : 0u) | (A.pathtag_scan ? JH_ABSORB_PATHTAG_SCAN : 0u);
     {
         const uint32_t n_words = (n_tags + 3u) / 4u;
         uint32_t n_blocks = (n_words + JL_WG - 1u) / JL_WG;  // blocks of 256 tag words
         auto red = mkbuf<JlTagMonoid>(nullptr, 0);
         int scan = 0;
-        if ((L.absorb & JH_ABSORB_PATHTAG_SCAN) != 0u) {
-            // the held-back last pathtag scan rides in the classification (kcommon.h: extra = its `reduced`, width = its workgroups)
-            red = mkbuf<JlTagMonoid>(L.extra.ptr, L.extra.size);
-            n_blocks = L.extra.width;
-            scan = L.extra.height != 0u ? 1 : 2;
+        if (A.pathtag_scan) {  // the held-back last pathtag scan rides in the classification
+            red = mkbuf<JlTagMonoid>(A.scan_reduced.ptr, A.scan_reduced.size);
+            n_blocks = A.scan_wgs;
+            scan = A.scan_small ? 1 : 2;
         }
         const dim3 gsc((n_blocks + PSC_BLOCKS - 1u) / PSC_BLOCKS);
         if (scan == 1)
             hipLaunchKernelGGL(k_flatten_classify<1>, gsc, dim3(JL_WG), 0, L.stream, cfg, scene, red, tm, n_blocks, pb, list, counters, n_slots, n_tags,
-                               counts, L.absorb, (uint32_t*)bump);
+                               counts, absorb, (uint32_t*)bump);
         else if (scan == 2)
             hipLaunchKernelGGL(k_flatten_classify<2>, gsc, dim3(JL_WG), 0, L.stream, cfg, scene, red, tm, n_blocks, pb, list, counters, n_slots, n_tags,
-                               counts, L.absorb, (uint32_t*)bump);
+                               counts, absorb, (uint32_t*)bump);
         else
             hipLaunchKernelGGL(k_flatten_classify<0>, gsc, dim3(JL_WG), 0, L.stream, cfg, scene, red, tm, n_blocks, pb, list, counters, n_slots, n_tags,
-                               counts, L.absorb, (uint32_t*)bump);
+                               counts, absorb, (uint32_t*)bump);
     }
     hipLaunchKernelGGL(k_flatten_items, dim3(g), dim3(JL_WG), 0, L.stream, cfg, scene, tm, pb, (const uint32_t*)list, counters, n_slots, counts,
                        T, L.debug_flatten);
-    int rc = jh_scan_u32(L, counts, 1, bases, n_slots, nullptr, &bump->lines);
+    JhResult rc = jh_scan_u32(L, counts, 1, bases, n_slots, nullptr, &bump->lines);
     if (rc) return rc;
     uint32_t gp = (uint32_t)((tcap + JL_WG - 1) / JL_WG);
-    uint32_t gp_cap = (uint32_t)(L.num_cus > 0 ? L.num_cus : 256) * 8u;
+    uint32_t gp_cap = L.cus() * 8u;
     // k_flatten_lines strides over its work units: exactly the workgroups that are resident together (more would run
     // as a second, partly filled round behind the first)
-    uint32_t gl_cap = (uint32_t)(L.num_cus > 0 ? L.num_cus : 256) * FL_LINES_WAVES_PER_EU;
+    uint32_t gl_cap = L.cus() * FL_LINES_WAVES_PER_EU;
     if (gp > gl_cap) gp = gl_cap;
     hipLaunchKernelGGL(k_flatten_lines, dim3(gp), dim3(JL_WG), 0, L.stream, cfg, scene, (const uint32_t*)counters, T, (const uint32_t*)bases, n_slots, lines);
     // a wave per 64 lines of the buffer's capacity (the line count is only known on the device), at most 16 waves
@@ -1821,6 +1819,6 @@ int jh_launch_flatten(const JhLaunch& L) {
     uint32_t gb = gb64 > gb_max ? gb_max : (uint32_t)(gb64 < 1u ? 1u : gb64);
     hipLaunchKernelGGL(k_flatten_bbox, dim3(gb), dim3(JL_WG), 0, L.stream, cfg, (const JlBump*)bump, (const uint32_t*)bases, n_slots, lines, pb,
                        counters, FL_CTR_WORDS);
-    *clean |= JH_CLEAN_FL_CTR;
-    return 0;
+    jh_scratch_left_clean(L.scratch, JH_SCR_FL_CTR);
+    return JH_L_OK;
 }

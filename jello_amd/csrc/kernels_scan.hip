@@ -156,24 +156,23 @@ __global__ __launch_bounds__(JL_WG) void k_scan_lookback(const uint32_t* __restr
     }
 }
 
-int jh_scan_u32(const JhLaunch& L, const uint32_t* in, uint32_t in_stride, uint32_t* out, uint32_t n_max, const uint32_t* n_dev,
-                uint32_t* total_dev) {
+JhResult jh_scan_u32(const JhLaunch& L, const uint32_t* in, uint32_t in_stride, uint32_t* out, uint32_t n_max, const uint32_t* n_dev,
+                     uint32_t* total_dev) {
     const uint64_t max_tiles = ((uint64_t)n_max + LB_TILE - 1u) / LB_TILE;
     // [ctrl: 256 bytes][one descriptor per tile]: zero between launches (the kernel cleans up after itself; the flag says
     // whether that has happened since the slot was allocated)
-    char* st = (char*)jh_scratch_get(L.scratch, JH_SCR_SCAN_TMP, 256u + (max_tiles + 1u) * 8u);
-    if (!st) return -5;
-    uint32_t* clean = jh_scratch_flags(L.scratch);
-    // (the WHOLE slot: a later scan of the frame may use more descriptors of the same allocation than this one)
-    if ((*clean & JH_CLEAN_SCAN) == 0u) (void)hipMemsetAsync(st, 0, jh_scratch_cap(L.scratch, JH_SCR_SCAN_TMP), L.stream);
-    *clean |= JH_CLEAN_SCAN;
+    // (the WHOLE slot is filled: a later scan of the frame may use more descriptors of the same allocation than this one --
+    // which is also why the flag goes up at once and not behind the kernel)
+    char* st = (char*)jh_scratch_acquire(L.scratch, JH_SCR_SCAN_TMP, 256u + (max_tiles + 1u) * 8u, JH_FILL_CAPACITY, L.stream);
+    if (!st) return JH_L_SCRATCH;
+    jh_scratch_left_clean(L.scratch, JH_SCR_SCAN_TMP);
     if (max_tiles == 0u) {
         if (total_dev) (void)hipMemsetAsync(total_dev, 0, 4, L.stream);
-        return 0;
+        return JH_L_OK;
     }
     hipLaunchKernelGGL(k_scan_lookback, dim3((uint32_t)max_tiles), dim3(JL_WG), 0, L.stream, in, in_stride, out, n_max, n_dev, total_dev,
                        (uint32_t*)st, (unsigned long long*)(st + 256));
-    return 0;
+    return JH_L_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(JL_WG) void k_pathtag_reduce2(Buf<JlTagMonoid> in, 
 // the WGSL's words).  The reference dispatches reduce2 with 256 workgroups whatever the scene (render.go:186-190); the entries
 // of reduced2 behind this grid -- sums over the unused (or absent: robust reads) tail of `reduced` -- are written by workgroup 0,
 // one per thread.  Only for grids of at most PT_ABSORB_MAX workgroups (w * 256 loads per workgroup); the dispatcher decides.
-#define PT_ABSORB_MAX 16u
+// (PT_ABSORB_MAX: kcommon.h, next to the launcher declarations)
 template <bool WITH_REDUCE2>
 __global__ __launch_bounds__(JL_WG) void k_pathtag_scan1(Buf<JlTagMonoid> reduced, Buf<JlTagMonoid> reduced2, Buf<JlTagMonoid> out, uint32_t n_red2) {
     __shared__ uint32_t sh[20];
@@ -252,46 +251,39 @@ __global__ __launch_bounds__(JL_WG) void k_pathtag_scan(const JlConfig* __restri
     if (out.ok(ix)) store_tm(&out.p[ix], monoid_add(prefix, ex));
 }
 
-int jh_launch_pathtag(const JhLaunch& L, int stage) {
-    if (L.gx == 0) return 0;
-    dim3 g(L.gx), blk(JL_WG);
-    switch (stage) {
-        case 0:
-            if (L.nb < 3) return -1;
-            hipLaunchKernelGGL(k_pathtag_reduce, g, blk, 0, L.stream, (const JlConfig*)L.b[0].ptr, mkbuf<uint32_t>(L.b[1].ptr, L.b[1].size),
-                               mkbuf<JlTagMonoid>(L.b[2].ptr, L.b[2].size));
-            break;
-        case 1:
-            if (L.nb < 2) return -1;
-            hipLaunchKernelGGL(k_pathtag_reduce2, g, blk, 0, L.stream, mkbuf<JlTagMonoid>(L.b[0].ptr, L.b[0].size),
-                               mkbuf<JlTagMonoid>(L.b[1].ptr, L.b[1].size));
-            break;
-        case 2:
-            if (L.nb < 3) return -1;
-            // (JH_ABSORB_SETUP here: the dispatcher held pathtag_reduce2 back and found this dispatch to be its consumer)
-            // (L.extra.size: the workgroup count of the held-back dispatch = entries of reduced2 it would have written)
-            if ((L.absorb & JH_ABSORB_SETUP) != 0u)
-                hipLaunchKernelGGL(k_pathtag_scan1<true>, g, blk, 0, L.stream, mkbuf<JlTagMonoid>(L.b[0].ptr, L.b[0].size),
-                                   mkbuf<JlTagMonoid>(L.b[1].ptr, L.b[1].size), mkbuf<JlTagMonoid>(L.b[2].ptr, L.b[2].size), (uint32_t)L.extra.size);
-            else
-                hipLaunchKernelGGL(k_pathtag_scan1<false>, g, blk, 0, L.stream, mkbuf<JlTagMonoid>(L.b[0].ptr, L.b[0].size),
-                                   mkbuf<JlTagMonoid>(L.b[1].ptr, L.b[1].size), mkbuf<JlTagMonoid>(L.b[2].ptr, L.b[2].size), 0u);
-            break;
-        case 3:
-        case 4: {
-            if (L.nb < 4) return -1;
-            auto cfg = (const JlConfig*)L.b[0].ptr;
-            auto scene = mkbuf<uint32_t>(L.b[1].ptr, L.b[1].size);
-            auto red = mkbuf<JlTagMonoid>(L.b[2].ptr, L.b[2].size);
-            auto out = mkbuf<JlTagMonoid>(L.b[3].ptr, L.b[3].size);
-            if (stage == 3) hipLaunchKernelGGL(k_pathtag_scan<true>, g, blk, 0, L.stream, cfg, scene, red, out);
-            else hipLaunchKernelGGL(k_pathtag_scan<false>, g, blk, 0, L.stream, cfg, scene, red, out);
-            break;
-        }
-        default: return -1;
-    }
-    return 0;
+enum { PR_CFG, PR_SCENE, PR_REDUCED };  // pathtag_reduce
+JhResult jh_launch_pathtag_reduce(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    hipLaunchKernelGGL(k_pathtag_reduce, dim3(L.gx), dim3(JL_WG), 0, L.stream, L.ptr<const JlConfig>(PR_CFG), L.buf<uint32_t>(PR_SCENE),
+                       L.buf<JlTagMonoid>(PR_REDUCED));
+    return JH_L_OK;
 }
+JhResult jh_launch_pathtag_reduce2(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    hipLaunchKernelGGL(k_pathtag_reduce2, dim3(L.gx), dim3(JL_WG), 0, L.stream, L.buf<JlTagMonoid>(PR2_REDUCED), L.buf<JlTagMonoid>(PR2_REDUCED2));
+    return JH_L_OK;
+}
+JhResult jh_launch_pathtag_scan1(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    dim3 g(L.gx), blk(JL_WG);
+    auto reduced = L.buf<JlTagMonoid>(PS1_REDUCED), reduced2 = L.buf<JlTagMonoid>(PS1_REDUCED2), out = L.buf<JlTagMonoid>(PS1_OUT);
+    // (the dispatcher held pathtag_reduce2 back and found this dispatch to be its consumer)
+    if (L.absorbed.reduce2) hipLaunchKernelGGL(k_pathtag_scan1<true>, g, blk, 0, L.stream, reduced, reduced2, out, L.absorbed.reduce2_entries);
+    else hipLaunchKernelGGL(k_pathtag_scan1<false>, g, blk, 0, L.stream, reduced, reduced2, out, 0u);
+    return JH_L_OK;
+}
+static JhResult launch_pathtag_scan(const JhLaunch& L, bool small) {
+    if (L.gx == 0) return JH_L_OK;
+    dim3 g(L.gx), blk(JL_WG);
+    auto cfg = L.ptr<const JlConfig>(PSC_CFG);
+    auto scene = L.buf<uint32_t>(PSC_SCENE);
+    auto red = L.buf<JlTagMonoid>(PSC_REDUCED), out = L.buf<JlTagMonoid>(PSC_TM);
+    if (small) hipLaunchKernelGGL(k_pathtag_scan<true>, g, blk, 0, L.stream, cfg, scene, red, out);
+    else hipLaunchKernelGGL(k_pathtag_scan<false>, g, blk, 0, L.stream, cfg, scene, red, out);
+    return JH_L_OK;
+}
+JhResult jh_launch_pathtag_scan_small(const JhLaunch& L) { return launch_pathtag_scan(L, true); }
+JhResult jh_launch_pathtag_scan_large(const JhLaunch& L) { return launch_pathtag_scan(L, false); }
 
 // ------------------------------------------------------------------------------------------------
 // bbox_clear (K5)
@@ -305,11 +297,10 @@ __global__ __launch_bounds__(JL_WG) void k_bbox_clear(const JlConfig* __restrict
         bb.p[ix].y1 = (int32_t)0x80000000;
     }
 }
-int jh_launch_bbox_clear(const JhLaunch& L) {
-    if (L.nb < 2) return -1;
-    if (L.gx == 0) return 0;
-    hipLaunchKernelGGL(k_bbox_clear, dim3(L.gx), dim3(JL_WG), 0, L.stream, (const JlConfig*)L.b[0].ptr, mkbuf<JlPathBbox>(L.b[1].ptr, L.b[1].size));
-    return 0;
+JhResult jh_launch_bbox_clear(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    hipLaunchKernelGGL(k_bbox_clear, dim3(L.gx), dim3(JL_WG), 0, L.stream, L.ptr<const JlConfig>(BC_CFG), L.buf<JlPathBbox>(BC_BBOX));
+    return JH_L_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -491,19 +482,18 @@ __global__ __launch_bounds__(JL_WG) void k_draw_leaf(const JlConfig* __restrict_
     }
 }
 
-int jh_launch_draw_reduce(const JhLaunch& L) {
-    if (L.nb < 3) return -1;
-    if (L.gx == 0) return 0;
-    hipLaunchKernelGGL(k_draw_reduce, dim3(L.gx), dim3(JL_WG), 0, L.stream, (const JlConfig*)L.b[0].ptr, mkbuf<uint32_t>(L.b[1].ptr, L.b[1].size),
-                       mkbuf<JlDrawMonoid>(L.b[2].ptr, L.b[2].size));
-    return 0;
+enum { DR_CFG, DR_SCENE, DR_REDUCED };  // draw_reduce
+JhResult jh_launch_draw_reduce(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    hipLaunchKernelGGL(k_draw_reduce, dim3(L.gx), dim3(JL_WG), 0, L.stream, L.ptr<const JlConfig>(DR_CFG), L.buf<uint32_t>(DR_SCENE),
+                       L.buf<JlDrawMonoid>(DR_REDUCED));
+    return JH_L_OK;
 }
-int jh_launch_draw_leaf(const JhLaunch& L) {
-    if (L.nb < 7) return -1;
-    if (L.gx == 0) return 0;
-    hipLaunchKernelGGL(k_draw_leaf, dim3(L.gx), dim3(JL_WG), 0, L.stream, (const JlConfig*)L.b[0].ptr, mkbuf<uint32_t>(L.b[1].ptr, L.b[1].size),
-                       mkbuf<JlDrawMonoid>(L.b[2].ptr, L.b[2].size), mkbuf<JlPathBbox>(L.b[3].ptr, L.b[3].size),
-                       mkbuf<JlDrawMonoid>(L.b[4].ptr, L.b[4].size), mkbuf<uint32_t>(L.b[5].ptr, L.b[5].size),
-                       mkbuf<JlClipInp>(L.b[6].ptr, L.b[6].size));
-    return 0;
+enum { DL_CFG, DL_SCENE, DL_REDUCED, DL_PATH_BBOX, DL_DRAW_MONOID, DL_INFO, DL_CLIP_INP };  // draw_leaf
+JhResult jh_launch_draw_leaf(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    hipLaunchKernelGGL(k_draw_leaf, dim3(L.gx), dim3(JL_WG), 0, L.stream, L.ptr<const JlConfig>(DL_CFG), L.buf<uint32_t>(DL_SCENE),
+                       L.buf<JlDrawMonoid>(DL_REDUCED), L.buf<JlPathBbox>(DL_PATH_BBOX), L.buf<JlDrawMonoid>(DL_DRAW_MONOID),
+                       L.buf<uint32_t>(DL_INFO), L.buf<JlClipInp>(DL_CLIP_INP));
+    return JH_L_OK;
 }

@@ -369,7 +369,7 @@ __global__ __launch_bounds__(JL_WG) void k_pc_count(const JlBump* __restrict__ b
                                                     uint32_t* __restrict__ zero, uint32_t zero_n, uint32_t* __restrict__ ptotal, uint32_t ptotal_n,
                                                     unsigned long long* __restrict__ bd_ctr,
                                                     JlIndirectCount* __restrict__ setup_out) {  // != nullptr: path_count_setup was held back (jello_hip.cpp,
-                                                                                                // Deferred): this kernel does its work (path_count_setup.wgsl:17-27)
+                                                                                                // held-back commands): this kernel does its work (path_count_setup.wgsl:17-27)
     // (the path ranges, the gate and the dense-tile counter of the later passes start from zero: cleared here, this
     // kernel does not use them, instead of by a separate fill launch; likewise the wide-row counter of the backdrop
     // stage that follows: kcommon.h, JH_CLEAN_*)
@@ -1079,74 +1079,67 @@ __global__ __launch_bounds__(JL_WG) void k_path_tiling(const JlBump* __restrict_
 #endif
 static inline uint32_t stride_grid(const JhLaunch& L, uint64_t n_items, uint32_t per_cu = TILE_GRID_PER_CU) {
     uint64_t blocks = (n_items + JL_WG - 1) / JL_WG;
-    uint64_t cap = (uint64_t)(L.num_cus > 0 ? L.num_cus : 256) * per_cu;
+    uint64_t cap = (uint64_t)L.cus() * per_cu;
     if (blocks > cap) blocks = cap;
     if (blocks == 0) blocks = 1;
     return (uint32_t)blocks;
 }
 
-// [config, draw_monoids, path_bbox, clip_bbox, intersected_bbox, bump, bin_data, bin_header]
-int jh_launch_binning(const JhLaunch& L) {
-    if (L.nb < 8) return -1;
-    if (L.gx == 0) return 0;
+enum { BN_CFG, BN_DRAW_MONOID, BN_PATH_BBOX, BN_CLIP_BBOX, BN_INTERSECTED_BBOX, BN_BUMP, BN_BIN_DATA, BN_BIN_HEADER };  // binning
+JhResult jh_launch_binning(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
     uint32_t* wg_tot = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_A, (uint64_t)L.gx * 4);
-    if (!wg_tot) return -5;
-    auto cfg = (const JlConfig*)L.b[0].ptr;
-    auto dm = mkbuf<JlDrawMonoid>(L.b[1].ptr, L.b[1].size);
-    auto pb = mkbuf<JlPathBbox>(L.b[2].ptr, L.b[2].size);
-    auto cb = mkbuf<Bb4>(L.b[3].ptr, L.b[3].size);
-    auto ib = mkbuf<Bb4>(L.b[4].ptr, L.b[4].size);
-    JlBump* bump = (JlBump*)L.b[5].ptr;
-    auto bd = mkbuf<uint32_t>(L.b[6].ptr, L.b[6].size);
-    auto bh = mkbuf<JlBinHeader>(L.b[7].ptr, L.b[7].size);
+    if (!wg_tot) return JH_L_SCRATCH;
+    auto cfg = L.ptr<const JlConfig>(BN_CFG);
+    auto dm = L.buf<JlDrawMonoid>(BN_DRAW_MONOID);
+    auto pb = L.buf<JlPathBbox>(BN_PATH_BBOX);
+    auto cb = L.buf<Bb4>(BN_CLIP_BBOX);
+    auto ib = L.buf<Bb4>(BN_INTERSECTED_BBOX);
+    JlBump* bump = L.ptr<JlBump>(BN_BUMP);
+    auto bd = L.buf<uint32_t>(BN_BIN_DATA);
+    auto bh = L.buf<JlBinHeader>(BN_BIN_HEADER);
     hipLaunchKernelGGL(k_binning<0>, dim3(L.gx), dim3(JL_WG), 0, L.stream, cfg, dm, pb, cb, ib, bump, bd, bh, wg_tot);
     hipLaunchKernelGGL(k_binning<1>, dim3(L.gx), dim3(JL_WG), 0, L.stream, cfg, dm, pb, cb, ib, bump, bd, bh, wg_tot);
-    return 0;
+    return JH_L_OK;
 }
 
-// [config, scene, draw_bboxes, bump, paths, tiles]
-int jh_launch_tile_alloc(const JhLaunch& L) {
-    if (L.nb < 6) return -1;
-    if (L.gx == 0) return 0;
+enum { TA_CFG, TA_SCENE, TA_DRAW_BBOX, TA_BUMP, TA_PATHS, TA_TILES };  // tile_alloc
+JhResult jh_launch_tile_alloc(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
     uint32_t n = L.gx * JL_WG;
     uint32_t* counts = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_A, (uint64_t)n * 4);
     uint32_t* wg_tot = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_B, (uint64_t)L.gx * 4);
-    if (!counts || !wg_tot) return -5;
-    auto cfg = (const JlConfig*)L.b[0].ptr;
-    auto scene = mkbuf<uint32_t>(L.b[1].ptr, L.b[1].size);
-    auto db = mkbuf<Bb4>(L.b[2].ptr, L.b[2].size);
-    JlBump* bump = (JlBump*)L.b[3].ptr;
-    auto paths = mkbuf<JlPath>(L.b[4].ptr, L.b[4].size);
-    auto tiles = mkbuf<JlTile>(L.b[5].ptr, L.b[5].size);
+    if (!counts || !wg_tot) return JH_L_SCRATCH;
+    auto cfg = L.ptr<const JlConfig>(TA_CFG);
+    auto scene = L.buf<uint32_t>(TA_SCENE);
+    auto db = L.buf<Bb4>(TA_DRAW_BBOX);
+    JlBump* bump = L.ptr<JlBump>(TA_BUMP);
+    auto paths = L.buf<JlPath>(TA_PATHS);
+    auto tiles = L.buf<JlTile>(TA_TILES);
     hipLaunchKernelGGL(k_tile_alloc_count, dim3(L.gx), dim3(JL_WG), 0, L.stream, cfg, scene, db, (const JlBump*)bump, paths, counts, wg_tot);
     hipLaunchKernelGGL(k_tile_alloc_write, dim3(L.gx + stride_grid(L, (uint64_t)tiles.n / 2u + 1u)), dim3(JL_WG), 0, L.stream, cfg, bump, paths, tiles,
                        (const uint32_t*)counts, (const uint32_t*)wg_tot, L.gx);
-    return 0;
+    return JH_L_OK;
 }
 
-// [bump, indirect]
-int jh_launch_path_count_setup(const JhLaunch& L) {
-    if (L.nb < 2) return -1;
-    hipLaunchKernelGGL(k_path_count_setup, dim3(1), dim3(1), 0, L.stream, (const JlBump*)L.b[0].ptr, (JlIndirectCount*)L.b[1].ptr);
-    return 0;
+JhResult jh_launch_path_count_setup(const JhLaunch& L) {
+    hipLaunchKernelGGL(k_path_count_setup, dim3(1), dim3(1), 0, L.stream, L.ptr<const JlBump>(PCS_BUMP), L.ptr<JlIndirectCount>(PCS_INDIRECT));
+    return JH_L_OK;
 }
-// [bump, indirect, ptcl]
-int jh_launch_path_tiling_setup(const JhLaunch& L) {
-    if (L.nb < 3) return -1;
-    hipLaunchKernelGGL(k_path_tiling_setup, dim3(1), dim3(1), 0, L.stream, (const JlBump*)L.b[0].ptr, (JlIndirectCount*)L.b[1].ptr,
-                       mkbuf<uint32_t>(L.b[2].ptr, L.b[2].size));
-    return 0;
+JhResult jh_launch_path_tiling_setup(const JhLaunch& L) {
+    hipLaunchKernelGGL(k_path_tiling_setup, dim3(1), dim3(1), 0, L.stream, L.ptr<const JlBump>(PTS_BUMP), L.ptr<JlIndirectCount>(PTS_INDIRECT),
+                       L.buf<uint32_t>(PTS_PTCL));
+    return JH_L_OK;
 }
 
-// indirect; [config, bump, lines, paths, tile, seg_counts]
-int jh_launch_path_count(const JhLaunch& L) {
-    if (L.nb < 6 || !L.indirect) return -1;
-    auto cfg = (const JlConfig*)L.b[0].ptr;
-    JlBump* bump = (JlBump*)L.b[1].ptr;
-    auto lines = mkbuf<JlLineSoup>(L.b[2].ptr, L.b[2].size);
-    auto paths = mkbuf<JlPath>(L.b[3].ptr, L.b[3].size);
-    auto tile = mkbuf<JlTile>(L.b[4].ptr, L.b[4].size);
-    auto segc = mkbuf<JlSegmentCount>(L.b[5].ptr, L.b[5].size);
+// (indirect only: the stage table refuses a direct dispatch)
+JhResult jh_launch_path_count(const JhLaunch& L) {
+    auto cfg = L.ptr<const JlConfig>(PC_CFG);
+    JlBump* bump = L.ptr<JlBump>(PC_BUMP);
+    auto lines = L.buf<JlLineSoup>(PC_LINES);
+    auto paths = L.buf<JlPath>(PC_PATHS);
+    auto tile = L.buf<JlTile>(PC_TILES);
+    auto segc = L.buf<JlSegmentCount>(PC_SEGC);
     auto ind = (const JlIndirectCount*)L.indirect;
     uint32_t lines_cap = lines.n, seg_cap = segc.n, tiles_cap = tile.n;
     uint32_t* counts = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_A, (uint64_t)lines_cap * 4);
@@ -1159,27 +1152,25 @@ int jh_launch_path_count(const JhLaunch& L) {
     uint32_t n_paths = paths.n;
     const uint32_t dense_cap = seg_cap / PC_DENSE_TILE + 1u;  // tiles with more than PC_DENSE_TILE crossings of a big path
     uint32_t* dense = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_G, (uint64_t)dense_cap * 4);
-    if (!dense) return -5;
+    if (!dense) return JH_L_SCRATCH;
     // [pstart | pend | gate, number of dense tiles ... | crossings per path]: zeroed every frame (by the launch in front of k_pc_count's atomics
     // on the last part, see below) (the variables below keep the names of the path_range parameters)
     uint32_t* prange = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_I, ((uint64_t)n_paths * 3 + 64) * 4);
-    if (!counts || !bases || !tile_of || !list || !list_base || !keys || !kbig || !prange) return -5;
+    if (!counts || !bases || !tile_of || !list || !list_base || !keys || !kbig || !prange) return JH_L_SCRATCH;
     uint32_t *pfirst = prange, *plast = prange + n_paths, *gate = prange + 2 * (size_t)n_paths;
     uint32_t gl = stride_grid(L, lines_cap), gs = stride_grid(L, seg_cap);
     unsigned long long* bd_ctr = (unsigned long long*)jh_scratch_get(L.scratch, JH_SCR_BD_CTR, 64);
-    if (!bd_ctr) return -5;
+    if (!bd_ctr) return JH_L_SCRATCH;
     // crossings per path: atomic sums of k_pc_count, so the array is zero BEFORE that kernel starts -- left so by k_pc_rank_small of
-    // the frame before, or filled here when the flag is down (first frame, regrown or poisoned scratch)
-    uint32_t* ptotal = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_PC_TOT, (uint64_t)n_paths * 4);
-    if (!ptotal) return -5;
+    // the frame before, or filled here when the flag is down (first frame, regrown or poisoned scratch): every word of the slot that
+    // k_pc_rank_small zeroes again (ptotal_words of them)
+    uint32_t* ptotal = (uint32_t*)jh_scratch_acquire(L.scratch, JH_SCR_PC_TOT, (uint64_t)n_paths * 4, 0xffffffffull * 4, L.stream);
+    if (!ptotal) return JH_L_SCRATCH;
     const uint32_t ptotal_words = (uint32_t)std::min<uint64_t>(jh_scratch_cap(L.scratch, JH_SCR_PC_TOT) / 4, 0xffffffffull);
-    uint32_t* clean = jh_scratch_flags(L.scratch);
-    if ((*clean & JH_CLEAN_PC_TOT) == 0u) (void)hipMemsetAsync(ptotal, 0, (size_t)ptotal_words * 4, L.stream);
-    *clean &= ~(uint32_t)JH_CLEAN_PC_TOT;
     hipLaunchKernelGGL(k_pc_count, dim3(gl), dim3(JL_WG), 0, L.stream, (const JlBump*)bump, ind, lines, paths, counts, lines_cap, prange,
-                       n_paths * 2u + 64u, ptotal, n_paths, bd_ctr, (L.absorb & JH_ABSORB_SETUP) ? (JlIndirectCount*)L.indirect : (JlIndirectCount*)nullptr);
-    *jh_scratch_flags(L.scratch) |= JH_CLEAN_BD_CTR;
-    int rc = jh_scan_u32(L, counts, 1, bases, lines_cap, &bump->lines, &bump->seg_counts);
+                       n_paths * 2u + 64u, ptotal, n_paths, bd_ctr, L.absorbed.write_indirect ? (JlIndirectCount*)L.indirect : (JlIndirectCount*)nullptr);
+    jh_scratch_left_clean(L.scratch, JH_SCR_BD_CTR);  // (k_pc_count zeroes backdrop's counter for the stage that follows)
+    JhResult rc = jh_scan_u32(L, counts, 1, bases, lines_cap, &bump->lines, &bump->seg_counts);
     if (rc) return rc;
     const uint32_t *cpf = pfirst, *cpl = plast, *cc = counts, *cb = bases;
     hipLaunchKernelGGL(k_pc_emit, dim3(stride_grid(L, lines_cap, PC_EMIT_GRID_PER_CU)), dim3(JL_WG), 0, L.stream, cfg, (const JlBump*)bump, ind, lines, paths, tile, segc, cb, lines_cap,
@@ -1195,46 +1186,43 @@ int jh_launch_path_count(const JhLaunch& L) {
     sc.dense_cap = dense_cap; sc.blocks = gs;
     hipLaunchKernelGGL(k_pc_rank_small, dim3(gs + stride_grid(L, (uint64_t)n_paths * 64u)), dim3(JL_WG), 0, L.stream, cfg, (const JlBump*)bump, tile,
                        (const uint32_t*)keys, seg_cap, cpf, cpl, cc, cb, n_paths, segc, sc, ptotal, ptotal_words);
-    *clean |= JH_CLEAN_PC_TOT;
+    jh_scratch_left_clean(L.scratch, JH_SCR_PC_TOT);
     hipLaunchKernelGGL(k_pc_rank, dim3(gs), dim3(JL_WG), 0, L.stream, cfg, (const JlBump*)bump, tile, (const uint2*)tile_of, seg_cap,
                        (const uint32_t*)list_base, tiles_cap, (const uint32_t*)list, segc, (const uint32_t*)kbig, (const uint32_t*)gate,
                        (const uint32_t*)dense, dense_cap);
-    return 0;
+    return JH_L_OK;
 }
 
-// [config, bump, paths, tiles]
-int jh_launch_backdrop_dyn(const JhLaunch& L) {
-    if (L.nb < 4) return -1;
-    if (L.gx == 0) return 0;
-    auto paths = mkbuf<JlPath>(L.b[2].ptr, L.b[2].size);
-    auto tiles = mkbuf<JlTile>(L.b[3].ptr, L.b[3].size);
+enum { BD_CFG, BD_BUMP, BD_PATHS, BD_TILES };  // backdrop_dyn
+JhResult jh_launch_backdrop_dyn(const JhLaunch& L) {
+    if (L.gx == 0) return JH_L_OK;
+    auto paths = L.buf<JlPath>(BD_PATHS);
+    auto tiles = L.buf<JlTile>(BD_TILES);
     const uint32_t wide_cap = paths.n;
     // [counter (entries << 40 | rows) | list of (first global row, first tile, width, rows)]
     uint8_t* w = (uint8_t*)jh_scratch_get(L.scratch, JH_SCR_A, 64 + (uint64_t)wide_cap * sizeof(uint4));
-    unsigned long long* wide_ctr = (unsigned long long*)jh_scratch_get(L.scratch, JH_SCR_BD_CTR, 64);
-    if (!w || !wide_ctr) return -5;
+    if (!w) return JH_L_SCRATCH;
+    // (filled only when path_count did not run in front)
+    unsigned long long* wide_ctr = (unsigned long long*)jh_scratch_acquire(L.scratch, JH_SCR_BD_CTR, 64, 8, L.stream);
+    if (!wide_ctr) return JH_L_SCRATCH;
     uint4* wide_list = (uint4*)(w + 64);
-    uint32_t* clean = jh_scratch_flags(L.scratch);
-    if ((*clean & JH_CLEAN_BD_CTR) == 0u) (void)hipMemsetAsync(wide_ctr, 0, 8, L.stream);  // (path_count did not run in front)
-    *clean &= ~(uint32_t)JH_CLEAN_BD_CTR;
     // one thread per row is the better deal only when there are enough paths to fill the device with such threads
     const uint32_t wide_min = L.gx < 64u ? 2u : BD_WIDE;
-    hipLaunchKernelGGL(k_backdrop_dyn, dim3(L.gx), dim3(JL_WG), 0, L.stream, (const JlConfig*)L.b[0].ptr, (const JlBump*)L.b[1].ptr, paths, tiles,
+    hipLaunchKernelGGL(k_backdrop_dyn, dim3(L.gx), dim3(JL_WG), 0, L.stream, L.ptr<const JlConfig>(BD_CFG), L.ptr<const JlBump>(BD_BUMP), paths, tiles,
                        wide_ctr, wide_list, wide_cap, wide_min);
     // (a wave per BD_UNIT rows; a wide path has tens to hundreds of rows)
-    hipLaunchKernelGGL(k_backdrop_wide, dim3(stride_grid(L, (uint64_t)wide_cap * 64u * 64u)), dim3(JL_WG), 0, L.stream, (const JlBump*)L.b[1].ptr, tiles,
+    hipLaunchKernelGGL(k_backdrop_wide, dim3(stride_grid(L, (uint64_t)wide_cap * 64u * 64u)), dim3(JL_WG), 0, L.stream, L.ptr<const JlBump>(BD_BUMP), tiles,
                        (const unsigned long long*)wide_ctr, (const uint4*)wide_list, wide_cap);
-    return 0;
+    return JH_L_OK;
 }
 
-// indirect; [bump, seg_counts, lines, paths, tiles, segments]
-int jh_launch_path_tiling(const JhLaunch& L) {
-    if (L.nb < 6 || !L.indirect) return -1;
-    auto segc = mkbuf<JlSegmentCount>(L.b[1].ptr, L.b[1].size);
+// (indirect only: the stage table refuses a direct dispatch)
+JhResult jh_launch_path_tiling(const JhLaunch& L) {
+    auto segc = L.buf<JlSegmentCount>(PT_SEGC);
     uint32_t g = stride_grid(L, segc.n);
-    hipLaunchKernelGGL(k_path_tiling, dim3(g), dim3(JL_WG), 0, L.stream, (const JlBump*)L.b[0].ptr, (const JlIndirectCount*)L.indirect, segc,
-                       mkbuf<JlLineSoup>(L.b[2].ptr, L.b[2].size), mkbuf<JlPath>(L.b[3].ptr, L.b[3].size),
-                       mkbuf<JlTile>(L.b[4].ptr, L.b[4].size), mkbuf<JlSegment>(L.b[5].ptr, L.b[5].size),
-                       (L.absorb & JH_ABSORB_SETUP) ? (JlIndirectCount*)L.indirect : (JlIndirectCount*)nullptr, mkbuf<uint32_t>(L.extra.ptr, L.extra.size));
-    return 0;
+    const JhBound& ptcl = L.absorbed.tiling_ptcl;  // (of the held-back path_tiling_setup; empty otherwise)
+    hipLaunchKernelGGL(k_path_tiling, dim3(g), dim3(JL_WG), 0, L.stream, L.ptr<const JlBump>(PT_BUMP), (const JlIndirectCount*)L.indirect, segc,
+                       L.buf<JlLineSoup>(PT_LINES), L.buf<JlPath>(PT_PATHS), L.buf<JlTile>(PT_TILES), L.buf<JlSegment>(PT_SEGMENTS),
+                       L.absorbed.write_indirect ? (JlIndirectCount*)L.indirect : (JlIndirectCount*)nullptr, mkbuf<uint32_t>(ptcl.ptr, ptcl.size));
+    return JH_L_OK;
 }

@@ -572,7 +572,7 @@ def test_flatten_regions_fill_up_and_are_left_behind(which, flags):
 @pytest.mark.parametrize("n,size", [(300, 256), (40000, 1024)])
 def test_held_back_commands_and_commands_as_recorded_give_the_same_frame(engine, n, size):
     """The engine holds back the last pathtag scan, bbox_clear, Clear(bump), both setup dispatches and pathtag_reduce2 and lets the
-    stage behind them do their work in passing (jello_hip.cpp, Deferred); with the profiler on every command is launched as
+    stage behind them do their work in passing (jello_hip.cpp, held-back commands); with the profiler on every command is launched as
     recorded (every query must time its own stage).  Both routes against the oracle, and against each other word for word:
     the small scene takes pathtag_scan_small, the large one the three-level path with pathtag_scan_large."""
     s, p = scenes.scene_c3(n, size)
