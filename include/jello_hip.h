@@ -18,6 +18,7 @@
  *   jh_profile_collect_tree       Profiler.Collect (nested results)    profiler.go:304-385
  *   jh_stage                      renderer.FullShaders field order     renderer/render.go:17-43
  *   jh_blit                       RenderToSurface's blit pass          engine/wgpu_engine/lib.go:109-198, 266-333
+ *   jh_pack_tiles / jh_unpack_tiles   (no counterpart: the frame's way off the GPU)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -220,6 +221,60 @@ typedef enum jh_surface_format {
  * from the source's, a pitch below 4 * width, a null dst or an unknown format. */
 int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t dst_pitch_bytes, uint32_t width, uint32_t height,
             int surface_format);
+
+/* ---- tile-packed frame transport (DESIGN.md 5.4 "Tile pack: the format") ----
+ * jh_pack_tiles turns a frame in device memory into only the bytes that have to leave the GPU, jh_unpack_tiles applies such a
+ * pack to a frame on the receiving side.  Lossless; the result is defined byte for byte (tests/tilepack_ref.py restates it).
+ *
+ * A frame is `height` rows of `width` texels of texel_bytes = 4 (an 8-bit surface as jh_blit writes it) or 8 (the RGBA16F
+ * target), rows `pitch` bytes apart.  Texels are opaque bit patterns: equal means equal bytes (NaNs and -0 are just patterns).
+ * Tiles are 16 x 16 texels, tiles_x = ceil(width / 16), tiles_y = ceil(height / 16), tile index t = ty * tiles_x + tx; only
+ * the texels of a tile that lie inside the frame take part in a comparison.  An optional reference frame has the same width,
+ * height and texel size and a pitch of its own.  Class of a tile, in this order of precedence:
+ *   SKIP   a reference is given and every in-frame texel equals the reference's: nothing is stored
+ *   SOLID  all in-frame texels are equal: one texel is stored
+ *   RAW    256 texels are stored, row-major inside the tile, texels outside the frame as zero bytes
+ * A pack is one byte string:
+ *   header   8 x u32, little endian: magic 0x3150544A ("JTP1"), width, height, texel_bytes, n_entries, n_solid, n_raw,
+ *            flags (bit 0: a reference was used)
+ *   entries  n_entries x (u32 word0, u32 word1), ascending tile index: word0 = t | (RAW ? 1u << 31 : 0), word1 = the index
+ *            of the tile's payload within its section (the k-th SOLID entry has k, the k-th RAW entry has k, both from 0)
+ *   solid    n_solid texels
+ *   raw      n_raw blocks of 256 texels
+ * Every section starts at the next multiple of 16 bytes and the padding bytes are zero.  n_entries = n_solid + n_raw, so the
+ * total size follows from the header alone:
+ *   32 + align16(8 n_entries) + align16(texel_bytes n_solid) + 256 texel_bytes n_raw.
+ * jh_pack_bound is the size of the all-RAW pack; no pack is larger (8 bytes per tile, plus the header, over the plain frame
+ * rounded up to whole tiles).  Bytes of the destination beyond the pack's total size are never written.
+ *
+ * Reading a pack (it arrives over a wire: untrusted).  The header is rejected -- the whole pack ignored, counted as one
+ * reject -- unless magic, width, height and texel_bytes are the expected ones, n_solid + n_raw = n_entries, n_entries <= the
+ * tile count, and the total size <= pack_bytes.  An entry is rejected -- ignored, counted -- when its tile index
+ * (word0 & 0x7fffffff) >= the tile count or its word1 >= its section's count.  flags are not interpreted; entries are not
+ * required to ascend, and which of two entries with the same tile index wins is unspecified.
+ *
+ * All pointers are caller-owned device memory (jh_image_device_ptr, jh_buffer_device_ptr, a surface given to jh_blit, another
+ * framework's tensor).  Both calls are stream-ordered on the context's stream, read nothing back and never wait; every count
+ * stays on the device, so both may be captured between jh_graph_begin and jh_graph_end (frame -> blit -> pack as one graph).
+ * Scratch (a byte per tile) comes from the context's arrays and only grows: like a recording, pack a frame of the size once
+ * eagerly before capturing.  jh_pack_tiles is two kernel launches, jh_unpack_tiles one.  Band mode (jh_set_band) affects
+ * neither call: both always cover the whole frame.  With profiling on each call is a query of its own ("pack", "unpack",
+ * stage = -1) in jh_profile_collect_tree, like jh_blit.
+ * jh_pack_tiles writes header, entries, payloads and padding; the result is a pure function of its inputs.
+ * jh_unpack_tiles writes the in-frame texels of the accepted SOLID and RAW entries into dst and touches nothing else: not the
+ * SKIP tiles, not the bytes between width * texel_bytes and the pitch, not the rows below the frame.  It never reads outside
+ * [pack, pack + pack_bytes) or writes outside the frame, whatever the bytes are.
+ * JH_ERR_INVALID, with nothing enqueued: a null src / dst / pack, a texel size other than 4 or 8, width or height 0 (or more than
+ * 2^31 - 1 tiles), a pitch below width * texel_bytes, a pointer or pitch that is not a multiple of texel_bytes,
+ * dst_capacity < jh_pack_bound(...), pack_bytes < 32.  Any other alignment works (a pitch of 4 * width + 4 is legal); the
+ * 16-byte accesses of the fast path need pointers and pitches that are multiples of 16. */
+uint64_t jh_pack_bound(uint32_t width, uint32_t height, uint32_t texel_bytes); /* 0 for a bad texel size */
+int jh_pack_tiles(jh_ctx* ctx, const void* src, uint64_t src_pitch, const void* ref /* or NULL */, uint64_t ref_pitch, uint32_t width,
+                  uint32_t height, uint32_t texel_bytes, void* dst, uint64_t dst_capacity);
+int jh_unpack_tiles(jh_ctx* ctx, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
+                    uint32_t texel_bytes);
+/* What jh_unpack_tiles has rejected since the last reset (entries; a rejected header counts once).  Synchronises the stream. */
+int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

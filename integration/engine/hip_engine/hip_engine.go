@@ -361,6 +361,48 @@ func (e *Engine) RenderToSurface(arena *mem.Arena, enc *encoding.Encoding, surfa
 	return attempts
 }
 
+// packBufferID names the pack's memory on the context for the two downloads of ReadPack (see surfaceTargetID).
+const packBufferID renderer.ResourceID = 1<<63 | 0x7061636b00000000
+
+// PackBound is jh_pack_bound: the size of the largest pack of a width x height frame (0 for a texel size other than 4 or 8).
+func PackBound(width, height, texelBytes uint32) uint64 {
+	return uint64(C.jh_pack_bound(C.uint32_t(width), C.uint32_t(height), C.uint32_t(texelBytes)))
+}
+
+// PackTiles is jh_pack_tiles (the format: include/jello_hip.h): the frame at src -- a surface RenderToSurface wrote
+// (texelBytes 4) or an RGBA16F target (8), rows srcPitch bytes apart -- as a tile pack in dst (capacity >= PackBound), against
+// the reference frame at ref unless that is nil.  Device memory throughout; stream-ordered, waits for nothing.
+func (e *Engine) PackTiles(src unsafe.Pointer, srcPitch uint64, ref unsafe.Pointer, refPitch uint64, width, height, texelBytes uint32,
+	dst unsafe.Pointer, capacity uint64) {
+	e.check(C.jh_pack_tiles(e.ctx, src, C.uint64_t(srcPitch), ref, C.uint64_t(refPitch), C.uint32_t(width), C.uint32_t(height),
+		C.uint32_t(texelBytes), dst, C.uint64_t(capacity)), "pack_tiles")
+}
+
+// UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
+// fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
+func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {
+	e.check(C.jh_unpack_tiles(e.ctx, pack, C.uint64_t(packBytes), dst, C.uint64_t(dstPitch), C.uint32_t(width), C.uint32_t(height),
+		C.uint32_t(texelBytes)), "unpack_tiles")
+}
+
+// ReadPack downloads the pack at pack (capacity bytes of device memory): the 32-byte header, then exactly the total size the
+// header states.  These two small copies are the only host waits of the transport.
+func (e *Engine) ReadPack(pack unsafe.Pointer, capacity uint64) []byte {
+	e.check(C.jh_buffer_import(e.ctx, C.uint64_t(packBufferID), pack, C.uint64_t(capacity)), "buffer_import")
+	defer C.jh_free(e.ctx, C.uint64_t(packBufferID)) // caller-owned memory: forgetting it frees nothing
+	var h [8]uint32
+	e.check(C.jh_download(e.ctx, C.uint64_t(packBufferID), unsafe.Pointer(&h[0]), 0, 32), "download")
+	align16 := func(v uint64) uint64 { return (v + 15) &^ 15 }
+	tb := uint64(h[3])
+	total := 32 + align16(8*uint64(h[4])) + align16(tb*uint64(h[5])) + 256*tb*uint64(h[6])
+	if h[0] != 0x3150544A || (tb != 4 && tb != 8) || uint64(h[5])+uint64(h[6]) != uint64(h[4]) || total > capacity {
+		panic("hip_engine: ReadPack: not a pack, or larger than the capacity given")
+	}
+	out := make([]byte, total)
+	e.check(C.jh_download(e.ctx, C.uint64_t(packBufferID), unsafe.Pointer(unsafe.SliceData(out)), 0, C.uint64_t(total)), "download")
+	return out
+}
+
 // TrimScratch gives the context's internal scratch arrays back (the count / offset arrays of the deterministic allocators,
 // flatten's temporary: they grow on demand and are kept).  For the frame after one that was much larger -- or after a first
 // frame that ran with far more generous BumpSizes than the scenes need.  Waits for the stream.

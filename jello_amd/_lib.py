@@ -168,6 +168,10 @@ def _declare(L):
     L.jl_engine_render_to_surface.argtypes = [vp, vp, ctypes.POINTER(CRenderParams), vp, ctypes.c_uint64, ci, ci,
                                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ci)]
     L.jl_engine_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
+    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+    L.jl_engine_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
+    L.jl_engine_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
+    L.jl_engine_read_pack.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
     L.hip = hip
@@ -196,6 +200,11 @@ def _declare(L):
     hip.jh_image_upload.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci, vp, ctypes.c_uint64]
     hip.jh_image_free.argtypes = [vp, ctypes.c_uint64]
     hip.jh_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
+    hip.jh_pack_bound.restype = u64
+    hip.jh_pack_bound.argtypes = [u32, u32, u32]
+    hip.jh_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
+    hip.jh_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
+    hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]
     hip.jh_graph_begin.argtypes = [vp]

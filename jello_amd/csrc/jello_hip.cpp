@@ -1165,6 +1165,118 @@ int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t d
     return JH_OK;
 }
 
+// ---- tile pack (include/jello_hip.h "tile-packed frame transport"; kernels_pack.hip) ----
+uint32_t jh_pack_groups(uint32_t n_tiles, uint32_t* run_out);
+int jh_pack_launch(hipStream_t stream, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
+                   uint32_t texel_bytes, void* dst, void* cls, void* totals);
+int jh_unpack_launch(hipStream_t stream, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
+                     uint32_t texel_bytes, uint32_t* rejects);
+// the word of the context's counter block (hint_overflow: 64 words, zeroed at creation) that counts what jh_unpack_tiles ignored
+static const uint32_t kUnpackRejectWord = 32u;
+
+uint64_t jh_pack_bound(uint32_t width, uint32_t height, uint32_t texel_bytes) {
+    if (texel_bytes != 4u && texel_bytes != 8u) return 0;
+    const uint64_t tiles = (uint64_t)((width + 15ull) / 16u) * ((height + 15ull) / 16u);
+    return 32u + ((8u * tiles + 15u) & ~15ull) + tiles * 256u * texel_bytes;  // header, entries, no solid texels, all blocks raw
+}
+
+// What both calls ask of a frame: a texel size of 4 or 8, a size that is not empty and whose tile indices fit 31 bits, a pitch
+// that holds a row, pointer and pitch multiples of the texel size.  nullptr when it holds, else what is wrong.
+static const char* pack_frame_error(const void* p, uint64_t pitch, uint32_t width, uint32_t height, uint32_t texel_bytes) {
+    if (texel_bytes != 4u && texel_bytes != 8u) return "texel_bytes is not 4 or 8";
+    if (width == 0u || height == 0u) return "empty frame";
+    if ((uint64_t)((width + 15ull) / 16u) * ((height + 15ull) / 16u) > 0x7fffffffull) return "more than 2^31 - 1 tiles";
+    if (!p) return "null pointer";
+    if (pitch < (uint64_t)width * texel_bytes) return "pitch below width * texel_bytes";
+    if (((uintptr_t)p | pitch) % texel_bytes) return "pointer or pitch is not a multiple of texel_bytes";
+    return nullptr;
+}
+
+// A query of its own around one of the two calls when profiling is on (like jh_blit's: stage = -1, a node of the tree only).
+static int pack_query_begin(jh_ctx* ctx, ProfEntry* pe, const char* label) {
+    if (!ctx->profiling) return JH_OK;
+    auto get_event = [&](hipEvent_t* e) {
+        if (!ctx->free_events.empty()) { *e = ctx->free_events.back(); ctx->free_events.pop_back(); return hipSuccess; }
+        return hipEventCreate(e);
+    };
+    HIP_TRY(ctx, get_event(&pe->start));
+    HIP_TRY(ctx, get_event(&pe->stop));
+    pe->kind = JH_PROF_QUERY;
+    pe->parent = ctx->prof_stack.empty() ? -1 : ctx->prof_stack.back();
+    pe->stage = -1;
+    pe->label = label;
+    pe->cpu_start_ms = now_ms();
+    HIP_TRY(ctx, hipEventRecord(pe->start, ctx->stream));
+    return JH_OK;
+}
+static int pack_query_end(jh_ctx* ctx, ProfEntry* pe) {
+    if (!ctx->profiling) return JH_OK;
+    HIP_TRY(ctx, hipEventRecord(pe->stop, ctx->stream));
+    pe->cpu_end_ms = now_ms();
+    ctx->prof.push_back(*pe);
+    return JH_OK;
+}
+
+int jh_pack_tiles(jh_ctx* ctx, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
+                  uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
+    if (!ctx) return JH_ERR_INVALID;
+    // every check comes before anything is enqueued: a refused call touches no memory
+    if (const char* why = pack_frame_error(src, src_pitch, width, height, texel_bytes)) return fail(ctx, JH_ERR_INVALID, std::string("jh_pack_tiles: source: ") + why);
+    if (ref)
+        if (const char* why = pack_frame_error(ref, ref_pitch, width, height, texel_bytes))
+            return fail(ctx, JH_ERR_INVALID, std::string("jh_pack_tiles: reference: ") + why);
+    if (!dst || (uintptr_t)dst % texel_bytes) return fail(ctx, JH_ERR_INVALID, "jh_pack_tiles: null destination, or not a multiple of texel_bytes");
+    if (dst_capacity < jh_pack_bound(width, height, texel_bytes)) return fail(ctx, JH_ERR_INVALID, "jh_pack_tiles: dst_capacity below jh_pack_bound");
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t n_tiles = ((width + 15u) / 16u) * ((height + 15u) / 16u);
+    void* cls = jh_scratch_get(&ctx->scratch, JH_SCR_H, n_tiles);
+    void* totals = jh_scratch_get(&ctx->scratch, JH_SCR_J, 8ull * jh_pack_groups(n_tiles, nullptr));
+    if (!cls || !totals)
+        return fail(ctx, JH_ERR_OOM, ctx->capturing ? "jh_pack_tiles: a scratch array would have to grow during graph capture: pack a frame of this size once eagerly first"
+                                                    : "jh_pack_tiles: scratch allocation failed");
+    ProfEntry pe;
+    int rc = pack_query_begin(ctx, &pe, "pack");
+    if (rc) return rc;
+    const int lrc = jh_pack_launch(ctx->stream, src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, cls, totals);
+    rc = pack_query_end(ctx, &pe);
+    if (lrc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_pack_tiles: launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+int jh_unpack_tiles(jh_ctx* ctx, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
+                    uint32_t texel_bytes) {
+    if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
+    if (const char* why = pack_frame_error(dst, dst_pitch, width, height, texel_bytes)) return fail(ctx, JH_ERR_INVALID, std::string("jh_unpack_tiles: destination: ") + why);
+    if (!pack || (uintptr_t)pack % texel_bytes) return fail(ctx, JH_ERR_INVALID, "jh_unpack_tiles: null pack, or not a multiple of texel_bytes");
+    if (pack_bytes < 32u) return fail(ctx, JH_ERR_INVALID, "jh_unpack_tiles: pack_bytes below the header's 32");
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ProfEntry pe;
+    int rc = pack_query_begin(ctx, &pe, "unpack");
+    if (rc) return rc;
+    const int lrc = jh_unpack_launch(ctx->stream, pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes, ctx->hint_overflow + kUnpackRejectWord);
+    rc = pack_query_end(ctx, &pe);
+    if (lrc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_unpack_tiles: launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.
+int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset) {
+    if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (count) {
+        HIP_TRY(ctx, hipMemcpyAsync(count, ctx->hint_overflow + kUnpackRejectWord, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (reset) {
+        HIP_TRY(ctx, hipMemsetAsync(ctx->hint_overflow + kUnpackRejectWord, 0, 4, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return JH_OK;
+}
+
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 
 int jh_selftest_math(jh_ctx* ctx, int op, const float* a, const float* b, float* out, uint32_t n) {

@@ -242,7 +242,7 @@ struct JhImageDesc {
 // shared between stages on purpose -- a stage is done with its arrays when the next one starts, and the big ones of
 // flatten sit where path_count's do, so a frame allocates them once:
 //
-//   slot      flatten           binning     tile_alloc  backdrop_dyn  path_count                 coarse               fine
+//   slot      flatten           binning     tile_alloc  backdrop_dyn  path_count                 coarse               fine         jh_pack_tiles
 //   SCAN_TMP  (jh_scan_u32's control words and tile descriptors, whichever stage scans: flatten, path_count)   self-cleaned
 //   A         counts / slot     wg totals   counts      wide list     counts / line              counts + wg totals
 //   B         bases / slot                  wg totals                 bases / line               scratch PTCL (clips)
@@ -251,9 +251,9 @@ struct JhImageDesc {
 //   E                                                                 list_base / tile
 //   F         item list                                               keys / crossing
 //   G                                                                 dense tiles
-//   H         -- unused --
+//   H                                                                                                                               class / tile
 //   I                                                                 path ranges + gate
-//   J         -- unused --
+//   J                                                                                                                               (solid, raw) / workgroup
 //   FL_CTR    list counters / chunk fills                                                                            self-cleaned
 //   BD_CTR                                              wide counter  (zeroed by k_pc_count)                         self-cleaned
 //   PC_TOT                                                            crossings per path                             self-cleaned
@@ -266,9 +266,9 @@ enum {
     JH_SCR_E = 5,
     JH_SCR_F = 6,
     JH_SCR_G = 7,
-    JH_SCR_H = 8,  // unused
+    JH_SCR_H = 8,  // jh_pack_tiles (after the frame: shared with no stage)
     JH_SCR_I = 9,
-    JH_SCR_J = 10,  // unused
+    JH_SCR_J = 10,  // jh_pack_tiles
     JH_SCR_FL_CTR = 11,  // flatten's list counters / chunk fills: NOT shared with other stages (they survive between frames)
     JH_SCR_BD_CTR = 12,  // backdrop's wide-row counter: likewise
     JH_SCR_PC_TOT = 13,  // path_count's crossings per path (atomic sums): likewise, zeroed by the stage's last kernel

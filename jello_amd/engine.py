@@ -26,6 +26,9 @@ class Surface(enum.IntEnum):
 
 # a context buffer that blit / render_to_surface convert into when the caller passes no device pointer (it only grows)
 _SURFACE_BUFFER_ID = 0x5355524641434500
+# context buffers of pack_tiles (the pack, when the caller passes no device pointer) and unpack_tiles (an uploaded pack)
+_PACK_BUFFER_ID = 0x5041434B4F555400
+_UNPACK_BUFFER_ID = 0x5041434B494E0000
 
 
 class CMD:
@@ -205,17 +208,66 @@ class Engine:
         surface = None if out_device_ptr is not None else self._download_surface(params.width, params.height)
         return surface, Recording(self._L, h), dict(zip(names, bump)), attempts.value
 
-    def capture(self, recording, out_device_ptr=None, surface=None):
+    def pack_tiles(self, src_ptr, pitch, width, height, texel_bytes, ref_ptr=None, ref_pitch=None, out_device_ptr=None,
+                   out_capacity=None):
+        """jh_pack_tiles: the frame at the device pointer `src_ptr` (rows `pitch` bytes apart, texels of 4 or 8 bytes) as a
+        tile pack (the format: include/jello_hip.h), against the reference frame at `ref_ptr` if one is given.  Into
+        `out_device_ptr` (`out_capacity` bytes, default and at least tilepack.bound(...); stream-ordered, returns None) or,
+        without a pointer, downloaded (read_pack) and returned as bytes."""
+        bound = int(self.hip.jh_pack_bound(width, height, texel_bytes))
+        if out_device_ptr is not None:
+            dst, cap = out_device_ptr, (bound if out_capacity is None else out_capacity)
+        else:
+            cap = max(bound, 32)
+            self._check(self.hip.jh_buffer_create(self.ctx, _PACK_BUFFER_ID, cap), "buffer_create")
+            dst = self.hip.jh_buffer_device_ptr(self.ctx, _PACK_BUFFER_ID)
+        rp = 0 if ref_ptr is None else (pitch if ref_pitch is None else ref_pitch)
+        self._check(self._L.jl_engine_pack_tiles(self._h, src_ptr, pitch, ref_ptr, rp, width, height, texel_bytes, dst, cap), "pack_tiles")
+        return None if out_device_ptr is not None else self.read_pack(dst, cap)
+
+    def read_pack(self, ptr, capacity):
+        """The pack at the device pointer `ptr` as bytes: downloads its 32-byte header, then exactly its total size."""
+        out = np.empty(capacity, dtype=np.uint8)
+        size = ctypes.c_uint64()
+        self._check(self._L.jl_engine_read_pack(self._h, ptr, capacity, out.ctypes.data, capacity, ctypes.byref(size)), "read_pack")
+        return out[:size.value].tobytes()
+
+    def unpack_tiles(self, pack, dst_ptr, pitch, width, height, texel_bytes):
+        """jh_unpack_tiles: writes the SOLID and RAW tiles of `pack` into the frame at the device pointer `dst_ptr` and nothing
+        else.  `pack` is bytes (uploaded for the caller) or (device pointer, size).  Stream-ordered."""
+        if isinstance(pack, (bytes, bytearray, memoryview)):
+            data = bytes(pack)
+            buf = ctypes.create_string_buffer(data, max(len(data), 1))
+            self._check(self.hip.jh_upload(self.ctx, _UNPACK_BUFFER_ID, buf, len(data)), "upload")
+            ptr, size = self.hip.jh_buffer_device_ptr(self.ctx, _UNPACK_BUFFER_ID), len(data)
+        else:
+            ptr, size = pack
+        self._check(self._L.jl_engine_unpack_tiles(self._h, ptr, size, dst_ptr, pitch, width, height, texel_bytes), "unpack_tiles")
+
+    def unpack_rejects(self, reset=False):
+        """Entries (a bad header: one) unpack_tiles has ignored since the last reset.  Waits for the stream."""
+        n = ctypes.c_uint32(0)
+        self._check(self.hip.jh_debug_unpack_rejects(self.ctx, ctypes.byref(n), 1 if reset else 0), "unpack_rejects")
+        return n.value
+
+    def capture(self, recording, out_device_ptr=None, surface=None, pack=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
-        appends the blit of the frame's target into that surface (one more kernel launch)."""
+        appends the blit of the frame's target into that surface (one more kernel launch).
+        pack=(src, pitch, ref, ref_pitch, dst, capacity, texel_bytes) appends jh_pack_tiles of the frame-sized image at the
+        device pointer `src` -- the surface, or the RGBA16F target -- against `ref` (or None) into `dst` (two more launches);
+        a frame of this size must have been packed once eagerly."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
+            t = recording.target
             if surface is not None:
                 ptr, pitch, fmt = surface
-                t = recording.target
                 self._check(self._L.jl_engine_blit(self._h, t["id"], ptr, pitch, t["width"], t["height"], int(fmt)), "blit")
+            if pack is not None:
+                src, spitch, ref, rpitch, dst, cap, tb = pack
+                self._check(self._L.jl_engine_pack_tiles(self._h, src, spitch, ref, rpitch or 0, t["width"], t["height"], tb, dst, cap),
+                            "pack_tiles")
         finally:
             g = ctypes.c_void_p()
             rc = self.hip.jh_graph_end(self.ctx, ctypes.byref(g))

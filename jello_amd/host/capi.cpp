@@ -404,4 +404,23 @@ int jl_engine_blit(void* e, uint64_t src_image_id, void* surface, uint64_t pitch
     return 0;
 }
 
+// Tile-packed frame transport (jh_pack_tiles / jh_unpack_tiles; the format is in jello_hip.h).  Device pointers throughout.
+int jl_engine_pack_tiles(void* e, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
+                         uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
+    GUARD(((Engine*)e)->pack_tiles(src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, dst_capacity), -1);
+    return 0;
+}
+int jl_engine_unpack_tiles(void* e, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
+                           uint32_t texel_bytes) {
+    GUARD(((Engine*)e)->unpack_tiles(pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes), -1);
+    return 0;
+}
+// The pack at device_ptr into `out`: the header first, then exactly the size it states (written to *size).
+int jl_engine_read_pack(void* e, const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity, uint64_t* size) {
+    uint64_t n = 0;
+    GUARD(n = ((Engine*)e)->read_pack(device_ptr, capacity, out, out_capacity), -1);
+    if (size) *size = n;
+    return 0;
+}
+
 }  // extern "C"

@@ -200,6 +200,34 @@ void Engine::blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32
     check(jh_blit(ctx_, src_image_id, surface, pitch, width, height, format), "blit");
 }
 
+void Engine::pack_tiles(const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
+                        uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
+    check(jh_pack_tiles(ctx_, src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, dst_capacity), "pack_tiles");
+}
+
+void Engine::unpack_tiles(const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
+                          uint32_t texel_bytes) {
+    check(jh_unpack_tiles(ctx_, pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes), "unpack_tiles");
+}
+
+uint64_t Engine::read_pack(const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity) {
+    if (!device_ptr || !out || capacity < 32u) throw EngineError(JH_ERR_INVALID, "read_pack: null pointer or a capacity below the header's 32 bytes");
+    // the pack's memory is the caller's: it is bound under an id of its own for the two downloads (an import of caller-owned
+    // memory and its free leave captured graphs valid)
+    const ResourceID id = next_resource_id();
+    check(jh_buffer_import(ctx_, id, const_cast<void*>(device_ptr), capacity), "buffer_import");
+    struct Forget { jh_ctx* c; ResourceID id; ~Forget() { (void)jh_free(c, id); } } forget{ctx_, id};
+    uint32_t h[8];
+    check(jh_download(ctx_, id, h, 0, sizeof h), "download");
+    auto align16 = [](uint64_t v) { return (v + 15u) & ~15ull; };
+    if (h[0] != 0x3150544Au || (h[3] != 4u && h[3] != 8u) || (uint64_t)h[5] + h[6] != h[4])
+        throw EngineError(JH_ERR_INVALID, "read_pack: not a pack header");
+    const uint64_t total = 32u + align16(8ull * h[4]) + align16((uint64_t)h[3] * h[5]) + 256ull * h[3] * h[6];
+    if (total > capacity || total > out_capacity) throw EngineError(JH_ERR_INVALID, "read_pack: the pack is larger than the capacity given");
+    check(jh_download(ctx_, id, out, 0, total), "download");
+    return total;
+}
+
 void Engine::download_target(const Frame& f, void* dst, size_t bytes) { check(jh_image_download(ctx_, f.target.id, dst, bytes), "image_download"); }
 
 void Engine::release(const Frame& f) {

@@ -70,6 +70,16 @@ class Engine {
     // The blit pass alone: the RGBA16F image src_image_id into a surface (jh_blit).
     void blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format);
 
+    // Tile-packed frame transport (jh_pack_tiles / jh_unpack_tiles, the format is in jello_hip.h): all pointers are device
+    // memory, both calls are stream-ordered and wait for nothing.
+    void pack_tiles(const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
+                    uint32_t texel_bytes, void* dst, uint64_t dst_capacity);
+    void unpack_tiles(const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height, uint32_t texel_bytes);
+    // Downloads the pack at device_ptr (capacity bytes of device memory): its 32-byte header first, then exactly the total size
+    // the header states -- the only two host waits of the feature.  Returns that size; throws when it exceeds capacity or
+    // out_capacity (a header that is not a pack's included).
+    uint64_t read_pack(const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity);
+
     Resolver& resolver() { return resolver_; }
     Renderer& renderer() { return renderer_; }
 
