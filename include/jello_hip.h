@@ -18,6 +18,7 @@
  *   jh_profile_collect_tree       Profiler.Collect (nested results)    profiler.go:304-385
  *   jh_stage                      renderer.FullShaders field order     renderer/render.go:17-43
  *   jh_blit                       RenderToSurface's blit pass          engine/wgpu_engine/lib.go:109-198, 266-333
+ *   jh_blit_yuv                   (no counterpart: the same target as NV12 / I420 video frames)
  *   jh_pack_tiles / jh_unpack_tiles   (no counterpart: the frame's way off the GPU)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
@@ -221,6 +222,52 @@ typedef enum jh_surface_format {
  * from the source's, a pitch below 4 * width, a null dst or an unknown format. */
 int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t dst_pitch_bytes, uint32_t width, uint32_t height,
             int surface_format);
+
+/* ---- YUV blit: the RGBA16F target as planar 8-bit Y'CbCr 4:2:0 for a video encoder (DESIGN.md 5.5 "YUV blit") ----
+ * The project defines the result byte for byte (tests/yuv_ref.py restates it):
+ *   codes     (R, G, B) of a pixel = bytes 0, 1, 2 of what jh_blit writes for it in JH_SURFACE_RGBA8_UNORM (JH_YUV_TRANSFER_NONE)
+ *             or JH_SURFACE_RGBA8_SRGB (JH_YUV_TRANSFER_SRGB): premultiplied, clamped, NaN -> 0.  Alpha is dropped: the frame
+ *             composited over black.
+ *   matrix    in integers, with the coefficient table M (3 x 3, 16.16 fixed point) and the luma offset o of the matrix and range:
+ *               Y  = clamp8(o   + floor((M[0] . (R, G, B)       + 2^15) / 2^16))
+ *               Cb = clamp8(128 + floor((M[1] . (S_R, S_G, S_B) + 2^17) / 2^18)),  Cr the same with M[2]
+ *             S_* = the sum of the codes of the four luma positions the chroma sample covers; floor is towards -inf (an
+ *             arithmetic shift); clamp8 is to [0, 255] (it only ever acts on full-range chroma, where 255.5 rounds to 256).
+ *   siting    chroma planes are ceil(w / 2) x ceil(h / 2); sample (cx, cy) covers x in {2 cx, min(2 cx + 1, w - 1)} and
+ *             y in {2 cy, min(2 cy + 1, h - 1)}: a centre-sited box average (JPEG / MPEG-1), the last column or row counted
+ *             twice at an odd edge.
+ *   tables    round-half-even(exact * 2^16) of the BT.601 (Kr 0.299, Kb 0.114) and BT.709 (Kr 0.2126, Kb 0.0722) coefficients,
+ *             scaled by 219/255 (luma) and 224/255 (chroma) in limited range (o = 16) and by 1 in full range (o = 0); the
+ *             green coefficient of a row adjusted so that the Y row sums to rne(scale * 2^16) and each chroma row to 0 -- every
+ *             grey has Cb = Cr = 128.  jello_amd/csrc/yuv_matrix_lut.h, tools/gen_yuv_table.py.   (Y row | Cb row | Cr row)
+ *               BT.601 limited   16829, 33039, 6416 |  -9714, -19070, 28784 | 28784, -24103, -4681
+ *               BT.601 full      19595, 38470, 7471 | -11058, -21710, 32768 | 32768, -27439, -5329
+ *               BT.709 limited   11966, 40254, 4064 |  -6596, -22188, 28784 | 28784, -26145, -2639
+ *               BT.709 full      13933, 46871, 4732 |  -7509, -25259, 32768 | 32768, -29763, -3005
+ *             The result is within 0.51 code of the exact real-valued formula on the same codes.
+ *   layouts   NV12: plane[0] = Y (w bytes per row), plane[1] = interleaved (Cb, Cr) pairs (2 ceil(w / 2) bytes per row);
+ *             plane[2] is ignored.  I420: plane[0] = Y, plane[1] = Cb, plane[2] = Cr (ceil(w / 2) bytes per row each).
+ *             YV12 is I420 with the two chroma pointers swapped. */
+typedef enum jh_yuv_layout { JH_YUV_NV12 = 0, JH_YUV_I420 = 1 } jh_yuv_layout;
+typedef enum jh_yuv_matrix { JH_YUV_BT601 = 0, JH_YUV_BT709 = 1 } jh_yuv_matrix;
+typedef enum jh_yuv_range { JH_YUV_LIMITED = 0, JH_YUV_FULL = 1 } jh_yuv_range;
+typedef enum jh_yuv_transfer { JH_YUV_TRANSFER_NONE = 0, JH_YUV_TRANSFER_SRGB = 1 } jh_yuv_transfer;
+typedef struct jh_yuv_desc {
+    int32_t layout, matrix, range, transfer; /* jh_yuv_layout, jh_yuv_matrix, jh_yuv_range, jh_yuv_transfer */
+    void* plane[3];                          /* caller-owned device memory */
+    uint64_t pitch[3];                       /* bytes between the rows of each plane */
+} jh_yuv_desc;
+/* Converts the RGBA16F image src_image_id (width x height, JL_RGBA16_FLOAT) into the planes of *desc (read during the call
+ * only).  Any plane pointer and any pitch >= the row's bytes is legal; planes whose pointers and pitches are all multiples of
+ * 16 take the kernel's wide stores, everything else single-byte stores of the same bytes.  The bytes between a row's end and
+ * the pitch, and the rows below a plane, are never written.  Otherwise as jh_blit: stream-ordered on the context's stream, one
+ * kernel launch, may be captured between jh_graph_begin and jh_graph_end (the graph then holds the plane pointers); a source
+ * that was never written converts as transparent black (Y = 16 or 0, chroma 128); with profiling on it is a query labelled
+ * "blit_yuv" with stage = -1 in jh_profile_collect_tree.  In band mode (jh_set_band) only the luma rows of the active bin rows
+ * and the chroma rows under them are written (a bin row is 256 pixel rows, so the cut is even and bands compose).
+ * JH_ERR_INVALID, with nothing enqueued, for a null desc, an unknown or non-RGBA16F source, a size that differs from the
+ * source's, a null required plane, a pitch below the row's bytes or an unknown layout, matrix, range or transfer. */
+int jh_blit_yuv(jh_ctx* ctx, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc);
 
 /* ---- tile-packed frame transport (DESIGN.md 5.4 "Tile pack: the format") ----
  * jh_pack_tiles turns a frame in device memory into only the bytes that have to leave the GPU, jh_unpack_tiles applies such a

@@ -51,6 +51,23 @@ const (
 	SurfaceBGRA8Srgb  SurfaceFormat = C.JH_SURFACE_BGRA8_SRGB
 )
 
+// YUVFormat selects what RenderToYUV writes (jh_yuv_layout, jh_yuv_matrix, jh_yuv_range, jh_yuv_transfer; the conversion
+// rule is in include/jello_hip.h, "YUV blit").
+type YUVFormat struct {
+	Layout, Matrix, Range, Transfer int
+}
+
+const (
+	YUVNV12         = C.JH_YUV_NV12
+	YUVI420         = C.JH_YUV_I420
+	YUVBT601        = C.JH_YUV_BT601
+	YUVBT709        = C.JH_YUV_BT709
+	YUVLimited      = C.JH_YUV_LIMITED
+	YUVFull         = C.JH_YUV_FULL
+	YUVTransferNone = C.JH_YUV_TRANSFER_NONE
+	YUVTransferSrgb = C.JH_YUV_TRANSFER_SRGB
+)
+
 // surfaceTargetID names the target's buffer on the context: recordings take their ResourceIDs from a counter that starts at 1
 // (recording.go:15-19) and never reaches the top bit.
 const surfaceTargetID renderer.ResourceID = 1<<63 | 0x7461726765740000
@@ -356,6 +373,40 @@ func (e *Engine) RenderToSurface(arena *mem.Arena, enc *encoding.Encoding, surfa
 	attempts := e.renderToTexture(arena, enc, e.target.ptr, params, pgroup, &out)
 	e.check(C.jh_blit(e.ctx, C.uint64_t(out.ID), surface, C.uint64_t(pitch), C.uint32_t(params.Width), C.uint32_t(params.Height),
 		C.int(format)), "blit")
+	// the target image of this frame is an import over e.target: forgetting it frees nothing
+	e.check(C.jh_image_free(e.ctx, C.uint64_t(out.ID)), "image_free")
+	return attempts
+}
+
+// RenderToYUV is RenderToSurface for a video encoder: RenderToTexture into the same engine-owned RGBA16F target, then
+// jh_blit_yuv into planar 8-bit Y'CbCr 4:2:0 -- planes[0] = Y, planes[1] = interleaved CbCr (NV12) or Cb (I420), planes[2] = Cr
+// (I420 only; YV12 is I420 with the two chroma pointers swapped) -- device memory with pitches[i] bytes between rows.  Bytes past
+// a row's end and rows below a plane are not written.  Stream-ordered behind the frame.  Returns the attempts
+// RenderToTexture took.
+func (e *Engine) RenderToYUV(arena *mem.Arena, enc *encoding.Encoding, planes [3]unsafe.Pointer, pitches [3]uint64, format YUVFormat,
+	params *renderer.RenderParams, pgroup profiler.ProfilerGroup) int {
+	label := C.CString("RenderToYUV")
+	defer C.free(unsafe.Pointer(label))
+	e.check(C.jh_profile_group_begin(e.ctx, label), "profile_group_begin")
+	defer C.jh_profile_group_end(e.ctx)
+	if e.target == nil || e.target.Width != params.Width || e.target.Height != params.Height {
+		if e.target != nil {
+			e.check(C.jh_free(e.ctx, C.uint64_t(e.target.id)), "free")
+		}
+		id := surfaceTargetID
+		e.check(C.jh_buffer_create(e.ctx, C.uint64_t(id), C.uint64_t(uint64(params.Width)*uint64(params.Height)*8)), "buffer_create")
+		e.target = &targetTexture{id: id, ptr: C.jh_buffer_device_ptr(e.ctx, C.uint64_t(id)), Width: params.Width, Height: params.Height}
+	}
+	var out renderer.ImageProxy
+	attempts := e.renderToTexture(arena, enc, e.target.ptr, params, pgroup, &out)
+	var d C.jh_yuv_desc
+	d.layout, d.matrix = C.int32_t(format.Layout), C.int32_t(format.Matrix)
+	d._range, d.transfer = C.int32_t(format.Range), C.int32_t(format.Transfer) // (cgo spells the C field `range` _range)
+	for i := range planes {
+		d.plane[i] = planes[i]
+		d.pitch[i] = C.uint64_t(pitches[i])
+	}
+	e.check(C.jh_blit_yuv(e.ctx, C.uint64_t(out.ID), C.uint32_t(params.Width), C.uint32_t(params.Height), &d), "blit_yuv")
 	// the target image of this frame is an import over e.target: forgetting it frees nothing
 	e.check(C.jh_image_free(e.ctx, C.uint64_t(out.ID)), "image_free")
 	return attempts

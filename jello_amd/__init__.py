@@ -8,4 +8,6 @@ from ._lib import build, lib_paths, load_host, HostLibraryMissing  # noqa: F401
 from .scene import (  # noqa: F401
     Scene, Path, Brush, Stroke, Color, ColorStop, RenderParams, BumpSizes, Fill, Join, Cap, Mix, Compose, Extend, Aa,
 )
-from .engine import Host, Recording, Engine, Surface, STAGE_NAMES, CMD  # noqa: F401
+from .engine import (  # noqa: F401
+    Host, Recording, Engine, Surface, YuvLayout, YuvMatrix, YuvRange, YuvTransfer, STAGE_NAMES, CMD,
+)

@@ -119,6 +119,12 @@ class CConfig(ctypes.Structure):
                 ("blend_size", ctypes.c_uint32), ("ptcl_size", ctypes.c_uint32)]
 
 
+class CYuvDesc(ctypes.Structure):
+    """jh_yuv_desc (include/jello_hip.h)."""
+    _fields_ = [("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32), ("transfer", ctypes.c_int32),
+                ("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_uint64 * 3)]
+
+
 def _declare(L):
     vp, ci, cu = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
     dp = ctypes.POINTER(ctypes.c_double)
@@ -168,6 +174,10 @@ def _declare(L):
     L.jl_engine_render_to_surface.argtypes = [vp, vp, ctypes.POINTER(CRenderParams), vp, ctypes.c_uint64, ci, ci,
                                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ci)]
     L.jl_engine_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
+    L.jl_engine_render_to_yuv.restype = vp
+    L.jl_engine_render_to_yuv.argtypes = [vp, vp, ctypes.POINTER(CRenderParams), ctypes.POINTER(CYuvDesc), ci, ctypes.POINTER(ctypes.c_uint32),
+                                          ctypes.POINTER(ci)]
+    L.jl_engine_blit_yuv.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(CYuvDesc)]
     u32, u64 = ctypes.c_uint32, ctypes.c_uint64
     L.jl_engine_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
     L.jl_engine_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
@@ -200,6 +210,7 @@ def _declare(L):
     hip.jh_image_upload.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci, vp, ctypes.c_uint64]
     hip.jh_image_free.argtypes = [vp, ctypes.c_uint64]
     hip.jh_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
+    hip.jh_blit_yuv.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(CYuvDesc)]
     hip.jh_pack_bound.restype = u64
     hip.jh_pack_bound.argtypes = [u32, u32, u32]
     hip.jh_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]

@@ -1165,6 +1165,50 @@ int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t d
     return JH_OK;
 }
 
+// ---- YUV blit (include/jello_hip.h "YUV blit"; kernels_yuv.hip) ----
+int jh_blit_yuv_launch(hipStream_t stream, const void* src, void* const* planes, const uint64_t* pitches, uint32_t width, uint32_t height,
+                       uint32_t row0, uint32_t row1, int layout, int matrix, int range, int transfer, int num_cus);
+
+int jh_blit_yuv(jh_ctx* ctx, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc) {
+    if (!ctx) return JH_ERR_INVALID;
+    // every check comes before anything is enqueued: a refused call touches no memory
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: null descriptor");
+    const Alloc* src = find_alloc(ctx->images, src_image_id);
+    if (!src) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown source image id");
+    const Alloc& a = *src;
+    if (a.format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: the source is not an RGBA16F image");
+    if (a.width != width || a.height != height) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: size differs from the source image");
+    if (desc->layout != JH_YUV_NV12 && desc->layout != JH_YUV_I420) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown layout");
+    if (desc->matrix != JH_YUV_BT601 && desc->matrix != JH_YUV_BT709) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown matrix");
+    if (desc->range != JH_YUV_LIMITED && desc->range != JH_YUV_FULL) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown range");
+    if (desc->transfer != JH_YUV_TRANSFER_NONE && desc->transfer != JH_YUV_TRANSFER_SRGB)
+        return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown transfer");
+    const uint64_t cw = (width + 1ull) / 2u;
+    const uint64_t row_bytes[3] = {width, desc->layout == JH_YUV_NV12 ? 2u * cw : cw, cw};
+    for (int i = 0; i < (desc->layout == JH_YUV_NV12 ? 2 : 3); i++) {
+        if (!desc->plane[i]) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: null plane");
+        if (desc->pitch[i] < row_bytes[i]) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: pitch below the row's bytes");
+    }
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // band mode: the luma rows of the active bin rows (a bin row = 256 pixel rows: an even cut) and the chroma rows under them
+    const uint64_t h = height;
+    const uint32_t row0 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row0 * 256u, h);
+    const uint32_t row1 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row1 * 256u, h);
+    ProfEntry pe;
+    int prc = prof_query_begin(ctx, pe, -1, "blit_yuv");
+    if (prc) return prc;
+    int rc = 0;
+    if (row1 > row0)  // a source that was never written reads as transparent black, like a fresh texture
+        rc = jh_blit_yuv_launch(ctx->stream, (a.written || a.stored) ? a.ptr : nullptr, desc->plane, desc->pitch, width, height, row0, row1,
+                                desc->layout, desc->matrix, desc->range, desc->transfer, ctx->num_cus);
+    prc = prof_query_end(ctx, pe);
+    if (prc) return prc;
+    if (rc == -1) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: image too large for one launch");
+    if (rc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_blit_yuv: launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return JH_OK;
+}
+
 // ---- tile pack (include/jello_hip.h "tile-packed frame transport"; kernels_pack.hip) ----
 uint32_t jh_pack_groups(uint32_t n_tiles, uint32_t* run_out);
 int jh_pack_launch(hipStream_t stream, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,

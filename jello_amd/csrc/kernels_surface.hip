@@ -3,6 +3,7 @@
 // The conversion rule is in include/jello_hip.h and DESIGN.md ("Surface blit"); the hardware's float -> unorm / sRGB
 // conversions are implementation-defined, so the project defines the answer itself:
 //   p = c * a (f32, exact)   v = clamp(p, 0, 1) with NaN -> 0   unorm: rint_f32(v * 255)   sRGB: table of 255 thresholds.
+// The per-pixel functions (blit_pixel and what it calls) live in blit_convert.h, which jh_blit_yuv (kernels_yuv.hip) shares.
 // Streaming: 8 B read and 4 B written per pixel, nothing reused.  A lane converts four adjacent pixels (two 16-B loads -- or
 // four 8-B loads when the source row is only 8-B aligned -- and one 16-B store); the first pixels of a row up to the
 // destination's next 16-B boundary and the last width % 4 go through a one-pixel path, as does every pixel of a row whose
@@ -11,51 +12,11 @@
 
 #include <stdint.h>
 
-#include "dmath.h"
-#include "srgb_encode_lut.h"
+#include "blit_convert.h"
 
 namespace {
 
 constexpr uint32_t kBlitThreads = 256;
-
-// clamp to [0, 1] by comparisons: NaN (inf * 0 included) fails both and becomes 0, +inf becomes 1, -0 becomes +0
-__device__ __forceinline__ float blit_clamp01(float p) {
-    const float v = p > 0.0f ? p : 0.0f;
-    return v < 1.0f ? v : 1.0f;
-}
-
-__device__ __forceinline__ uint32_t blit_unorm(float v) { return (uint32_t)__builtin_rintf(v * 255.0f); }
-
-// sRGB code of v in [0, 1]: a hardware log2 / exp2 estimate of 255 enc(v) (the constants folded: 255 * 12.92, 255 * 1.055,
-// 255 * 0.055; an fma is fine in an estimate), rounded -- within one code of the rule -- then corrected against the thresholds.  lut[u] = (threshold of
-// code u, threshold of code u + 1) with code 0's threshold 0 and code 256's +inf: the code is the u with
-// lut[u].x <= v < lut[u].y, one 8-B LDS read per channel.
-__device__ __forceinline__ uint32_t blit_srgb(float v, const float2* lut) {
-    const float e = v <= 0.0031308f ? v * 3294.6f
-                                    : __builtin_fmaf(269.025f, __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(v) * (1.0f / 2.4f)), -14.025f);
-    int u = (int)__builtin_rintf(e);
-    u = u < 0 ? 0 : (u > 255 ? 255 : u);
-    const float2 t = lut[u];
-    return (uint32_t)(u - (v < t.x ? 1 : 0) + (v >= t.y ? 1 : 0));
-}
-
-// one RGBA16F texel (x = r | g << 16, y = b | a << 16, f16 bits) -> the surface's 4 bytes, byte 0 lowest
-template <bool SRGB, bool BGRA>
-__device__ __forceinline__ uint32_t blit_pixel(uint2 t, const float2* lut) {
-    const float a = jd::f16_to_f32((uint16_t)(t.y >> 16));
-    const float r = blit_clamp01(jd::f16_to_f32((uint16_t)(t.x & 0xffffu)) * a);
-    const float g = blit_clamp01(jd::f16_to_f32((uint16_t)(t.x >> 16)) * a);
-    const float b = blit_clamp01(jd::f16_to_f32((uint16_t)(t.y & 0xffffu)) * a);
-    const uint32_t ua = blit_unorm(blit_clamp01(a));
-    uint32_t c0, c1, c2;
-    if (SRGB) {
-        c0 = blit_srgb(r, lut); c1 = blit_srgb(g, lut); c2 = blit_srgb(b, lut);
-    } else {
-        c0 = blit_unorm(r); c1 = blit_unorm(g); c2 = blit_unorm(b);
-    }
-    if (BGRA) { const uint32_t s = c0; c0 = c2; c2 = s; }
-    return c0 | (c1 << 8) | (c2 << 16) | (ua << 24);
-}
 
 // Pixels of the row that go through the one-pixel path before the first four-pixel group (dst row not 16-B aligned yet);
 // the whole row when its destination is not 4-B aligned.
@@ -73,7 +34,7 @@ __global__ __launch_bounds__(kBlitThreads) void k_blit(const uint2* __restrict__
     __shared__ float2 lut[SRGB ? 256 : 1];
     if (SRGB) {
         const uint32_t i = threadIdx.x;  // (kBlitThreads = 256 entries)
-        lut[i] = make_float2(i == 0u ? 0.0f : kSrgbEncodeThreshold[i - 1u], i == 255u ? __builtin_huge_valf() : kSrgbEncodeThreshold[i]);
+        blit_srgb_lut_fill(lut, i);
         __syncthreads();
     }
     for (uint32_t wb = blockIdx.x; wb < total_blocks; wb += gridDim.x) {

@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CConfig
+from ._lib import CConfig, CYuvDesc
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
                "flatten", "draw_reduce", "draw_leaf", "clip_reduce", "clip_leaf", "binning", "tile_alloc", "backdrop_dyn",
@@ -24,11 +24,37 @@ class Surface(enum.IntEnum):
     BGRA8_SRGB = 3
 
 
+class YuvLayout(enum.IntEnum):
+    """jh_yuv_layout: NV12 = Y plane + interleaved (Cb, Cr) plane; I420 = Y, Cb, Cr planes (YV12: swap the chroma pointers)."""
+    NV12 = 0
+    I420 = 1
+
+
+class YuvMatrix(enum.IntEnum):
+    """jh_yuv_matrix."""
+    BT601 = 0
+    BT709 = 1
+
+
+class YuvRange(enum.IntEnum):
+    """jh_yuv_range: LIMITED = Y in [16, 235], chroma in [16, 240]; FULL = [0, 255]."""
+    LIMITED = 0
+    FULL = 1
+
+
+class YuvTransfer(enum.IntEnum):
+    """jh_yuv_transfer: the R'G'B' codes are those of Surface.RGBA8_UNORM (NONE) or Surface.RGBA8_SRGB (SRGB)."""
+    NONE = 0
+    SRGB = 1
+
+
 # a context buffer that blit / render_to_surface convert into when the caller passes no device pointer (it only grows)
 _SURFACE_BUFFER_ID = 0x5355524641434500
 # context buffers of pack_tiles (the pack, when the caller passes no device pointer) and unpack_tiles (an uploaded pack)
 _PACK_BUFFER_ID = 0x5041434B4F555400
 _UNPACK_BUFFER_ID = 0x5041434B494E0000
+# a context buffer that blit_yuv / render_to_yuv convert into when the caller passes no planes (it only grows)
+_YUV_BUFFER_ID = 0x5955565F4F555400
 
 
 class CMD:
@@ -208,6 +234,70 @@ class Engine:
         surface = None if out_device_ptr is not None else self._download_surface(params.width, params.height)
         return surface, Recording(self._L, h), dict(zip(names, bump)), attempts.value
 
+    @staticmethod
+    def yuv_plane_shapes(width, height, layout):
+        """[(rows, bytes per row)] of the planes of a width x height frame: Y, then CbCr (NV12) or Cb and Cr (I420)."""
+        cw, ch = (width + 1) // 2, (height + 1) // 2
+        return [(height, width), (ch, 2 * cw)] if int(layout) == YuvLayout.NV12 else [(height, width), (ch, cw), (ch, cw)]
+
+    def _yuv_desc(self, width, height, layout, matrix, rng, transfer, planes):
+        """(CYuvDesc, own) for `planes` = [(device pointer, pitch or None)] per plane, or None: the engine's own buffer, the
+        planes one after the other with tightly packed rows, each starting at a multiple of 16 (own = their offsets)."""
+        shapes = self.yuv_plane_shapes(width, height, layout)
+        d = CYuvDesc(int(layout), int(matrix), int(rng), int(transfer))
+        own = None
+        if planes is None:
+            own, off = [], 0
+            for rows, rb in shapes:
+                own.append(off)
+                off += (rows * rb + 15) & ~15
+            self._check(self.hip.jh_buffer_create(self.ctx, _YUV_BUFFER_ID, max(off, 16)), "buffer_create")
+            base = self.hip.jh_buffer_device_ptr(self.ctx, _YUV_BUFFER_ID)
+            planes = [(base + o, None) for o in own]
+        for i, pl in enumerate(planes):
+            ptr, pitch = pl if isinstance(pl, (tuple, list)) else (pl, None)
+            d.plane[i] = ptr
+            d.pitch[i] = (shapes[i][1] if i < len(shapes) else 0) if pitch is None else pitch
+        return d, own
+
+    def _download_yuv(self, width, height, layout, own):
+        out = []
+        for (rows, rb), off in zip(self.yuv_plane_shapes(width, height, layout), own):
+            a = np.empty((rows, rb), dtype=np.uint8)
+            if a.nbytes:
+                self._check(self.hip.jh_download(self.ctx, _YUV_BUFFER_ID, a.ctypes.data, off, a.nbytes), "download")
+            out.append(a)
+        if int(layout) == YuvLayout.NV12:
+            out[1] = out[1].reshape(out[1].shape[0], -1, 2)
+        return tuple(out)
+
+    def blit_yuv(self, src_image_id, width, height, layout=YuvLayout.NV12, matrix=YuvMatrix.BT709, range=YuvRange.LIMITED,
+                 transfer=YuvTransfer.NONE, planes=None):
+        """jh_blit_yuv: the RGBA16F image `src_image_id` as 8-bit Y'CbCr 4:2:0 (the rule: include/jello_hip.h "YUV blit").
+        Into `planes` = [(device pointer, pitch)] -- Y and CbCr for NV12; Y, Cb and Cr for I420; a pitch of None means tightly
+        packed rows; returns None -- or, without planes, returned as uint8 arrays: (Y (H, W), CbCr (ceil(H/2), ceil(W/2), 2))
+        for NV12, (Y, Cb, Cr) for I420."""
+        d, own = self._yuv_desc(width, height, layout, matrix, range, transfer, planes)
+        self._check(self._L.jl_engine_blit_yuv(self._h, src_image_id, width, height, ctypes.byref(d)), "blit_yuv")
+        return None if own is None else self._download_yuv(width, height, layout, own)
+
+    def render_to_yuv(self, scene, params, layout=YuvLayout.NV12, matrix=YuvMatrix.BT709, range=YuvRange.LIMITED,
+                      transfer=YuvTransfer.NONE, planes=None, robust=True):
+        """RenderToTexture into the engine's own RGBA16F target, then blit_yuv.  Returns (planes, Recording, bump dict,
+        attempts); planes as blit_yuv returns them.  The Recording's target image is the engine's target until the next
+        render_to_surface / render_to_yuv."""
+        d, own = self._yuv_desc(params.width, params.height, layout, matrix, range, transfer, planes)
+        p = params._c()
+        bump = (ctypes.c_uint32 * 8)()
+        attempts = ctypes.c_int()
+        h = self._L.jl_engine_render_to_yuv(self._h, scene._h, ctypes.byref(p), ctypes.byref(d), 1 if robust else 0, bump,
+                                            ctypes.byref(attempts))
+        if not h:
+            raise RuntimeError("render_to_yuv: " + self._L.jl_last_error().decode())
+        names = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]
+        out = None if own is None else self._download_yuv(params.width, params.height, layout, own)
+        return out, Recording(self._L, h), dict(zip(names, bump)), attempts.value
+
     def pack_tiles(self, src_ptr, pitch, width, height, texel_bytes, ref_ptr=None, ref_pitch=None, out_device_ptr=None,
                    out_capacity=None):
         """jh_pack_tiles: the frame at the device pointer `src_ptr` (rows `pitch` bytes apart, texels of 4 or 8 bytes) as a
@@ -250,13 +340,15 @@ class Engine:
         self._check(self.hip.jh_debug_unpack_rejects(self.ctx, ctypes.byref(n), 1 if reset else 0), "unpack_rejects")
         return n.value
 
-    def capture(self, recording, out_device_ptr=None, surface=None, pack=None):
+    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
         pack=(src, pitch, ref, ref_pitch, dst, capacity, texel_bytes) appends jh_pack_tiles of the frame-sized image at the
         device pointer `src` -- the surface, or the RGBA16F target -- against `ref` (or None) into `dst` (two more launches);
-        a frame of this size must have been packed once eagerly."""
+        a frame of this size must have been packed once eagerly.
+        yuv=(planes, YuvLayout, YuvMatrix, YuvRange, YuvTransfer), planes as for blit_yuv, appends the conversion of the
+        frame's target into those planes (one more kernel launch)."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
@@ -264,6 +356,10 @@ class Engine:
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._check(self._L.jl_engine_blit(self._h, t["id"], ptr, pitch, t["width"], t["height"], int(fmt)), "blit")
+            if yuv is not None:
+                planes, layout, matrix, rng, transfer = yuv
+                d, _ = self._yuv_desc(t["width"], t["height"], layout, matrix, rng, transfer, planes)
+                self._check(self._L.jl_engine_blit_yuv(self._h, t["id"], t["width"], t["height"], ctypes.byref(d)), "blit_yuv")
             if pack is not None:
                 src, spitch, ref, rpitch, dst, cap, tb = pack
                 self._check(self._L.jl_engine_pack_tiles(self._h, src, spitch, ref, rpitch or 0, t["width"], t["height"], tb, dst, cap),

@@ -404,6 +404,30 @@ int jl_engine_blit(void* e, uint64_t src_image_id, void* surface, uint64_t pitch
     return 0;
 }
 
+// RenderToSurface for a video encoder: the same target, then jh_blit_yuv into the planes of *desc (NV12 / I420; the rule is in
+// jello_hip.h).  Returns the final attempt's recording handle like jl_engine_render_to_surface.
+void* jl_engine_render_to_yuv(void* e, void* scene, const jl_render_params* params, const jh_yuv_desc* desc, int robust, uint32_t* bump_out,
+                              int* attempts) {
+    Engine* eng = (Engine*)e;
+    if (!desc) { g_err = "render_to_yuv: null descriptor"; return nullptr; }
+    std::unique_ptr<RecHandle> h(new RecHandle());
+    Engine::Frame f;
+    GUARD(f = eng->render_to_yuv(((Scene*)scene)->encoding(), to_params(params), *desc, robust != 0), nullptr);
+    h->result.recording = std::move(f.recording);
+    h->result.config = f.config;
+    h->result.out_image = ResourceProxy::of(f.target);
+    h->buffers = f.buffers;
+    if (bump_out) std::memcpy(bump_out, &f.bump, sizeof(JlBump));
+    if (attempts) *attempts = f.attempts;
+    flatten_recording(h.get());
+    return h.release();
+}
+int jl_engine_blit_yuv(void* e, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc) {
+    if (!desc) { g_err = "blit_yuv: null descriptor"; return -1; }
+    GUARD(((Engine*)e)->blit_yuv(src_image_id, width, height, *desc), -1);
+    return 0;
+}
+
 // Tile-packed frame transport (jh_pack_tiles / jh_unpack_tiles; the format is in jello_hip.h).  Device pointers throughout.
 int jl_engine_pack_tiles(void* e, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
                          uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {

@@ -178,6 +178,24 @@ Engine::Frame Engine::render_to_surface(const Encoding& enc, RenderParams params
     // pgroup = pgroup.Nest("RenderToSurface"); defer pgroup.End()  (lib.go:274-275)
     check(jh_profile_group_begin(ctx_, "RenderToSurface"), "profile_group_begin");
     struct GroupEnd { jh_ctx* c; ~GroupEnd() { (void)jh_profile_group_end(c); } } group_end{ctx_};
+    Frame f = render_to_own_target(enc, params, robust);
+    blit(f.target.id, surface, pitch, params.width, params.height, format);
+    return f;
+}
+
+Engine::Frame Engine::render_to_yuv(const Encoding& enc, RenderParams params, const jh_yuv_desc& desc, bool robust) {
+    check(jh_profile_group_begin(ctx_, "RenderToYUV"), "profile_group_begin");
+    struct GroupEnd { jh_ctx* c; ~GroupEnd() { (void)jh_profile_group_end(c); } } group_end{ctx_};
+    Frame f = render_to_own_target(enc, params, robust);
+    blit_yuv(f.target.id, params.width, params.height, desc);
+    return f;
+}
+
+void Engine::blit_yuv(ResourceID src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc& desc) {
+    check(jh_blit_yuv(ctx_, src_image_id, width, height, &desc), "blit_yuv");
+}
+
+Engine::Frame Engine::render_to_own_target(const Encoding& enc, const RenderParams& params, bool robust) {
     SurfaceTarget& t = surface_target_;
     if (t.image) {  // the previous frame's image over the target: an import, forgetting it frees nothing
         check(jh_image_free(ctx_, t.image), "image_free");
@@ -192,7 +210,6 @@ Engine::Frame Engine::render_to_surface(const Encoding& enc, RenderParams params
     }
     Frame f = render_to_texture(enc, params, jh_buffer_device_ptr(ctx_, t.buffer), robust, false);
     t.image = f.target.id;
-    blit(f.target.id, surface, pitch, params.width, params.height, format);
     return f;
 }
 

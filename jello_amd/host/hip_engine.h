@@ -65,10 +65,16 @@ class Engine {
     // RenderToSurface (lib.go:266-333): render_to_texture into an engine-owned RGBA16F target -- kept while width and height
     // stay the same (eng.target, lib.go:279-284) -- then jh_blit into `surface`: device memory of height rows of 4 * width
     // bytes, `pitch` bytes apart, in the jh_surface_format `format`.  The frame's target image stays readable under
-    // Frame::target.id until the next render_to_surface.
+    // Frame::target.id until the next render_to_surface / render_to_yuv.
     Frame render_to_surface(const Encoding& enc, RenderParams params, void* surface, uint64_t pitch, int format, bool robust = true);
     // The blit pass alone: the RGBA16F image src_image_id into a surface (jh_blit).
     void blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format);
+    // RenderToSurface for a video encoder: render_to_texture into the same engine-owned target, then jh_blit_yuv into the
+    // planes of `desc` (NV12 / I420, include/jello_hip.h "YUV blit").  The frame's target image stays readable under
+    // Frame::target.id until the next render_to_surface / render_to_yuv./ render_to_yuv.
+    Frame render_to_yuv(const Encoding& enc, RenderParams params, const jh_yuv_desc& desc, bool robust = true);
+    // The conversion alone: the RGBA16F image src_image_id into the planes of `desc` (jh_blit_yuv).
+    void blit_yuv(ResourceID src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc& desc);
 
     // Tile-packed frame transport (jh_pack_tiles / jh_unpack_tiles, the format is in jello_hip.h): all pointers are device
     // memory, both calls are stream-ordered and wait for nothing.
@@ -91,6 +97,8 @@ class Engine {
     FullShaders shaders_;
     std::map<ResourceID, std::vector<uint8_t>> downloads_;
     struct SurfaceTarget { ResourceID buffer = 0, image = 0; uint32_t width = 0, height = 0; };
+    // render_to_texture into the engine's own target (created or resized first; the previous frame's image forgotten)
+    Frame render_to_own_target(const Encoding& enc, const RenderParams& params, bool robust);
     SurfaceTarget surface_target_;  // render_to_surface's RGBA16F target (a context buffer) and the last frame's image over it
 
    public:
