@@ -7,15 +7,25 @@ contours that tests/exact_coverage.py integrates and a tolerance class:
 * "large"  -- vertices at +-2^12 ... +-2^16: path_tiling's intersection formulas run on absolute f32 coordinates;
 * "xform"  -- a non-identity transform, applied by flatten in f32 (the reference applies it in float64 to the same
   f32 inputs);
-* "stroke" -- the outline is computed by the stroker in f32.
+* "stroke" -- the outline is computed by the stroker in f32;
+* "stroke-xform" -- a stroke under a non-identity transform: the stroker works in local space, flatten transforms its
+  lines in f32.
 
 Families (the `family` field): 1 rectangles on and near pixel / tile lines, 2 geometry outside the viewport,
 3 near-horizontal / near-vertical / corner-crossing edges, 4 degenerate contours, 5 winding other than +-1, 6 large
 coordinates, 7 transforms, 8 stroked segments, 9 target sizes, 10 the same expected alpha through the CLIPS and PAINTS
-instantiations of fine (see `variants`)."""
+instantiations of fine (see `variants`).
+
+STROKE_BATTERY holds stroked polylines (StrokeEntry), whose reference outline is tests/exact_stroke.py's and which are
+rendered non-zero only (the outline overlaps itself at every join): 11 joins x caps on an open L, 12 closed subpaths,
+13 turning angles and miter limits, 14 extremes, 15 transforms.  The encoder writes every path point as f32 (it has no
+i16 form to choose), so there is no entry per point format.  Family 3 also holds the outline that showed how far the
+MSAA band reaches past the end of an edge (near-vertical-cap-end) and its siblings."""
 import math
 
 import numpy as np
+
+import exact_stroke
 
 from jello_amd import Brush, Cap, ColorStop, Compose, Fill, Join, Mix, Path, RenderParams, Scene, Stroke
 
@@ -153,6 +163,18 @@ def _battery():
     E.append(Entry("tile-corners", 3, 64, 64, [[(0.0, 0.0), (64.0, 64.0), (0.0, 64.0)], [(64.0, 0.0), (16.0, 48.0), (64.0, 48.0)]]))
     E.append(Entry("pixel-corners", 3, 64, 48, [[(3.0, 5.0), (43.0, 25.0), (61.0, 44.0), (7.0, 39.0)]]))
     E.append(Entry("diagonal-45", 3, 64, 64, [[(8.0, 2.0), (58.0, 52.0), (8.0, 52.0)], [(60.5, 3.5), (20.5, 43.5), (60.5, 43.5)]]))
+    # a near-vertical edge that ends inside a pixel where a horizontal edge begins: the outline of a 6-px butt-capped
+    # miter stroke through a 0.1-degree turn (its end cap is 1.7e-3 off vertical; at 8 samples the quantised LUT line of
+    # the bottom edge, y = 50.93, puts the sample at (100.3125, 50.9375) above it although the edge has ended at
+    # x = 100.005), and quads with the same corner at other offsets inside the pixel, slopes 5e-4 ... 5e-3, mirrored
+    cap = exact_stroke.stroke_outline([([(20.0, 48.0), (60.0, 48.0), (100.0, 47.93)], False)], 6.0, "miter", 4.0, "butt", "butt")
+    E.append(Entry("near-vertical-cap-end", 3, 128, 96, cap.contours))
+    quads = [[(bx - 12.0, cy - 6.0), (bx + fx - 6.0 * slope, cy - 6.0), (bx + fx, cy), (bx - 12.0, cy)]
+             for (bx, fx) in ((20.0, 0.00525), (50.0, 0.25), (80.0, 0.6), (110.0, 0.95))
+             for (cy, slope) in ((20.93, 5e-4), (50.93, 1.75e-3), (80.93, 5e-3))]
+    for name, mx, my in (("", 1, 1), ("-mirror-x", -1, 1), ("-mirror-y", 1, -1), ("-mirror-xy", -1, -1)):
+        E.append(Entry("near-vertical-ends-in-pixel" + name, 3, 128, 96,
+                       [[(x if mx > 0 else 128.0 - x, y if my > 0 else 96.0 - y) for x, y in q] for q in quads]))
     # --- 4: slivers, sub-pixel triangles, zero-area and repeated / zero-length edges
     E.append(Entry("sliver-1e-4", 4, 64, 48, [[(3.0, 4.0), (60.0, 40.0), (60.0, 40.0001)]]))
     E.append(Entry("sliver-vertical", 4, 64, 48, [[(20.25, 2.0), (20.2501, 45.0), (20.2502, 2.0)]]))
@@ -198,8 +220,177 @@ def _battery():
     return E
 
 
+JOINS = {"miter": Join.Miter, "bevel": Join.Bevel, "round": Join.Round}
+CAPS = {"butt": Cap.Butt, "square": Cap.Square, "round": Cap.Round}
+
+
+class StrokeEntry(Entry):
+    """A stroked polyline (families 11-15): `subpaths` is a list of (points, closed); join and caps are the style names
+    of tests/exact_stroke.py, which computes the reference outline.  Strokes are filled non-zero whatever the rule."""
+    def __init__(self, name, family, width, height, subpaths, stroke_width, join="miter", limit=4.0, caps=("butt", "butt"),
+                 transform=None, defect=None):
+        self.name, self.family, self.width, self.height = name, family, width, height
+        self.subpaths = [(f32(p).reshape(-1, 2), bool(closed)) for p, closed in subpaths]
+        self.contours = [p for p, _ in self.subpaths]
+        self.stroke_width, self.join, self.limit, self.caps = stroke_width, join, limit, caps
+        self.transform, self.defect = transform, defect
+        self.tclass = "stroke" if transform is None else "stroke-xform"
+        self.stroke = None
+        self._outline = {}
+
+    def with_defect(self, defect=None, **changes):
+        """A copy whose reference outline is wrong in one respect (the sensitivity tests)."""
+        kw = dict(stroke_width=self.stroke_width, join=self.join, limit=self.limit, caps=self.caps, transform=self.transform)
+        kw.update(changes)
+        return StrokeEntry(self.name, self.family, self.width, self.height, self.subpaths, defect=defect, **kw)
+
+    def outline(self, arcs="rule"):
+        if arcs not in self._outline:
+            self._outline[arcs] = exact_stroke.stroke_outline(self.subpaths, self.stroke_width, self.join, self.limit, self.caps[0],
+                                                              self.caps[1], self.transform, arcs, self.defect)
+        return self._outline[arcs]
+
+    def path(self):
+        p = Path()
+        for pts, closed in self.subpaths:
+            p.move_to(float(pts[0, 0]), float(pts[0, 1]))
+            for x, y in pts[1:]:
+                p.line_to(float(x), float(y))
+            if closed:
+                p.close()
+        return p
+
+    def reference_contours(self):
+        return self.outline().contours
+
+    def transform_norm(self):
+        """The largest factor by which the linear part stretches an error bounded per coordinate."""
+        if self.transform is None:
+            return 1.0
+        a, b, c, d, _, _ = self.transform
+        return max(abs(a) + abs(c), abs(b) + abs(d))
+
+    def max_local_coordinate(self):
+        """The largest coordinate of the outline before the transform."""
+        if self.transform is None:
+            return self.max_coordinate()
+        local = exact_stroke.stroke_outline(self.subpaths, self.stroke_width, self.join, self.limit, self.caps[0], self.caps[1],
+                                            None, "upper")
+        return max(float(np.abs(c).max()) for c in local.contours)
+
+    def arc_edges(self):
+        """(edge index in exact_coverage.edges_of(reference_contours()), arc) for every line of every arc."""
+        contours = self.reference_contours()
+        base = np.concatenate([[0], np.cumsum([len(c) for c in contours])])
+        out = []
+        for arc in self.outline().arcs:
+            n = len(contours[arc.contour])
+            out += [(int(base[arc.contour]) + (arc.first + k) % n, arc) for k in range(arc.n)]
+        return out
+
+    def scene(self, rule="nonzero", variant="plain"):
+        s = Scene()
+        brush = Brush.solid(WHITE)
+        if variant == "paint":
+            brush = Brush.linear((0.0, 0.0), (float(self.width), float(self.height) + 1.0),
+                                 [ColorStop(0.0, WHITE), ColorStop(1.0, WHITE)])
+        if variant == "clip":
+            s.push_layer(Mix.Clip, Compose.SrcOver, 1.0, None, Path.rect(0, 0, self.width, self.height))
+        style = Stroke(self.stroke_width, JOINS[self.join], self.limit, CAPS[self.caps[0]], CAPS[self.caps[1]])
+        s.stroke(style, self.transform, brush, None, self.path())
+        if variant == "clip":
+            s.pop_layer()
+        return s
+
+
+def corner(apex, leg, interior_deg, mirror=False, heading_deg=0.0):
+    """Two legs of length `leg` meeting at `apex` with the given interior angle; the first leg arrives with the given
+    heading.  mirror flips the turning direction (the sign of cr)."""
+    h = math.radians(heading_deg)
+    turn = math.radians(180.0 - interior_deg) * (-1.0 if mirror else 1.0)
+    ax, ay = apex
+    return [(ax - leg * math.cos(h), ay - leg * math.sin(h)), (ax, ay), (ax + leg * math.cos(h + turn), ay + leg * math.sin(h + turn))]
+
+
+def _stroke_battery():
+    E = []
+    # --- 11: joins x caps on an open L whose outline mixes tile lines (x = 64, y = 16), pixel lines and fractions
+    L = [(13.0, 19.0), (61.0, 19.0), (61.0, 70.25)]
+    caps = ("butt", "square", "round")
+    for join in ("miter", "bevel", "round"):
+        for k, c in enumerate(caps):
+            E.append(StrokeEntry("L-%s-%s-%s" % (join, c, caps[(k + 1) % 3]), 11, 96, 96, [(L, False)], 6.0, join, 4.0, (c, caps[(k + 1) % 3])))
+    E.append(StrokeEntry("L-fraction-round", 11, 96, 96, [([(12.3, 20.7), (70.1, 31.9), (40.6, 80.2)], False)], 7.3, "round", 4.0, ("round", "round")))
+    E.append(StrokeEntry("stadium", 11, 96, 96, [([(20.5, 30.25), (70.0, 60.0)], False)], 12.0, "miter", 4.0, ("round", "round")))
+    # --- 12: closed subpaths (the closing join); the outer outline of the mitered ones lies on tile / pixel lines
+    for join in ("miter", "bevel", "round"):
+        E.append(StrokeEntry("rect-%s" % join, 12, 96, 96, [(rect(19, 19, 77, 61), True)], 6.0, join))
+        E.append(StrokeEntry("triangle-%s" % join, 12, 96, 96, [([(20.0, 76.0), (76.0, 76.0), (20.0, 20.0)], True)], 8.0, join))
+    E.append(StrokeEntry("triangle-explicit-close", 12, 96, 96, [([(20.5, 70.25), (80.0, 60.0), (33.0, 12.0), (20.5, 70.25)], True)], 5.0, "miter"))
+    E.append(StrokeEntry("two-subpaths", 12, 96, 96, [([(10.0, 10.0), (40.0, 12.0), (20.0, 40.0)], True),
+                                                       ([(50.0, 50.0), (85.0, 55.0), (60.0, 85.0)], False)], 4.0, "miter", 4.0, ("square", "butt")))
+    # --- 13: turning angles.  Limit 4 flips at an interior angle of 28.955 degrees, 1.5 at 83.62, 10 at 11.48
+    for ang in (5.0, 28.0, 28.9, 29.0, 30.0, 90.0, 150.0, 175.0, 179.9):
+        for mirror in (False, True):
+            E.append(StrokeEntry("angle-%g%s" % (ang, "-mirror" if mirror else ""), 13, 128, 96,
+                                 [(corner((90.25, 48.5), 60.0, ang, mirror), False)], 6.0, "miter", 4.0))
+    for limit, ang in ((1.5, 80.0), (1.5, 90.0), (10.0, 10.0), (10.0, 15.0)):
+        for mirror in (False, True):
+            E.append(StrokeEntry("limit-%g-angle-%g%s" % (limit, ang, "-mirror" if mirror else ""), 13, 128, 96,
+                                 [(corner((90.25, 48.5), 60.0, ang, mirror, 10.0), False)], 6.0, "miter", limit))
+    for join in ("miter", "bevel", "round"):
+        E.append(StrokeEntry("reversal-%s" % join, 13, 96, 96, [([(20.0, 40.5), (70.0, 40.5), (35.0, 40.5)], False)], 8.0, join))
+        E.append(StrokeEntry("collinear-%s" % join, 13, 96, 96, [([(40.5, 10.0), (40.5, 50.0), (40.5, 85.0)], False)], 8.0, join))
+    for ang in (30.0, 90.0, 150.0, 179.0):
+        for mirror in (False, True):
+            E.append(StrokeEntry("round-angle-%g%s" % (ang, "-mirror" if mirror else ""), 13, 128, 96,
+                                 [(corner((84.25, 48.5), 55.0, ang, mirror, -7.0), False)], 9.0, "round"))
+    # --- 14: extremes
+    stairs = [(30.0 + 10.0 * ((i + 1) // 2), 30.0 + 10.0 * (i // 2)) for i in range(8)]
+    E.append(StrokeEntry("w40-on-segments-of-10", 14, 128, 128, [(stairs, False)], 40.0, "miter", 4.0, ("square", "butt")))
+    E.append(StrokeEntry("w40-on-segments-of-10-round", 14, 128, 128, [(stairs, False)], 40.0, "round", 4.0, ("round", "round")))
+    zz = [(10.0 + 19.25 * i, 30.0 + 41.5 * (i % 2)) for i in range(5)]
+    E.append(StrokeEntry("w0.05", 14, 96, 96, [(zz, False)], 0.05, "miter"))
+    E.append(StrokeEntry("w0.3", 14, 96, 96, [(zz, False)], 0.3, "miter", 4.0, ("square", "square")))
+    E.append(StrokeEntry("w0.3-round-join", 14, 96, 96, [(zz, False)], 0.3, "round"))          # arcs of one line
+    E.append(StrokeEntry("w0.6-round", 14, 96, 96, [(zz, False)], 0.6, "round", 4.0, ("round", "round")))
+    joins = [(17.25 + 13.5 * (i % 2), 17.0 + 0.14 * i) for i in range(102)]
+    E.append(StrokeEntry("100-joins-one-tile", 14, 64, 64, [(joins, False)], 1.0, "miter"))
+    E.append(StrokeEntry("100-joins-one-tile-bevel", 14, 64, 64, [(joins, False)], 0.5, "bevel", 4.0, ("square", "square")))
+    out = [(-20.0, 30.0), (48.0, -25.0), (120.0, 50.0), (40.0, 125.0), (-25.0, 60.0)]
+    E.append(StrokeEntry("leaves-all-sides", 14, 96, 96, [(out, False)], 9.0, "miter"))
+    E.append(StrokeEntry("leaves-all-sides-round-closed", 14, 96, 96, [(out, True)], 9.0, "round"))
+    zl = [(20.0, 25.5), (60.25, 30.0), (60.25, 30.0), (30.0, 75.0)]
+    E.append(StrokeEntry("zero-length-segment", 14, 96, 96, [(zl, False)], 5.0, "miter", 4.0, ("square", "round")))
+    E.append(StrokeEntry("zero-length-segment-removed", 14, 96, 96, [(zl[:2] + zl[3:], False)], 5.0, "miter", 4.0, ("square", "round")))
+    rng = np.random.default_rng(20261017)
+    E.append(StrokeEntry("random-12-open", 14, 96, 96, [(rng.uniform(8, 88, (12, 2)), False)], 3.0, "miter", 4.0, ("butt", "square")))
+    E.append(StrokeEntry("random-12-closed", 14, 96, 96, [(rng.uniform(8, 88, (12, 2)), True)], 3.0, "miter"))
+    E.append(StrokeEntry("random-12-closed-round", 14, 96, 96, [(rng.uniform(8, 88, (12, 2)), True)], 4.5, "round"))
+    # a round cap of 60 lines: radius 735, its arc crosses the viewport near y = 25
+    E.append(StrokeEntry("round-cap-60-lines", 14, 96, 96, [([(48.0, 760.0), (48.0, 900.0)], False)], 1470.0, "miter", 4.0, ("round", "butt")))
+    # --- 15: transforms (class "stroke-xform")
+    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
+    Lx = [(4.0, 6.0), (40.0, 8.5), (30.0, 36.0)]
+    for join, cp in (("miter", ("butt", "square")), ("round", ("round", "round"))):
+        E.append(StrokeEntry("rotate-30-%s" % join, 15, 64, 64, [(Lx, False)], 5.0, join, 4.0, cp, (c, s, -s, c, 22.0, 4.0)))
+        E.append(StrokeEntry("scale-3x0.5-%s" % join, 15, 144, 32, [(Lx, False)], 5.0, join, 4.0, cp, (3.0, 0.0, 0.0, 0.5, 6.5, 3.25)))
+        E.append(StrokeEntry("skew-%s" % join, 15, 96, 64, [(Lx, False)], 5.0, join, 4.0, cp, (1.0, 0.0, 0.75, 1.0, 4.0, 10.0)))
+        E.append(StrokeEntry("mirror-%s" % join, 15, 64, 64, [(Lx, False)], 5.0, join, 4.0, cp, (-1.0, 0.0, 0.0, 1.0, 60.0, 8.0)))
+        E.append(StrokeEntry("zoom-40-w0.8-%s" % join, 15, 96, 96, [([(0.3, 0.4), (1.7, 0.55), (1.2, 1.9)], False)], 0.8, join, 4.0, cp,
+                             (40.0, 0.0, 0.0, 40.0, 2.0, 3.0)))
+        E.append(StrokeEntry("shrink-8-w200-%s" % join, 15, 288, 128, [([(250.0, 300.0), (1900.0, 420.0), (1500.0, 800.0)], False)], 200.0, join,
+                             4.0, cp, (0.125, 0.0, 0.0, 0.125, 3.0, -10.0)))
+    E.append(StrokeEntry("closed-rotate-30-round", 15, 64, 64, [([(6.0, 6.0), (38.0, 9.0), (20.0, 34.0)], True)], 4.0, "round", 4.0,
+                         ("butt", "butt"), (c, s, -s, c, 22.0, 4.0)))
+    return E
+
+
 BATTERY = _battery()
+STROKE_BATTERY = _stroke_battery()
+# these stroke entries are rendered again inside a viewport clip and with an opaque gradient
+STROKE_VARIANT_ENTRIES = ["f11-L-miter-butt-square", "f12-triangle-round", "f14-leaves-all-sides"]
 # family 10: these entries of families 1-5 are rendered again inside a viewport clip and with an opaque gradient
 VARIANT_ENTRIES = ["f1-tile-lines", "f1-tile-lines-2^-10", "f1-viewport", "f2-left-shallow", "f2-left-only", "f2-cover-w2",
                    "f3-near-horizontal-one-tile-row", "f3-tile-corners", "f4-sliver-1e-4", "f5-star-7", "f5-zigzag-one-tile"]
-BY_ID = {e.id: e for e in BATTERY}
+BY_ID = {e.id: e for e in BATTERY + STROKE_BATTERY}

@@ -151,11 +151,21 @@ def sample_alpha(wind, rule):
 
 def near_samples(contours, width, height, samples, delta):
     """(height, width) int: the number k of a pixel's samples within `delta` (< 1) of some edge, end points included."""
+    return near_mask(contours, width, height, samples, delta).sum(axis=-1)
+
+
+def near_mask(contours, width, height, samples, delta):
+    """(height, width, samples) bool: the samples that an edge may misclassify.  In a pixel that the edge passes through
+    or ends in, fine looks every sample of the rows the edge spans up in the mask LUT of the edge's LINE -- an edge that
+    ends inside the pixel is cut by sample row only (fine.wgsl:308-315), never along its length -- so there the
+    distance is taken from the line; a horizontal edge cuts no row at all, and a sample beyond its end point but within
+    `delta` of its line is classified by the quantised LUT line like any other.  In the eight pixels around such a
+    pixel the distance is taken from the edge itself, end points included (`delta` < 1)."""
     e = edges_of(contours)
     e = e[(e[:, 0] != e[:, 2]) | (e[:, 1] != e[:, 3])]
     near = np.zeros((height, width, samples), bool)
     if len(e) == 0:
-        return near.sum(axis=-1)
+        return near
     _, _, _, _, col, row, i = _pieces(e, width, height)
     horiz = e[:, 1] == e[:, 3]                     # horizontal edges have no pieces of their own: add their cells
     for j in np.flatnonzero(horiz):
@@ -164,6 +174,7 @@ def near_samples(contours, width, height, samples, delta):
         col = np.concatenate([col, c])
         row = np.concatenate([row, np.full(len(c), int(np.floor(y)))])
         i = np.concatenate([i, np.full(len(c), j)])
+    own = np.unique((i * (height + 2) + row) * (width + 2) + col)     # (edge, pixel) pairs the edge has a piece in
     off = np.array([(dc, dr) for dc in (-1, 0, 1) for dr in (-1, 0, 1)])
     col = (col[:, None] + off[None, :, 0]).ravel()
     row = (row[:, None] + off[None, :, 1]).ravel()
@@ -171,6 +182,7 @@ def near_samples(contours, width, height, samples, delta):
     ok = (col >= 0) & (col < width) & (row >= 0) & (row < height)
     col, row, i = col[ok], row[ok], i[ok]
     key = np.unique((i * (height + 2) + row) * (width + 2) + col)
+    on_line = np.isin(key, own)
     col = key % (width + 2)
     row = (key // (width + 2)) % (height + 2)
     i = key // ((width + 2) * (height + 2))
@@ -179,11 +191,12 @@ def near_samples(contours, width, height, samples, delta):
     qy = row[:, None] + sp[None, :, 1]
     x0, y0, x1, y1 = (e[i, k][:, None] for k in range(4))
     dx, dy = x1 - x0, y1 - y0
-    t = np.clip(((qx - x0) * dx + (qy - y0) * dy) / (dx * dx + dy * dy), 0.0, 1.0)
+    t = ((qx - x0) * dx + (qy - y0) * dy) / (dx * dx + dy * dy)
+    t = np.where(on_line[:, None], t, np.clip(t, 0.0, 1.0))
     d = np.hypot(qx - (x0 + t * dx), qy - (y0 + t * dy))
     r, s = np.nonzero(d <= delta)
     near[row[r], col[r], s] = True
-    return near.sum(axis=-1)
+    return near
 
 
 def lut_from_definition(samples):

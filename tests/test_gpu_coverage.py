@@ -30,6 +30,35 @@ Area tolerance of a pixel, one term per source (fine.wgsl / path_tiling.wgsl lin
                                                                       in every pixel left or right of a piece (test_
                                                                       coverage_spec.test_fine_area_formula_...)
 
+  arc         line of an      (n - 1) * r * (5 * 2^-24 + dtheta),     flatten.wgsl:490-517: vertex i of an arc of n
+              arc, added to   dtheta = 2^-24 * (1 / sin(theta / 2)    lines is the begin point rotated i <= n - 1 times
+              f32 for that    + 3 theta), r the largest device        in f32.  One step rounds two products and a sum
+              line alone      distance of a vertex from the centre    per component (<= 2^-24 r (1 + 1 + sqrt 2)) with
+                                                                      cs, sn rounded once each (<= 2^-24 r sqrt 2): 5.
+                                                                      theta = 2 acos(1 - 0.25 / radius): the rounding of
+                                                                      1 - x (<= 2^-25) is divided by sin(theta / 2) and
+                                                                      doubled, acos and the radius round once more
+                                                                      (<= 3 * 2^-24 theta); step i is off by i dtheta.
+                                                                      Linear in n: 1.3e-4 px for a cap of radius 20
+                                                                      (10 lines), 0.11 for the 61 lines of radius 735
+
+The f32 constant per class, in units of 2^-24 * max|coordinate| (device pixels, at least the target's size):
+
+  class          C_F32     roundings counted
+  ident          4         path_tiling's intersection: a difference, a quotient, a product, a sum
+  large, xform   8         the same, and the transform's two products and two sums per coordinate
+  stroke         16        the tangent's difference, its normalisation (square, sum, root, quotient), the product with
+                           w / 2 and the sum with the point, for both ends of a line; for the miter point the difference
+                           of the two offset points, the cross product, the quotient by cr and the final product and
+                           difference.  The quotient by cr does not amplify: it moves the miter point ALONG the next
+                           edge by err / |cr|, which moves the previous edge across by err (the cross product again).
+  stroke-xform   16 * |T| * max|local coordinate| + 8 * max|device coordinate|: the normal and the miter point are
+                           computed in f32 in LOCAL space, and that error is stretched by the transform (|T|: the
+                           larger absolute row sum of its linear part, errors being bounded per coordinate); then the
+                           f32 transform of the outline points as in class "xform".  At a 40x zoom of local
+                           coordinates near 2 both parts are about the same; at a 1/8 shrink of coordinates near 2000
+                           the local part is twice the device part.
+
 "edge in the row, tile" counts the distinct edges that touch the pixel's row inside its tile at or left of the pixel
 (a moved crossing changes the cover of everything right of it in the tile).  For the identity classes the bound of a
 pixel crossed by one edge away from tile corners is about 2.4e-4 + 1e-5; next to a tile corner it is near 1.3e-3 per
@@ -37,7 +66,11 @@ edge (2e-3 for the two edges of a rectangle corner).  Only pieces that are nearl
 inside their pixel get a cancellation term above 2e-4: 1e-3 of width already brings it below 1.2e-4 * h.
 
 MSAA: delta (exact_coverage.msaa_delta) = 0.0558 px for 8 samples, 0.0286 px for 16 (LUT quantisation + the 1e-3 clamp),
-plus the f32 term above.  Counts k / S are exact in f16.
+plus the f32 term above (and the arc term around the lines of an arc).  Counts k / S are exact in f16.  The band is
+measured from the edge's LINE in every pixel the edge has a piece in, and from the edge itself in the pixels around
+them: fine classifies the samples of such a pixel against the LUT line and cuts an edge that ends inside it by sample
+row only, so a sample past the end point of a near-horizontal edge but within delta of its line can be misread like
+any other sample near it (exact_coverage.near_mask; found by f3-near-vertical-cap-end).
 
 Section-5 allowance (GPU = oracle != reference, explained by the WGSL): fill_path_ms_evenodd sets is_bump = xy0.x == 0
 for the first pixel of a segment (fine.wgsl:623) without the `y0i != xy0.y` test of fill_path_ms (fine.wgsl:282),
@@ -66,6 +99,7 @@ import exact_coverage as X
 pytestmark = pytest.mark.gpu
 
 C_F32 = {"ident": 4.0, "large": 8.0, "xform": 8.0, "stroke": 16.0}
+ROTATION = 5.0      # roundings of one rotation step of flatten_arc, per component, in units of 2^-24 * radius
 NUDGE = 2e-6
 CANCEL = 2.0 ** -24
 DELTA = {8: X.msaa_delta(8), 16: X.msaa_delta(16)}
@@ -89,7 +123,27 @@ def _edges(entry):
 
 
 def f32_term(entry):
+    if entry.tclass == "stroke-xform":
+        return 2.0 ** -24 * (C_F32["stroke"] * entry.transform_norm() * entry.max_local_coordinate() +
+                             C_F32["xform"] * entry.max_coordinate())
     return C_F32[entry.tclass] * 2.0 ** -24 * entry.max_coordinate()
+
+
+def arc_term(arc):
+    """The distance by which the f32 vertices of one arc may leave their float64 positions, beyond f32_term (table
+    above, row "arc"): vertex i is rotated i <= n - 1 times."""
+    r = float(np.hypot(*(arc.device - arc.centre).T).max())     # no vertex is farther from the centre than this
+    dtheta = 2.0 ** -24 * (1.0 / np.sin(0.5 * arc.theta) + 3.0 * arc.theta)
+    return (arc.n - 1) * r * (ROTATION * 2.0 ** -24 + dtheta)
+
+
+def edge_extra(entry):
+    """Per edge of _edges(entry): what its end points may be off by beyond f32_term(entry) (the lines of arcs only)."""
+    e = X.edges_of(entry.reference_contours())
+    extra = np.zeros(len(e))
+    for i, arc in (entry.arc_edges() if hasattr(entry, "arc_edges") else ()):
+        extra[i] = max(extra[i], arc_term(arc))
+    return extra[(e[:, 0] != e[:, 2]) | (e[:, 1] != e[:, 3])]
 
 
 def area_tolerance(entry, value):
@@ -114,6 +168,12 @@ def area_tolerance(entry, value):
     for t0 in range(0, W, 16):
         per_row[:, t0:t0 + 16] = np.cumsum(starts[:, t0:min(t0 + 16, W)], axis=1)
     tol = tol + per_row * (f32_term(entry) + NUDGE)
+    extra = edge_extra(entry)
+    if extra.any():        # the lines of arcs: their own term, counted like the edges themselves
+        starts = np.zeros((H, W + 1))
+        np.add.at(starts, (krow, mincol), extra[key % len(e)])
+        for t0 in range(0, W, 16):
+            tol[:, t0:t0 + 16] += np.cumsum(starts[:, t0:min(t0 + 16, W)], axis=1)
     # cancellation in fine's area formula, in the pixel that holds the piece.  Beside a piece the formula is exact
     # (b, c, d and xmin are the constants 1, 1, 1 - 1e-6 left of it, and a = 1 exactly right of it).  For transformed
     # or computed outlines an edge on a pixel line may land just left of it: give the left neighbour the full term.
@@ -124,7 +184,7 @@ def area_tolerance(entry, value):
     np.add.at(cancel, (row[inside], col[inside]), CANCEL * (2 * m * m + 2 * m) / (w[inside] + 1e-6) * h[inside])
     if entry.tclass != "ident":
         lx = np.minimum(xa, xb)[inside] - col[inside]
-        left = (col[inside] >= 1) & (lx <= f32_term(entry))
+        left = (col[inside] >= 1) & (lx <= f32_term(entry) + extra[i[inside]])
         np.add.at(cancel, (row[inside][left], col[inside][left] - 1), CANCEL * 4.0 / (w[inside][left] + 1e-6) * h[inside][left])
     tol = tol + cancel
     # the 1e-3 clamp: edges within 1e-3 of the top-left, top-right or bottom-left corner of the tile
@@ -135,7 +195,7 @@ def area_tolerance(entry, value):
     dx, dy = x1 - x0, y1 - y0
     t = np.clip(((cx - x0) * dx + (cy - y0) * dy) / (dx * dx + dy * dy), 0.0, 1.0)
     d = np.hypot(cx - (x0 + t * dx), cy - (y0 + t * dy))
-    near = (d <= X.TILE_CLAMP + f32_term(entry)).sum(axis=0).reshape(ht + 1, wt + 1)
+    near = (d <= X.TILE_CLAMP + f32_term(entry) + extra[:, None]).sum(axis=0).reshape(ht + 1, wt + 1)
     n_tile = near[:-1, :-1] + near[:-1, 1:] + near[1:, :-1]
     clamp = np.repeat(np.repeat(n_tile, 16, axis=0), 16, axis=1)[:H, :W] * X.TILE_CLAMP
     return tol + clamp
@@ -171,7 +231,14 @@ def check(entry, rule, aa, alpha):
     else:
         S = 8 if aa == "msaa8" else 16
         want = X.sample_alpha(X.sample_winding(ref, W, H, S), rule)
-        k = X.near_samples(ref, W, H, S, DELTA[S] + f32_term(entry))
+        near = X.near_mask(ref, W, H, S, DELTA[S] + f32_term(entry))
+        extra = edge_extra(entry)
+        if extra.any():    # the lines of arcs: a wider band by their own term, around those lines alone
+            e = _edges(entry)
+            for x in np.unique(extra[extra > 0]):
+                lines = [l.reshape(2, 2) for l in e[extra == x]]
+                near |= X.near_mask(lines, W, H, S, DELTA[S] + f32_term(entry) + x)
+        k = near.sum(axis=-1)
         err = np.abs(alpha - want)
         if rule == "evenodd" and entry.id in EVENODD_MSAA_ROW_FLIP:
             flip = evenodd_row_flip_mask(entry)
