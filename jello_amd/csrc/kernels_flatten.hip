@@ -967,8 +967,10 @@ JD void run_item(const JlConfig* cfg, const Scene& s, Out<EMIT>& o, uint32_t slo
 // pieces before it -- is filled in when the batch has drained: every piece adds up the line counts of its job's
 // pieces with a smaller t0 (a linked list per job in LDS; a job has ~5 pieces).
 // Bounds: the stack is LIFO, so it holds at most 64 nodes per tree level (+128); if it or the piece list of a batch
-// overflows, or a tree goes deeper than FLQ_MAX_LEVEL (dt < 2^-9; none of the test scenes goes below 2^-6), the
-// unfinished jobs of the batch fall back to the sequential walk.
+// overflows, or a tree goes deeper than FLQ_MAX_LEVEL (dt < 2^-9), the unfinished jobs of the batch fall back to the
+// sequential walk.  The benchmark scenes stay above 2^-6; family 18 of tests/coverage_scenes.py goes to 2^-9 (the last
+// cooperative level), 2^-11 and 2^-13 (the walk) and has a scene of 64 cubics with 23 pieces each (the piece
+// list of a batch overflows); tests/test_gpu_curves.py holds the product build to the oracle's lines on them.
 // ------------------------------------------------------------------------------------------------
 // (capacities, overridable only so that tools/soak_flatten_fallback.sh can force the fall-back: results do not depend on them)
 #ifndef FLQ_STACK

@@ -490,6 +490,13 @@ extern "C" size_t oracle_flatten_pairs_count() { return g_flatten_pairs_n; }
 extern "C" void oracle_flatten_stats(uint64_t* out, int reset) {
     for (int i = 0; i < 32; i++) { out[i] = g_flatten_stats[i]; if (reset) g_flatten_stats[i] = 0; }
 }
+// instrumentation only (tests/test_curve_spec.py): pieces per route of the serial form -- [robust normal, low k1, low dist,
+// pieces of exactly 100 lines (the clamp), pieces accepted at SUBDIV_LIMIT with the error still above tol, end-point
+// derivatives replaced at DERIV_THRESH, pieces whose chord is below DERIV_THRESH, most lines in one piece]
+static uint64_t g_flatten_routes[8];
+extern "C" void oracle_flatten_routes(uint64_t* out, int reset) {
+    for (int i = 0; i < 8; i++) { out[i] = g_flatten_routes[i]; if (reset) g_flatten_routes[i] = 0; }
+}
 static void flatten_euler(Ctx& c, const CubicPoints& cubic, uint32_t path_ix, const Transform& local_to_device,
                           float offset, V2 start_p, V2 end_p) {
     V2 p0, p1, p2, p3;
@@ -535,6 +542,7 @@ static void flatten_euler(Ctx& c, const CubicPoints& cubic, uint32_t path_ix, co
         if (dot(this_pq1.deriv, this_pq1.deriv) < DERIV_THRESH_SQUARED) {
             PointDeriv new_pq1 = eval_cubic_and_deriv(p0, p1, p2, p3, t1 - DERIV_EPS);
             this_pq1.deriv = new_pq1.deriv;
+            if (!g_oracle_parallel_alloc) g_flatten_routes[5] += 1u;
             if (t1 < 1.0f) {
                 this_pq1.point = new_pq1.point;
                 t1 = t1 - DERIV_EPS;
@@ -603,7 +611,14 @@ static void flatten_euler(Ctx& c, const CubicPoints& cubic, uint32_t path_ix, co
             }
             st_pieces++;
             { uint32_t d = 0u; float q = dt; while (q < 1.0f && d < 19u) { q *= 2.0f; d++; } if (d > st_depth) st_depth = d; }
-            if (!g_oracle_parallel_alloc) g_flatten_stats[2] += n_u;
+            if (!g_oracle_parallel_alloc) {
+                g_flatten_stats[2] += n_u;
+                g_flatten_routes[robust] += 1u;
+                if (n_u == 100u) g_flatten_routes[3] += 1u;
+                if (!(cp.err * scale <= tol)) g_flatten_routes[4] += 1u;
+                if (cp.th0 == 0.0f && cp.th1 == 0.0f && cp.chord_len == DERIV_THRESH) g_flatten_routes[6] += 1u;
+                if (n_u > g_flatten_routes[7]) g_flatten_routes[7] = n_u;
+            }
             last_p = this_pq1.point;
             last_q = this_pq1.deriv;
             last_t = t1;

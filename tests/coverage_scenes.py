@@ -20,7 +20,14 @@ STROKE_BATTERY holds stroked polylines (StrokeEntry), whose reference outline is
 rendered non-zero only (the outline overlaps itself at every join): 11 joins x caps on an open L, 12 closed subpaths,
 13 turning angles and miter limits, 14 extremes, 15 transforms.  The encoder writes every path point as f32 (it has no
 i16 form to choose), so there is no entry per point format.  Family 3 also holds the outline that showed how far the
-MSAA band reaches past the end of an edge (near-vertical-cap-end) and its siblings."""
+MSAA band reaches past the end of an edge (near-vertical-cap-end) and its siblings.
+
+CURVE_BATTERY holds curves (CurveEntry), whose reference is tests/exact_curve.py and whose LINES are checked
+(tests/test_curve_spec.py on the oracle, tests/test_gpu_curves.py on the HIP line buffer): 16 one filled cubic (plain,
+loop, cusps, inflection, sub-pixel), 17 degenerate control polygons, 18 deep subdivision trees, a full batch, long and
+clamped pieces, 19 quads and contours of several segments, 20 transforms and large coordinates, 21 stroked cubics at
+widths 0.3 ... 120, 22 joins between cubics, round caps and strokes under transforms.  Every entry names the route of
+the flattener it is there for; test_curve_spec.test_the_battery_reaches_its_routes holds it to that."""
 import math
 
 import numpy as np
@@ -386,11 +393,198 @@ def _stroke_battery():
     return E
 
 
+class CurveEntry:
+    """Curves (families 16-22) for tests/test_curve_spec.py and tests/test_gpu_curves.py, whose reference is
+    tests/exact_curve.py.  `paths` is a list of paths, each a list of subpaths (start point, segments); a segment is
+    the tuple of its remaining control points: one (line), two (quad) or three (cubic).  A fill draws every path as its
+    own non-zero fill (the encoder closes each subpath with a line unless it ends on its start point, bit for bit); a
+    stroke entry has one path of one open subpath and `stroke` = (width, join, miter limit, start cap, end cap).
+    `route` says what the entry is there for; `unbounded` says why the shader promises no distance for it (a piece
+    accepted at SUBDIV_LIMIT without an error test, a piece clamped to 100 lines): the structure checks still hold."""
+    def __init__(self, name, family, width, height, paths, route, tclass=None, transform=None, stroke=None, unbounded=None):
+        self.name, self.family, self.width, self.height = name, family, width, height
+        self.paths = [[(tuple(start), [tuple(tuple(q) for q in seg) for seg in segs]) for start, segs in path] for path in paths]
+        self.route, self.transform, self.stroke, self.unbounded = route, transform, stroke, unbounded
+        if tclass is None:
+            tclass = ("stroke" if transform is None else "stroke-xform") if stroke else ("ident" if transform is None else "xform")
+        self.tclass = tclass
+
+    @property
+    def id(self):
+        return "f%d-%s" % (self.family, self.name)
+
+    def path(self, k):
+        p = Path()
+        for start, segs in self.paths[k]:
+            p.move_to(*start)
+            for seg in segs:
+                flat = [float(v) for q in seg for v in q]
+                {1: p.line_to, 2: p.quad_to, 3: p.cubic_to}[len(seg)](*flat)
+        return p
+
+    def control_points(self, k=None):
+        """Per subpath of path k (or of all paths): the control polygons of its segments, f32 values, local space."""
+        out = []
+        for path in (self.paths if k is None else [self.paths[k]]):
+            for start, segs in path:
+                cur, polys = start, []
+                for seg in segs:
+                    polys.append(f32([cur] + list(seg)))
+                    cur = seg[-1]
+                out.append(polys)
+        return out
+
+    def transform_norm(self):
+        if self.transform is None:
+            return 1.0
+        a, b, c, d, _, _ = self.transform
+        return max(abs(a) + abs(c), abs(b) + abs(d))
+
+    def _local_points(self):
+        return np.concatenate([p for polys in self.control_points() for p in polys])
+
+    def max_local_coordinate(self):
+        half = 0.5 * self.stroke[0] if self.stroke else 0.0
+        return float(np.abs(self._local_points()).max()) + half
+
+    def max_coordinate(self):
+        """The control polygon bounds the curve, and the roundings of an f32 evaluation scale with its points."""
+        p = self._local_points()
+        if self.transform is not None:
+            a, b, c, d, e, f = f32(self.transform)
+            p = np.stack([a * p[:, 0] + c * p[:, 1] + e, b * p[:, 0] + d * p[:, 1] + f], axis=1)
+        half = 0.5 * self.stroke[0] * self.transform_norm() if self.stroke else 0.0
+        return max(self.width, self.height, 16, float(np.abs(p).max()) + half)
+
+    def scene(self, rule="nonzero", variant="plain"):
+        s = Scene()
+        brush = Brush.solid(WHITE)
+        for k in range(len(self.paths)):
+            if self.stroke:
+                w, join, limit, cap0, cap1 = self.stroke
+                s.stroke(Stroke(w, JOINS[join], limit, CAPS[cap0], CAPS[cap1]), self.transform, brush, None, self.path(k))
+            else:
+                s.fill(Fill.NonZero if rule == "nonzero" else Fill.EvenOdd, self.transform, brush, None, self.path(k))
+        return s
+
+    def params(self, aa):
+        return RenderParams(self.width, self.height, aa=aa)
+
+
+PLAIN = [(40, 40), (200, 400), (300, 20), (460, 300)]
+LOOP = [(100, 300), (450, 50), (50, 50), (400, 300)]
+CUSP = [(100, 400), (400, 100), (100, 100), (400, 400)]          # c'(1/2) = 0 exactly, symmetric about x = 250
+CUSP_SHEARED = [(150, 400), (375, 100), (75, 100), (450, 400)]   # its image under x + y / 4 - 50: a cusp, not symmetric
+ESS = [(60, 250), (250, -50), (260, 550), (450, 250)]
+
+
+def hairpin(right, left, dx=0.0):
+    return [(100 + dx, 100), (right + dx, 110), (left + dx, 120), (120 + dx, 130)]
+
+
+HAIRPIN = hairpin(4000, -3000)
+TWO_SMOOTH = [(60, 300), [((100, 100), (200, 80), (260, 200)), ((320, 320), (380, 440), (460, 200))]]   # tangent (60, 120) both sides
+TWO_CORNER = [(60, 300), [((100, 100), (200, 80), (260, 200)), ((380, 140), (400, 300), (460, 380))]]   # (60, 120) then (120, -60)
+
+
+def one(points):
+    return [[(points[0], [tuple(points[1:])])]]
+
+
+def _curve_battery():
+    E = []
+    BUTT = ("butt", "butt")
+    # --- 16: one cubic, filled
+    E.append(CurveEntry("plain", 16, 512, 512, one(PLAIN), "cooperative subdivision, depth 3"))
+    E.append(CurveEntry("loop", 16, 512, 512, one(LOOP), "a self-crossing"))
+    E.append(CurveEntry("cusp", 16, 512, 512, one(CUSP), "an exact, symmetric cusp: the derivative vanishes at a subdivision point"))
+    E.append(CurveEntry("cusp-sheared", 16, 512, 512, one(CUSP_SHEARED), "an exact cusp that is not symmetric"))
+    E.append(CurveEntry("ess", 16, 512, 512, one(ESS), "an inflection"))
+    E.append(CurveEntry("sub-pixel", 16, 256, 256, one([(100.25, 100.25), (100.5, 100.75), (100.75, 100.0), (100.9, 100.6)]),
+                        "accepted at the root, one line per piece"))
+    # --- 17: degenerate control polygons
+    E.append(CurveEntry("p0=p1", 17, 512, 512, one([(60, 60), (60, 60), (400, 100), (300, 400)]), "vanishing start derivative"))
+    E.append(CurveEntry("p2=p3", 17, 512, 512, one([(60, 400), (100, 100), (420, 300), (420, 300)]), "vanishing end derivative"))
+    E.append(CurveEntry("p0=p1-p2=p3", 17, 512, 512, one([(50, 70), (50, 70), (450, 390), (450, 390)]),
+                        "a straight line with both end derivatives zero"))
+    E.append(CurveEntry("collinear-doubling-back", 17, 512, 512, one([(100, 100), (500, 200), (-100, 50), (300, 150)]),
+                        "collinear control points: the curve doubles back on its own line, between its end points"))
+    E.append(CurveEntry("collinear-overshoot", 17, 512, 512, one([(100, 100), (1000, 325), (-600, -75), (300, 150)]),
+                        "collinear control points: the curve runs up to 88 px past its end points on its own line",
+                        unbounded="both end tangents lie along the chord: th0 = th1 = 0 makes every term of flatten.wgsl's error "
+                                  "measure zero, the root is accepted and becomes the one line p0 -> p3"))
+    E.append(CurveEntry("all-equal", 17, 512, 512, [[((200, 200), [((200, 200), (200, 200), (200, 200))]),
+                                                      (PLAIN[0], [tuple(PLAIN[1:])])]],
+                        "a subpath whose four points are equal adds no line"))
+    # --- 18: deep subdivision trees, full batches, long pieces
+    E.append(CurveEntry("hairpin-4000", 18, 512, 512, one(HAIRPIN), "depth 9: the last level of the cooperative route"))
+    E.append(CurveEntry("hairpin-1e5", 18, 512, 512, one(hairpin(1e5, -1e5)), "depth >= 10: the sequential walk"))
+    E.append(CurveEntry("hairpin-1e6", 18, 512, 512, one(hairpin(1e6, -1e6)), "depth >= 13: the sequential walk"))
+    E.append(CurveEntry("hairpins-64", 18, 512, 512, [one(hairpin(4000, -3000, float(i)))[0] for i in range(64)],
+                        "more than 640 pieces from the 64 jobs of one batch: the piece list overflows"))
+    E.append(CurveEntry("large-arc", 18, 512, 512, one([(0, 0), (0, 60000), (60000, 60000), (60000, 0)]),
+                        "long pieces of up to 27 lines", tclass="large"))
+    R, phi = 3e6, 0.3          # the arc's last 0.3 rad before its top at (256, 256)
+    kk = 4.0 / 3.0 * math.tan(phi / 4) * R
+    a0 = (256 - R * math.sin(phi), 256 + R - R * math.cos(phi))
+    E.append(CurveEntry("clamped-arc", 18, 512, 512, one([a0, (a0[0] + kk * math.cos(phi), a0[1] - kk * math.sin(phi)), (256 - kk, 256), (256, 256)]),
+                        "0.3 rad of a circle of radius 3e6: pieces at the clamp of 100 lines", tclass="large",
+                        unbounded="a piece that needs more than 100 lines gets 100: their sagitta is whatever that gives"))
+    # --- 19: quads, contours of several segments
+    E.append(CurveEntry("quad", 19, 512, 512, [[((40, 60), [((300, 480), (470, 90))])]], "a quad, raised to a cubic in f32"))
+    E.append(CurveEntry("quad-p1=p2", 19, 512, 512, [[((60, 60), [((400, 300), (400, 300))])]], "a quad whose end derivative vanishes"))
+    E.append(CurveEntry("quad-hairpin", 19, 512, 512, [[((100, 100), [((5000, 115), (120, 130))])]], "a quad that turns back"))
+    k = 0.6
+    cx, cy, r = 250.5, 240.25, 180.0
+    four = [((cx + r, cy), [((cx + r, cy + k * r), (cx + k * r, cy + r), (cx, cy + r)),
+                            ((cx - k * r, cy + r), (cx - r, cy + k * r), (cx - r, cy)),
+                            ((cx - r, cy - k * r), (cx - k * r, cy - r), (cx, cy - r)),
+                            ((cx + k * r, cy - r), (cx + r, cy - k * r), (cx + r, cy))])]
+    E.append(CurveEntry("four-cubics", 19, 512, 512, [four], "a closed contour: the last cubic ends on the start point, no closing line"))
+    mixed = [((50, 60), [((200, 40),), ((330, 30), (420, 160)), ((500, 300), (300, 330), (380, 460)), ((120, 470),),
+                         ((20, 400), (90, 250))])]
+    E.append(CurveEntry("mixed", 19, 512, 512, [mixed], "lines, quads and cubics in one contour, closed by the encoder's line"))
+    # --- 20: transforms and large coordinates
+    E.append(CurveEntry("zoom-64", 20, 512, 512, one([(0.5, 0.5), (2.0, 6.0), (4.0, -1.0), (6.5, 5.5)]), "the transform in f32",
+                        transform=(64.0, 0.0, 0.0, 64.0, 20.0, 30.0)))
+    E.append(CurveEntry("zoom-3000", 20, 512, 512, one([(0.01, 0.01), (0.05, 0.12), (0.09, -0.02), (0.14, 0.11)]), "the transform in f32",
+                        transform=(3000.0, 0.0, 0.0, 3000.0, 10.0, 90.0)))
+    E.append(CurveEntry("large-3e4", 20, 512, 512, one([(-30000, 200), (100, -29000), (400, 31000), (30500, 300)]),
+                        "absolute f32 coordinates near 3e4", tclass="large"))
+    # --- 21: stroked cubics, butt caps (one segment: the bevel join is never drawn)
+    for name, pts in (("plain", PLAIN), ("loop", LOOP), ("cusp", CUSP), ("ess", ESS), ("hairpin-4000", HAIRPIN)):
+        for w in (0.3, 2.0, 20.0, 120.0):
+            E.append(CurveEntry("stroke-%s-w%g" % (name, w), 21, 512, 512, one(pts), "the offset route of flatten_euler",
+                                stroke=(w, "bevel", 4.0) + BUTT))
+    # --- 22: joins between cubics, a round cap, strokes under transforms
+    for join in ("miter", "round"):
+        E.append(CurveEntry("stroke-smooth-%s" % join, 22, 512, 512, [[TWO_SMOOTH]], "cr = 0 at the join: it adds nothing visible",
+                            stroke=(14.0, join, 4.0) + BUTT))
+        E.append(CurveEntry("stroke-corner-%s" % join, 22, 512, 512, [[TWO_CORNER]], "a 90 degree corner between two cubics",
+                            stroke=(14.0, join, 4.0) + BUTT))
+    E.append(CurveEntry("stroke-round-caps", 22, 512, 512, one(PLAIN), "round caps on a cubic", stroke=(30.0, "bevel", 4.0, "round", "round")))
+    c, s = math.cos(math.radians(30)), math.sin(math.radians(30))
+    small = [(10, 10), (50, 100), (75, 5), (115, 75)]
+    E.append(CurveEntry("stroke-similarity", 22, 512, 512, one(small), "scale = 3 in flatten_euler's offset route",
+                        transform=(3 * c, 3 * s, -3 * s, 3 * c, 150.0, 40.0), stroke=(6.0, "bevel", 4.0) + BUTT))
+    E.append(CurveEntry("stroke-anisotropic", 22, 512, 512, one(small), "flatten_euler's scale formula under an anisotropic transform",
+                        transform=(4.0, 0.0, 1.0, 1.5, 20.0, 60.0), stroke=(6.0, "bevel", 4.0) + BUTT))
+    return E
+
+
+# Not in the battery: the forced acceptance at SUBDIV_LIMIT needs a tree of depth 16, which this family reaches at
+# +-1e8.  There a line of the polyline crosses more than 65535 tiles, past the 16 bits path_count has for a crossing's
+# index in its line, and everything after flatten is undefined (path_tiling reads tiles that nobody wrote).  Only the
+# oracle's flatten stage runs it (tests/test_curve_spec.py).
+SUBDIV_LIMIT_ENTRY = CurveEntry("hairpin-1e8", 18, 512, 512, one(hairpin(1e8, -1e8)),
+                                "depth 16: pieces accepted at SUBDIV_LIMIT whatever their error",
+                                unbounded="SUBDIV_LIMIT accepts a piece without an error test (and one f32 step is 8 px at 1e8)")
 BATTERY = _battery()
 STROKE_BATTERY = _stroke_battery()
+CURVE_BATTERY = _curve_battery()
 # these stroke entries are rendered again inside a viewport clip and with an opaque gradient
 STROKE_VARIANT_ENTRIES = ["f11-L-miter-butt-square", "f12-triangle-round", "f14-leaves-all-sides"]
 # family 10: these entries of families 1-5 are rendered again inside a viewport clip and with an opaque gradient
 VARIANT_ENTRIES = ["f1-tile-lines", "f1-tile-lines-2^-10", "f1-viewport", "f2-left-shallow", "f2-left-only", "f2-cover-w2",
                    "f3-near-horizontal-one-tile-row", "f3-tile-corners", "f4-sliver-1e-4", "f5-star-7", "f5-zigzag-one-tile"]
-BY_ID = {e.id: e for e in BATTERY + STROKE_BATTERY}
+BY_ID = {e.id: e for e in BATTERY + STROKE_BATTERY + CURVE_BATTERY}
