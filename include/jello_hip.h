@@ -359,7 +359,9 @@ uint64_t jh_debug_scratch_bytes(jh_ctx* ctx, int slot);   /* capacity of an inte
 int jh_scratch_trim(jh_ctx* ctx);
 /* tests: bit 0 = every wave of flatten starts in region 0 of its temporary, bit 1 = always eight regions (kernels_flatten.hip,
    FlTemp): ordinary scenes then fill regions up and move on, which the product only does close to the line buffer's capacity;
-   bit 2 = a batch of more than 48 lines allocates its slots job by job (the product: more than 51 200) */
+   bit 2 = a batch of more than 48 lines allocates its slots job by job (the product: more than 51 200);
+   bit 3 = k_flatten_items runs as ONE workgroup: four waves and one unit counter, so that the item counts at which its work
+   distribution changes (a unit of 64 filled exactly, one item more, heavy items only, ...) are scenes of a few hundred shapes */
 int jh_debug_flatten_regions(jh_ctx* ctx, uint32_t flags);
 uint64_t jh_debug_graph_self_cleans(jh_ctx* ctx);  /* replays that had to zero an internal counter first (tests) */
 int jh_debug_poison_scratch(jh_ctx* ctx, int byte);

@@ -759,7 +759,10 @@ JD Seg load_seg(const Scene& s, uint32_t ix) {
 // k_flatten_classify waits for its two returns) and live in different memory channels --, from FL_CTR_CURSOR the cursors of
 // the temporary's regions (FlTemp)
 #define FL_CTR_LIGHT 256u
-#define FL_CTR_WORDS (FL_CTR_CURSOR + FL_CUR_STRIDE * FL_MAX_REGIONS)
+#define FL_CTR_DEAL (FL_CTR_CURSOR + FL_CUR_STRIDE * FL_MAX_REGIONS)  // the unit counters of k_flatten_items' workgroup groups, FL_DEAL_STRIDE words apart
+#define FL_DEAL_GROUPS 256u
+#define FL_DEAL_STRIDE 16u
+#define FL_CTR_WORDS (FL_CTR_DEAL + FL_DEAL_STRIDE * FL_DEAL_GROUPS)
 // The classification: one thread per tag WORD (four tag bytes: the word and its monoid are read once, the bytes' monoids follow from
 // them; up to round 5 a thread took eight tag bytes and fetched word and monoid for each).  SCAN != 0: as an epilogue of the LAST
 // pathtag scan (pathtag_scan.wgsl:24-64 / pathtag_scan_large; the engine holds that dispatch back when flatten follows it,
@@ -1162,22 +1165,43 @@ __device__ uint32_t g_ff_stats[8];  // nodes tested, undecided, contradictions, 
                            // and 149 VGPRs (same box); without the inlined fallback the loop needs 131 and runs in 182 us at 4 waves
 #endif
 #ifndef FL_BLOCKS_PER_CU
-#define FL_BLOCKS_PER_CU 4  // = what is resident at 4 waves per SIMD (round 5, C3, same box: 162 / 139 / 129 / 136 / 138 / 147 us with 2 / 3 / 4 / 5 / 6 / 8;
-                            // a fifth workgroup per CU only starts when one has finished and then has a full share of batches in front of it)
+#define FL_BLOCKS_PER_CU 4  // = what is resident at 4 waves per SIMD, and the workgroups that share one unit counter (C3, same box, with the shared
+                            // counters: 126 / 114 / 115 / 113 us with 3 / 4 / 5 / 6 -- a fifth workgroup per CU only starts when one has finished
+                            // and then finds its group's units nearly gone; profiles/flatten_shares.md)
+#endif
+#ifdef FL_TIMING  // (variant builds only, tools/flatten_timeline.py: when every wave of k_flatten_items ran which unit)
+#define FL_TL_WAVES 8192u
+#define FL_TL_BATCHES 15u
+#define FL_TL_WORDS (2u + 3u * FL_TL_BATCHES)  // entry clock, units run, then per unit: start | heavy << 63, end, pieces | steps of phase A << 16 | bail << 31
+__device__ unsigned long long g_fl_timeline[FL_TL_WAVES * FL_TL_WORDS];
 #endif
 __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_PER_EU, FL_WAVES_PER_EU))) void k_flatten_items(const JlConfig* __restrict__ cfg, Buf<uint32_t> scene, Buf<JlTagMonoid> tag_monoids,
                                                          Buf<JlPathBbox> path_bboxes, const uint32_t* __restrict__ list,
                                                          uint32_t* __restrict__ counters, uint32_t cap, uint32_t* __restrict__ counts,
                                                          FlTemp T, uint32_t debug) {
-    __shared__ uint32_t sh_item;  // next position of this workgroup's share of the item list
     __shared__ FlBatch sh_batch[JL_WG / 64];
     Scene s;
     s.cfg = cfg; s.scene = scene; s.tag_monoids = tag_monoids;
     uint32_t n_heavy = umin_(counters[0], cap), n_light = umin_(counters[FL_CTR_LIGHT], cap - n_heavy);
     uint32_t n = n_heavy + n_light;
-    if (blockIdx.x * 64u >= n) return;  // uniform: this workgroup's share of the list is empty
+    // Work distribution.  The item list is cut into units of 64: the heavy items (Euler jobs) first, then the light ones; no
+    // unit holds both kinds.  The workgroups form n_groups groups -- FL_BLOCKS_PER_CU workgroups each, blockIdx.x mod n_groups,
+    // which puts one workgroup of every dispatch round into a group -- and unit u belongs to group u mod n_groups.  A wave
+    // takes one unit (= one batch) at a time from its group's counter in global memory.  The counter is shared because the
+    // waves of a SIMD do not advance alike: the issue arbiter prefers the older wave, so the workgroups of the first dispatch
+    // round finish a batch in 49 us and those of the fourth in 95 us (C3).  With a share of its own per workgroup the early
+    // ones idled while the late ones still had all their light units in front of them: 128 us against 113 us.  One counter
+    // for the whole device is no alternative (a hot word sustains 60-90 atomics per us), nor are smaller batches: DESIGN 4.2.
+    const uint32_t units_h = n_heavy / 64u + (n_heavy % 64u != 0u ? 1u : 0u);
+    const uint32_t units = units_h + n_light / 64u + (n_light % 64u != 0u ? 1u : 0u);
+    const uint32_t n_groups = umin_(umax_(gridDim.x / FL_BLOCKS_PER_CU, 1u), FL_DEAL_GROUPS), group = blockIdx.x % n_groups;
+    if (group >= units) return;  // uniform: this group's share of the list is empty
+#ifdef FL_TIMING
+    const unsigned long long tl_entry = wall_clock64();
+    const uint32_t tl_wave = blockIdx.x * (JL_WG / 64u) + (threadIdx.x >> 6);
+    uint32_t tl_n = 0u;
+#endif
     atan_tab_fill();
-    if (threadIdx.x == 0) sh_item = 0u;
     __syncthreads();
     const uint32_t lane = lane_id();
     FlBatch& B = sh_batch[threadIdx.x >> 6];
@@ -1188,15 +1212,31 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
     o.home_s = o.home_r = 0u;
 #endif
     o.cursor = 0u; o.a_first = 0u; o.a_spos = 0u; o.a_rpos = 0u;
-    // Work distribution: the item list (heavy items first) is dealt to the workgroups in chunks of 64, round robin; a
-    // wave takes one chunk (= one batch) at a time through the workgroup's LDS counter.
     for (;;) {
-        uint32_t base = 0u;
-        if (lane == 0u) base = atomicAdd(&sh_item, 64u);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        const uint32_t t_first = ((base >> 6) * gridDim.x + blockIdx.x) * 64u;
-        if (t_first >= n) break;
+        uint32_t k = 0u;
+        if (lane == 0u) k = atomicAdd(&counters[FL_CTR_DEAL + FL_DEAL_STRIDE * group], 1u);
+        k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+        const uint32_t u = k * n_groups + group;
+        if (u >= units) break;
+        const bool heavy = u < units_h;  // uniform
+        const uint32_t t_first = heavy ? u * 64u : n_heavy + (u - units_h) * 64u;
+        const uint32_t t_end = umin_(t_first + 64u, heavy ? n_heavy : n);
         const uint32_t t = t_first + lane;
+#ifdef FL_TIMING
+        const unsigned long long tl_start = wall_clock64() | (heavy ? 1ull << 63 : 0ull);
+        uint32_t tl_info = 0u;
+#define FL_TL_END()                                                                                      \
+    do {                                                                                                 \
+        if (lane == 0u && tl_wave < FL_TL_WAVES && tl_n < FL_TL_BATCHES) {                               \
+            g_fl_timeline[tl_wave * FL_TL_WORDS + 2u + 3u * tl_n] = tl_start;                            \
+            g_fl_timeline[tl_wave * FL_TL_WORDS + 3u + 3u * tl_n] = wall_clock64();                      \
+            g_fl_timeline[tl_wave * FL_TL_WORDS + 4u + 3u * tl_n] = tl_info;                             \
+        }                                                                                                \
+        tl_n++;                                                                                          \
+    } while (0)
+#else
+#define FL_TL_END() do {} while (0)
+#endif
         // (a region of the temporary that is full is left behind at this uniform point)
         if (__builtin_amdgcn_ballot_w64(o.failed_s) != 0ull) { o.home_s = fl_next_home(T, o.home_s, 0); o.failed_s = false; }
         if (__builtin_amdgcn_ballot_w64(o.failed_r) != 0ull) { o.home_r = fl_next_home(T, o.home_r, 1); o.failed_r = false; }
@@ -1207,8 +1247,8 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
         job.cubic.p0 = job.cubic.p1 = job.cubic.p2 = job.cubic.p3 = v2(0, 0);
         job.local_to_device = xf_identity();
         uint32_t slot = FL_INVALID;
-        if (t < n) {
-            slot = t < n_heavy ? list[t] : list[cap - 1u - (t - n_heavy)];
+        if (t < t_end) {
+            slot = heavy ? list[t] : list[cap - 1u - (t - n_heavy)];
             o.slot = slot; o.cursor = 0u; o.a_first = 0u; o.a_spos = 0u; o.a_rpos = 0u;
             uint32_t path_ix;
             run_item<true>(cfg, s, o, slot, job, path_ix);
@@ -1217,7 +1257,10 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
         EulerLane e;
         euler_begin(e, job);  // (transforms the control points of a fill, scale of an offset curve, degenerate test)
         const bool active = job.valid && !e.done;
-        if (__builtin_amdgcn_ballot_w64(active) == 0ull) continue;  // uniform: nothing to subdivide in this batch
+        if (__builtin_amdgcn_ballot_w64(active) == 0ull) {  // uniform: nothing to subdivide in this batch
+            FL_TL_END();
+            continue;
+        }
         B.jhead[lane] = 0u;
         {
             const uint64_t am = __builtin_amdgcn_ballot_w64(active);
@@ -1233,6 +1276,9 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
         // undecided by the transcendental-free test (flatten_fast.h; ~0.1 % of the nodes); the undecided ones wait in a list of
         // their own and get the pinned sequence in rounds of up to 64 when the stack has run dry (or 64 are waiting). ----
         for (;;) {
+#ifdef FL_TIMING
+            tl_info += 1u << 16;
+#endif
             const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_stack);
             const uint32_t nu = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_unsure);
             if (ns == 0u && nu == 0u) break;
@@ -1312,6 +1358,9 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
         // A batch that gave up (bail) leaves no pieces: all its jobs take the sequential walk below. ----
         const bool bail = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.bail) != 0u;
         const uint32_t nl = bail ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_leaves);
+#ifdef FL_TIMING
+        tl_info = (tl_info & 0x7fff0000u) | (nl & 0xffffu) | (bail ? 1u << 31 : 0u);
+#endif
         uint32_t rec_base = 0u;
         if (nl != 0u && lane == 0u) rec_base = fl_grab<1>(T, o.home_r, nl, o.failed_r);
         rec_base = (uint32_t)__builtin_amdgcn_readlane((int)rec_base, 0);
@@ -1399,7 +1448,15 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             };
             flatten_euler_wave(o, e, finish);
         }
+        FL_TL_END();
     }
+#ifdef FL_TIMING
+    if (lane == 0u && tl_wave < FL_TL_WAVES) {
+        g_fl_timeline[tl_wave * FL_TL_WORDS] = tl_entry;
+        g_fl_timeline[tl_wave * FL_TL_WORDS + 1u] = tl_n;
+    }
+#endif
+#undef FL_TL_END
 }
 
 // One thread per temporary slot: the Euler line (or the directly emitted line) that lives there, moved to
@@ -1736,6 +1793,29 @@ extern "C" int jh_debug_flatten_fast_stats(uint32_t* out8, int reset) {
 }
 #endif
 
+#ifdef FL_TIMING
+// (timing build only: tools/flatten_timeline.py) out = the timeline of the last k_flatten_items, FL_TL_WORDS words for each of
+// dims[0] waves; dims[2] = the rate of the clock in kHz.  reset clears it (a wave that never ran keeps entry clock 0).
+extern "C" int jh_debug_flatten_timeline(unsigned long long* out, uint32_t n_words, int reset, uint32_t* dims3) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (dims3) {
+        int dev = 0, khz = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) return -1;
+        dims3[0] = FL_TL_WAVES; dims3[1] = FL_TL_WORDS; dims3[2] = (uint32_t)khz;
+    }
+    if (out) {
+        if (n_words > FL_TL_WAVES * FL_TL_WORDS) return -1;
+        if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fl_timeline), (size_t)n_words * 8u) != hipSuccess) return -1;
+    }
+    if (reset) {
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_fl_timeline)) != hipSuccess) return -1;
+        if (hipMemset(p, 0, sizeof(unsigned long long) * FL_TL_WAVES * FL_TL_WORDS) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
+
 JhResult jh_launch_flatten(const JhLaunch& L) {
     if (L.gx == 0) return JH_L_OK;
     uint32_t n_tags = L.gx * JL_WG;
@@ -1751,6 +1831,7 @@ JhResult jh_launch_flatten(const JhLaunch& L) {
     uint32_t cap_blocks = L.cus() * FL_BLOCKS_PER_CU;
     uint32_t g = (n_slots + JL_WG - 1) / JL_WG;
     if (g > cap_blocks) g = cap_blocks;
+    if ((L.debug_flatten & 8u) != 0u) g = 1u;  // (jh_debug_flatten_regions bit 3, tests: four waves on one unit counter)
     // The temporary (FlTemp): a slot per line and at most a record per line, K regions of R each; K * R = the line buffer's
     // capacity + what the regions' ends can waste -- a frame that overflows the temporary has overflowed `lines` and fails as
     // the reference's.  (At least 4096 lines: a frame that overflows a tiny line buffer by less still has every line of the
