@@ -20,6 +20,7 @@
  *   jh_blit                       RenderToSurface's blit pass          engine/wgpu_engine/lib.go:109-198, 266-333
  *   jh_blit_yuv                   (no counterpart: the same target as NV12 / I420 video frames)
  *   jh_pack_tiles / jh_unpack_tiles   (no counterpart: the frame's way off the GPU)
+ *   jh_dash                           (no counterpart: the reference dashes on the CPU with curve.Dash)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -322,6 +323,44 @@ int jh_unpack_tiles(jh_ctx* ctx, const void* pack, uint64_t pack_bytes, void* ds
                     uint32_t texel_bytes);
 /* What jh_unpack_tiles has rejected since the last reset (entries; a rejected header counts once).  Synchronises the stream. */
 int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset);
+
+/* ---- dashing (DESIGN.md 5.6 "Dash rule") ----
+ * jh_dash turns a batch of paths into their dashes on the device: for callers that dash many paths per frame (the host route,
+ * Scene.stroke with a pattern, does the same on one core).  The result is defined word for word by the rule of DESIGN.md 5.6,
+ * stated in include/jello_dash.h -- which the host route compiles too -- and restated by tests/dash_ref.py; all three agree
+ * byte for byte.  The rule in short: dashing happens in user space; pattern entries, the offset and every segment's length are
+ * quantised once to 2^-20 user units and every position along a subpath is an integer sum; the pattern alternates on / off
+ * starting with on (an odd one keeps alternating, its period is two cycles), every subpath starts again at the offset, "on"
+ * intervals are half open, a zero "on" emits nothing and a zero "off" joins its neighbours; a dash is MoveTo(its start) + one
+ * sub-curve of the source's kind per segment it overlaps, cut by de Casteljau in binary64 and rounded once to binary32, with
+ * the source's control points copied where a cut falls on a segment's end; a closed subpath's last and first dash are one
+ * dash when they meet at its start (emitted last), and one dash that covers a closed subpath is closed with ClosePath.
+ *
+ * Input, host memory, read during the call only:
+ *   els      the elements of all paths: {i32 kind (0 MoveTo, 1 LineTo, 2 QuadTo, 3 CubicTo, 4 ClosePath), i32 pad, f64 pts[6]}
+ *   paths    per path {u32 first_el, n_els, first_dash, n_dash; f64 offset}: its elements, and its pattern in `dashes`
+ *   dashes   the concatenated patterns
+ * Output, caller-owned device memory:
+ *   out_els    out_capacity elements {u32 kind, f32 p[6]} (28 bytes): path after path, subpath after subpath, dash by ascending
+ *              start (a merged one last), segment after segment inside a dash
+ *   out_index  n_paths + 1 words: the exclusive offset of every path's elements, the last word = the total the job needs
+ * Elements at or beyond out_capacity are not written, the total still reports the need: read it, regrow, call again (the
+ * pipeline's clean-failure-and-regrow convention).  Bytes beyond out_capacity elements are never touched.
+ *
+ * The job is copied through the pinned staging arena like jh_upload's data; the call is stream-ordered on the context's stream
+ * and never waits for the device.  Its grids depend on the job, so it is refused during graph capture.  Scratch comes from the
+ * context's arrays (slots A-E, kcommon.h) and only grows.  Seven kernel launches.  With profiling on the call is a query "dash"
+ * with stage = -1 in jh_profile_collect_tree.
+ * JH_ERR_INVALID, with nothing enqueued and nothing written: a null pointer; a pattern with 0 or more than 64 entries; an entry
+ * that is negative, not finite or above 2^30; a quantised period of 0; an offset that is not finite or beyond 2^40 in magnitude;
+ * a coordinate that is not finite or beyond 2^20 in magnitude; an unknown element kind; a path whose elements or pattern lie
+ * outside the arrays; more than 2^31 - 1 drawn segments; out_capacity above 2^32 - 1.  The totals are 32-bit words: a job whose
+ * output would pass 2^32 - 1 elements writes nothing out of bounds but its index is meaningless. */
+typedef struct jh_dash_el { int32_t kind, pad; double pts[6]; } jh_dash_el;
+typedef struct jh_dash_path { uint32_t first_el, n_els, first_dash, n_dash; double offset; } jh_dash_path;
+typedef struct jh_dash_out_el { uint32_t kind; float p[6]; } jh_dash_out_el;
+int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
+            uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -429,6 +429,38 @@ func (e *Engine) PackTiles(src unsafe.Pointer, srcPitch uint64, ref unsafe.Point
 		C.uint32_t(texelBytes), dst, C.uint64_t(capacity)), "pack_tiles")
 }
 
+// DashEl, DashPath are jh_dash_el and jh_dash_path (include/jello_hip.h "dashing").
+type DashEl struct {
+	Kind, _ int32
+	Pts     [6]float64
+}
+type DashPath struct {
+	FirstEl, NEls, FirstDash, NDash uint32
+	Offset                          float64
+}
+
+// DashPaths is jh_dash: the dashes of a batch of paths by the rule of DESIGN.md 5.6, computed on the device.  els, paths and
+// dashes are host slices read during the call; outEls (capacity elements of 28 bytes) and outIndex (len(paths)+1 words) are
+// device memory.  Stream-ordered, waits for nothing: the last index word reports the elements the job needs -- regrow and call
+// again when it exceeds capacity.  The Go Scene keeps curve.Dash (scene.go:169-177); this is the opt-in device route for callers
+// that dash many paths.
+func (e *Engine) DashPaths(els []DashEl, paths []DashPath, dashes []float64, outEls unsafe.Pointer, capacity uint64, outIndex unsafe.Pointer) {
+	var pe *C.jh_dash_el
+	var pp *C.jh_dash_path
+	var pd *C.double
+	if len(els) > 0 {
+		pe = (*C.jh_dash_el)(unsafe.Pointer(&els[0]))
+	}
+	if len(paths) > 0 {
+		pp = (*C.jh_dash_path)(unsafe.Pointer(&paths[0]))
+	}
+	if len(dashes) > 0 {
+		pd = (*C.double)(unsafe.Pointer(&dashes[0]))
+	}
+	e.check(C.jh_dash(e.ctx, pe, C.uint64_t(len(els)), pp, C.uint32_t(len(paths)), pd, C.uint64_t(len(dashes)), outEls,
+		C.uint64_t(capacity), (*C.uint32_t)(outIndex)), "dash")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -6,7 +6,7 @@ Scene / encoding / renderer recording surface).  See DESIGN.md and INTEGRATION.m
 """
 from ._lib import build, lib_paths, load_host, HostLibraryMissing  # noqa: F401
 from .scene import (  # noqa: F401
-    Scene, Path, Brush, Stroke, Color, ColorStop, RenderParams, BumpSizes, Fill, Join, Cap, Mix, Compose, Extend, Aa,
+    Scene, Path, Brush, Stroke, dash, Color, ColorStop, RenderParams, BumpSizes, Fill, Join, Cap, Mix, Compose, Extend, Aa,
 )
 from .engine import (  # noqa: F401
     Host, Recording, Engine, Surface, YuvLayout, YuvMatrix, YuvRange, YuvTransfer, STAGE_NAMES, CMD,

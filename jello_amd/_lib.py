@@ -79,7 +79,9 @@ class CBrush(ctypes.Structure):
 
 class CStroke(ctypes.Structure):
     _fields_ = [("width", ctypes.c_double), ("join", ctypes.c_int32), ("start_cap", ctypes.c_int32),
-                ("end_cap", ctypes.c_int32), ("pad", ctypes.c_int32), ("miter_limit", ctypes.c_double)]
+                ("end_cap", ctypes.c_int32), ("pad", ctypes.c_int32), ("miter_limit", ctypes.c_double),
+                ("dash_pattern", ctypes.POINTER(ctypes.c_double)), ("n_dash", ctypes.c_int32), ("pad2", ctypes.c_int32),
+                ("dash_offset", ctypes.c_double)]
 
 
 class CBumpSizes(ctypes.Structure):
@@ -119,6 +121,12 @@ class CConfig(ctypes.Structure):
                 ("blend_size", ctypes.c_uint32), ("ptcl_size", ctypes.c_uint32)]
 
 
+class CDashPath(ctypes.Structure):
+    """jh_dash_path (include/jello_hip.h)."""
+    _fields_ = [("first_el", ctypes.c_uint32), ("n_els", ctypes.c_uint32), ("first_dash", ctypes.c_uint32), ("n_dash", ctypes.c_uint32),
+                ("offset", ctypes.c_double)]
+
+
 class CYuvDesc(ctypes.Structure):
     """jh_yuv_desc (include/jello_hip.h)."""
     _fields_ = [("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32), ("transfer", ctypes.c_int32),
@@ -134,6 +142,8 @@ def _declare(L):
     L.jl_scene_reset.argtypes = [vp]
     L.jl_scene_fill.argtypes = [vp, ci, dp, ctypes.POINTER(CBrush), dp, ctypes.POINTER(PathEl), ci]
     L.jl_scene_stroke.argtypes = [vp, ctypes.POINTER(CStroke), dp, ctypes.POINTER(CBrush), dp, ctypes.POINTER(PathEl), ci]
+    L.jl_dash_path.restype = ctypes.c_int64
+    L.jl_dash_path.argtypes = [ctypes.POINTER(PathEl), ci, dp, ci, ctypes.c_double, ctypes.POINTER(PathEl), ctypes.c_int64]
     L.jl_scene_push_layer.argtypes = [vp, ci, ci, ctypes.c_float, dp, ctypes.POINTER(PathEl), ci]
     L.jl_scene_pop_layer.argtypes = [vp]
     L.jl_scene_append.argtypes = [vp, vp, dp]
@@ -182,6 +192,7 @@ def _declare(L):
     L.jl_engine_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
     L.jl_engine_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
     L.jl_engine_read_pack.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
+    L.jl_engine_dash_paths.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
     L.hip = hip
@@ -215,6 +226,7 @@ def _declare(L):
     hip.jh_pack_bound.argtypes = [u32, u32, u32]
     hip.jh_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
     hip.jh_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
+    hip.jh_dash.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "kcommon.h"
+#include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
 #define JH_SCR_SKEW 1280u
@@ -1302,6 +1303,60 @@ int jh_unpack_tiles(jh_ctx* ctx, const void* pack, uint64_t pack_bytes, void* ds
     const int lrc = jh_unpack_launch(ctx->stream, pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes, ctx->hint_overflow + kUnpackRejectWord);
     rc = pack_query_end(ctx, &pe);
     if (lrc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_unpack_tiles: launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// ---- dashing (include/jello_hip.h "dashing"; kernels_dash.hip) ----
+int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
+            uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index) {
+    if (!ctx) return JH_ERR_INVALID;
+    // every check comes before anything is enqueued: a refused call touches no memory
+    if (!out_index || (!out_els && out_capacity) || (!els && n_els) || (!paths && n_paths) || (!dashes && n_dashes))
+        return fail(ctx, JH_ERR_INVALID, "jh_dash: null pointer");
+    if (n_paths == 0xffffffffu || out_capacity > 0xffffffffull) return fail(ctx, JH_ERR_INVALID, "jh_dash: too many paths, or a capacity above 2^32 - 1 elements");
+    static_assert(sizeof(jh_dash_el) == sizeof(JDashInEl) && sizeof(jh_dash_path) == sizeof(JDashInPath) && sizeof(jh_dash_out_el) == sizeof(JDashEl),
+                  "the C ABI's structs are the rule's");
+    JDashJob job;
+    if (const char* why = jdash_prepare((const JDashInEl*)els, n_els, (const JDashInPath*)paths, n_paths, dashes, n_dashes, &job))
+        return fail(ctx, JH_ERR_INVALID, std::string("jh_dash: ") + why);
+    if (ctx->capturing) return fail(ctx, JH_ERR_INVALID, "jh_dash: not during graph capture (its grids depend on the job)");
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ProfEntry pe;
+    if (job.segs.empty()) {  // nothing is drawn: every offset is 0
+        int rc0 = pack_query_begin(ctx, &pe, "dash");
+        if (rc0) return rc0;
+        HIP_TRY(ctx, hipMemsetAsync(out_index, 0, ((uint64_t)n_paths + 1u) * 4u, ctx->stream));
+        return pack_query_end(ctx, &pe);
+    }
+    // one upload for the whole job: [segs][subs][pats][runs][path_first_seg], each section on a 16-byte boundary
+    auto al = [](uint64_t v) { return (v + 15u) & ~15ull; };
+    const uint64_t o_subs = al(job.segs.size() * sizeof(JDashSeg)), o_pats = o_subs + al(job.subs.size() * sizeof(JDashSub));
+    const uint64_t o_runs = o_pats + al(job.pats.size() * sizeof(JDashPat)), o_first = o_runs + al(job.runs.size() * sizeof(JDashRun));
+    const uint64_t bytes = o_first + al(job.path_first_seg.size() * 4u);
+    std::vector<char> blob(bytes, 0);
+    std::memcpy(blob.data(), job.segs.data(), job.segs.size() * sizeof(JDashSeg));
+    std::memcpy(blob.data() + o_subs, job.subs.data(), job.subs.size() * sizeof(JDashSub));
+    std::memcpy(blob.data() + o_pats, job.pats.data(), job.pats.size() * sizeof(JDashPat));
+    if (!job.runs.empty()) std::memcpy(blob.data() + o_runs, job.runs.data(), job.runs.size() * sizeof(JDashRun));
+    std::memcpy(blob.data() + o_first, job.path_first_seg.data(), job.path_first_seg.size() * 4u);
+    char* dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_A, bytes);
+    if (!dev) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
+    void* src = stage_copy(ctx, blob.data(), bytes);  // the pinned arena, as jh_upload: the DMA is left in flight
+    if (!src) return fail(ctx, JH_ERR_OOM, "jh_dash: pinned staging allocation failed");
+    int rc = pack_query_begin(ctx, &pe, "dash");  // (the query holds the upload too)
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    JhDashJob dj;
+    dj.segs = (const JDashSeg*)dev; dj.subs = (const JDashSub*)(dev + o_subs); dj.pats = (const JDashPat*)(dev + o_pats);
+    dj.runs = (const JDashRun*)(dev + o_runs); dj.path_first_seg = (const uint32_t*)(dev + o_first);
+    dj.n_segs = (uint32_t)job.segs.size(); dj.n_subs = (uint32_t)job.subs.size(); dj.n_paths = n_paths;
+    const std::vector<JhBound> none;
+    const JhLaunch L = make_launch(ctx, 0, 0, 0, none);
+    const JhResult lr = jh_dash_launch(L, dj, out_els, out_capacity, out_index);
+    rc = pack_query_end(ctx, &pe);
+    if (lr == JH_L_SCRATCH) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
+    if (hipGetLastError() != hipSuccess) return fail(ctx, JH_ERR_DEVICE, "jh_dash: launch failed");
     return rc;
 }
 

@@ -243,6 +243,8 @@ struct JhImageDesc {
 // flatten sit where path_count's do, so a frame allocates them once:
 //
 //   slot      flatten           binning     tile_alloc  backdrop_dyn  path_count                 coarse               fine         jh_pack_tiles
+//             (jh_dash, a call outside the frame's stages, uses A: the uploaded job, B: lengths / segment, C: counts and relocation
+//              flags / segment, D: their scans, E: whole / merged / subpath, and SCAN_TMP through jh_scan_u32)
 //   SCAN_TMP  (jh_scan_u32's control words and tile descriptors, whichever stage scans: flatten, path_count)   self-cleaned
 //   A         counts / slot     wg totals   counts      wide list     counts / line              counts + wg totals
 //   B         bases / slot                  wg totals                 bases / line               scratch PTCL (clips)
@@ -337,6 +339,22 @@ enum JhResult { JH_L_OK = 0, JH_L_BAD_BINDINGS, JH_L_SCRATCH };  // mapped to JH
 // *total_dev (if non-null).  One launch (decoupled look-back).
 JhResult jh_scan_u32(const JhLaunch& L, const uint32_t* in, uint32_t in_stride, uint32_t* out, uint32_t n_max, const uint32_t* n_dev,
                      uint32_t* total_dev);
+
+// jh_dash (kernels_dash.hip): the uploaded job as device pointers (the structs: include/jello_dash.h), and the launcher that
+// enqueues the stage's kernels on L.stream.  JH_L_SCRATCH when a scratch array could not be had; nothing is enqueued then.
+struct JDashSeg;
+struct JDashSub;
+struct JDashPat;
+struct JDashRun;
+struct JhDashJob {
+    const JDashSeg* segs;
+    const JDashSub* subs;
+    const JDashPat* pats;
+    const JDashRun* runs;
+    const uint32_t* path_first_seg;  // n_paths + 1
+    uint32_t n_segs, n_subs, n_paths;
+};
+JhResult jh_dash_launch(const JhLaunch& L, const JhDashJob& job, void* out, uint64_t capacity, uint32_t* index);
 
 // Binding slots (the WGSL @binding order) of the stages whose bindings the held-back rules compare; the other stages name
 // theirs next to their launcher.

@@ -53,6 +53,9 @@ _SURFACE_BUFFER_ID = 0x5355524641434500
 # context buffers of pack_tiles (the pack, when the caller passes no device pointer) and unpack_tiles (an uploaded pack)
 _PACK_BUFFER_ID = 0x5041434B4F555400
 _UNPACK_BUFFER_ID = 0x5041434B494E0000
+_DASH_ELS_BUFFER_ID = 0x44415348454C5300
+_DASH_INDEX_BUFFER_ID = 0x44415348494E4400
+DASH_EL = np.dtype([("kind", "<u4"), ("p", "<f4", 6)])  # jh_dash_out_el, 28 bytes
 # a context buffer that blit_yuv / render_to_yuv convert into when the caller passes no planes (it only grows)
 _YUV_BUFFER_ID = 0x5955565F4F555400
 
@@ -339,6 +342,67 @@ class Engine:
         n = ctypes.c_uint32(0)
         self._check(self.hip.jh_debug_unpack_rejects(self.ctx, ctypes.byref(n), 1 if reset else 0), "unpack_rejects")
         return n.value
+
+    @staticmethod
+    def _dash_job(paths, patterns, offsets):
+        """The host arrays of jh_dash for a batch: (elements, descriptors, concatenated patterns), ctypes arrays."""
+        if not (len(paths) == len(patterns) == len(offsets)):
+            raise ValueError("dash_paths: paths, patterns and offsets differ in length")
+        n_els = sum(len(p.els) for p in paths)
+        els = (_lib.PathEl * max(n_els, 1))()
+        desc = (_lib.CDashPath * max(len(paths), 1))()
+        flat = [float(d) for pat in patterns for d in pat]
+        dashes = (ctypes.c_double * max(len(flat), 1))(*flat)
+        k = d0 = 0
+        for i, (path, pat, off) in enumerate(zip(paths, patterns, offsets)):
+            desc[i].first_el, desc[i].n_els, desc[i].first_dash, desc[i].n_dash, desc[i].offset = k, len(path.els), d0, len(pat), float(off)
+            for kind, pts in path.els:
+                els[k].kind = kind
+                for j in range(6):
+                    els[k].pts[j] = pts[j]
+                k += 1
+            d0 += len(pat)
+        return els, n_els, desc, dashes, len(flat)
+
+    def dash_into(self, paths, patterns, offsets, els_ptr, capacity, index_ptr):
+        """jh_dash: the dashes of the batch into caller-owned device memory -- `capacity` elements of 28 bytes at `els_ptr`,
+        len(paths) + 1 words at `index_ptr`.  Stream-ordered, returns nothing; ValueError for an input the rule rejects."""
+        els, n_els, desc, dashes, n_dashes = self._dash_job(paths, patterns, offsets)
+        rc = self._L.jl_engine_dash_paths(self._h, els, n_els, desc, len(paths), dashes, n_dashes, els_ptr, capacity, index_ptr)
+        if rc == -1:  # JH_ERR_INVALID
+            raise ValueError(self._L.jl_last_error().decode())
+        self._check(rc, "dash_paths")
+
+    def dash_paths(self, paths, patterns, offsets, capacity=None, raw=False):
+        """The dashes of every path of the batch (scene.Path objects; one pattern and one offset each), computed on the device
+        by the rule of DESIGN.md 5.6: a list of Paths, or with raw=True (elements as a DASH_EL array, the len(paths) + 1
+        exclusive offsets).  The element buffer is sized from a bound (or `capacity`) and regrown once from the need the first
+        call reports."""
+        n_els = sum(len(p.els) for p in paths)
+        cap = int(capacity) if capacity is not None else 8 * n_els + 256
+        index = np.zeros(len(paths) + 1, dtype=np.uint32)
+        self._check(self.hip.jh_buffer_create(self.ctx, _DASH_INDEX_BUFFER_ID, index.nbytes), "buffer_create")
+        for attempt in range(2):
+            self._check(self.hip.jh_buffer_create(self.ctx, _DASH_ELS_BUFFER_ID, max(cap, 1) * DASH_EL.itemsize), "buffer_create")
+            self.dash_into(paths, patterns, offsets, self.hip.jh_buffer_device_ptr(self.ctx, _DASH_ELS_BUFFER_ID), cap,
+                           self.hip.jh_buffer_device_ptr(self.ctx, _DASH_INDEX_BUFFER_ID))
+            self._check(self.hip.jh_download(self.ctx, _DASH_INDEX_BUFFER_ID, index.ctypes.data, 0, index.nbytes), "download")
+            if int(index[-1]) <= cap:
+                break
+            cap = int(index[-1])
+        total = int(index[-1])
+        els = np.zeros(total, dtype=DASH_EL)
+        if total:
+            self._check(self.hip.jh_download(self.ctx, _DASH_ELS_BUFFER_ID, els.ctypes.data, 0, els.nbytes), "download")
+        if raw:
+            return els, index
+        from .scene import Path
+        out = []
+        for i in range(len(paths)):
+            p = Path()
+            p.els = [(int(e["kind"]), tuple(float(v) for v in e["p"])) for e in els[index[i]:index[i + 1]]]
+            out.append(p)
+        return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().

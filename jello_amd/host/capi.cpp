@@ -6,6 +6,7 @@
 #include <memory>
 #include <string>
 
+#include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
 
@@ -27,7 +28,12 @@ struct jl_brush {
     const uint8_t* image_pixels;
     uint64_t image_key;
 };
-struct jl_stroke { double width; int32_t join; int32_t start_cap; int32_t end_cap; int32_t pad; double miter_limit; };
+struct jl_stroke {
+    double width; int32_t join; int32_t start_cap; int32_t end_cap; int32_t pad; double miter_limit;
+    const double* dash_pattern;  // n_dash entries, or NULL: a solid stroke
+    int32_t n_dash; int32_t pad2;
+    double dash_offset;
+};
 struct jl_bump_sizes { uint32_t bin_data, tiles, lines, seg_counts, segments, blend_spill, ptcl; };
 struct jl_render_params { double base_color[4]; uint32_t width, height; int32_t aa; uint32_t pad; jl_bump_sizes bump; };
 
@@ -119,8 +125,23 @@ int jl_scene_stroke(void* s, const jl_stroke* st, const double* transform, const
                     const jl_path_el* els, int n) {
     Stroke k;
     k.width = st->width; k.join = (Join)st->join; k.start_cap = (Cap)st->start_cap; k.end_cap = (Cap)st->end_cap; k.miter_limit = st->miter_limit;
+    if (st->dash_pattern && st->n_dash > 0) k.dash_pattern.assign(st->dash_pattern, st->dash_pattern + st->n_dash);
+    k.dash_offset = st->dash_offset;
     GUARD(((Scene*)s)->stroke(k, to_affine(transform), to_brush((Scene*)s, brush), to_affine(brush_transform), to_path(els, n)), -1);
     return 0;
+}
+// The bare dash function (host/dash.h): the dashes of els[0..n) as path elements.  Returns their count, or -1 for a rejected
+// input (jl_last_error says why).  At most `capacity` elements are written to `out`; a count above it means call again.
+int64_t jl_dash_path(const jl_path_el* els, int n, const double* pattern, int n_dash, double offset, jl_path_el* out, int64_t capacity) {
+    BezPath r;
+    if (n < 0 || n_dash < 0 || (n_dash > 0 && !pattern)) { g_err = "dash: negative count or null pattern"; return -1; }
+    GUARD(r = dash(to_path(els, n), std::vector<double>(pattern, pattern + n_dash), offset), -1);
+    for (int64_t i = 0; i < (int64_t)r.size() && i < capacity; i++) {
+        out[i].kind = (int32_t)r[i].kind; out[i].pad = 0;
+        out[i].pts[0] = r[i].p0[0]; out[i].pts[1] = r[i].p0[1]; out[i].pts[2] = r[i].p1[0]; out[i].pts[3] = r[i].p1[1];
+        out[i].pts[4] = r[i].p2[0]; out[i].pts[5] = r[i].p2[1];
+    }
+    return (int64_t)r.size();
 }
 int jl_scene_push_layer(void* s, int mix, int compose, float alpha, const double* transform, const jl_path_el* els, int n) {
     BlendMode bm;
@@ -437,6 +458,20 @@ int jl_engine_pack_tiles(void* e, const void* src, uint64_t src_pitch, const voi
 int jl_engine_unpack_tiles(void* e, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
                            uint32_t texel_bytes) {
     GUARD(((Engine*)e)->unpack_tiles(pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes), -1);
+    return 0;
+}
+// Engine::dash_paths (jh_dash).  Returns 0, or the JH_ERR_* code (negative) with jl_last_error set.
+int jl_engine_dash_paths(void* e, const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
+                         uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index) {
+    try {
+        ((Engine*)e)->dash_paths(els, n_els, paths, n_paths, dashes, n_dashes, out_els, out_capacity, out_index);
+    } catch (const EngineError& err) {
+        g_err = err.what();
+        return err.code;
+    } catch (const std::exception& err) {
+        g_err = err.what();
+        return -100;
+    }
     return 0;
 }
 // The pack at device_ptr into `out`: the header first, then exactly the size it states (written to *size).

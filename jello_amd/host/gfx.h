@@ -95,8 +95,8 @@ struct Stroke {
     Join join = Join::Round;
     double miter_limit = 4.0;
     Cap start_cap = Cap::Round, end_cap = Cap::Round;
-    // Dash patterns are expanded on the CPU by curve.Dash in the reference (scene.go:169-177);
-    // that third-party routine is out of scope here, so dashes are rejected.
+    // Dash patterns are expanded on the CPU before encoding, as in the reference (scene.go:169-177, curve.Dash); the
+    // result is defined by this project's dash rule (host/dash.h).  Empty: a solid stroke.
     std::vector<double> dash_pattern;
     double dash_offset = 0;
 };

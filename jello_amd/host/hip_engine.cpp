@@ -227,6 +227,11 @@ void Engine::unpack_tiles(const void* pack, uint64_t pack_bytes, void* dst, uint
     check(jh_unpack_tiles(ctx_, pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes), "unpack_tiles");
 }
 
+void Engine::dash_paths(const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
+                        uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index) {
+    check(jh_dash(ctx_, els, n_els, paths, n_paths, dashes, n_dashes, out_els, out_capacity, out_index), "dash");
+}
+
 uint64_t Engine::read_pack(const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity) {
     if (!device_ptr || !out || capacity < 32u) throw EngineError(JH_ERR_INVALID, "read_pack: null pointer or a capacity below the header's 32 bytes");
     // the pack's memory is the caller's: it is bound under an id of its own for the two downloads (an import of caller-owned

@@ -86,6 +86,12 @@ class Engine {
     // out_capacity (a header that is not a pack's included).
     uint64_t read_pack(const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity);
 
+    // Dashing on the device (jh_dash, include/jello_hip.h "dashing"; the rule: DESIGN.md 5.6): host arrays in, out_els
+    // (out_capacity elements of 28 bytes) and out_index (n_paths + 1 words) are device memory.  Stream-ordered, never waits; the
+    // last index word reports the elements the job needs.  Throws EngineError(JH_ERR_INVALID) for an input the rule rejects.
+    void dash_paths(const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes, uint64_t n_dashes,
+                    void* out_els, uint64_t out_capacity, uint32_t* out_index);
+
     Resolver& resolver() { return resolver_; }
     Renderer& renderer() { return renderer_; }
 

@@ -2,6 +2,7 @@
 // style de-duplication produces the same streams.
 #include "scene.h"
 
+#include "dash.h"
 #include "renderer.h"
 
 #include <algorithm>
@@ -99,8 +100,17 @@ void Scene::fill(Fill style, const Affine& transform, const Brush& brush, const 
 }
 
 void Scene::stroke(const Stroke& style, const Affine& transform, const Brush& brush, const Affine& brush_transform, const BezPath& shape) {  // scene.go:112-198
-    if (!style.dash_pattern.empty())
-        throw std::invalid_argument("dashed strokes are expanded by the third-party curve.Dash in the reference; not supported here");
+    // scene.go:169-177 expands dashes on the CPU before encoding; so does this (the rule: DESIGN.md 5.6).  A rejected pattern
+    // throws before anything is encoded.
+    if (!style.dash_pattern.empty()) {
+        const BezPath dashed = dash(shape, style.dash_pattern, style.dash_offset);
+        stroke_undashed(style, transform, brush, brush_transform, dashed);
+        return;
+    }
+    stroke_undashed(style, transform, brush, brush_transform, shape);
+}
+
+void Scene::stroke_undashed(const Stroke& style, const Affine& transform, const Brush& brush, const Affine& brush_transform, const BezPath& shape) {
     Transform t = transform.to_transform();
     encoding_.encode_transform(t);
     encoding_.encode_stroke_style(style);

@@ -58,6 +58,8 @@ class Scene {
     }
 
    private:
+    // stroke() past the dash expansion: scene.go:157-198 with the path it is given
+    void stroke_undashed(const Stroke& style, const Affine& transform, const Brush& brush, const Affine& brush_transform, const BezPath& shape);
     std::unordered_map<uint64_t, std::shared_ptr<const std::vector<uint8_t>>> image_store_;
     Encoding encoding_;
     BumpEstimator estimator_;

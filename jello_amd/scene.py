@@ -100,6 +100,22 @@ class Path:
         return arr
 
 
+def dash(path, pattern, offset=0.0):
+    """The dashes of `path` as a Path: MoveTo + one sub-curve per segment a dash overlaps (the dash rule of DESIGN.md 5.6, on
+    the host).  Coordinates are exactly representable in binary32.  ValueError for an input the rule rejects."""
+    L = _lib.load_host()
+    els = path._c()
+    pat = (ctypes.c_double * max(len(pattern), 1))(*[float(d) for d in pattern])
+    n = L.jl_dash_path(els, len(path.els), pat, len(pattern), float(offset), None, 0)
+    if n < 0:
+        raise ValueError(L.jl_last_error().decode())
+    out = (PathEl * max(n, 1))()
+    L.jl_dash_path(els, len(path.els), pat, len(pattern), float(offset), out, n)
+    r = Path()
+    r.els = [(out[i].kind, tuple(out[i].pts)) for i in range(n)]
+    return r
+
+
 class Brush:
     SOLID, LINEAR, RADIAL, SWEEP, IMAGE = 0, 1, 2, 3, 4
 
@@ -167,13 +183,19 @@ class Brush:
 
 
 class Stroke:
-    """curve.Stroke subset: width, join, miter_limit, caps (dashes unsupported, see host/gfx.h)."""
-    def __init__(self, width=1.0, join=Join.Round, miter_limit=4.0, start_cap=Cap.Round, end_cap=Cap.Round):
+    """curve.Stroke subset: width, join, miter_limit, caps, dashes.  A non-empty dash_pattern (1 to 64 lengths, on / off
+    alternating, in user units) is expanded by Scene.stroke with the dash rule of DESIGN.md 5.6, starting dash_offset into it."""
+    def __init__(self, width=1.0, join=Join.Round, miter_limit=4.0, start_cap=Cap.Round, end_cap=Cap.Round, dash_pattern=(), dash_offset=0.0):
         self.width, self.join, self.miter_limit, self.start_cap, self.end_cap = width, join, miter_limit, start_cap, end_cap
+        self.dash_pattern, self.dash_offset = tuple(float(d) for d in dash_pattern), float(dash_offset)
 
     def _c(self):
         s = CStroke()
         s.width, s.join, s.start_cap, s.end_cap, s.miter_limit = self.width, int(self.join), int(self.start_cap), int(self.end_cap), self.miter_limit
+        if self.dash_pattern:
+            self._dashes = (ctypes.c_double * len(self.dash_pattern))(*self.dash_pattern)  # kept alive with the style
+            s.dash_pattern, s.n_dash = self._dashes, len(self.dash_pattern)
+        s.dash_offset = self.dash_offset
         return s
 
 
