@@ -849,7 +849,7 @@ static int check_bin_limit(jh_ctx* ctx, int stage, const JlConfig* cfg_host) {
 }
 
 // One GPU query of the profile tree around whatever is enqueued between begin and end; both do nothing with the profiler off.
-// stage = -1: a query that is no stage record (the blit).
+// stage = -1: a query that is no stage record (the post-render calls).
 static int prof_query_begin(jh_ctx* ctx, ProfEntry& pe, int stage, const char* label) {
     if (!ctx->profiling) return JH_OK;
     for (hipEvent_t* e : {&pe.start, &pe.stop}) {
@@ -873,12 +873,14 @@ static int prof_query_end(jh_ctx* ctx, ProfEntry& pe) {
     return JH_OK;
 }
 
+// What a scratch array that could not be had is reported as; `remedy`: what to do first when a capture kept it from growing.
+static std::string scratch_failure(const jh_ctx* ctx, const char* remedy) {
+    return ctx->capturing ? std::string("a scratch array would have to grow during graph capture: ") + remedy : "scratch allocation failed";
+}
 static int launch_result(jh_ctx* ctx, int stage, JhResult r) {
     switch (r) {
         case JH_L_OK: return JH_OK;
-        case JH_L_SCRATCH:
-            return fail(ctx, JH_ERR_OOM, ctx->capturing ? "a scratch array would have to grow during graph capture: run the recording once eagerly first"
-                                                        : "scratch allocation failed");
+        case JH_L_SCRATCH: return fail(ctx, JH_ERR_OOM, scratch_failure(ctx, "run the recording once eagerly first"));
         default: return fail(ctx, JH_ERR_INVALID, std::string("bad bindings for stage ") + jh_stage_name(stage));
     }
 }
@@ -1067,7 +1069,7 @@ int jh_profile_collect(jh_ctx* ctx, jh_profile_record* out, int max) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     int n = 0;
     for (auto& p : ctx->prof) {
-        if (p.kind != JH_PROF_QUERY || p.stage < 0) continue;  // (the blit is a query of the tree, not a stage record)
+        if (p.kind != JH_PROF_QUERY || p.stage < 0) continue;  // (a post-render call is a query of the tree, not a stage record)
         float ms = 0.0f;
         (void)hipEventElapsedTime(&ms, p.start, p.stop);
         if (out && n < max) {
@@ -1130,55 +1132,101 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- surface blit (RenderToSurface's blit pass, engine/wgpu_engine/lib.go:109-198, 266-333) ----
-int jh_blit_launch(hipStream_t stream, const void* src, void* dst, uint64_t pitch, uint32_t width, uint32_t row0, uint32_t row1, int format,
-                   int num_cus);
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing ----
+// The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
+enum {
+    kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
+    kFineTimingWord = 8,     // fine under FINE_TIMING: six 64-bit counters
+    kUnpackRejectWord = 32,  // jh_unpack_tiles: what it ignored
+};
+// n_words of the block from first_word on into `out` (if non-null), then zeroed if `reset`.  Synchronises the stream.
+static int counter_words(jh_ctx* ctx, uint32_t first_word, uint32_t n_words, void* out, int reset) {
+    uint32_t* words = ctx->hint_overflow + first_word;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (out) {
+        HIP_TRY(ctx, hipMemcpyAsync(out, words, 4u * n_words, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (reset) {
+        HIP_TRY(ctx, hipMemsetAsync(words, 0, 4u * n_words, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return JH_OK;
+}
 
+extern "C++" {  // (a template cannot have C linkage)
+// The frame of a post-render call once its own checks have passed (every check comes before anything is enqueued: a refused call
+// touches no memory and flushes nothing): what is held back is launched, the device selected, `prepare` gets what has to be there
+// before the query opens (scratch, staging), and `launch` enqueues the call's work -- inside a query of its own when profiling is on
+// (the reference's pgroup.Render(arena, "blit")): stage -1, a node of the tree and no stage record.  Both answer a JH_* code and
+// have reported their own failure.
+template <class Prepare, class Launch>
+static int post_render_call(jh_ctx* ctx, const char* label, Prepare&& prepare, Launch&& launch) {
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = prepare();
+    if (rc) return rc;
+    ProfEntry pe;
+    rc = prof_query_begin(ctx, pe, -1, label);
+    if (rc) return rc;
+    rc = launch();
+    const int prc = prof_query_end(ctx, pe);
+    return rc ? rc : prc;
+}
+template <class Launch>
+static int post_render_call(jh_ctx* ctx, const char* label, Launch&& launch) {
+    return post_render_call(ctx, label, [] { return (int)JH_OK; }, launch);
+}
+}
+// What the launchers of kcommon.h's list answer -- 0, -1 for a frame they refuse, anything else for a failed launch -- as a JH_* code.
+static int launch_status(jh_ctx* ctx, const char* who, int rc) {
+    if (rc == 0) return JH_OK;
+    if (rc == -1) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": image too large for one launch");
+    return fail(ctx, JH_ERR_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
+}
+
+// The source of a blit: a known image, RGBA16F, of the size the caller gives.
+static int rgba16f_source(jh_ctx* ctx, uint64_t id, uint32_t width, uint32_t height, const char* who, const Alloc** out) {
+    const Alloc* a = find_alloc(ctx->images, id);
+    if (!a) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": unknown source image id");
+    if (a->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": the source is not an RGBA16F image");
+    if (a->width != width || a->height != height) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": size differs from the source image");
+    *out = a;
+    return JH_OK;
+}
+// a source that was never written reads as transparent black, like a fresh texture: the kernels take a null pointer for it
+static const void* content_or_null(const Alloc& a) { return (a.written || a.stored) ? a.ptr : nullptr; }
+// band mode: the pixel rows [*row0, *row1) of the active bin rows only (a bin row = 256 pixel rows: an even cut), so that bands of
+// several ranks compose; row1 = row0 when the band lies below the image
+static void band_pixel_rows(const jh_ctx* ctx, uint32_t height, uint32_t* row0, uint32_t* row1) {
+    *row0 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row0 * 256u, height);
+    *row1 = std::max(*row0, (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row1 * 256u, height));
+}
+
+// surface blit (RenderToSurface's blit pass, engine/wgpu_engine/lib.go:109-198, 266-333; kernels_surface.hip)
 int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t dst_pitch_bytes, uint32_t width, uint32_t height,
             int surface_format) {
     if (!ctx) return JH_ERR_INVALID;
-    // every check comes before anything is enqueued: a refused call touches no memory
-    const Alloc* src = find_alloc(ctx->images, src_image_id);
-    if (!src) return fail(ctx, JH_ERR_INVALID, "jh_blit: unknown source image id");
-    const Alloc& a = *src;
-    if (a.format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_blit: the source is not an RGBA16F image");
-    if (a.width != width || a.height != height) return fail(ctx, JH_ERR_INVALID, "jh_blit: size differs from the source image");
+    const Alloc* a = nullptr;
+    if (int rc = rgba16f_source(ctx, src_image_id, width, height, "jh_blit", &a)) return rc;
     if (!dst_device_ptr) return fail(ctx, JH_ERR_INVALID, "jh_blit: null destination");
     if (dst_pitch_bytes < 4ull * width) return fail(ctx, JH_ERR_INVALID, "jh_blit: pitch below 4 * width");
     if (surface_format < JH_SURFACE_RGBA8_UNORM || surface_format > JH_SURFACE_BGRA8_SRGB)
         return fail(ctx, JH_ERR_INVALID, "jh_blit: unknown surface format");
-    JH_FLUSH(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // band mode: the pixel rows of the active bin rows only (a bin row = 256 pixel rows), so that bands of several ranks compose
-    const uint64_t h = height;
-    const uint32_t row0 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row0 * 256u, h);
-    const uint32_t row1 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row1 * 256u, h);
-    ProfEntry pe;  // a query of its own (the reference's pgroup.Render(arena, "blit")), not a stage
-    int prc = prof_query_begin(ctx, pe, -1, "blit");
-    if (prc) return prc;
-    // a source that was never written reads as transparent black, like a fresh texture
-    const int rc = jh_blit_launch(ctx->stream, (a.written || a.stored) ? a.ptr : nullptr, dst_device_ptr, dst_pitch_bytes, width, row0,
-                                  row1 > row0 ? row1 : row0, surface_format, ctx->num_cus);
-    prc = prof_query_end(ctx, pe);
-    if (prc) return prc;
-    if (rc == -1) return fail(ctx, JH_ERR_INVALID, "jh_blit: image too large for one launch");
-    if (rc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_blit: launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return JH_OK;
+    return post_render_call(ctx, "blit", [&] {
+        uint32_t row0, row1;
+        band_pixel_rows(ctx, height, &row0, &row1);
+        return launch_status(ctx, "jh_blit", jh_blit_launch(ctx->stream, content_or_null(*a), dst_device_ptr, dst_pitch_bytes, width, row0, row1,
+                                                            surface_format, ctx->num_cus));
+    });
 }
 
-// ---- YUV blit (include/jello_hip.h "YUV blit"; kernels_yuv.hip) ----
-int jh_blit_yuv_launch(hipStream_t stream, const void* src, void* const* planes, const uint64_t* pitches, uint32_t width, uint32_t height,
-                       uint32_t row0, uint32_t row1, int layout, int matrix, int range, int transfer, int num_cus);
-
+// YUV blit (include/jello_hip.h "YUV blit"; kernels_yuv.hip)
 int jh_blit_yuv(jh_ctx* ctx, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc) {
     if (!ctx) return JH_ERR_INVALID;
-    // every check comes before anything is enqueued: a refused call touches no memory
     if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: null descriptor");
-    const Alloc* src = find_alloc(ctx->images, src_image_id);
-    if (!src) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown source image id");
-    const Alloc& a = *src;
-    if (a.format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: the source is not an RGBA16F image");
-    if (a.width != width || a.height != height) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: size differs from the source image");
+    const Alloc* a = nullptr;
+    if (int rc = rgba16f_source(ctx, src_image_id, width, height, "jh_blit_yuv", &a)) return rc;
     if (desc->layout != JH_YUV_NV12 && desc->layout != JH_YUV_I420) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown layout");
     if (desc->matrix != JH_YUV_BT601 && desc->matrix != JH_YUV_BT709) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown matrix");
     if (desc->range != JH_YUV_LIMITED && desc->range != JH_YUV_FULL) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown range");
@@ -1190,35 +1238,16 @@ int jh_blit_yuv(jh_ctx* ctx, uint64_t src_image_id, uint32_t width, uint32_t hei
         if (!desc->plane[i]) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: null plane");
         if (desc->pitch[i] < row_bytes[i]) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: pitch below the row's bytes");
     }
-    JH_FLUSH(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // band mode: the luma rows of the active bin rows (a bin row = 256 pixel rows: an even cut) and the chroma rows under them
-    const uint64_t h = height;
-    const uint32_t row0 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row0 * 256u, h);
-    const uint32_t row1 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row1 * 256u, h);
-    ProfEntry pe;
-    int prc = prof_query_begin(ctx, pe, -1, "blit_yuv");
-    if (prc) return prc;
-    int rc = 0;
-    if (row1 > row0)  // a source that was never written reads as transparent black, like a fresh texture
-        rc = jh_blit_yuv_launch(ctx->stream, (a.written || a.stored) ? a.ptr : nullptr, desc->plane, desc->pitch, width, height, row0, row1,
-                                desc->layout, desc->matrix, desc->range, desc->transfer, ctx->num_cus);
-    prc = prof_query_end(ctx, pe);
-    if (prc) return prc;
-    if (rc == -1) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: image too large for one launch");
-    if (rc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_blit_yuv: launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return JH_OK;
+    return post_render_call(ctx, "blit_yuv", [&] {
+        uint32_t row0, row1;  // the luma rows of the band, and the chroma rows under them
+        band_pixel_rows(ctx, height, &row0, &row1);
+        if (row1 == row0) return (int)JH_OK;
+        return launch_status(ctx, "jh_blit_yuv", jh_blit_yuv_launch(ctx->stream, content_or_null(*a), desc->plane, desc->pitch, width, height, row0, row1,
+                                                                    desc->layout, desc->matrix, desc->range, desc->transfer, ctx->num_cus));
+    });
 }
 
-// ---- tile pack (include/jello_hip.h "tile-packed frame transport"; kernels_pack.hip) ----
-uint32_t jh_pack_groups(uint32_t n_tiles, uint32_t* run_out);
-int jh_pack_launch(hipStream_t stream, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
-                   uint32_t texel_bytes, void* dst, void* cls, void* totals);
-int jh_unpack_launch(hipStream_t stream, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
-                     uint32_t texel_bytes, uint32_t* rejects);
-// the word of the context's counter block (hint_overflow: 64 words, zeroed at creation) that counts what jh_unpack_tiles ignored
-static const uint32_t kUnpackRejectWord = 32u;
-
+// tile pack (include/jello_hip.h "tile-packed frame transport"; kernels_pack.hip)
 uint64_t jh_pack_bound(uint32_t width, uint32_t height, uint32_t texel_bytes) {
     if (texel_bytes != 4u && texel_bytes != 8u) return 0;
     const uint64_t tiles = (uint64_t)((width + 15ull) / 16u) * ((height + 15ull) / 16u);
@@ -1237,56 +1266,26 @@ static const char* pack_frame_error(const void* p, uint64_t pitch, uint32_t widt
     return nullptr;
 }
 
-// A query of its own around one of the two calls when profiling is on (like jh_blit's: stage = -1, a node of the tree only).
-static int pack_query_begin(jh_ctx* ctx, ProfEntry* pe, const char* label) {
-    if (!ctx->profiling) return JH_OK;
-    auto get_event = [&](hipEvent_t* e) {
-        if (!ctx->free_events.empty()) { *e = ctx->free_events.back(); ctx->free_events.pop_back(); return hipSuccess; }
-        return hipEventCreate(e);
-    };
-    HIP_TRY(ctx, get_event(&pe->start));
-    HIP_TRY(ctx, get_event(&pe->stop));
-    pe->kind = JH_PROF_QUERY;
-    pe->parent = ctx->prof_stack.empty() ? -1 : ctx->prof_stack.back();
-    pe->stage = -1;
-    pe->label = label;
-    pe->cpu_start_ms = now_ms();
-    HIP_TRY(ctx, hipEventRecord(pe->start, ctx->stream));
-    return JH_OK;
-}
-static int pack_query_end(jh_ctx* ctx, ProfEntry* pe) {
-    if (!ctx->profiling) return JH_OK;
-    HIP_TRY(ctx, hipEventRecord(pe->stop, ctx->stream));
-    pe->cpu_end_ms = now_ms();
-    ctx->prof.push_back(*pe);
-    return JH_OK;
-}
-
 int jh_pack_tiles(jh_ctx* ctx, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
                   uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
     if (!ctx) return JH_ERR_INVALID;
-    // every check comes before anything is enqueued: a refused call touches no memory
     if (const char* why = pack_frame_error(src, src_pitch, width, height, texel_bytes)) return fail(ctx, JH_ERR_INVALID, std::string("jh_pack_tiles: source: ") + why);
     if (ref)
         if (const char* why = pack_frame_error(ref, ref_pitch, width, height, texel_bytes))
             return fail(ctx, JH_ERR_INVALID, std::string("jh_pack_tiles: reference: ") + why);
     if (!dst || (uintptr_t)dst % texel_bytes) return fail(ctx, JH_ERR_INVALID, "jh_pack_tiles: null destination, or not a multiple of texel_bytes");
     if (dst_capacity < jh_pack_bound(width, height, texel_bytes)) return fail(ctx, JH_ERR_INVALID, "jh_pack_tiles: dst_capacity below jh_pack_bound");
-    JH_FLUSH(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint32_t n_tiles = ((width + 15u) / 16u) * ((height + 15u) / 16u);
-    void* cls = jh_scratch_get(&ctx->scratch, JH_SCR_H, n_tiles);
-    void* totals = jh_scratch_get(&ctx->scratch, JH_SCR_J, 8ull * jh_pack_groups(n_tiles, nullptr));
-    if (!cls || !totals)
-        return fail(ctx, JH_ERR_OOM, ctx->capturing ? "jh_pack_tiles: a scratch array would have to grow during graph capture: pack a frame of this size once eagerly first"
-                                                    : "jh_pack_tiles: scratch allocation failed");
-    ProfEntry pe;
-    int rc = pack_query_begin(ctx, &pe, "pack");
-    if (rc) return rc;
-    const int lrc = jh_pack_launch(ctx->stream, src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, cls, totals);
-    rc = pack_query_end(ctx, &pe);
-    if (lrc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_pack_tiles: launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return rc;
+    void *cls = nullptr, *totals = nullptr;
+    return post_render_call(
+        ctx, "pack",
+        [&] {
+            const uint32_t n_tiles = ((width + 15u) / 16u) * ((height + 15u) / 16u);
+            cls = jh_scratch_get(&ctx->scratch, JH_SCR_H, n_tiles);
+            totals = jh_scratch_get(&ctx->scratch, JH_SCR_J, 8ull * jh_pack_groups(n_tiles, nullptr));
+            if (cls && totals) return (int)JH_OK;
+            return fail(ctx, JH_ERR_OOM, "jh_pack_tiles: " + scratch_failure(ctx, "pack a frame of this size once eagerly first"));
+        },
+        [&] { return launch_status(ctx, "jh_pack_tiles", jh_pack_launch(ctx->stream, src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, cls, totals)); });
 }
 
 int jh_unpack_tiles(jh_ctx* ctx, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
@@ -1295,22 +1294,16 @@ int jh_unpack_tiles(jh_ctx* ctx, const void* pack, uint64_t pack_bytes, void* ds
     if (const char* why = pack_frame_error(dst, dst_pitch, width, height, texel_bytes)) return fail(ctx, JH_ERR_INVALID, std::string("jh_unpack_tiles: destination: ") + why);
     if (!pack || (uintptr_t)pack % texel_bytes) return fail(ctx, JH_ERR_INVALID, "jh_unpack_tiles: null pack, or not a multiple of texel_bytes");
     if (pack_bytes < 32u) return fail(ctx, JH_ERR_INVALID, "jh_unpack_tiles: pack_bytes below the header's 32");
-    JH_FLUSH(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ProfEntry pe;
-    int rc = pack_query_begin(ctx, &pe, "unpack");
-    if (rc) return rc;
-    const int lrc = jh_unpack_launch(ctx->stream, pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes, ctx->hint_overflow + kUnpackRejectWord);
-    rc = pack_query_end(ctx, &pe);
-    if (lrc) return fail(ctx, JH_ERR_DEVICE, std::string("jh_unpack_tiles: launch failed: ") + hipGetErrorString(hipGetLastError()));
-    return rc;
+    return post_render_call(ctx, "unpack", [&] {
+        return launch_status(ctx, "jh_unpack_tiles", jh_unpack_launch(ctx->stream, pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes,
+                                                                      ctx->hint_overflow + kUnpackRejectWord));
+    });
 }
 
-// ---- dashing (include/jello_hip.h "dashing"; kernels_dash.hip) ----
+// dashing (include/jello_hip.h "dashing"; kernels_dash.hip)
 int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
             uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index) {
     if (!ctx) return JH_ERR_INVALID;
-    // every check comes before anything is enqueued: a refused call touches no memory
     if (!out_index || (!out_els && out_capacity) || (!els && n_els) || (!paths && n_paths) || (!dashes && n_dashes))
         return fail(ctx, JH_ERR_INVALID, "jh_dash: null pointer");
     if (n_paths == 0xffffffffu || out_capacity > 0xffffffffull) return fail(ctx, JH_ERR_INVALID, "jh_dash: too many paths, or a capacity above 2^32 - 1 elements");
@@ -1320,15 +1313,11 @@ int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_pa
     if (const char* why = jdash_prepare((const JDashInEl*)els, n_els, (const JDashInPath*)paths, n_paths, dashes, n_dashes, &job))
         return fail(ctx, JH_ERR_INVALID, std::string("jh_dash: ") + why);
     if (ctx->capturing) return fail(ctx, JH_ERR_INVALID, "jh_dash: not during graph capture (its grids depend on the job)");
-    JH_FLUSH(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ProfEntry pe;
-    if (job.segs.empty()) {  // nothing is drawn: every offset is 0
-        int rc0 = pack_query_begin(ctx, &pe, "dash");
-        if (rc0) return rc0;
-        HIP_TRY(ctx, hipMemsetAsync(out_index, 0, ((uint64_t)n_paths + 1u) * 4u, ctx->stream));
-        return pack_query_end(ctx, &pe);
-    }
+    if (job.segs.empty())  // nothing is drawn: every offset is 0
+        return post_render_call(ctx, "dash", [&] {
+            HIP_TRY(ctx, hipMemsetAsync(out_index, 0, ((uint64_t)n_paths + 1u) * 4u, ctx->stream));
+            return (int)JH_OK;
+        });
     // one upload for the whole job: [segs][subs][pats][runs][path_first_seg], each section on a 16-byte boundary
     auto al = [](uint64_t v) { return (v + 15u) & ~15ull; };
     const uint64_t o_subs = al(job.segs.size() * sizeof(JDashSeg)), o_pats = o_subs + al(job.subs.size() * sizeof(JDashSub));
@@ -1340,43 +1329,37 @@ int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_pa
     std::memcpy(blob.data() + o_pats, job.pats.data(), job.pats.size() * sizeof(JDashPat));
     if (!job.runs.empty()) std::memcpy(blob.data() + o_runs, job.runs.data(), job.runs.size() * sizeof(JDashRun));
     std::memcpy(blob.data() + o_first, job.path_first_seg.data(), job.path_first_seg.size() * 4u);
-    char* dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_A, bytes);
-    if (!dev) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
-    void* src = stage_copy(ctx, blob.data(), bytes);  // the pinned arena, as jh_upload: the DMA is left in flight
-    if (!src) return fail(ctx, JH_ERR_OOM, "jh_dash: pinned staging allocation failed");
-    int rc = pack_query_begin(ctx, &pe, "dash");  // (the query holds the upload too)
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    JhDashJob dj;
-    dj.segs = (const JDashSeg*)dev; dj.subs = (const JDashSub*)(dev + o_subs); dj.pats = (const JDashPat*)(dev + o_pats);
-    dj.runs = (const JDashRun*)(dev + o_runs); dj.path_first_seg = (const uint32_t*)(dev + o_first);
-    dj.n_segs = (uint32_t)job.segs.size(); dj.n_subs = (uint32_t)job.subs.size(); dj.n_paths = n_paths;
-    const std::vector<JhBound> none;
-    const JhLaunch L = make_launch(ctx, 0, 0, 0, none);
-    const JhResult lr = jh_dash_launch(L, dj, out_els, out_capacity, out_index);
-    rc = pack_query_end(ctx, &pe);
-    if (lr == JH_L_SCRATCH) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
-    if (hipGetLastError() != hipSuccess) return fail(ctx, JH_ERR_DEVICE, "jh_dash: launch failed");
-    return rc;
+    char* dev = nullptr;
+    void* staged = nullptr;
+    return post_render_call(
+        ctx, "dash",
+        [&] {
+            dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_A, bytes);
+            if (!dev) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
+            staged = stage_copy(ctx, blob.data(), bytes);  // the pinned arena, as jh_upload: the DMA is left in flight
+            if (!staged) return fail(ctx, JH_ERR_OOM, "jh_dash: pinned staging allocation failed");
+            return (int)JH_OK;
+        },
+        [&] {  // (the query holds the upload too)
+            HIP_TRY(ctx, hipMemcpyAsync(dev, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+            JhDashJob dj;
+            dj.segs = (const JDashSeg*)dev; dj.subs = (const JDashSub*)(dev + o_subs); dj.pats = (const JDashPat*)(dev + o_pats);
+            dj.runs = (const JDashRun*)(dev + o_runs); dj.path_first_seg = (const uint32_t*)(dev + o_first);
+            dj.n_segs = (uint32_t)job.segs.size(); dj.n_subs = (uint32_t)job.subs.size(); dj.n_paths = n_paths;
+            const std::vector<JhBound> none;
+            const JhResult lr = jh_dash_launch(make_launch(ctx, 0, 0, 0, none), dj, out_els, out_capacity, out_index);
+            if (lr == JH_L_SCRATCH) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
+            if (hipGetLastError() != hipSuccess) return fail(ctx, JH_ERR_DEVICE, "jh_dash: launch failed");
+            return (int)JH_OK;
+        });
 }
 
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.
 int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (count) {
-        HIP_TRY(ctx, hipMemcpyAsync(count, ctx->hint_overflow + kUnpackRejectWord, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (reset) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->hint_overflow + kUnpackRejectWord, 0, 4, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return JH_OK;
+    return counter_words(ctx, kUnpackRejectWord, 1, count, reset);
 }
-
-int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 
 int jh_selftest_math(jh_ctx* ctx, int op, const float* a, const float* b, float* out, uint32_t n) {
     if (!ctx || !a || !out) return JH_ERR_INVALID;
@@ -1398,8 +1381,6 @@ int jh_selftest_math(jh_ctx* ctx, int op, const float* a, const float* b, float*
     if (db) (void)hipFree(db);
     return rc == 0 ? JH_OK : fail(ctx, JH_ERR_DEVICE, "selftest launch failed");
 }
-
-int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 
 int jh_selftest_atomics(jh_ctx* ctx, int form, uint32_t seed, uint32_t n_waves) {
     if (!ctx) return JH_ERR_INVALID;
@@ -1444,24 +1425,12 @@ int jh_debug_flatten_regions(jh_ctx* ctx, uint32_t flags) {
 int jh_debug_clip_hint_overflows(jh_ctx* ctx, uint32_t* count, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (count) {
-        HIP_TRY(ctx, hipMemcpyAsync(count, ctx->hint_overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (reset) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->hint_overflow, 0, 4, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return JH_OK;
+    return counter_words(ctx, kHintOverflowWord, 1, count, reset);
 }
 #ifdef FINE_TIMING
 extern "C" int jh_debug_fine_timing(jh_ctx* ctx, unsigned long long* out6, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (out6) { HIP_TRY(ctx, hipMemcpyAsync(out6, ctx->hint_overflow + 8, 48, hipMemcpyDeviceToHost, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); }
-    if (reset) { HIP_TRY(ctx, hipMemsetAsync(ctx->hint_overflow + 8, 0, 48, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); }
-    return JH_OK;
+    return counter_words(ctx, kFineTimingWord, 12, out6, reset);
 }
 #endif
 uint64_t jh_debug_scratch_bytes(jh_ctx* ctx, int slot) {

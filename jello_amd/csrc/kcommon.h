@@ -356,6 +356,23 @@ struct JhDashJob {
 };
 JhResult jh_dash_launch(const JhLaunch& L, const JhDashJob& job, void* out, uint64_t capacity, uint32_t* index);
 
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _selftest .hip).  Declared
+// here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
+// side only does not compile.  int results: 0, -1 for arguments the launcher refuses, another negative value for a failed launch.
+extern "C" {
+int jh_blit_launch(hipStream_t stream, const void* src, void* dst, uint64_t pitch, uint32_t width, uint32_t row0, uint32_t row1, int format,
+                   int num_cus);
+int jh_blit_yuv_launch(hipStream_t stream, const void* src, void* const* planes, const uint64_t* pitches, uint32_t width, uint32_t height,
+                       uint32_t row0, uint32_t row1, int layout, int matrix, int range, int transfer, int num_cus);
+uint32_t jh_pack_groups(uint32_t n_tiles, uint32_t* run_out);
+int jh_pack_launch(hipStream_t stream, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
+                   uint32_t texel_bytes, void* dst, void* cls, void* totals);
+int jh_unpack_launch(hipStream_t stream, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
+                     uint32_t texel_bytes, uint32_t* rejects);
+int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
+int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
+}
+
 // Binding slots (the WGSL @binding order) of the stages whose bindings the held-back rules compare; the other stages name
 // theirs next to their launcher.
 enum { PR2_REDUCED, PR2_REDUCED2 };                            // pathtag_reduce2

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "blit_convert.h"
+#include "kcommon.h"
 
 namespace {
 
@@ -93,9 +94,7 @@ extern "C" int jh_blit_launch(hipStream_t stream, const void* src, void* dst, ui
     const uint64_t blocks_per_row = (items + kBlitThreads - 1u) / kBlitThreads;
     const uint64_t total = blocks_per_row * (row1 - row0);
     if (total > 0x7fffffffull) return -1;
-    // memory-bound: at most 8 resident blocks of 256 per CU, the rest by grid stride (the sRGB table is loaded once per block)
-    const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * 8u;
-    const dim3 grid((uint32_t)(total < cap ? total : cap)), block(kBlitThreads);
+    const dim3 grid(blit_grid_blocks(total, num_cus)), block(kBlitThreads);
     const uint2* s = (const uint2*)src;
     uint8_t* d = (uint8_t*)dst;
     const uint32_t bpr = (uint32_t)blocks_per_row, tb = (uint32_t)total;

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "blit_convert.h"
+#include "kcommon.h"
 #include "yuv_matrix_lut.h"
 
 namespace {
@@ -174,9 +175,7 @@ extern "C" int jh_blit_yuv_launch(hipStream_t stream, const void* src, void* con
     const int* m = kYuvMatrix[matrix][range];
     for (int i = 0; i < 3; i++) { k.y[i] = m[i]; k.cb[i] = m[3 + i]; k.cr[i] = m[6 + i]; }
     k.off = kYuvOffset[range];
-    // memory-bound: at most 8 resident blocks of 256 per CU, the rest by grid stride (the sRGB table is loaded once per block)
-    const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * 8u;
-    const dim3 grid((uint32_t)(total < cap ? total : cap)), block(kYuvThreads);
+    const dim3 grid(blit_grid_blocks(total, num_cus)), block(kYuvThreads);
     const uint2* s = (const uint2*)src;
     const uint32_t tpp = (uint32_t)tiles_per_pair, tt = (uint32_t)total;
     switch (transfer * 2 + layout) {

@@ -64,6 +64,7 @@ class CMD:
     UPLOAD, UPLOAD_UNIFORM, UPLOAD_IMAGE, WRITE_IMAGE, DISPATCH, DISPATCH_INDIRECT, DOWNLOAD, CLEAR, FREE_BUFFER, FREE_IMAGE = range(10)
 
 
+BUMP_NAMES = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]  # the words of a BumpAllocators
 RUN_UPLOADS, RUN_DISPATCHES, RUN_FREES, RUN_ALL = 1, 2, 4, 7
 RUN_SKIP_FINE, RUN_ONLY_FINE = 8, 16  # with RUN_DISPATCHES: everything but the fine stage / the fine stage alone
 
@@ -182,6 +183,22 @@ class Engine:
         if rc != 0:
             raise RuntimeError("%s failed (%d): %s | %s" % (what, rc, self._L.jl_last_error().decode(), self.hip.jh_last_error(self.ctx).decode()))
 
+    @staticmethod
+    def _frame_out():
+        """The (bump, attempts) out-parameters of the jl_engine_render* calls."""
+        return (ctypes.c_uint32 * 8)(), ctypes.c_int()
+
+    def _frame(self, h, bump, attempts, label):
+        """(Recording, bump dict, attempts) of the handle such a call returned; raises in `label`'s name if it returned none."""
+        if not h:
+            raise RuntimeError(label + ": " + self._L.jl_last_error().decode())
+        return Recording(self._L, h), dict(zip(BUMP_NAMES, bump)), attempts.value
+
+    def _own_buffer(self, buffer_id, nbytes):
+        """Device pointer of the context buffer `buffer_id`, created or grown to `nbytes` first (it only grows)."""
+        self._check(self.hip.jh_buffer_create(self.ctx, buffer_id, nbytes), "buffer_create")
+        return self.hip.jh_buffer_device_ptr(self.ctx, buffer_id)
+
     def run(self, recording, flags=RUN_ALL, out_device_ptr=None):
         self._check(self._L.jl_engine_run(self._h, recording._h, flags, 0, out_device_ptr), "run_recording")
 
@@ -191,21 +208,15 @@ class Engine:
     def render(self, scene, params, out_device_ptr=None, robust=True, retain=False):
         """RenderToTexture (+ regrow loop).  Returns (Recording, bump dict, attempts)."""
         p = params._c()
-        bump = (ctypes.c_uint32 * 8)()
-        attempts = ctypes.c_int()
+        bump, attempts = self._frame_out()
         h = self._L.jl_engine_render(self._h, scene._h, ctypes.byref(p), out_device_ptr, 1 if robust else 0, 1 if retain else 0, bump, ctypes.byref(attempts))
-        if not h:
-            raise RuntimeError("render_to_texture: " + self._L.jl_last_error().decode())
-        names = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]
-        return Recording(self._L, h), dict(zip(names, bump)), attempts.value
+        return self._frame(h, bump, attempts, "render_to_texture")
 
     def _surface(self, width, height, fmt, out_device_ptr, pitch):
         """(device pointer, pitch) to convert into: the caller's, or the engine's own buffer (tightly packed rows)."""
         if out_device_ptr is not None:
             return out_device_ptr, (4 * width if pitch is None else pitch)
-        pitch = 4 * width
-        self._check(self.hip.jh_buffer_create(self.ctx, _SURFACE_BUFFER_ID, max(pitch * height, 16)), "buffer_create")
-        return self.hip.jh_buffer_device_ptr(self.ctx, _SURFACE_BUFFER_ID), pitch
+        return self._own_buffer(_SURFACE_BUFFER_ID, max(4 * width * height, 16)), 4 * width
 
     def _download_surface(self, width, height):
         out = np.empty((height, width, 4), dtype=np.uint8)
@@ -227,15 +238,11 @@ class Engine:
         None with it.  The Recording's target image is the engine's target until the next render_to_surface."""
         ptr, pitch = self._surface(params.width, params.height, fmt, out_device_ptr, pitch)
         p = params._c()
-        bump = (ctypes.c_uint32 * 8)()
-        attempts = ctypes.c_int()
+        bump, attempts = self._frame_out()
         h = self._L.jl_engine_render_to_surface(self._h, scene._h, ctypes.byref(p), ptr, pitch, int(fmt), 1 if robust else 0, bump,
                                                 ctypes.byref(attempts))
-        if not h:
-            raise RuntimeError("render_to_surface: " + self._L.jl_last_error().decode())
-        names = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]
-        surface = None if out_device_ptr is not None else self._download_surface(params.width, params.height)
-        return surface, Recording(self._L, h), dict(zip(names, bump)), attempts.value
+        frame = self._frame(h, bump, attempts, "render_to_surface")
+        return (None if out_device_ptr is not None else self._download_surface(params.width, params.height),) + frame
 
     @staticmethod
     def yuv_plane_shapes(width, height, layout):
@@ -254,8 +261,7 @@ class Engine:
             for rows, rb in shapes:
                 own.append(off)
                 off += (rows * rb + 15) & ~15
-            self._check(self.hip.jh_buffer_create(self.ctx, _YUV_BUFFER_ID, max(off, 16)), "buffer_create")
-            base = self.hip.jh_buffer_device_ptr(self.ctx, _YUV_BUFFER_ID)
+            base = self._own_buffer(_YUV_BUFFER_ID, max(off, 16))
             planes = [(base + o, None) for o in own]
         for i, pl in enumerate(planes):
             ptr, pitch = pl if isinstance(pl, (tuple, list)) else (pl, None)
@@ -291,15 +297,11 @@ class Engine:
         render_to_surface / render_to_yuv."""
         d, own = self._yuv_desc(params.width, params.height, layout, matrix, range, transfer, planes)
         p = params._c()
-        bump = (ctypes.c_uint32 * 8)()
-        attempts = ctypes.c_int()
+        bump, attempts = self._frame_out()
         h = self._L.jl_engine_render_to_yuv(self._h, scene._h, ctypes.byref(p), ctypes.byref(d), 1 if robust else 0, bump,
                                             ctypes.byref(attempts))
-        if not h:
-            raise RuntimeError("render_to_yuv: " + self._L.jl_last_error().decode())
-        names = ["failed", "binning", "ptcl", "tile", "seg_counts", "segments", "blend", "lines"]
-        out = None if own is None else self._download_yuv(params.width, params.height, layout, own)
-        return out, Recording(self._L, h), dict(zip(names, bump)), attempts.value
+        frame = self._frame(h, bump, attempts, "render_to_yuv")
+        return (None if own is None else self._download_yuv(params.width, params.height, layout, own),) + frame
 
     def pack_tiles(self, src_ptr, pitch, width, height, texel_bytes, ref_ptr=None, ref_pitch=None, out_device_ptr=None,
                    out_capacity=None):
@@ -312,8 +314,7 @@ class Engine:
             dst, cap = out_device_ptr, (bound if out_capacity is None else out_capacity)
         else:
             cap = max(bound, 32)
-            self._check(self.hip.jh_buffer_create(self.ctx, _PACK_BUFFER_ID, cap), "buffer_create")
-            dst = self.hip.jh_buffer_device_ptr(self.ctx, _PACK_BUFFER_ID)
+            dst = self._own_buffer(_PACK_BUFFER_ID, cap)
         rp = 0 if ref_ptr is None else (pitch if ref_pitch is None else ref_pitch)
         self._check(self._L.jl_engine_pack_tiles(self._h, src_ptr, pitch, ref_ptr, rp, width, height, texel_bytes, dst, cap), "pack_tiles")
         return None if out_device_ptr is not None else self.read_pack(dst, cap)
@@ -331,8 +332,8 @@ class Engine:
         if isinstance(pack, (bytes, bytearray, memoryview)):
             data = bytes(pack)
             buf = ctypes.create_string_buffer(data, max(len(data), 1))
-            self._check(self.hip.jh_upload(self.ctx, _UNPACK_BUFFER_ID, buf, len(data)), "upload")
-            ptr, size = self.hip.jh_buffer_device_ptr(self.ctx, _UNPACK_BUFFER_ID), len(data)
+            ptr, size = self._own_buffer(_UNPACK_BUFFER_ID, len(data)), len(data)
+            self._check(self.hip.jh_upload(self.ctx, _UNPACK_BUFFER_ID, buf, size), "upload")
         else:
             ptr, size = pack
         self._check(self._L.jl_engine_unpack_tiles(self._h, ptr, size, dst_ptr, pitch, width, height, texel_bytes), "unpack_tiles")
@@ -381,11 +382,9 @@ class Engine:
         n_els = sum(len(p.els) for p in paths)
         cap = int(capacity) if capacity is not None else 8 * n_els + 256
         index = np.zeros(len(paths) + 1, dtype=np.uint32)
-        self._check(self.hip.jh_buffer_create(self.ctx, _DASH_INDEX_BUFFER_ID, index.nbytes), "buffer_create")
+        index_ptr = self._own_buffer(_DASH_INDEX_BUFFER_ID, index.nbytes)
         for attempt in range(2):
-            self._check(self.hip.jh_buffer_create(self.ctx, _DASH_ELS_BUFFER_ID, max(cap, 1) * DASH_EL.itemsize), "buffer_create")
-            self.dash_into(paths, patterns, offsets, self.hip.jh_buffer_device_ptr(self.ctx, _DASH_ELS_BUFFER_ID), cap,
-                           self.hip.jh_buffer_device_ptr(self.ctx, _DASH_INDEX_BUFFER_ID))
+            self.dash_into(paths, patterns, offsets, self._own_buffer(_DASH_ELS_BUFFER_ID, max(cap, 1) * DASH_EL.itemsize), cap, index_ptr)
             self._check(self.hip.jh_download(self.ctx, _DASH_INDEX_BUFFER_ID, index.ctypes.data, 0, index.nbytes), "download")
             if int(index[-1]) <= cap:
                 break

@@ -73,6 +73,18 @@ const char* jl_last_error() { return g_err.c_str(); }
         return failval;                     \
     }
 
+// GUARD for the calls that report the engine's own code: the JH_ERR_* of an EngineError, -100 for any other exception.
+#define GUARD_CODE(expr)                    \
+    try {                                   \
+        expr;                               \
+    } catch (const EngineError& e) {        \
+        g_err = e.what();                   \
+        return e.code;                      \
+    } catch (const std::exception& e) {     \
+        g_err = e.what();                   \
+        return -100;                        \
+    }
+
 static BezPath to_path(const jl_path_el* els, int n) {
     BezPath p;
     p.reserve((size_t)n);
@@ -384,14 +396,9 @@ int jl_engine_release(void* e, void* rec) {
     GUARD(eng->release(f), -1);
     return 0;
 }
-// One-call RenderToTexture with the regrow loop; returns a recording handle of the final attempt
-// (retain=1 keeps every buffer alive for inspection until jl_engine_release).
-void* jl_engine_render(void* e, void* scene, const jl_render_params* params, void* out_device, int robust, int retain, uint32_t* bump_out,
-                       int* attempts) {
-    Engine* eng = (Engine*)e;
+// The recording handle of a rendered frame's final attempt, with its bump allocators and attempt count for the caller.
+static void* rec_handle_of(Engine::Frame&& f, uint32_t* bump_out, int* attempts) {
     std::unique_ptr<RecHandle> h(new RecHandle());
-    Engine::Frame f;
-    GUARD(f = eng->render_to_texture(((Scene*)scene)->encoding(), to_params(params), out_device, robust != 0, retain != 0), nullptr);
     h->result.recording = std::move(f.recording);
     h->result.config = f.config;
     h->result.out_image = ResourceProxy::of(f.target);
@@ -401,6 +408,15 @@ void* jl_engine_render(void* e, void* scene, const jl_render_params* params, voi
     flatten_recording(h.get());
     return h.release();
 }
+// One-call RenderToTexture with the regrow loop; returns a recording handle of the final attempt
+// (retain=1 keeps every buffer alive for inspection until jl_engine_release).
+void* jl_engine_render(void* e, void* scene, const jl_render_params* params, void* out_device, int robust, int retain, uint32_t* bump_out,
+                       int* attempts) {
+    Engine* eng = (Engine*)e;
+    Engine::Frame f;
+    GUARD(f = eng->render_to_texture(((Scene*)scene)->encoding(), to_params(params), out_device, robust != 0, retain != 0), nullptr);
+    return rec_handle_of(std::move(f), bump_out, attempts);
+}
 
 // RenderToSurface (lib.go:266-333): RenderToTexture into the engine's own RGBA16F target, then the blit into `surface`
 // (jh_surface_format `format`, `pitch` bytes per row).  Returns the final attempt's recording handle like jl_engine_render;
@@ -408,17 +424,9 @@ void* jl_engine_render(void* e, void* scene, const jl_render_params* params, voi
 void* jl_engine_render_to_surface(void* e, void* scene, const jl_render_params* params, void* surface, uint64_t pitch, int format,
                                   int robust, uint32_t* bump_out, int* attempts) {
     Engine* eng = (Engine*)e;
-    std::unique_ptr<RecHandle> h(new RecHandle());
     Engine::Frame f;
     GUARD(f = eng->render_to_surface(((Scene*)scene)->encoding(), to_params(params), surface, pitch, format, robust != 0), nullptr);
-    h->result.recording = std::move(f.recording);
-    h->result.config = f.config;
-    h->result.out_image = ResourceProxy::of(f.target);
-    h->buffers = f.buffers;
-    if (bump_out) std::memcpy(bump_out, &f.bump, sizeof(JlBump));
-    if (attempts) *attempts = f.attempts;
-    flatten_recording(h.get());
-    return h.release();
+    return rec_handle_of(std::move(f), bump_out, attempts);
 }
 int jl_engine_blit(void* e, uint64_t src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format) {
     GUARD(((Engine*)e)->blit(src_image_id, surface, pitch, width, height, format), -1);
@@ -431,17 +439,9 @@ void* jl_engine_render_to_yuv(void* e, void* scene, const jl_render_params* para
                               int* attempts) {
     Engine* eng = (Engine*)e;
     if (!desc) { g_err = "render_to_yuv: null descriptor"; return nullptr; }
-    std::unique_ptr<RecHandle> h(new RecHandle());
     Engine::Frame f;
     GUARD(f = eng->render_to_yuv(((Scene*)scene)->encoding(), to_params(params), *desc, robust != 0), nullptr);
-    h->result.recording = std::move(f.recording);
-    h->result.config = f.config;
-    h->result.out_image = ResourceProxy::of(f.target);
-    h->buffers = f.buffers;
-    if (bump_out) std::memcpy(bump_out, &f.bump, sizeof(JlBump));
-    if (attempts) *attempts = f.attempts;
-    flatten_recording(h.get());
-    return h.release();
+    return rec_handle_of(std::move(f), bump_out, attempts);
 }
 int jl_engine_blit_yuv(void* e, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc) {
     if (!desc) { g_err = "blit_yuv: null descriptor"; return -1; }
@@ -463,15 +463,7 @@ int jl_engine_unpack_tiles(void* e, const void* pack, uint64_t pack_bytes, void*
 // Engine::dash_paths (jh_dash).  Returns 0, or the JH_ERR_* code (negative) with jl_last_error set.
 int jl_engine_dash_paths(void* e, const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
                          uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index) {
-    try {
-        ((Engine*)e)->dash_paths(els, n_els, paths, n_paths, dashes, n_dashes, out_els, out_capacity, out_index);
-    } catch (const EngineError& err) {
-        g_err = err.what();
-        return err.code;
-    } catch (const std::exception& err) {
-        g_err = err.what();
-        return -100;
-    }
+    GUARD_CODE(((Engine*)e)->dash_paths(els, n_els, paths, n_paths, dashes, n_dashes, out_els, out_capacity, out_index));
     return 0;
 }
 // The pack at device_ptr into `out`: the header first, then exactly the size it states (written to *size).

@@ -19,9 +19,8 @@ void Engine::check(int rc, const char* what) {
 
 void Engine::run_recording(const Recording& rec, const std::vector<ExternalImage>& ext_images, const std::vector<ExternalBuffer>& ext_buffers,
                            unsigned flags) {
-    // pgroup = pgroup.Nest("RunRecording"); defer pgroup.End()  (wgpu.go:330-331) -- a no-op unless profiling is on
-    check(jh_profile_group_begin(ctx_, "RunRecording"), "profile_group_begin");
-    struct GroupEnd { jh_ctx* c; ~GroupEnd() { (void)jh_profile_group_end(c); } } group_end{ctx_};
+    // pgroup = pgroup.Nest("RunRecording"); defer pgroup.End()  (wgpu.go:330-331)
+    ProfileGroup group(*this, "RunRecording");
     // every recording brings its own bound (0 = unknown: fine reserves the worst case): a stale hint must never outlive its scene
     check(jh_set_clip_depth_hint(ctx_, rec.max_clip_depth), "set_clip_depth_hint");
     for (const ExternalImage& e : ext_images)
@@ -176,16 +175,14 @@ Engine::Frame Engine::render_to_texture(const Encoding& enc, RenderParams params
 
 Engine::Frame Engine::render_to_surface(const Encoding& enc, RenderParams params, void* surface, uint64_t pitch, int format, bool robust) {
     // pgroup = pgroup.Nest("RenderToSurface"); defer pgroup.End()  (lib.go:274-275)
-    check(jh_profile_group_begin(ctx_, "RenderToSurface"), "profile_group_begin");
-    struct GroupEnd { jh_ctx* c; ~GroupEnd() { (void)jh_profile_group_end(c); } } group_end{ctx_};
+    ProfileGroup group(*this, "RenderToSurface");
     Frame f = render_to_own_target(enc, params, robust);
     blit(f.target.id, surface, pitch, params.width, params.height, format);
     return f;
 }
 
 Engine::Frame Engine::render_to_yuv(const Encoding& enc, RenderParams params, const jh_yuv_desc& desc, bool robust) {
-    check(jh_profile_group_begin(ctx_, "RenderToYUV"), "profile_group_begin");
-    struct GroupEnd { jh_ctx* c; ~GroupEnd() { (void)jh_profile_group_end(c); } } group_end{ctx_};
+    ProfileGroup group(*this, "RenderToYUV");
     Frame f = render_to_own_target(enc, params, robust);
     blit_yuv(f.target.id, params.width, params.height, desc);
     return f;

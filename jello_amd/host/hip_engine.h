@@ -98,6 +98,14 @@ class Engine {
    private:
     void check(int rc, const char* what);
     jh_ctx* ctx_ = nullptr;
+    // One group of the profile tree (pgroup.Nest(label); defer pgroup.End()): open for as long as the object lives.  A no-op
+    // unless profiling is on.
+    struct ProfileGroup {
+        ProfileGroup(Engine& e, const char* label) : ctx(e.ctx_) { e.check(jh_profile_group_begin(ctx, label), "profile_group_begin"); }
+        ~ProfileGroup() { (void)jh_profile_group_end(ctx); }
+        ProfileGroup(const ProfileGroup&) = delete;
+        jh_ctx* ctx;
+    };
     Renderer renderer_;
     Resolver resolver_;
     FullShaders shaders_;

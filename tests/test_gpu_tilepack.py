@@ -13,36 +13,12 @@ from jello_amd import Surface, scenes, tilepack
 from jello_amd.engine import RUN_DISPATCHES, RUN_UPLOADS
 
 import tilepack_ref as ref
+from devmem import CANARY, DevBuf
 from tilepack_cases import CASES, DTYPES, case_frames, make_frame
 
 pytestmark = pytest.mark.gpu
 
 JH_ERR_INVALID = -1
-CANARY = 0xA7
-_next_id = [0x7E57_7000_0000]
-
-
-def _id():
-    _next_id[0] += 1
-    return _next_id[0]
-
-
-class DevBuf:
-    """A context buffer used as caller-owned device memory: `data` (bytes-like) or `nbytes` of CANARY."""
-
-    def __init__(self, engine, nbytes=None, data=None):
-        host = np.full(max(int(nbytes), 16), CANARY, np.uint8) if data is None else np.frombuffer(bytes(data), np.uint8)
-        self.e, self.id, self.n = engine, _id(), host.size
-        engine._check(engine.hip.jh_upload(engine.ctx, self.id, host.ctypes.data, self.n), "upload")
-        self.ptr = engine.hip.jh_buffer_device_ptr(engine.ctx, self.id)
-
-    def bytes(self):
-        return self.e.download(self.id, self.n).copy()
-
-    def free(self):
-        self.e.hip.jh_free(self.e.ctx, self.id)
-
-
 def laid_out(frame, pitch, offset, tail=64):
     """The frame's rows `pitch` bytes apart, `offset` bytes into a CANARY-filled byte array with `tail` bytes behind."""
     h, w = frame.shape[:2]

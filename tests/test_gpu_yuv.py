@@ -17,40 +17,13 @@ from oracle.oracle_engine import OracleEngine
 
 import surface_ref
 import yuv_ref as ref
+from devmem import CANARY, SCENES, DevBuf, _id, target_of
 
 pytestmark = pytest.mark.gpu
 
 JL_RGBA8, JL_RGBA16_FLOAT = 0, 3
 JH_ERR_INVALID = -1
-CANARY = 0xA7
-_next_id = [0x7E57_6000_0000]
 COMBOS = list(itertools.product(YuvLayout, YuvMatrix, YuvRange, YuvTransfer))
-
-
-def _id():
-    _next_id[0] += 1
-    return _next_id[0]
-
-
-class DevBuf:
-    """A context buffer used as caller-owned device memory, filled with CANARY."""
-
-    def __init__(self, engine, nbytes):
-        self.e, self.id, self.n = engine, _id(), max(int(nbytes), 16)
-        fill = np.full(self.n, CANARY, np.uint8)
-        engine._check(engine.hip.jh_upload(engine.ctx, self.id, fill.ctypes.data, self.n), "upload")
-        self.ptr = engine.hip.jh_buffer_device_ptr(engine.ctx, self.id)
-
-    def bytes(self):
-        return self.e.download(self.id, self.n).copy()
-
-    def free(self):
-        self.e.hip.jh_free(self.e.ctx, self.id)
-
-
-def target_of(engine, rec):
-    t = rec.target
-    return engine.download_image(t["id"], t["width"], t["height"]).copy()
 
 
 def assert_planes(got, want, what):
@@ -67,34 +40,6 @@ def _name(layout, matrix, rng, transfer):
     return "%s %s %s %s" % (layout.name, matrix.name, rng.name, transfer.name)
 
 
-def _fuzz(seed, size=256):
-    return scenes.scene_fuzz(seed, size=size)
-
-
-def _odd(w, h, seed):
-    s, p = scenes.scene_fuzz(seed, size=max(w, h), n=20)
-    p.width, p.height = w, h
-    return s, p
-
-
-def _msaa(aa):
-    s, p = scenes.scene_c1()
-    p.aa = aa
-    return s, p
-
-
-# the scene set of test_gpu_surface.py
-SCENES = {
-    "c1_area": scenes.scene_c1,
-    "c1_msaa8": lambda: _msaa(jello_amd.Aa.Msaa8),
-    "c1_msaa16": lambda: _msaa(jello_amd.Aa.Msaa16),
-    "images": scenes.scene_images,
-    "c4_small": lambda: scenes.scene_c4(1500, 512),
-    "odd_1x1": lambda: _odd(1, 1, 11),
-    "odd_3x7": lambda: _odd(3, 7, 12),
-    "odd_1001x517": lambda: _odd(1001, 517, 13),
-}
-SCENES.update({"fuzz%d" % k: (lambda k=k: _fuzz(k)) for k in range(8)})
 ORACLE_SUBSET = ("c1_area", "images", "odd_3x7", "odd_1001x517", "fuzz0", "fuzz5")
 
 

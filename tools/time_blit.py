@@ -9,15 +9,12 @@ import argparse
 import json
 import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT, open_engine_on_stream, timed, write_json
 
-import jello_amd  # noqa: E402
-from jello_amd import Surface  # noqa: E402
+from jello_amd import Surface  # noqa: E402 (timing puts the root on sys.path)
 
 JL_RGBA16_FLOAT = 3
 
@@ -29,11 +26,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "blit_timing.json"))
     a = ap.parse_args()
     import torch
-    dev = torch.device("cuda", 0)
-    eng = jello_amd.Engine(0)
+    eng, stream = open_engine_on_stream()
     hip, ctx = eng.hip, eng.ctx
-    stream = torch.cuda.Stream(dev)
-    eng.set_stream(stream.cuda_stream)
     rng = np.random.default_rng(1)
     results = []
     for size in (4096, 2048):
@@ -45,17 +39,7 @@ def main():
         eng._check(hip.jh_buffer_create(ctx, dst, 4 * n), "buffer_create")
         ptr = hip.jh_buffer_device_ptr(ctx, dst)
         for fmt in Surface:
-            for _ in range(3):  # warm-up
-                eng._check(hip.jh_blit(ctx, src, ptr, 4 * size, size, size, int(fmt)), "blit")
-            times = []
-            for _ in range(a.blocks):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                for _ in range(a.per_block):
-                    eng._check(hip.jh_blit(ctx, src, ptr, 4 * size, size, size, int(fmt)), "blit")
-                e1.record(stream)
-                e1.synchronize()
-                times.append(e0.elapsed_time(e1) * 1e3 / a.per_block)  # us per blit
+            times = timed(stream, lambda: eng._check(hip.jh_blit(ctx, src, ptr, 4 * size, size, size, int(fmt)), "blit"), a.blocks, a.per_block)
             med = statistics.median(times)
             r = {"size": size, "format": fmt.name, "us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times],
                  "algorithmic_bytes": 12 * n, "tb_per_s": round(12 * n / (med * 1e-6) / 1e12, 3)}
@@ -66,14 +50,11 @@ def main():
     eng.sync()
     eng.set_stream(None)
     eng.close()
-    out = {"tool": "tools/time_blit.py", "device": torch.cuda.get_device_name(dev), "blocks": a.blocks, "per_block": a.per_block,
+    out = {"tool": "tools/time_blit.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block,
            "note": "hipEvents around back-to-back blits of one source into one surface (both stay in the 256 MiB Infinity "
                    "Cache at 4096^2: 201 MB); kernel times: the rocprofv3 stats file next to this one",
            "results": results}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    write_json(a.out, out)
 
 
 if __name__ == "__main__":

@@ -12,15 +12,13 @@ import ctypes
 import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT, write_json
 
-import jello_amd  # noqa: E402
+import jello_amd  # noqa: E402 (timing puts the root on sys.path)
 from jello_amd import _lib, scenes  # noqa: E402
 from jello_amd.engine import DASH_EL  # noqa: E402
 
@@ -112,10 +110,7 @@ def main():
                  "host_route_ms_all_paths: jl_dash_path on the first host_route_sample paths, single-threaded, minus the same number of "
                  "calls on an empty path, scaled to all paths"}
     print(json.dumps(r))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(r, f, indent=1)
-    print("wrote", a.out)
+    write_json(a.out, r)
     eng.close()
 
 

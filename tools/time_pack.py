@@ -16,15 +16,13 @@ import ctypes
 import json
 import os
 import statistics
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT, open_engine_on_stream, timed, write_json
 
-import jello_amd  # noqa: E402
+import jello_amd  # noqa: E402 (timing puts the root on sys.path)
 from jello_amd import Surface, scenes, tilepack  # noqa: E402
 
 _ids = [0x71C0_0000_0000]
@@ -68,27 +66,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pack_kernel_times.json"))
     a = ap.parse_args()
     import torch
-    dev = torch.device("cuda", 0)
-    eng = jello_amd.Engine(0)
+    eng, stream = open_engine_on_stream()
     hip, ctx = eng.hip, eng.ctx
     rt = ctypes.CDLL("libamdhip64.so")
     rt.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    stream = torch.cuda.Stream(dev)
-    eng.set_stream(stream.cuda_stream)
     rng = np.random.default_rng(1)
 
     def device_us(fn):
-        for _ in range(3):  # warm-up
-            fn()
-        times = []
-        for _ in range(a.blocks):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for _ in range(a.per_block):
-                fn()
-            e1.record(stream)
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3 / a.per_block)
+        times = timed(stream, fn, a.blocks, a.per_block)
         return round(statistics.median(times), 3), round(min(times), 3), round(max(times), 3)
 
     def host_us(fn):
@@ -172,7 +157,7 @@ def main():
     eng.sync()
     eng.set_stream(None)
     eng.close()
-    out = {"tool": "tools/time_pack.py", "device": torch.cuda.get_device_name(dev), "blocks": a.blocks, "per_block": a.per_block,
+    out = {"tool": "tools/time_pack.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block,
            "host_reps": a.host_reps,
            "note": "device times: hipEvents around blocks of back-to-back calls on one stream, median of the blocks, us per call; "
                    "copy = hipMemcpyDtoDAsync of frame_bytes in the same run (source, pack and destination of a 4096^2 RGBA8 "
@@ -180,10 +165,7 @@ def main():
                    "pack + read_pack (two synchronising downloads into pageable memory) and around jh_download of the whole "
                    "frame (one), median of the repetitions",
            "results": results}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    write_json(a.out, out)
 
 
 if __name__ == "__main__":

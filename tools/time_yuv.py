@@ -13,15 +13,12 @@ import ctypes
 import json
 import os
 import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_json
 
-import jello_amd  # noqa: E402
-from jello_amd import Surface, YuvLayout, YuvMatrix, YuvRange, YuvTransfer  # noqa: E402
+from jello_amd import Surface, YuvLayout, YuvMatrix, YuvRange, YuvTransfer  # noqa: E402 (timing puts the root on sys.path)
 
 JL_RGBA16_FLOAT = 3
 
@@ -33,26 +30,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "yuv_kernel_times.json"))
     a = ap.parse_args()
     import torch
-    dev = torch.device("cuda", 0)
-    eng = jello_amd.Engine(0)
+    eng, stream = open_engine_on_stream()
     hip, ctx = eng.hip, eng.ctx
-    stream = torch.cuda.Stream(dev)
-    eng.set_stream(stream.cuda_stream)
     rng = np.random.default_rng(1)
 
     def timed(launch):
-        for _ in range(3):  # warm-up
-            launch()
-        times = []
-        for _ in range(a.blocks):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for _ in range(a.per_block):
-                launch()
-            e1.record(stream)
-            e1.synchronize()
-            times.append(e0.elapsed_time(e1) * 1e3 / a.per_block)  # us per launch
-        return times
+        return timed_blocks(stream, launch, a.blocks, a.per_block)
 
     blits, yuvs = [], []
     for size in (4096, 2048):
@@ -94,15 +77,12 @@ def main():
     eng.sync()
     eng.set_stream(None)
     eng.close()
-    out = {"tool": "tools/time_yuv.py", "device": torch.cuda.get_device_name(dev), "blocks": a.blocks, "per_block": a.per_block,
+    out = {"tool": "tools/time_yuv.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block,
            "note": "hipEvents around back-to-back launches of one source into one destination (both stay in the Infinity Cache); "
                    "the yardstick of a jh_blit_yuv case is the jh_blit of the same transfer from this run, the margin that "
                    "blit's own max - min over its blocks",
            "blit": blits, "blit_yuv": yuvs}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    write_json(a.out, out)
 
 
 if __name__ == "__main__":
