@@ -21,6 +21,7 @@
  *   jh_blit_yuv                   (no counterpart: the same target as NV12 / I420 video frames)
  *   jh_pack_tiles / jh_unpack_tiles   (no counterpart: the frame's way off the GPU)
  *   jh_dash                           (no counterpart: the reference dashes on the CPU with curve.Dash)
+ *   jh_blur                           (no counterpart: Gaussian blur of the RGBA16F target on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -361,6 +362,52 @@ typedef struct jh_dash_path { uint32_t first_el, n_els, first_dash, n_dash; doub
 typedef struct jh_dash_out_el { uint32_t kind; float p[6]; } jh_dash_out_el;
 int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
             uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index);
+
+/* ---- Gaussian blur of an RGBA16F image (DESIGN.md 5.7 "Blur rule") ----
+ * Drop shadows, glows, backdrop blur, feGaussianBlur and CSS blur() without the target leaving the device.  The result is defined
+ * on values, not on passes, and every implementation produces these bits (include/jello_blur.h states the host half,
+ * tests/blur_ref.py restates all of it):
+ *   taps        one axis with standard deviation sigma (binary32, used as binary64), 0 <= sigma <= 64 = JH_BLUR_MAX_SIGMA:
+ *               R = ceil(3 sigma) <= 192; sigma = 0: R = 0 and the single tap 1.0f; otherwise g_k = exp(-(double)(k k) / (2.0 sigma
+ *               sigma)), k = 0..R (one libm exp per tap, the only inexact library call), S = g_0 + 2 (g_1 + ... + g_R) with the
+ *               bracket summed in that order in binary64, w_k = (float)(g_k / S), w_-k = w_k.
+ *   horizontal  per texel and channel  H = 0.0f; for k = -R_x .. +R_x ascending: H = fmaf(w_k, (float)src[x + k], H)
+ *               -- a fused multiply-add; H is binary32 and is never rounded to f16.
+ *   vertical    V = 0.0f; for k = -R_y .. +R_y ascending: V = fmaf(w_k, H[y + k], V); dst = f16(V), round to nearest even, once.
+ *   edges       JH_BLUR_EDGE_ZERO: a tap outside the image contributes nothing (its fmaf is not executed);
+ *               JH_BLUR_EDGE_CLAMP: it reads the nearest texel of the image.  The image is the edge, not the rectangle.
+ *   values      f16 subnormals are values, in and out: nothing is flushed.  Inf and NaN follow IEEE; a NaN result is any NaN.
+ * So sigma_x = sigma_y = 0 is a bit-exact copy of every value (a -0 comes out as +0: fmaf(1, -0, +0) = +0; a NaN as a NaN), and
+ * sigma = 0 on one axis leaves the one rounding of the other axis' sum.
+ *
+ * jh_blur_taps: the 2R + 1 taps of `sigma` into weights (weights[k + R] = w_k; may be NULL) and R into *radius (may be NULL).
+ * Host only, no context.  JH_ERR_INVALID for a sigma that is negative, above 64 or NaN.
+ *
+ * jh_blur: blurs the image src_image_id (width x height, JL_RGBA16_FLOAT) into the rectangle (x, y, width, height) of
+ * dst_image_id (the same size and format); desc->width == desc->height == 0 means the whole image (x and y are then ignored).
+ * dst_image_id may equal src_image_id: in place, with the result of a blur into a second image.  Texels of dst outside the
+ * rectangle keep their bits; a dst that was never written is cleared to transparent black first, so outside the rectangle it
+ * reads as it did before; dst then counts as written.  Source texels outside the rectangle but inside the image take part with
+ * their real values; a source that was never written reads as transparent black.
+ * Stream-ordered on the context's stream, never waits: two kernel launches (rows into a binary32 intermediate, columns out of
+ * it), plus a fill when dst has to be cleared.  The intermediate lives in a scratch array of the context, at most
+ * (rect height + 2 R_y) x rect width x 16 bytes, which only grows: the call may be captured between jh_graph_begin and
+ * jh_graph_end once a rectangle of this size has been blurred eagerly (a capture that would have to grow it is refused with
+ * JH_ERR_OOM and that advice).  With profiling on the call is a query "blur" with stage = -1 in jh_profile_collect_tree.
+ * Not in band mode (jh_set_band): the rows next to a band belong to another rank's context, and a blur reads across them.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_blur: ": a null
+ * desc; an unknown source or destination id; an image that is not RGBA16F or whose size differs from width x height; a sigma that
+ * is negative, above 64 or NaN; an unknown edge mode; a rectangle that is not inside the image or that is empty in exactly one
+ * dimension; a band set with jh_set_band. */
+#define JH_BLUR_MAX_SIGMA 64.0f
+typedef enum jh_blur_edge { JH_BLUR_EDGE_ZERO = 0, JH_BLUR_EDGE_CLAMP = 1 } jh_blur_edge;
+typedef struct jh_blur_desc {
+    float sigma_x, sigma_y;
+    int edge;                     /* JH_BLUR_EDGE_ZERO | JH_BLUR_EDGE_CLAMP */
+    uint32_t x, y, width, height; /* rectangle of dst that is written; width == height == 0: the whole image */
+} jh_blur_desc;
+int jh_blur_taps(float sigma, float* weights /* 2R+1 entries, or NULL */, uint32_t* radius);
+int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -461,6 +461,32 @@ func (e *Engine) DashPaths(els []DashEl, paths []DashPath, dashes []float64, out
 		C.uint64_t(capacity), (*C.uint32_t)(outIndex)), "dash")
 }
 
+// BlurEdge is jh_blur_edge: what a tap outside the image reads.
+type BlurEdge int32
+
+const (
+	BlurEdgeZero  BlurEdge = 0 // nothing
+	BlurEdgeClamp BlurEdge = 1 // the nearest texel of the image
+)
+
+// BlurDesc is jh_blur_desc (include/jello_hip.h "Gaussian blur"): the standard deviations of the two axes (0 .. 64), the edge
+// mode and the rectangle of dst that is written (Width == Height == 0: the whole image).
+type BlurDesc struct {
+	SigmaX, SigmaY      float32
+	Edge                BlurEdge
+	X, Y, Width, Height uint32
+}
+
+// Blur is jh_blur: the Gaussian blur of the RGBA16F image src into the rectangle of dst that desc names, by the rule of
+// DESIGN.md 5.7 (defined on values: every implementation gives the same bits).  dst may be src.  Texels of dst outside the
+// rectangle keep their bits; source texels outside it take part.  Stream-ordered behind the frame, waits for nothing; for drop
+// shadows, glows, backdrop blur, feGaussianBlur and CSS blur() between RenderToTexture and the surface / YUV / pack conversion.
+func (e *Engine) Blur(src, dst renderer.ImageProxy, desc BlurDesc) {
+	d := C.jh_blur_desc{sigma_x: C.float(desc.SigmaX), sigma_y: C.float(desc.SigmaY), edge: C.int(desc.Edge), x: C.uint32_t(desc.X),
+		y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height)}
+	e.check(C.jh_blur(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), C.uint32_t(src.Width), C.uint32_t(src.Height), &d), "blur")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -133,6 +133,12 @@ class CYuvDesc(ctypes.Structure):
                 ("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_uint64 * 3)]
 
 
+class CBlurDesc(ctypes.Structure):
+    """jh_blur_desc (include/jello_hip.h)."""
+    _fields_ = [("sigma_x", ctypes.c_float), ("sigma_y", ctypes.c_float), ("edge", ctypes.c_int32), ("x", ctypes.c_uint32),
+                ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
+
+
 def _declare(L):
     vp, ci, cu = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
     dp = ctypes.POINTER(ctypes.c_double)
@@ -193,6 +199,8 @@ def _declare(L):
     L.jl_engine_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
     L.jl_engine_read_pack.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
     L.jl_engine_dash_paths.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
+    L.jl_engine_blur.argtypes = [vp, u64, u64, u32, u32, ctypes.POINTER(CBlurDesc)]
+    L.jl_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
     L.hip = hip
@@ -220,6 +228,7 @@ def _declare(L):
     hip.jh_image_create.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
     hip.jh_image_upload.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci, vp, ctypes.c_uint64]
     hip.jh_image_free.argtypes = [vp, ctypes.c_uint64]
+    hip.jh_image_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint32, ctypes.c_uint32, ci]
     hip.jh_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
     hip.jh_blit_yuv.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(CYuvDesc)]
     hip.jh_pack_bound.restype = u64
@@ -227,6 +236,8 @@ def _declare(L):
     hip.jh_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
     hip.jh_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
     hip.jh_dash.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
+    hip.jh_blur.argtypes = [vp, u64, u64, u32, u32, ctypes.POINTER(CBlurDesc)]
+    hip.jh_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "kcommon.h"
+#include "../../include/jello_blur.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -1132,7 +1133,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1351,6 +1352,56 @@ int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_pa
             if (lr == JH_L_SCRATCH) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
             if (hipGetLastError() != hipSuccess) return fail(ctx, JH_ERR_DEVICE, "jh_dash: launch failed");
             return (int)JH_OK;
+        });
+}
+
+// blur (include/jello_hip.h "Gaussian blur"; the taps: include/jello_blur.h; kernels_blur.hip)
+int jh_blur_taps(float sigma, float* weights, uint32_t* radius) {
+    if (!jblur_sigma_ok(sigma)) return JH_ERR_INVALID;
+    const uint32_t R = jblur_taps(sigma, weights);
+    if (radius) *radius = R;
+    return JH_OK;
+}
+
+int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_blur: null descriptor");
+    const Alloc* src = nullptr;
+    if (int rc = rgba16f_source(ctx, src_image_id, width, height, "jh_blur", &src)) return rc;
+    Alloc* dst = find_alloc(ctx->images, dst_image_id);
+    if (!dst) return fail(ctx, JH_ERR_INVALID, "jh_blur: unknown destination image id");
+    if (dst->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_blur: the destination is not an RGBA16F image");
+    if (dst->width != width || dst->height != height) return fail(ctx, JH_ERR_INVALID, "jh_blur: size differs from the destination image");
+    if (!jblur_sigma_ok(desc->sigma_x) || !jblur_sigma_ok(desc->sigma_y)) return fail(ctx, JH_ERR_INVALID, "jh_blur: sigma is negative, above 64 or NaN");
+    if (desc->edge != JH_BLUR_EDGE_ZERO && desc->edge != JH_BLUR_EDGE_CLAMP) return fail(ctx, JH_ERR_INVALID, "jh_blur: unknown edge mode");
+    uint32_t x = desc->x, y = desc->y, rw = desc->width, rh = desc->height;
+    if (rw == 0u && rh == 0u) { x = 0u; y = 0u; rw = width; rh = height; }  // the whole image
+    else if (rw == 0u || rh == 0u) return fail(ctx, JH_ERR_INVALID, "jh_blur: the rectangle is empty in one dimension");
+    if ((uint64_t)x + rw > width || (uint64_t)y + rh > height) return fail(ctx, JH_ERR_INVALID, "jh_blur: the rectangle is not inside the image");
+    if (ctx->band_row0 != 0u || ctx->band_row1 != 0xffffffffu)
+        return fail(ctx, JH_ERR_INVALID, "jh_blur: not in band mode (the rows next to a band belong to another rank)");
+    float taps_x[2u * JBLUR_MAX_RADIUS + 1u], taps_y[2u * JBLUR_MAX_RADIUS + 1u];
+    const uint32_t radius_x = jblur_taps(desc->sigma_x, taps_x), radius_y = jblur_taps(desc->sigma_y, taps_y);
+    void* tmp = nullptr;
+    return post_render_call(
+        ctx, "blur",
+        [&] {
+            if (rw == 0u || rh == 0u) return (int)JH_OK;  // (an image without texels)
+            const uint64_t rows = std::min<uint64_t>(height, (uint64_t)y + rh + radius_y) - (y > radius_y ? y - radius_y : 0u);
+            tmp = jh_scratch_get(&ctx->scratch, JH_SCR_BLUR, rows * rw * 16u);
+            if (tmp) return (int)JH_OK;
+            return fail(ctx, JH_ERR_OOM, "jh_blur: " + scratch_failure(ctx, "blur a rectangle of this size once eagerly first"));
+        },
+        [&] {
+            if (rw == 0u || rh == 0u) return (int)JH_OK;
+            const void* from = content_or_null(*src);  // (before dst, which may be the same image, becomes written)
+            if (!(dst->written || dst->stored)) {  // outside the rectangle it goes on reading as transparent black
+                if (rw != width || rh != height) HIP_TRY(ctx, hipMemsetAsync(dst->ptr, 0, dst->size, ctx->stream));
+                ctx->generation++;  // (fine binds a never-written image as absent: the choice is baked into a graph)
+            }
+            dst->written = true;
+            return launch_status(ctx, "jh_blur", jh_blur_launch(ctx->stream, from, dst->ptr, width, height, x, y, rw, rh, desc->edge == JH_BLUR_EDGE_CLAMP,
+                                                                taps_x, radius_x, taps_y, radius_y, tmp, ctx->num_cus));
         });
 }
 

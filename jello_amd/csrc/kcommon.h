@@ -259,6 +259,8 @@ struct JhImageDesc {
 //   FL_CTR    list counters / chunk fills                                                                            self-cleaned
 //   BD_CTR                                              wide counter  (zeroed by k_pc_count)                         self-cleaned
 //   PC_TOT                                                            crossings per path                             self-cleaned
+//   BLUR      (jh_blur, a call outside the frame's stages: the binary32 rows between its two passes -- a slot of its own, so that a
+//              frame between two blurs of one size never makes it grow and a captured blur stays valid)
 enum {
     JH_SCR_SCAN_TMP = 0,
     JH_SCR_A = 1,
@@ -274,7 +276,8 @@ enum {
     JH_SCR_FL_CTR = 11,  // flatten's list counters / chunk fills: NOT shared with other stages (they survive between frames)
     JH_SCR_BD_CTR = 12,  // backdrop's wide-row counter: likewise
     JH_SCR_PC_TOT = 13,  // path_count's crossings per path (atomic sums): likewise, zeroed by the stage's last kernel
-    JH_SCR_COUNT = 14
+    JH_SCR_BLUR = 14,    // jh_blur's intermediate
+    JH_SCR_COUNT = 15
 };
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
@@ -356,7 +359,7 @@ struct JhDashJob {
 };
 JhResult jh_dash_launch(const JhLaunch& L, const JhDashJob& job, void* out, uint64_t capacity, uint32_t* index);
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses, another negative value for a failed launch.
 extern "C" {
@@ -369,6 +372,8 @@ int jh_pack_launch(hipStream_t stream, const void* src, uint64_t src_pitch, cons
                    uint32_t texel_bytes, void* dst, void* cls, void* totals);
 int jh_unpack_launch(hipStream_t stream, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
                      uint32_t texel_bytes, uint32_t* rejects);
+int jh_blur_launch(hipStream_t stream, const void* src, void* dst, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t rect_w,
+                   uint32_t rect_h, int clamp, const float* taps_x, uint32_t radius_x, const float* taps_y, uint32_t radius_y, void* tmp, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

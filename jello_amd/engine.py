@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CConfig, CYuvDesc
+from ._lib import CBlurDesc, CConfig, CYuvDesc
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
                "flatten", "draw_reduce", "draw_leaf", "clip_reduce", "clip_leaf", "binning", "tile_alloc", "backdrop_dyn",
@@ -46,6 +46,34 @@ class YuvTransfer(enum.IntEnum):
     """jh_yuv_transfer: the R'G'B' codes are those of Surface.RGBA8_UNORM (NONE) or Surface.RGBA8_SRGB (SRGB)."""
     NONE = 0
     SRGB = 1
+
+
+class BlurEdge(enum.IntEnum):
+    """jh_blur_edge: what a tap outside the image reads -- nothing (ZERO), or the nearest texel of the image (CLAMP)."""
+    ZERO = 0
+    CLAMP = 1
+
+
+BLUR_MAX_SIGMA = 64.0
+
+
+def blur_taps(sigma):
+    """jh_blur_taps: (weights, R) of one axis of the blur rule -- the 2R + 1 float32 taps w[-R..R] of `sigma` and
+    R = ceil(3 sigma).  No GPU needed.  ValueError for a sigma that is negative, above 64 or NaN."""
+    hip = _lib.load_host().hip
+    sigma = float(np.float32(sigma))
+    r = ctypes.c_uint32(0)
+    if hip.jh_blur_taps(sigma, None, ctypes.byref(r)) != 0:
+        raise ValueError("blur_taps: sigma is negative, above 64 or NaN")
+    w = np.empty(2 * r.value + 1, dtype=np.float32)
+    hip.jh_blur_taps(sigma, w.ctypes.data, None)
+    return w, r.value
+
+
+def _blur_desc(sigma, edge, rect):
+    sx, sy = sigma if isinstance(sigma, (tuple, list)) else (sigma, sigma)
+    x, y, w, h = (0, 0, 0, 0) if rect is None else rect
+    return CBlurDesc(float(sx), float(sy), int(edge), int(x), int(y), int(w), int(h))
 
 
 # a context buffer that blit / render_to_surface convert into when the caller passes no device pointer (it only grows)
@@ -303,6 +331,17 @@ class Engine:
         frame = self._frame(h, bump, attempts, "render_to_yuv")
         return (None if own is None else self._download_yuv(params.width, params.height, layout, own),) + frame
 
+    def blur(self, image_id, width, height, sigma, dst_image_id=None, edge=BlurEdge.ZERO, rect=None):
+        """jh_blur: the Gaussian blur (the rule: DESIGN.md 5.7) of the RGBA16F image `image_id` into `dst_image_id` -- None: in
+        place.  `sigma` is a scalar or (sigma_x, sigma_y), each in [0, 64]; `rect` = (x, y, width, height) is the rectangle of the
+        destination that is written (None: the whole image); texels outside it keep their bits, source texels outside it take
+        part.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _blur_desc(sigma, edge, rect)
+        rc = self._L.jl_engine_blur(self._h, image_id, image_id if dst_image_id is None else dst_image_id, width, height, ctypes.byref(d))
+        if rc == -1:  # JH_ERR_INVALID
+            raise ValueError(self._L.jl_last_error().decode())
+        self._check(rc, "blur")
+
     def pack_tiles(self, src_ptr, pitch, width, height, texel_bytes, ref_ptr=None, ref_pitch=None, out_device_ptr=None,
                    out_capacity=None):
         """jh_pack_tiles: the frame at the device pointer `src_ptr` (rows `pitch` bytes apart, texels of 4 or 8 bytes) as a
@@ -403,7 +442,7 @@ class Engine:
             out.append(p)
         return out
 
-    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None):
+    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -411,11 +450,16 @@ class Engine:
         device pointer `src` -- the surface, or the RGBA16F target -- against `ref` (or None) into `dst` (two more launches);
         a frame of this size must have been packed once eagerly.
         yuv=(planes, YuvLayout, YuvMatrix, YuvRange, YuvTransfer), planes as for blit_yuv, appends the conversion of the
-        frame's target into those planes (one more kernel launch)."""
+        frame's target into those planes (one more kernel launch).
+        blur=dict(sigma=..., edge=..., rect=...) (edge and rect optional, as for blur()) blurs the frame's target in place after
+        the render and before the surface, YUV or pack conversion of the same capture (two more launches); a rectangle of this
+        size must have been blurred once eagerly."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
             t = recording.target
+            if blur is not None:
+                self.blur(t["id"], t["width"], t["height"], blur["sigma"], edge=blur.get("edge", BlurEdge.ZERO), rect=blur.get("rect"))
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._check(self._L.jl_engine_blit(self._h, t["id"], ptr, pitch, t["width"], t["height"], int(fmt)), "blit")

@@ -6,6 +6,7 @@
 #include <memory>
 #include <string>
 
+#include "../../include/jello_blur.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -446,6 +447,21 @@ void* jl_engine_render_to_yuv(void* e, void* scene, const jl_render_params* para
 int jl_engine_blit_yuv(void* e, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc) {
     if (!desc) { g_err = "blit_yuv: null descriptor"; return -1; }
     GUARD(((Engine*)e)->blit_yuv(src_image_id, width, height, *desc), -1);
+    return 0;
+}
+
+// Gaussian blur (jh_blur; the rule is in jello_hip.h and DESIGN.md 5.7).  jl_blur_taps is the host twin of jh_blur_taps: the same
+// header, compiled here by the host compiler -- the 2R + 1 taps of sigma into weights (or null) and R into *radius; -1 for a
+// sigma that is negative, above 64 or NaN.
+int jl_engine_blur(void* e, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc) {
+    if (!desc) { g_err = "blur: null descriptor"; return -1; }
+    GUARD_CODE(((Engine*)e)->blur(src_image_id, dst_image_id, width, height, *desc));
+    return 0;
+}
+int jl_blur_taps(float sigma, float* weights, uint32_t* radius) {
+    if (!jblur_sigma_ok(sigma)) { g_err = "blur_taps: sigma is negative, above 64 or NaN"; return -1; }
+    const uint32_t R = jblur_taps(sigma, weights);
+    if (radius) *radius = R;
     return 0;
 }
 

@@ -214,6 +214,10 @@ void Engine::blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32
     check(jh_blit(ctx_, src_image_id, surface, pitch, width, height, format), "blit");
 }
 
+void Engine::blur(ResourceID src_image_id, ResourceID dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc& desc) {
+    check(jh_blur(ctx_, src_image_id, dst_image_id, width, height, &desc), "blur");
+}
+
 void Engine::pack_tiles(const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
                         uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
     check(jh_pack_tiles(ctx_, src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, dst_capacity), "pack_tiles");
