@@ -22,6 +22,7 @@
  *   jh_pack_tiles / jh_unpack_tiles   (no counterpart: the frame's way off the GPU)
  *   jh_dash                           (no counterpart: the reference dashes on the CPU with curve.Dash)
  *   jh_blur                           (no counterpart: Gaussian blur of the RGBA16F target on the device)
+ *   jh_composite                      (no counterpart: one RGBA16F image blended onto another on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -408,6 +409,50 @@ typedef struct jh_blur_desc {
 } jh_blur_desc;
 int jh_blur_taps(float sigma, float* weights /* 2R+1 entries, or NULL */, uint32_t* radius);
 int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc);
+
+/* ---- Composite: one RGBA16F image blended onto another (DESIGN.md 5.8 "Composite rule") ----
+ * What a blurred layer needs to become a drop shadow, a glow or an overlay without leaving the device: a rectangle of the image
+ * src_image_id is blended onto dst_image_id with any of the 16 mix modes x 14 Porter-Duff operators, an opacity and an optional
+ * tint.  The images are stored un-premultiplied (as fine stores them), and may differ in size.  The result is defined on values
+ * (include/jello_composite.h states the geometry, jello_amd/csrc/blend_rule.h the blend, tests/composite_ref.py restates all of
+ * it); per texel of the written rectangle, all in binary32, every operation rounded once, nothing contracted:
+ *   source      (c_s, a_s) = the f16 texel widened.  With JH_COMPOSITE_TINT: c_s = tint.rgb (binary32 as given) and
+ *               a_s = a_s * tint.a.  Then a_s = a_s * opacity, and p_s = c_s * a_s.  (No tint and opacity 1: every step is exact.)
+ *   backdrop    (c_b, a_b) = the dst texel widened, p_b = c_b * a_b (exact).  A dst that was never written reads as transparent black.
+ *   blend       R = blend_mix_compose((p_b, a_b), (p_s, a_s), mix << 8 | compose): the function the fine stage applies at END_CLIP
+ *               (shared/blend.wgsl), operation for operation, with its fast arm for Normal + SrcOver (R = p_b * (1 - a_s) + p_s, also
+ *               for alpha) and EPSILON = 1e-15f.  Its min / max are IEEE minNum / maxNum (a NaN operand yields the other one) with
+ *               -0 below +0.
+ *   store       as fine does: a_inv = 1.0f / max(R.a, 1e-6f); dst = (f16(R.r * a_inv + 0.0f), f16(R.g * a_inv + 0.0f),
+ *               f16(R.b * a_inv + 0.0f), f16(R.a + 0.0f)), round to nearest even.  The + 0.0f turns a binary32 -0 into +0.
+ *               A NaN result is any NaN; f16 subnormals are values, nothing is flushed.
+ * Consequences: opacity 0, or a transparent source, under Normal + SrcOver gives back every dst texel with a_b >= 1e-6 bit for bit
+ * (a -0 as +0); the colour of a dst texel with a_b = 0 becomes 0; Compose.Clear (compose = 3) clears the
+ * rectangle.  Outside the placed rectangle nothing is ever written, also by operators that would erase the backdrop where the
+ * source is absent (SrcIn, Copy, ...): the layer is its rectangle.
+ *
+ * Geometry: the source rectangle (sx, sy, sw, sh) must lie inside the source image; sw == sh == 0 means the whole image (sx, sy
+ * ignored).  Its top-left lands at the signed (dx, dy) of dst and it is clipped to dst; a placement that clips to nothing is
+ * JH_OK and launches nothing.
+ * Stream-ordered on the context's stream, never waits: one kernel launch (plus a fill when a never-written dst has to be cleared:
+ * it is cleared first when the placed rectangle is not the whole image, and counts as written afterwards).  No scratch, a fixed
+ * grid: the call may always be captured between jh_graph_begin and jh_graph_end.  With profiling on it is a query "composite" with
+ * stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band): a shifted source row belongs to another rank.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_composite: ":
+ * a null desc; an unknown source or destination id; an image that is not RGBA16F; src == dst (a shifted blend in place reads what
+ * it writes); mix > 15 (so Mix.Clip); compose > 13; an opacity or a tint alpha outside [0, 1] or NaN; a tint colour that is not
+ * finite; unknown flag bits; a source rectangle that is not inside the source image or that is empty in exactly one dimension; a
+ * band set with jh_set_band.  (The tint is read only with the flag.) */
+#define JH_COMPOSITE_TINT 1u
+typedef struct jh_composite_desc {
+    uint32_t mix, compose;          /* Mix 0..15, Compose 0..13 (the encodings of gfx.h / scene.py) */
+    float opacity;                  /* [0, 1] */
+    uint32_t flags;                 /* bit 0: JH_COMPOSITE_TINT */
+    float tint[4];                  /* r, g, b finite; a in [0, 1]; read only with the flag */
+    uint32_t sx, sy, sw, sh;        /* source rectangle; sw == sh == 0: the whole source */
+    int32_t dx, dy;                 /* where its top-left lands in dst */
+} jh_composite_desc;
+int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_composite_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

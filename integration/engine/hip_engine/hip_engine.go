@@ -487,6 +487,35 @@ func (e *Engine) Blur(src, dst renderer.ImageProxy, desc BlurDesc) {
 	e.check(C.jh_blur(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), C.uint32_t(src.Width), C.uint32_t(src.Height), &d), "blur")
 }
 
+// CompositeTint is JH_COMPOSITE_TINT: the source's colour is replaced by CompositeDesc.Tint's and its alpha scaled by Tint[3].
+const CompositeTint uint32 = 1
+
+// CompositeDesc is jh_composite_desc (include/jello_hip.h "Composite"): the mix mode (0..15, not Clip) and the Porter-Duff operator
+// (0..13) in the encodings of gfx, an opacity in [0, 1], the flags, the tint (read only with CompositeTint), the rectangle of the
+// source that is placed (SW == SH == 0: the whole source) and where its top-left lands in dst (clipped to dst).
+type CompositeDesc struct {
+	Mix, Compose   uint32
+	Opacity        float32
+	Flags          uint32
+	Tint           [4]float32
+	SX, SY, SW, SH uint32
+	DX, DY         int32
+}
+
+// Composite is jh_composite: the RGBA16F image src blended onto the RGBA16F image dst (another image; the sizes may differ) by the
+// rule of DESIGN.md 5.8 (defined on values: every implementation gives the same bits) -- the blend the fine stage applies to a
+// layer, image to image.  Only the placed rectangle is written.  Stream-ordered behind the frame, waits for nothing, one kernel
+// launch; with Blur it makes a drop shadow: blur the layer into a scratch image, Composite that with a tint and an offset, Composite
+// the layer.
+func (e *Engine) Composite(src, dst renderer.ImageProxy, desc CompositeDesc) {
+	d := C.jh_composite_desc{mix: C.uint32_t(desc.Mix), compose: C.uint32_t(desc.Compose), opacity: C.float(desc.Opacity), flags: C.uint32_t(desc.Flags),
+		sx: C.uint32_t(desc.SX), sy: C.uint32_t(desc.SY), sw: C.uint32_t(desc.SW), sh: C.uint32_t(desc.SH), dx: C.int32_t(desc.DX), dy: C.int32_t(desc.DY)}
+	for i, v := range desc.Tint {
+		d.tint[i] = C.float(v)
+	}
+	e.check(C.jh_composite(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "composite")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

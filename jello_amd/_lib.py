@@ -139,6 +139,13 @@ class CBlurDesc(ctypes.Structure):
                 ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
 
 
+class CCompositeDesc(ctypes.Structure):
+    """jh_composite_desc (include/jello_hip.h)."""
+    _fields_ = [("mix", ctypes.c_uint32), ("compose", ctypes.c_uint32), ("opacity", ctypes.c_float), ("flags", ctypes.c_uint32),
+                ("tint", ctypes.c_float * 4), ("sx", ctypes.c_uint32), ("sy", ctypes.c_uint32), ("sw", ctypes.c_uint32),
+                ("sh", ctypes.c_uint32), ("dx", ctypes.c_int32), ("dy", ctypes.c_int32)]
+
+
 def _declare(L):
     vp, ci, cu = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
     dp = ctypes.POINTER(ctypes.c_double)
@@ -201,6 +208,8 @@ def _declare(L):
     L.jl_engine_dash_paths.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
     L.jl_engine_blur.argtypes = [vp, u64, u64, u32, u32, ctypes.POINTER(CBlurDesc)]
     L.jl_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
+    L.jl_engine_composite.argtypes = [vp, u64, u64, ctypes.POINTER(CCompositeDesc)]
+    L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
     L.hip = hip
@@ -238,6 +247,7 @@ def _declare(L):
     hip.jh_dash.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
     hip.jh_blur.argtypes = [vp, u64, u64, u32, u32, ctypes.POINTER(CBlurDesc)]
     hip.jh_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
+    hip.jh_composite.argtypes = [vp, u64, u64, ctypes.POINTER(CCompositeDesc)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -19,6 +20,7 @@
 
 #include "kcommon.h"
 #include "../../include/jello_blur.h"
+#include "../../include/jello_composite.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -1133,7 +1135,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1403,6 +1405,45 @@ int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t 
             return launch_status(ctx, "jh_blur", jh_blur_launch(ctx->stream, from, dst->ptr, width, height, x, y, rw, rh, desc->edge == JH_BLUR_EDGE_CLAMP,
                                                                 taps_x, radius_x, taps_y, radius_y, tmp, ctx->num_cus));
         });
+}
+
+// composite (include/jello_hip.h "Composite"; the geometry: include/jello_composite.h; kernels_composite.hip)
+int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_composite_desc* desc) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_composite: null descriptor");
+    const Alloc* src = find_alloc(ctx->images, src_image_id);
+    if (!src) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown source image id");
+    Alloc* dst = find_alloc(ctx->images, dst_image_id);
+    if (!dst) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown destination image id");
+    if (src->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_composite: the source is not an RGBA16F image");
+    if (dst->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_composite: the destination is not an RGBA16F image");
+    if (src == dst) return fail(ctx, JH_ERR_INVALID, "jh_composite: the source is the destination (a shifted blend in place reads what it writes)");
+    if (desc->mix > 15u) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown mix mode (Mix.Clip is not a blend of two images)");
+    if (desc->compose > 13u) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown compose operator");
+    if (!(desc->opacity >= 0.0f && desc->opacity <= 1.0f)) return fail(ctx, JH_ERR_INVALID, "jh_composite: opacity is outside [0, 1] or NaN");
+    if ((desc->flags & ~(uint32_t)JH_COMPOSITE_TINT) != 0u) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown flag bits");
+    if (desc->flags & JH_COMPOSITE_TINT) {
+        if (!std::isfinite(desc->tint[0]) || !std::isfinite(desc->tint[1]) || !std::isfinite(desc->tint[2]))
+            return fail(ctx, JH_ERR_INVALID, "jh_composite: the tint colour is not finite");
+        if (!(desc->tint[3] >= 0.0f && desc->tint[3] <= 1.0f)) return fail(ctx, JH_ERR_INVALID, "jh_composite: the tint alpha is outside [0, 1] or NaN");
+    }
+    jcomp_rect rect;
+    if (jcomp_clip(src->width, src->height, desc->sx, desc->sy, desc->sw, desc->sh, desc->dx, desc->dy, dst->width, dst->height, &rect))
+        return fail(ctx, JH_ERR_INVALID, "jh_composite: the source rectangle is not inside the source image or is empty in one dimension");
+    if (ctx->band_row0 != 0u || ctx->band_row1 != 0xffffffffu)
+        return fail(ctx, JH_ERR_INVALID, "jh_composite: not in band mode (a shifted source row belongs to another rank)");
+    if (rect.w == 0u || rect.h == 0u) return JH_OK;  // placed outside dst: nothing to write, nothing launched
+    return post_render_call(ctx, "composite", [&] {
+        const bool backdrop = dst->written || dst->stored;
+        if (!backdrop) {  // outside the rectangle it goes on reading as transparent black
+            if (rect.w != dst->width || rect.h != dst->height) HIP_TRY(ctx, hipMemsetAsync(dst->ptr, 0, dst->size, ctx->stream));
+            ctx->generation++;  // (fine binds a never-written image as absent: the choice is baked into a graph)
+        }
+        dst->written = true;
+        return launch_status(ctx, "jh_composite",
+                             jh_composite_launch(ctx->stream, content_or_null(*src), src->width, src->height, dst->ptr, dst->width, dst->height, backdrop,
+                                                 &rect, desc->mix << 8 | desc->compose, desc->flags, desc->opacity, desc->tint, ctx->num_cus));
+    });
 }
 
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.

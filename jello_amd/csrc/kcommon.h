@@ -359,7 +359,7 @@ struct JhDashJob {
 };
 JhResult jh_dash_launch(const JhLaunch& L, const JhDashJob& job, void* out, uint64_t capacity, uint32_t* index);
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses, another negative value for a failed launch.
 extern "C" {
@@ -374,6 +374,9 @@ int jh_unpack_launch(hipStream_t stream, const void* pack, uint64_t pack_bytes, 
                      uint32_t texel_bytes, uint32_t* rejects);
 int jh_blur_launch(hipStream_t stream, const void* src, void* dst, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t rect_w,
                    uint32_t rect_h, int clamp, const float* taps_x, uint32_t radius_x, const float* taps_y, uint32_t radius_y, void* tmp, int num_cus);
+struct jcomp_rect;  // include/jello_composite.h
+int jh_composite_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h,
+                        int dst_has_content, const jcomp_rect* rect, uint32_t mode, uint32_t flags, float opacity, const float* tint, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

@@ -30,6 +30,7 @@
 
 #include "kcommon.h"
 #include <algorithm>
+#include "blend_rule.h"
 #include "srgb_lut.h"
 
 using namespace jk;
@@ -37,134 +38,16 @@ using namespace jd;
 
 namespace {
 
-struct V4 {
-    float x, y, z, w;
-};
-struct V3 {
-    float x, y, z;
-};
-JD V4 v4(float x, float y, float z, float w) { V4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
-JD V3 v3(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
-
-// ---- shared/blend.wgsl ----
-JD V3 screen(V3 cb, V3 cs) { return v3(cb.x + cs.x - (cb.x * cs.x), cb.y + cs.y - (cb.y * cs.y), cb.z + cs.z - (cb.z * cs.z)); }
-JD float color_dodge(float cb, float cs) {
-    if (cb == 0.0f) return 0.0f; else if (cs == 1.0f) return 1.0f; else return fmin_(1.0f, cb / (1.0f - cs));
-}
-JD float color_burn(float cb, float cs) {
-    if (cb == 1.0f) return 1.0f; else if (cs == 0.0f) return 0.0f; else return 1.0f - fmin_(1.0f, (1.0f - cb) / cs);
-}
-JD float hard_light1(float cb, float cs) {
-    float scr_cs = 2.0f * cs - 1.0f;
-    float a = cb + scr_cs - (cb * scr_cs);
-    float b = cb * 2.0f * cs;
-    return (cs <= 0.5f) ? b : a;
-}
-JD V3 hard_light(V3 cb, V3 cs) { return v3(hard_light1(cb.x, cs.x), hard_light1(cb.y, cs.y), hard_light1(cb.z, cs.z)); }
-JD float soft_light1(float cb, float cs) {
-    float d = (cb <= 0.25f) ? (((16.0f * cb - 12.0f) * cb + 4.0f) * cb) : sqrt_(cb);
-    float t = cb + (2.0f * cs - 1.0f) * (d - cb);
-    float f = cb - (1.0f - 2.0f * cs) * cb * (1.0f - cb);
-    return (cs <= 0.5f) ? f : t;
-}
-JD V3 soft_light(V3 cb, V3 cs) { return v3(soft_light1(cb.x, cs.x), soft_light1(cb.y, cs.y), soft_light1(cb.z, cs.z)); }
-JD float sat(V3 c) { return fmax_(c.x, fmax_(c.y, c.z)) - fmin_(c.x, fmin_(c.y, c.z)); }
-JD float lum(V3 c) { return c.x * 0.3f + c.y * 0.59f + c.z * 0.11f; }
-JD V3 clip_color(V3 c) {
-    float l = lum(c);
-    float n = fmin_(c.x, fmin_(c.y, c.z));
-    float x = fmax_(c.x, fmax_(c.y, c.z));
-    if (n < 0.0f) c = v3(l + (((c.x - l) * l) / (l - n)), l + (((c.y - l) * l) / (l - n)), l + (((c.z - l) * l) / (l - n)));
-    if (x > 1.0f) c = v3(l + (((c.x - l) * (1.0f - l)) / (x - l)), l + (((c.y - l) * (1.0f - l)) / (x - l)), l + (((c.z - l) * (1.0f - l)) / (x - l)));
-    return c;
-}
-JD V3 set_lum(V3 c, float l) { float d = l - lum(c); return clip_color(v3(c.x + d, c.y + d, c.z + d)); }
-JD void set_sat_inner(float& cmin, float& cmid, float& cmax, float s) {
-    if (cmax > cmin) { cmid = ((cmid - cmin) * s) / (cmax - cmin); cmax = s; }
-    else { cmid = 0.0f; cmax = 0.0f; }
-    cmin = 0.0f;
-}
-JD V3 set_sat(V3 c, float s) {
-    float r = c.x, g = c.y, b = c.z;
-    if (r <= g) {
-        if (g <= b) set_sat_inner(r, g, b, s);
-        else { if (r <= b) set_sat_inner(r, b, g, s); else set_sat_inner(b, r, g, s); }
-    } else {
-        if (r <= b) set_sat_inner(g, r, b, s);
-        else { if (g <= b) set_sat_inner(g, b, r, s); else set_sat_inner(b, g, r, s); }
-    }
-    return v3(r, g, b);
-}
-JD V3 blend_mix(V3 cb, V3 cs, uint32_t mode) {  // blend.wgsl:142-195
-    switch (mode) {
-        case 1: return v3(cb.x * cs.x, cb.y * cs.y, cb.z * cs.z);
-        case 2: return screen(cb, cs);
-        case 3: return hard_light(cs, cb);
-        case 4: return v3(fmin_(cb.x, cs.x), fmin_(cb.y, cs.y), fmin_(cb.z, cs.z));
-        case 5: return v3(fmax_(cb.x, cs.x), fmax_(cb.y, cs.y), fmax_(cb.z, cs.z));
-        case 6: return v3(color_dodge(cb.x, cs.x), color_dodge(cb.y, cs.y), color_dodge(cb.z, cs.z));
-        case 7: return v3(color_burn(cb.x, cs.x), color_burn(cb.y, cs.y), color_burn(cb.z, cs.z));
-        case 8: return hard_light(cb, cs);
-        case 9: return soft_light(cb, cs);
-        case 10: return v3(abs_(cb.x - cs.x), abs_(cb.y - cs.y), abs_(cb.z - cs.z));
-        case 11: return v3(cb.x + cs.x - 2.0f * cb.x * cs.x, cb.y + cs.y - 2.0f * cb.y * cs.y, cb.z + cs.z - 2.0f * cb.z * cs.z);
-        case 12: return set_lum(set_sat(cs, sat(cb)), lum(cb));
-        case 13: return set_lum(set_sat(cb, sat(cs)), lum(cb));
-        case 14: return set_lum(cs, lum(cb));
-        case 15: return set_lum(cb, lum(cs));
-        default: return cs;
-    }
-}
-JD V4 blend_compose(V3 cb, V3 cs, float ab, float as_, uint32_t mode) {  // blend.wgsl:216-284
-    float fa = 0.0f, fb = 0.0f;
-    switch (mode) {
-        case 1: fa = 1.0f; fb = 0.0f; break;
-        case 2: fa = 0.0f; fb = 1.0f; break;
-        case 0: fa = 1.0f; fb = 1.0f - as_; break;
-        case 4: fa = 1.0f - ab; fb = 1.0f; break;
-        case 5: fa = ab; fb = 0.0f; break;
-        case 6: fa = 0.0f; fb = as_; break;
-        case 7: fa = 1.0f - ab; fb = 0.0f; break;
-        case 8: fa = 0.0f; fb = 1.0f - as_; break;
-        case 9: fa = ab; fb = 1.0f - as_; break;
-        case 10: fa = 1.0f - ab; fb = as_; break;
-        case 11: fa = 1.0f - ab; fb = 1.0f - as_; break;
-        case 12: fa = 1.0f; fb = 1.0f; break;
-        case 13:
-            return v4(fmin_(1.0f, as_ * cs.x + ab * cb.x), fmin_(1.0f, as_ * cs.y + ab * cb.y), fmin_(1.0f, as_ * cs.z + ab * cb.z),
-                      fmin_(1.0f, as_ + ab));
-        default: break;
-    }
-    float as_fa = as_ * fa;
-    float ab_fb = ab * fb;
-    return v4(as_fa * cs.x + ab_fb * cb.x, as_fa * cs.y + ab_fb * cb.y, as_fa * cs.z + ab_fb * cb.z, fmin_(as_fa + ab_fb, 1.0f));
-}
 // Not inlined: with the sixteen mix modes and fourteen compose operators expanded for each of a lane's four pixels the
 // clip + paint instantiation was 68 KB of code -- more than the 64 KB instruction cache -- and with lazy layers the full
 // formula is the rare case.
 __device__ __attribute__((noinline)) V4 blend_mix_compose(V4 backdrop, V4 src, uint32_t mode) {  // blend.wgsl:288-310
-    const float EPSILON = 1e-15f;
     // `mode` is a PTCL word: the same in every lane.  As a function argument it arrives in a vector register, and the two switches
-    // below became trees of v_cmp / s_and_saveexec / s_cbranch_execz -- ~25 vector + scalar instructions per call in front of the
+    // of blend_rule became trees of v_cmp / s_and_saveexec / s_cbranch_execz -- ~25 vector + scalar instructions per call in front of the
     // arithmetic (round 6: nested C4 spends 55 % of its fine kernel in here, 85 calls x 4 pixels per tile).  As a scalar the switches
     // are compare-and-branch on the scalar pipe.
     mode = (uint32_t)__builtin_amdgcn_readfirstlane((int)mode);
-    if ((mode & 0x7fffu) == 0u) {
-        float k = 1.0f - src.w;
-        return v4(backdrop.x * k + src.x, backdrop.y * k + src.y, backdrop.z * k + src.z, backdrop.w * k + src.w);
-    }
-    float inv_src_a = 1.0f / fmax_(src.w, EPSILON);
-    V3 cs = v3(src.x * inv_src_a, src.y * inv_src_a, src.z * inv_src_a);
-    float inv_backdrop_a = 1.0f / fmax_(backdrop.w, EPSILON);
-    V3 cb = v3(backdrop.x * inv_backdrop_a, backdrop.y * inv_backdrop_a, backdrop.z * inv_backdrop_a);
-    uint32_t mix_mode = mode >> 8;
-    V3 mixed = blend_mix(cb, cs, mix_mode);
-    cs = v3(mix_(cs.x, mixed.x, backdrop.w), mix_(cs.y, mixed.y, backdrop.w), mix_(cs.z, mixed.z, backdrop.w));
-    uint32_t compose_mode = mode & 0xffu;
-    if (compose_mode == 0u) {
-        return v4(mix_(backdrop.x, cs.x, src.w), mix_(backdrop.y, cs.y, src.w), mix_(backdrop.z, cs.z, src.w), src.w + backdrop.w * (1.0f - src.w));
-    }
-    return blend_compose(cb, cs, backdrop.w, src.w, compose_mode);
+    return blend_rule(backdrop, src, mode);
 }
 
 JD float extend_mode(float t, uint32_t mode) {  // fine.wgsl:800-812

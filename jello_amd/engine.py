@@ -9,7 +9,8 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CConfig, CYuvDesc
+from ._lib import CBlurDesc, CCompositeDesc, CConfig, CYuvDesc
+from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
                "flatten", "draw_reduce", "draw_leaf", "clip_reduce", "clip_leaf", "binning", "tile_alloc", "backdrop_dyn",
@@ -74,6 +75,32 @@ def _blur_desc(sigma, edge, rect):
     sx, sy = sigma if isinstance(sigma, (tuple, list)) else (sigma, sigma)
     x, y, w, h = (0, 0, 0, 0) if rect is None else rect
     return CBlurDesc(float(sx), float(sy), int(edge), int(x), int(y), int(w), int(h))
+
+
+COMPOSITE_TINT = 1  # JH_COMPOSITE_TINT
+
+
+def _composite_desc(mix, compose, opacity, tint, src_rect, offset):
+    sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
+    d = CCompositeDesc(int(mix), int(compose), float(opacity), 0 if tint is None else COMPOSITE_TINT)
+    if tint is not None:
+        d.tint[:] = [float(v) for v in tint]
+    d.sx, d.sy, d.sw, d.sh = int(sx), int(sy), int(sw), int(sh)
+    d.dx, d.dy = int(offset[0]), int(offset[1])
+    return d
+
+
+def composite_clip(src_size, dst_size, src_rect=None, offset=(0, 0)):
+    """jl_composite_clip: where the rectangle `src_rect` = (sx, sy, sw, sh) (None: the whole image) of a source of `src_size` =
+    (width, height) lands when its top-left is placed at the signed `offset` of a destination of `dst_size` and clipped to it
+    (the geometry of DESIGN.md 5.8): (sx', sy', dx', dy', w, h), all zero when nothing is left.  No GPU needed.  ValueError for a
+    source rectangle the rule refuses."""
+    L = _lib.load_host()
+    sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
+    out = (ctypes.c_uint32 * 6)()
+    if L.jl_composite_clip(src_size[0], src_size[1], sx, sy, sw, sh, offset[0], offset[1], dst_size[0], dst_size[1], out) != 0:
+        raise ValueError(L.jl_last_error().decode())
+    return tuple(out)
 
 
 # a context buffer that blit / render_to_surface convert into when the caller passes no device pointer (it only grows)
@@ -342,6 +369,27 @@ class Engine:
             raise ValueError(self._L.jl_last_error().decode())
         self._check(rc, "blur")
 
+    def composite(self, src_id, dst_id, mix=Mix.Normal, compose=Compose.SrcOver, opacity=1.0, tint=None, src_rect=None, offset=(0, 0)):
+        """jh_composite: the RGBA16F image `src_id` blended onto the RGBA16F image `dst_id` (another image; the sizes may differ)
+        by the rule of DESIGN.md 5.8 -- any Mix but Clip, any Compose, `opacity` in [0, 1]; `tint` = (r, g, b, a) replaces the
+        source's colour and scales its alpha (a shadow out of a blurred layer); `src_rect` = (sx, sy, sw, sh) is the part of the
+        source that is placed (None: all of it), `offset` = (dx, dy) where its top-left lands in dst, negative or beyond dst
+        included: it is clipped, and only the placed rectangle is written.  Stream-ordered, returns nothing; ValueError for a
+        call the rule refuses."""
+        d = _composite_desc(mix, compose, opacity, tint, src_rect, offset)
+        rc = self._L.jl_engine_composite(self._h, src_id, dst_id, ctypes.byref(d))
+        if rc == -1:  # JH_ERR_INVALID
+            raise ValueError(self._L.jl_last_error().decode())
+        self._check(rc, "composite")
+
+    def drop_shadow(self, layer_id, target_id, width, height, sigma, offset, color, scratch_image_id):
+        """A layer with its drop shadow onto a target, three calls: blur(layer -> scratch, edge ZERO); composite(scratch -> target,
+        tint=color, offset): the blurred alpha in the shadow's colour, shifted; composite(layer -> target).  `layer_id` and
+        `scratch_image_id` are RGBA16F images of width x height (the scratch's content is overwritten), `color` = (r, g, b, a)."""
+        self.blur(layer_id, width, height, sigma, dst_image_id=scratch_image_id, edge=BlurEdge.ZERO)
+        self.composite(scratch_image_id, target_id, tint=color, offset=offset)
+        self.composite(layer_id, target_id)
+
     def pack_tiles(self, src_ptr, pitch, width, height, texel_bytes, ref_ptr=None, ref_pitch=None, out_device_ptr=None,
                    out_capacity=None):
         """jh_pack_tiles: the frame at the device pointer `src_ptr` (rows `pitch` bytes apart, texels of 4 or 8 bytes) as a
@@ -442,7 +490,7 @@ class Engine:
             out.append(p)
         return out
 
-    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None):
+    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -453,13 +501,17 @@ class Engine:
         frame's target into those planes (one more kernel launch).
         blur=dict(sigma=..., edge=..., rect=...) (edge and rect optional, as for blur()) blurs the frame's target in place after
         the render and before the surface, YUV or pack conversion of the same capture (two more launches); a rectangle of this
-        size must have been blurred once eagerly."""
+        size must have been blurred once eagerly.
+        composite=dict(src=image id, ...) (the other keywords of composite(), optional) blends that image onto the frame's target
+        after the blur and before the surface, YUV or pack conversion of the same capture (one more launch)."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
             t = recording.target
             if blur is not None:
                 self.blur(t["id"], t["width"], t["height"], blur["sigma"], edge=blur.get("edge", BlurEdge.ZERO), rect=blur.get("rect"))
+            if composite is not None:
+                self.composite(composite["src"], t["id"], **{k: v for k, v in composite.items() if k != "src"})
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._check(self._L.jl_engine_blit(self._h, t["id"], ptr, pitch, t["width"], t["height"], int(fmt)), "blit")

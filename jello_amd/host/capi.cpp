@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/jello_blur.h"
+#include "../../include/jello_composite.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -462,6 +463,23 @@ int jl_blur_taps(float sigma, float* weights, uint32_t* radius) {
     if (!jblur_sigma_ok(sigma)) { g_err = "blur_taps: sigma is negative, above 64 or NaN"; return -1; }
     const uint32_t R = jblur_taps(sigma, weights);
     if (radius) *radius = R;
+    return 0;
+}
+
+// Composite (jh_composite; the rule is in jello_hip.h and DESIGN.md 5.8).  jl_composite_clip is the geometry of the call without a
+// GPU: the same header the library compiles, compiled here by the host compiler -- the source rectangle (sx, sy, sw, sh) of a
+// src_w x src_h image placed at (dx, dy) of a dst_w x dst_h one, clipped, into out[6] = {sx', sy', dx', dy', w, h} (all zero when
+// nothing is left); -1 for a source rectangle the rule refuses.
+int jl_engine_composite(void* e, uint64_t src_image_id, uint64_t dst_image_id, const jh_composite_desc* desc) {
+    if (!desc) { g_err = "composite: null descriptor"; return -1; }
+    GUARD_CODE(((Engine*)e)->composite(src_image_id, dst_image_id, *desc));
+    return 0;
+}
+int jl_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w,
+                      uint32_t dst_h, uint32_t* out) {
+    jcomp_rect r;
+    if (!out || jcomp_clip(src_w, src_h, sx, sy, sw, sh, dx, dy, dst_w, dst_h, &r)) { g_err = "composite_clip: the source rectangle is not inside the source image or is empty in one dimension"; return -1; }
+    out[0] = r.sx; out[1] = r.sy; out[2] = r.dx; out[3] = r.dy; out[4] = r.w; out[5] = r.h;
     return 0;
 }
 

@@ -218,6 +218,10 @@ void Engine::blur(ResourceID src_image_id, ResourceID dst_image_id, uint32_t wid
     check(jh_blur(ctx_, src_image_id, dst_image_id, width, height, &desc), "blur");
 }
 
+void Engine::composite(ResourceID src_image_id, ResourceID dst_image_id, const jh_composite_desc& desc) {
+    check(jh_composite(ctx_, src_image_id, dst_image_id, &desc), "composite");
+}
+
 void Engine::pack_tiles(const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
                         uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
     check(jh_pack_tiles(ctx_, src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, dst_capacity), "pack_tiles");

@@ -80,6 +80,10 @@ class Engine {
     // "Gaussian blur"; dst may be src).  Stream-ordered, waits for nothing.
     void blur(ResourceID src_image_id, ResourceID dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc& desc);
 
+    // The rectangle of the RGBA16F image src_image_id that `desc` names blended onto dst_image_id (jh_composite, include/jello_hip.h
+    // "Composite"; the two must differ).  Stream-ordered, waits for nothing.
+    void composite(ResourceID src_image_id, ResourceID dst_image_id, const jh_composite_desc& desc);
+
     // Tile-packed frame transport (jh_pack_tiles / jh_unpack_tiles, the format is in jello_hip.h): all pointers are device
     // memory, both calls are stream-ordered and wait for nothing.
     void pack_tiles(const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
