@@ -146,6 +146,18 @@ class CCompositeDesc(ctypes.Structure):
                 ("sh", ctypes.c_uint32), ("dx", ctypes.c_int32), ("dy", ctypes.c_int32)]
 
 
+class CProfileRecord(ctypes.Structure):
+    """jh_profile_record (include/jello_hip.h)."""
+    _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
+
+
+class CProfileNode(ctypes.Structure):
+    """jh_profile_node (include/jello_hip.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("parent", ctypes.c_int32), ("stage", ctypes.c_int32), ("pad", ctypes.c_uint32),
+                ("label", ctypes.c_char * 48), ("cpu_start_ms", ctypes.c_double), ("cpu_end_ms", ctypes.c_double),
+                ("gpu_start_ms", ctypes.c_float), ("gpu_end_ms", ctypes.c_float)]
+
+
 def _declare(L):
     vp, ci, cu = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint
     dp = ctypes.POINTER(ctypes.c_double)
@@ -196,19 +208,12 @@ def _declare(L):
     L.jl_engine_render_to_surface.restype = vp
     L.jl_engine_render_to_surface.argtypes = [vp, vp, ctypes.POINTER(CRenderParams), vp, ctypes.c_uint64, ci, ci,
                                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ci)]
-    L.jl_engine_blit.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ci]
     L.jl_engine_render_to_yuv.restype = vp
     L.jl_engine_render_to_yuv.argtypes = [vp, vp, ctypes.POINTER(CRenderParams), ctypes.POINTER(CYuvDesc), ci, ctypes.POINTER(ctypes.c_uint32),
                                           ctypes.POINTER(ci)]
-    L.jl_engine_blit_yuv.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(CYuvDesc)]
     u32, u64 = ctypes.c_uint32, ctypes.c_uint64
-    L.jl_engine_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
-    L.jl_engine_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
     L.jl_engine_read_pack.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
-    L.jl_engine_dash_paths.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
-    L.jl_engine_blur.argtypes = [vp, u64, u64, u32, u32, ctypes.POINTER(CBlurDesc)]
     L.jl_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
-    L.jl_engine_composite.argtypes = [vp, u64, u64, ctypes.POINTER(CCompositeDesc)]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -1188,17 +1189,38 @@ static int launch_status(jh_ctx* ctx, const char* who, int rc) {
     return fail(ctx, JH_ERR_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
 }
 
-// The source of a blit: a known image, RGBA16F, of the size the caller gives.
-static int rgba16f_source(jh_ctx* ctx, uint64_t id, uint32_t width, uint32_t height, const char* who, const Alloc** out) {
-    const Alloc* a = find_alloc(ctx->images, id);
-    if (!a) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": unknown source image id");
-    if (a->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": the source is not an RGBA16F image");
-    if (a->width != width || a->height != height) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": size differs from the source image");
-    *out = a;
+// The images a call names by id, each in its role ("source" or "destination"): all of them known, then each of them RGBA16F and
+// -- where the caller gives one -- of the size size[0] x size[1].
+struct ImageRole { uint64_t id; const char* role; Alloc** out; };
+static int rgba16f_images(jh_ctx* ctx, const char* who, std::initializer_list<ImageRole> images, const uint32_t* size = nullptr) {
+    const std::string w(who);
+    for (const ImageRole& i : images)
+        if (!(*i.out = find_alloc(ctx->images, i.id))) return fail(ctx, JH_ERR_INVALID, w + ": unknown " + i.role + " image id");
+    for (const ImageRole& i : images) {
+        const Alloc& a = **i.out;
+        if (a.format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, w + ": the " + i.role + " is not an RGBA16F image");
+        if (size && (a.width != size[0] || a.height != size[1])) return fail(ctx, JH_ERR_INVALID, w + ": size differs from the " + i.role + " image");
+    }
     return JH_OK;
 }
 // a source that was never written reads as transparent black, like a fresh texture: the kernels take a null pointer for it
 static const void* content_or_null(const Alloc& a) { return (a.written || a.stored) ? a.ptr : nullptr; }
+// A call is about to write the width x height rectangle of dst.  If that is dst's first content, the texels outside the rectangle
+// go on reading as transparent black.  (Not jh_image_write's condition: a frame's target is stored, never written, and a call
+// that writes it must not make captured graphs stale.)
+static int first_content(jh_ctx* ctx, Alloc* dst, uint32_t width, uint32_t height) {
+    if (!(dst->written || dst->stored)) {
+        if (width != dst->width || height != dst->height) HIP_TRY(ctx, hipMemsetAsync(dst->ptr, 0, dst->size, ctx->stream));
+        ctx->generation++;  // (fine binds a never-written image as absent: the choice is baked into a graph)
+    }
+    dst->written = true;
+    return JH_OK;
+}
+// A call whose texels depend on rows outside a band (`why` names them) is refused in band mode.
+static int refuse_band_mode(jh_ctx* ctx, const char* who, const char* why) {
+    if (ctx->band_row0 == 0u && ctx->band_row1 == 0xffffffffu) return JH_OK;
+    return fail(ctx, JH_ERR_INVALID, std::string(who) + ": not in band mode (" + why + ")");
+}
 // band mode: the pixel rows [*row0, *row1) of the active bin rows only (a bin row = 256 pixel rows: an even cut), so that bands of
 // several ranks compose; row1 = row0 when the band lies below the image
 static void band_pixel_rows(const jh_ctx* ctx, uint32_t height, uint32_t* row0, uint32_t* row1) {
@@ -1210,8 +1232,9 @@ static void band_pixel_rows(const jh_ctx* ctx, uint32_t height, uint32_t* row0, 
 int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t dst_pitch_bytes, uint32_t width, uint32_t height,
             int surface_format) {
     if (!ctx) return JH_ERR_INVALID;
-    const Alloc* a = nullptr;
-    if (int rc = rgba16f_source(ctx, src_image_id, width, height, "jh_blit", &a)) return rc;
+    const uint32_t size[2] = {width, height};
+    Alloc* a = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_blit", {{src_image_id, "source", &a}}, size)) return rc;
     if (!dst_device_ptr) return fail(ctx, JH_ERR_INVALID, "jh_blit: null destination");
     if (dst_pitch_bytes < 4ull * width) return fail(ctx, JH_ERR_INVALID, "jh_blit: pitch below 4 * width");
     if (surface_format < JH_SURFACE_RGBA8_UNORM || surface_format > JH_SURFACE_BGRA8_SRGB)
@@ -1228,8 +1251,9 @@ int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t d
 int jh_blit_yuv(jh_ctx* ctx, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc) {
     if (!ctx) return JH_ERR_INVALID;
     if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: null descriptor");
-    const Alloc* a = nullptr;
-    if (int rc = rgba16f_source(ctx, src_image_id, width, height, "jh_blit_yuv", &a)) return rc;
+    const uint32_t size[2] = {width, height};
+    Alloc* a = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_blit_yuv", {{src_image_id, "source", &a}}, size)) return rc;
     if (desc->layout != JH_YUV_NV12 && desc->layout != JH_YUV_I420) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown layout");
     if (desc->matrix != JH_YUV_BT601 && desc->matrix != JH_YUV_BT709) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown matrix");
     if (desc->range != JH_YUV_LIMITED && desc->range != JH_YUV_FULL) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown range");
@@ -1368,20 +1392,17 @@ int jh_blur_taps(float sigma, float* weights, uint32_t* radius) {
 int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc) {
     if (!ctx) return JH_ERR_INVALID;
     if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_blur: null descriptor");
-    const Alloc* src = nullptr;
-    if (int rc = rgba16f_source(ctx, src_image_id, width, height, "jh_blur", &src)) return rc;
-    Alloc* dst = find_alloc(ctx->images, dst_image_id);
-    if (!dst) return fail(ctx, JH_ERR_INVALID, "jh_blur: unknown destination image id");
-    if (dst->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_blur: the destination is not an RGBA16F image");
-    if (dst->width != width || dst->height != height) return fail(ctx, JH_ERR_INVALID, "jh_blur: size differs from the destination image");
+    const uint32_t size[2] = {width, height};
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_blur", {{src_image_id, "source", &src}}, size)) return rc;
+    if (int rc = rgba16f_images(ctx, "jh_blur", {{dst_image_id, "destination", &dst}}, size)) return rc;
     if (!jblur_sigma_ok(desc->sigma_x) || !jblur_sigma_ok(desc->sigma_y)) return fail(ctx, JH_ERR_INVALID, "jh_blur: sigma is negative, above 64 or NaN");
     if (desc->edge != JH_BLUR_EDGE_ZERO && desc->edge != JH_BLUR_EDGE_CLAMP) return fail(ctx, JH_ERR_INVALID, "jh_blur: unknown edge mode");
     uint32_t x = desc->x, y = desc->y, rw = desc->width, rh = desc->height;
     if (rw == 0u && rh == 0u) { x = 0u; y = 0u; rw = width; rh = height; }  // the whole image
     else if (rw == 0u || rh == 0u) return fail(ctx, JH_ERR_INVALID, "jh_blur: the rectangle is empty in one dimension");
     if ((uint64_t)x + rw > width || (uint64_t)y + rh > height) return fail(ctx, JH_ERR_INVALID, "jh_blur: the rectangle is not inside the image");
-    if (ctx->band_row0 != 0u || ctx->band_row1 != 0xffffffffu)
-        return fail(ctx, JH_ERR_INVALID, "jh_blur: not in band mode (the rows next to a band belong to another rank)");
+    if (int rc = refuse_band_mode(ctx, "jh_blur", "the rows next to a band belong to another rank")) return rc;
     float taps_x[2u * JBLUR_MAX_RADIUS + 1u], taps_y[2u * JBLUR_MAX_RADIUS + 1u];
     const uint32_t radius_x = jblur_taps(desc->sigma_x, taps_x), radius_y = jblur_taps(desc->sigma_y, taps_y);
     void* tmp = nullptr;
@@ -1397,11 +1418,7 @@ int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t 
         [&] {
             if (rw == 0u || rh == 0u) return (int)JH_OK;
             const void* from = content_or_null(*src);  // (before dst, which may be the same image, becomes written)
-            if (!(dst->written || dst->stored)) {  // outside the rectangle it goes on reading as transparent black
-                if (rw != width || rh != height) HIP_TRY(ctx, hipMemsetAsync(dst->ptr, 0, dst->size, ctx->stream));
-                ctx->generation++;  // (fine binds a never-written image as absent: the choice is baked into a graph)
-            }
-            dst->written = true;
+            if (int rc = first_content(ctx, dst, rw, rh)) return rc;
             return launch_status(ctx, "jh_blur", jh_blur_launch(ctx->stream, from, dst->ptr, width, height, x, y, rw, rh, desc->edge == JH_BLUR_EDGE_CLAMP,
                                                                 taps_x, radius_x, taps_y, radius_y, tmp, ctx->num_cus));
         });
@@ -1411,12 +1428,8 @@ int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t 
 int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_composite_desc* desc) {
     if (!ctx) return JH_ERR_INVALID;
     if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_composite: null descriptor");
-    const Alloc* src = find_alloc(ctx->images, src_image_id);
-    if (!src) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown source image id");
-    Alloc* dst = find_alloc(ctx->images, dst_image_id);
-    if (!dst) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown destination image id");
-    if (src->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_composite: the source is not an RGBA16F image");
-    if (dst->format != JL_RGBA16_FLOAT) return fail(ctx, JH_ERR_INVALID, "jh_composite: the destination is not an RGBA16F image");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_composite", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
     if (src == dst) return fail(ctx, JH_ERR_INVALID, "jh_composite: the source is the destination (a shifted blend in place reads what it writes)");
     if (desc->mix > 15u) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown mix mode (Mix.Clip is not a blend of two images)");
     if (desc->compose > 13u) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown compose operator");
@@ -1430,16 +1443,11 @@ int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, cons
     jcomp_rect rect;
     if (jcomp_clip(src->width, src->height, desc->sx, desc->sy, desc->sw, desc->sh, desc->dx, desc->dy, dst->width, dst->height, &rect))
         return fail(ctx, JH_ERR_INVALID, "jh_composite: the source rectangle is not inside the source image or is empty in one dimension");
-    if (ctx->band_row0 != 0u || ctx->band_row1 != 0xffffffffu)
-        return fail(ctx, JH_ERR_INVALID, "jh_composite: not in band mode (a shifted source row belongs to another rank)");
+    if (int rc = refuse_band_mode(ctx, "jh_composite", "a shifted source row belongs to another rank")) return rc;
     if (rect.w == 0u || rect.h == 0u) return JH_OK;  // placed outside dst: nothing to write, nothing launched
     return post_render_call(ctx, "composite", [&] {
         const bool backdrop = dst->written || dst->stored;
-        if (!backdrop) {  // outside the rectangle it goes on reading as transparent black
-            if (rect.w != dst->width || rect.h != dst->height) HIP_TRY(ctx, hipMemsetAsync(dst->ptr, 0, dst->size, ctx->stream));
-            ctx->generation++;  // (fine binds a never-written image as absent: the choice is baked into a graph)
-        }
-        dst->written = true;
+        if (int rc = first_content(ctx, dst, rect.w, rect.h)) return rc;
         return launch_status(ctx, "jh_composite",
                              jh_composite_launch(ctx->stream, content_or_null(*src), src->width, src->height, dst->ptr, dst->width, dst->height, backdrop,
                                                  &rect, desc->mix << 8 | desc->compose, desc->flags, desc->opacity, desc->tint, ctx->num_cus));

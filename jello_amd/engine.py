@@ -9,12 +9,23 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CCompositeDesc, CConfig, CYuvDesc
+from ._lib import CBlurDesc, CCompositeDesc, CConfig, CProfileNode, CProfileRecord, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
                "flatten", "draw_reduce", "draw_leaf", "clip_reduce", "clip_leaf", "binning", "tile_alloc", "backdrop_dyn",
                "path_count_setup", "path_count", "coarse", "path_tiling_setup", "path_tiling", "fine_area", "fine_msaa8", "fine_msaa16"]
+
+
+JH_ERR_INVALID = -1  # jh_status: the call was refused, nothing was launched or written
+
+
+class ImageFormat(enum.IntEnum):
+    """JlImageFormat (include/jello_formats.h): the texel format of a context image."""
+    RGBA8 = 0
+    RGBA8_SRGB = 1
+    BGRA8 = 2
+    RGBA16_FLOAT = 3
 
 
 class Surface(enum.IntEnum):
@@ -234,9 +245,12 @@ class Engine:
         except Exception:
             pass
 
-    def _check(self, rc, what):
+    def _check(self, rc, what, invalid=RuntimeError, host=False):
+        """Raises for a non-zero `rc` of the call `what`: `invalid` for JH_ERR_INVALID, RuntimeError for every other code.  The
+        text is jh_last_error's -- the C ABI was called directly -- or, with host=True, jl_last_error's (a jl_engine_* call)."""
         if rc != 0:
-            raise RuntimeError("%s failed (%d): %s | %s" % (what, rc, self._L.jl_last_error().decode(), self.hip.jh_last_error(self.ctx).decode()))
+            text = self._L.jl_last_error() if host else self.hip.jh_last_error(self.ctx)
+            raise (invalid if rc == JH_ERR_INVALID else RuntimeError)("%s failed (%d): %s" % (what, rc, text.decode()))
 
     @staticmethod
     def _frame_out():
@@ -255,10 +269,10 @@ class Engine:
         return self.hip.jh_buffer_device_ptr(self.ctx, buffer_id)
 
     def run(self, recording, flags=RUN_ALL, out_device_ptr=None):
-        self._check(self._L.jl_engine_run(self._h, recording._h, flags, 0, out_device_ptr), "run_recording")
+        self._check(self._L.jl_engine_run(self._h, recording._h, flags, 0, out_device_ptr), "run_recording", host=True)
 
     def release(self, recording):
-        self._check(self._L.jl_engine_release(self._h, recording._h), "release")
+        self._check(self._L.jl_engine_release(self._h, recording._h), "release", host=True)
 
     def render(self, scene, params, out_device_ptr=None, robust=True, retain=False):
         """RenderToTexture (+ regrow loop).  Returns (Recording, bump dict, attempts)."""
@@ -279,12 +293,15 @@ class Engine:
             self._check(self.hip.jh_download(self.ctx, _SURFACE_BUFFER_ID, out.ctypes.data, 0, out.nbytes), "download")
         return out
 
+    def _blit(self, src_image_id, ptr, pitch, width, height, fmt):
+        self._check(self.hip.jh_blit(self.ctx, src_image_id, ptr, pitch, width, height, int(fmt)), "blit")
+
     def blit(self, src_image_id, width, height, fmt, out_device_ptr=None, pitch=None):
         """The blit pass of RenderToSurface (jh_blit): the RGBA16F image `src_image_id` premultiplied and converted to the
         Surface format `fmt`.  Into `out_device_ptr` (rows `pitch` bytes apart, default 4 * width; returns None) or, without
         a pointer, returned as an (height, width, 4) uint8 array."""
         ptr, pitch = self._surface(width, height, fmt, out_device_ptr, pitch)
-        self._check(self._L.jl_engine_blit(self._h, src_image_id, ptr, pitch, width, height, int(fmt)), "blit")
+        self._blit(src_image_id, ptr, pitch, width, height, fmt)
         return None if out_device_ptr is not None else self._download_surface(width, height)
 
     def render_to_surface(self, scene, params, fmt, out_device_ptr=None, pitch=None, robust=True):
@@ -335,6 +352,9 @@ class Engine:
             out[1] = out[1].reshape(out[1].shape[0], -1, 2)
         return tuple(out)
 
+    def _blit_yuv(self, src_image_id, width, height, desc):
+        self._check(self.hip.jh_blit_yuv(self.ctx, src_image_id, width, height, ctypes.byref(desc)), "blit_yuv")
+
     def blit_yuv(self, src_image_id, width, height, layout=YuvLayout.NV12, matrix=YuvMatrix.BT709, range=YuvRange.LIMITED,
                  transfer=YuvTransfer.NONE, planes=None):
         """jh_blit_yuv: the RGBA16F image `src_image_id` as 8-bit Y'CbCr 4:2:0 (the rule: include/jello_hip.h "YUV blit").
@@ -342,7 +362,7 @@ class Engine:
         packed rows; returns None -- or, without planes, returned as uint8 arrays: (Y (H, W), CbCr (ceil(H/2), ceil(W/2), 2))
         for NV12, (Y, Cb, Cr) for I420."""
         d, own = self._yuv_desc(width, height, layout, matrix, range, transfer, planes)
-        self._check(self._L.jl_engine_blit_yuv(self._h, src_image_id, width, height, ctypes.byref(d)), "blit_yuv")
+        self._blit_yuv(src_image_id, width, height, d)
         return None if own is None else self._download_yuv(width, height, layout, own)
 
     def render_to_yuv(self, scene, params, layout=YuvLayout.NV12, matrix=YuvMatrix.BT709, range=YuvRange.LIMITED,
@@ -364,10 +384,8 @@ class Engine:
         destination that is written (None: the whole image); texels outside it keep their bits, source texels outside it take
         part.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
         d = _blur_desc(sigma, edge, rect)
-        rc = self._L.jl_engine_blur(self._h, image_id, image_id if dst_image_id is None else dst_image_id, width, height, ctypes.byref(d))
-        if rc == -1:  # JH_ERR_INVALID
-            raise ValueError(self._L.jl_last_error().decode())
-        self._check(rc, "blur")
+        dst = image_id if dst_image_id is None else dst_image_id
+        self._check(self.hip.jh_blur(self.ctx, image_id, dst, width, height, ctypes.byref(d)), "blur", invalid=ValueError)
 
     def composite(self, src_id, dst_id, mix=Mix.Normal, compose=Compose.SrcOver, opacity=1.0, tint=None, src_rect=None, offset=(0, 0)):
         """jh_composite: the RGBA16F image `src_id` blended onto the RGBA16F image `dst_id` (another image; the sizes may differ)
@@ -377,10 +395,7 @@ class Engine:
         included: it is clipped, and only the placed rectangle is written.  Stream-ordered, returns nothing; ValueError for a
         call the rule refuses."""
         d = _composite_desc(mix, compose, opacity, tint, src_rect, offset)
-        rc = self._L.jl_engine_composite(self._h, src_id, dst_id, ctypes.byref(d))
-        if rc == -1:  # JH_ERR_INVALID
-            raise ValueError(self._L.jl_last_error().decode())
-        self._check(rc, "composite")
+        self._check(self.hip.jh_composite(self.ctx, src_id, dst_id, ctypes.byref(d)), "composite", invalid=ValueError)
 
     def drop_shadow(self, layer_id, target_id, width, height, sigma, offset, color, scratch_image_id):
         """A layer with its drop shadow onto a target, three calls: blur(layer -> scratch, edge ZERO); composite(scratch -> target,
@@ -389,6 +404,10 @@ class Engine:
         self.blur(layer_id, width, height, sigma, dst_image_id=scratch_image_id, edge=BlurEdge.ZERO)
         self.composite(scratch_image_id, target_id, tint=color, offset=offset)
         self.composite(layer_id, target_id)
+
+    def _pack_tiles(self, src_ptr, pitch, ref_ptr, ref_pitch, width, height, texel_bytes, dst_ptr, capacity):
+        self._check(self.hip.jh_pack_tiles(self.ctx, src_ptr, pitch, ref_ptr, ref_pitch, width, height, texel_bytes, dst_ptr, capacity),
+                    "pack_tiles")
 
     def pack_tiles(self, src_ptr, pitch, width, height, texel_bytes, ref_ptr=None, ref_pitch=None, out_device_ptr=None,
                    out_capacity=None):
@@ -403,14 +422,14 @@ class Engine:
             cap = max(bound, 32)
             dst = self._own_buffer(_PACK_BUFFER_ID, cap)
         rp = 0 if ref_ptr is None else (pitch if ref_pitch is None else ref_pitch)
-        self._check(self._L.jl_engine_pack_tiles(self._h, src_ptr, pitch, ref_ptr, rp, width, height, texel_bytes, dst, cap), "pack_tiles")
+        self._pack_tiles(src_ptr, pitch, ref_ptr, rp, width, height, texel_bytes, dst, cap)
         return None if out_device_ptr is not None else self.read_pack(dst, cap)
 
     def read_pack(self, ptr, capacity):
         """The pack at the device pointer `ptr` as bytes: downloads its 32-byte header, then exactly its total size."""
         out = np.empty(capacity, dtype=np.uint8)
         size = ctypes.c_uint64()
-        self._check(self._L.jl_engine_read_pack(self._h, ptr, capacity, out.ctypes.data, capacity, ctypes.byref(size)), "read_pack")
+        self._check(self._L.jl_engine_read_pack(self._h, ptr, capacity, out.ctypes.data, capacity, ctypes.byref(size)), "read_pack", host=True)
         return out[:size.value].tobytes()
 
     def unpack_tiles(self, pack, dst_ptr, pitch, width, height, texel_bytes):
@@ -423,7 +442,7 @@ class Engine:
             self._check(self.hip.jh_upload(self.ctx, _UNPACK_BUFFER_ID, buf, size), "upload")
         else:
             ptr, size = pack
-        self._check(self._L.jl_engine_unpack_tiles(self._h, ptr, size, dst_ptr, pitch, width, height, texel_bytes), "unpack_tiles")
+        self._check(self.hip.jh_unpack_tiles(self.ctx, ptr, size, dst_ptr, pitch, width, height, texel_bytes), "unpack_tiles")
 
     def unpack_rejects(self, reset=False):
         """Entries (a bad header: one) unpack_tiles has ignored since the last reset.  Waits for the stream."""
@@ -456,10 +475,8 @@ class Engine:
         """jh_dash: the dashes of the batch into caller-owned device memory -- `capacity` elements of 28 bytes at `els_ptr`,
         len(paths) + 1 words at `index_ptr`.  Stream-ordered, returns nothing; ValueError for an input the rule rejects."""
         els, n_els, desc, dashes, n_dashes = self._dash_job(paths, patterns, offsets)
-        rc = self._L.jl_engine_dash_paths(self._h, els, n_els, desc, len(paths), dashes, n_dashes, els_ptr, capacity, index_ptr)
-        if rc == -1:  # JH_ERR_INVALID
-            raise ValueError(self._L.jl_last_error().decode())
-        self._check(rc, "dash_paths")
+        self._check(self.hip.jh_dash(self.ctx, els, n_els, desc, len(paths), dashes, n_dashes, els_ptr, capacity, index_ptr), "dash_paths",
+                    invalid=ValueError)
 
     def dash_paths(self, paths, patterns, offsets, capacity=None, raw=False):
         """The dashes of every path of the batch (scene.Path objects; one pattern and one offset each), computed on the device
@@ -514,15 +531,14 @@ class Engine:
                 self.composite(composite["src"], t["id"], **{k: v for k, v in composite.items() if k != "src"})
             if surface is not None:
                 ptr, pitch, fmt = surface
-                self._check(self._L.jl_engine_blit(self._h, t["id"], ptr, pitch, t["width"], t["height"], int(fmt)), "blit")
+                self._blit(t["id"], ptr, pitch, t["width"], t["height"], fmt)
             if yuv is not None:
                 planes, layout, matrix, rng, transfer = yuv
                 d, _ = self._yuv_desc(t["width"], t["height"], layout, matrix, rng, transfer, planes)
-                self._check(self._L.jl_engine_blit_yuv(self._h, t["id"], t["width"], t["height"], ctypes.byref(d)), "blit_yuv")
+                self._blit_yuv(t["id"], t["width"], t["height"], d)
             if pack is not None:
                 src, spitch, ref, rpitch, dst, cap, tb = pack
-                self._check(self._L.jl_engine_pack_tiles(self._h, src, spitch, ref, rpitch or 0, t["width"], t["height"], tb, dst, cap),
-                            "pack_tiles")
+                self._pack_tiles(src, spitch, ref, rpitch or 0, t["width"], t["height"], tb, dst, cap)
         finally:
             g = ctypes.c_void_p()
             rc = self.hip.jh_graph_end(self.ctx, ctypes.byref(g))
@@ -572,6 +588,19 @@ class Engine:
         self._check(self.hip.jh_download(self.ctx, buf_id, out.ctypes.data, offset, nbytes), "download")
         return out.view(dtype)
 
+    def upload_image(self, image_id, array, fmt=ImageFormat.RGBA16_FLOAT):
+        """jh_image_upload: the (H, W, 4) `array` of texels in the ImageFormat `fmt` as the image `image_id`, created or replaced."""
+        a = np.ascontiguousarray(array)
+        self._check(self.hip.jh_image_upload(self.ctx, image_id, a.shape[1], a.shape[0], int(fmt), a.ctypes.data, a.nbytes), "image_upload")
+
+    def create_image(self, image_id, width, height, fmt):
+        """jh_image_create: the image `image_id` of width x height texels in the ImageFormat `fmt`, without content."""
+        self._check(self.hip.jh_image_create(self.ctx, image_id, width, height, int(fmt)), "image_create")
+
+    def free_image(self, image_id):
+        """jh_image_free."""
+        self._check(self.hip.jh_image_free(self.ctx, image_id), "image_free")
+
     def download_image(self, img_id, width, height):
         out = np.empty((height, width, 4), dtype=np.uint16)
         self._check(self.hip.jh_image_download(self.ctx, img_id, out.ctypes.data, out.nbytes), "image_download")
@@ -581,9 +610,7 @@ class Engine:
         self.hip.jh_profile_enable(self.ctx, 1 if on else 0)
 
     def profile_collect(self, max_records=4096):
-        class Rec(ctypes.Structure):
-            _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
-        arr = (Rec * max_records)()
+        arr = (CProfileRecord * max_records)()
         n = self.hip.jh_profile_collect(self.ctx, arr, max_records)
         if n < 0:
             self._check(n, "profile_collect")
@@ -592,11 +619,7 @@ class Engine:
     def profile_collect_tree(self, max_nodes=1 << 16):
         """Profiler.Collect (profiler.go:337-385): list of dicts {kind, parent, stage, label, cpu_start_ms, cpu_end_ms,
         gpu_start_ms, gpu_end_ms}; a node's parent precedes it."""
-        class Node(ctypes.Structure):
-            _fields_ = [("kind", ctypes.c_int32), ("parent", ctypes.c_int32), ("stage", ctypes.c_int32), ("pad", ctypes.c_uint32),
-                        ("label", ctypes.c_char * 48), ("cpu_start_ms", ctypes.c_double), ("cpu_end_ms", ctypes.c_double),
-                        ("gpu_start_ms", ctypes.c_float), ("gpu_end_ms", ctypes.c_float)]
-        arr = (Node * max_nodes)()
+        arr = (CProfileNode * max_nodes)()
         n = self.hip.jh_profile_collect_tree(self.ctx, arr, max_nodes)
         if n < 0:
             self._check(n, "profile_collect_tree")

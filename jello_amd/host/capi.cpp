@@ -75,18 +75,6 @@ const char* jl_last_error() { return g_err.c_str(); }
         return failval;                     \
     }
 
-// GUARD for the calls that report the engine's own code: the JH_ERR_* of an EngineError, -100 for any other exception.
-#define GUARD_CODE(expr)                    \
-    try {                                   \
-        expr;                               \
-    } catch (const EngineError& e) {        \
-        g_err = e.what();                   \
-        return e.code;                      \
-    } catch (const std::exception& e) {     \
-        g_err = e.what();                   \
-        return -100;                        \
-    }
-
 static BezPath to_path(const jl_path_el* els, int n) {
     BezPath p;
     p.reserve((size_t)n);
@@ -430,10 +418,6 @@ void* jl_engine_render_to_surface(void* e, void* scene, const jl_render_params* 
     GUARD(f = eng->render_to_surface(((Scene*)scene)->encoding(), to_params(params), surface, pitch, format, robust != 0), nullptr);
     return rec_handle_of(std::move(f), bump_out, attempts);
 }
-int jl_engine_blit(void* e, uint64_t src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format) {
-    GUARD(((Engine*)e)->blit(src_image_id, surface, pitch, width, height, format), -1);
-    return 0;
-}
 
 // RenderToSurface for a video encoder: the same target, then jh_blit_yuv into the planes of *desc (NV12 / I420; the rule is in
 // jello_hip.h).  Returns the final attempt's recording handle like jl_engine_render_to_surface.
@@ -445,20 +429,10 @@ void* jl_engine_render_to_yuv(void* e, void* scene, const jl_render_params* para
     GUARD(f = eng->render_to_yuv(((Scene*)scene)->encoding(), to_params(params), *desc, robust != 0), nullptr);
     return rec_handle_of(std::move(f), bump_out, attempts);
 }
-int jl_engine_blit_yuv(void* e, uint64_t src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc* desc) {
-    if (!desc) { g_err = "blit_yuv: null descriptor"; return -1; }
-    GUARD(((Engine*)e)->blit_yuv(src_image_id, width, height, *desc), -1);
-    return 0;
-}
 
-// Gaussian blur (jh_blur; the rule is in jello_hip.h and DESIGN.md 5.7).  jl_blur_taps is the host twin of jh_blur_taps: the same
-// header, compiled here by the host compiler -- the 2R + 1 taps of sigma into weights (or null) and R into *radius; -1 for a
-// sigma that is negative, above 64 or NaN.
-int jl_engine_blur(void* e, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc) {
-    if (!desc) { g_err = "blur: null descriptor"; return -1; }
-    GUARD_CODE(((Engine*)e)->blur(src_image_id, dst_image_id, width, height, *desc));
-    return 0;
-}
+// jl_blur_taps is the host twin of jh_blur_taps (the rule is in jello_hip.h and DESIGN.md 5.7): the same header, compiled here by the
+// host compiler -- the 2R + 1 taps of sigma into weights (or null) and R into *radius; -1 for a sigma that is negative, above 64
+// or NaN.
 int jl_blur_taps(float sigma, float* weights, uint32_t* radius) {
     if (!jblur_sigma_ok(sigma)) { g_err = "blur_taps: sigma is negative, above 64 or NaN"; return -1; }
     const uint32_t R = jblur_taps(sigma, weights);
@@ -466,15 +440,10 @@ int jl_blur_taps(float sigma, float* weights, uint32_t* radius) {
     return 0;
 }
 
-// Composite (jh_composite; the rule is in jello_hip.h and DESIGN.md 5.8).  jl_composite_clip is the geometry of the call without a
-// GPU: the same header the library compiles, compiled here by the host compiler -- the source rectangle (sx, sy, sw, sh) of a
-// src_w x src_h image placed at (dx, dy) of a dst_w x dst_h one, clipped, into out[6] = {sx', sy', dx', dy', w, h} (all zero when
-// nothing is left); -1 for a source rectangle the rule refuses.
-int jl_engine_composite(void* e, uint64_t src_image_id, uint64_t dst_image_id, const jh_composite_desc* desc) {
-    if (!desc) { g_err = "composite: null descriptor"; return -1; }
-    GUARD_CODE(((Engine*)e)->composite(src_image_id, dst_image_id, *desc));
-    return 0;
-}
+// jl_composite_clip is the geometry of jh_composite (the rule is in jello_hip.h and DESIGN.md 5.8) without a GPU: the same header
+// the library compiles, compiled here by the host compiler -- the source rectangle (sx, sy, sw, sh) of a src_w x src_h image
+// placed at (dx, dy) of a dst_w x dst_h one, clipped, into out[6] = {sx', sy', dx', dy', w, h} (all zero when nothing is left);
+// -1 for a source rectangle the rule refuses.
 int jl_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w,
                       uint32_t dst_h, uint32_t* out) {
     jcomp_rect r;
@@ -483,24 +452,8 @@ int jl_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, 
     return 0;
 }
 
-// Tile-packed frame transport (jh_pack_tiles / jh_unpack_tiles; the format is in jello_hip.h).  Device pointers throughout.
-int jl_engine_pack_tiles(void* e, const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
-                         uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
-    GUARD(((Engine*)e)->pack_tiles(src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, dst_capacity), -1);
-    return 0;
-}
-int jl_engine_unpack_tiles(void* e, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
-                           uint32_t texel_bytes) {
-    GUARD(((Engine*)e)->unpack_tiles(pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes), -1);
-    return 0;
-}
-// Engine::dash_paths (jh_dash).  Returns 0, or the JH_ERR_* code (negative) with jl_last_error set.
-int jl_engine_dash_paths(void* e, const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
-                         uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index) {
-    GUARD_CODE(((Engine*)e)->dash_paths(els, n_els, paths, n_paths, dashes, n_dashes, out_els, out_capacity, out_index));
-    return 0;
-}
-// The pack at device_ptr into `out`: the header first, then exactly the size it states (written to *size).
+// The tile pack (jh_pack_tiles; the format is in jello_hip.h) at the device pointer device_ptr into `out`: the header first, then
+// exactly the size it states (written to *size).
 int jl_engine_read_pack(void* e, const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity, uint64_t* size) {
     uint64_t n = 0;
     GUARD(n = ((Engine*)e)->read_pack(device_ptr, capacity, out, out_capacity), -1);

@@ -177,19 +177,15 @@ Engine::Frame Engine::render_to_surface(const Encoding& enc, RenderParams params
     // pgroup = pgroup.Nest("RenderToSurface"); defer pgroup.End()  (lib.go:274-275)
     ProfileGroup group(*this, "RenderToSurface");
     Frame f = render_to_own_target(enc, params, robust);
-    blit(f.target.id, surface, pitch, params.width, params.height, format);
+    check(jh_blit(ctx_, f.target.id, surface, pitch, params.width, params.height, format), "blit");
     return f;
 }
 
 Engine::Frame Engine::render_to_yuv(const Encoding& enc, RenderParams params, const jh_yuv_desc& desc, bool robust) {
     ProfileGroup group(*this, "RenderToYUV");
     Frame f = render_to_own_target(enc, params, robust);
-    blit_yuv(f.target.id, params.width, params.height, desc);
+    check(jh_blit_yuv(ctx_, f.target.id, params.width, params.height, &desc), "blit_yuv");
     return f;
-}
-
-void Engine::blit_yuv(ResourceID src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc& desc) {
-    check(jh_blit_yuv(ctx_, src_image_id, width, height, &desc), "blit_yuv");
 }
 
 Engine::Frame Engine::render_to_own_target(const Encoding& enc, const RenderParams& params, bool robust) {
@@ -208,33 +204,6 @@ Engine::Frame Engine::render_to_own_target(const Encoding& enc, const RenderPara
     Frame f = render_to_texture(enc, params, jh_buffer_device_ptr(ctx_, t.buffer), robust, false);
     t.image = f.target.id;
     return f;
-}
-
-void Engine::blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format) {
-    check(jh_blit(ctx_, src_image_id, surface, pitch, width, height, format), "blit");
-}
-
-void Engine::blur(ResourceID src_image_id, ResourceID dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc& desc) {
-    check(jh_blur(ctx_, src_image_id, dst_image_id, width, height, &desc), "blur");
-}
-
-void Engine::composite(ResourceID src_image_id, ResourceID dst_image_id, const jh_composite_desc& desc) {
-    check(jh_composite(ctx_, src_image_id, dst_image_id, &desc), "composite");
-}
-
-void Engine::pack_tiles(const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
-                        uint32_t texel_bytes, void* dst, uint64_t dst_capacity) {
-    check(jh_pack_tiles(ctx_, src, src_pitch, ref, ref_pitch, width, height, texel_bytes, dst, dst_capacity), "pack_tiles");
-}
-
-void Engine::unpack_tiles(const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
-                          uint32_t texel_bytes) {
-    check(jh_unpack_tiles(ctx_, pack, pack_bytes, dst, dst_pitch, width, height, texel_bytes), "unpack_tiles");
-}
-
-void Engine::dash_paths(const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes,
-                        uint64_t n_dashes, void* out_els, uint64_t out_capacity, uint32_t* out_index) {
-    check(jh_dash(ctx_, els, n_els, paths, n_paths, dashes, n_dashes, out_els, out_capacity, out_index), "dash");
 }
 
 uint64_t Engine::read_pack(const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity) {

@@ -67,38 +67,15 @@ class Engine {
     // bytes, `pitch` bytes apart, in the jh_surface_format `format`.  The frame's target image stays readable under
     // Frame::target.id until the next render_to_surface / render_to_yuv.
     Frame render_to_surface(const Encoding& enc, RenderParams params, void* surface, uint64_t pitch, int format, bool robust = true);
-    // The blit pass alone: the RGBA16F image src_image_id into a surface (jh_blit).
-    void blit(ResourceID src_image_id, void* surface, uint64_t pitch, uint32_t width, uint32_t height, int format);
     // RenderToSurface for a video encoder: render_to_texture into the same engine-owned target, then jh_blit_yuv into the
     // planes of `desc` (NV12 / I420, include/jello_hip.h "YUV blit").  The frame's target image stays readable under
-    // Frame::target.id until the next render_to_surface / render_to_yuv./ render_to_yuv.
+    // Frame::target.id until the next render_to_surface / render_to_yuv.
     Frame render_to_yuv(const Encoding& enc, RenderParams params, const jh_yuv_desc& desc, bool robust = true);
-    // The conversion alone: the RGBA16F image src_image_id into the planes of `desc` (jh_blit_yuv).
-    void blit_yuv(ResourceID src_image_id, uint32_t width, uint32_t height, const jh_yuv_desc& desc);
 
-    // Gaussian blur of the RGBA16F image src_image_id into the rectangle of dst_image_id that `desc` names (jh_blur, include/jello_hip.h
-    // "Gaussian blur"; dst may be src).  Stream-ordered, waits for nothing.
-    void blur(ResourceID src_image_id, ResourceID dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc& desc);
-
-    // The rectangle of the RGBA16F image src_image_id that `desc` names blended onto dst_image_id (jh_composite, include/jello_hip.h
-    // "Composite"; the two must differ).  Stream-ordered, waits for nothing.
-    void composite(ResourceID src_image_id, ResourceID dst_image_id, const jh_composite_desc& desc);
-
-    // Tile-packed frame transport (jh_pack_tiles / jh_unpack_tiles, the format is in jello_hip.h): all pointers are device
-    // memory, both calls are stream-ordered and wait for nothing.
-    void pack_tiles(const void* src, uint64_t src_pitch, const void* ref, uint64_t ref_pitch, uint32_t width, uint32_t height,
-                    uint32_t texel_bytes, void* dst, uint64_t dst_capacity);
-    void unpack_tiles(const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height, uint32_t texel_bytes);
-    // Downloads the pack at device_ptr (capacity bytes of device memory): its 32-byte header first, then exactly the total size
-    // the header states -- the only two host waits of the feature.  Returns that size; throws when it exceeds capacity or
-    // out_capacity (a header that is not a pack's included).
+    // Downloads the tile pack (jh_pack_tiles; the format is in jello_hip.h) at device_ptr (capacity bytes of device memory): its
+    // 32-byte header first, then exactly the total size the header states -- the only two host waits of the feature.  Returns
+    // that size; throws when it exceeds capacity or out_capacity (a header that is not a pack's included).
     uint64_t read_pack(const void* device_ptr, uint64_t capacity, void* out, uint64_t out_capacity);
-
-    // Dashing on the device (jh_dash, include/jello_hip.h "dashing"; the rule: DESIGN.md 5.6): host arrays in, out_els
-    // (out_capacity elements of 28 bytes) and out_index (n_paths + 1 words) are device memory.  Stream-ordered, never waits; the
-    // last index word reports the elements the job needs.  Throws EngineError(JH_ERR_INVALID) for an input the rule rejects.
-    void dash_paths(const jh_dash_el* els, uint64_t n_els, const jh_dash_path* paths, uint32_t n_paths, const double* dashes, uint64_t n_dashes,
-                    void* out_els, uint64_t out_capacity, uint32_t* out_index);
 
     Resolver& resolver() { return resolver_; }
     Renderer& renderer() { return renderer_; }

@@ -1,9 +1,9 @@
 """What the -m gpu tests of the post-render calls share: ids that never collide within a session, caller-owned device memory
-behind a canary, the frame's RGBA16F target, and the scene set the blits are tested on."""
+behind a canary, context images, the frame's RGBA16F target, and the scene set the blits are tested on."""
 import numpy as np
 
 import jello_amd
-from jello_amd import scenes
+from jello_amd import ImageFormat, scenes
 
 CANARY = 0xA7
 _next_id = [0x7E57_5000_0000]
@@ -28,6 +28,26 @@ class DevBuf:
 
     def free(self):
         self.e.hip.jh_free(self.e.ctx, self.id)
+
+
+class Image:
+    """An image of the context: uploaded from (H, W, 4) uint16 bits, or only created (`bits` None: never written)."""
+
+    def __init__(self, engine, bits=None, width=None, height=None, fmt=ImageFormat.RGBA16_FLOAT):
+        self.e, self.id = engine, _id()
+        if bits is None:
+            self.w, self.h = width, height
+            engine.create_image(self.id, width, height, fmt)
+        else:
+            bits = np.ascontiguousarray(bits, np.uint16)
+            self.h, self.w, _ = bits.shape
+            engine.upload_image(self.id, bits, fmt)
+
+    def bits(self):
+        return self.e.download_image(self.id, self.w, self.h).copy()
+
+    def free(self):
+        self.e.free_image(self.id)
 
 
 def target_of(engine, rec):

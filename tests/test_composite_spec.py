@@ -266,7 +266,6 @@ def test_clip_refuses_a_bad_source_rectangle(built):
 def test_the_abi_has_the_call(built):
     hip = jello_amd.load_host().hip
     assert hip.jh_composite.argtypes[3]._type_ is CCompositeDesc
-    assert ctypes.sizeof(CCompositeDesc) == 56 and CCompositeDesc.tint.offset == 16 and CCompositeDesc.dx.offset == 48
     assert hip.jh_composite(None, 1, 2, None) == -1  # JH_ERR_INVALID without a context
 
 

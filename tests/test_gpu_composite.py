@@ -7,40 +7,18 @@ import numpy as np
 import pytest
 
 import jello_amd
-from jello_amd import BlurEdge, Brush, Cap, Compose, Fill, Join, Mix, Path, RenderParams, Scene, Stroke, Surface
+from jello_amd import BlurEdge, Brush, Cap, Compose, Fill, ImageFormat, Join, Mix, Path, RenderParams, Scene, Stroke, Surface
 from jello_amd._lib import CCompositeDesc
-from jello_amd.engine import RUN_DISPATCHES, RUN_UPLOADS
+from jello_amd.engine import JH_ERR_INVALID, RUN_DISPATCHES, RUN_UPLOADS
 
 import blur_ref
 import composite_cases
 import composite_ref
 import surface_ref
-from devmem import CANARY, DevBuf, _id, target_of
+from devmem import CANARY, DevBuf, Image, _id, target_of
 
 pytestmark = pytest.mark.gpu
 
-JL_RGBA8, JL_RGBA16_FLOAT = 0, 3
-JH_ERR_INVALID = -1
-
-
-class Image:
-    """An RGBA16F image of the context: uploaded from (H, W, 4) uint16 bits, or only created (`bits` None: never written)."""
-
-    def __init__(self, engine, bits=None, width=None, height=None, fmt=JL_RGBA16_FLOAT):
-        self.e, self.id = engine, _id()
-        if bits is None:
-            self.w, self.h = width, height
-            engine._check(engine.hip.jh_image_create(engine.ctx, self.id, width, height, fmt), "image_create")
-        else:
-            bits = np.ascontiguousarray(bits, np.uint16)
-            self.h, self.w, _ = bits.shape
-            engine._check(engine.hip.jh_image_upload(engine.ctx, self.id, self.w, self.h, fmt, bits.ctypes.data, bits.nbytes), "image_upload")
-
-    def bits(self):
-        return self.e.download_image(self.id, self.w, self.h).copy()
-
-    def free(self):
-        self.e.hip.jh_image_free(self.e.ctx, self.id)
 
 
 def _differences(got, want):
@@ -196,7 +174,7 @@ def test_refusals(engine):
     W, H = 16, 12
     canary = np.full((H, W, 4), CANARY | (CANARY << 8), np.uint16)
     src, dst = Image(engine, canary), Image(engine, canary)
-    rgba8 = Image(engine, np.full((H, W, 2), 0x1111, np.uint16), fmt=JL_RGBA8)  # (W x H texels of 4 bytes)
+    rgba8 = Image(engine, np.full((H, W, 2), 0x1111, np.uint16), fmt=ImageFormat.RGBA8)  # (W x H texels of 4 bytes)
     nan, inf = float("nan"), float("inf")
 
     def call(s=None, d=None, null=False, mix=0, compose=0, opacity=1.0, flags=0, tint=(0.0, 0.0, 0.0, 0.0), rect=(0, 0, 0, 0), at=(0, 0)):
@@ -290,7 +268,7 @@ def test_the_call_launches_what_is_held_back_first(engine):
     plain = [Image(engine, np.full((2, 2, 4), composite_cases.POISON, np.uint16)), Image(engine, ones)]
     try:
         for b, i in zip(bufs, over):
-            engine._check(hip.jh_image_import(ctx, i, b.ptr, 2, 2, JL_RGBA16_FLOAT), "image_import")
+            engine._check(hip.jh_image_import(ctx, i, b.ptr, 2, 2, ImageFormat.RGBA16_FLOAT), "image_import")
         # as the source: without the flush Copy copies the canary
         engine.clear(bufs[0].id)
         engine.composite(over[0], plain[0].id, compose=Compose.Copy)
@@ -301,6 +279,6 @@ def test_the_call_launches_what_is_held_back_first(engine):
         assert np.array_equal(bufs[1].bytes().view(np.uint16).reshape(2, 2, 4), ones)
     finally:
         for i in over:
-            hip.jh_image_free(ctx, i)
+            engine.free_image(i)
         for b in bufs + plain:
             b.free()

@@ -1,6 +1,7 @@
 """-m gpu: what the post-render calls -- jh_blit, jh_blit_yuv, jh_pack_tiles, jh_unpack_tiles, jh_dash -- share: each is one
 query of the profile tree (stage -1, no flat record), each launches the held-back commands before its own work, and each
-refused call answers JH_ERR_INVALID with a message that starts with the entry point's own name."""
+refused call answers JH_ERR_INVALID with a message that starts with the entry point's own name -- which the Engine method raises
+as the exception it documents."""
 import ctypes
 
 import numpy as np
@@ -8,30 +9,16 @@ import pytest
 
 from jello_amd import Path, Surface, YuvLayout, tilepack
 from jello_amd._lib import CDashPath
+from jello_amd.engine import JH_ERR_INVALID
 
 import surface_ref
 import tilepack_ref
 import yuv_ref
-from devmem import CANARY, DevBuf, _id
+from devmem import CANARY, DevBuf, Image, _id
 
 pytestmark = pytest.mark.gpu
 
-JL_RGBA16_FLOAT = 3
-JH_ERR_INVALID = -1
 W, H = 48, 33  # not tile-aligned; the odd height has a chroma row with one luma row above it
-
-
-class Image:
-    """An (H, W, 4) uint16 f16 image uploaded with jh_image_upload."""
-
-    def __init__(self, engine, bits):
-        self.e, self.id = engine, _id()
-        h, w, _ = bits.shape
-        bits = np.ascontiguousarray(bits, np.uint16)
-        engine._check(engine.hip.jh_image_upload(engine.ctx, self.id, w, h, JL_RGBA16_FLOAT, bits.ctypes.data, bits.nbytes), "image_upload")
-
-    def free(self):
-        self.e.hip.jh_image_free(self.e.ctx, self.id)
 
 
 def test_the_five_calls_are_queries_of_one_tree(engine):
@@ -136,6 +123,33 @@ def test_messages_keep_their_prefixes(engine):
         for name, call in refused.items():
             assert call() == JH_ERR_INVALID, name
             assert hip.jh_last_error(ctx).startswith(name.encode() + b": "), (name, hip.jh_last_error(ctx))
+        assert np.all(mem.bytes() == CANARY)
+    finally:
+        img.free()
+        mem.free()
+
+
+def test_engine_methods_raise_for_a_refused_call(engine):
+    """One refused call per Engine method on a 16 x 16 image (one tile): the exception class the method documents -- ValueError
+    for what the rule of blur and composite refuses, RuntimeError elsewhere -- with the entry point's own text in it, and the
+    image's bits are what was uploaded."""
+    bits = np.random.default_rng(16).random((16, 16, 4), dtype=np.float32).astype(np.float16).view(np.uint16)
+    img = Image(engine, bits)
+    mem = DevBuf(engine, 4096)
+    refused = [
+        (RuntimeError, "jh_blit: pitch below", lambda: engine.blit(img.id, 16, 16, Surface.RGBA8_UNORM, out_device_ptr=mem.ptr, pitch=4 * 16 - 4)),
+        (RuntimeError, "jh_blit_yuv: pitch below", lambda: engine.blit_yuv(img.id, 16, 16, planes=[(mem.ptr, 15), (mem.ptr + 256, None)])),
+        (RuntimeError, "jh_pack_tiles: source: texel_bytes", lambda: engine.pack_tiles(mem.ptr, 64, 16, 16, 3, out_device_ptr=mem.ptr + 1024)),
+        (RuntimeError, "jh_unpack_tiles: pack_bytes below", lambda: engine.unpack_tiles((mem.ptr, 16), mem.ptr + 1024, 64, 16, 16, 4)),
+        (ValueError, "jh_blur: ", lambda: engine.blur(img.id, 16, 16, 65.0)),
+        (ValueError, "jh_composite: ", lambda: engine.composite(img.id, img.id)),
+    ]
+    try:
+        for exc, text, call in refused:
+            with pytest.raises(exc, match=text) as info:
+                call()
+            assert info.type is exc, (text, info.type)  # (not a subclass: ValueError is not RuntimeError, and the reverse)
+        assert np.array_equal(engine.download_image(img.id, 16, 16), bits)
         assert np.all(mem.bytes() == CANARY)
     finally:
         img.free()

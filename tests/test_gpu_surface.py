@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import jello_amd
-from jello_amd import BumpSizes, Surface, scenes
-from jello_amd.engine import RUN_DISPATCHES, RUN_UPLOADS
+from jello_amd import BumpSizes, ImageFormat, Surface, scenes
+from jello_amd.engine import JH_ERR_INVALID, RUN_DISPATCHES, RUN_UPLOADS
 from oracle.oracle_engine import OracleEngine
 
 import surface_ref as ref
@@ -15,8 +15,6 @@ from devmem import CANARY, SCENES, DevBuf, _id, _odd, target_of
 
 pytestmark = pytest.mark.gpu
 
-JL_RGBA8, JL_RGBA16_FLOAT = 0, 3
-JH_ERR_INVALID = -1
 def assert_surface(got, want, what):
     if not np.array_equal(got, want):
         bad = np.argwhere(got != want)
@@ -44,15 +42,14 @@ def test_scenes_in_every_format(engine, name):
 
 
 def _blit_crafted(engine, img_bits, fmt):
-    """Uploads an (H, W, 4) uint16 f16 image with jh_image_upload and blits it; returns the (H, W, 4) uint8 surface."""
+    """Uploads an (H, W, 4) uint16 f16 image and blits it; returns the (H, W, 4) uint8 surface."""
     h, w, _ = img_bits.shape
     iid = _id()
-    img = np.ascontiguousarray(img_bits, np.uint16)
     try:
-        engine._check(engine.hip.jh_image_upload(engine.ctx, iid, w, h, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
+        engine.upload_image(iid, np.asarray(img_bits, np.uint16))
         return engine.blit(iid, w, h, fmt)
     finally:
-        engine.hip.jh_image_free(engine.ctx, iid)
+        engine.free_image(iid)
 
 
 ALPHAS = [0x0000, 0x8000, 0x0001, 0x0002, 0x00FF, 0x03FF, 0x8001, 0x83FF, 0x0400, 0x1C00, 0x1E00, 0x2000, 0x2E66, 0x3000,
@@ -183,8 +180,8 @@ def test_refused_calls_touch_nothing(engine):
     rng = np.random.default_rng(7)
     img = rng.integers(0, 0x3C01, size=(h, w, 4), dtype=np.uint16)
     src, rgba8 = _id(), _id()
-    engine._check(hip.jh_image_upload(ctx, src, w, h, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
-    engine._check(hip.jh_image_create(ctx, rgba8, w, h, JL_RGBA8), "image_create")
+    engine.upload_image(src, img)
+    engine.create_image(rgba8, w, h, ImageFormat.RGBA8)
     canary = DevBuf(engine, 4 * w * h + 256)
     good = DevBuf(engine, 4 * w * h)
     want = ref.convert(img, 0)
@@ -207,20 +204,20 @@ def test_refused_calls_touch_nothing(engine):
             engine.sync()
             assert_surface(good.bytes().reshape(h, w, 4), want, "valid blit after " + what)
     finally:
-        hip.jh_image_free(ctx, src)
-        hip.jh_image_free(ctx, rgba8)
+        engine.free_image(src)
+        engine.free_image(rgba8)
         canary.free()
         good.free()
 
 
 def test_never_written_source_is_transparent_black(engine):
     iid = _id()
-    engine._check(engine.hip.jh_image_create(engine.ctx, iid, 9, 4, JL_RGBA16_FLOAT), "image_create")
+    engine.create_image(iid, 9, 4, ImageFormat.RGBA16_FLOAT)
     try:
         for fmt in Surface:
             assert not engine.blit(iid, 9, 4, fmt).any()
     finally:
-        engine.hip.jh_image_free(engine.ctx, iid)
+        engine.free_image(iid)
 
 
 def test_regrow_loop(engine):

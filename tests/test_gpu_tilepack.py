@@ -10,7 +10,7 @@ import pytest
 
 import jello_amd
 from jello_amd import Surface, scenes, tilepack
-from jello_amd.engine import RUN_DISPATCHES, RUN_UPLOADS
+from jello_amd.engine import JH_ERR_INVALID, RUN_DISPATCHES, RUN_UPLOADS
 
 import tilepack_ref as ref
 from devmem import CANARY, DevBuf
@@ -18,7 +18,6 @@ from tilepack_cases import CASES, DTYPES, case_frames, make_frame
 
 pytestmark = pytest.mark.gpu
 
-JH_ERR_INVALID = -1
 def laid_out(frame, pitch, offset, tail=64):
     """The frame's rows `pitch` bytes apart, `offset` bytes into a CANARY-filled byte array with `tail` bytes behind."""
     h, w = frame.shape[:2]

@@ -10,19 +10,17 @@ import numpy as np
 import pytest
 
 import jello_amd
-from jello_amd import BumpSizes, YuvLayout, YuvMatrix, YuvRange, YuvTransfer, scenes
+from jello_amd import BumpSizes, ImageFormat, YuvLayout, YuvMatrix, YuvRange, YuvTransfer, scenes
 from jello_amd._lib import CYuvDesc
-from jello_amd.engine import RUN_DISPATCHES, RUN_UPLOADS
+from jello_amd.engine import JH_ERR_INVALID, RUN_DISPATCHES, RUN_UPLOADS
 from oracle.oracle_engine import OracleEngine
 
 import surface_ref
 import yuv_ref as ref
-from devmem import CANARY, SCENES, DevBuf, _id, target_of
+from devmem import CANARY, SCENES, DevBuf, Image, _id, target_of
 
 pytestmark = pytest.mark.gpu
 
-JL_RGBA8, JL_RGBA16_FLOAT = 0, 3
-JH_ERR_INVALID = -1
 COMBOS = list(itertools.product(YuvLayout, YuvMatrix, YuvRange, YuvTransfer))
 
 
@@ -66,20 +64,6 @@ def test_scenes_in_every_combination(engine, name):
             assert_planes(planes, ref.convert(oracle_img, int(layout), int(matrix), int(rng), int(transfer)), what + " vs the oracle")
 
 
-class Crafted:
-    """An (H, W, 4) uint16 f16 image uploaded with jh_image_upload."""
-
-    def __init__(self, engine, img_bits):
-        self.e = engine
-        self.h, self.w, _ = img_bits.shape
-        self.id = _id()
-        img = np.ascontiguousarray(img_bits, np.uint16)
-        engine._check(engine.hip.jh_image_upload(engine.ctx, self.id, self.w, self.h, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
-
-    def free(self):
-        self.e.hip.jh_image_free(self.e.ctx, self.id)
-
-
 def test_all_code_triples(engine):
     """A 4096 x 4096 image of all 2^24 (R, G, B): pixel i has R = i & 255, G = (i >> 8) & 255, B = i >> 16, stored as
     f16(k / 255) with alpha 1.  Transfer NONE, all four tables, both layouts, Y and chroma planes."""
@@ -91,7 +75,7 @@ def test_all_code_triples(engine):
     img = np.empty((4096, 4096, 4), np.uint16)
     img[..., :3] = lut.view(np.uint16)[codes]
     img[..., 3] = 0x3C00
-    src = Crafted(engine, img)
+    src = Image(engine, img)
     del img
     try:
         for matrix, rng in itertools.product(YuvMatrix, YuvRange):
@@ -111,7 +95,7 @@ def test_random_f16_bit_patterns(engine):
     img = rng_.integers(0, 65536, size=(512, 512, 4), dtype=np.uint16)
     f = img.view(np.float16)
     assert np.isnan(f).any() and np.isinf(f).any() and (f[..., :3] > 1).any() and (f[..., 3] < 0).any() and (f[..., 3] > 1).any()
-    src = Crafted(engine, img)
+    src = Image(engine, img)
     try:
         for layout, matrix, rng, transfer in COMBOS:
             got = engine.blit_yuv(src.id, 512, 512, layout, matrix, rng, transfer)
@@ -168,7 +152,7 @@ def test_pitch_alignment_and_canaries(engine, size, extra, offset):
     planes' rows are right (the wide and the narrow path write the same bytes) and no other byte changes."""
     w, h = size
     img = _crafted_plausible(w, h, 100 * w + h)
-    src = Crafted(engine, img)
+    src = Image(engine, img)
     try:
         for layout, transfer in itertools.product(YuvLayout, YuvTransfer):
             pl = Planes(engine, w, h, layout, extra, offset)
@@ -261,8 +245,8 @@ def test_refused_calls_touch_nothing(engine):
     w, h = 13, 5
     cw, ch = 7, 3
     img = _crafted_plausible(w, h, 7)
-    src, rgba8 = Crafted(engine, img), _id()
-    engine._check(hip.jh_image_create(ctx, rgba8, w, h, JL_RGBA8), "image_create")
+    src, rgba8 = Image(engine, img), _id()
+    engine.create_image(rgba8, w, h, ImageFormat.RGBA8)
     canary = [DevBuf(engine, 512) for _ in range(3)]
     nv12 = [(canary[0].ptr, w), (canary[1].ptr, 2 * cw), (None, 0)]
     i420 = [(canary[0].ptr, w), (canary[1].ptr, cw), (canary[2].ptr, cw)]
@@ -306,7 +290,7 @@ def test_refused_calls_touch_nothing(engine):
             good.check(want, "valid call after " + what)
     finally:
         src.free()
-        hip.jh_image_free(ctx, rgba8)
+        engine.free_image(rgba8)
         good.free()
         for c in canary:
             c.free()
@@ -315,7 +299,7 @@ def test_refused_calls_touch_nothing(engine):
 
 def test_never_written_source_is_black(engine):
     iid = _id()
-    engine._check(engine.hip.jh_image_create(engine.ctx, iid, 9, 5, JL_RGBA16_FLOAT), "image_create")
+    engine.create_image(iid, 9, 5, ImageFormat.RGBA16_FLOAT)
     try:
         for layout, matrix, rng, transfer in COMBOS:
             planes = engine.blit_yuv(iid, 9, 5, layout, matrix, rng, transfer)
@@ -323,7 +307,7 @@ def test_never_written_source_is_black(engine):
             for c in planes[1:]:
                 assert c.shape[:2] == (3, 5) and np.all(c == 128)
     finally:
-        engine.hip.jh_image_free(engine.ctx, iid)
+        engine.free_image(iid)
 
 
 def test_regrow_loop(engine):

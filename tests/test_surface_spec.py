@@ -3,20 +3,16 @@ table against its generator and the binary64 rule, hand values, the Python Surfa
 shim's C calls against the declarations of include/jello_hip.h."""
 import importlib.util
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import surface_ref as ref
+from abi_text import c_values, go_calls, header_arity
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "jello_amd", "csrc", "srgb_encode_lut.h")
 GEN = os.path.join(ROOT, "tools", "gen_srgb_encode_table.py")
-JH = os.path.join(ROOT, "include", "jello_hip.h")
-GO = os.path.join(ROOT, "integration", "engine", "hip_engine", "hip_engine.go")
 
 
 def _gen():
@@ -99,55 +95,15 @@ def test_specials(table):
 
 def test_surface_enum_matches_header():
     from jello_amd import Surface
-    src = '#include <stdio.h>\n#include "jello_hip.h"\nint main(void){printf("%d %d %d %d\\n", JH_SURFACE_RGBA8_UNORM, ' \
-          'JH_SURFACE_BGRA8_UNORM, JH_SURFACE_RGBA8_SRGB, JH_SURFACE_BGRA8_SRGB); return 0;}\n'
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "e.c")
-        with open(c, "w") as f:
-            f.write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "e")])
-        vals = [int(x) for x in subprocess.check_output([os.path.join(d, "e")]).split()]
+    vals = c_values(["JH_SURFACE_RGBA8_UNORM", "JH_SURFACE_BGRA8_UNORM", "JH_SURFACE_RGBA8_SRGB", "JH_SURFACE_BGRA8_SRGB"])
     assert vals == [Surface.RGBA8_UNORM, Surface.BGRA8_UNORM, Surface.RGBA8_SRGB, Surface.BGRA8_SRGB] == [0, 1, 2, 3]
     assert [s.name for s in Surface] == ["RGBA8_UNORM", "BGRA8_UNORM", "RGBA8_SRGB", "BGRA8_SRGB"]
 
 
-def _declared_arity():
-    """name -> parameter count of every function declared in include/jello_hip.h."""
-    with open(JH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(jh_\w+)\s*\(([^()]*)\)\s*;", text):
-        params = m.group(2).strip()
-        out[m.group(1)] = 0 if params in ("", "void") else params.count(",") + 1
-    return out
-
-
-def _go_calls():
-    """(name, argument count) of every C.jh_* call in the Go shim, by paren matching."""
-    with open(GO) as f:
-        text = f.read()
-    calls = []
-    for m in re.finditer(r"\bC\.(jh_\w+)\s*\(", text):
-        i, depth, commas = m.end(), 1, 0
-        start = i
-        while depth:
-            ch = text[i]
-            if ch in "([{":
-                depth += 1
-            elif ch in ")]}":
-                depth -= 1
-            elif ch == "," and depth == 1:
-                commas += 1
-            i += 1
-        body = text[start:i - 1].strip()
-        calls.append((m.group(1), 0 if not body else commas + 1))
-    return calls
-
-
 def test_go_shim_calls_match_the_header():
-    decl = _declared_arity()
+    decl = header_arity()
     assert decl.get("jh_blit") == 7
-    calls = _go_calls()
+    calls = go_calls()
     assert len(calls) > 20
     for name, n in calls:
         assert name in decl, "hip_engine.go calls %s, which include/jello_hip.h does not declare" % name

@@ -12,11 +12,10 @@ import pytest
 from jello_amd import tilepack
 
 import tilepack_ref as ref
+from abi_text import GO, JH, go_calls, header_arity
 from tilepack_cases import CASES, DTYPES, SIZES, case_frames, make_frame
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-JH = os.path.join(ROOT, "include", "jello_hip.h")
-GO = os.path.join(ROOT, "integration", "engine", "hip_engine", "hip_engine.go")
 
 POISON = 0xA7
 
@@ -207,42 +206,11 @@ def test_tile_statistics_of_oracle_frames(built):
     assert tilepack.apply(p, out) == 0 and np.array_equal(out, b)
 
 
-# ---- the Go shim against the header (parsed as tests/test_surface_spec.py does for jh_blit) ----
-def _declared_arity():
-    with open(JH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(jh_\w+)\s*\(([^()]*)\)\s*;", text):
-        params = m.group(2).strip()
-        out[m.group(1)] = 0 if params in ("", "void") else params.count(",") + 1
-    return out
-
-
-def _go_calls():
-    with open(GO) as f:
-        text = f.read()
-    calls = []
-    for m in re.finditer(r"\bC\.(jh_\w+)\s*\(", text):
-        i, depth, commas = m.end(), 1, 0
-        start = i
-        while depth:
-            ch = text[i]
-            if ch in "([{":
-                depth += 1
-            elif ch in ")]}":
-                depth -= 1
-            elif ch == "," and depth == 1:
-                commas += 1
-            i += 1
-        body = text[start:i - 1].strip()
-        calls.append((m.group(1), 0 if not body else commas + 1))
-    return calls
-
-
+# ---- the Go shim against the header ----
 def test_go_shim_calls_pack_and_unpack_as_declared():
-    decl = _declared_arity()
+    decl = header_arity()
     assert decl.get("jh_pack_tiles") == 10 and decl.get("jh_unpack_tiles") == 8 and decl.get("jh_pack_bound") == 3
-    calls = _go_calls()
+    calls = go_calls()
     by_name = {}
     for name, n in calls:
         by_name.setdefault(name, set()).add(n)

@@ -4,20 +4,16 @@ the sixteen rows the rule prints; hand values, greys, ranges and the distance to
 plane shapes and edge replication, the Python enums against the header, the Go shim's C calls against the declarations."""
 import importlib.util
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import yuv_ref as ref
+from abi_text import c_values, go_calls, header_arity
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "jello_amd", "csrc", "yuv_matrix_lut.h")
 GEN = os.path.join(ROOT, "tools", "gen_yuv_table.py")
-JH = os.path.join(ROOT, "include", "jello_hip.h")
-GO = os.path.join(ROOT, "integration", "engine", "hip_engine", "hip_engine.go")
 
 # the rows of the rule: (matrix, range) -> Y row, Cb row, Cr row
 ROWS = {
@@ -184,62 +180,17 @@ def test_yuv_enums_match_header():
     from jello_amd import YuvLayout, YuvMatrix, YuvRange, YuvTransfer
     names = ["JH_YUV_NV12", "JH_YUV_I420", "JH_YUV_BT601", "JH_YUV_BT709", "JH_YUV_LIMITED", "JH_YUV_FULL", "JH_YUV_TRANSFER_NONE",
              "JH_YUV_TRANSFER_SRGB"]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "jello_hip.h"\nint main(void){printf("' + "%d " * len(names) + '%d %d %d\\n", ' + \
-          ", ".join(names) + ", (int)sizeof(jh_yuv_desc), (int)offsetof(jh_yuv_desc, plane), (int)offsetof(jh_yuv_desc, pitch)); return 0;}\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "e.c")
-        with open(c, "w") as f:
-            f.write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(d, "e")])
-        vals = [int(x) for x in subprocess.check_output([os.path.join(d, "e")]).split()]
-    assert vals[:8] == [YuvLayout.NV12, YuvLayout.I420, YuvMatrix.BT601, YuvMatrix.BT709, YuvRange.LIMITED, YuvRange.FULL,
+    vals = c_values(names)
+    assert vals == [YuvLayout.NV12, YuvLayout.I420, YuvMatrix.BT601, YuvMatrix.BT709, YuvRange.LIMITED, YuvRange.FULL,
                         YuvTransfer.NONE, YuvTransfer.SRGB] == [0, 1, 0, 1, 0, 1, 0, 1]
     assert [e.name for e in YuvLayout] == ["NV12", "I420"] and [e.name for e in YuvMatrix] == ["BT601", "BT709"]
     assert [e.name for e in YuvRange] == ["LIMITED", "FULL"] and [e.name for e in YuvTransfer] == ["NONE", "SRGB"]
     assert (ref.NV12, ref.I420, ref.BT601, ref.BT709, ref.LIMITED, ref.FULL, ref.NONE, ref.SRGB) == (0, 1, 0, 1, 0, 1, 0, 1)
-    # the ctypes mirror of jh_yuv_desc
-    import ctypes
-    from jello_amd._lib import CYuvDesc
-    assert vals[8:] == [ctypes.sizeof(CYuvDesc), CYuvDesc.plane.offset, CYuvDesc.pitch.offset]
-
-
-def _declared_arity():
-    """name -> parameter count of every function declared in include/jello_hip.h."""
-    with open(JH) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(jh_\w+)\s*\(([^()]*)\)\s*;", text):
-        params = m.group(2).strip()
-        out[m.group(1)] = 0 if params in ("", "void") else params.count(",") + 1
-    return out
-
-
-def _go_calls():
-    """(name, argument count) of every C.jh_* call in the Go shim, by paren matching."""
-    with open(GO) as f:
-        text = f.read()
-    calls = []
-    for m in re.finditer(r"\bC\.(jh_\w+)\s*\(", text):
-        i, depth, commas = m.end(), 1, 0
-        start = i
-        while depth:
-            ch = text[i]
-            if ch in "([{":
-                depth += 1
-            elif ch in ")]}":
-                depth -= 1
-            elif ch == "," and depth == 1:
-                commas += 1
-            i += 1
-        body = text[start:i - 1].strip()
-        calls.append((m.group(1), 0 if not body else commas + 1))
-    return calls
-
 
 def test_go_shim_calls_blit_yuv_as_declared():
-    decl = _declared_arity()
+    decl = header_arity()
     assert decl.get("jh_blit_yuv") == 5
-    calls = _go_calls()
+    calls = go_calls()
     assert len(calls) > 20
     for name, n in calls:
         assert name in decl, "hip_engine.go calls %s, which include/jello_hip.h does not declare" % name

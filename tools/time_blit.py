@@ -16,7 +16,6 @@ from timing import ROOT, open_engine_on_stream, timed, write_json
 
 from jello_amd import Surface  # noqa: E402 (timing puts the root on sys.path)
 
-JL_RGBA16_FLOAT = 3
 
 
 def main():
@@ -35,7 +34,7 @@ def main():
         # colours and alphas spread over [0, 1.25) (some values above 1 clamp), as a fine stage leaves them
         img = (rng.random((size, size, 4), dtype=np.float32) * 1.25).astype(np.float16).view(np.uint16)
         src, dst = 0x71BE_0000 + size, 0x71BF_0000 + size
-        eng._check(hip.jh_image_upload(ctx, src, size, size, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
+        eng.upload_image(src, img)
         eng._check(hip.jh_buffer_create(ctx, dst, 4 * n), "buffer_create")
         ptr = hip.jh_buffer_device_ptr(ctx, dst)
         for fmt in Surface:
@@ -46,7 +45,7 @@ def main():
             results.append(r)
             print(json.dumps(r), flush=True)
         hip.jh_free(ctx, dst)
-        hip.jh_image_free(ctx, src)
+        eng.free_image(src)
     eng.sync()
     eng.set_stream(None)
     eng.close()

@@ -20,7 +20,6 @@ from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_jso
 
 from jello_amd import BlurEdge  # noqa: E402 (timing puts the root on sys.path)
 
-JL_RGBA16_FLOAT = 3
 SIZE = 4096
 
 
@@ -37,8 +36,8 @@ def main():
     # colours and alphas spread over [0, 1.25), as a fine stage leaves them
     img = (rng.random((SIZE, SIZE, 4), dtype=np.float32) * 1.25).astype(np.float16).view(np.uint16)
     src, dst = 0x71C0_0000, 0x71C1_0000
-    eng._check(hip.jh_image_upload(ctx, src, SIZE, SIZE, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
-    eng._check(hip.jh_image_upload(ctx, dst, SIZE, SIZE, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
+    eng.upload_image(src, img)
+    eng.upload_image(dst, img)
     with torch.cuda.stream(stream):
         ta = torch.zeros((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
         tb = torch.ones((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
@@ -71,8 +70,8 @@ def main():
                      "traffic_bytes": (8 + 16 + 16 + 8) * texels, "traffic_tb_per_s": round(48 * texels / (med * 1e-6) / 1e12, 3)}
                 results.append(r)
                 print(json.dumps(r), flush=True)
-    hip.jh_image_free(ctx, src)
-    hip.jh_image_free(ctx, dst)
+    eng.free_image(src)
+    eng.free_image(dst)
     eng.sync()
     eng.set_stream(None)
     eng.close()

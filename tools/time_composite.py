@@ -19,7 +19,6 @@ from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_jso
 
 from jello_amd import Compose, Mix, Surface  # noqa: E402 (timing puts the root on sys.path)
 
-JL_RGBA16_FLOAT = 3
 SIZE = 4096
 MODES = [("Normal+SrcOver", Mix.Normal, None), ("Normal+SrcOver, tint", Mix.Normal, (0.0, 0.0, 0.0, 0.5)), ("Multiply+SrcOver", Mix.Multiply, None),
          ("Hue+SrcOver", Mix.Hue, None)]
@@ -38,8 +37,8 @@ def main():
     # colours spread over [0, 1.25) and alphas over [0, 1], as a fine stage leaves them
     img = (rng.random((SIZE, SIZE, 4), dtype=np.float32) * np.array([1.25, 1.25, 1.25, 1.0], np.float32)).astype(np.float16).view(np.uint16)
     src, dst = 0x71C2_0000, 0x71C3_0000
-    eng._check(hip.jh_image_upload(ctx, src, SIZE, SIZE, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
-    eng._check(hip.jh_image_upload(ctx, dst, SIZE, SIZE, JL_RGBA16_FLOAT, img.ctypes.data, img.nbytes), "image_upload")
+    eng.upload_image(src, img)
+    eng.upload_image(dst, img)
     with torch.cuda.stream(stream):
         ta = torch.zeros((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
         tb = torch.ones((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
@@ -79,8 +78,8 @@ def main():
             record({"rect": label, "call": "jh_composite", "mode": name, "us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times],
                     "us_spread": round(max(times) - min(times), 3), "copy_us_median": round(floor, 3), "ratio_to_copy": round(med / floor, 2),
                     "algorithmic_bytes": 24 * texels, "tb_per_s": round(24 * texels / (med * 1e-6) / 1e12, 3)})
-    hip.jh_image_free(ctx, src)
-    hip.jh_image_free(ctx, dst)
+    eng.free_image(src)
+    eng.free_image(dst)
     eng.sync()
     eng.set_stream(None)
     eng.close()
