@@ -35,6 +35,7 @@ __device__ __forceinline__ uint32_t blit_srgb(float v, const float2* lut) {
 // one RGBA16F texel (x = r | g << 16, y = b | a << 16, f16 bits) -> the surface's 4 bytes, byte 0 lowest
 template <bool SRGB, bool BGRA>
 __device__ __forceinline__ uint32_t blit_pixel(uint2 t, const float2* lut) {
+    // (not jd::rgba16f_to_f32: alpha first -- with the four conversions in the helper's order the compiler reorders k_blit_yuv)
     const float a = jd::f16_to_f32((uint16_t)(t.y >> 16));
     const float r = blit_clamp01(jd::f16_to_f32((uint16_t)(t.x & 0xffffu)) * a);
     const float g = blit_clamp01(jd::f16_to_f32((uint16_t)(t.x >> 16)) * a);

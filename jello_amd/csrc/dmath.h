@@ -69,6 +69,8 @@ JD int32_t to_i32(float f) {
     return (int32_t)f;
 #endif
 }
+// Cells of the unit grid that the interval between a and b reaches into, at least one (path_count: tiles, multisampled fine: pixels)
+JD uint32_t cell_span(float a, float b) { return to_u32(fmax_(ceil_(fmax_(a, b)) - floor_(fmin_(a, b)), 1.0f)); }
 
 // ---- binary64 kernels ----
 // Every polynomial is evaluated with explicit fused multiply-adds in Estrin form (a fixed tree, written out below):
@@ -203,6 +205,10 @@ JD float f16_to_f32(uint16_t h) {
     union { uint16_t u; _Float16 f; } c;
     c.u = h;
     return (float)c.f;
+}
+JD float4 rgba16f_to_f32(uint2 t) {  // an RGBA16F texel as it is loaded: x = g << 16 | r, y = a << 16 | b
+    return make_float4(f16_to_f32((uint16_t)(t.x & 0xffffu)), f16_to_f32((uint16_t)(t.x >> 16)), f16_to_f32((uint16_t)(t.y & 0xffffu)),
+                       f16_to_f32((uint16_t)(t.y >> 16)));
 }
 JD uint16_t f32_to_f16(float f) {
     union { uint16_t u; _Float16 h; } c;

@@ -1,12 +1,13 @@
 // kcommon.h -- shared device helpers: bounds-checked buffer views (the WGSL robust-access rule:
 // out-of-range reads give zero, writes are dropped -- also what keeps a malformed scene from
-// faulting the GPU), wave64/LDS block scans, and the launcher declarations used by jello_hip.cpp.
+// faulting the GPU), wave64/LDS block scans (on kwave.h), and the launcher declarations used by jello_hip.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/jello_formats.h"
 #include "dmath.h"
+#include "kwave.h"
 
 #define JL_WG 256
 
@@ -37,39 +38,6 @@ static inline Buf<T> mkbuf(void* p, uint64_t bytes) {
     return b;
 }
 
-// ---- wave64 primitives ----
-JD uint32_t lane_id() { return threadIdx.x & 63u; }
-JD uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }  // a value that is the same in every lane, as a scalar
-// Inclusive wave64 prefix operations on the DPP path (row_shr 1,2,4,8 inside each 16-lane row, then
-// row_bcast:15 / row_bcast:31 across rows): six VALU instructions, no LDS crossbar round trips
-// (__shfl_up compiles to ds_bpermute_b32, ~100 cycles each and six of them dependent).
-#define JK_DPP_ROW_SHR(n) (0x110 + (n))
-#define JK_DPP_ROW_BCAST15 0x142
-#define JK_DPP_ROW_BCAST31 0x143
-JD uint32_t wave_incl_scan_u32(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(1), 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(2), 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(4), 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(8), 0xf, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_BCAST15, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_BCAST31, 0xc, 0xf, false);
-    return v;
-}
-JD uint32_t wave_incl_max_u32(uint32_t v) {
-    v = jd::umax_(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(1), 0xf, 0xf, false));
-    v = jd::umax_(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(2), 0xf, 0xf, false));
-    v = jd::umax_(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(4), 0xf, 0xf, false));
-    v = jd::umax_(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_SHR(8), 0xf, 0xf, false));
-    v = jd::umax_(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_BCAST15, 0xa, 0xf, false));
-    v = jd::umax_(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, JK_DPP_ROW_BCAST31, 0xc, 0xf, false));
-    return v;
-}
-// Orders this wave's LDS accesses (a wave's DS instructions execute in issue order; the fence only has to stop the
-// compiler from moving them) -- the synchronisation primitive of kernels whose waves own private LDS regions.
-JD void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 // [p, p + n) of a bump counter for every ACTIVE lane of the wave, with ONE atomic: the lanes are served value by value (the
 // lanes of a call site mostly ask for the same n: one round), a lane's offset = what the rounds before it and the lanes below
 // it in its own round take.  By hand, because LLVM's atomic optimizer in its DPP strategy -- which does the same with a wave

@@ -28,10 +28,6 @@ struct BlurTaps { float w[kTapSlots]; };           // by value in the kernel arg
 constexpr uint32_t kRowSeg = 256;                  // k_blur_rows: output texels of a wave's row segment (64 lanes x 4)
 constexpr uint32_t kColStrip = 128, kColRows = 8;  // k_blur_cols: a wave's item is 128 columns (64 lanes x 2) x 8 output rows
 
-JD float4 texel_f32(uint2 t) {
-    return make_float4(jd::f16_to_f32((uint16_t)(t.x & 0xffffu)), jd::f16_to_f32((uint16_t)(t.x >> 16)), jd::f16_to_f32((uint16_t)(t.y & 0xffffu)),
-                       jd::f16_to_f32((uint16_t)(t.y >> 16)));
-}
 JD uint2 texel_f16(const float4& v) {  // round to nearest even, subnormals kept (the default float mode)
     return make_uint2((uint32_t)jd::f32_to_f16(v.x) | ((uint32_t)jd::f32_to_f16(v.y) << 16), (uint32_t)jd::f32_to_f16(v.z) | ((uint32_t)jd::f32_to_f16(v.w) << 16));
 }
@@ -50,7 +46,7 @@ JD float4 staged_texel(const uint2* srow, int64_t x, uint32_t W) {
         if (!CLAMP) return make_float4(-0.0f, -0.0f, -0.0f, -0.0f);
         x = x < 0 ? 0 : (int64_t)W - 1;
     }
-    return srow ? texel_f32(srow[x]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return srow ? jd::rgba16f_to_f32(srow[x]) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // Rows [row0, row0 + n_rows) of the image, columns [x0, x0 + rw): H into tmp (n_rows x rw float4).  An item = one row segment of up
@@ -82,8 +78,8 @@ __global__ __launch_bounds__(kBlurThreads) void k_blur_rows(const uint2* __restr
             float4 a, b;
             if (pair_aligned && xa >= 0 && xa + 1 < (int64_t)W) {
                 const uint4 q = *(const uint4*)(srow + xa);
-                a = texel_f32(make_uint2(q.x, q.y));
-                b = texel_f32(make_uint2(q.z, q.w));
+                a = jd::rgba16f_to_f32(make_uint2(q.x, q.y));
+                b = jd::rgba16f_to_f32(make_uint2(q.z, q.w));
             } else {
                 a = staged_texel<CLAMP>(srow, xa, W);
                 b = staged_texel<CLAMP>(srow, xa + 1, W);

@@ -47,50 +47,18 @@ JD Box box_meet(Box a, Box b) { return Box{fmax_(a.x0, b.x0), fmax_(a.y0, b.y0),
 JD Box box_everything() { return Box{-1e9f, -1e9f, 1e9f, 1e9f}; }
 JD Box box_of_path(const JlPathBbox& pb) { return Box{(float)pb.x0, (float)pb.y0, (float)pb.x1, (float)pb.y1}; }
 
-// ---- wave64 scans on the DPP path (row_shr 1/2/4/8, row_bcast 15/31); lanes without a source keep their own value ----
-#define CLIP_DPP(old, v, ctrl, rows) __builtin_amdgcn_update_dpp((int)(old), (int)(v), ctrl, rows, 0xf, false)
-#define CLIP_SCAN_STEPS(STEP)       \
-    STEP(JK_DPP_ROW_SHR(1), 0xf)    \
-    STEP(JK_DPP_ROW_SHR(2), 0xf)    \
-    STEP(JK_DPP_ROW_SHR(4), 0xf)    \
-    STEP(JK_DPP_ROW_SHR(8), 0xf)    \
-    STEP(JK_DPP_ROW_BCAST15, 0xa)   \
-    STEP(JK_DPP_ROW_BCAST31, 0xc)
-
-JD int32_t wave_running_min(int32_t v) {
-#define STEP(ctrl, rows) v = imin_(v, CLIP_DPP(v, v, ctrl, rows));
-    CLIP_SCAN_STEPS(STEP)
-#undef STEP
-    return v;
-}
-JD int32_t wave_running_max(int32_t v) {
-#define STEP(ctrl, rows) v = imax_(v, CLIP_DPP(v, v, ctrl, rows));
-    CLIP_SCAN_STEPS(STEP)
-#undef STEP
-    return v;
-}
+// ---- wave64 scans (kwave.h); in the running min / max and the box meet lanes without a source keep their own value ----
+JD int32_t wave_running_min(int32_t v) { return wave_incl_scan_self(v, [](int32_t a, int32_t b) { return imin_(a, b); }); }
+JD int32_t wave_running_max(int32_t v) { return wave_incl_scan_self(v, [](int32_t a, int32_t b) { return imax_(a, b); }); }
 // Inclusive join over lanes 0..own, the own lane's stretch IN FRONT of the lower lanes' (the caller lays the stream out against
 // the lanes).  Lanes without a source receive the neutral element (0, 0).
-JD Nest wave_nest_scan(Nest v) {
-#define STEP(ctrl, rows) v = nest_join(v, Nest{(uint32_t)CLIP_DPP(0, v.closes, ctrl, rows), (uint32_t)CLIP_DPP(0, v.opens, ctrl, rows)});
-    CLIP_SCAN_STEPS(STEP)
-#undef STEP
-    return v;
-}
-#define CLIP_DPP_F(v, ctrl, rows) __int_as_float(CLIP_DPP(__float_as_int(v), __float_as_int(v), ctrl, rows))
-JD Box wave_box_scan(Box v) {
-#define STEP(ctrl, rows) \
-    v = box_meet(v, Box{CLIP_DPP_F(v.x0, ctrl, rows), CLIP_DPP_F(v.y0, ctrl, rows), CLIP_DPP_F(v.x1, ctrl, rows), CLIP_DPP_F(v.y1, ctrl, rows)});
-    CLIP_SCAN_STEPS(STEP)
-#undef STEP
-    return v;
-}
+JD Nest wave_nest_scan(Nest v) { return wave_incl_scan(v, Nest{0u, 0u}, [](Nest x, Nest y) { return nest_join(x, y); }); }
+JD Box wave_box_scan(Box v) { return wave_incl_scan_self(v, [](Box a, Box b) { return box_meet(a, b); }); }
 JD Nest lane_below(Nest v) {  // the value of lane - 1; lane 0 receives the neutral element
     Nest r{(uint32_t)__shfl_up((int)v.closes, 1, 64), (uint32_t)__shfl_up((int)v.opens, 1, 64)};
     if (lane_id() == 0u) r = Nest{0u, 0u};
     return r;
 }
-JD Nest nest_of_lane(Nest v, int lane) { return Nest{(uint32_t)__builtin_amdgcn_readlane((int)v.closes, lane), (uint32_t)__builtin_amdgcn_readlane((int)v.opens, lane)}; }
 
 constexpr uint32_t BLOCK = 256u;  // records per nesting summary (the reference's workgroup: the layout of `reduced` / `clip_els`)
 constexpr uint32_t RUN = 64u;     // records per wave

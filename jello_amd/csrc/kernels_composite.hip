@@ -35,8 +35,8 @@ struct CompositeParams {  // by value in the kernel arguments
 };
 
 JD V4 comp_f32(uint2 t) {
-    return v4(jd::f16_to_f32((uint16_t)(t.x & 0xffffu)), jd::f16_to_f32((uint16_t)(t.x >> 16)), jd::f16_to_f32((uint16_t)(t.y & 0xffffu)),
-              jd::f16_to_f32((uint16_t)(t.y >> 16)));
+    const float4 c = jd::rgba16f_to_f32(t);
+    return v4(c.x, c.y, c.z, c.w);
 }
 
 template <bool FAST>

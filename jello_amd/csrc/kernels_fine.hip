@@ -46,7 +46,7 @@ __device__ __attribute__((noinline)) V4 blend_mix_compose(V4 backdrop, V4 src, u
     // of blend_rule became trees of v_cmp / s_and_saveexec / s_cbranch_execz -- ~25 vector + scalar instructions per call in front of the
     // arithmetic (round 6: nested C4 spends 55 % of its fine kernel in here, 85 calls x 4 pixels per tile).  As a scalar the switches
     // are compare-and-branch on the scalar pipe.
-    mode = (uint32_t)__builtin_amdgcn_readfirstlane((int)mode);
+    mode = uni(mode);
     return blend_rule(backdrop, src, mode);
 }
 
@@ -283,7 +283,6 @@ template <int SAMPLES> struct MsLds {
 };
 JD uint32_t shl32(uint32_t v, uint32_t s) { return v << (s & 31u); }
 JD uint32_t shr32(uint32_t v, uint32_t s) { return v >> (s & 31u); }
-JD uint32_t ms_span(float a, float b) { return to_u32(fmax_(ceil_(fmax_(a, b)) - floor_(fmin_(a, b)), 1.0f)); }
 
 // lane = segment (or every lane the same segment: ms_direct): fine.wgsl:180-203 / :237-262.  Returns the number of touched pixels;
 // `edge` = the left-edge term: row | 16 if it counts upwards | 32 if there is one.
@@ -291,7 +290,7 @@ template <int SAMPLES>
 JD uint32_t ms_setup(float x0, float y0, float x1, float y1, MsSeg& K, uint32_t& edge) {
     const float LUT_W = SAMPLES == 8 ? 32.0f : 64.0f, HALF_H = SAMPLES == 8 ? 16.0f : 32.0f;
     uint32_t touched = 0u;
-    if (!(y0 == y1 && y0 == floor_(y0))) touched = ms_span(x0, x1) + ms_span(y0, y1) - 1u;  // (a horizontal line on the pixel grid touches nothing)
+    if (!(y0 == y1 && y0 == floor_(y0))) touched = cell_span(x0, x1) + cell_span(y0, y1) - 1u;  // (a horizontal line on the pixel grid touches nothing)
     float edge_y = 16.0f;
     if (x0 == 0.0f) edge_y = y0;
     else if (x1 == 0.0f) edge_y = y1;
@@ -308,8 +307,8 @@ JD uint32_t ms_setup(float x0, float y0, float x1, float y1, MsSeg& K, uint32_t&
     const float frac = tx * sgn - xt;
     const float row0 = floor_(ty);
     const float b = fmin_((dy * frac + dx * ((row0 + 1.0f) - ty)) * inv, 0.99999994f);
-    const uint32_t cols = ms_span(tx, bx) - 1u;
-    const uint32_t steps = cols + ms_span(ty, by);
+    const uint32_t cols = cell_span(tx, bx) - 1u;
+    const uint32_t steps = cols + cell_span(ty, by);
     const float err = floor_(a * ((float)steps - 1.0f) + b) - (float)cols;
     if (err != 0.0f) a -= 2e-7f * sign_(err);
     K.a = a; K.b = b;
@@ -613,9 +612,7 @@ JD void ms_fill(MsLds<SAMPLES>& T, MsState& B, uint32_t lane, uint32_t size_and_
     wx += (wx - 0x8080u) << 16;
     {
         const uint32_t tot = ((wx >> 24) - 0x80u) * 0x1010101u;
-        const uint32_t t1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tot, JK_DPP_ROW_SHR(1), 0xf, 0xf, false);
-        const uint32_t t2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tot, JK_DPP_ROW_SHR(2), 0xf, 0xf, false);
-        const uint32_t t3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)tot, JK_DPP_ROW_SHR(3), 0xf, 0xf, false);
+        const uint32_t t1 = row_prev<1>(tot, 0u), t2 = row_prev<2>(tot, 0u), t3 = row_prev<3>(tot, 0u);
         wx += (lx >= 1u ? t1 : 0u) + (lx >= 2u ? t2 : 0u) + (lx >= 3u ? t3 : 0u);
     }
     // y: the same on the four uniform words; a row's value = its byte of its word's running sum + the totals of the words above
@@ -772,8 +769,8 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
         if (x < 0 || x >= JL_GRADIENT_WIDTH || y >= grad_h) return v4(0, 0, 0, 0);
         const uint16_t* t = gradients + ((size_t)y * JL_GRADIENT_WIDTH + (size_t)x) * 4;
         uint2 raw = *(const uint2*)t;
-        return v4(f16_to_f32((uint16_t)(raw.x & 0xffffu)), f16_to_f32((uint16_t)(raw.x >> 16)), f16_to_f32((uint16_t)(raw.y & 0xffffu)),
-                  f16_to_f32((uint16_t)(raw.y >> 16)));
+        const float4 c = rgba16f_to_f32(raw);
+        return v4(c.x, c.y, c.z, c.w);
     };
     auto pix_i = [&](int k) -> float { return (float)k; };
     auto pix_spill = [&](int k) -> uint32_t { return ly * JL_TILE_WIDTH + lx * 4u + (uint32_t)k; };
@@ -922,11 +919,8 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
         const uint64_t rm_pair = F.rowmask[row];
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rm_pair >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm_pair, 0u));
         const uint32_t c16 = (uint32_t)__builtin_popcountll(F.rowmask[lane & 15u]);
-        uint32_t inc16 = c16;  // inclusive prefix inside each 16-lane DPP row (every row of lanes holds the 16 pixel rows)
-        inc16 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc16, JK_DPP_ROW_SHR(1), 0xf, 0xf, false);
-        inc16 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc16, JK_DPP_ROW_SHR(2), 0xf, 0xf, false);
-        inc16 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc16, JK_DPP_ROW_SHR(4), 0xf, 0xf, false);
-        inc16 += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc16, JK_DPP_ROW_SHR(8), 0xf, 0xf, false);
+        // inclusive prefix inside each 16-lane DPP row (every row of lanes holds the 16 pixel rows)
+        const uint32_t inc16 = row_incl_scan(c16, 0u, [](uint32_t a, uint32_t b) { return a + b; });
         const uint32_t excl16 = inc16 - c16;
         const uint32_t pos = (__shfl(excl16, (int)row, 64) + rank) & 63u;
         if constexpr (CLIPS) {
@@ -1327,8 +1321,7 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
                         {
                             const uint32_t wo = pc - wbase;  // <= 64 - FINE_TRIP_WORDS
                             const uint32_t w0 = wcur;
-                            const uint32_t w1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w0, 0x138, 0xf, 0xf, false);  // wave_shr:1: word k - 1
-                            const uint32_t w2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w1, 0x138, 0xf, 0xf, false);  // word k - 2
+                            const uint32_t w1 = lane_prev(w0, 0u), w2 = lane_prev(w1, 0u);  // words k - 1, k - 2
                             const bool in = lane >= wo;
                             const bool tag0 = (w0 == JL_CMD_BEGIN_CLIP) | (w0 == JL_CMD_SOLID) | (w0 == JL_CMD_END_CLIP);
                             const bool is_blend = (lane >= wo + 1u) & (w1 == JL_CMD_END_CLIP);

@@ -369,11 +369,6 @@ struct Scene {
 // record.  Every point is computed once, with the same operations on the same values as in the sequential
 // formulation, hence the same bits.  Lines emitted directly (caps, joins) wait in records of their own and are copied.
 // ------------------------------------------------------------------------------------------------
-JD void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // piece record: one 64-byte sector, 4 x uint4 at recs[4 * r]:
 //   0: es_p0.x es_p0.y es_p1.x es_p1.y   1: th0 th1 int0 integral   2: noff item path_ix trans_ix<<6|flags
 //   3: (first piece of its item ? t_start.x : index of the piece's first line in the item) t_start.y t_end.x t_end.y
@@ -995,10 +990,6 @@ struct FlBatch {
                                        // after phase B: [job] = lines of the batch's jobs before it
     uint32_t n_stack, n_leaves, bail, n_unsure;
 };
-// The job state (control points, scale, offset, ids) stays in the registers of the lane that set the job up; the lane
-// that evaluates one of its nodes fetches it with ds_bpermute (no LDS storage: occupancy is bound by registers only).
-JD float lanef(float v, uint32_t src) { return u2f((uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)f2u(v))); }
-JD uint32_t laneu(uint32_t v, uint32_t src) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v); }
 
 struct NodeResult {
     bool accept;
@@ -1215,7 +1206,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
     for (;;) {
         uint32_t k = 0u;
         if (lane == 0u) k = atomicAdd(&counters[FL_CTR_DEAL + FL_DEAL_STRIDE * group], 1u);
-        k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+        k = uni(k);
         const uint32_t u = k * n_groups + group;
         if (u >= units) break;
         const bool heavy = u < units_h;  // uniform
@@ -1267,10 +1258,10 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             if (active) B.stack[(uint32_t)__builtin_popcountll(am & ((1ull << lane) - 1ull))] = lane;  // root: level 0, t0_u 0
             if (lane == 0u) { B.n_stack = (uint32_t)__builtin_popcountll(am); B.n_leaves = 0u; B.bail = 0u; B.n_unsure = 0u; }
         }
-        wave_fence();
+        wave_sync();
 #ifdef FL_SPLIT_NO_A  // (measurement builds only, tools/flatten_split.sh: the kernel without its subdivision -- results are wrong)
         if (lane == 0u) B.n_stack = 0u;
-        wave_fence();
+        wave_sync();
 #endif
         // ---- phase A: drain the stack -- DECISIONS only.  A node is accepted, rejected (its halves are pushed) or left
         // undecided by the transcendental-free test (flatten_fast.h; ~0.1 % of the nodes); the undecided ones wait in a list of
@@ -1279,19 +1270,21 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
 #ifdef FL_TIMING
             tl_info += 1u << 16;
 #endif
-            const uint32_t ns = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_stack);
+            const uint32_t ns = uni(B.n_stack);
+            // (the builtin, not uni(): through the helper the compiler allocates this kernel's registers differently -- other spills, other code)
             const uint32_t nu = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_unsure);
             if (ns == 0u && nu == 0u) break;
             const bool exact_round = ns == 0u || nu >= 64u;  // uniform
             const uint32_t take = umin_(exact_round ? nu : ns, 64u);
             const bool has = lane < take;
             const uint32_t node = has ? (exact_round ? B.unsure[nu - 1u - lane] : B.stack[ns - 1u - lane]) : 0u;
-            wave_fence();
+            wave_sync();
             const uint32_t j = node & 63u, level = (node >> 6) & 31u, t0_u = node >> 11;
-            // the job's state from its owner lane (every lane takes part in the permutes)
-            const V2 jp0 = v2(lanef(e.p0.x, j), lanef(e.p0.y, j)), jp1 = v2(lanef(e.p1.x, j), lanef(e.p1.y, j));
-            const V2 jp2 = v2(lanef(e.p2.x, j), lanef(e.p2.y, j)), jp3 = v2(lanef(e.p3.x, j), lanef(e.p3.y, j));
-            const float scale = lanef(e.scale, j);
+            // the job's state (control points, scale, offset, ids) stays in the registers of the lane that set the job up -- no LDS
+            // storage: occupancy is bound by registers only -- and is fetched from there (every lane takes part in the permutes)
+            const V2 jp0 = v2(read_lane_var(e.p0.x, j), read_lane_var(e.p0.y, j)), jp1 = v2(read_lane_var(e.p1.x, j), read_lane_var(e.p1.y, j));
+            const V2 jp2 = v2(read_lane_var(e.p2.x, j), read_lane_var(e.p2.y, j)), jp3 = v2(read_lane_var(e.p3.x, j), read_lane_var(e.p3.y, j));
+            const float scale = read_lane_var(e.scale, j);
             int kind = ffast::FF_UNSURE;
             if (exact_round) {
                 if (has) kind = node_test(jp0, jp1, jp2, jp3, scale, level, t0_u).accept ? ffast::FF_ACCEPT : ffast::FF_REJECT;
@@ -1327,12 +1320,12 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             const uint64_t accm = __builtin_amdgcn_ballot_w64(acc), rejm = __builtin_amdgcn_ballot_w64(rej), unsm = __builtin_amdgcn_ballot_w64(uns);
             const uint32_t n_acc = (uint32_t)__builtin_popcountll(accm), n_rej = (uint32_t)__builtin_popcountll(rejm);
             const uint32_t n_uns = (uint32_t)__builtin_popcountll(unsm);
-            const uint32_t nl = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_leaves);
+            const uint32_t nl = uni(B.n_leaves);
             const uint32_t ns_left = exact_round ? ns : ns - take, nu_left = exact_round ? nu - take : nu;
             const bool too_deep = __builtin_amdgcn_ballot_w64(rej && level + 1u > FLQ_MAX_LEVEL) != 0ull;
             if (too_deep || ns_left + 2u * n_rej > FLQ_STACK || nl + n_acc > FLQ_LEAVES) {  // uniform: give up on the unfinished jobs
                 if (lane == 0u) B.bail = 1u;
-                wave_fence();
+                wave_sync();
                 break;
             }
             const uint64_t below = (1ull << lane) - 1ull;
@@ -1350,14 +1343,14 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             }
             if (uns) B.unsure[nu_left + (uint32_t)__builtin_popcountll(unsm & below)] = node;  // (nu_left < 64 in a fast round)
             if (lane == 0u) { B.n_stack = ns_left + 2u * n_rej; B.n_leaves = nl + n_acc; B.n_unsure = nu_left + n_uns; }
-            wave_fence();
+            wave_sync();
         }
         // ---- phase B: the pieces, 64 at a time whichever jobs they belong to: the pinned angles (two atan2), the Euler
         // parameters and the line count (flatten.wgsl:404-447), the record.  The records of a batch are one dense range in the
         // order of the piece list (one returning atomic per batch; its round trip passes under the first pass's arithmetic).
         // A batch that gave up (bail) leaves no pieces: all its jobs take the sequential walk below. ----
-        const bool bail = (uint32_t)__builtin_amdgcn_readfirstlane((int)B.bail) != 0u;
-        const uint32_t nl = bail ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)B.n_leaves);
+        const bool bail = uni(B.bail) != 0u;
+        const uint32_t nl = bail ? 0u : uni(B.n_leaves);
 #ifdef FL_TIMING
         tl_info = (tl_info & 0x7fff0000u) | (nl & 0xffffu) | (bail ? 1u << 31 : 0u);
 #endif
@@ -1373,12 +1366,12 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             const bool has = li < nl;
             const uint32_t node = has ? B.l_tpos[li] : 0u;
             const uint32_t j = node & 63u, level = (node >> 6) & 31u, t0_u = node >> 11;
-            const V2 jp0 = v2(lanef(e.p0.x, j), lanef(e.p0.y, j)), jp1 = v2(lanef(e.p1.x, j), lanef(e.p1.y, j));
-            const V2 jp2 = v2(lanef(e.p2.x, j), lanef(e.p2.y, j)), jp3 = v2(lanef(e.p3.x, j), lanef(e.p3.y, j));
-            const float scale = lanef(e.scale, j), offset = lanef(e.offset, j);
+            const V2 jp0 = v2(read_lane_var(e.p0.x, j), read_lane_var(e.p0.y, j)), jp1 = v2(read_lane_var(e.p1.x, j), read_lane_var(e.p1.y, j));
+            const V2 jp2 = v2(read_lane_var(e.p2.x, j), read_lane_var(e.p2.y, j)), jp3 = v2(read_lane_var(e.p3.x, j), read_lane_var(e.p3.y, j));
+            const float scale = read_lane_var(e.scale, j), offset = read_lane_var(e.offset, j);
             // a piece needs the ids of its job and, if it is the item's first or last, the item's end points
-            const uint32_t j_slot = laneu(slot, j), j_path = laneu(e.path_ix, j), j_trans = laneu(e.trans_ix, j);
-            const float j_tsx = lanef(e.t_start.x, j), j_tsy = lanef(e.t_start.y, j), j_tex = lanef(e.t_end.x, j), j_tey = lanef(e.t_end.y, j);
+            const uint32_t j_slot = read_lane_var(slot, j), j_path = read_lane_var(e.path_ix, j), j_trans = read_lane_var(e.trans_ix, j);
+            const float j_tsx = read_lane_var(e.t_start.x, j), j_tsy = read_lane_var(e.t_start.y, j), j_tex = read_lane_var(e.t_end.x, j), j_tey = read_lane_var(e.t_end.y, j);
             if (has) {
                 const NodeEnds ne = node_ends(jp0, jp1, jp2, jp3, level, t0_u);
                 const CubicParams cp = piece_angles(ne);
@@ -1392,7 +1385,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
                 B.l_key[li] = (uint16_t)(B.l_key[li] | pp.n_u);
             }
         }
-        wave_fence();
+        wave_sync();
         if (nl != 0u) {  // uniform
             // ---- the lines of a job; the slots of the batch: ONE range (one returning atomic), the jobs in lane order ----
             uint32_t total = 0u;
@@ -1423,7 +1416,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
                 const uint32_t base0 = (uint32_t)__builtin_amdgcn_readlane((int)grab, 0);
                 B.unsure[lane] = together ? (base0 == FL_INVALID ? FL_INVALID : base0 + (incl - total)) : grab;
             }
-            wave_fence();
+            wave_sync();
             // ---- the slots: in the canonical order of the batch's lines (job, piece, line), so that k_flatten_lines reads
             // consecutive slots and writes consecutive lines ----
             for (uint32_t li = lane; li < nl; li += 64u) {
@@ -1434,7 +1427,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
                 if (rec_base != FL_INVALID) piece_slots_write(T.sinfo, jb + first, key & 127u, r);
                 else for (uint32_t i = 0u; i < (key & 127u); i++) T.sinfo[jb + first + i] = make_uint2(0u, 0u);  // (slots without a record: empty)
             }
-            wave_fence();
+            wave_sync();
         }
         if (__builtin_expect(bail, 0)) {  // uniform, rare: the sequential walk for all jobs of the batch
             o.slot = slot; o.cursor = 0u; o.a_first = 0u; o.a_spos = 0u; o.a_rpos = 0u;
@@ -1740,32 +1733,28 @@ __global__ __launch_bounds__(JL_WG) void k_flatten_bbox(const JlConfig* __restri
                 if (counts) { x0 = to_i32(floor_(lx0)); y0 = to_i32(floor_(ly0)); x1 = to_i32(ceil_(lx1)); y1 = to_i32(ceil_(ly1)); }
             }
             // a carried segment that does not continue in this batch is complete
-            const uint32_t p_lane0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)pix);
+            const uint32_t p_lane0 = uni(pix);
             if (c_path != FB_NONE && c_path != p_lane0) {
                 if (lane == 0u) fb_merge(path_bboxes, c_path, cx0, cy0, cx1, cy1, c_path == p_shared);
                 c_path = FB_NONE;
             }
-#define FB_SEG_STEP(CTRL, ROWS)                                                                                        \
-    {                                                                                                                  \
-        const bool take = (uint32_t)__builtin_amdgcn_update_dpp((int)~pix, (int)pix, CTRL, ROWS, 0xf, false) == pix;   \
-        const int32_t a = imin_(x0, __builtin_amdgcn_update_dpp(x0, x0, CTRL, ROWS, 0xf, false));                      \
-        const int32_t b = imin_(y0, __builtin_amdgcn_update_dpp(y0, y0, CTRL, ROWS, 0xf, false));                      \
-        const int32_t c = imax_(x1, __builtin_amdgcn_update_dpp(x1, x1, CTRL, ROWS, 0xf, false));                      \
-        const int32_t d = imax_(y1, __builtin_amdgcn_update_dpp(y1, y1, CTRL, ROWS, 0xf, false));                      \
-        if (take) { x0 = a; y0 = b; x1 = c; y1 = d; }                                                                   \
+            // One step of the segmented min / max scan: the bounds of the lane below are folded in iff it is on the same path (a lane
+            // without a source sees ~pix there, which never matches).  Written out, not a functor for wave_scan_steps: through one the
+            // compiler orders the min / max of a step differently, and this kernel is held to the code that was measured.
+#define FB_SEG_STEP(CTRL, ROWS)                                                             \
+    {                                                                                       \
+        const bool take = dpp_move<CTRL, ROWS>(~pix, pix) == pix;                           \
+        const int32_t a = imin_(x0, dpp_move<CTRL, ROWS>(x0, x0)), b = imin_(y0, dpp_move<CTRL, ROWS>(y0, y0)); \
+        const int32_t c = imax_(x1, dpp_move<CTRL, ROWS>(x1, x1)), d = imax_(y1, dpp_move<CTRL, ROWS>(y1, y1)); \
+        if (take) { x0 = a; y0 = b; x1 = c; y1 = d; }                                        \
     }
-            FB_SEG_STEP(JK_DPP_ROW_SHR(1), 0xf)
-            FB_SEG_STEP(JK_DPP_ROW_SHR(2), 0xf)
-            FB_SEG_STEP(JK_DPP_ROW_SHR(4), 0xf)
-            FB_SEG_STEP(JK_DPP_ROW_SHR(8), 0xf)
-            FB_SEG_STEP(JK_DPP_ROW_BCAST15, 0xa)
-            FB_SEG_STEP(JK_DPP_ROW_BCAST31, 0xc)
+            FB_SEG_STEP(JK_DPP_ROW_SHR(1), 0xf) FB_SEG_STEP(JK_DPP_ROW_SHR(2), 0xf) FB_SEG_STEP(JK_DPP_ROW_SHR(4), 0xf)
+            FB_SEG_STEP(JK_DPP_ROW_SHR(8), 0xf) FB_SEG_STEP(JK_DPP_ROW_BCAST15, 0xa) FB_SEG_STEP(JK_DPP_ROW_BCAST31, 0xc)
 #undef FB_SEG_STEP
             if (pix == c_path) {  // (only the values of the segment's last lane are used)
                 x0 = imin_(x0, cx0); y0 = imin_(y0, cy0); x1 = imax_(x1, cx1); y1 = imax_(y1, cy1);
             }
-            // lane i reads the path of lane i + 1 (wave_shl:1); lane 63 has no source: its segment stays open
-            const uint32_t pix_next = (uint32_t)__builtin_amdgcn_update_dpp((int)pix, (int)pix, 0x130, 0xf, 0xf, false);
+            const uint32_t pix_next = lane_next(pix, pix);  // lane 63 has no source: its segment stays open
             if (valid && !skipped && pix_next != pix) fb_merge(path_bboxes, pix, x0, y0, x1, y1, pix == p_shared);
             c_path = (uint32_t)__builtin_amdgcn_readlane((int)pix, 63);
             cx0 = __builtin_amdgcn_readlane(x0, 63); cy0 = __builtin_amdgcn_readlane(y0, 63);

@@ -56,9 +56,6 @@ struct Quad {
     T v[4];
 };
 
-JD uint32_t bcast_first(uint32_t v) { return jk::uni(v); }
-JD uint64_t bcast_first(uint64_t v) { return (uint64_t)jk::uni((uint32_t)v) | ((uint64_t)jk::uni((uint32_t)(v >> 32)) << 32); }
-
 // four texels at p: one or two 16-B loads when `vec` (p is then 16-B aligned), else texel by texel; only the first n are read,
 // the others are zero
 template <typename T>
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(JL_WG) void k_pack_classify(const PackArgs a) {
 #pragma unroll
             for (uint32_t k = 0; k < 4u; k++) same_as_ref = same_as_ref && (k >= p.n || q.v[k] == r.v[k]);
         }
-        const T first = bcast_first(q.v[0]);  // lane 0 holds the tile's texel (0, 0), which is always inside the frame
+        const T first = jk::uni(q.v[0]);  // lane 0 holds the tile's texel (0, 0), which is always inside the frame
         bool same_as_first = true;
 #pragma unroll
         for (uint32_t k = 0; k < 4u; k++) same_as_first = same_as_first && (k >= p.n || q.v[k] == first);

@@ -256,7 +256,6 @@ __global__ void k_path_tiling_setup(const JlBump* __restrict__ bump, JlIndirectC
 // ------------------------------------------------------------------------------------------------
 // path_count
 // ------------------------------------------------------------------------------------------------
-JD uint32_t span(float a, float b) { return to_u32(fmax_(ceil_(fmax_(a, b)) - floor_(fmin_(a, b)), 1.0f)); }
 #define ONE_MINUS_ULP 0.99999994f
 #define ROBUST_EPSILON 2e-7f
 #define TILE_SCALE 0.0625f
@@ -282,8 +281,8 @@ JD LineSetup line_setup(const JlLineSoup& line, const Buf<JlPath>& paths) {
     V2 xy1 = is_down ? lp1 : lp0;
     V2 s0 = xy0 * TILE_SCALE;
     V2 s1 = xy1 * TILE_SCALE;
-    uint32_t count_x = span(s0.x, s1.x) - 1u;
-    uint32_t count = count_x + span(s0.y, s1.y);
+    uint32_t count_x = cell_span(s0.x, s1.x) - 1u;
+    uint32_t count = count_x + cell_span(s0.y, s1.y);
     float dx = abs_(s1.x - s0.x);
     float dy = s1.y - s0.y;
     if (dx + dy == 0.0f) return r;
@@ -399,7 +398,7 @@ __global__ __launch_bounds__(JL_WG) void k_pc_count(const JlBump* __restrict__ b
         // sends ONE atomic.  (Round 5: the sums used to be derived from first / last line of every path by a launch of its own,
         // k_pc_paths, behind the scan; the ranges it also produced are written by k_pc_emit in passing now.)
         const uint32_t incl = wave_incl_scan_u32(c);
-        const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)~pix, (int)pix, 0x138, 0xf, 0xf, false);  // wave_shr:1 (lane 0: a head)
+        const uint32_t prev = lane_prev(pix, ~pix);  // (lane 0: a head)
         const uint64_t heads = __builtin_amdgcn_ballot_w64(lane == 0u || pix != prev);
         const uint32_t leader = 63u - (uint32_t)__builtin_clzll(heads & ((2ull << lane) - 1ull));  // nearest head at or before the lane
         const uint32_t lead_incl = (uint32_t)__shfl((int)incl, (int)leader, 64), lead_c = (uint32_t)__shfl((int)c, (int)leader, 64);
@@ -427,7 +426,6 @@ JD void path_range(uint32_t P, const uint32_t* __restrict__ pstart, const uint32
 #define PC_BIG_PATH 64u  // (tools/sweep_pc.sh builds other values)
 #endif
 JD bool npe_big(uint32_t n) { return n > PC_BIG_PATH; }
-JD uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // pass 2: backdrops, SegmentCount records, the tile of every crossing (slice ranks are filled in later).
 // path_count.wgsl:168-199 is one thread per line walking the line's crossings; the walk only depends on the crossing
@@ -492,9 +490,6 @@ JD void emit_crossing(const EmitCtx& c, const LineSetup& s, uint32_t i, uint32_t
         }
     }
 }
-JD float rl_f(float v, uint32_t src) { return u2f((uint32_t)__builtin_amdgcn_readlane((int)f2u(v), (int)src)); }
-JD int32_t rl_i(int32_t v, uint32_t src) { return __builtin_amdgcn_readlane(v, (int)src); }
-JD uint32_t rl_u(uint32_t v, uint32_t src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)src); }
 
 __global__ __launch_bounds__(JL_WG) void k_pc_emit(const JlConfig* __restrict__ cfg, const JlBump* __restrict__ bump,
                                                    const JlIndirectCount* __restrict__ ind, Buf<JlLineSoup> lines, Buf<JlPath> paths, Buf<JlTile> tile,
@@ -531,8 +526,7 @@ __global__ __launch_bounds__(JL_WG) void k_pc_emit(const JlConfig* __restrict__ 
             s.imin = 0u; s.imax = 0u; s.ymin = 0; s.ymax = 0;
         }
         {   // the path's crossing range, written at its first and its last line (the neighbours: a lane over, or the line next door)
-            uint32_t prevP = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)P, 0x138, 0xf, 0xf, false);  // wave_shr:1
-            uint32_t nextP = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)P, 0x130, 0xf, 0xf, false);  // wave_shl:1
+            uint32_t prevP = lane_prev(P, 0u), nextP = lane_next(P, 0u);
             if (lane == 0u) prevP = edgeP;
             if (lane == 63u) nextP = edgeP;
             if (gid < n_lines && P < n_paths) {
@@ -584,14 +578,14 @@ __global__ __launch_bounds__(JL_WG) void k_pc_emit(const JlConfig* __restrict__ 
             m &= m - 1ull;
             LineSetup t;
             t.valid = true; t.is_down = false; t.is_positive_slope = false;
-            t.a = rl_f(s.a, src); t.b = rl_f(s.b, src); t.x0 = rl_f(s.x0, src); t.y0 = rl_f(s.y0, src);
-            t.x_sign = rl_f(s.x_sign, src); t.s0y = rl_f(s.s0y, src);
-            t.imin = rl_u(s.imin, src); t.imax = rl_u(s.imax, src);
-            t.ymin = rl_i(s.ymin, src); t.ymax = rl_i(s.ymax, src); t.delta = rl_i(s.delta, src);
-            t.bbox[0] = rl_i(s.bbox[0], src); t.bbox[1] = rl_i(s.bbox[1], src); t.bbox[2] = rl_i(s.bbox[2], src); t.bbox[3] = rl_i(s.bbox[3], src);
-            t.stride = rl_i(s.stride, src); t.tiles = rl_u(s.tiles, src);
-            const uint32_t t_gid = g0 + src, t_seg_base = rl_u(seg_base, src);
-            const bool t_big = rl_u(big ? 1u : 0u, src) != 0u;
+            t.a = read_lane(s.a, src); t.b = read_lane(s.b, src); t.x0 = read_lane(s.x0, src); t.y0 = read_lane(s.y0, src);
+            t.x_sign = read_lane(s.x_sign, src); t.s0y = read_lane(s.s0y, src);
+            t.imin = read_lane(s.imin, src); t.imax = read_lane(s.imax, src);
+            t.ymin = read_lane(s.ymin, src); t.ymax = read_lane(s.ymax, src); t.delta = read_lane(s.delta, src);
+            t.bbox[0] = read_lane(s.bbox[0], src); t.bbox[1] = read_lane(s.bbox[1], src); t.bbox[2] = read_lane(s.bbox[2], src); t.bbox[3] = read_lane(s.bbox[3], src);
+            t.stride = read_lane(s.stride, src); t.tiles = read_lane(s.tiles, src);
+            const uint32_t t_gid = g0 + src, t_seg_base = read_lane(seg_base, src);
+            const bool t_big = read_lane(big ? 1u : 0u, src) != 0u;
             for (int32_t y = t.ymin + (int32_t)lane; y < t.ymax; y += 64) emit_backdrop_row(c, t, y);
             for (uint32_t i = t.imin + lane; i < t.imax; i += 64u) emit_crossing<false>(c, t, i, t_gid, t_seg_base, t_big, dummy_t, dummy_ix);
         }
@@ -757,7 +751,7 @@ JD void pc_scatter_part(const JlConfig* __restrict__ cfg, const JlBump* __restri
         if (m != 0ull) {  // one atomic per wave
             uint32_t at = 0u;
             if (lane == 0u) at = atomicAdd(&gate[1], (uint32_t)__builtin_popcountll(m));
-            at = uni32(at) + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            at = uni(at) + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             if (first_of_dense && at < dense_cap) dense[at] = t;
         }
     }
@@ -794,11 +788,11 @@ __global__ __launch_bounds__(JL_WG) void k_pc_rank(const JlConfig* __restrict__ 
     uint32_t* my_list = sh_list[wv];
     const uint32_t n_dense = umin_(gate[1], dense_cap);
     const uint32_t waves = (gridDim.x * JL_WG) >> 6;
-    for (uint32_t d = uni32((blockIdx.x * JL_WG + threadIdx.x) >> 6); d < n_dense; d += waves) {
-        const uint32_t t = uni32(dense[d]);
+    for (uint32_t d = uni((blockIdx.x * JL_WG + threadIdx.x) >> 6); d < n_dense; d += waves) {
+        const uint32_t t = uni(dense[d]);
         if (t >= tiles_cap || !tile.ok(t)) continue;
-        const uint32_t base = uni32(list_base[t]);
-        uint32_t m = uni32(tile.p[t].segment_count_or_ix);
+        const uint32_t base = uni(list_base[t]);
+        uint32_t m = uni(tile.p[t].segment_count_or_ix);
         if (base >= n_cap) continue;
         m = umin_(m, n_cap - base);
         for (uint32_t o0 = 0u; o0 < m; o0 += PC_DENSE_LDS) {  // the "other" entries, PC_DENSE_LDS at a time
@@ -863,8 +857,8 @@ __global__ __launch_bounds__(JL_WG) void k_backdrop_dyn(const JlConfig* __restri
             const uint32_t lane = lane_id();
             unsigned long long old = 0ull;
             if (lane == 0u) old = atomicAdd(wide_ctr, ((unsigned long long)__builtin_popcountll(m) << 40) | (unsigned long long)total);
-            const uint32_t old_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)old);
-            const uint32_t old_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(old >> 32));
+            const uint32_t old_lo = uni((uint32_t)old);
+            const uint32_t old_hi = uni((uint32_t)(old >> 32));
             const unsigned long long o = ((unsigned long long)old_hi << 32) | old_lo;
             if (wide) {
                 const uint32_t slot = (uint32_t)(o >> 40) + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
@@ -910,7 +904,7 @@ __global__ __launch_bounds__(JL_WG) void k_backdrop_wide(const JlBump* __restric
     if (n_wide == 0u) return;
     const uint32_t lane = lane_id();
     const uint32_t waves = (gridDim.x * JL_WG) >> 6;
-    for (uint32_t g0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * JL_WG + threadIdx.x) >> 6)) * BD_UNIT; g0 < total_rows;
+    for (uint32_t g0 = uni((blockIdx.x * JL_WG + threadIdx.x) >> 6) * BD_UNIT; g0 < total_rows;
          g0 += waves * BD_UNIT) {
         uint32_t lo = 0u, hi = n_wide;  // the last entry whose first row is <= g0
         while (hi - lo > 1u) {
@@ -979,8 +973,8 @@ __global__ __launch_bounds__(JL_WG) void k_path_tiling(const JlBump* __restrict_
         V2 xy1 = is_down ? lp1 : lp0;
         V2 s0 = xy0 * TILE_SCALE;
         V2 s1 = xy1 * TILE_SCALE;
-        uint32_t count_x = span(s0.x, s1.x) - 1u;
-        uint32_t count = count_x + span(s0.y, s1.y);
+        uint32_t count_x = cell_span(s0.x, s1.x) - 1u;
+        uint32_t count = count_x + cell_span(s0.y, s1.y);
         float dx = abs_(s1.x - s0.x);
         float dy = s1.y - s0.y;
         float idxdy = 1.0f / (dx + dy);
