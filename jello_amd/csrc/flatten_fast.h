@@ -11,7 +11,7 @@
 //                 the caller runs the pinned sequence.
 // The pinned numerics do not change: the oracle keeps evaluating the exact sequence for every node, and the parity suite
 // compares the lines.  `make VARIANT=ffcheck EXTRA=-DFL_FAST_CHECK` builds a library that evaluates BOTH and counts
-// contradictions (tools/soak_flatten_fast.sh).
+// contradictions (tools/lab.py soak-ffcheck).
 //
 // Domain of the estimate: cosines of the same sign and clear of zero (|c| >= 1e-3) and, for obtuse pairs, 1 + c >= 1/256
 // (the quotients e = (2/3) / (1 + c) stay below 171); when the cosines have opposite signs (|c| >= 1e-3 each) the WGSL

@@ -139,8 +139,8 @@ JD V4 over(V4 bg, V4 fg, float area) {
 #define FINE_WAVES 1  // tile-waves per workgroup (round 3, C3: 0.405 ms with 1, 0.421 with 2, 0.428 with 4)
 #endif
 #define FB_PLANE 65
-// FINE_SKIP (differential builds, `make VARIANT=... EXTRA=-DFINE_SKIP=n`; results are WRONG, only counters and times of
-// such a library are of interest -- tools/fine_split.sh): 1 no crossing-pixel formula (stage 3), 2 no row walk / y_edge
+// FINE_SKIP (differential builds, `make VARIANT=skipN EXTRA='-DJH_VARIANT_BUILD -DFINE_SKIP=N'`; results are WRONG, only counters and times of
+// such a library are of interest -- tools/lab.py split fine): 1 no crossing-pixel formula (stage 3), 2 no row walk / y_edge
 // terms (stage 4), 3 no pair evaluation (stages 2 + 3), 4 no batches at all, 5 no compositing of solid colours,
 // 6 the FLOOR build (round 5): the real PTCL, the real segment windows, the real number of pairs and crossing pixels, but of
 // the coverage pipeline only the arithmetic the output is made of -- the WGSL's y-part once per (segment,row) pair, its
@@ -152,7 +152,7 @@ JD V4 over(V4 bg, V4 fg, float area) {
 #define FINE_SKIP 0
 #endif
 #if FINE_SKIP != 0 && !defined(JH_VARIANT_BUILD)
-#error "FINE_SKIP changes results: build it as a variant library (make VARIANT=name EXTRA='-DJH_VARIANT_BUILD -DFINE_SKIP=n')"
+#error "FINE_SKIP changes results: build it as a variant library (tools/lab.py split fine; make VARIANT=skipN EXTRA='-DJH_VARIANT_BUILD -DFINE_SKIP=N')"
 #endif
 #define RK_NONEG 1u
 #define RK_RANGE 2u
@@ -444,7 +444,7 @@ JD void ms_build(MsLds<SAMPLES>& T, MsState& B, uint32_t lane, uint32_t so, cons
     MsSeg K;
     uint32_t edge;
     const uint32_t touched = ms_setup<SAMPLES>(x0, y0, x1, y1, K, edge);
-#ifdef MS_FORCE_DIRECT_ABOVE  // (soak builds, tools/soak_round6_shapes.sh: segments with more touched pixels than this take the walk at the fill, which no sane scene reaches otherwise)
+#ifdef MS_FORCE_DIRECT_ABOVE  // (soak builds, tools/lab.py parity msdirect5: segments with more touched pixels than this take the walk at the fill, which no sane scene reaches otherwise)
     const bool force_direct = touched > MS_FORCE_DIRECT_ABOVE;
 #else
     const bool force_direct = false;

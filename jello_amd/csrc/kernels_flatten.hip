@@ -970,7 +970,7 @@ JD void run_item(const JlConfig* cfg, const Scene& s, Out<EMIT>& o, uint32_t slo
 // cooperative level), 2^-11 and 2^-13 (the walk) and has a scene of 64 cubics with 23 pieces each (the piece
 // list of a batch overflows); tests/test_gpu_curves.py holds the product build to the oracle's lines on them.
 // ------------------------------------------------------------------------------------------------
-// (capacities, overridable only so that tools/soak_flatten_fallback.sh can force the fall-back: results do not depend on them)
+// (capacities, overridable only so that tools/lab.py parity tinycap can force the fall-back: results do not depend on them)
 #ifndef FLQ_STACK
 #define FLQ_STACK 448u
 #endif
@@ -1199,7 +1199,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
     Out<true> o;
     o.cfg = cfg; o.T = T; o.home_s = o.home_r = blockIdx.x % T.K; o.failed_s = o.failed_r = false; o.slot = 0u;
     if ((debug & 1u) != 0u) o.home_s = o.home_r = 0u;  // (jh_debug_flatten_regions: regions fill up and are left behind on ordinary scenes)
-#ifdef FL_SOAK_HOME0  // (tools/soak_flatten_fallback.sh: the same for every frame of the build)
+#ifdef FL_SOAK_HOME0  // (tools/lab.py parity home0: the same for every frame of the build)
     o.home_s = o.home_r = 0u;
 #endif
     o.cursor = 0u; o.a_first = 0u; o.a_spos = 0u; o.a_rpos = 0u;
@@ -1259,7 +1259,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             if (lane == 0u) { B.n_stack = (uint32_t)__builtin_popcountll(am); B.n_leaves = 0u; B.bail = 0u; B.n_unsure = 0u; }
         }
         wave_sync();
-#ifdef FL_SPLIT_NO_A  // (measurement builds only, tools/flatten_split.sh: the kernel without its subdivision -- results are wrong)
+#ifdef FL_SPLIT_NO_A  // (measurement builds only, tools/lab.py split flatten: the kernel without its subdivision -- results are wrong)
         if (lane == 0u) B.n_stack = 0u;
         wave_sync();
 #endif
@@ -1455,7 +1455,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
 // One thread per temporary slot: the Euler line (or the directly emitted line) that lives there, moved to
 // lines[bases[item] + k], the canonical (tag byte, emission order) LineSoup position.
 #ifndef FL_LINES_WAVES_PER_EU
-#define FL_LINES_WAVES_PER_EU 4  // C3: 152 / 121 / 106 / 120 / 159 us at 2 / 3 / 4 / 5 / 8 (tools/sweep_flatten.sh)
+#define FL_LINES_WAVES_PER_EU 4  // C3: 152 / 121 / 106 / 120 / 159 us at 2 / 3 / 4 / 5 / 8 (tools/lab.py sweep flatten)
 #endif
 __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_LINES_WAVES_PER_EU, FL_LINES_WAVES_PER_EU))) void k_flatten_lines(const JlConfig* __restrict__ cfg, Buf<uint32_t> scene, const uint32_t* __restrict__ counters,
                                                          FlTemp T, const uint32_t* __restrict__ bases, uint32_t n_slots, Buf<JlLineSoup> lines) {
@@ -1551,7 +1551,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_LINES_
             V2 lp1;
             if (last_of_item) {
                 lp1 = v2(u2f(r3.z), u2f(r3.w));
-#if defined(FL_LSPLIT) && FL_LSPLIT == 1  // (measurement builds only, tools/lines_split.sh: k_flatten_lines without the Euler evaluation -- results are wrong)
+#if defined(FL_LSPLIT) && FL_LSPLIT == 1  // (measurement builds only, tools/lab.py split lines: k_flatten_lines without the Euler evaluation -- results are wrong)
             } else if (true) {
                 lp1 = v2(u2f(r0.x) + (float)i, u2f(r0.w) + u2f(r1.x) + u2f(r1.y) + u2f(r1.z) + u2f(r1.w) + u2f(r2.x));
 #endif
@@ -1883,7 +1883,7 @@ JhResult jh_launch_flatten(const JhLaunch& L) {
     // a wave per 64 lines of the buffer's capacity (the line count is only known on the device), at most 16 waves
     // per SIMD: the kernel lengthens the ranges to match
     uint64_t gb64 = ((uint64_t)lines.n + 255u) / 256u;  // four waves per workgroup
-#ifdef FB_MAX_BLOCKS  // (tools/soak_flatten_fallback.sh: a tiny grid, so that every wave strides over many ranges)
+#ifdef FB_MAX_BLOCKS  // (tools/lab.py parity fbblocks2: a tiny grid, so that every wave strides over many ranges)
     const uint32_t gb_max = FB_MAX_BLOCKS;
 #else
     const uint32_t gb_max = 4u * gp_cap;

@@ -423,7 +423,7 @@ JD void path_range(uint32_t P, const uint32_t* __restrict__ pstart, const uint32
 // (measured: 45 us for a 256-crossing path, 1.7 ms for 20 circles of 700 crossings), while the atomic route is linear
 // and spread over the whole device.  64 was the best threshold on every scene tried (tools/time_shapes.py, C3).
 #ifndef PC_BIG_PATH
-#define PC_BIG_PATH 64u  // (tools/sweep_pc.sh builds other values)
+#define PC_BIG_PATH 64u  // (tools/lab.py sweep pc builds other values)
 #endif
 JD bool npe_big(uint32_t n) { return n > PC_BIG_PATH; }
 

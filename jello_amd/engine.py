@@ -566,7 +566,7 @@ class Engine:
 
     def trim_scratch(self):
         """Frees the internal scratch arrays (they only grow): after a frame much larger than the ones to come."""
-        if hasattr(self.hip, "jh_scratch_trim"):  # (an older library under JELLO_HIP_LIB, tools/ab_kernels.sh: nothing to give back)
+        if hasattr(self.hip, "jh_scratch_trim"):  # (an older library under JELLO_HIP_LIB, tools/lab.py kstats: nothing to give back)
             self._check(self.hip.jh_scratch_trim(self.ctx), "scratch_trim")
 
     def set_stream(self, stream_ptr):

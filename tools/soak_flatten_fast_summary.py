@@ -4,6 +4,7 @@ by the time limit) and the totals.  usage: python3 tools/soak_flatten_fast_summa
 import glob, os, re, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 logs = sorted(glob.glob(os.path.join(R, "gpurun_out", "r4_ffsoak*.log")) + glob.glob(os.path.join(R, "gpurun_out", "ffsoak_*.log")))
+logs += sorted(glob.glob(os.path.join(R, "lab_out", "ffsoak_*.log")))  # (where tools/lab.py soak-ffcheck leaves them)
 tot = dict(seeds=0, nodes=0, und=0, con=0, vio=0, runs=0)
 rows = []
 scene_rows = {}
