@@ -22,6 +22,7 @@
  *   jh_pack_tiles / jh_unpack_tiles   (no counterpart: the frame's way off the GPU)
  *   jh_dash                           (no counterpart: the reference dashes on the CPU with curve.Dash)
  *   jh_blur                           (no counterpart: Gaussian blur of the RGBA16F target on the device)
+ *   jh_resample                       (no counterpart: an RGBA16F image resized on the device, four filters)
  *   jh_composite                      (no counterpart: one RGBA16F image blended onto another on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
@@ -453,6 +454,67 @@ typedef struct jh_composite_desc {
     int32_t dx, dy;                 /* where its top-left lands in dst */
 } jh_composite_desc;
 int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_composite_desc* desc);
+
+/* ---- Resample: one RGBA16F image resized into a rectangle of another (DESIGN.md 5.9 "Resample rule") ----
+ * A 4096^2 render as a 1080p video frame, a supersampled render at display size, thumbnails, mip levels, a layer scaled before
+ * jh_composite places it -- without the image leaving the device.  The result is defined on values, and every implementation
+ * produces these bits (include/jello_resample.h states the host half, tests/resample_ref.py restates all of it).
+ * Per axis, with n_in the SOURCE RECTANGLE's extent and n_out the destination rectangle's, binary64 unless said otherwise:
+ *   support     scale = (double)n_in / (double)n_out; fs = max(scale, 1.0); support = base fs, base = 0.5 BOX, 1.0 TRIANGLE,
+ *               2.0 CATMULL_ROM, 3.0 LANCZOS3.  Legal: n_in >= 1, n_out >= 1, n_in <= 16 n_out (16:1 down at most, any ratio up).
+ *   window      of output i: c = ((double)i + 0.5) scale; lo = max(0, (int64)(c - support + 0.5)); hi = min(n_in, (int64)(c +
+ *               support + 0.5)), the casts truncating.  It is clipped to the source rectangle, not to the image: an atlas cell
+ *               does not bleed.  g_k = f(((double)k - c + 0.5) / fs), k = lo .. hi - 1; leading and trailing g_k that are exactly
+ *               0.0 are dropped, interior zeros stay.  No window is empty, none has more than 96 taps.
+ *   filters     operations in this order -- BOX: 1.0 if -0.5 < x <= 0.5, else 0.0.  TRIANGLE: x = |x|; 1.0 - x if x < 1.0, else 0.0.
+ *               CATMULL_ROM: a = -0.5, x = |x|; ((a + 2.0) x - (a + 3.0)) x x + 1.0 if x < 1.0; (((x - 5.0) x + 8.0) x - 4.0) a if
+ *               x < 2.0; else 0.0.  LANCZOS3: sinc(x) sinc(x / 3.0) if -3.0 <= x < 3.0, else 0.0; sinc(0) = 1, otherwise t = x M_PI,
+ *               sin(t) / t -- sin is the libm call, the rule's only inexact library call.
+ *   taps        S = the sum of the window's g_k, ascending k; w_k = (float)(g_k / S).
+ * Per texel, binary32, nothing contracted but the stated fmaf:
+ *   source      the f16 texel widened to (c, a); p = (c.r a, c.g a, c.b a, a), exact -- or with JH_RESAMPLE_STRAIGHT p = (c, a), for
+ *               data images and constant alpha.  (The images are stored un-premultiplied, DESIGN.md 5.8: filtering their colour
+ *               channels is right only where alpha is constant, so premultiplying is the default.)
+ *   horizontal  H = 0.0f; for k ascending over the x window: H = fmaf(w_k, p[k], H).  H stays binary32.
+ *   vertical    V = 0.0f; for k ascending over the y window: V = fmaf(w_k, H[k], V).  Rows before columns: the bits depend on it.
+ *   store       STRAIGHT: f16(V) per channel, round to nearest even.  Otherwise as fine and jh_composite store: a_inv = 1.0f /
+ *               max(V.a, 1e-6f); (f16(V.r a_inv + 0.0f), f16(V.g a_inv + 0.0f), f16(V.b a_inv + 0.0f), f16(V.a + 0.0f)).
+ *   values      f16 subnormals are values, Inf and NaN follow IEEE, a NaN result is any NaN.  Nothing is clamped: the negative lobes
+ *               of CATMULL_ROM and LANCZOS3 can leave alpha below 0 or colour above 1.
+ * So STRAIGHT with equal sizes is a bit-exact copy under BOX, TRIANGLE and CATMULL_ROM (the single tap 1.0f; a -0 comes out as +0,
+ * a NaN as a NaN) -- not under LANCZOS3, because sin(k pi) is not 0 in binary64 -- and STRAIGHT BOX at an exact 2:1 is the 2 x 2
+ * mean with the rule's roundings.
+ *
+ * jh_resample_taps: the window of output i of an axis: its weights into weights (96 entries are enough; may be NULL), its first
+ * source index (relative to the source rectangle) into *first and its tap count into *count (either may be NULL).  Host only, no
+ * context.  JH_ERR_INVALID for an unknown filter, illegal sizes or i >= n_out.
+ *
+ * jh_resample: the rectangle (src_x, src_y, src_width, src_height) of src_image_id resized into the rectangle (dst_x, dst_y,
+ * dst_width, dst_height) of dst_image_id, another image; the images carry their own sizes; width == height == 0 means the whole
+ * image (x and y are then ignored).  Only the destination rectangle is written; a dst that was never written is cleared to
+ * transparent black first and then counts as written; a source that was never written reads as transparent black.
+ * Stream-ordered on the context's stream, never waits: two kernel launches (rows into a binary32 intermediate of source-rectangle
+ * rows x dst_width x 16 bytes, columns out of it), plus a fill when dst has to be cleared.  The windows and taps of both axes live in
+ * a device table of the context, which holds ONE geometry (filter and the four extents) at a time: a call with the geometry the
+ * table holds uploads nothing; an eager call with another builds the tables on the host, uploads them stream-ordered and makes every
+ * graph captured before it stale (jh_graph_launch refuses it).  During a capture a call whose geometry is resident records its two
+ * launches; any other is refused with JH_ERR_OOM and the advice to resample this geometry once eagerly first.  With profiling on the
+ * call is a query "resample" with stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band).
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_resample: ": a
+ * null desc; an unknown source or destination id; an image that is not RGBA16F; an unknown filter or flag bit; a rectangle that is
+ * not inside its image or that is empty in exactly one dimension; a ratio above 16:1 on either axis; src_image_id == dst_image_id; a
+ * band set with jh_set_band. */
+typedef enum jh_resample_filter { JH_RESAMPLE_BOX = 0, JH_RESAMPLE_TRIANGLE = 1, JH_RESAMPLE_CATMULL_ROM = 2, JH_RESAMPLE_LANCZOS3 = 3 } jh_resample_filter;
+#define JH_RESAMPLE_STRAIGHT 1u
+#define JH_RESAMPLE_MAX_TAPS 96u
+typedef struct jh_resample_desc {
+    int filter;                                       /* jh_resample_filter */
+    uint32_t flags;                                   /* bit 0: JH_RESAMPLE_STRAIGHT */
+    uint32_t src_x, src_y, src_width, src_height;     /* source rectangle; width == height == 0: the whole image */
+    uint32_t dst_x, dst_y, dst_width, dst_height;     /* destination rectangle, likewise */
+} jh_resample_desc;
+int jh_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, float* weights /* or NULL */, uint32_t* first, uint32_t* count);
+int jh_resample(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_resample_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

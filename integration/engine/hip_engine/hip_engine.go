@@ -516,6 +516,41 @@ func (e *Engine) Composite(src, dst renderer.ImageProxy, desc CompositeDesc) {
 	e.check(C.jh_composite(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "composite")
 }
 
+// ResampleFilter is jh_resample_filter: the kernel of Resample, by its support at 1:1.
+type ResampleFilter int32
+
+const (
+	ResampleBox        ResampleFilter = 0 // 0.5 texels
+	ResampleTriangle   ResampleFilter = 1 // 1
+	ResampleCatmullRom ResampleFilter = 2 // 2
+	ResampleLanczos3   ResampleFilter = 3 // 3
+)
+
+// ResampleStraight is JH_RESAMPLE_STRAIGHT: the four channels are filtered as they are stored, colour is not weighted by alpha.
+const ResampleStraight uint32 = 1
+
+// ResampleDesc is jh_resample_desc (include/jello_hip.h "Resample"): the filter, the flags, and the rectangles of the source that is
+// read and of the destination that is written (Width == Height == 0: the whole image).
+type ResampleDesc struct {
+	Filter                          ResampleFilter
+	Flags                           uint32
+	SrcX, SrcY, SrcWidth, SrcHeight uint32
+	DstX, DstY, DstWidth, DstHeight uint32
+}
+
+// Resample is jh_resample: a rectangle of the RGBA16F image src resized into a rectangle of the RGBA16F image dst (another image)
+// by the rule of DESIGN.md 5.9 (defined on values: every implementation gives the same bits), at most 16:1 down on either axis.
+// Only the destination rectangle is written.  Stream-ordered behind the frame, waits for nothing, two kernel launches; the context
+// keeps the tap tables of one geometry (filter and the rectangles' extents), so a call that repeats the last one's uploads nothing
+// and can be captured.  For a video frame or a thumbnail of a larger render, a supersampled render at display size, mip levels, a
+// layer scaled before Composite places it.
+func (e *Engine) Resample(src, dst renderer.ImageProxy, desc ResampleDesc) {
+	d := C.jh_resample_desc{filter: C.int(desc.Filter), flags: C.uint32_t(desc.Flags), src_x: C.uint32_t(desc.SrcX), src_y: C.uint32_t(desc.SrcY),
+		src_width: C.uint32_t(desc.SrcWidth), src_height: C.uint32_t(desc.SrcHeight), dst_x: C.uint32_t(desc.DstX), dst_y: C.uint32_t(desc.DstY),
+		dst_width: C.uint32_t(desc.DstWidth), dst_height: C.uint32_t(desc.DstHeight)}
+	e.check(C.jh_resample(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "resample")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

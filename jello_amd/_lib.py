@@ -146,6 +146,13 @@ class CCompositeDesc(ctypes.Structure):
                 ("sh", ctypes.c_uint32), ("dx", ctypes.c_int32), ("dy", ctypes.c_int32)]
 
 
+class CResampleDesc(ctypes.Structure):
+    """jh_resample_desc (include/jello_hip.h)."""
+    _fields_ = [("filter", ctypes.c_int32), ("flags", ctypes.c_uint32), ("src_x", ctypes.c_uint32), ("src_y", ctypes.c_uint32),
+                ("src_width", ctypes.c_uint32), ("src_height", ctypes.c_uint32), ("dst_x", ctypes.c_uint32), ("dst_y", ctypes.c_uint32),
+                ("dst_width", ctypes.c_uint32), ("dst_height", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -214,6 +221,7 @@ def _declare(L):
     u32, u64 = ctypes.c_uint32, ctypes.c_uint64
     L.jl_engine_read_pack.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
     L.jl_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
+    L.jl_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -253,6 +261,8 @@ def _declare(L):
     hip.jh_blur.argtypes = [vp, u64, u64, u32, u32, ctypes.POINTER(CBlurDesc)]
     hip.jh_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
     hip.jh_composite.argtypes = [vp, u64, u64, ctypes.POINTER(CCompositeDesc)]
+    hip.jh_resample.argtypes = [vp, u64, u64, ctypes.POINTER(CResampleDesc)]
+    hip.jh_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

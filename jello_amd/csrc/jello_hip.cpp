@@ -22,6 +22,7 @@
 #include "kcommon.h"
 #include "../../include/jello_blur.h"
 #include "../../include/jello_composite.h"
+#include "../../include/jello_resample.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -127,6 +128,13 @@ struct jh_ctx {
     uint32_t* hint_overflow = nullptr;  // device word: blend-stack saves fine had to drop because the clip-depth hint was too small
     std::vector<JhImageDesc> image_table_host;
     std::vector<Held> held;  // held-back commands, in recording order
+    // jh_resample: the geometry whose tables the JH_SCR_RESAMPLE_TAPS slot holds, and where they lie in it
+    struct {
+        bool valid = false;
+        int filter = 0;
+        uint32_t sw = 0, sh = 0, dw = 0, dh = 0;
+        JhResampleTables tables = {};
+    } resample;
 };
 
 static int flush_held(jh_ctx* ctx);
@@ -1136,7 +1144,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1454,6 +1462,136 @@ int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, cons
     });
 }
 
+// resample (include/jello_hip.h "Resample"; windows and taps: include/jello_resample.h; kernels_resample.hip)
+int jh_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, float* weights, uint32_t* first, uint32_t* count) {
+    if (!jresample_filter_ok(filter) || !jresample_sizes_ok(n_in, n_out) || i >= n_out) return JH_ERR_INVALID;
+    uint32_t f = 0u;
+    const uint32_t n = jresample_taps(filter, n_in, n_out, i, weights, &f, nullptr);
+    if (n == 0u) return JH_ERR_INVALID;
+    if (first) *first = f;
+    if (count) *count = n;
+    return JH_OK;
+}
+
+// The tables of one geometry as kernels_resample.hip reads them (JhResampleTables, kcommon.h), in one blob: [win_x][seg_x][w_x]
+// [win_y][w_y], each section on a 16-byte boundary.  false for a window without taps (the rule has none).
+struct ResampleBlob {
+    std::vector<char> bytes;
+    uint64_t o_seg_x = 0, o_w_x = 0, o_win_y = 0, o_w_y = 0;
+    uint32_t taps_x = 0, stride_y = 0, region_x = 0;
+};
+static bool resample_build(int filter, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, ResampleBlob& b) {
+    struct Axis { std::vector<uint32_t> first, count; std::vector<float> w; uint32_t most = 0; };
+    auto axis = [&](uint32_t n_in, uint32_t n_out, Axis& a) {
+        a.first.resize(n_out);
+        a.count.resize(n_out);
+        a.w.assign((size_t)n_out * JRESAMPLE_MAX_TAPS, 0.0f);
+        for (uint32_t i = 0; i < n_out; i++) {
+            a.count[i] = jresample_taps(filter, n_in, n_out, i, &a.w[(size_t)i * JRESAMPLE_MAX_TAPS], &a.first[i], nullptr);
+            if (a.count[i] == 0u || (uint64_t)a.first[i] + a.count[i] > n_in) return false;
+            a.most = std::max(a.most, a.count[i]);
+        }
+        return true;
+    };
+    Axis ax, ay;
+    if (!axis(sw, dw, ax) || !axis(sh, dh, ay)) return false;
+    auto al = [](uint64_t v) { return (v + 15u) & ~15ull; };
+    const uint32_t segs = (dw + JH_RESAMPLE_ROW_SEG - 1u) / JH_RESAMPLE_ROW_SEG;
+    b.taps_x = ax.most;
+    b.stride_y = ay.most;
+    b.o_seg_x = al(8ull * dw);
+    b.o_w_x = b.o_seg_x + al(16ull * segs);
+    b.o_win_y = b.o_w_x + al(4ull * ax.most * dw);
+    b.o_w_y = b.o_win_y + al(8ull * dh);
+    b.bytes.assign(b.o_w_y + al(4ull * ay.most * dh), 0);
+    uint32_t* win_x = (uint32_t*)b.bytes.data();
+    uint32_t* seg_x = (uint32_t*)(b.bytes.data() + b.o_seg_x);
+    float* w_x = (float*)(b.bytes.data() + b.o_w_x);
+    uint32_t* win_y = (uint32_t*)(b.bytes.data() + b.o_win_y);
+    float* w_y = (float*)(b.bytes.data() + b.o_w_y);
+    uint32_t longest = 1u;
+    for (uint32_t s = 0; s < segs; s++) {
+        uint32_t lo = 0xffffffffu, hi = 0u, most = 0u;
+        for (uint32_t o = s * JH_RESAMPLE_ROW_SEG; o < dw && o < (s + 1u) * JH_RESAMPLE_ROW_SEG; o++) {
+            lo = std::min(lo, ax.first[o]);
+            hi = std::max(hi, ax.first[o] + ax.count[o]);
+            most = std::max(most, ax.count[o]);
+        }
+        seg_x[4u * s] = lo; seg_x[4u * s + 1u] = hi - lo; seg_x[4u * s + 2u] = most;
+        longest = std::max(longest, hi - lo);
+    }
+    b.region_x = jh_resample_skew(longest - 1u) + 1u;
+    for (uint32_t o = 0; o < dw; o++) {
+        win_x[2u * o] = ax.first[o]; win_x[2u * o + 1u] = ax.count[o];
+        for (uint32_t j = 0; j < ax.count[o]; j++) w_x[(size_t)j * dw + o] = ax.w[(size_t)o * JRESAMPLE_MAX_TAPS + j];
+    }
+    for (uint32_t o = 0; o < dh; o++) {
+        win_y[2u * o] = ay.first[o]; win_y[2u * o + 1u] = ay.count[o];
+        for (uint32_t j = 0; j < ay.count[o]; j++) w_y[(size_t)o * ay.most + j] = ay.w[(size_t)o * JRESAMPLE_MAX_TAPS + j];
+    }
+    return true;
+}
+
+int jh_resample(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_resample_desc* desc) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_resample: null descriptor");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_resample", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
+    if (src == dst) return fail(ctx, JH_ERR_INVALID, "jh_resample: the source is the destination (a resize in place reads what it writes)");
+    if (!jresample_filter_ok(desc->filter)) return fail(ctx, JH_ERR_INVALID, "jh_resample: unknown filter");
+    if ((desc->flags & ~(uint32_t)JH_RESAMPLE_STRAIGHT) != 0u) return fail(ctx, JH_ERR_INVALID, "jh_resample: unknown flag bits");
+    uint32_t sx = desc->src_x, sy = desc->src_y, sw = desc->src_width, sh = desc->src_height;
+    uint32_t dx = desc->dst_x, dy = desc->dst_y, dw = desc->dst_width, dh = desc->dst_height;
+    if (sw == 0u && sh == 0u) { sx = 0u; sy = 0u; sw = src->width; sh = src->height; }  // the whole image
+    if (dw == 0u && dh == 0u) { dx = 0u; dy = 0u; dw = dst->width; dh = dst->height; }
+    if (sw == 0u || sh == 0u || dw == 0u || dh == 0u) return fail(ctx, JH_ERR_INVALID, "jh_resample: a rectangle is empty in one dimension");
+    if ((uint64_t)sx + sw > src->width || (uint64_t)sy + sh > src->height)
+        return fail(ctx, JH_ERR_INVALID, "jh_resample: the source rectangle is not inside the source image");
+    if ((uint64_t)dx + dw > dst->width || (uint64_t)dy + dh > dst->height)
+        return fail(ctx, JH_ERR_INVALID, "jh_resample: the destination rectangle is not inside the destination image");
+    if (!jresample_sizes_ok(sw, dw) || !jresample_sizes_ok(sh, dh)) return fail(ctx, JH_ERR_INVALID, "jh_resample: a ratio above 16:1");
+    if (int rc = refuse_band_mode(ctx, "jh_resample", "the rows a window reads belong to another rank")) return rc;
+    auto& key = ctx->resample;
+    const bool resident = key.valid && key.filter == desc->filter && key.sw == sw && key.sh == sh && key.dw == dw && key.dh == dh;
+    ResampleBlob blob;
+    if (!resident && !ctx->capturing && !resample_build(desc->filter, sw, sh, dw, dh, blob))
+        return fail(ctx, JH_ERR_INVALID, "jh_resample: a window without taps");
+    void *tmp = nullptr, *staged = nullptr;
+    char* dev = nullptr;
+    return post_render_call(
+        ctx, "resample",
+        [&] {
+            // (a capture can neither grow an array nor upload: its geometry has to be resident)
+            tmp = jh_scratch_get(&ctx->scratch, JH_SCR_RESAMPLE, (uint64_t)sh * dw * 16u);
+            if (tmp && !resident && !ctx->capturing) dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_RESAMPLE_TAPS, blob.bytes.size());
+            if (!tmp || (!resident && !dev))
+                return fail(ctx, JH_ERR_OOM, "jh_resample: " + scratch_failure(ctx, "resample this geometry once eagerly first"));
+            if (!resident) {
+                staged = stage_copy(ctx, blob.bytes.data(), blob.bytes.size());  // the pinned arena, as jh_upload: the DMA is left in flight
+                if (!staged) return fail(ctx, JH_ERR_OOM, "jh_resample: pinned staging allocation failed");
+            }
+            return (int)JH_OK;
+        },
+        [&] {  // (the query holds the upload too)
+            const void* from = content_or_null(*src);
+            if (int rc = first_content(ctx, dst, dw, dh)) return rc;
+            if (!resident) {
+                key.valid = false;
+                HIP_TRY(ctx, hipMemcpyAsync(dev, staged, blob.bytes.size(), hipMemcpyHostToDevice, ctx->stream));
+                JhResampleTables& t = key.tables;
+                t.win_x = (const uint2*)dev; t.seg_x = (const uint4*)(dev + blob.o_seg_x); t.w_x = (const float*)(dev + blob.o_w_x);
+                t.win_y = (const uint2*)(dev + blob.o_win_y); t.w_y = (const float*)(dev + blob.o_w_y);
+                t.taps_x = blob.taps_x; t.stride_y = blob.stride_y; t.region_x = blob.region_x;
+                key.filter = desc->filter; key.sw = sw; key.sh = sh; key.dw = dw; key.dh = dh;
+                key.valid = true;
+                ctx->generation++;  // (a graph captured against the tables of another geometry would read these)
+            }
+            return launch_status(ctx, "jh_resample", jh_resample_launch(ctx->stream, from, src->width, src->height, sx, sy, sw, sh, dst->ptr, dst->width,
+                                                                        dst->height, dx, dy, dw, dh, (desc->flags & JH_RESAMPLE_STRAIGHT) != 0u, &key.tables,
+                                                                        tmp, ctx->num_cus));
+        });
+}
+
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.
 int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
@@ -1496,8 +1634,10 @@ int jh_debug_poison_scratch(jh_ctx* ctx, int byte) {
     if (!ctx) return JH_ERR_INVALID;
     JH_FLUSH(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    for (int i = 0; i < JH_SCR_COUNT; i++)
+    for (int i = 0; i < JH_SCR_COUNT; i++) {
+        if (i == JH_SCR_RESAMPLE_TAPS) continue;  // (uploaded content a captured jh_resample reads, not an array a frame fills before it reads it)
         if (ctx->scratch.ptr[i] && ctx->scratch.cap[i]) HIP_TRY(ctx, hipMemsetAsync(ctx->scratch.ptr[i], byte, ctx->scratch.cap[i], ctx->stream));
+    }
     ctx->scratch.clean_flags = 0u;
     return JH_OK;
 }
@@ -1560,6 +1700,7 @@ int jh_scratch_trim(jh_ctx* ctx) {
         ctx->scratch.cap[i] = 0;
     }
     ctx->scratch.clean_flags = 0;  // (new memory holds anything: every self-cleaned array is filled again on its next use)
+    ctx->resample.valid = false;   // (jh_resample's tables went with their slot)
     ctx->generation++;
     return JH_OK;
 }

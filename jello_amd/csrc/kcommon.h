@@ -229,6 +229,9 @@ struct JhImageDesc {
 //   PC_TOT                                                            crossings per path                             self-cleaned
 //   BLUR      (jh_blur, a call outside the frame's stages: the binary32 rows between its two passes -- a slot of its own, so that a
 //              frame between two blurs of one size never makes it grow and a captured blur stays valid)
+//   RESAMPLE  (jh_resample, likewise: the binary32 rows between its two passes, source-rectangle rows x destination width x 16 B)
+//   RESAMPLE_TAPS  (jh_resample: the uploaded window and tap tables of both axes for ONE geometry -- content that a captured call
+//              reads on every replay, so nothing else may write the slot; the context keeps the key of what it holds)
 enum {
     JH_SCR_SCAN_TMP = 0,
     JH_SCR_A = 1,
@@ -245,7 +248,9 @@ enum {
     JH_SCR_BD_CTR = 12,  // backdrop's wide-row counter: likewise
     JH_SCR_PC_TOT = 13,  // path_count's crossings per path (atomic sums): likewise, zeroed by the stage's last kernel
     JH_SCR_BLUR = 14,    // jh_blur's intermediate
-    JH_SCR_COUNT = 15
+    JH_SCR_RESAMPLE = 15,       // jh_resample's intermediate
+    JH_SCR_RESAMPLE_TAPS = 16,  // jh_resample's tables
+    JH_SCR_COUNT = 17
 };
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
@@ -327,7 +332,23 @@ struct JhDashJob {
 };
 JhResult jh_dash_launch(const JhLaunch& L, const JhDashJob& job, void* out, uint64_t capacity, uint32_t* index);
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _selftest .hip).  Declared
+// jh_resample (kernels_resample.hip): the tables of one geometry as the host lays them out (jello_hip.cpp builds and uploads them)
+// and the kernels read them.  Windows are relative to the source rectangle.
+#define JH_RESAMPLE_ROW_SEG 64u  // outputs of a row-pass item: one per lane of a wave
+// A staged source span in LDS: texel t sits at float4 index t + t / 16, so that lanes whose windows start 16 texels apart (the 16:1
+// limit) are 272 bytes apart instead of 256 and a ds_read_b128 of 16 lanes covers all 64 banks.
+__host__ __device__ __forceinline__ uint32_t jh_resample_skew(uint32_t t) { return t + (t >> 4); }
+struct JhResampleTables {
+    const uint2* win_x;  // per output column: {first source column, taps}
+    const uint4* seg_x;  // per segment of JH_RESAMPLE_ROW_SEG output columns: {first source column any of them reads, columns they span, most taps of one, 0}
+    const float* w_x;    // tap j of output column o at w_x[j * dst_w + o] (the lanes of a wave read neighbouring words); zero where o has fewer taps
+    const uint2* win_y;  // per output row: {first source row, taps}
+    const float* w_y;    // tap j of output row o at w_y[o * stride_y + j]
+    uint32_t taps_x, stride_y;  // the largest tap count of an output column / row
+    uint32_t region_x;          // float4 slots of LDS a wave of the row pass needs: jh_resample_skew(longest span - 1) + 1
+};
+
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses, another negative value for a failed launch.
 extern "C" {
@@ -345,6 +366,9 @@ int jh_blur_launch(hipStream_t stream, const void* src, void* dst, uint32_t widt
 struct jcomp_rect;  // include/jello_composite.h
 int jh_composite_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h,
                         int dst_has_content, const jcomp_rect* rect, uint32_t mode, uint32_t flags, float opacity, const float* tint, int num_cus);
+int jh_resample_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh,
+                       void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t dx, uint32_t dy, uint32_t dw, uint32_t dh, int straight,
+                       const JhResampleTables* tables, void* tmp, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

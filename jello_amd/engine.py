@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CCompositeDesc, CConfig, CProfileNode, CProfileRecord, CYuvDesc
+from ._lib import CBlurDesc, CCompositeDesc, CConfig, CProfileNode, CProfileRecord, CResampleDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -99,6 +99,39 @@ def _composite_desc(mix, compose, opacity, tint, src_rect, offset):
     d.sx, d.sy, d.sw, d.sh = int(sx), int(sy), int(sw), int(sh)
     d.dx, d.dy = int(offset[0]), int(offset[1])
     return d
+
+
+class ResampleFilter(enum.IntEnum):
+    """jh_resample_filter: the kernel of jh_resample, by its support at 1:1 -- 0.5, 1, 2 and 3 texels."""
+    BOX = 0
+    TRIANGLE = 1
+    CATMULL_ROM = 2
+    LANCZOS3 = 3
+
+
+RESAMPLE_STRAIGHT = 1  # JH_RESAMPLE_STRAIGHT
+RESAMPLE_MAX_TAPS = 96  # JH_RESAMPLE_MAX_TAPS
+
+
+def resample_taps(filter, n_in, n_out):
+    """jh_resample_taps for every output index of one axis of the resample rule, n_in source texels onto n_out: a
+    list of (first, weights) -- the window's first source index and its float32 taps.  No GPU needed.  ValueError for an unknown
+    filter or sizes outside 1 <= n_in <= 16 n_out."""
+    hip = _lib.load_host().hip
+    out = []
+    w = np.empty(RESAMPLE_MAX_TAPS, dtype=np.float32)
+    first, count = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    for i in range(max(int(n_out), 1)):
+        if hip.jh_resample_taps(int(filter), int(n_in), int(n_out), i, w.ctypes.data, ctypes.byref(first), ctypes.byref(count)) != 0:
+            raise ValueError("resample_taps: unknown filter, or sizes outside 1 <= n_in <= 16 n_out")
+        out.append((first.value, w[:count.value].copy()))
+    return out
+
+
+def _resample_desc(filter, src_rect, dst_rect, premultiplied):
+    sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
+    dx, dy, dw, dh = (0, 0, 0, 0) if dst_rect is None else dst_rect
+    return CResampleDesc(int(filter), 0 if premultiplied else RESAMPLE_STRAIGHT, int(sx), int(sy), int(sw), int(sh), int(dx), int(dy), int(dw), int(dh))
 
 
 def composite_clip(src_size, dst_size, src_rect=None, offset=(0, 0)):
@@ -397,6 +430,17 @@ class Engine:
         d = _composite_desc(mix, compose, opacity, tint, src_rect, offset)
         self._check(self.hip.jh_composite(self.ctx, src_id, dst_id, ctypes.byref(d)), "composite", invalid=ValueError)
 
+    def resample(self, src_id, dst_id, filter=ResampleFilter.CATMULL_ROM, src_rect=None, dst_rect=None, premultiplied=True):
+        """jh_resample: the rectangle `src_rect` = (x, y, width, height) of the RGBA16F image `src_id` (None: the whole image)
+        resized into the rectangle `dst_rect` of the RGBA16F image `dst_id` (another image; None: the whole image) by the rule of
+        DESIGN.md 5.9, at most 16:1 down on either axis.  `premultiplied`: colour is weighted by alpha while it is filtered (the
+        default); False filters the four channels as they are stored (JH_RESAMPLE_STRAIGHT: data images, constant alpha).  Only the
+        destination rectangle is written.  The context holds the tap tables of one geometry (filter and the rectangles' extents): a
+        call with another uploads its own and makes graphs captured before it stale.  Stream-ordered, returns nothing; ValueError
+        for a call the rule refuses."""
+        d = _resample_desc(filter, src_rect, dst_rect, premultiplied)
+        self._check(self.hip.jh_resample(self.ctx, src_id, dst_id, ctypes.byref(d)), "resample", invalid=ValueError)
+
     def drop_shadow(self, layer_id, target_id, width, height, sigma, offset, color, scratch_image_id):
         """A layer with its drop shadow onto a target, three calls: blur(layer -> scratch, edge ZERO); composite(scratch -> target,
         tint=color, offset): the blurred alpha in the shadow's colour, shifted; composite(layer -> target).  `layer_id` and
@@ -507,7 +551,7 @@ class Engine:
             out.append(p)
         return out
 
-    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None):
+    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -520,7 +564,11 @@ class Engine:
         the render and before the surface, YUV or pack conversion of the same capture (two more launches); a rectangle of this
         size must have been blurred once eagerly.
         composite=dict(src=image id, ...) (the other keywords of composite(), optional) blends that image onto the frame's target
-        after the blur and before the surface, YUV or pack conversion of the same capture (one more launch)."""
+        after the blur and before the surface, YUV or pack conversion of the same capture (one more launch).
+        resample=dict(dst=image id, width=..., height=..., ...) (the other keywords of resample(), optional) resizes the frame's
+        target into the RGBA16F image `dst` of width x height after the blur and the composite (two more launches); the surface,
+        YUV or pack conversion of the same capture then reads that image at its size.  This geometry must have been resampled once
+        eagerly, and no other since."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
@@ -529,6 +577,9 @@ class Engine:
                 self.blur(t["id"], t["width"], t["height"], blur["sigma"], edge=blur.get("edge", BlurEdge.ZERO), rect=blur.get("rect"))
             if composite is not None:
                 self.composite(composite["src"], t["id"], **{k: v for k, v in composite.items() if k != "src"})
+            if resample is not None:
+                self.resample(t["id"], resample["dst"], **{k: v for k, v in resample.items() if k not in ("dst", "width", "height")})
+                t = {"id": resample["dst"], "width": resample["width"], "height": resample["height"]}
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._blit(t["id"], ptr, pitch, t["width"], t["height"], fmt)

@@ -8,6 +8,7 @@
 
 #include "../../include/jello_blur.h"
 #include "../../include/jello_composite.h"
+#include "../../include/jello_resample.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -437,6 +438,23 @@ int jl_blur_taps(float sigma, float* weights, uint32_t* radius) {
     if (!jblur_sigma_ok(sigma)) { g_err = "blur_taps: sigma is negative, above 64 or NaN"; return -1; }
     const uint32_t R = jblur_taps(sigma, weights);
     if (radius) *radius = R;
+    return 0;
+}
+
+// jl_resample_taps is the host twin of jh_resample_taps (the rule is in jello_hip.h and DESIGN.md 5.9): the same header, compiled here
+// by the host compiler -- the window of output i of an axis of n_in source texels onto n_out: its weights into weights (96 entries
+// are enough; or null), its first source index into *first, its tap count into *count; -1 for an unknown filter, illegal sizes or
+// i >= n_out.
+int jl_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, float* weights, uint32_t* first, uint32_t* count) {
+    if (!jresample_filter_ok(filter) || !jresample_sizes_ok(n_in, n_out) || i >= n_out) {
+        g_err = "resample_taps: unknown filter, sizes outside 1 <= n_in <= 16 n_out, or an index outside the axis";
+        return -1;
+    }
+    uint32_t f = 0u;
+    const uint32_t n = jresample_taps(filter, n_in, n_out, i, weights, &f, nullptr);
+    if (n == 0u) { g_err = "resample_taps: a window without taps"; return -1; }
+    if (first) *first = f;
+    if (count) *count = n;
     return 0;
 }
 
