@@ -24,6 +24,7 @@
  *   jh_blur                           (no counterpart: Gaussian blur of the RGBA16F target on the device)
  *   jh_resample                       (no counterpart: an RGBA16F image resized on the device, four filters)
  *   jh_composite                      (no counterpart: one RGBA16F image blended onto another on the device)
+ *   jh_color_filter                   (no counterpart: colour matrix and transfer functions on an RGBA16F image)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -515,6 +516,80 @@ typedef struct jh_resample_desc {
 } jh_resample_desc;
 int jh_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, float* weights /* or NULL */, uint32_t* first, uint32_t* count);
 int jh_resample(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_resample_desc* desc);
+
+/* ---- Colour filter: a colour matrix and per-channel transfer functions on an RGBA16F image (DESIGN.md 5.10 "Colour-filter rule") ----
+ * feColorMatrix, feComponentTransfer, the CSS filter functions (grayscale, sepia, saturate, hue-rotate, invert, opacity, brightness,
+ * contrast), a tint, a luminance mask's first half -- without the image leaving the device.  The result is defined on values, and
+ * every implementation produces these bits (include/jello_color.h states the host half, tests/color_ref.py restates all of it).
+ * Per texel, binary32, nothing contracted but the stated fmaf; h_c is the stored f16 bit pattern of channel c, un-premultiplied:
+ *   input    t_c = PRE_c[h_c] for c = r, g, b when space == JH_COLOR_SRGB; otherwise, and always for alpha, t_c = h_c widened (exact).
+ *   matrix   for each output channel i: m = M[i][4]; then m = fmaf(M[i][k], t_k, m) for k = 0, 1, 2, 3 in that order (M = matrix,
+ *            row-major 4 x 5, acting on (r, g, b, a, 1): what feColorMatrix is defined on).  THE ORDER IS STATED HERE: the offset
+ *            first, then r, g, b, a.  0 x Inf is NaN: a texel with an infinite channel makes every row NaN that multiplies it by 0.
+ *   clamp    with JH_COLOR_CLAMP: m = m > 0 ? m : 0, then m = m < 1 ? m : 1 -- compare and select, which sends NaN and -0 to +0.
+ *   round    g = f16(m), round to nearest even, a NaN m gives 0x7e00.  The only rounding to f16 on the device.
+ *   output   out_i = POST_i[g] where channel i has a table, otherwise out_i = g.
+ * The tables have one entry per f16 bit pattern and are built on the host in binary64 (x: the value of the index pattern):
+ *   enc      a = |x|; 12.92 a if a <= 0.0031308, else 1.055 pow(a, 1.0 / 2.4) - 0.055; with x's sign (DESIGN.md 5.3's curve extended
+ *            odd; +-0 keep their sign, +-Inf give +-Inf).  dec: a = |x|; a / 12.92 if a <= 0.04045, else pow((a + 0.055) / 1.055,
+ *            2.4); with x's sign.  pow is the libm call, the rule's only inexact library call, and never runs on the device.
+ *   PRE_c    (float)enc(x), in SRGB space only; a NaN x gives the binary32 NaN 0x7fc00000.  Alpha is never encoded.
+ *   func_i   IDENTITY x; LINEAR slope x + intercept; GAMMA amplitude pow(x, exponent) + offset; TABLE over n values v_0 .. v_n-1
+ *            with N = n - 1: v_0 if N = 0, else c = x > 0 ? x : 0, c = c < 1 ? c : 1, k = min((int)(c N), N - 1), v_k + ((x - k / N)
+ *            N) (v_k+1 - v_k) (Filter Effects' formula; the input is clamped for the index only, so outside [0, 1] the first and the
+ *            last segment go on); DISCRETE: the same c, k = min((int)(c n), n - 1), v_k.  Parameters are binary32, widened.
+ *   POST_i   y = func_i(x); with JH_COLOR_CLAMP y = y > 0 ? y : 0, y = y < 1 ? y : 1; in SRGB space and for i = r, g, b y = dec(y);
+ *            the entry is f16(y), rounded once from binary64; a NaN y and every NaN x give 0x7e00.
+ *   exists   PRE_c in SRGB space; POST_i where func_i is not IDENTITY or dec applies -- a channel whose composition is the
+ *            identity has no table.
+ * So in LINEAR space with IDENTITY funcs and no clamp the identity matrix returns a texel of finite channels unchanged except that
+ * -0 comes out as +0 (m starts at the offset +0); a NaN comes out as 0x7e00, and an infinite channel survives itself and makes the
+ * other three NaN.  In SRGB space the identity is not exact (DESIGN.md 5.10 has the largest deviation).
+ *
+ * jh_color_tables: the tables of desc (its rectangle and matrix are not looked at): PRE_c into pre[c * 65536 ..], POST_i into
+ * post[i * 65536 ..] for the tables that exist -- the entries of the others are left alone -- and into *which bit c for PRE_c and
+ * bit 4 + i for POST_i; each pointer may be NULL.  Host only, no context.  JH_ERR_INVALID for a null desc, an unknown space, func
+ * type or flag bit, n = 0 or n > 64 values, or a parameter that is not finite (only the parameters a func's type uses are read).
+ *
+ * jh_color_filter: the rule applied to the rectangle (x, y, width, height) of src_image_id, written to the same rectangle of
+ * dst_image_id; width == height == 0 means the whole image (which then has to fit into the other one too).  src == dst is legal: the
+ * rule is per texel.  Only the rectangle is written; a dst that was never written is cleared to transparent black first and then
+ * counts as written; a source that was never written reads as transparent black (and so gives the matrix's offsets).
+ * Stream-ordered on the context's stream, never waits: one kernel launch, plus a fill when dst has to be cleared.  A descriptor that
+ * needs no tables (LINEAR space, IDENTITY funcs) touches no scratch and is always capturable.  Otherwise the tables live in a device
+ * slot of the context, which holds the tables of ONE key (space, clamp bit, the four funcs with the values their types use; the
+ * matrix is a kernel argument and no part of it) at a time: a call with the resident key uploads nothing; an eager call with another
+ * builds the tables on the host, uploads them stream-ordered and makes every graph captured before it stale (jh_graph_launch refuses
+ * it).  During a capture a call whose key is resident records its launch; any other is refused with JH_ERR_OOM and the advice to
+ * run this filter once eagerly first.  jh_scratch_trim forgets the key.  With profiling on the call is a query "color" with
+ * stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band).
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts
+ * "jh_color_filter: ": a null desc; an unknown source or destination id; an image that is not RGBA16F; what jh_color_tables refuses;
+ * a matrix entry that is not finite; a rectangle that is not inside both images or that is empty in exactly one dimension; a band
+ * set with jh_set_band. */
+typedef enum jh_color_space { JH_COLOR_LINEAR = 0, JH_COLOR_SRGB = 1 } jh_color_space;
+typedef enum jh_color_func_type {
+    JH_COLOR_FUNC_IDENTITY = 0, JH_COLOR_FUNC_LINEAR = 1, JH_COLOR_FUNC_GAMMA = 2, JH_COLOR_FUNC_TABLE = 3, JH_COLOR_FUNC_DISCRETE = 4
+} jh_color_func_type;
+#define JH_COLOR_CLAMP 1u
+#define JH_COLOR_MAX_VALUES 64u
+#define JH_COLOR_TABLE_ENTRIES 65536u
+typedef struct jh_color_func {
+    int type;                                  /* jh_color_func_type */
+    uint32_t n;                                /* TABLE, DISCRETE: the count of values, 1 .. 64 */
+    float slope, intercept;                    /* LINEAR */
+    float amplitude, exponent, offset;         /* GAMMA */
+    float values[JH_COLOR_MAX_VALUES];         /* TABLE, DISCRETE */
+} jh_color_func;
+typedef struct jh_color_desc {
+    uint32_t x, y, width, height;              /* the rectangle, in both images; width == height == 0: the whole image */
+    float matrix[20];                          /* row-major 4 x 5 on (r, g, b, a, 1) */
+    int space;                                 /* jh_color_space */
+    uint32_t flags;                            /* bit 0: JH_COLOR_CLAMP */
+    jh_color_func func[4];                     /* per output channel r, g, b, a, applied after the matrix */
+} jh_color_desc;
+int jh_color_tables(const jh_color_desc* desc, float* pre /* 3 x 65536 or NULL */, uint16_t* post /* 4 x 65536 or NULL */, uint32_t* which);
+int jh_color_filter(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_color_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

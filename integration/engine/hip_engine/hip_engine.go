@@ -551,6 +551,73 @@ func (e *Engine) Resample(src, dst renderer.ImageProxy, desc ResampleDesc) {
 	e.check(C.jh_resample(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "resample")
 }
 
+// ColorSpace is jh_color_space: the values the matrix and the funcs of ColorFilter act on.
+type ColorSpace int32
+
+const (
+	ColorLinear ColorSpace = 0 // the stored, linear values
+	ColorSRGB   ColorSpace = 1 // colour channels sRGB-encoded before the matrix and decoded after the funcs; alpha never
+)
+
+// ColorFuncType is jh_color_func_type: feComponentTransfer's function types.
+type ColorFuncType int32
+
+const (
+	ColorFuncIdentity ColorFuncType = 0
+	ColorFuncLinear   ColorFuncType = 1 // Slope, Intercept
+	ColorFuncGamma    ColorFuncType = 2 // Amplitude, Exponent, Offset
+	ColorFuncTable    ColorFuncType = 3 // Values, 1..64 of them
+	ColorFuncDiscrete ColorFuncType = 4 // Values, 1..64 of them
+)
+
+// ColorClamp is JH_COLOR_CLAMP: the matrix's result and each func's are clamped to [0, 1].
+const ColorClamp uint32 = 1
+
+// ColorFunc is jh_color_func: the transfer function of one output channel.
+type ColorFunc struct {
+	Type                        ColorFuncType
+	Slope, Intercept            float32
+	Amplitude, Exponent, Offset float32
+	Values                      []float32
+}
+
+// ColorDesc is jh_color_desc (include/jello_hip.h "Colour filter"): the rectangle, in both images (Width == Height == 0: the whole
+// image), the row-major 4 x 5 matrix on the un-premultiplied (r, g, b, a, 1), the space, the flags and the four funcs.
+type ColorDesc struct {
+	X, Y, Width, Height uint32
+	Matrix              [20]float32
+	Space               ColorSpace
+	Flags               uint32
+	Func                [4]ColorFunc
+}
+
+// ColorFilter is jh_color_filter: a colour matrix and per-channel transfer functions on a rectangle of the RGBA16F image src,
+// written to the same rectangle of the RGBA16F image dst (which may be src) by the rule of DESIGN.md 5.10 (defined on values: every
+// implementation gives the same bits).  feColorMatrix, feComponentTransfer, the CSS filter functions, a tint, the first half of a
+// luminance mask.  Stream-ordered behind the frame, waits for nothing, one kernel launch; the context keeps the tables of one key
+// (space, clamp bit, funcs), so a call that repeats the last one's uploads nothing and can be captured; LINEAR space with IDENTITY
+// funcs needs no tables.  More than 64 values in a func are the call's to refuse.
+func (e *Engine) ColorFilter(src, dst renderer.ImageProxy, desc ColorDesc) {
+	d := C.jh_color_desc{x: C.uint32_t(desc.X), y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height),
+		space: C.int(desc.Space), flags: C.uint32_t(desc.Flags)}
+	for i, m := range desc.Matrix {
+		d.matrix[i] = C.float(m)
+	}
+	for i, f := range desc.Func {
+		c := &d._func[i]
+		c._type = C.int(f.Type)
+		c.n = C.uint32_t(len(f.Values))
+		c.slope, c.intercept = C.float(f.Slope), C.float(f.Intercept)
+		c.amplitude, c.exponent, c.offset = C.float(f.Amplitude), C.float(f.Exponent), C.float(f.Offset)
+		for k, v := range f.Values {
+			if k < len(c.values) {
+				c.values[k] = C.float(v)
+			}
+		}
+	}
+	e.check(C.jh_color_filter(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "color_filter")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -153,6 +153,18 @@ class CResampleDesc(ctypes.Structure):
                 ("dst_width", ctypes.c_uint32), ("dst_height", ctypes.c_uint32)]
 
 
+class CColorFunc(ctypes.Structure):
+    """jh_color_func (include/jello_hip.h)."""
+    _fields_ = [("type", ctypes.c_int32), ("n", ctypes.c_uint32), ("slope", ctypes.c_float), ("intercept", ctypes.c_float),
+                ("amplitude", ctypes.c_float), ("exponent", ctypes.c_float), ("offset", ctypes.c_float), ("values", ctypes.c_float * 64)]
+
+
+class CColorDesc(ctypes.Structure):
+    """jh_color_desc (include/jello_hip.h)."""
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("matrix", ctypes.c_float * 20), ("space", ctypes.c_int32), ("flags", ctypes.c_uint32), ("func", CColorFunc * 4)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -222,6 +234,7 @@ def _declare(L):
     L.jl_engine_read_pack.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
     L.jl_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
     L.jl_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.jl_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -263,6 +276,8 @@ def _declare(L):
     hip.jh_composite.argtypes = [vp, u64, u64, ctypes.POINTER(CCompositeDesc)]
     hip.jh_resample.argtypes = [vp, u64, u64, ctypes.POINTER(CResampleDesc)]
     hip.jh_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    hip.jh_color_filter.argtypes = [vp, u64, u64, ctypes.POINTER(CColorDesc)]
+    hip.jh_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

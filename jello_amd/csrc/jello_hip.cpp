@@ -23,6 +23,7 @@
 #include "../../include/jello_blur.h"
 #include "../../include/jello_composite.h"
 #include "../../include/jello_resample.h"
+#include "../../include/jello_color.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -135,6 +136,11 @@ struct jh_ctx {
         uint32_t sw = 0, sh = 0, dw = 0, dh = 0;
         JhResampleTables tables = {};
     } resample;
+    // jh_color_filter: the key whose tables the JH_SCR_COLOR_TABLES slot holds
+    struct {
+        bool valid = false;
+        jcolor_key key = {};
+    } color;
 };
 
 static int flush_held(jh_ctx* ctx);
@@ -1144,7 +1150,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1592,6 +1598,75 @@ int jh_resample(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const
         });
 }
 
+// colour filter (include/jello_hip.h "Colour filter"; the tables: include/jello_color.h; kernels_color.hip)
+int jh_color_tables(const jh_color_desc* desc, float* pre, uint16_t* post, uint32_t* which) {
+    if (!desc || jcolor_desc_error(desc)) return JH_ERR_INVALID;
+    const uint32_t w = jcolor_tables(desc, pre, post);
+    if (which) *which = w;
+    return JH_OK;
+}
+
+int jh_color_filter(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_color_desc* desc) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_color_filter: null descriptor");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_color_filter", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
+    if (const char* why = jcolor_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_color_filter: ") + why);
+    for (float m : desc->matrix)
+        if (!std::isfinite(m)) return fail(ctx, JH_ERR_INVALID, "jh_color_filter: a matrix entry is not finite");
+    uint32_t x = desc->x, y = desc->y, rw = desc->width, rh = desc->height;
+    if (rw == 0u && rh == 0u) { x = 0u; y = 0u; rw = src->width; rh = src->height; }  // the whole image
+    else if (rw == 0u || rh == 0u) return fail(ctx, JH_ERR_INVALID, "jh_color_filter: the rectangle is empty in one dimension");
+    if ((uint64_t)x + rw > src->width || (uint64_t)y + rh > src->height)
+        return fail(ctx, JH_ERR_INVALID, "jh_color_filter: the rectangle is not inside the source image");
+    if ((uint64_t)x + rw > dst->width || (uint64_t)y + rh > dst->height)
+        return fail(ctx, JH_ERR_INVALID, "jh_color_filter: the rectangle is not inside the destination image");
+    if (int rc = refuse_band_mode(ctx, "jh_color_filter", "a band's rows are one rank's, the tables and their key the context's")) return rc;
+    if (rw == 0u || rh == 0u) return JH_OK;  // (an image without texels)
+    const uint32_t which = jcolor_which(desc);
+    jcolor_key key;
+    jcolor_key_of(desc, &key);
+    const bool resident = which == 0u || (ctx->color.valid && jcolor_key_equal(&ctx->color.key, &key));
+    const uint64_t pre_bytes = 3ull * JCOLOR_ENTRIES * sizeof(float), all_bytes = pre_bytes + 4ull * JCOLOR_ENTRIES * sizeof(uint16_t);
+    std::vector<char> blob;
+    if (!resident && !ctx->capturing) {
+        blob.assign(all_bytes, 0);
+        jcolor_tables(desc, (float*)blob.data(), (uint16_t*)(blob.data() + pre_bytes));
+    }
+    char* dev = nullptr;
+    void* staged = nullptr;
+    return post_render_call(
+        ctx, "color",
+        [&] {
+            if (which == 0u) return (int)JH_OK;  // (no tables: the slot is not touched)
+            // (a capture can neither grow an array nor upload: its key has to be resident)
+            if (resident || !ctx->capturing) dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_COLOR_TABLES, all_bytes);
+            if (!dev) return fail(ctx, JH_ERR_OOM, "jh_color_filter: " + scratch_failure(ctx, "run this filter once eagerly first"));
+            if (!resident) {
+                staged = stage_copy(ctx, blob.data(), blob.size());  // the pinned arena, as jh_upload: the DMA is left in flight
+                if (!staged) return fail(ctx, JH_ERR_OOM, "jh_color_filter: pinned staging allocation failed");
+            }
+            return (int)JH_OK;
+        },
+        [&] {  // (the query holds the upload too)
+            const void* from = content_or_null(*src);  // (before dst, which may be the same image, becomes written)
+            if (int rc = first_content(ctx, dst, rw, rh)) return rc;
+            if (!resident) {
+                ctx->color.valid = false;
+                HIP_TRY(ctx, hipMemcpyAsync(dev, staged, all_bytes, hipMemcpyHostToDevice, ctx->stream));
+                ctx->color.key = key;
+                ctx->color.valid = true;
+                ctx->generation++;  // (a graph captured against the tables of another key would read these)
+            }
+            const float* pre = (which & JCOLOR_PRE(0)) ? (const float*)dev : nullptr;
+            const uint16_t* post[4];
+            for (uint32_t i = 0; i < 4u; i++) post[i] = (which & JCOLOR_POST(i)) ? (const uint16_t*)(dev + pre_bytes) + (size_t)i * JCOLOR_ENTRIES : nullptr;
+            return launch_status(ctx, "jh_color_filter",
+                                 jh_color_launch(ctx->stream, from, src->width, src->height, dst->ptr, dst->width, dst->height, x, y, rw, rh, desc->matrix,
+                                                 (desc->flags & JH_COLOR_CLAMP) != 0u, pre, post, ctx->num_cus));
+        });
+}
+
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.
 int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
@@ -1635,7 +1710,7 @@ int jh_debug_poison_scratch(jh_ctx* ctx, int byte) {
     JH_FLUSH(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int i = 0; i < JH_SCR_COUNT; i++) {
-        if (i == JH_SCR_RESAMPLE_TAPS) continue;  // (uploaded content a captured jh_resample reads, not an array a frame fills before it reads it)
+        if (i == JH_SCR_RESAMPLE_TAPS || i == JH_SCR_COLOR_TABLES) continue;  // (uploaded content a captured jh_resample / jh_color_filter reads, not an array a frame fills before it reads it)
         if (ctx->scratch.ptr[i] && ctx->scratch.cap[i]) HIP_TRY(ctx, hipMemsetAsync(ctx->scratch.ptr[i], byte, ctx->scratch.cap[i], ctx->stream));
     }
     ctx->scratch.clean_flags = 0u;
@@ -1701,6 +1776,7 @@ int jh_scratch_trim(jh_ctx* ctx) {
     }
     ctx->scratch.clean_flags = 0;  // (new memory holds anything: every self-cleaned array is filled again on its next use)
     ctx->resample.valid = false;   // (jh_resample's tables went with their slot)
+    ctx->color.valid = false;      // (jh_color_filter's likewise)
     ctx->generation++;
     return JH_OK;
 }

@@ -232,6 +232,8 @@ struct JhImageDesc {
 //   RESAMPLE  (jh_resample, likewise: the binary32 rows between its two passes, source-rectangle rows x destination width x 16 B)
 //   RESAMPLE_TAPS  (jh_resample: the uploaded window and tap tables of both axes for ONE geometry -- content that a captured call
 //              reads on every replay, so nothing else may write the slot; the context keeps the key of what it holds)
+//   COLOR_TABLES   (jh_color_filter, the same contract: the uploaded PRE and POST tables of ONE key, 3 x 65 536 floats then
+//              4 x 65 536 f16 bit patterns, 1.25 MB; a call that needs no tables does not touch the slot)
 enum {
     JH_SCR_SCAN_TMP = 0,
     JH_SCR_A = 1,
@@ -250,7 +252,8 @@ enum {
     JH_SCR_BLUR = 14,    // jh_blur's intermediate
     JH_SCR_RESAMPLE = 15,       // jh_resample's intermediate
     JH_SCR_RESAMPLE_TAPS = 16,  // jh_resample's tables
-    JH_SCR_COUNT = 17
+    JH_SCR_COLOR_TABLES = 17,   // jh_color_filter's tables
+    JH_SCR_COUNT = 18
 };
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
@@ -348,7 +351,7 @@ struct JhResampleTables {
     uint32_t region_x;          // float4 slots of LDS a wave of the row pass needs: jh_resample_skew(longest span - 1) + 1
 };
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses, another negative value for a failed launch.
 extern "C" {
@@ -369,6 +372,9 @@ int jh_composite_launch(hipStream_t stream, const void* src, uint32_t src_w, uin
 int jh_resample_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh,
                        void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t dx, uint32_t dy, uint32_t dw, uint32_t dh, int straight,
                        const JhResampleTables* tables, void* tmp, int num_cus);
+int jh_color_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t x,
+                    uint32_t y, uint32_t rect_w, uint32_t rect_h, const float* matrix, int clamp, const float* pre, const uint16_t* const* post,
+                    int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

@@ -1,0 +1,128 @@
+// kernels_color.hip -- jh_color_filter: a colour matrix and per-channel transfer functions on an RGBA16F image, the device half of the
+// rule in include/jello_hip.h ("Colour filter") and DESIGN.md 5.10; the tables come from the host (include/jello_color.h).  Per texel
+// of the rectangle, binary32:
+//   input    t_c = PRE_c[h_c] for the colour channels where a PRE table is given, else the f16 widened; alpha always widened
+//   matrix   m = M[i][4], then m = fmaf(M[i][k], t_k, m) for k = 0, 1, 2, 3 -- the order include/jello_hip.h states, four fmaf and
+//            nothing else
+//   clamp    m = m > 0 ? m : 0; m = m < 1 ? m : 1 (with the flag; compare and select: NaN and -0 become +0)
+//   round    g = f16(m), a NaN as 0x7e00
+//   output   POST_i[g] where a POST table is given, else g
+// Streaming, as k_composite (kernels_composite.hip): 8 B in and 8 B out per texel, nothing reused, no LDS.  A lane owns two
+// neighbouring texels of a dst row, laid on the row's 16-byte grid (`phase`), so a pair inside the rectangle is one 16-byte store, and
+// one 16-byte load of the source when its own address is aligned too; a row's first or last texel alone is an 8-byte access.  A work
+// item is a row segment of 512 texels = one workgroup of 256 lanes; the grid is bounded by blit_grid_blocks and strides.  src may be
+// dst: a lane reads its texels before it writes them and no other lane touches them.
+// The matrix, the clamp flag and the table pointers are kernel arguments: they sit in scalar registers, and an absent table is a
+// branch on the scalar pipe.  Two instantiations: TABLES = false has no gather (LINEAR space, IDENTITY funcs: feColorMatrix,
+// luminanceToAlpha, a tint); TABLES = true gathers up to 3 x 4 B and 4 x 2 B per texel from tables of 1.25 MB in all.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "blit_convert.h"
+#include "kcommon.h"
+
+namespace {
+
+constexpr uint32_t kColorThreads = 256, kColorSeg = 2u * kColorThreads;  // texels of a work item
+constexpr uint32_t kColorEntries = 65536u;                               // of a table: one per f16 bit pattern
+
+struct ColorParams {  // by value in the kernel arguments
+    float m[20];      // row-major 4 x 5
+    uint32_t clamp;
+    const float* pre;         // PRE_c at pre + c * kColorEntries, or null
+    const uint16_t* post[4];  // POST_i, or null
+};
+
+template <bool TABLES>
+JD uint2 color_texel(uint2 s, const ColorParams& p) {
+    const uint32_t h[4] = {s.x & 0xffffu, s.x >> 16, s.y & 0xffffu, s.y >> 16};
+    float t[4];
+    t[3] = jd::f16_to_f32((uint16_t)h[3]);
+    if (TABLES && p.pre) {
+        for (int c = 0; c < 3; c++) t[c] = p.pre[(uint32_t)c * kColorEntries + h[c]];
+    } else {
+        for (int c = 0; c < 3; c++) t[c] = jd::f16_to_f32((uint16_t)h[c]);
+    }
+    uint32_t g[4];
+    for (int i = 0; i < 4; i++) {
+        float m = p.m[5 * i + 4];
+        for (int k = 0; k < 4; k++) m = __builtin_fmaf(p.m[5 * i + k], t[k], m);
+        if (p.clamp) {
+            m = m > 0.0f ? m : 0.0f;
+            m = m < 1.0f ? m : 1.0f;
+        }
+        g[i] = m != m ? 0x7e00u : (uint32_t)jd::f32_to_f16(m);
+        if (TABLES && p.post[i]) g[i] = p.post[i][g[i]];
+    }
+    return make_uint2(g[0] | (g[1] << 16), g[2] | (g[3] << 16));
+}
+
+// The w x h texels at (x, y) of src (src_w texels per row; null: transparent black) into the same rectangle of dst (dst_w per row).
+// item = row * segs + seg.
+template <bool TABLES>
+__global__ __launch_bounds__(kColorThreads) void k_color(const uint2* src, uint32_t src_w, uint2* dst, uint32_t dst_w, uint32_t x, uint32_t y,
+                                                         uint32_t w, uint32_t segs, uint32_t total_items, ColorParams p) {
+    for (uint32_t it = blockIdx.x; it < total_items; it += gridDim.x) {
+        const uint32_t row = it / segs, seg = it - row * segs;
+        uint2* drow = dst + ((uint64_t)(y + row) * dst_w + x);
+        const uint2* srow = src ? src + ((uint64_t)(y + row) * src_w + x) : nullptr;
+        const uint32_t phase = (uint32_t)(((uintptr_t)drow >> 3) & 1u);
+        const int64_t c = (int64_t)seg * kColorSeg + 2u * threadIdx.x - phase;  // the lane's texels c, c + 1 of the rectangle's row
+        const bool va = c >= 0 && c < (int64_t)w, vb = c + 1 < (int64_t)w;
+        if (!va && !vb) continue;
+        uint2 sa = make_uint2(0u, 0u), sb = sa;
+        if (va && vb) {
+            if (srow) {
+                const uint2* s = srow + c;
+                if (((uintptr_t)s & 15u) == 0u) {  // (the same for every pair of the row)
+                    const uint4 q = *(const uint4*)s;
+                    sa = make_uint2(q.x, q.y);
+                    sb = make_uint2(q.z, q.w);
+                } else {
+                    sa = s[0];
+                    sb = s[1];
+                }
+            }
+            const uint2 oa = color_texel<TABLES>(sa, p), ob = color_texel<TABLES>(sb, p);
+            *(uint4*)(drow + c) = make_uint4(oa.x, oa.y, ob.x, ob.y);
+        } else {  // the row's first or last texel alone
+            const int64_t at = va ? c : c + 1;
+            if (srow) sa = srow[at];
+            drow[at] = color_texel<TABLES>(sa, p);
+        }
+    }
+}
+
+}  // namespace
+
+// The rule on the rect_w x rect_h texels at (x, y) of the src_w x src_h RGBA16F image at src (null: transparent black; may be dst),
+// written to the same rectangle of the dst_w x dst_h image at dst.  matrix: 20 floats, row-major 4 x 5; clamp: JH_COLOR_CLAMP's bit;
+// pre: the three PRE tables of 65 536 floats one after the other, or null; post[i]: POST_i, 65 536 entries, or null.  One launch on
+// `stream`, none for an empty rectangle.  Returns 0, -1 on arguments it refuses, -2 on a launch error.
+extern "C" int jh_color_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h,
+                               uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h, const float* matrix, int clamp, const float* pre,
+                               const uint16_t* const* post, int num_cus) {
+    if (!dst || !matrix || !post) return -1;
+    if ((uint64_t)x + rect_w > src_w || (uint64_t)y + rect_h > src_h || (uint64_t)x + rect_w > dst_w || (uint64_t)y + rect_h > dst_h) return -1;
+    if (rect_w == 0u || rect_h == 0u) return 0;
+    const uint64_t segs = ((uint64_t)rect_w + 1u + kColorSeg - 1u) / kColorSeg;  // (+ 1: the pair grid may start one texel before the row)
+    const uint64_t total = segs * rect_h;
+    if (total > 0x7fffffffull) return -1;
+    ColorParams p;
+    for (int i = 0; i < 20; i++) p.m[i] = matrix[i];
+    p.clamp = clamp ? 1u : 0u;
+    p.pre = pre;
+    bool tables = pre != nullptr;
+    for (int i = 0; i < 4; i++) {
+        p.post[i] = post[i];
+        tables = tables || post[i] != nullptr;
+    }
+    const dim3 grid(blit_grid_blocks(total, num_cus)), block(kColorThreads);
+    const uint2* s = (const uint2*)src;
+    if (tables)
+        hipLaunchKernelGGL(k_color<true>, grid, block, 0, stream, s, src_w, (uint2*)dst, dst_w, x, y, rect_w, (uint32_t)segs, (uint32_t)total, p);
+    else
+        hipLaunchKernelGGL(k_color<false>, grid, block, 0, stream, s, src_w, (uint2*)dst, dst_w, x, y, rect_w, (uint32_t)segs, (uint32_t)total, p);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}

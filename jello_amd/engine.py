@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CCompositeDesc, CConfig, CProfileNode, CProfileRecord, CResampleDesc, CYuvDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CProfileNode, CProfileRecord, CResampleDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -132,6 +132,75 @@ def _resample_desc(filter, src_rect, dst_rect, premultiplied):
     sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
     dx, dy, dw, dh = (0, 0, 0, 0) if dst_rect is None else dst_rect
     return CResampleDesc(int(filter), 0 if premultiplied else RESAMPLE_STRAIGHT, int(sx), int(sy), int(sw), int(sh), int(dx), int(dy), int(dw), int(dh))
+
+
+class ColorSpace(enum.IntEnum):
+    """jh_color_space: the values the matrix and the funcs of jh_color_filter act on -- the stored linear ones,
+    or the colour channels sRGB-encoded (what the CSS filter functions are defined on); alpha is never encoded."""
+    LINEAR = 0
+    SRGB = 1
+
+
+class ColorFunc(enum.IntEnum):
+    """jh_color_func_type: feComponentTransfer's function types."""
+    IDENTITY = 0
+    LINEAR = 1
+    GAMMA = 2
+    TABLE = 3
+    DISCRETE = 4
+
+
+COLOR_CLAMP = 1  # JH_COLOR_CLAMP
+COLOR_MAX_VALUES = 64  # JH_COLOR_MAX_VALUES
+COLOR_POST_SHIFT = 4  # jh_color_tables' `which`: bit c is PRE_c, bit 4 + i is POST_i
+IDENTITY_MATRIX = (1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def _color_desc(matrix, funcs, space, clamp, rect):
+    """jh_color_desc.  `funcs`: None or four entries, each None (IDENTITY) or (ColorFunc.LINEAR, slope, intercept),
+    (ColorFunc.GAMMA, amplitude, exponent, offset), (ColorFunc.TABLE, values), (ColorFunc.DISCRETE, values) -- what
+    colorfilter.linear / gamma / table / discrete return.  What the rule refuses is left for the call to refuse, except a value
+    list that does not fit the struct."""
+    d = CColorDesc()
+    d.x, d.y, d.width, d.height = (0, 0, 0, 0) if rect is None else [int(v) for v in rect]
+    m = np.asarray(IDENTITY_MATRIX if matrix is None else matrix, np.float32).reshape(-1)
+    if m.size != 20:
+        raise ValueError("color_filter: the matrix has 20 entries (row-major 4 x 5)")
+    d.matrix[:] = [float(v) for v in m]
+    d.space, d.flags = int(space), COLOR_CLAMP if clamp else 0
+    funcs = (None,) * 4 if funcs is None else tuple(funcs)
+    if len(funcs) != 4:
+        raise ValueError("color_filter: four funcs, one per output channel")
+    for i, f in enumerate(funcs):
+        if f is None:
+            continue
+        c, kind = d.func[i], int(f[0])
+        c.type = kind
+        if kind == ColorFunc.LINEAR:
+            c.slope, c.intercept = float(f[1]), float(f[2])
+        elif kind == ColorFunc.GAMMA:
+            c.amplitude, c.exponent, c.offset = float(f[1]), float(f[2]), float(f[3])
+        elif kind in (ColorFunc.TABLE, ColorFunc.DISCRETE):
+            values = [float(v) for v in f[1]]
+            c.n = len(values)  # (0 and more than 64 are the call's to refuse; only 64 fit the struct)
+            c.values[:min(len(values), COLOR_MAX_VALUES)] = values[:COLOR_MAX_VALUES]
+    return d
+
+
+def color_tables(funcs=None, space=ColorSpace.LINEAR, clamp=True, twin=False):
+    """jh_color_tables (twin: jl_color_tables, the host twin): the tables of the colour-filter rule for these
+    funcs, space and clamp setting, one entry per f16 bit pattern: (pre, post, which) -- pre a dict {channel: float32 [65536]},
+    post a dict {channel: uint16 [65536]} of the tables that exist, which the bit mask.  No GPU needed.  ValueError for what the
+    rule refuses."""
+    L = _lib.load_host()
+    d = _color_desc(None, funcs, space, clamp, None)
+    pre, post = np.zeros((3, 65536), np.float32), np.zeros((4, 65536), np.uint16)
+    which = ctypes.c_uint32(0)
+    f = L.jl_color_tables if twin else L.hip.jh_color_tables
+    if f(ctypes.byref(d), pre.ctypes.data, post.ctypes.data, ctypes.byref(which)) != 0:
+        raise ValueError("color_tables: unknown space or func type, n = 0 or n > 64 values, or a parameter that is not finite")
+    w = which.value
+    return ({c: pre[c] for c in range(3) if w >> c & 1}, {i: post[i] for i in range(4) if w >> (COLOR_POST_SHIFT + i) & 1}, w)
 
 
 def composite_clip(src_size, dst_size, src_rect=None, offset=(0, 0)):
@@ -441,6 +510,28 @@ class Engine:
         d = _resample_desc(filter, src_rect, dst_rect, premultiplied)
         self._check(self.hip.jh_resample(self.ctx, src_id, dst_id, ctypes.byref(d)), "resample", invalid=ValueError)
 
+    def color_filter(self, src_id, dst_id=None, matrix=None, funcs=None, space=ColorSpace.LINEAR, clamp=True, rect=None):
+        """jh_color_filter: a colour matrix and per-channel transfer functions (the rule: DESIGN.md 5.10) on the rectangle `rect` =
+        (x, y, width, height) of the RGBA16F image `src_id` (None: the whole image), written to the same rectangle of `dst_id` --
+        None: in place.  `matrix`: 20 values, row-major 4 x 5 on the un-premultiplied (r, g, b, a, 1) (None: the identity);
+        `funcs`: None or four entries as colorfilter.linear / gamma / table / discrete make them (None: IDENTITY), applied after
+        the matrix; `space`: ColorSpace.SRGB encodes the colour channels before the matrix and decodes them after the funcs;
+        `clamp`: the matrix's result and each func's are clamped to [0, 1].  jello_amd.colorfilter has the Filter Effects
+        constructors, each the keywords of this call.  The context holds the tables of one (funcs, space, clamp): a call with
+        another uploads its own and makes graphs captured before it stale; LINEAR space without funcs needs none.
+        Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _color_desc(matrix, funcs, space, clamp, rect)
+        dst = src_id if dst_id is None else dst_id
+        self._check(self.hip.jh_color_filter(self.ctx, src_id, dst, ctypes.byref(d)), "color_filter", invalid=ValueError)
+
+    def luminance_mask(self, layer_id, mask_id, scratch_id):
+        """`mask-type: luminance`, two calls: color_filter(mask -> scratch, luminance_to_alpha): the mask's luminance becomes the
+        scratch's alpha; composite(scratch -> layer, DstIn): the layer is kept where that alpha is.  Three RGBA16F images; the
+        scratch is at least as large as the mask and its content is overwritten."""
+        from . import colorfilter
+        self.color_filter(mask_id, scratch_id, **colorfilter.luminance_to_alpha())
+        self.composite(scratch_id, layer_id, compose=Compose.DestIn)
+
     def drop_shadow(self, layer_id, target_id, width, height, sigma, offset, color, scratch_image_id):
         """A layer with its drop shadow onto a target, three calls: blur(layer -> scratch, edge ZERO); composite(scratch -> target,
         tint=color, offset): the blurred alpha in the shadow's colour, shifted; composite(layer -> target).  `layer_id` and
@@ -551,7 +642,7 @@ class Engine:
             out.append(p)
         return out
 
-    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None):
+    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -568,7 +659,10 @@ class Engine:
         resample=dict(dst=image id, width=..., height=..., ...) (the other keywords of resample(), optional) resizes the frame's
         target into the RGBA16F image `dst` of width x height after the blur and the composite (two more launches); the surface,
         YUV or pack conversion of the same capture then reads that image at its size.  This geometry must have been resampled once
-        eagerly, and no other since."""
+        eagerly, and no other since.
+        color=dict(...) (the keywords of color_filter() but the ids, e.g. **colorfilter.grayscale(1)) filters the frame's target
+        in place after the blur and the composite and before the resample (one more launch); a filter that needs tables must have
+        run once eagerly, and no other such filter since."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
@@ -577,6 +671,8 @@ class Engine:
                 self.blur(t["id"], t["width"], t["height"], blur["sigma"], edge=blur.get("edge", BlurEdge.ZERO), rect=blur.get("rect"))
             if composite is not None:
                 self.composite(composite["src"], t["id"], **{k: v for k, v in composite.items() if k != "src"})
+            if color is not None:
+                self.color_filter(t["id"], **color)
             if resample is not None:
                 self.resample(t["id"], resample["dst"], **{k: v for k, v in resample.items() if k not in ("dst", "width", "height")})
                 t = {"id": resample["dst"], "width": resample["width"], "height": resample["height"]}

@@ -9,6 +9,7 @@
 #include "../../include/jello_blur.h"
 #include "../../include/jello_composite.h"
 #include "../../include/jello_resample.h"
+#include "../../include/jello_color.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -455,6 +456,18 @@ int jl_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, floa
     if (n == 0u) { g_err = "resample_taps: a window without taps"; return -1; }
     if (first) *first = f;
     if (count) *count = n;
+    return 0;
+}
+
+// jl_color_tables is the host twin of jh_color_tables (the rule is in jello_hip.h and DESIGN.md 5.10): the same header, compiled here
+// by the host compiler -- the PRE tables of desc into pre (3 x 65 536 floats; or null), its POST tables into post (4 x 65 536 f16 bit
+// patterns; or null), only those that exist, and which they are into *which (bit c: PRE_c, bit 4 + i: POST_i); -1 for a descriptor
+// the rule refuses.
+int jl_color_tables(const jh_color_desc* desc, float* pre, uint16_t* post, uint32_t* which) {
+    const char* why = desc ? jcolor_desc_error(desc) : "null descriptor";
+    if (why) { g_err = std::string("color_tables: ") + why; return -1; }
+    const uint32_t w = jcolor_tables(desc, pre, post);
+    if (which) *which = w;
     return 0;
 }
 
