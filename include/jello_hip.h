@@ -25,6 +25,7 @@
  *   jh_resample                       (no counterpart: an RGBA16F image resized on the device, four filters)
  *   jh_composite                      (no counterpart: one RGBA16F image blended onto another on the device)
  *   jh_color_filter                   (no counterpart: colour matrix and transfer functions on an RGBA16F image)
+ *   jh_morphology                     (no counterpart: erode / dilate of an RGBA16F image by a box on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -590,6 +591,69 @@ typedef struct jh_color_desc {
 } jh_color_desc;
 int jh_color_tables(const jh_color_desc* desc, float* pre /* 3 x 65536 or NULL */, uint16_t* post /* 4 x 65536 or NULL */, uint32_t* which);
 int jh_color_filter(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_color_desc* desc);
+
+/* ---- Morphology: erode and dilate of an RGBA16F image by a box (DESIGN.md 5.11 "Morphology rule") ----
+ * A shadow with spread, an outline or halo around text, a matte choked before compositing, opening and closing a mask,
+ * feMorphology -- without the image leaving the device.  The result is defined on values, and every implementation produces these
+ * bits (include/jello_morph.h states the host half and the order key, tests/morph_ref.py restates all of it).
+ *   arguments   op: JH_MORPH_ERODE = 0 | JH_MORPH_DILATE = 1.  radius_x, radius_y: integers in [0, JH_MORPH_MAX_RADIUS = 255].
+ *               edge: JH_MORPH_EDGE_ZERO = 0 | JH_MORPH_EDGE_CLAMP = 1.  flags: bit 0, JH_MORPH_STRAIGHT.  The rectangle (x, y, width,
+ *               height) of dst is written; width == height == 0 means the whole image (x and y are then ignored).
+ *   operand     the f16 texel widened to binary32 (c, a); p = (c.r a, c.g a, c.b a, a), each product of two f16 values exact in
+ *               binary32: the premultiplied colour feMorphology is defined on.  With JH_MORPH_STRAIGHT p = (c, a) as stored, for
+ *               data images and masks.
+ *   window      output texel (X, Y) of the rectangle takes the image positions [X - rx, X + rx] x [Y - ry, Y + ry], the box
+ *               structuring element of feMorphology.  The IMAGE is the edge, not the rectangle: source texels outside the rectangle
+ *               but inside the image take part with their real values.  A position outside the image: EDGE_ZERO: it takes part as
+ *               transparent black, +0.0f in all four channels (an erode eats the shape at the image's border, as the specification
+ *               has it); EDGE_CLAMP: it does not take part -- the window is clipped to the image, which is what reading the nearest
+ *               texel gives for an idempotent operator.  A source that was never written reads as transparent black.
+ *   order       per channel, independently, on binary32.  If any operand of the window is a NaN (either sign) the result is a NaN.
+ *               Otherwise DILATE is the greatest and ERODE the least operand in IEEE 754 totalOrder (-Inf < ... < -0 < +0 < ... <
+ *               +Inf; -0 and +0 are different values and +0 is the greater).  As integer keys: k = bits ^ ((int32)bits >> 31 &
+ *               0x7fffffff) compared as signed, a NaN mapped to the extreme the operator selects.  Nothing else is computed: the
+ *               result is one of the operands, no rounding occurs and no evaluation order has to be fixed.  THE RESULT IS DEFINED ON
+ *               THE WINDOW, NOT ON PASSES: rows then columns, block prefix / suffix extrema and doubling all give these bits, and
+ *               the implementation is free to choose.
+ *   store       STRAIGHT: f16(V) per channel, exact (V is a widened f16).  Otherwise as fine, jh_composite and jh_resample store:
+ *               a_inv = 1.0f / max(V.a, 1e-6f); (f16(V.r a_inv + 0.0f), f16(V.g a_inv + 0.0f), f16(V.b a_inv + 0.0f), f16(V.a +
+ *               0.0f)), round to nearest even.
+ *   values      f16 subnormals are values, in and out.  Inf x 0 in the premultiply is a NaN and propagates.  A NaN result is any NaN.
+ * So STRAIGHT with rx = ry = 0 is a bit-exact copy of every non-NaN value, -0 included (unlike the blur); without STRAIGHT radius 0
+ * leaves the store's rounding of c a / a.  STRAIGHT erode equals the sign-flipped dilate of the sign-flipped image: exactly under
+ * CLAMP; under ZERO the flipped route pads with -0 seen from the original, so the two differ exactly in the channels whose window
+ * reaches outside the image and holds no operand below +0 inside it -- erode gives +0 there (the padding), the flipped route -0 --
+ * and nowhere else.  Under CLAMP dilate >= source >= erode in the order, texel by texel; on values (STRAIGHT) both are the identity
+ * at radius 0, hence idempotent there, and monotone in the radius; erode by r then dilate by r never exceeds the source.
+ *
+ * jh_morphology: the rule applied to src_image_id, written to the rectangle of dst_image_id.  The images carry their own sizes and
+ * must be JL_RGBA16_FLOAT and of equal size.  dst_image_id may equal src_image_id: in place, with the result of the call into a
+ * second image (no pass reads what the call has written).  Texels of dst outside the rectangle keep their bits; a dst that was never
+ * written is cleared to transparent black first and then counts as written.
+ * Stream-ordered on the context's stream, never waits: THREE kernel launches (rows into a plane of keys; the block prefix of its
+ * columns into a second plane; the block suffix, the combination and the store), plus a fill when dst has to be cleared.  None of
+ * them walks a window: the cost per texel does not grow with the radius beyond the row pass's log2(2 rx + 1) doubling steps.  The
+ * two planes live in a scratch array of the context, 2 x (rect height + 2 radius_y) x rect width x 16 bytes, which only grows: the
+ * call may be captured between jh_graph_begin and jh_graph_end once a call of this rectangle size and these radii has run eagerly (a
+ * capture that would have to grow it is refused with JH_ERR_OOM and that advice).  With profiling on the call is a query
+ * "morphology" with stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band): the rows next to a band belong to
+ * another rank's context.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_morphology: ": a
+ * null desc; an unknown source or destination id; an image that is not RGBA16F; images of different size; an unknown op, edge or flag
+ * bit; a radius above 255; a rectangle that is not inside the image or that is empty in exactly one dimension; a band set with
+ * jh_set_band. */
+typedef enum jh_morph_op { JH_MORPH_ERODE = 0, JH_MORPH_DILATE = 1 } jh_morph_op;
+typedef enum jh_morph_edge { JH_MORPH_EDGE_ZERO = 0, JH_MORPH_EDGE_CLAMP = 1 } jh_morph_edge;
+#define JH_MORPH_STRAIGHT 1u
+#define JH_MORPH_MAX_RADIUS 255u
+typedef struct jh_morph_desc {
+    int op;                        /* jh_morph_op */
+    int edge;                      /* jh_morph_edge */
+    uint32_t flags;                /* bit 0: JH_MORPH_STRAIGHT */
+    uint32_t radius_x, radius_y;
+    uint32_t x, y, width, height;  /* rectangle of dst that is written; 0 x 0: the whole image */
+} jh_morph_desc;
+int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_morph_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -618,6 +618,46 @@ func (e *Engine) ColorFilter(src, dst renderer.ImageProxy, desc ColorDesc) {
 	e.check(C.jh_color_filter(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "color_filter")
 }
 
+// MorphOp is jh_morph_op: the least (erode) or the greatest (dilate) operand of the window.
+type MorphOp int32
+
+const (
+	MorphErode  MorphOp = 0
+	MorphDilate MorphOp = 1
+)
+
+// MorphEdge is jh_morph_edge: what a position outside the image is.
+type MorphEdge int32
+
+const (
+	MorphEdgeZero  MorphEdge = 0 // transparent black takes part (feMorphology)
+	MorphEdgeClamp MorphEdge = 1 // the position does not take part
+)
+
+// MorphStraight is JH_MORPH_STRAIGHT: the operands are the four channels as stored, not colour times alpha.
+const MorphStraight uint32 = 1
+
+// MorphDesc is jh_morph_desc (include/jello_hip.h "Morphology"): the operator, the edge mode, the flags, the radii (0..255 each) and
+// the rectangle of dst that is written (Width == Height == 0: the whole image).
+type MorphDesc struct {
+	Op                  MorphOp
+	Edge                MorphEdge
+	Flags               uint32
+	RadiusX, RadiusY    uint32
+	X, Y, Width, Height uint32
+}
+
+// Morphology is jh_morphology: the RGBA16F image src eroded or dilated by a box of (2 RadiusX + 1) x (2 RadiusY + 1) texels into the
+// rectangle of the RGBA16F image dst of the same size (which may be src) by the rule of DESIGN.md 5.11 (defined on values: every
+// implementation gives the same bits).  A shadow's spread, an outline, a choked matte, feMorphology.  Stream-ordered behind the frame,
+// waits for nothing, three kernel launches whatever the radius; the intermediate lives in a scratch array of the context that only
+// grows, so a call can be captured once one of its rectangle size and radii has run eagerly.
+func (e *Engine) Morphology(src, dst renderer.ImageProxy, desc MorphDesc) {
+	d := C.jh_morph_desc{op: C.int(desc.Op), edge: C.int(desc.Edge), flags: C.uint32_t(desc.Flags), radius_x: C.uint32_t(desc.RadiusX),
+		radius_y: C.uint32_t(desc.RadiusY), x: C.uint32_t(desc.X), y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height)}
+	e.check(C.jh_morphology(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "morphology")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -165,6 +165,13 @@ class CColorDesc(ctypes.Structure):
                 ("matrix", ctypes.c_float * 20), ("space", ctypes.c_int32), ("flags", ctypes.c_uint32), ("func", CColorFunc * 4)]
 
 
+class CMorphDesc(ctypes.Structure):
+    """jh_morph_desc (include/jello_hip.h)."""
+    _fields_ = [("op", ctypes.c_int32), ("edge", ctypes.c_int32), ("flags", ctypes.c_uint32), ("radius_x", ctypes.c_uint32),
+                ("radius_y", ctypes.c_uint32), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -278,6 +285,7 @@ def _declare(L):
     hip.jh_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     hip.jh_color_filter.argtypes = [vp, u64, u64, ctypes.POINTER(CColorDesc)]
     hip.jh_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
+    hip.jh_morphology.argtypes = [vp, u64, u64, ctypes.POINTER(CMorphDesc)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

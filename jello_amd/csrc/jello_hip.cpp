@@ -24,6 +24,7 @@
 #include "../../include/jello_composite.h"
 #include "../../include/jello_resample.h"
 #include "../../include/jello_color.h"
+#include "../../include/jello_morph.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -1150,7 +1151,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1664,6 +1665,41 @@ int jh_color_filter(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, c
             return launch_status(ctx, "jh_color_filter",
                                  jh_color_launch(ctx->stream, from, src->width, src->height, dst->ptr, dst->width, dst->height, x, y, rw, rh, desc->matrix,
                                                  (desc->flags & JH_COLOR_CLAMP) != 0u, pre, post, ctx->num_cus));
+        });
+}
+
+// morphology (include/jello_hip.h "Morphology"; the descriptor, the planes and the key: include/jello_morph.h; kernels_morph.hip)
+int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_morph_desc* desc) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_morphology: null descriptor");
+    static_assert(JH_MORPH_ERODE == JMORPH_ERODE && JH_MORPH_DILATE == JMORPH_DILATE && JH_MORPH_EDGE_ZERO == JMORPH_EDGE_ZERO &&
+                      JH_MORPH_EDGE_CLAMP == JMORPH_EDGE_CLAMP && JH_MORPH_STRAIGHT == JMORPH_STRAIGHT && JH_MORPH_MAX_RADIUS == JMORPH_MAX_RADIUS,
+                  "the C ABI's values are the rule's");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_morphology", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
+    if (src->width != dst->width || src->height != dst->height) return fail(ctx, JH_ERR_INVALID, "jh_morphology: the images differ in size");
+    const uint32_t width = dst->width, height = dst->height;
+    if (const char* why = jmorph_desc_error(desc->op, desc->edge, desc->flags, desc->radius_x, desc->radius_y, desc->x, desc->y, desc->width, desc->height, width, height))
+        return fail(ctx, JH_ERR_INVALID, std::string("jh_morphology: ") + why);
+    if (int rc = refuse_band_mode(ctx, "jh_morphology", "the rows next to a band belong to another rank")) return rc;
+    const jmorph_rect r = jmorph_resolve(desc->x, desc->y, desc->width, desc->height, width, height);
+    void* tmp = nullptr;
+    return post_render_call(
+        ctx, "morphology",
+        [&] {
+            if (r.w == 0u || r.h == 0u) return (int)JH_OK;  // (an image without texels)
+            tmp = jh_scratch_get(&ctx->scratch, JH_SCR_MORPH, jmorph_scratch_bytes(r.w, r.h, desc->radius_y));
+            if (tmp) return (int)JH_OK;
+            return fail(ctx, JH_ERR_OOM, "jh_morphology: " + scratch_failure(ctx, "run a call of this rectangle size and these radii once eagerly first"));
+        },
+        [&] {
+            if (r.w == 0u || r.h == 0u) return (int)JH_OK;
+            const void* from = content_or_null(*src);  // (before dst, which may be the same image, becomes written)
+            if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
+            return launch_status(ctx, "jh_morphology",
+                                 jh_morph_launch(ctx->stream, from, dst->ptr, width, height, r.x, r.y, r.w, r.h, desc->op == JH_MORPH_DILATE,
+                                                 desc->edge == JH_MORPH_EDGE_CLAMP, (desc->flags & JH_MORPH_STRAIGHT) != 0u, desc->radius_x, desc->radius_y, tmp,
+                                                 ctx->num_cus));
         });
 }
 

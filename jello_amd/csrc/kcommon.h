@@ -234,6 +234,8 @@ struct JhImageDesc {
 //              reads on every replay, so nothing else may write the slot; the context keeps the key of what it holds)
 //   COLOR_TABLES   (jh_color_filter, the same contract: the uploaded PRE and POST tables of ONE key, 3 x 65 536 floats then
 //              4 x 65 536 f16 bit patterns, 1.25 MB; a call that needs no tables does not touch the slot)
+//   MORPH     (jh_morphology, as BLUR: the two planes of order keys between its three passes, each (rect height + 2 radius_y) x
+//              rect width x 16 B; it only grows and nothing else writes it, so a captured call stays valid)
 enum {
     JH_SCR_SCAN_TMP = 0,
     JH_SCR_A = 1,
@@ -253,7 +255,8 @@ enum {
     JH_SCR_RESAMPLE = 15,       // jh_resample's intermediate
     JH_SCR_RESAMPLE_TAPS = 16,  // jh_resample's tables
     JH_SCR_COLOR_TABLES = 17,   // jh_color_filter's tables
-    JH_SCR_COUNT = 18
+    JH_SCR_MORPH = 18,          // jh_morphology's intermediate planes
+    JH_SCR_COUNT = 19
 };
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
@@ -351,7 +354,7 @@ struct JhResampleTables {
     uint32_t region_x;          // float4 slots of LDS a wave of the row pass needs: jh_resample_skew(longest span - 1) + 1
 };
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses, another negative value for a failed launch.
 extern "C" {
@@ -375,6 +378,8 @@ int jh_resample_launch(hipStream_t stream, const void* src, uint32_t src_w, uint
 int jh_color_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t x,
                     uint32_t y, uint32_t rect_w, uint32_t rect_h, const float* matrix, int clamp, const float* pre, const uint16_t* const* post,
                     int num_cus);
+int jh_morph_launch(hipStream_t stream, const void* src, void* dst, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t rect_w,
+                    uint32_t rect_h, int dilate, int clamp, int straight, uint32_t radius_x, uint32_t radius_y, void* tmp, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

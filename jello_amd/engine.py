@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CProfileNode, CProfileRecord, CResampleDesc, CYuvDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -132,6 +132,30 @@ def _resample_desc(filter, src_rect, dst_rect, premultiplied):
     sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
     dx, dy, dw, dh = (0, 0, 0, 0) if dst_rect is None else dst_rect
     return CResampleDesc(int(filter), 0 if premultiplied else RESAMPLE_STRAIGHT, int(sx), int(sy), int(sw), int(sh), int(dx), int(dy), int(dw), int(dh))
+
+
+class MorphOp(enum.IntEnum):
+    """jh_morph_op: the least (ERODE) or the greatest (DILATE) operand of the window."""
+    ERODE = 0
+    DILATE = 1
+
+
+class MorphEdge(enum.IntEnum):
+    """jh_morph_edge: a position outside the image takes part as transparent black (ZERO) or not at all (CLAMP)."""
+    ZERO = 0
+    CLAMP = 1
+
+
+MORPH_STRAIGHT = 1  # JH_MORPH_STRAIGHT
+MORPH_MAX_RADIUS = 255  # JH_MORPH_MAX_RADIUS
+
+
+def _morph_desc(op, radius, edge, rect, premultiplied):
+    rx, ry = radius if isinstance(radius, (tuple, list)) else (radius, radius)
+    x, y, w, h = (0, 0, 0, 0) if rect is None else rect
+    if not (0 <= int(rx) <= MORPH_MAX_RADIUS and 0 <= int(ry) <= MORPH_MAX_RADIUS):
+        raise ValueError("jh_morphology: a radius above 255 or below 0")
+    return CMorphDesc(int(op), int(edge), 0 if premultiplied else MORPH_STRAIGHT, int(rx), int(ry), int(x), int(y), int(w), int(h))
 
 
 class ColorSpace(enum.IntEnum):
@@ -524,6 +548,27 @@ class Engine:
         dst = src_id if dst_id is None else dst_id
         self._check(self.hip.jh_color_filter(self.ctx, src_id, dst, ctypes.byref(d)), "color_filter", invalid=ValueError)
 
+    def morphology(self, src_id, dst_id=None, op=MorphOp.DILATE, radius=1, edge=MorphEdge.ZERO, rect=None, premultiplied=True):
+        """jh_morphology: the RGBA16F image `src_id` eroded or dilated by a box (the rule: DESIGN.md 5.11) into the image `dst_id`
+        of the same size -- None: in place.  `radius` is a scalar or (rx, ry), integers in [0, 255]: the window of a texel is
+        (2 rx + 1) x (2 ry + 1).  `edge`: what a position outside the image is (MorphEdge).  `rect` = (x, y, width, height) is the
+        rectangle of the destination that is written (None: the whole image); texels outside it keep their bits, source texels
+        outside it take part.  `premultiplied`: the operands are colour times alpha, what feMorphology is defined on (the default);
+        False takes the four channels as they are stored (JH_MORPH_STRAIGHT: data images, masks).  Stream-ordered, returns nothing;
+        ValueError for a call the rule refuses."""
+        d = _morph_desc(op, radius, edge, rect, premultiplied)
+        dst = src_id if dst_id is None else dst_id
+        self._check(self.hip.jh_morphology(self.ctx, src_id, dst, ctypes.byref(d)), "morphology", invalid=ValueError)
+
+    def outline(self, layer_id, target_id, radius, color, scratch_image_id):
+        """A layer with an outline (a halo) of `radius` texels onto a target, three calls: morphology(layer -> scratch, DILATE, edge
+        ZERO); composite(scratch -> target, tint=color): the grown alpha in the outline's colour; composite(layer -> target).
+        `layer_id` and `scratch_image_id` are RGBA16F images of one size (the scratch's content is overwritten), `color` =
+        (r, g, b, a)."""
+        self.morphology(layer_id, scratch_image_id, op=MorphOp.DILATE, radius=radius, edge=MorphEdge.ZERO)
+        self.composite(scratch_image_id, target_id, tint=color)
+        self.composite(layer_id, target_id)
+
     def luminance_mask(self, layer_id, mask_id, scratch_id):
         """`mask-type: luminance`, two calls: color_filter(mask -> scratch, luminance_to_alpha): the mask's luminance becomes the
         scratch's alpha; composite(scratch -> layer, DstIn): the layer is kept where that alpha is.  Three RGBA16F images; the
@@ -532,11 +577,17 @@ class Engine:
         self.color_filter(mask_id, scratch_id, **colorfilter.luminance_to_alpha())
         self.composite(scratch_id, layer_id, compose=Compose.DestIn)
 
-    def drop_shadow(self, layer_id, target_id, width, height, sigma, offset, color, scratch_image_id):
+    def drop_shadow(self, layer_id, target_id, width, height, sigma, offset, color, scratch_image_id, spread=0):
         """A layer with its drop shadow onto a target, three calls: blur(layer -> scratch, edge ZERO); composite(scratch -> target,
         tint=color, offset): the blurred alpha in the shadow's colour, shifted; composite(layer -> target).  `layer_id` and
-        `scratch_image_id` are RGBA16F images of width x height (the scratch's content is overwritten), `color` = (r, g, b, a)."""
-        self.blur(layer_id, width, height, sigma, dst_image_id=scratch_image_id, edge=BlurEdge.ZERO)
+        `scratch_image_id` are RGBA16F images of width x height (the scratch's content is overwritten), `color` = (r, g, b, a).
+        `spread` > 0 (a scalar or (rx, ry), CSS box-shadow's spread radius) grows the layer first, four calls: morphology(layer ->
+        scratch, DILATE, edge ZERO), then the scratch is blurred in place."""
+        if any(int(r) != 0 for r in (spread if isinstance(spread, (tuple, list)) else (spread,))):
+            self.morphology(layer_id, scratch_image_id, op=MorphOp.DILATE, radius=spread, edge=MorphEdge.ZERO)
+            self.blur(scratch_image_id, width, height, sigma, edge=BlurEdge.ZERO)
+        else:
+            self.blur(layer_id, width, height, sigma, dst_image_id=scratch_image_id, edge=BlurEdge.ZERO)
         self.composite(scratch_image_id, target_id, tint=color, offset=offset)
         self.composite(layer_id, target_id)
 
@@ -642,7 +693,8 @@ class Engine:
             out.append(p)
         return out
 
-    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None):
+    def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
+                morphology=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -662,11 +714,17 @@ class Engine:
         eagerly, and no other since.
         color=dict(...) (the keywords of color_filter() but the ids, e.g. **colorfilter.grayscale(1)) filters the frame's target
         in place after the blur and the composite and before the resample (one more launch); a filter that needs tables must have
-        run once eagerly, and no other such filter since."""
+        run once eagerly, and no other such filter since.
+        morphology=dict(...) (the keywords of morphology() but the ids) erodes or dilates the frame's target in place, after the
+        render and BEFORE the blur (three more launches) -- the order of a shadow with spread; a call of this rectangle size and
+        these radii must have run once eagerly.  So the order of a capture is: render, morphology, blur, composite, color,
+        resample, then the surface, YUV or pack conversion."""
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
             t = recording.target
+            if morphology is not None:
+                self.morphology(t["id"], **morphology)
             if blur is not None:
                 self.blur(t["id"], t["width"], t["height"], blur["sigma"], edge=blur.get("edge", BlurEdge.ZERO), rect=blur.get("rect"))
             if composite is not None:
