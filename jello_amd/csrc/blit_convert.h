@@ -1,6 +1,6 @@
 // blit_convert.h -- the per-pixel conversion rule shared by jh_blit (kernels_surface.hip) and jh_blit_yuv (kernels_yuv.hip):
 // premultiply in f32, clamp with NaN -> 0, then rint_f32(v * 255) or the sRGB threshold table (include/jello_hip.h, DESIGN.md
-// "Surface blit"), and the grid rule of the two launchers.  Every function is internal to the file that includes it.
+// "Surface blit").  Every function is internal to the file that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,13 +55,6 @@ __device__ __forceinline__ uint32_t blit_pixel(uint2 t, const float2* lut) {
 // (threshold of code i, threshold of code i + 1).
 __device__ __forceinline__ void blit_srgb_lut_fill(float2* lut, uint32_t i) {
     lut[i] = make_float2(i == 0u ? 0.0f : kSrgbEncodeThreshold[i - 1u], i == 255u ? __builtin_huge_valf() : kSrgbEncodeThreshold[i]);
-}
-
-// Blocks to launch for `total` blocks of work.  Memory-bound: at most 8 resident blocks of 256 per CU, the rest by grid stride (the
-// sRGB table is loaded once per block).
-inline uint32_t blit_grid_blocks(uint64_t total, int num_cus) {
-    const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * 8u;
-    return (uint32_t)(total < cap ? total : cap);
 }
 
 }  // namespace

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "kcommon.h"
+#include "texel_io.h"
 
 namespace {
 
@@ -28,12 +29,6 @@ struct BlurTaps { float w[kTapSlots]; };           // by value in the kernel arg
 constexpr uint32_t kRowSeg = 256;                  // k_blur_rows: output texels of a wave's row segment (64 lanes x 4)
 constexpr uint32_t kColStrip = 128, kColRows = 8;  // k_blur_cols: a wave's item is 128 columns (64 lanes x 2) x 8 output rows
 
-JD uint2 texel_f16(const float4& v) {  // round to nearest even, subnormals kept (the default float mode)
-    return make_uint2((uint32_t)jd::f32_to_f16(v.x) | ((uint32_t)jd::f32_to_f16(v.y) << 16), (uint32_t)jd::f32_to_f16(v.z) | ((uint32_t)jd::f32_to_f16(v.w) << 16));
-}
-JD void fma4(float4& a, float w, const float4& t) {
-    a.x = __builtin_fmaf(w, t.x, a.x); a.y = __builtin_fmaf(w, t.y, a.y); a.z = __builtin_fmaf(w, t.z, a.z); a.w = __builtin_fmaf(w, t.w, a.w);
-}
 // A staged row in LDS: texel t of the segment sits at float4 index t + t / 4.  A lane reads texels 4 * lane + c (c the same in
 // every lane), i.e. 80 bytes apart instead of 64: the 16 lanes a ds_read_b128 serves together then hit 16 different bank quads
 // (64 bytes apart they would share four).
@@ -171,7 +166,7 @@ __global__ __launch_bounds__(kBlurThreads) void k_blur_cols(const float4* __rest
         for (uint32_t o = 0; o < kColRows; o++) {
             if (o >= n_o) break;
             uint2* d = dst + (uint64_t)(yc + o) * W + x0 + c;
-            const uint2 ta = texel_f16(acc[o][0]), tb = texel_f16(acc[o][1]);
+            const uint2 ta = texel_pack(acc[o][0]), tb = texel_pack(acc[o][1]);
             if (c + 1u < rw && ((uintptr_t)d & 15u) == 0u) {
                 *(uint4*)d = make_uint4(ta.x, ta.y, tb.x, tb.y);
             } else {
@@ -180,11 +175,6 @@ __global__ __launch_bounds__(kBlurThreads) void k_blur_cols(const float4* __rest
             }
         }
     }
-}
-
-uint32_t blur_grid(uint64_t items, int num_cus) {  // blocks of four wave items; at most 8 per CU, the rest by stride
-    const uint64_t blocks = (items + kBlurWaves - 1u) / kBlurWaves, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * 8u;
-    return (uint32_t)(blocks < cap ? blocks : cap);
 }
 
 }  // namespace
@@ -197,13 +187,11 @@ extern "C" int jh_blur_launch(hipStream_t stream, const void* src, void* dst, ui
                               uint32_t rect_w, uint32_t rect_h, int clamp, const float* taps_x, uint32_t radius_x, const float* taps_y,
                               uint32_t radius_y, void* tmp, int num_cus) {
     if (!dst || !tmp || !taps_x || !taps_y || radius_x > kMaxRadius || radius_y > kMaxRadius) return -1;
-    if ((uint64_t)x + rect_w > width || (uint64_t)y + rect_h > height) return -1;
+    if (!rect_inside(x, y, rect_w, rect_h, width, height)) return -1;
     if (rect_w == 0u || rect_h == 0u) return 0;
-    const uint32_t row0 = y > radius_y ? y - radius_y : 0u;
-    const uint64_t row1 = (uint64_t)y + rect_h + radius_y < height ? (uint64_t)y + rect_h + radius_y : height;
-    const uint32_t n_rows = (uint32_t)(row1 - row0);
+    const RowWindow rows = row_window(y, rect_h, radius_y, height);
     const uint32_t segs = (rect_w + kRowSeg - 1u) / kRowSeg, strips = (rect_w + kColStrip - 1u) / kColStrip;
-    const uint64_t items_h = (uint64_t)n_rows * segs, items_v = (uint64_t)((rect_h + kColRows - 1u) / kColRows) * strips;
+    const uint64_t items_h = (uint64_t)rows.n_rows * segs, items_v = (uint64_t)((rect_h + kColRows - 1u) / kColRows) * strips;
     if (items_h > 0x7fffffffull || items_v > 0x7fffffffull) return -1;
     BlurTaps tx, ty;
     memset(&tx, 0, sizeof tx);
@@ -212,16 +200,13 @@ extern "C" int jh_blur_launch(hipStream_t stream, const void* src, void* dst, ui
     memcpy(ty.w, taps_y, (2u * radius_y + 1u) * sizeof(float));
     const uint32_t region = skew(kRowSeg - 1u + 2u * radius_x) + 1u;
     const size_t lds = (size_t)(kTapSlots / 4u + kBlurWaves * region) * sizeof(float4);
-    const dim3 block(kBlurThreads), grid_h(blur_grid(items_h, num_cus)), grid_v(blur_grid(items_v, num_cus));
-    const uint2* s = (const uint2*)src;
-    if (clamp) {
-        hipLaunchKernelGGL(k_blur_rows<true>, grid_h, block, lds, stream, s, (float4*)tmp, width, x, rect_w, row0, radius_x, segs, region, (uint32_t)items_h, tx);
-        hipLaunchKernelGGL(k_blur_cols<true>, grid_v, block, 0, stream, (const float4*)tmp, (uint2*)dst, width, height, x, y, rect_w, rect_h, row0, radius_y,
+    const dim3 block(kBlurThreads), grid_h(grid_blocks(items_h, kBlurWaves, 8u, num_cus)), grid_v(grid_blocks(items_v, kBlurWaves, 8u, num_cus));
+    with_flag(clamp != 0, [&](auto edge) {
+        constexpr bool CLAMP = decltype(edge)::value;
+        hipLaunchKernelGGL(k_blur_rows<CLAMP>, grid_h, block, lds, stream, (const uint2*)src, (float4*)tmp, width, x, rect_w, rows.row0, radius_x, segs, region,
+                           (uint32_t)items_h, tx);
+        hipLaunchKernelGGL(k_blur_cols<CLAMP>, grid_v, block, 0, stream, (const float4*)tmp, (uint2*)dst, width, height, x, y, rect_w, rect_h, rows.row0, radius_y,
                            strips, (uint32_t)items_v, ty);
-    } else {
-        hipLaunchKernelGGL(k_blur_rows<false>, grid_h, block, lds, stream, s, (float4*)tmp, width, x, rect_w, row0, radius_x, segs, region, (uint32_t)items_h, tx);
-        hipLaunchKernelGGL(k_blur_cols<false>, grid_v, block, 0, stream, (const float4*)tmp, (uint2*)dst, width, height, x, y, rect_w, rect_h, row0, radius_y,
-                           strips, (uint32_t)items_v, ty);
-    }
+    });
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -7,11 +7,9 @@
 //   clamp    m = m > 0 ? m : 0; m = m < 1 ? m : 1 (with the flag; compare and select: NaN and -0 become +0)
 //   round    g = f16(m), a NaN as 0x7e00
 //   output   POST_i[g] where a POST table is given, else g
-// Streaming, as k_composite (kernels_composite.hip): 8 B in and 8 B out per texel, nothing reused, no LDS.  A lane owns two
-// neighbouring texels of a dst row, laid on the row's 16-byte grid (`phase`), so a pair inside the rectangle is one 16-byte store, and
-// one 16-byte load of the source when its own address is aligned too; a row's first or last texel alone is an 8-byte access.  A work
-// item is a row segment of 512 texels = one workgroup of 256 lanes; the grid is bounded by blit_grid_blocks and strides.  src may be
-// dst: a lane reads its texels before it writes them and no other lane touches them.
+// Streaming: 8 B in and 8 B out per texel, nothing reused, no LDS: the pair walk of texel_io.h without a backdrop, a lane two
+// neighbouring texels of a dst row, 16-byte accesses where a pair allows.  A work item is a row segment of 512 texels = one workgroup
+// of 256 lanes; the grid is bounded by 8 x the CU count and strides.  src may be dst.
 // The matrix, the clamp flag and the table pointers are kernel arguments: they sit in scalar registers, and an absent table is a
 // branch on the scalar pipe.  Two instantiations: TABLES = false has no gather (LINEAR space, IDENTITY funcs: feColorMatrix,
 // luminanceToAlpha, a tint); TABLES = true gathers up to 3 x 4 B and 4 x 2 B per texel from tables of 1.25 MB in all.
@@ -19,13 +17,13 @@
 
 #include <stdint.h>
 
-#include "blit_convert.h"
 #include "kcommon.h"
+#include "texel_io.h"
 
 namespace {
 
-constexpr uint32_t kColorThreads = 256, kColorSeg = 2u * kColorThreads;  // texels of a work item
-constexpr uint32_t kColorEntries = 65536u;                               // of a table: one per f16 bit pattern
+constexpr uint32_t kColorThreads = 256;
+constexpr uint32_t kColorEntries = 65536u;  // of a table: one per f16 bit pattern
 
 struct ColorParams {  // by value in the kernel arguments
     float m[20];      // row-major 4 x 5
@@ -63,35 +61,7 @@ JD uint2 color_texel(uint2 s, const ColorParams& p) {
 template <bool TABLES>
 __global__ __launch_bounds__(kColorThreads) void k_color(const uint2* src, uint32_t src_w, uint2* dst, uint32_t dst_w, uint32_t x, uint32_t y,
                                                          uint32_t w, uint32_t segs, uint32_t total_items, ColorParams p) {
-    for (uint32_t it = blockIdx.x; it < total_items; it += gridDim.x) {
-        const uint32_t row = it / segs, seg = it - row * segs;
-        uint2* drow = dst + ((uint64_t)(y + row) * dst_w + x);
-        const uint2* srow = src ? src + ((uint64_t)(y + row) * src_w + x) : nullptr;
-        const uint32_t phase = (uint32_t)(((uintptr_t)drow >> 3) & 1u);
-        const int64_t c = (int64_t)seg * kColorSeg + 2u * threadIdx.x - phase;  // the lane's texels c, c + 1 of the rectangle's row
-        const bool va = c >= 0 && c < (int64_t)w, vb = c + 1 < (int64_t)w;
-        if (!va && !vb) continue;
-        uint2 sa = make_uint2(0u, 0u), sb = sa;
-        if (va && vb) {
-            if (srow) {
-                const uint2* s = srow + c;
-                if (((uintptr_t)s & 15u) == 0u) {  // (the same for every pair of the row)
-                    const uint4 q = *(const uint4*)s;
-                    sa = make_uint2(q.x, q.y);
-                    sb = make_uint2(q.z, q.w);
-                } else {
-                    sa = s[0];
-                    sb = s[1];
-                }
-            }
-            const uint2 oa = color_texel<TABLES>(sa, p), ob = color_texel<TABLES>(sb, p);
-            *(uint4*)(drow + c) = make_uint4(oa.x, oa.y, ob.x, ob.y);
-        } else {  // the row's first or last texel alone
-            const int64_t at = va ? c : c + 1;
-            if (srow) sa = srow[at];
-            drow[at] = color_texel<TABLES>(sa, p);
-        }
-    }
+    pair_walk<kColorThreads, false>(src, src_w, x, y, dst, dst_w, x, y, w, 0u, segs, total_items, [&](uint2 s, uint2) { return color_texel<TABLES>(s, p); });
 }
 
 }  // namespace
@@ -104,10 +74,9 @@ extern "C" int jh_color_launch(hipStream_t stream, const void* src, uint32_t src
                                uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h, const float* matrix, int clamp, const float* pre,
                                const uint16_t* const* post, int num_cus) {
     if (!dst || !matrix || !post) return -1;
-    if ((uint64_t)x + rect_w > src_w || (uint64_t)y + rect_h > src_h || (uint64_t)x + rect_w > dst_w || (uint64_t)y + rect_h > dst_h) return -1;
+    if (!rect_inside(x, y, rect_w, rect_h, src_w, src_h) || !rect_inside(x, y, rect_w, rect_h, dst_w, dst_h)) return -1;
     if (rect_w == 0u || rect_h == 0u) return 0;
-    const uint64_t segs = ((uint64_t)rect_w + 1u + kColorSeg - 1u) / kColorSeg;  // (+ 1: the pair grid may start one texel before the row)
-    const uint64_t total = segs * rect_h;
+    const uint64_t segs = walk_segs(rect_w, kColorThreads), total = segs * rect_h;
     if (total > 0x7fffffffull) return -1;
     ColorParams p;
     for (int i = 0; i < 20; i++) p.m[i] = matrix[i];
@@ -118,11 +87,10 @@ extern "C" int jh_color_launch(hipStream_t stream, const void* src, uint32_t src
         p.post[i] = post[i];
         tables = tables || post[i] != nullptr;
     }
-    const dim3 grid(blit_grid_blocks(total, num_cus)), block(kColorThreads);
-    const uint2* s = (const uint2*)src;
-    if (tables)
-        hipLaunchKernelGGL(k_color<true>, grid, block, 0, stream, s, src_w, (uint2*)dst, dst_w, x, y, rect_w, (uint32_t)segs, (uint32_t)total, p);
-    else
-        hipLaunchKernelGGL(k_color<false>, grid, block, 0, stream, s, src_w, (uint2*)dst, dst_w, x, y, rect_w, (uint32_t)segs, (uint32_t)total, p);
+    const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kColorThreads);
+    with_flag(tables, [&](auto tab) {
+        hipLaunchKernelGGL(k_color<decltype(tab)::value>, grid, block, 0, stream, (const uint2*)src, src_w, (uint2*)dst, dst_w, x, y, rect_w, (uint32_t)segs,
+                           (uint32_t)total, p);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -19,7 +19,7 @@
 //                   column and walks down a block: P[v] = op of H over the block's rows up to v.
 //   k_morph_final   H, P -> f16 image.  The same walk bottom-up forms the suffix S[v] = op of H over the block's rows from v on; the
 //                   window of output row v is rows v .. v + 2 ry, the end of v's block and the beginning of the next: op(S[v], P[v +
-//                   2 ry]).  Un-keyed, stored as the rule says (STRAIGHT: exact; otherwise fine's un-premultiplying store).
+//                   2 ry]).  Un-keyed, stored as the rule says (STRAIGHT: exact; otherwise the store rule, texel_io.h).
 // A column item is one texel per lane x 64 lanes (8-byte stores, 512 B per wave and row) instead of the blur's column pair: with
 // blocks of up to 511 rows the strips are what gives the launch its items (DESIGN.md 5.11 has the count), and eight rows' loads are
 // in flight per lane before the first is used.  Blocks shorter than kItemRows are grouped so that an item is never a row or two.
@@ -29,6 +29,7 @@
 
 #include "../../include/jello_morph.h"
 #include "kcommon.h"
+#include "texel_io.h"
 
 namespace {
 
@@ -49,8 +50,7 @@ JD int4 splat(int32_t k) { return make_int4(k, k, k, k); }
 // The keys of a source texel: widened, colour times alpha unless STRAIGHT (exact: 11 + 11 bits; Inf x 0 is a NaN and gets its key).
 template <bool DILATE, bool STRAIGHT>
 JD int4 texel_keys(uint2 t) {
-    const float4 c = jd::rgba16f_to_f32(t);
-    const float4 p = STRAIGHT ? c : make_float4(c.x * c.w, c.y * c.w, c.z * c.w, c.w);
+    const float4 p = texel_widen<STRAIGHT>(t);
     return make_int4(jmorph_key(__float_as_uint(p.x), DILATE), jmorph_key(__float_as_uint(p.y), DILATE), jmorph_key(__float_as_uint(p.z), DILATE),
                      jmorph_key(__float_as_uint(p.w), DILATE));
 }
@@ -62,15 +62,9 @@ JD int4 staged_keys(const uint2* srow, int64_t x, uint32_t W, int32_t pad) {
 }
 
 template <bool STRAIGHT>
-JD uint2 stored_texel(const int4& k) {  // as kernels_resample.hip stores: round to nearest even, subnormals kept
-    const float4 v = make_float4(__uint_as_float(jmorph_unkey(k.x)), __uint_as_float(jmorph_unkey(k.y)), __uint_as_float(jmorph_unkey(k.z)),
-                                 __uint_as_float(jmorph_unkey(k.w)));
-    if (STRAIGHT)
-        return make_uint2((uint32_t)jd::f32_to_f16(v.x) | ((uint32_t)jd::f32_to_f16(v.y) << 16), (uint32_t)jd::f32_to_f16(v.z) | ((uint32_t)jd::f32_to_f16(v.w) << 16));
-    const float a_inv = 1.0f / jd::fmax_(v.w, 1e-6f);
-    const uint32_t ro = jd::f32_to_f16(v.x * a_inv + 0.0f), go = jd::f32_to_f16(v.y * a_inv + 0.0f), bo = jd::f32_to_f16(v.z * a_inv + 0.0f),
-                   ao = jd::f32_to_f16(v.w + 0.0f);
-    return make_uint2(ro | (go << 16), bo | (ao << 16));
+JD uint2 stored_texel(const int4& k) {
+    return texel_store<STRAIGHT>(make_float4(__uint_as_float(jmorph_unkey(k.x)), __uint_as_float(jmorph_unkey(k.y)), __uint_as_float(jmorph_unkey(k.z)),
+                                             __uint_as_float(jmorph_unkey(k.w))));
 }
 
 // Rows [row0, row0 + n_rows) of the image, columns [x0, x0 + rw): the row extremum into plane rows vrow0 + row of H (rw int4 each).
@@ -229,26 +223,6 @@ __global__ __launch_bounds__(kColThreads) void k_morph_final(const int4* __restr
     }
 }
 
-// workgroups of `waves` wave items; at most 32 waves per CU, the rest by stride (blur_grid's bound: 8 workgroups of four)
-uint32_t morph_grid(uint64_t items, uint32_t waves, int num_cus) {
-    const uint64_t blocks = (items + waves - 1u) / waves, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * (32u / waves);
-    return (uint32_t)(blocks < cap ? blocks : cap);
-}
-
-template <bool DILATE, bool STRAIGHT>
-void morph_enqueue(hipStream_t stream, const uint2* src, uint2* dst, uint32_t W, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh, uint32_t row0,
-                   uint32_t rx, int4* hp, int4* pp, const MorphPlanes& m, uint32_t out_blocks, uint64_t items_rows,
-                   uint64_t items_prefix, uint64_t items_final, int num_cus) {
-    const uint32_t region = kRowSeg + 2u * rx;
-    const size_t lds = (size_t)kMorphWaves * region * sizeof(int4);
-    const dim3 block(kMorphThreads);
-    hipLaunchKernelGGL((k_morph_rows<DILATE, STRAIGHT>), dim3(morph_grid(items_rows, kMorphWaves, num_cus)), block, lds, stream, src, hp, W, x, rw, row0, m.vlo, rx,
-                       (rw + kRowSeg - 1u) / kRowSeg, region, (uint32_t)items_rows, m.pad);
-    hipLaunchKernelGGL((k_morph_prefix<DILATE>), dim3(morph_grid(items_prefix, 1u, num_cus)), dim3(kColThreads), 0, stream, (const int4*)hp, pp, m, (uint32_t)items_prefix);
-    hipLaunchKernelGGL((k_morph_final<DILATE, STRAIGHT>), dim3(morph_grid(items_final, 1u, num_cus)), dim3(kColThreads), 0, stream, (const int4*)hp, (const int4*)pp, dst, W, x,
-                       y, rh, out_blocks, m, (uint32_t)items_final);
-}
-
 }  // namespace
 
 // The rectangle (x, y, rect_w, rect_h) of the width x height RGBA16F image at dst = the erosion (dilate = 0) or dilation of the image
@@ -259,37 +233,39 @@ extern "C" int jh_morph_launch(hipStream_t stream, const void* src, void* dst, u
                                uint32_t rect_w, uint32_t rect_h, int dilate, int clamp, int straight, uint32_t radius_x, uint32_t radius_y, void* tmp,
                                int num_cus) {
     if (!dst || !tmp || radius_x > JMORPH_MAX_RADIUS || radius_y > JMORPH_MAX_RADIUS) return -1;
-    if ((uint64_t)x + rect_w > width || (uint64_t)y + rect_h > height) return -1;
+    if (!rect_inside(x, y, rect_w, rect_h, width, height)) return -1;
     if (rect_w == 0u || rect_h == 0u) return 0;
-    const uint32_t row0 = y > radius_y ? y - radius_y : 0u;
-    const uint64_t row1 = (uint64_t)y + rect_h + radius_y < height ? (uint64_t)y + rect_h + radius_y : height;
-    const uint32_t n_rows = (uint32_t)(row1 - row0);
+    const RowWindow rows = row_window(y, rect_h, radius_y, height);
     const uint64_t nv = jmorph_plane_rows(rect_h, radius_y);
     if (nv > 0x7fffffffull) return -1;
     MorphPlanes m;
     m.rw = rect_w;
     m.nv = (uint32_t)nv;
-    m.vlo = row0 + radius_y - y;  // the plane row of image row row0
-    m.vhi = m.vlo + n_rows;
+    m.vlo = rows.row0 + radius_y - y;  // the plane row of image row rows.row0
+    m.vhi = m.vlo + rows.n_rows;
     m.L = 2u * radius_y + 1u;
     m.group = m.L >= kItemRows ? 1u : (kItemRows + m.L - 1u) / m.L;
     m.strips = (rect_w + kColStrip - 1u) / kColStrip;
     m.pad = jmorph_pad(dilate, clamp);
     const uint64_t blocks_all = (nv + m.L - 1u) / m.L, blocks_out = ((uint64_t)rect_h + m.L - 1u) / m.L;
-    const uint64_t items_rows = (uint64_t)n_rows * ((rect_w + kRowSeg - 1u) / kRowSeg);
+    const uint64_t items_rows = (uint64_t)rows.n_rows * ((rect_w + kRowSeg - 1u) / kRowSeg);
     const uint64_t items_prefix = ((blocks_all + m.group - 1u) / m.group) * m.strips, items_final = ((blocks_out + m.group - 1u) / m.group) * m.strips;
     if (items_rows > 0x7fffffffull || items_prefix > 0x7fffffffull || items_final > 0x7fffffffull) return -1;
     int4* hp = (int4*)tmp;
     int4* pp = (int4*)((char*)tmp + jmorph_plane_bytes(rect_w, rect_h, radius_y));
-    const uint2* s = (const uint2*)src;
-    uint2* d = (uint2*)dst;
-#define JH_MORPH_ENQUEUE(D, S) \
-    morph_enqueue<D, S>(stream, s, d, width, x, y, rect_w, rect_h, row0, radius_x, hp, pp, m, (uint32_t)blocks_out, items_rows, items_prefix, items_final, num_cus)
-    if (dilate) {
-        if (straight) JH_MORPH_ENQUEUE(true, true); else JH_MORPH_ENQUEUE(true, false);
-    } else {
-        if (straight) JH_MORPH_ENQUEUE(false, true); else JH_MORPH_ENQUEUE(false, false);
-    }
-#undef JH_MORPH_ENQUEUE
+    const uint32_t segs = (rect_w + kRowSeg - 1u) / kRowSeg, region = kRowSeg + 2u * radius_x;
+    const size_t lds = (size_t)kMorphWaves * region * sizeof(int4);
+    const dim3 grid_rows(grid_blocks(items_rows, kMorphWaves, 8u, num_cus)), grid_prefix(grid_blocks(items_prefix, 1u, 32u, num_cus)),
+        grid_final(grid_blocks(items_final, 1u, 32u, num_cus));
+    with_flag(dilate != 0, [&](auto op) {
+        with_flag(straight != 0, [&](auto flag) {
+            constexpr bool DILATE = decltype(op)::value, STRAIGHT = decltype(flag)::value;
+            hipLaunchKernelGGL((k_morph_rows<DILATE, STRAIGHT>), grid_rows, dim3(kMorphThreads), lds, stream, (const uint2*)src, hp, width, x, rect_w, rows.row0, m.vlo,
+                               radius_x, segs, region, (uint32_t)items_rows, m.pad);
+            hipLaunchKernelGGL((k_morph_prefix<DILATE>), grid_prefix, dim3(kColThreads), 0, stream, (const int4*)hp, pp, m, (uint32_t)items_prefix);
+            hipLaunchKernelGGL((k_morph_final<DILATE, STRAIGHT>), grid_final, dim3(kColThreads), 0, stream, (const int4*)hp, (const int4*)pp, (uint2*)dst, width, x, y,
+                               rect_h, (uint32_t)blocks_out, m, (uint32_t)items_final);
+        });
+    });
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

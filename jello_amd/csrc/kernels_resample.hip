@@ -4,8 +4,7 @@
 //   p = the f16 source texel widened, colour times alpha unless STRAIGHT                       once per source texel, when it is staged
 //   H = 0; for k ascending over the x window: H = fmaf(w_k, p[k], H)      k_resample_rows: f16 image -> binary32 rows (tmp)
 //   V = 0; for k ascending over the y window: V = fmaf(w_k, H[k], V)      k_resample_cols: tmp -> f16 image
-//   store: STRAIGHT f16(V); otherwise a_inv = 1 / max(V.a, 1e-6), f16(V.rgb * a_inv + 0.0f), f16(V.a + 0.0f) -- as fine and
-//   jh_composite store (restated here: kernels_composite.hip keeps its own text, and its machine code)
+//   store: STRAIGHT f16(V), otherwise V by the store rule (texel_io.h)
 // and every implementation has to produce these bits, so the order of a sum is fixed and the parallelism is across outputs: a lane of
 // k_resample_rows carries one output texel x 4 channels, a lane of k_resample_cols 4 rows x 2 columns x 4 channels = 32 accumulators,
 // all independent fmaf chains.
@@ -24,6 +23,7 @@
 
 #include "../../include/jello_resample.h"
 #include "kcommon.h"
+#include "texel_io.h"
 
 namespace {
 
@@ -34,27 +34,6 @@ constexpr uint32_t kColStrip = 128, kColRows = 4;  // k_resample_cols: a wave's 
 // and what its skewed region takes
 constexpr uint32_t kMaxSpan = JH_RESAMPLE_ROW_SEG * JRESAMPLE_MAX_RATIO + JRESAMPLE_MAX_TAPS;
 constexpr uint32_t kMaxRegion = kMaxSpan - 1u + ((kMaxSpan - 1u) >> 4) + 1u;
-
-JD void fma4(float4& a, float w, const float4& t) {
-    a.x = __builtin_fmaf(w, t.x, a.x); a.y = __builtin_fmaf(w, t.y, a.y); a.z = __builtin_fmaf(w, t.z, a.z); a.w = __builtin_fmaf(w, t.w, a.w);
-}
-
-// A source texel as the sums take it: widened, and its colour times its alpha unless STRAIGHT (exact: 11 + 11 bits).
-template <bool STRAIGHT>
-JD float4 source_texel(uint2 t) {
-    const float4 c = jd::rgba16f_to_f32(t);
-    return STRAIGHT ? c : make_float4(c.x * c.w, c.y * c.w, c.z * c.w, c.w);
-}
-
-template <bool STRAIGHT>
-JD uint2 stored_texel(const float4& v) {  // round to nearest even, subnormals kept (the default float mode)
-    if (STRAIGHT)
-        return make_uint2((uint32_t)jd::f32_to_f16(v.x) | ((uint32_t)jd::f32_to_f16(v.y) << 16), (uint32_t)jd::f32_to_f16(v.z) | ((uint32_t)jd::f32_to_f16(v.w) << 16));
-    const float a_inv = 1.0f / jd::fmax_(v.w, 1e-6f);
-    const uint32_t ro = jd::f32_to_f16(v.x * a_inv + 0.0f), go = jd::f32_to_f16(v.y * a_inv + 0.0f), bo = jd::f32_to_f16(v.z * a_inv + 0.0f),
-                   ao = jd::f32_to_f16(v.w + 0.0f);
-    return make_uint2(ro | (go << 16), bo | (ao << 16));
-}
 
 // Rows [sy, sy + n_rows) of the source image (W texels per row; null: never written, transparent black), the columns of the source
 // rectangle from sx on: H of every output column into tmp (n_rows x dw float4).  item = row * segs + seg; the waves stride over the
@@ -83,11 +62,11 @@ __global__ __launch_bounds__(kRowThreads) void k_resample_rows(const uint2* __re
             if (srow) {
                 if (pair_aligned && e + 1u < len) {
                     const uint4 q = *(const uint4*)(srow + e);
-                    a = source_texel<STRAIGHT>(make_uint2(q.x, q.y));
-                    b = source_texel<STRAIGHT>(make_uint2(q.z, q.w));
+                    a = texel_widen<STRAIGHT>(make_uint2(q.x, q.y));
+                    b = texel_widen<STRAIGHT>(make_uint2(q.z, q.w));
                 } else {
-                    a = source_texel<STRAIGHT>(srow[e]);
-                    if (e + 1u < len) b = source_texel<STRAIGHT>(srow[e + 1u]);
+                    a = texel_widen<STRAIGHT>(srow[e]);
+                    if (e + 1u < len) b = texel_widen<STRAIGHT>(srow[e + 1u]);
                 }
             }
             reg[jh_resample_skew(e)] = a;
@@ -171,7 +150,7 @@ __global__ __launch_bounds__(kColThreads) void k_resample_cols(const float4* __r
         for (uint32_t o = 0; o < kColRows; o++) {
             if (o >= n_o) break;
             uint2* d = dst + ((uint64_t)(dy + ry + o) * DW + dx + c);
-            const uint2 ta = stored_texel<STRAIGHT>(acc[o][0]), tb = stored_texel<STRAIGHT>(acc[o][1]);
+            const uint2 ta = texel_store<STRAIGHT>(acc[o][0]), tb = texel_store<STRAIGHT>(acc[o][1]);
             if (c + 1u < dw && ((uintptr_t)d & 15u) == 0u) {
                 *(uint4*)d = make_uint4(ta.x, ta.y, tb.x, tb.y);
             } else {
@@ -180,11 +159,6 @@ __global__ __launch_bounds__(kColThreads) void k_resample_cols(const float4* __r
             }
         }
     }
-}
-
-uint32_t resample_grid(uint64_t items, uint32_t waves, int num_cus) {  // blocks of `waves` wave items; at most 8 per CU, the rest by stride
-    const uint64_t blocks = (items + waves - 1u) / waves, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * 8u;
-    return (uint32_t)(blocks < cap ? blocks : cap);
 }
 
 }  // namespace
@@ -199,7 +173,7 @@ extern "C" int jh_resample_launch(hipStream_t stream, const void* src, uint32_t 
     if (!dst || !tmp || !tables || src == dst) return -1;
     const JhResampleTables t = *tables;
     if (!t.win_x || !t.seg_x || !t.w_x || !t.win_y || !t.w_y) return -1;
-    if ((uint64_t)sx + sw > src_w || (uint64_t)sy + sh > src_h || (uint64_t)dx + dw > dst_w || (uint64_t)dy + dh > dst_h) return -1;
+    if (!rect_inside(sx, sy, sw, sh, src_w, src_h) || !rect_inside(dx, dy, dw, dh, dst_w, dst_h)) return -1;
     if (sw == 0u || sh == 0u || dw == 0u || dh == 0u) return -1;
     if (t.taps_x == 0u || t.taps_x > JRESAMPLE_MAX_TAPS || t.stride_y == 0u || t.stride_y > JRESAMPLE_MAX_TAPS || t.region_x == 0u || t.region_x > kMaxRegion)
         return -1;
@@ -207,18 +181,13 @@ extern "C" int jh_resample_launch(hipStream_t stream, const void* src, uint32_t 
     const uint64_t items_h = (uint64_t)sh * segs, items_v = (uint64_t)((dh + kColRows - 1u) / kColRows) * strips;
     if (items_h > 0x7fffffffull || items_v > 0x7fffffffull) return -1;
     const size_t lds = (size_t)kRowWaves * t.region_x * sizeof(float4);
-    const dim3 grid_h(resample_grid(items_h, kRowWaves, num_cus)), grid_v(resample_grid(items_v, kColWaves, num_cus));
-    const uint2* s = (const uint2*)src;
-    if (straight) {
-        hipLaunchKernelGGL(k_resample_rows<true>, grid_h, dim3(kRowThreads), lds, stream, s, (float4*)tmp, src_w, sx, sy, dw, segs, t.region_x, (uint32_t)items_h,
-                           t.win_x, t.seg_x, t.w_x);
-        hipLaunchKernelGGL(k_resample_cols<true>, grid_v, dim3(kColThreads), 0, stream, (const float4*)tmp, (uint2*)dst, dst_w, dx, dy, dw, dh, strips,
+    const dim3 grid_h(grid_blocks(items_h, kRowWaves, 8u, num_cus)), grid_v(grid_blocks(items_v, kColWaves, 8u, num_cus));
+    with_flag(straight != 0, [&](auto flag) {
+        constexpr bool STRAIGHT = decltype(flag)::value;
+        hipLaunchKernelGGL(k_resample_rows<STRAIGHT>, grid_h, dim3(kRowThreads), lds, stream, (const uint2*)src, (float4*)tmp, src_w, sx, sy, dw, segs, t.region_x,
+                           (uint32_t)items_h, t.win_x, t.seg_x, t.w_x);
+        hipLaunchKernelGGL(k_resample_cols<STRAIGHT>, grid_v, dim3(kColThreads), 0, stream, (const float4*)tmp, (uint2*)dst, dst_w, dx, dy, dw, dh, strips,
                            (uint32_t)items_v, t.win_y, t.w_y, t.stride_y);
-    } else {
-        hipLaunchKernelGGL(k_resample_rows<false>, grid_h, dim3(kRowThreads), lds, stream, s, (float4*)tmp, src_w, sx, sy, dw, segs, t.region_x, (uint32_t)items_h,
-                           t.win_x, t.seg_x, t.w_x);
-        hipLaunchKernelGGL(k_resample_cols<false>, grid_v, dim3(kColThreads), 0, stream, (const float4*)tmp, (uint2*)dst, dst_w, dx, dy, dw, dh, strips,
-                           (uint32_t)items_v, t.win_y, t.w_y, t.stride_y);
-    }
+    });
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

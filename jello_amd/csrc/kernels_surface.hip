@@ -14,6 +14,7 @@
 
 #include "blit_convert.h"
 #include "kcommon.h"
+#include "texel_io.h"
 
 namespace {
 
@@ -94,7 +95,7 @@ extern "C" int jh_blit_launch(hipStream_t stream, const void* src, void* dst, ui
     const uint64_t blocks_per_row = (items + kBlitThreads - 1u) / kBlitThreads;
     const uint64_t total = blocks_per_row * (row1 - row0);
     if (total > 0x7fffffffull) return -1;
-    const dim3 grid(blit_grid_blocks(total, num_cus)), block(kBlitThreads);
+    const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kBlitThreads);
     const uint2* s = (const uint2*)src;
     uint8_t* d = (uint8_t*)dst;
     const uint32_t bpr = (uint32_t)blocks_per_row, tb = (uint32_t)total;

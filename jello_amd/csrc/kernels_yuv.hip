@@ -16,6 +16,7 @@
 
 #include "blit_convert.h"
 #include "kcommon.h"
+#include "texel_io.h"
 #include "yuv_matrix_lut.h"
 
 namespace {
@@ -175,7 +176,7 @@ extern "C" int jh_blit_yuv_launch(hipStream_t stream, const void* src, void* con
     const int* m = kYuvMatrix[matrix][range];
     for (int i = 0; i < 3; i++) { k.y[i] = m[i]; k.cb[i] = m[3 + i]; k.cr[i] = m[6 + i]; }
     k.off = kYuvOffset[range];
-    const dim3 grid(blit_grid_blocks(total, num_cus)), block(kYuvThreads);
+    const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kYuvThreads);
     const uint2* s = (const uint2*)src;
     const uint32_t tpp = (uint32_t)tiles_per_pair, tt = (uint32_t)total;
     switch (transfer * 2 + layout) {
