@@ -26,6 +26,7 @@
  *   jh_composite                      (no counterpart: one RGBA16F image blended onto another on the device)
  *   jh_color_filter                   (no counterpart: colour matrix and transfer functions on an RGBA16F image)
  *   jh_morphology                     (no counterpart: erode / dilate of an RGBA16F image by a box on the device)
+ *   jh_warp                           (no counterpart: an affine transform of an RGBA16F image on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -654,6 +655,79 @@ typedef struct jh_morph_desc {
     uint32_t x, y, width, height;  /* rectangle of dst that is written; 0 x 0: the whole image */
 } jh_morph_desc;
 int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_morph_desc* desc);
+
+/* ---- Warp: an affine transform of a rectangle of one RGBA16F image into a rectangle of another (DESIGN.md 5.12 "Warp rule") ----
+ * A rotated, skewed or sub-texel-translated layer, sprite or glyph run, a CSS transform on a filtered layer, a skewed shadow, a tiled
+ * pattern (feTile) under REPEAT -- without the image leaving the device.  The result is defined on values, and every implementation
+ * produces these bits (include/jello_warp.h states the host half, tests/warp_ref.py restates all of it).
+ *   arguments   matrix[6], binary64, in the order the Scene transforms use: (a, b, c, d, e, f), x' = a x + c y + e, y' = b x + d y +
+ *               f.  It maps continuous coordinates of the SOURCE RECTANGLE (origin its top-left corner, texel (i, j) centred at
+ *               (i + 0.5, j + 0.5)) to continuous coordinates of the DESTINATION IMAGE, not of the destination rectangle: the
+ *               destination rectangle is only what gets written, so a warp written in four quadrant rectangles equals the
+ *               whole-image warp.  A rectangle of 0 x 0 means the whole image (x and y are then ignored).  filter: JH_WARP_NEAREST
+ *               = 0 | JH_WARP_BILINEAR = 1 | JH_WARP_BICUBIC = 2 (Catmull-Rom).  edge: JH_WARP_EDGE_ZERO = 0 | _CLAMP = 1 | _REPEAT
+ *               = 2 | _MIRROR = 3.  flags: bit 0, JH_WARP_STRAIGHT.
+ *   inverse     binary64, nothing contracted, every product and quotient rounded once: det = a d - b c; p = d / det, q = -c / det,
+ *               r = (c f - d e) / det; s = -b / det, t = a / det, w = (b e - a f) / det.  u = p x' + q y' + r, v = s x' + t y' + w.
+ *   legal       all six entries finite; det finite and not 0; |p|, |q|, |s|, |t| <= 64; |r|, |w| <= 2^22; both images at most 32768
+ *               on a side.  With these limits every integer below stays under 2^58.
+ *   plan        six int64: P = rint(p 2^31), likewise Q, S, T; R = rint(r 2^32), likewise W; rint rounds half to even.  For the
+ *               destination texel (X, Y) of the image: U = P (2 X + 1) + Q (2 Y + 1) + R, V = S (2 X + 1) + T (2 Y + 1) + W, both
+ *               exact: the source position in units of 2^-32 texel.  The device computes exactly these integers.
+ *   taps        per axis, on U (V likewise).  NEAREST: one tap at i = U >> 32 (an arithmetic shift: a floor), weight 1.0f.
+ *               BILINEAR: U' = U - 2^31, i0 = U' >> 32, k = (U' >> 16) & 0xffff (the low 16 bits are dropped, not rounded), f =
+ *               (float)k 2^-16 (exact); taps i0, i0 + 1 with weights 1.0f - f, f (both exact).  BICUBIC: the same i0 and f; taps
+ *               i0 - 1 .. i0 + 2; weights in binary32 with these fmaf's and single multiplications:
+ *                 w0 = fmaf(fmaf(-0.5f, f, 1.0f), f, -0.5f) f        w1 = fmaf(fmaf(1.5f, f, -2.5f) f, f, 1.0f)
+ *                 w2 = fmaf(fmaf(-1.5f, f, 2.0f), f, 0.5f) f         w3 = (fmaf(0.5f, f, -0.5f) f) f
+ *   edge        a tap index i is resolved against the source RECTANGLE's extent n (the rectangle is the edge, not the image: an atlas
+ *               cell does not bleed).  ZERO: outside [0, n) the operand is +0.0f in all four channels and still takes part in the
+ *               sum.  CLAMP: min(max(i, 0), n - 1).  REPEAT: i mod n, non-negative.  MIRROR: m = i mod 2 n; m if m < n, otherwise
+ *               2 n - 1 - m.
+ *   sum         binary32.  The operand p is the f16 texel widened, its colour times its alpha unless STRAIGHT (exact).  For each tap
+ *               row j ascending: H_j = 0.0f, then H_j = fmaf(wx_i, p[i][j], H_j) for i ascending.  Then V = 0.0f and V =
+ *               fmaf(wy_j, H_j, V) for j ascending.  Rows before columns, as in Resample; a zero weight still multiplies.
+ *   store       STRAIGHT: f16(V) per channel, round to nearest even.  Otherwise as fine, jh_composite and jh_resample store: a_inv =
+ *               1.0f / max(V.a, 1e-6f); (f16(V.r a_inv + 0.0f), f16(V.g a_inv + 0.0f), f16(V.b a_inv + 0.0f), f16(V.a + 0.0f)).
+ *   values      f16 subnormals are values, Inf and NaN follow IEEE, a NaN result is any NaN.  Nothing is clamped: BICUBIC can
+ *               overshoot.
+ * So under STRAIGHT the identity, an integer translation under ZERO and the eight flips and quarter turns are copies or permutations
+ * of every finite value for every filter and edge (a -0 comes out as +0), and BILINEAR keeps a constant image constant.
+ * What the rule does not do: no minification prefilter -- below about 1:2 the result aliases, jh_resample comes first for that, and
+ * the limit of 64 is only there to bound the integers; no perspective; no call in place.
+ *
+ * jh_warp_plan: P, Q, R, S, T, W of a matrix into plan.  Host only, no context.  JH_ERR_INVALID for an illegal matrix.
+ * jh_warp_bounds: a rectangle {x, y, width, height} of the dst_w x dst_h image into rect such that under EDGE_ZERO every destination
+ * texel outside it is transparent black: the forward images (binary64, uncontracted, (a x + c y) + e and (b x + d y) + f) of the
+ * four corners of the src_w x src_h source rectangle grown by m = 0.5 NEAREST, 1 BILINEAR, 2 BICUBIC; floor(min) - 1 and ceil(max) +
+ * 1, clipped to the destination; an empty result is 0, 0, 0, 0.  Host only, no context.  JH_ERR_INVALID for an illegal matrix, an
+ * unknown filter or a side above 32768.
+ *
+ * jh_warp: the rule from the rectangle (src_x, src_y, src_width, src_height) of src_image_id into the rectangle (dst_x, dst_y,
+ * dst_width, dst_height) of dst_image_id, another image; the images carry their own sizes.  Only the destination rectangle is
+ * written; a dst that was never written is cleared to transparent black first and then counts as written; a source that was never
+ * written reads as transparent black.  Stream-ordered on the context's stream, never waits: ONE kernel launch, plus a fill when dst
+ * has to be cleared.  No scratch and no tables: the call is always capturable.  With profiling on the call is a query "warp" with
+ * stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band): the rows a tap reads belong to another rank's context.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_warp: ": a null
+ * desc; an unknown source or destination id; an image that is not RGBA16F; an unknown filter, edge or flag bit; an illegal matrix
+ * (the message names the condition that failed); an image side above 32768; a rectangle that is not inside its image or that is
+ * empty in exactly one dimension; src_image_id == dst_image_id; a band set with jh_set_band. */
+typedef enum jh_warp_filter { JH_WARP_NEAREST = 0, JH_WARP_BILINEAR = 1, JH_WARP_BICUBIC = 2 } jh_warp_filter;
+typedef enum jh_warp_edge { JH_WARP_EDGE_ZERO = 0, JH_WARP_EDGE_CLAMP = 1, JH_WARP_EDGE_REPEAT = 2, JH_WARP_EDGE_MIRROR = 3 } jh_warp_edge;
+#define JH_WARP_STRAIGHT 1u
+#define JH_WARP_MAX_SIDE 32768u
+typedef struct jh_warp_desc {
+    double matrix[6];                                 /* (a, b, c, d, e, f): source rectangle -> destination image */
+    int filter;                                       /* jh_warp_filter */
+    int edge;                                         /* jh_warp_edge */
+    uint32_t flags;                                   /* bit 0: JH_WARP_STRAIGHT */
+    uint32_t src_x, src_y, src_width, src_height;     /* source rectangle; width == height == 0: the whole image */
+    uint32_t dst_x, dst_y, dst_width, dst_height;     /* destination rectangle, likewise */
+} jh_warp_desc;
+int jh_warp_plan(const double matrix[6], int64_t plan[6]);
+int jh_warp_bounds(const double matrix[6], uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t rect[4]);
+int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_warp_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -658,6 +658,55 @@ func (e *Engine) Morphology(src, dst renderer.ImageProxy, desc MorphDesc) {
 	e.check(C.jh_morphology(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "morphology")
 }
 
+// WarpFilter is jh_warp_filter: 1, 2 x 2 or 4 x 4 (Catmull-Rom) source texels per destination texel.
+type WarpFilter int32
+
+const (
+	WarpNearest  WarpFilter = 0
+	WarpBilinear WarpFilter = 1
+	WarpBicubic  WarpFilter = 2
+)
+
+// WarpEdge is jh_warp_edge: what a tap outside the source rectangle reads.
+type WarpEdge int32
+
+const (
+	WarpEdgeZero   WarpEdge = 0 // transparent black
+	WarpEdgeClamp  WarpEdge = 1 // the nearest texel of the rectangle
+	WarpEdgeRepeat WarpEdge = 2 // the rectangle tiled (feTile)
+	WarpEdgeMirror WarpEdge = 3 // the rectangle tiled, every other copy flipped
+)
+
+// WarpStraight is JH_WARP_STRAIGHT: the four channels are filtered as stored, not colour times alpha.
+const WarpStraight uint32 = 1
+
+// WarpDesc is jh_warp_desc (include/jello_hip.h "Warp"): the matrix (a, b, c, d, e, f) in the order the Scene transforms use, from
+// continuous coordinates of the source rectangle to continuous coordinates of the destination IMAGE, the filter, the edge mode, the
+// flags, and the two rectangles (Width == Height == 0: the whole image); the destination rectangle is only what gets written.
+type WarpDesc struct {
+	Matrix                          [6]float64
+	Filter                          WarpFilter
+	Edge                            WarpEdge
+	Flags                           uint32
+	SrcX, SrcY, SrcWidth, SrcHeight uint32
+	DstX, DstY, DstWidth, DstHeight uint32
+}
+
+// Warp is jh_warp: a rectangle of the RGBA16F image src under an affine map into a rectangle of the RGBA16F image dst (another image)
+// by the rule of DESIGN.md 5.12 (defined on values: every implementation gives the same bits).  A rotated, skewed or
+// sub-texel-translated layer, a CSS transform on a filtered layer, a tiled pattern under WarpEdgeRepeat.  No minification prefilter:
+// below about 1:2 Resample comes first.  Stream-ordered behind the frame, waits for nothing, one kernel launch, no scratch and no
+// tables: always capturable.
+func (e *Engine) Warp(src, dst renderer.ImageProxy, desc WarpDesc) {
+	d := C.jh_warp_desc{filter: C.int(desc.Filter), edge: C.int(desc.Edge), flags: C.uint32_t(desc.Flags),
+		src_x: C.uint32_t(desc.SrcX), src_y: C.uint32_t(desc.SrcY), src_width: C.uint32_t(desc.SrcWidth), src_height: C.uint32_t(desc.SrcHeight),
+		dst_x: C.uint32_t(desc.DstX), dst_y: C.uint32_t(desc.DstY), dst_width: C.uint32_t(desc.DstWidth), dst_height: C.uint32_t(desc.DstHeight)}
+	for i, m := range desc.Matrix {
+		d.matrix[i] = C.double(m)
+	}
+	e.check(C.jh_warp(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "warp")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -172,6 +172,13 @@ class CMorphDesc(ctypes.Structure):
                 ("height", ctypes.c_uint32)]
 
 
+class CWarpDesc(ctypes.Structure):
+    """jh_warp_desc (include/jello_hip.h)."""
+    _fields_ = [("matrix", ctypes.c_double * 6), ("filter", ctypes.c_int32), ("edge", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("src_x", ctypes.c_uint32), ("src_y", ctypes.c_uint32), ("src_width", ctypes.c_uint32), ("src_height", ctypes.c_uint32),
+                ("dst_x", ctypes.c_uint32), ("dst_y", ctypes.c_uint32), ("dst_width", ctypes.c_uint32), ("dst_height", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -242,6 +249,8 @@ def _declare(L):
     L.jl_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
     L.jl_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.jl_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
+    L.jl_warp_plan.argtypes = [dp, ctypes.POINTER(ctypes.c_int64)]
+    L.jl_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -286,6 +295,9 @@ def _declare(L):
     hip.jh_color_filter.argtypes = [vp, u64, u64, ctypes.POINTER(CColorDesc)]
     hip.jh_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
     hip.jh_morphology.argtypes = [vp, u64, u64, ctypes.POINTER(CMorphDesc)]
+    hip.jh_warp.argtypes = [vp, u64, u64, ctypes.POINTER(CWarpDesc)]
+    hip.jh_warp_plan.argtypes = [dp, ctypes.POINTER(ctypes.c_int64)]
+    hip.jh_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -25,6 +25,7 @@
 #include "../../include/jello_resample.h"
 #include "../../include/jello_color.h"
 #include "../../include/jello_morph.h"
+#include "../../include/jello_warp.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -1151,7 +1152,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1701,6 +1702,44 @@ int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, con
                                                  desc->edge == JH_MORPH_EDGE_CLAMP, (desc->flags & JH_MORPH_STRAIGHT) != 0u, desc->radius_x, desc->radius_y, tmp,
                                                  ctx->num_cus));
         });
+}
+
+// warp (include/jello_hip.h "Warp"; the plan, the bounds and the descriptor: include/jello_warp.h; kernels_warp.hip)
+int jh_warp_plan(const double matrix[6], int64_t plan[6]) {
+    if (!matrix || !plan) return JH_ERR_INVALID;
+    return jwarp_plan(matrix, plan) ? JH_ERR_INVALID : JH_OK;
+}
+int jh_warp_bounds(const double matrix[6], uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t rect[4]) {
+    if (!matrix || !rect) return JH_ERR_INVALID;
+    return jwarp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect) ? JH_ERR_INVALID : JH_OK;
+}
+int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_warp_desc* desc) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_warp: null descriptor");
+    static_assert(JH_WARP_NEAREST == JWARP_NEAREST && JH_WARP_BILINEAR == JWARP_BILINEAR && JH_WARP_BICUBIC == JWARP_BICUBIC &&
+                      JH_WARP_EDGE_ZERO == JWARP_EDGE_ZERO && JH_WARP_EDGE_CLAMP == JWARP_EDGE_CLAMP && JH_WARP_EDGE_REPEAT == JWARP_EDGE_REPEAT &&
+                      JH_WARP_EDGE_MIRROR == JWARP_EDGE_MIRROR && JH_WARP_STRAIGHT == JWARP_STRAIGHT && JH_WARP_MAX_SIDE == JWARP_MAX_SIDE,
+                  "the C ABI's values are the rule's");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_warp", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
+    if (src == dst) return fail(ctx, JH_ERR_INVALID, "jh_warp: the source is the destination (a warp in place reads what it writes)");
+    if (const char* why = jwarp_desc_error(desc->filter, desc->edge, desc->flags, desc->src_x, desc->src_y, desc->src_width, desc->src_height, src->width,
+                                           src->height, desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height, dst->width, dst->height))
+        return fail(ctx, JH_ERR_INVALID, std::string("jh_warp: ") + why);
+    int64_t plan[6];
+    if (const char* why = jwarp_plan(desc->matrix, plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_warp: illegal matrix: ") + why);
+    if (int rc = refuse_band_mode(ctx, "jh_warp", "the rows a tap reads belong to another rank")) return rc;
+    const jwarp_rect s = jwarp_resolve(desc->src_x, desc->src_y, desc->src_width, desc->src_height, src->width, src->height);
+    const jwarp_rect d = jwarp_resolve(desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height, dst->width, dst->height);
+    return post_render_call(ctx, "warp", [&] {
+        if (d.w == 0u || d.h == 0u) return (int)JH_OK;  // (an image without texels)
+        const void* from = s.w == 0u || s.h == 0u ? nullptr : content_or_null(*src);
+        if (int rc = first_content(ctx, dst, d.w, d.h)) return rc;
+        const uint32_t sw = s.w ? s.w : 1u, sh = s.h ? s.h : 1u;  // (a source without texels reads as transparent black: nothing is loaded)
+        return launch_status(ctx, "jh_warp", jh_warp_launch(ctx->stream, from, s.w ? src->width : 1u, s.h ? src->height : 1u, s.x, s.y, sw, sh, dst->ptr,
+                                                            dst->width, dst->height, d.x, d.y, d.w, d.h, plan, desc->filter, desc->edge,
+                                                            (desc->flags & JH_WARP_STRAIGHT) != 0u, ctx->num_cus));
+    });
 }
 
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.

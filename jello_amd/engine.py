@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CYuvDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CWarpDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -156,6 +156,65 @@ def _morph_desc(op, radius, edge, rect, premultiplied):
     if not (0 <= int(rx) <= MORPH_MAX_RADIUS and 0 <= int(ry) <= MORPH_MAX_RADIUS):
         raise ValueError("jh_morphology: a radius above 255 or below 0")
     return CMorphDesc(int(op), int(edge), 0 if premultiplied else MORPH_STRAIGHT, int(rx), int(ry), int(x), int(y), int(w), int(h))
+
+
+class WarpFilter(enum.IntEnum):
+    """jh_warp_filter: the taps of jh_warp -- 1, 2 x 2 and 4 x 4 (Catmull-Rom) source texels."""
+    NEAREST = 0
+    BILINEAR = 1
+    BICUBIC = 2
+
+
+class WarpEdge(enum.IntEnum):
+    """jh_warp_edge: what a tap outside the source rectangle reads -- transparent black, the nearest texel, the rectangle tiled, the
+    rectangle tiled with every other copy flipped."""
+    ZERO = 0
+    CLAMP = 1
+    REPEAT = 2
+    MIRROR = 3
+
+
+WARP_STRAIGHT = 1  # JH_WARP_STRAIGHT
+WARP_MAX_SIDE = 32768  # JH_WARP_MAX_SIDE
+
+
+def _matrix6(matrix):
+    m = [float(v) for v in matrix]
+    if len(m) != 6:
+        raise ValueError("jh_warp: the matrix has 6 entries (a, b, c, d, e, f)")
+    return (ctypes.c_double * 6)(*m)
+
+
+def warp_plan(matrix, twin=False):
+    """jh_warp_plan (twin: jl_warp_plan, the host twin): the six integers (P, Q, R, S, T, W) of the warp rule for
+    `matrix` = (a, b, c, d, e, f), source rectangle -> destination image.  No GPU needed.  ValueError for an illegal matrix."""
+    L = _lib.load_host()
+    plan = (ctypes.c_int64 * 6)()
+    if (L.jl_warp_plan if twin else L.hip.jh_warp_plan)(_matrix6(matrix), plan) != 0:
+        raise ValueError("jh_warp: illegal matrix (an entry not finite, a determinant that is 0 or not finite, an inverse coefficient "
+                         "above 64 or an inverse offset above 2^22)")
+    return tuple(int(v) for v in plan)
+
+
+def warp_bounds(matrix, src_size, filter, dst_size, twin=False):
+    """jh_warp_bounds (twin: jl_warp_bounds): the rectangle (x, y, width, height) of a destination of `dst_size` = (width, height)
+    outside which a warp of a source rectangle of `src_size` under WarpEdge.ZERO is transparent black; (0, 0, 0, 0) when nothing is
+    left.  No GPU needed.  ValueError for an illegal matrix, an unknown filter or a side above 32768."""
+    L = _lib.load_host()
+    rect = (ctypes.c_uint32 * 4)()
+    f = L.jl_warp_bounds if twin else L.hip.jh_warp_bounds
+    if f(_matrix6(matrix), int(src_size[0]), int(src_size[1]), int(filter), int(dst_size[0]), int(dst_size[1]), rect) != 0:
+        raise ValueError("jh_warp: illegal matrix, unknown filter or a side above 32768")
+    return tuple(int(v) for v in rect)
+
+
+def _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
+    d = CWarpDesc()
+    d.matrix[:] = list(_matrix6(matrix))
+    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else WARP_STRAIGHT
+    d.src_x, d.src_y, d.src_width, d.src_height = (0, 0, 0, 0) if src_rect is None else [int(v) for v in src_rect]
+    d.dst_x, d.dst_y, d.dst_width, d.dst_height = (0, 0, 0, 0) if dst_rect is None else [int(v) for v in dst_rect]
+    return d
 
 
 class ColorSpace(enum.IntEnum):
@@ -560,6 +619,34 @@ class Engine:
         dst = src_id if dst_id is None else dst_id
         self._check(self.hip.jh_morphology(self.ctx, src_id, dst, ctypes.byref(d)), "morphology", invalid=ValueError)
 
+    def warp(self, src_id, dst_id, matrix, filter=WarpFilter.BILINEAR, edge=WarpEdge.ZERO, src_rect=None, dst_rect=None, premultiplied=True):
+        """jh_warp: the rectangle `src_rect` = (x, y, width, height) of the RGBA16F image `src_id` (None: the whole image) under the
+        affine map `matrix` = (a, b, c, d, e, f), x' = a x + c y + e, y' = b x + d y + f, into the RGBA16F image `dst_id` (another
+        image) by the rule of DESIGN.md 5.12.  The matrix takes continuous coordinates of the source rectangle to continuous
+        coordinates of the destination IMAGE; `dst_rect` (None: the whole image) is only what gets written.  `edge`: what a tap
+        outside the source rectangle reads (WarpEdge).  `premultiplied`: colour is weighted by alpha while it is filtered (the
+        default); False filters the four channels as they are stored (JH_WARP_STRAIGHT: data images).  There is no minification
+        prefilter: below about 1:2 resample() comes first.  One launch, no scratch: always capturable.  Stream-ordered, returns
+        nothing; ValueError for a call the rule refuses."""
+        d = _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied)
+        self._check(self.hip.jh_warp(self.ctx, src_id, dst_id, ctypes.byref(d)), "warp", invalid=ValueError)
+
+    def place_layer(self, layer_id, target_id, matrix, scratch_image_id, layer_size, target_size, filter=WarpFilter.BILINEAR, **composite_keywords):
+        """A cached layer onto a target under an affine transform, two calls: warp(layer -> scratch, edge ZERO, dst_rect =
+        warp_bounds(...)): the layer in target space, written only where it can be other than transparent black;
+        composite(scratch -> target, src_rect = that rectangle, offset = its corner, **composite_keywords).  `layer_size` and
+        `target_size` are (width, height) of the layer and of the target; the scratch is an RGBA16F image of the target's size (the
+        rectangle of it is overwritten).  Returns the rectangle; nothing is enqueued when it is empty."""
+        for k in ("src_rect", "offset"):
+            if k in composite_keywords:
+                raise ValueError("place_layer: %s is the placed rectangle's" % k)
+        rect = warp_bounds(matrix, layer_size, filter, target_size)
+        if rect[2] == 0 or rect[3] == 0:
+            return rect
+        self.warp(layer_id, scratch_image_id, matrix, filter=filter, edge=WarpEdge.ZERO, dst_rect=rect)
+        self.composite(scratch_image_id, target_id, src_rect=rect, offset=(rect[0], rect[1]), **composite_keywords)
+        return rect
+
     def outline(self, layer_id, target_id, radius, color, scratch_image_id):
         """A layer with an outline (a halo) of `radius` texels onto a target, three calls: morphology(layer -> scratch, DILATE, edge
         ZERO); composite(scratch -> target, tint=color): the grown alpha in the outline's colour; composite(layer -> target).
@@ -694,7 +781,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None):
+                morphology=None, warp=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -717,8 +804,14 @@ class Engine:
         run once eagerly, and no other such filter since.
         morphology=dict(...) (the keywords of morphology() but the ids) erodes or dilates the frame's target in place, after the
         render and BEFORE the blur (three more launches) -- the order of a shadow with spread; a call of this rectangle size and
-        these radii must have run once eagerly.  So the order of a capture is: render, morphology, blur, composite, color,
-        resample, then the surface, YUV or pack conversion."""
+        these radii must have run once eagerly.
+        warp=dict(dst=image id, width=..., height=..., matrix=..., ...) (the other keywords of warp(), optional) transforms the
+        frame's target into the RGBA16F image `dst` of width x height where resample= would resize it (one more launch, nothing to
+        run eagerly first); the surface, YUV or pack conversion of the same capture then reads that image at its size.  It is
+        exclusive with resample=: giving both is a ValueError before anything is captured.  So the order of a capture is: render,
+        morphology, blur, composite, color, resample or warp, then the surface, YUV or pack conversion."""
+        if resample is not None and warp is not None:
+            raise ValueError("capture: resample= and warp= are exclusive (both would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
@@ -734,6 +827,9 @@ class Engine:
             if resample is not None:
                 self.resample(t["id"], resample["dst"], **{k: v for k, v in resample.items() if k not in ("dst", "width", "height")})
                 t = {"id": resample["dst"], "width": resample["width"], "height": resample["height"]}
+            if warp is not None:
+                self.warp(t["id"], warp["dst"], warp["matrix"], **{k: v for k, v in warp.items() if k not in ("dst", "width", "height", "matrix")})
+                t = {"id": warp["dst"], "width": warp["width"], "height": warp["height"]}
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._blit(t["id"], ptr, pitch, t["width"], t["height"], fmt)

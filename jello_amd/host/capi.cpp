@@ -10,6 +10,7 @@
 #include "../../include/jello_composite.h"
 #include "../../include/jello_resample.h"
 #include "../../include/jello_color.h"
+#include "../../include/jello_warp.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -456,6 +457,20 @@ int jl_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, floa
     if (n == 0u) { g_err = "resample_taps: a window without taps"; return -1; }
     if (first) *first = f;
     if (count) *count = n;
+    return 0;
+}
+
+// jl_warp_plan and jl_warp_bounds are the host twins of jh_warp_plan and jh_warp_bounds (the rule is in jello_hip.h and DESIGN.md
+// 5.12): the same header, compiled here by the host compiler -- the six integers of a matrix's plan, and the rectangle of the
+// destination outside which a ZERO warp is transparent black; -1 for what the rule refuses.
+int jl_warp_plan(const double* matrix, int64_t* plan) {
+    const char* why = matrix && plan ? jwarp_plan(matrix, plan) : "null argument";
+    if (why) { g_err = std::string("warp_plan: ") + why; return -1; }
+    return 0;
+}
+int jl_warp_bounds(const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect) {
+    const char* why = matrix && rect ? jwarp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect) : "null argument";
+    if (why) { g_err = std::string("warp_bounds: ") + why; return -1; }
     return 0;
 }
 
