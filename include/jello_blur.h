@@ -1,7 +1,7 @@
 // jello_blur.h -- the host half of the blur rule (DESIGN.md 5.7 "Blur rule"): which sigma is legal, the radius, and the taps of
-// one axis.  Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_blur_taps, jh_blur) and by the C++ host twin
-// (jello_amd/host/capi.cpp: jl_blur_taps) and by nothing else; tests/blur_ref.py restates it.  The device half -- the two
-// fused-multiply-add sums over these taps -- is jello_amd/csrc/kernels_blur.hip.
+// one axis, and the bytes of the intermediate.  Compiled by the library and the launcher (jello_amd/csrc/jello_hip.cpp: jh_blur_taps,
+// jh_blur; kernels_blur.hip: the intermediate), by the C++ host twin (jello_amd/host/capi.cpp: jl_blur_taps) and by tools/image_rect_check.cpp;
+// tests/blur_ref.py restates it.  The device half -- the two fused-multiply-add sums over these taps -- is jello_amd/csrc/kernels_blur.hip.
 //
 //   sigma   given as binary32, used as binary64; legal: 0 <= sigma <= JBLUR_MAX_SIGMA (a NaN is not)
 //   R       ceil(3 sigma) in binary64, so R <= JBLUR_MAX_RADIUS; sigma = 0: R = 0 and the single tap 1.0f
@@ -11,6 +11,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "jello_image.h"
 
 #define JBLUR_MAX_SIGMA 64.0f
 #define JBLUR_MAX_RADIUS 192u
@@ -41,3 +42,8 @@ static inline uint32_t jblur_taps(float sigma, float* weights) {
     }
     return R;
 }
+
+// The intermediate between the two passes: a binary32 texel (16 bytes) per column of the rectangle r (resolved, inside an image of
+// `height` rows) and per row of the image within radius_y of r's.  jh_blur sizes it and jh_blur_launch fills it by these two alone.
+static inline jimage_rows jblur_scratch_rows(jimage_rect r, uint32_t radius_y, uint32_t height) { return jimage_row_window(r.y, r.h, radius_y, height); }
+static inline uint64_t jblur_scratch_bytes(jimage_rect r, uint32_t radius_y, uint32_t height) { return (uint64_t)jblur_scratch_rows(r, radius_y, height).n_rows * r.w * 16u; }

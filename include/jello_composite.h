@@ -10,6 +10,7 @@
 // Every sum is formed in 64 bits, so int32 offsets and uint32 sizes at their limits neither wrap nor overflow.
 #pragma once
 #include <stdint.h>
+#include "jello_image.h"
 
 typedef struct jcomp_rect {
     uint32_t sx, sy;  // first texel read in src
@@ -36,12 +37,11 @@ static inline uint32_t jcomp_clip_axis(uint32_t s, uint32_t n, int32_t d, uint32
 // 0: *out is the clipped placement (possibly empty); -1: the source rectangle is refused (*out untouched).
 static inline int jcomp_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy,
                              uint32_t dst_w, uint32_t dst_h, jcomp_rect* out) {
-    if (sw == 0u && sh == 0u) { sx = 0u; sy = 0u; sw = src_w; sh = src_h; }  // the whole image (which may have no texels)
-    else if (sw == 0u || sh == 0u) return -1;
-    if ((uint64_t)sx + sw > src_w || (uint64_t)sy + sh > src_h) return -1;
+    if (jimage_rect_check({sx, sy, sw, sh}, src_w, src_h) != JIMAGE_RECT_OK) return -1;
+    const jimage_rect s = jimage_resolve({sx, sy, sw, sh}, src_w, src_h);  // (the whole image may have no texels)
     jcomp_rect r;
-    r.w = jcomp_clip_axis(sx, sw, dx, dst_w, &r.sx, &r.dx);
-    r.h = jcomp_clip_axis(sy, sh, dy, dst_h, &r.sy, &r.dy);
+    r.w = jcomp_clip_axis(s.x, s.w, dx, dst_w, &r.sx, &r.dx);
+    r.h = jcomp_clip_axis(s.y, s.h, dy, dst_h, &r.sy, &r.dy);
     if (r.w == 0u || r.h == 0u) r.sx = r.sy = r.dx = r.dy = r.w = r.h = 0u;
     *out = r;
     return 0;

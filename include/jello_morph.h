@@ -1,5 +1,5 @@
-// jello_morph.h -- the host half of the morphology rule (DESIGN.md 5.11 "Morphology rule"): which descriptor is legal, the resolved
-// rectangle, the rows and bytes of the intermediate, and the order key with its inverse.  Compiled by the library
+// jello_morph.h -- the host half of the morphology rule (DESIGN.md 5.11 "Morphology rule"): which descriptor is legal (its
+// rectangle apart: jello_image.h), the rows and bytes of the intermediate, and the order key with its inverse.  Compiled by the library
 // (jello_amd/csrc/jello_hip.cpp: jh_morphology), by the kernels (jello_amd/csrc/kernels_morph.hip: the key and its inverse are the
 // one text the device and the stand-alone check both compile) and by tools/morph_check.cpp; tests/morph_ref.py restates it.
 //
@@ -37,25 +37,12 @@ JMORPH_HD int32_t jmorph_neutral(int dilate) { return dilate ? (int32_t)0x800000
 // What a position outside the image is staged as: ZERO: +0.0f, whose key is 0; CLAMP: the neutral key.
 JMORPH_HD int32_t jmorph_pad(int dilate, int clamp) { return clamp ? jmorph_neutral(dilate) : 0; }
 
-// The rectangle a descriptor writes in a width x height image: its own, or the whole image for 0 x 0.
-struct jmorph_rect { uint32_t x, y, w, h; };
-static inline jmorph_rect jmorph_resolve(uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t width, uint32_t height) {
-    jmorph_rect r = {x, y, w, h};
-    if (w == 0u && h == 0u) { r.x = 0u; r.y = 0u; r.w = width; r.h = height; }
-    return r;
-}
-
-// nullptr for a legal descriptor on a width x height image, else what is wrong with it (jh_morphology puts "jh_morphology: " in front).
-static inline const char* jmorph_desc_error(int op, int edge, uint32_t flags, uint32_t radius_x, uint32_t radius_y, uint32_t x, uint32_t y,
-                                            uint32_t w, uint32_t h, uint32_t width, uint32_t height) {
+// nullptr for a legal descriptor (the rectangle apart: jimage_rect_check), else what is wrong with it (jh_morphology puts "jh_morphology: " in front).
+static inline const char* jmorph_desc_error(int op, int edge, uint32_t flags, uint32_t radius_x, uint32_t radius_y) {
     if (op != JMORPH_ERODE && op != JMORPH_DILATE) return "unknown op";
     if (edge != JMORPH_EDGE_ZERO && edge != JMORPH_EDGE_CLAMP) return "unknown edge mode";
     if ((flags & ~JMORPH_STRAIGHT) != 0u) return "unknown flag bits";
-    if (radius_x > JMORPH_MAX_RADIUS || radius_y > JMORPH_MAX_RADIUS) return "a radius above 255";
-    if ((w == 0u) != (h == 0u)) return "the rectangle is empty in one dimension";
-    const jmorph_rect r = jmorph_resolve(x, y, w, h, width, height);
-    if ((uint64_t)r.x + r.w > width || (uint64_t)r.y + r.h > height) return "the rectangle is not inside the image";
-    return nullptr;
+    return radius_x > JMORPH_MAX_RADIUS || radius_y > JMORPH_MAX_RADIUS ? "a radius above 255" : nullptr;
 }
 
 // The intermediate: two planes of keys (16 bytes per texel), each rect_w texels wide and jmorph_plane_rows high.  Row v of a plane

@@ -1,7 +1,8 @@
 // jello_resample.h -- the host half of the resample rule (DESIGN.md 5.9 "Resample rule"): which sizes are legal, and the window and
-// the taps of one output index of one axis.  Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_resample_taps, jh_resample)
-// and by the C++ host twin (jello_amd/host/capi.cpp: jl_resample_taps) and by nothing else; tests/resample_ref.py restates it.  The
-// device half -- the two fused-multiply-add sums over these taps -- is jello_amd/csrc/kernels_resample.hip.
+// the taps of one output index of one axis, and the bytes of the intermediate.  Compiled by the library and the launcher
+// (jello_amd/csrc/jello_hip.cpp: jh_resample_taps, jh_resample; kernels_resample.hip: the intermediate), by the C++ host twin
+// (jello_amd/host/capi.cpp: jl_resample_taps) and by tools/image_rect_check.cpp; tests/resample_ref.py restates it.  The device half
+// -- the two fused-multiply-add sums over these taps -- is jello_amd/csrc/kernels_resample.hip.
 //
 // One axis, n_in source texels (the source RECTANGLE's extent) onto n_out; binary64 throughout, nothing contracted:
 //   scale    (double)n_in / (double)n_out;  fs = max(scale, 1.0);  support = base fs, base = 0.5 BOX, 1.0 TRIANGLE, 2.0 CATMULL_ROM,
@@ -17,6 +18,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "jello_image.h"
 
 #define JRESAMPLE_BOX 0
 #define JRESAMPLE_TRIANGLE 1
@@ -85,3 +87,8 @@ static inline uint32_t jresample_taps(int filter, uint32_t n_in, uint32_t n_out,
     if (sum) *sum = S;
     return (uint32_t)(b - a);
 }
+
+// The intermediate between the two passes: a binary32 texel (16 bytes) per row of the source rectangle and per column of the
+// destination rectangle (both resolved).  jh_resample sizes it and jh_resample_launch fills it by these two alone.
+static inline uint32_t jresample_scratch_rows(jimage_rect src) { return src.h; }
+static inline uint64_t jresample_scratch_bytes(jimage_rect src, jimage_rect dst) { return (uint64_t)jresample_scratch_rows(src) * dst.w * 16u; }

@@ -113,14 +113,6 @@ JWARP_HD int32_t jwarp_index(int edge, int32_t i, int32_t n) {
     }
 }
 
-// The rectangle a descriptor names in a width x height image: its own, or the whole image for 0 x 0.
-struct jwarp_rect { uint32_t x, y, w, h; };
-static inline jwarp_rect jwarp_resolve(uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t width, uint32_t height) {
-    jwarp_rect r = {x, y, w, h};
-    if (w == 0u && h == 0u) { r.x = 0u; r.y = 0u; r.w = width; r.h = height; }
-    return r;
-}
-
 // The bounds rectangle {x, y, width, height}: under ZERO every destination texel outside it is transparent black.  The forward
 // images (binary64, uncontracted: (a x + c y) + e, (b x + d y) + f) of the four corners of the src_w x src_h source rectangle grown
 // by m = 0.5 NEAREST, 1 BILINEAR, 2 BICUBIC; floor(min) - 1 and ceil(max) + 1, clipped to the dst_w x dst_h image; empty: 0, 0, 0, 0.
@@ -157,18 +149,11 @@ static inline const char* jwarp_bounds(const double m[6], uint32_t src_w, uint32
     return nullptr;
 }
 
-// nullptr for a legal descriptor between a src_w x src_h and a dst_w x dst_h image (the matrix apart: jwarp_plan), else what is
-// wrong with it (jh_warp puts "jh_warp: " in front).
-static inline const char* jwarp_desc_error(int filter, int edge, uint32_t flags, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, uint32_t src_w,
-                                           uint32_t src_h, uint32_t dx, uint32_t dy, uint32_t dw, uint32_t dh, uint32_t dst_w, uint32_t dst_h) {
+// nullptr for a legal descriptor between a src_w x src_h and a dst_w x dst_h image (the matrix apart: jwarp_plan; the rectangles
+// apart: jimage_rect_check), else what is wrong with it (jh_warp puts "jh_warp: " in front).
+static inline const char* jwarp_desc_error(int filter, int edge, uint32_t flags, uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h) {
     if (!jwarp_filter_ok(filter)) return "unknown filter";
     if (!jwarp_edge_ok(edge)) return "unknown edge mode";
     if ((flags & ~JWARP_STRAIGHT) != 0u) return "unknown flag bits";
-    if (src_w > JWARP_MAX_SIDE || src_h > JWARP_MAX_SIDE || dst_w > JWARP_MAX_SIDE || dst_h > JWARP_MAX_SIDE) return "an image side above 32768";
-    if ((sw == 0u) != (sh == 0u)) return "the source rectangle is empty in one dimension";
-    if ((dw == 0u) != (dh == 0u)) return "the destination rectangle is empty in one dimension";
-    const jwarp_rect s = jwarp_resolve(sx, sy, sw, sh, src_w, src_h), d = jwarp_resolve(dx, dy, dw, dh, dst_w, dst_h);
-    if ((uint64_t)s.x + s.w > src_w || (uint64_t)s.y + s.h > src_h) return "the source rectangle is not inside the source image";
-    if ((uint64_t)d.x + d.w > dst_w || (uint64_t)d.y + d.h > dst_h) return "the destination rectangle is not inside the destination image";
-    return nullptr;
+    return src_w > JWARP_MAX_SIDE || src_h > JWARP_MAX_SIDE || dst_w > JWARP_MAX_SIDE || dst_h > JWARP_MAX_SIDE ? "an image side above 32768" : nullptr;
 }

@@ -138,10 +138,11 @@ struct jh_ctx {
         uint32_t sw = 0, sh = 0, dw = 0, dh = 0;
         JhResampleTables tables = {};
     } resample;
-    // jh_color_filter: the key whose tables the JH_SCR_COLOR_TABLES slot holds
+    // jh_color_filter: the key whose tables the JH_SCR_COLOR_TABLES slot holds, and where
     struct {
         bool valid = false;
         jcolor_key key = {};
+        const char* dev = nullptr;
     } color;
 };
 
@@ -1232,16 +1233,87 @@ static int first_content(jh_ctx* ctx, Alloc* dst, uint32_t width, uint32_t heigh
     dst->written = true;
     return JH_OK;
 }
-// A call whose texels depend on rows outside a band (`why` names them) is refused in band mode.
-static int refuse_band_mode(jh_ctx* ctx, const char* who, const char* why) {
-    if (ctx->band_row0 == 0u && ctx->band_row1 == 0xffffffffu) return JH_OK;
-    return fail(ctx, JH_ERR_INVALID, std::string(who) + ": not in band mode (" + why + ")");
-}
 // band mode: the pixel rows [*row0, *row1) of the active bin rows only (a bin row = 256 pixel rows: an even cut), so that bands of
 // several ranks compose; row1 = row0 when the band lies below the image
 static void band_pixel_rows(const jh_ctx* ctx, uint32_t height, uint32_t* row0, uint32_t* row1) {
     *row0 = (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row0 * 256u, height);
     *row1 = std::max(*row0, (uint32_t)std::min<uint64_t>((uint64_t)ctx->band_row1 * 256u, height));
+}
+
+// What a call from one RGBA16F image into another checks first: the context, the descriptor, both ids known, both images RGBA16F (and
+// of `size`, where the call takes one), two images where the call cannot run in place (`in_place` says what it would do there), and
+// no band set: the call's texels depend on rows outside a band (`band_rows` names them).
+static int image_call_images(jh_ctx* ctx, const char* who, const void* desc, uint64_t src_id, uint64_t dst_id, const char* in_place, const char* band_rows,
+                             Alloc** src, Alloc** dst, const uint32_t* size = nullptr) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": null descriptor");
+    if (int rc = rgba16f_images(ctx, who, {{src_id, "source", src}, {dst_id, "destination", dst}}, size)) return rc;
+    if (in_place && *src == *dst) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": the source is the destination (" + in_place + ")");
+    if (ctx->band_row0 == 0u && ctx->band_row1 == 0xffffffffu) return JH_OK;
+    return fail(ctx, JH_ERR_INVALID, std::string(who) + ": not in band mode (" + band_rows + ")");
+}
+// The refusal of a rectangle after jimage_rect_check's answer (`role`: which rectangle of the call and which image: "", "source " or
+// "destination "), and the rectangle a descriptor names in `image`, resolved into *out, or its refusal.
+static int refuse_rect(jh_ctx* ctx, const char* who, int check, const std::string& role) {
+    return fail(ctx, JH_ERR_INVALID, std::string(who) + ": the " + role + "rectangle is " + (check == JIMAGE_RECT_HALF_EMPTY ? "empty in one dimension" : "not inside the " + role + "image"));
+}
+static int image_call_rect(jh_ctx* ctx, const char* who, jimage_rect named, const Alloc& image, const char* role, jimage_rect* out) {
+    *out = jimage_resolve(named, image.width, image.height);
+    const int check = jimage_rect_check(named, image.width, image.height);
+    return check ? refuse_rect(ctx, who, check, role) : (int)JH_OK;
+}
+// A call is about to write the rectangle `written` of dst from src, inside its query: the views its launcher takes.  The source pointer
+// is taken first: dst may be the same image, and one that was never written reads as transparent black (null), not as its memory.
+struct ImageViews { jimage_src from; jimage_dst to; };
+static int image_call_views(jh_ctx* ctx, const Alloc* src, Alloc* dst, jimage_rect written, ImageViews* v) {
+    v->from = {content_or_null(*src), src->width, src->height};
+    if (int rc = first_content(ctx, dst, written.w, written.h)) return rc;
+    v->to = {dst->ptr, dst->width, dst->height};
+    return JH_OK;
+}
+
+// `bytes` of scratch slot `slot` into *out, in a call's `prepare` (`remedy`: scratch_failure's advice).
+static int scratch_take(jh_ctx* ctx, const char* who, const char* remedy, int slot, uint64_t bytes, void** out) {
+    if ((*out = jh_scratch_get(&ctx->scratch, slot, bytes))) return JH_OK;
+    return fail(ctx, JH_ERR_OOM, std::string(who) + ": " + scratch_failure(ctx, remedy));
+}
+// Bytes that have to be in a scratch slot before a call's launch.  slot_upload_take, in `prepare`: the slot, and a copy in the pinned
+// arena (as jh_upload: the DMA is left in flight); slot_upload_send, in `launch`: the asynchronous copy (the query holds the upload too).
+struct SlotUpload { char* dev = nullptr; void* staged = nullptr; uint64_t bytes = 0; };
+static int slot_upload_take(jh_ctx* ctx, const char* who, const char* remedy, int slot, const void* data, uint64_t bytes, SlotUpload* u) {
+    u->bytes = bytes;
+    if (int rc = scratch_take(ctx, who, remedy, slot, bytes, (void**)&u->dev)) return rc;
+    if ((u->staged = stage_copy(ctx, data, bytes))) return JH_OK;
+    return fail(ctx, JH_ERR_OOM, std::string(who) + ": pinned staging allocation failed");
+}
+static int slot_upload_send(jh_ctx* ctx, const SlotUpload& u) {
+    HIP_TRY(ctx, hipMemcpyAsync(u.dev, u.staged, u.bytes, hipMemcpyHostToDevice, ctx->stream));
+    return JH_OK;
+}
+// Tables a call keeps in a scratch slot of their own under a key of the context's (jh_resample: one geometry, jh_color_filter: one
+// key): content that a captured call reads on every replay.  `resident`: the slot holds this call's, nothing is uploaded.  A capture
+// can neither grow an array nor upload, so its tables have to be resident: the blob is built only where to_build(), tables_take (in
+// `prepare`) refuses the capture, and tables_send (in `launch`) invalidates the key, uploads, has set_key(device pointer) note the
+// new key and bumps the generation (a graph captured against the tables of another key would read these).
+struct ResidentTables {
+    bool resident;
+    SlotUpload up;
+    bool to_build(const jh_ctx* ctx) const { return !resident && !ctx->capturing; }
+};
+static int tables_take(jh_ctx* ctx, const char* who, const char* remedy, int slot, const std::vector<char>& blob, ResidentTables* t) {
+    if (t->resident) return JH_OK;
+    if (ctx->capturing) return fail(ctx, JH_ERR_OOM, std::string(who) + ": " + scratch_failure(ctx, remedy));
+    return slot_upload_take(ctx, who, remedy, slot, blob.data(), blob.size(), &t->up);
+}
+extern "C++" template <class SetKey>
+static int tables_send(jh_ctx* ctx, const ResidentTables& t, bool* valid, SetKey&& set_key) {
+    if (t.resident) return JH_OK;
+    *valid = false;
+    if (int rc = slot_upload_send(ctx, t.up)) return rc;
+    set_key(t.up.dev);
+    *valid = true;
+    ctx->generation++;
+    return JH_OK;
 }
 
 // surface blit (RenderToSurface's blit pass, engine/wgpu_engine/lib.go:109-198, 266-333; kernels_surface.hip)
@@ -1372,22 +1444,14 @@ int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_pa
     std::memcpy(blob.data() + o_pats, job.pats.data(), job.pats.size() * sizeof(JDashPat));
     if (!job.runs.empty()) std::memcpy(blob.data() + o_runs, job.runs.data(), job.runs.size() * sizeof(JDashRun));
     std::memcpy(blob.data() + o_first, job.path_first_seg.data(), job.path_first_seg.size() * 4u);
-    char* dev = nullptr;
-    void* staged = nullptr;
+    SlotUpload up;
     return post_render_call(
-        ctx, "dash",
+        ctx, "dash", [&] { return slot_upload_take(ctx, "jh_dash", "dash outside the capture", JH_SCR_A, blob.data(), bytes, &up); },
         [&] {
-            dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_A, bytes);
-            if (!dev) return fail(ctx, JH_ERR_OOM, "jh_dash: scratch allocation failed");
-            staged = stage_copy(ctx, blob.data(), bytes);  // the pinned arena, as jh_upload: the DMA is left in flight
-            if (!staged) return fail(ctx, JH_ERR_OOM, "jh_dash: pinned staging allocation failed");
-            return (int)JH_OK;
-        },
-        [&] {  // (the query holds the upload too)
-            HIP_TRY(ctx, hipMemcpyAsync(dev, staged, bytes, hipMemcpyHostToDevice, ctx->stream));
+            if (int rc = slot_upload_send(ctx, up)) return rc;
             JhDashJob dj;
-            dj.segs = (const JDashSeg*)dev; dj.subs = (const JDashSub*)(dev + o_subs); dj.pats = (const JDashPat*)(dev + o_pats);
-            dj.runs = (const JDashRun*)(dev + o_runs); dj.path_first_seg = (const uint32_t*)(dev + o_first);
+            dj.segs = (const JDashSeg*)up.dev; dj.subs = (const JDashSub*)(up.dev + o_subs); dj.pats = (const JDashPat*)(up.dev + o_pats);
+            dj.runs = (const JDashRun*)(up.dev + o_runs); dj.path_first_seg = (const uint32_t*)(up.dev + o_first);
             dj.n_segs = (uint32_t)job.segs.size(); dj.n_subs = (uint32_t)job.subs.size(); dj.n_paths = n_paths;
             const std::vector<JhBound> none;
             const JhResult lr = jh_dash_launch(make_launch(ctx, 0, 0, 0, none), dj, out_els, out_capacity, out_index);
@@ -1406,47 +1470,32 @@ int jh_blur_taps(float sigma, float* weights, uint32_t* radius) {
 }
 
 int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc) {
-    if (!ctx) return JH_ERR_INVALID;
-    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_blur: null descriptor");
-    const uint32_t size[2] = {width, height};
     Alloc *src = nullptr, *dst = nullptr;
-    if (int rc = rgba16f_images(ctx, "jh_blur", {{src_image_id, "source", &src}}, size)) return rc;
-    if (int rc = rgba16f_images(ctx, "jh_blur", {{dst_image_id, "destination", &dst}}, size)) return rc;
+    const uint32_t size[2] = {width, height};
+    if (int rc = image_call_images(ctx, "jh_blur", desc, src_image_id, dst_image_id, nullptr, "the rows next to a band belong to another rank", &src, &dst, size)) return rc;
     if (!jblur_sigma_ok(desc->sigma_x) || !jblur_sigma_ok(desc->sigma_y)) return fail(ctx, JH_ERR_INVALID, "jh_blur: sigma is negative, above 64 or NaN");
     if (desc->edge != JH_BLUR_EDGE_ZERO && desc->edge != JH_BLUR_EDGE_CLAMP) return fail(ctx, JH_ERR_INVALID, "jh_blur: unknown edge mode");
-    uint32_t x = desc->x, y = desc->y, rw = desc->width, rh = desc->height;
-    if (rw == 0u && rh == 0u) { x = 0u; y = 0u; rw = width; rh = height; }  // the whole image
-    else if (rw == 0u || rh == 0u) return fail(ctx, JH_ERR_INVALID, "jh_blur: the rectangle is empty in one dimension");
-    if ((uint64_t)x + rw > width || (uint64_t)y + rh > height) return fail(ctx, JH_ERR_INVALID, "jh_blur: the rectangle is not inside the image");
-    if (int rc = refuse_band_mode(ctx, "jh_blur", "the rows next to a band belong to another rank")) return rc;
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_blur", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
     float taps_x[2u * JBLUR_MAX_RADIUS + 1u], taps_y[2u * JBLUR_MAX_RADIUS + 1u];
     const uint32_t radius_x = jblur_taps(desc->sigma_x, taps_x), radius_y = jblur_taps(desc->sigma_y, taps_y);
     void* tmp = nullptr;
     return post_render_call(
         ctx, "blur",
+        [&] { return scratch_take(ctx, "jh_blur", "blur a rectangle of this size once eagerly first", JH_SCR_BLUR, jblur_scratch_bytes(r, radius_y, height), &tmp); },
         [&] {
-            if (rw == 0u || rh == 0u) return (int)JH_OK;  // (an image without texels)
-            const uint64_t rows = std::min<uint64_t>(height, (uint64_t)y + rh + radius_y) - (y > radius_y ? y - radius_y : 0u);
-            tmp = jh_scratch_get(&ctx->scratch, JH_SCR_BLUR, rows * rw * 16u);
-            if (tmp) return (int)JH_OK;
-            return fail(ctx, JH_ERR_OOM, "jh_blur: " + scratch_failure(ctx, "blur a rectangle of this size once eagerly first"));
-        },
-        [&] {
-            if (rw == 0u || rh == 0u) return (int)JH_OK;
-            const void* from = content_or_null(*src);  // (before dst, which may be the same image, becomes written)
-            if (int rc = first_content(ctx, dst, rw, rh)) return rc;
-            return launch_status(ctx, "jh_blur", jh_blur_launch(ctx->stream, from, dst->ptr, width, height, x, y, rw, rh, desc->edge == JH_BLUR_EDGE_CLAMP,
-                                                                taps_x, radius_x, taps_y, radius_y, tmp, ctx->num_cus));
+            ImageViews v;
+            if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
+            return launch_status(ctx, "jh_blur", jh_blur_launch(ctx->stream, v.from, v.to, r, desc->edge == JH_BLUR_EDGE_CLAMP, taps_x, radius_x, taps_y,
+                                                                radius_y, tmp, ctx->num_cus));
         });
 }
 
 // composite (include/jello_hip.h "Composite"; the geometry: include/jello_composite.h; kernels_composite.hip)
 int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_composite_desc* desc) {
-    if (!ctx) return JH_ERR_INVALID;
-    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_composite: null descriptor");
     Alloc *src = nullptr, *dst = nullptr;
-    if (int rc = rgba16f_images(ctx, "jh_composite", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
-    if (src == dst) return fail(ctx, JH_ERR_INVALID, "jh_composite: the source is the destination (a shifted blend in place reads what it writes)");
+    if (int rc = image_call_images(ctx, "jh_composite", desc, src_image_id, dst_image_id, "a shifted blend in place reads what it writes", "a shifted source row belongs to another rank", &src, &dst)) return rc;
     if (desc->mix > 15u) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown mix mode (Mix.Clip is not a blend of two images)");
     if (desc->compose > 13u) return fail(ctx, JH_ERR_INVALID, "jh_composite: unknown compose operator");
     if (!(desc->opacity >= 0.0f && desc->opacity <= 1.0f)) return fail(ctx, JH_ERR_INVALID, "jh_composite: opacity is outside [0, 1] or NaN");
@@ -1459,14 +1508,13 @@ int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, cons
     jcomp_rect rect;
     if (jcomp_clip(src->width, src->height, desc->sx, desc->sy, desc->sw, desc->sh, desc->dx, desc->dy, dst->width, dst->height, &rect))
         return fail(ctx, JH_ERR_INVALID, "jh_composite: the source rectangle is not inside the source image or is empty in one dimension");
-    if (int rc = refuse_band_mode(ctx, "jh_composite", "a shifted source row belongs to another rank")) return rc;
     if (rect.w == 0u || rect.h == 0u) return JH_OK;  // placed outside dst: nothing to write, nothing launched
     return post_render_call(ctx, "composite", [&] {
         const bool backdrop = dst->written || dst->stored;
-        if (int rc = first_content(ctx, dst, rect.w, rect.h)) return rc;
-        return launch_status(ctx, "jh_composite",
-                             jh_composite_launch(ctx->stream, content_or_null(*src), src->width, src->height, dst->ptr, dst->width, dst->height, backdrop,
-                                                 &rect, desc->mix << 8 | desc->compose, desc->flags, desc->opacity, desc->tint, ctx->num_cus));
+        ImageViews v;
+        if (int rc = image_call_views(ctx, src, dst, {rect.dx, rect.dy, rect.w, rect.h}, &v)) return rc;
+        return launch_status(ctx, "jh_composite", jh_composite_launch(ctx->stream, v.from, v.to, backdrop, &rect, desc->mix << 8 | desc->compose, desc->flags,
+                                                                      desc->opacity, desc->tint, ctx->num_cus));
     });
 }
 
@@ -1541,61 +1589,39 @@ static bool resample_build(int filter, uint32_t sw, uint32_t sh, uint32_t dw, ui
 }
 
 int jh_resample(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_resample_desc* desc) {
-    if (!ctx) return JH_ERR_INVALID;
-    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_resample: null descriptor");
+    static const char* const kRemedy = "resample this geometry once eagerly first";
     Alloc *src = nullptr, *dst = nullptr;
-    if (int rc = rgba16f_images(ctx, "jh_resample", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
-    if (src == dst) return fail(ctx, JH_ERR_INVALID, "jh_resample: the source is the destination (a resize in place reads what it writes)");
+    if (int rc = image_call_images(ctx, "jh_resample", desc, src_image_id, dst_image_id, "a resize in place reads what it writes", "the rows a window reads belong to another rank", &src, &dst)) return rc;
     if (!jresample_filter_ok(desc->filter)) return fail(ctx, JH_ERR_INVALID, "jh_resample: unknown filter");
     if ((desc->flags & ~(uint32_t)JH_RESAMPLE_STRAIGHT) != 0u) return fail(ctx, JH_ERR_INVALID, "jh_resample: unknown flag bits");
-    uint32_t sx = desc->src_x, sy = desc->src_y, sw = desc->src_width, sh = desc->src_height;
-    uint32_t dx = desc->dst_x, dy = desc->dst_y, dw = desc->dst_width, dh = desc->dst_height;
-    if (sw == 0u && sh == 0u) { sx = 0u; sy = 0u; sw = src->width; sh = src->height; }  // the whole image
-    if (dw == 0u && dh == 0u) { dx = 0u; dy = 0u; dw = dst->width; dh = dst->height; }
-    if (sw == 0u || sh == 0u || dw == 0u || dh == 0u) return fail(ctx, JH_ERR_INVALID, "jh_resample: a rectangle is empty in one dimension");
-    if ((uint64_t)sx + sw > src->width || (uint64_t)sy + sh > src->height)
-        return fail(ctx, JH_ERR_INVALID, "jh_resample: the source rectangle is not inside the source image");
-    if ((uint64_t)dx + dw > dst->width || (uint64_t)dy + dh > dst->height)
-        return fail(ctx, JH_ERR_INVALID, "jh_resample: the destination rectangle is not inside the destination image");
-    if (!jresample_sizes_ok(sw, dw) || !jresample_sizes_ok(sh, dh)) return fail(ctx, JH_ERR_INVALID, "jh_resample: a ratio above 16:1");
-    if (int rc = refuse_band_mode(ctx, "jh_resample", "the rows a window reads belong to another rank")) return rc;
+    jimage_rect s, d;
+    if (int rc = image_call_rect(ctx, "jh_resample", {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, *src, "source ", &s)) return rc;
+    if (int rc = image_call_rect(ctx, "jh_resample", {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, *dst, "destination ", &d)) return rc;
+    if (jimage_rect_empty(s) || jimage_rect_empty(d)) return fail(ctx, JH_ERR_INVALID, "jh_resample: an image without texels");
+    if (!jresample_sizes_ok(s.w, d.w) || !jresample_sizes_ok(s.h, d.h)) return fail(ctx, JH_ERR_INVALID, "jh_resample: a ratio above 16:1");
     auto& key = ctx->resample;
-    const bool resident = key.valid && key.filter == desc->filter && key.sw == sw && key.sh == sh && key.dw == dw && key.dh == dh;
+    ResidentTables tables = {key.valid && key.filter == desc->filter && key.sw == s.w && key.sh == s.h && key.dw == d.w && key.dh == d.h, {}};
     ResampleBlob blob;
-    if (!resident && !ctx->capturing && !resample_build(desc->filter, sw, sh, dw, dh, blob))
-        return fail(ctx, JH_ERR_INVALID, "jh_resample: a window without taps");
-    void *tmp = nullptr, *staged = nullptr;
-    char* dev = nullptr;
+    if (tables.to_build(ctx) && !resample_build(desc->filter, s.w, s.h, d.w, d.h, blob)) return fail(ctx, JH_ERR_INVALID, "jh_resample: a window without taps");
+    void* tmp = nullptr;
     return post_render_call(
         ctx, "resample",
         [&] {
-            // (a capture can neither grow an array nor upload: its geometry has to be resident)
-            tmp = jh_scratch_get(&ctx->scratch, JH_SCR_RESAMPLE, (uint64_t)sh * dw * 16u);
-            if (tmp && !resident && !ctx->capturing) dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_RESAMPLE_TAPS, blob.bytes.size());
-            if (!tmp || (!resident && !dev))
-                return fail(ctx, JH_ERR_OOM, "jh_resample: " + scratch_failure(ctx, "resample this geometry once eagerly first"));
-            if (!resident) {
-                staged = stage_copy(ctx, blob.bytes.data(), blob.bytes.size());  // the pinned arena, as jh_upload: the DMA is left in flight
-                if (!staged) return fail(ctx, JH_ERR_OOM, "jh_resample: pinned staging allocation failed");
-            }
-            return (int)JH_OK;
+            if (int rc = scratch_take(ctx, "jh_resample", kRemedy, JH_SCR_RESAMPLE, jresample_scratch_bytes(s, d), &tmp)) return rc;
+            return tables_take(ctx, "jh_resample", kRemedy, JH_SCR_RESAMPLE_TAPS, blob.bytes, &tables);
         },
-        [&] {  // (the query holds the upload too)
-            const void* from = content_or_null(*src);
-            if (int rc = first_content(ctx, dst, dw, dh)) return rc;
-            if (!resident) {
-                key.valid = false;
-                HIP_TRY(ctx, hipMemcpyAsync(dev, staged, blob.bytes.size(), hipMemcpyHostToDevice, ctx->stream));
+        [&] {
+            ImageViews v;
+            if (int rc = image_call_views(ctx, src, dst, d, &v)) return rc;
+            const int rc = tables_send(ctx, tables, &key.valid, [&](const char* dev) {
                 JhResampleTables& t = key.tables;
                 t.win_x = (const uint2*)dev; t.seg_x = (const uint4*)(dev + blob.o_seg_x); t.w_x = (const float*)(dev + blob.o_w_x);
                 t.win_y = (const uint2*)(dev + blob.o_win_y); t.w_y = (const float*)(dev + blob.o_w_y);
                 t.taps_x = blob.taps_x; t.stride_y = blob.stride_y; t.region_x = blob.region_x;
-                key.filter = desc->filter; key.sw = sw; key.sh = sh; key.dw = dw; key.dh = dh;
-                key.valid = true;
-                ctx->generation++;  // (a graph captured against the tables of another geometry would read these)
-            }
-            return launch_status(ctx, "jh_resample", jh_resample_launch(ctx->stream, from, src->width, src->height, sx, sy, sw, sh, dst->ptr, dst->width,
-                                                                        dst->height, dx, dy, dw, dh, (desc->flags & JH_RESAMPLE_STRAIGHT) != 0u, &key.tables,
+                key.filter = desc->filter; key.sw = s.w; key.sh = s.h; key.dw = d.w; key.dh = d.h;
+            });
+            if (rc) return rc;
+            return launch_status(ctx, "jh_resample", jh_resample_launch(ctx->stream, v.from, s, v.to, d, (desc->flags & JH_RESAMPLE_STRAIGHT) != 0u, &key.tables,
                                                                         tmp, ctx->num_cus));
         });
 }
@@ -1609,98 +1635,66 @@ int jh_color_tables(const jh_color_desc* desc, float* pre, uint16_t* post, uint3
 }
 
 int jh_color_filter(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_color_desc* desc) {
-    if (!ctx) return JH_ERR_INVALID;
-    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_color_filter: null descriptor");
     Alloc *src = nullptr, *dst = nullptr;
-    if (int rc = rgba16f_images(ctx, "jh_color_filter", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
+    if (int rc = image_call_images(ctx, "jh_color_filter", desc, src_image_id, dst_image_id, nullptr, "a band's rows are one rank's, the tables and their key the context's", &src, &dst)) return rc;
     if (const char* why = jcolor_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_color_filter: ") + why);
     for (float m : desc->matrix)
         if (!std::isfinite(m)) return fail(ctx, JH_ERR_INVALID, "jh_color_filter: a matrix entry is not finite");
-    uint32_t x = desc->x, y = desc->y, rw = desc->width, rh = desc->height;
-    if (rw == 0u && rh == 0u) { x = 0u; y = 0u; rw = src->width; rh = src->height; }  // the whole image
-    else if (rw == 0u || rh == 0u) return fail(ctx, JH_ERR_INVALID, "jh_color_filter: the rectangle is empty in one dimension");
-    if ((uint64_t)x + rw > src->width || (uint64_t)y + rh > src->height)
-        return fail(ctx, JH_ERR_INVALID, "jh_color_filter: the rectangle is not inside the source image");
-    if ((uint64_t)x + rw > dst->width || (uint64_t)y + rh > dst->height)
-        return fail(ctx, JH_ERR_INVALID, "jh_color_filter: the rectangle is not inside the destination image");
-    if (int rc = refuse_band_mode(ctx, "jh_color_filter", "a band's rows are one rank's, the tables and their key the context's")) return rc;
-    if (rw == 0u || rh == 0u) return JH_OK;  // (an image without texels)
+    jimage_rect r;  // (named in the source, where 0 x 0 is the whole of it, and the same texels of the destination)
+    if (int rc = image_call_rect(ctx, "jh_color_filter", {desc->x, desc->y, desc->width, desc->height}, *src, "source ", &r)) return rc;
+    if (!jimage_rect_inside(r, dst->width, dst->height)) return refuse_rect(ctx, "jh_color_filter", JIMAGE_RECT_OUTSIDE, "destination ");
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
     const uint32_t which = jcolor_which(desc);
     jcolor_key key;
     jcolor_key_of(desc, &key);
-    const bool resident = which == 0u || (ctx->color.valid && jcolor_key_equal(&ctx->color.key, &key));
+    // (a filter without tables does not touch the slot: nothing of it has to be resident)
+    ResidentTables tables = {which == 0u || (ctx->color.valid && jcolor_key_equal(&ctx->color.key, &key)), {}};
     const uint64_t pre_bytes = 3ull * JCOLOR_ENTRIES * sizeof(float), all_bytes = pre_bytes + 4ull * JCOLOR_ENTRIES * sizeof(uint16_t);
     std::vector<char> blob;
-    if (!resident && !ctx->capturing) {
+    if (tables.to_build(ctx)) {
         blob.assign(all_bytes, 0);
         jcolor_tables(desc, (float*)blob.data(), (uint16_t*)(blob.data() + pre_bytes));
     }
-    char* dev = nullptr;
-    void* staged = nullptr;
     return post_render_call(
-        ctx, "color",
+        ctx, "color", [&] { return tables_take(ctx, "jh_color_filter", "run this filter once eagerly first", JH_SCR_COLOR_TABLES, blob, &tables); },
         [&] {
-            if (which == 0u) return (int)JH_OK;  // (no tables: the slot is not touched)
-            // (a capture can neither grow an array nor upload: its key has to be resident)
-            if (resident || !ctx->capturing) dev = (char*)jh_scratch_get(&ctx->scratch, JH_SCR_COLOR_TABLES, all_bytes);
-            if (!dev) return fail(ctx, JH_ERR_OOM, "jh_color_filter: " + scratch_failure(ctx, "run this filter once eagerly first"));
-            if (!resident) {
-                staged = stage_copy(ctx, blob.data(), blob.size());  // the pinned arena, as jh_upload: the DMA is left in flight
-                if (!staged) return fail(ctx, JH_ERR_OOM, "jh_color_filter: pinned staging allocation failed");
-            }
-            return (int)JH_OK;
-        },
-        [&] {  // (the query holds the upload too)
-            const void* from = content_or_null(*src);  // (before dst, which may be the same image, becomes written)
-            if (int rc = first_content(ctx, dst, rw, rh)) return rc;
-            if (!resident) {
-                ctx->color.valid = false;
-                HIP_TRY(ctx, hipMemcpyAsync(dev, staged, all_bytes, hipMemcpyHostToDevice, ctx->stream));
-                ctx->color.key = key;
-                ctx->color.valid = true;
-                ctx->generation++;  // (a graph captured against the tables of another key would read these)
-            }
+            ImageViews v;
+            if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
+            if (int rc = tables_send(ctx, tables, &ctx->color.valid, [&](const char* dev) { ctx->color.key = key; ctx->color.dev = dev; })) return rc;
+            const char* dev = ctx->color.dev;
             const float* pre = (which & JCOLOR_PRE(0)) ? (const float*)dev : nullptr;
             const uint16_t* post[4];
             for (uint32_t i = 0; i < 4u; i++) post[i] = (which & JCOLOR_POST(i)) ? (const uint16_t*)(dev + pre_bytes) + (size_t)i * JCOLOR_ENTRIES : nullptr;
             return launch_status(ctx, "jh_color_filter",
-                                 jh_color_launch(ctx->stream, from, src->width, src->height, dst->ptr, dst->width, dst->height, x, y, rw, rh, desc->matrix,
-                                                 (desc->flags & JH_COLOR_CLAMP) != 0u, pre, post, ctx->num_cus));
+                                 jh_color_launch(ctx->stream, v.from, v.to, r, desc->matrix, (desc->flags & JH_COLOR_CLAMP) != 0u, pre, post, ctx->num_cus));
         });
 }
 
 // morphology (include/jello_hip.h "Morphology"; the descriptor, the planes and the key: include/jello_morph.h; kernels_morph.hip)
 int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_morph_desc* desc) {
-    if (!ctx) return JH_ERR_INVALID;
-    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_morphology: null descriptor");
     static_assert(JH_MORPH_ERODE == JMORPH_ERODE && JH_MORPH_DILATE == JMORPH_DILATE && JH_MORPH_EDGE_ZERO == JMORPH_EDGE_ZERO &&
                       JH_MORPH_EDGE_CLAMP == JMORPH_EDGE_CLAMP && JH_MORPH_STRAIGHT == JMORPH_STRAIGHT && JH_MORPH_MAX_RADIUS == JMORPH_MAX_RADIUS,
                   "the C ABI's values are the rule's");
     Alloc *src = nullptr, *dst = nullptr;
-    if (int rc = rgba16f_images(ctx, "jh_morphology", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
+    if (int rc = image_call_images(ctx, "jh_morphology", desc, src_image_id, dst_image_id, nullptr, "the rows next to a band belong to another rank", &src, &dst)) return rc;
     if (src->width != dst->width || src->height != dst->height) return fail(ctx, JH_ERR_INVALID, "jh_morphology: the images differ in size");
-    const uint32_t width = dst->width, height = dst->height;
-    if (const char* why = jmorph_desc_error(desc->op, desc->edge, desc->flags, desc->radius_x, desc->radius_y, desc->x, desc->y, desc->width, desc->height, width, height))
-        return fail(ctx, JH_ERR_INVALID, std::string("jh_morphology: ") + why);
-    if (int rc = refuse_band_mode(ctx, "jh_morphology", "the rows next to a band belong to another rank")) return rc;
-    const jmorph_rect r = jmorph_resolve(desc->x, desc->y, desc->width, desc->height, width, height);
+    if (const char* why = jmorph_desc_error(desc->op, desc->edge, desc->flags, desc->radius_x, desc->radius_y)) return fail(ctx, JH_ERR_INVALID, std::string("jh_morphology: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_morphology", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
     void* tmp = nullptr;
     return post_render_call(
         ctx, "morphology",
         [&] {
-            if (r.w == 0u || r.h == 0u) return (int)JH_OK;  // (an image without texels)
-            tmp = jh_scratch_get(&ctx->scratch, JH_SCR_MORPH, jmorph_scratch_bytes(r.w, r.h, desc->radius_y));
-            if (tmp) return (int)JH_OK;
-            return fail(ctx, JH_ERR_OOM, "jh_morphology: " + scratch_failure(ctx, "run a call of this rectangle size and these radii once eagerly first"));
+            return scratch_take(ctx, "jh_morphology", "run a call of this rectangle size and these radii once eagerly first", JH_SCR_MORPH,
+                                jmorph_scratch_bytes(r.w, r.h, desc->radius_y), &tmp);
         },
         [&] {
-            if (r.w == 0u || r.h == 0u) return (int)JH_OK;
-            const void* from = content_or_null(*src);  // (before dst, which may be the same image, becomes written)
-            if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
+            ImageViews v;
+            if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
             return launch_status(ctx, "jh_morphology",
-                                 jh_morph_launch(ctx->stream, from, dst->ptr, width, height, r.x, r.y, r.w, r.h, desc->op == JH_MORPH_DILATE,
-                                                 desc->edge == JH_MORPH_EDGE_CLAMP, (desc->flags & JH_MORPH_STRAIGHT) != 0u, desc->radius_x, desc->radius_y, tmp,
-                                                 ctx->num_cus));
+                                 jh_morph_launch(ctx->stream, v.from, v.to, r, desc->op == JH_MORPH_DILATE, desc->edge == JH_MORPH_EDGE_CLAMP,
+                                                 (desc->flags & JH_MORPH_STRAIGHT) != 0u, desc->radius_x, desc->radius_y, tmp, ctx->num_cus));
         });
 }
 
@@ -1714,31 +1708,29 @@ int jh_warp_bounds(const double matrix[6], uint32_t src_w, uint32_t src_h, int f
     return jwarp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect) ? JH_ERR_INVALID : JH_OK;
 }
 int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_warp_desc* desc) {
-    if (!ctx) return JH_ERR_INVALID;
-    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_warp: null descriptor");
     static_assert(JH_WARP_NEAREST == JWARP_NEAREST && JH_WARP_BILINEAR == JWARP_BILINEAR && JH_WARP_BICUBIC == JWARP_BICUBIC &&
                       JH_WARP_EDGE_ZERO == JWARP_EDGE_ZERO && JH_WARP_EDGE_CLAMP == JWARP_EDGE_CLAMP && JH_WARP_EDGE_REPEAT == JWARP_EDGE_REPEAT &&
                       JH_WARP_EDGE_MIRROR == JWARP_EDGE_MIRROR && JH_WARP_STRAIGHT == JWARP_STRAIGHT && JH_WARP_MAX_SIDE == JWARP_MAX_SIDE,
                   "the C ABI's values are the rule's");
     Alloc *src = nullptr, *dst = nullptr;
-    if (int rc = rgba16f_images(ctx, "jh_warp", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}})) return rc;
-    if (src == dst) return fail(ctx, JH_ERR_INVALID, "jh_warp: the source is the destination (a warp in place reads what it writes)");
-    if (const char* why = jwarp_desc_error(desc->filter, desc->edge, desc->flags, desc->src_x, desc->src_y, desc->src_width, desc->src_height, src->width,
-                                           src->height, desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height, dst->width, dst->height))
+    if (int rc = image_call_images(ctx, "jh_warp", desc, src_image_id, dst_image_id, "a warp in place reads what it writes", "the rows a tap reads belong to another rank", &src, &dst)) return rc;
+    if (const char* why = jwarp_desc_error(desc->filter, desc->edge, desc->flags, src->width, src->height, dst->width, dst->height))
         return fail(ctx, JH_ERR_INVALID, std::string("jh_warp: ") + why);
+    jimage_rect s, d;
+    if (int rc = image_call_rect(ctx, "jh_warp", {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, *src, "source ", &s)) return rc;
+    if (int rc = image_call_rect(ctx, "jh_warp", {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, *dst, "destination ", &d)) return rc;
     int64_t plan[6];
     if (const char* why = jwarp_plan(desc->matrix, plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_warp: illegal matrix: ") + why);
-    if (int rc = refuse_band_mode(ctx, "jh_warp", "the rows a tap reads belong to another rank")) return rc;
-    const jwarp_rect s = jwarp_resolve(desc->src_x, desc->src_y, desc->src_width, desc->src_height, src->width, src->height);
-    const jwarp_rect d = jwarp_resolve(desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height, dst->width, dst->height);
+    if (jimage_rect_empty(d)) return JH_OK;  // (an image without texels)
     return post_render_call(ctx, "warp", [&] {
-        if (d.w == 0u || d.h == 0u) return (int)JH_OK;  // (an image without texels)
-        const void* from = s.w == 0u || s.h == 0u ? nullptr : content_or_null(*src);
-        if (int rc = first_content(ctx, dst, d.w, d.h)) return rc;
-        const uint32_t sw = s.w ? s.w : 1u, sh = s.h ? s.h : 1u;  // (a source without texels reads as transparent black: nothing is loaded)
-        return launch_status(ctx, "jh_warp", jh_warp_launch(ctx->stream, from, s.w ? src->width : 1u, s.h ? src->height : 1u, s.x, s.y, sw, sh, dst->ptr,
-                                                            dst->width, dst->height, d.x, d.y, d.w, d.h, plan, desc->filter, desc->edge,
-                                                            (desc->flags & JH_WARP_STRAIGHT) != 0u, ctx->num_cus));
+        ImageViews v;
+        if (int rc = image_call_views(ctx, src, dst, d, &v)) return rc;
+        if (jimage_rect_empty(s)) {  // a source without texels reads as transparent black: nothing is loaded, and the launcher gets a texel it can name
+            v.from = {nullptr, std::max(src->width, 1u), std::max(src->height, 1u)};
+            s = {s.x, s.y, std::max(s.w, 1u), std::max(s.h, 1u)};
+        }
+        return launch_status(ctx, "jh_warp",
+                             jh_warp_launch(ctx->stream, v.from, s, v.to, d, plan, desc->filter, desc->edge, (desc->flags & JH_WARP_STRAIGHT) != 0u, ctx->num_cus));
     });
 }
 

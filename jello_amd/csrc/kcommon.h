@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/jello_formats.h"
+#include "../../include/jello_image.h"
 #include "dmath.h"
 #include "kwave.h"
 
@@ -356,7 +357,8 @@ struct JhResampleTables {
 
 // The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
-// side only does not compile.  int results: 0, -1 for arguments the launcher refuses, another negative value for a failed launch.
+// side only does not compile.  int results: 0, -1 for arguments the launcher refuses (an image launcher, which takes the views and resolved
+// rectangles of include/jello_image.h: a rectangle that is not inside its image), another negative value (-2) for a failed launch.
 extern "C" {
 int jh_blit_launch(hipStream_t stream, const void* src, void* dst, uint64_t pitch, uint32_t width, uint32_t row0, uint32_t row1, int format,
                    int num_cus);
@@ -367,22 +369,19 @@ int jh_pack_launch(hipStream_t stream, const void* src, uint64_t src_pitch, cons
                    uint32_t texel_bytes, void* dst, void* cls, void* totals);
 int jh_unpack_launch(hipStream_t stream, const void* pack, uint64_t pack_bytes, void* dst, uint64_t dst_pitch, uint32_t width, uint32_t height,
                      uint32_t texel_bytes, uint32_t* rejects);
-int jh_blur_launch(hipStream_t stream, const void* src, void* dst, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t rect_w,
-                   uint32_t rect_h, int clamp, const float* taps_x, uint32_t radius_x, const float* taps_y, uint32_t radius_y, void* tmp, int num_cus);
+int jh_blur_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect rect, int clamp, const float* taps_x, uint32_t radius_x,
+                   const float* taps_y, uint32_t radius_y, void* tmp, int num_cus);
 struct jcomp_rect;  // include/jello_composite.h
-int jh_composite_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h,
-                        int dst_has_content, const jcomp_rect* rect, uint32_t mode, uint32_t flags, float opacity, const float* tint, int num_cus);
-int jh_resample_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh,
-                       void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t dx, uint32_t dy, uint32_t dw, uint32_t dh, int straight,
+int jh_composite_launch(hipStream_t stream, jimage_src src, jimage_dst dst, int dst_has_content, const jcomp_rect* rect, uint32_t mode,
+                        uint32_t flags, float opacity, const float* tint, int num_cus);
+int jh_resample_launch(hipStream_t stream, jimage_src src, jimage_rect src_rect, jimage_dst dst, jimage_rect dst_rect, int straight,
                        const JhResampleTables* tables, void* tmp, int num_cus);
-int jh_color_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t x,
-                    uint32_t y, uint32_t rect_w, uint32_t rect_h, const float* matrix, int clamp, const float* pre, const uint16_t* const* post,
-                    int num_cus);
-int jh_morph_launch(hipStream_t stream, const void* src, void* dst, uint32_t width, uint32_t height, uint32_t x, uint32_t y, uint32_t rect_w,
-                    uint32_t rect_h, int dilate, int clamp, int straight, uint32_t radius_x, uint32_t radius_y, void* tmp, int num_cus);
-int jh_warp_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, void* dst,
-                   uint32_t dst_w, uint32_t dst_h, uint32_t dx, uint32_t dy, uint32_t dw, uint32_t dh, const int64_t* plan, int filter, int edge,
-                   int straight, int num_cus);
+int jh_color_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect rect, const float* matrix, int clamp, const float* pre,
+                    const uint16_t* const* post, int num_cus);
+int jh_morph_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect rect, int dilate, int clamp, int straight, uint32_t radius_x,
+                    uint32_t radius_y, void* tmp, int num_cus);
+int jh_warp_launch(hipStream_t stream, jimage_src src, jimage_rect src_rect, jimage_dst dst, jimage_rect dst_rect, const int64_t* plan, int filter,
+                   int edge, int straight, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

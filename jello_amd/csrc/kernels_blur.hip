@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "../../include/jello_blur.h"
 #include "kcommon.h"
 #include "texel_io.h"
 
@@ -179,19 +180,17 @@ __global__ __launch_bounds__(kBlurThreads) void k_blur_cols(const float4* __rest
 
 }  // namespace
 
-// The rectangle (x, y, rect_w, rect_h) of the width x height RGBA16F image at dst = the blur of the image at src (null: transparent
-// black; may be dst).  taps_x / taps_y: 2 R + 1 weights each (jblur_taps), read during the call.  tmp: device memory for
-// (rows of the image within radius_y of the rectangle's) x rect_w float4.  clamp: JH_BLUR_EDGE_CLAMP.  Two launches on `stream`.
-// Returns 0, -1 on arguments it refuses, -2 on a launch error.
-extern "C" int jh_blur_launch(hipStream_t stream, const void* src, void* dst, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
-                              uint32_t rect_w, uint32_t rect_h, int clamp, const float* taps_x, uint32_t radius_x, const float* taps_y,
-                              uint32_t radius_y, void* tmp, int num_cus) {
-    if (!dst || !tmp || !taps_x || !taps_y || radius_x > kMaxRadius || radius_y > kMaxRadius) return -1;
-    if (!rect_inside(x, y, rect_w, rect_h, width, height)) return -1;
-    if (rect_w == 0u || rect_h == 0u) return 0;
-    const RowWindow rows = row_window(y, rect_h, radius_y, height);
-    const uint32_t segs = (rect_w + kRowSeg - 1u) / kRowSeg, strips = (rect_w + kColStrip - 1u) / kColStrip;
-    const uint64_t items_h = (uint64_t)rows.n_rows * segs, items_v = (uint64_t)((rect_h + kColRows - 1u) / kColRows) * strips;
+// The rectangle r of the RGBA16F image dst = the blur of the image src of the same size (null texels: transparent black; may be
+// dst).  taps_x / taps_y: 2 R + 1 weights each (jblur_taps), read during the call.  tmp: device memory of jblur_scratch_bytes(r,
+// radius_y, height), the rows jblur_scratch_rows names.  clamp: JH_BLUR_EDGE_CLAMP.  Two launches on `stream`.
+extern "C" int jh_blur_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect r, int clamp, const float* taps_x, uint32_t radius_x,
+                              const float* taps_y, uint32_t radius_y, void* tmp, int num_cus) {
+    if (!dst.texels || !tmp || !taps_x || !taps_y || radius_x > kMaxRadius || radius_y > kMaxRadius) return -1;
+    if (src.width != dst.width || src.height != dst.height || !jimage_rect_inside(r, dst.width, dst.height)) return -1;
+    if (jimage_rect_empty(r)) return 0;
+    const jimage_rows rows = jblur_scratch_rows(r, radius_y, dst.height);
+    const uint32_t segs = (r.w + kRowSeg - 1u) / kRowSeg, strips = (r.w + kColStrip - 1u) / kColStrip;
+    const uint64_t items_h = (uint64_t)rows.n_rows * segs, items_v = (uint64_t)((r.h + kColRows - 1u) / kColRows) * strips;
     if (items_h > 0x7fffffffull || items_v > 0x7fffffffull) return -1;
     BlurTaps tx, ty;
     memset(&tx, 0, sizeof tx);
@@ -203,9 +202,9 @@ extern "C" int jh_blur_launch(hipStream_t stream, const void* src, void* dst, ui
     const dim3 block(kBlurThreads), grid_h(grid_blocks(items_h, kBlurWaves, 8u, num_cus)), grid_v(grid_blocks(items_v, kBlurWaves, 8u, num_cus));
     with_flag(clamp != 0, [&](auto edge) {
         constexpr bool CLAMP = decltype(edge)::value;
-        hipLaunchKernelGGL(k_blur_rows<CLAMP>, grid_h, block, lds, stream, (const uint2*)src, (float4*)tmp, width, x, rect_w, rows.row0, radius_x, segs, region,
+        hipLaunchKernelGGL(k_blur_rows<CLAMP>, grid_h, block, lds, stream, (const uint2*)src.texels, (float4*)tmp, dst.width, r.x, r.w, rows.row0, radius_x, segs, region,
                            (uint32_t)items_h, tx);
-        hipLaunchKernelGGL(k_blur_cols<CLAMP>, grid_v, block, 0, stream, (const float4*)tmp, (uint2*)dst, width, height, x, y, rect_w, rect_h, rows.row0, radius_y,
+        hipLaunchKernelGGL(k_blur_cols<CLAMP>, grid_v, block, 0, stream, (const float4*)tmp, (uint2*)dst.texels, dst.width, dst.height, r.x, r.y, r.w, r.h, rows.row0, radius_y,
                            strips, (uint32_t)items_v, ty);
     });
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -66,17 +66,16 @@ __global__ __launch_bounds__(kColorThreads) void k_color(const uint2* src, uint3
 
 }  // namespace
 
-// The rule on the rect_w x rect_h texels at (x, y) of the src_w x src_h RGBA16F image at src (null: transparent black; may be dst),
-// written to the same rectangle of the dst_w x dst_h image at dst.  matrix: 20 floats, row-major 4 x 5; clamp: JH_COLOR_CLAMP's bit;
+// The rule on the rectangle r of the RGBA16F image src (null texels: transparent black; may be dst), written to the same rectangle
+// of the image dst.  matrix: 20 floats, row-major 4 x 5; clamp: JH_COLOR_CLAMP's bit;
 // pre: the three PRE tables of 65 536 floats one after the other, or null; post[i]: POST_i, 65 536 entries, or null.  One launch on
 // `stream`, none for an empty rectangle.  Returns 0, -1 on arguments it refuses, -2 on a launch error.
-extern "C" int jh_color_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h,
-                               uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h, const float* matrix, int clamp, const float* pre,
+extern "C" int jh_color_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect r, const float* matrix, int clamp, const float* pre,
                                const uint16_t* const* post, int num_cus) {
-    if (!dst || !matrix || !post) return -1;
-    if (!rect_inside(x, y, rect_w, rect_h, src_w, src_h) || !rect_inside(x, y, rect_w, rect_h, dst_w, dst_h)) return -1;
-    if (rect_w == 0u || rect_h == 0u) return 0;
-    const uint64_t segs = walk_segs(rect_w, kColorThreads), total = segs * rect_h;
+    if (!dst.texels || !matrix || !post) return -1;
+    if (!jimage_rect_inside(r, src.width, src.height) || !jimage_rect_inside(r, dst.width, dst.height)) return -1;
+    if (jimage_rect_empty(r)) return 0;
+    const uint64_t segs = walk_segs(r.w, kColorThreads), total = segs * r.h;
     if (total > 0x7fffffffull) return -1;
     ColorParams p;
     for (int i = 0; i < 20; i++) p.m[i] = matrix[i];
@@ -89,7 +88,7 @@ extern "C" int jh_color_launch(hipStream_t stream, const void* src, uint32_t src
     }
     const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kColorThreads);
     with_flag(tables, [&](auto tab) {
-        hipLaunchKernelGGL(k_color<decltype(tab)::value>, grid, block, 0, stream, (const uint2*)src, src_w, (uint2*)dst, dst_w, x, y, rect_w, (uint32_t)segs,
+        hipLaunchKernelGGL(k_color<decltype(tab)::value>, grid, block, 0, stream, (const uint2*)src.texels, src.width, (uint2*)dst.texels, dst.width, r.x, r.y, r.w, (uint32_t)segs,
                            (uint32_t)total, p);
     });
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -58,16 +58,15 @@ __global__ __launch_bounds__(kCompThreads) void k_composite(const uint2* __restr
 
 }  // namespace
 
-// The rectangle `rect` (jcomp_clip's result for these two images) of the src_w x src_h RGBA16F image at src (null: transparent
-// black) blended onto the dst_w x dst_h image at dst; dst_has_content = 0: dst's memory is not read, the backdrop is transparent
+// The rectangle `rect` (jcomp_clip's result for these two images) of the RGBA16F image src (null texels: transparent black) blended
+// onto the image dst; dst_has_content = 0: dst's memory is not read, the backdrop is transparent
 // black.  mode = mix << 8 | compose (mix 0..15, compose 0..13); flags bit 0: the tint (four floats) is applied.  One launch on
 // `stream`, none for an empty rectangle.  Returns 0, -1 on arguments it refuses, -2 on a launch error.
-extern "C" int jh_composite_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, void* dst, uint32_t dst_w, uint32_t dst_h,
-                                   int dst_has_content, const jcomp_rect* rect, uint32_t mode, uint32_t flags, float opacity, const float* tint,
-                                   int num_cus) {
-    if (!dst || !rect || !tint || (mode >> 8) > 15u || (mode & 0xffu) > 13u || (flags & ~1u) != 0u) return -1;
+extern "C" int jh_composite_launch(hipStream_t stream, jimage_src src, jimage_dst dst, int dst_has_content, const jcomp_rect* rect, uint32_t mode,
+                                   uint32_t flags, float opacity, const float* tint, int num_cus) {
+    if (!dst.texels || !rect || !tint || (mode >> 8) > 15u || (mode & 0xffu) > 13u || (flags & ~1u) != 0u) return -1;
     const jcomp_rect r = *rect;
-    if (!rect_inside(r.sx, r.sy, r.w, r.h, src_w, src_h) || !rect_inside(r.dx, r.dy, r.w, r.h, dst_w, dst_h)) return -1;
+    if (!jimage_rect_inside({r.sx, r.sy, r.w, r.h}, src.width, src.height) || !jimage_rect_inside({r.dx, r.dy, r.w, r.h}, dst.width, dst.height)) return -1;
     if (r.w == 0u || r.h == 0u) return 0;
     const uint64_t segs = walk_segs(r.w, kCompThreads), total = segs * r.h;
     if (total > 0x7fffffffull) return -1;
@@ -78,7 +77,7 @@ extern "C" int jh_composite_launch(hipStream_t stream, const void* src, uint32_t
     for (int i = 0; i < 4; i++) p.tint[i] = tint[i];
     const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kCompThreads);
     with_flag(mode == 0u, [&](auto fast) {
-        hipLaunchKernelGGL(k_composite<decltype(fast)::value>, grid, block, 0, stream, (const uint2*)src, src_w, (uint2*)dst, dst_w, dst_has_content ? 1u : 0u, r,
+        hipLaunchKernelGGL(k_composite<decltype(fast)::value>, grid, block, 0, stream, (const uint2*)src.texels, src.width, (uint2*)dst.texels, dst.width, dst_has_content ? 1u : 0u, r,
                            (uint32_t)segs, (uint32_t)total, p);
     });
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -225,46 +225,45 @@ __global__ __launch_bounds__(kColThreads) void k_morph_final(const int4* __restr
 
 }  // namespace
 
-// The rectangle (x, y, rect_w, rect_h) of the width x height RGBA16F image at dst = the erosion (dilate = 0) or dilation of the image
-// at src (null: transparent black; may be dst) by the box of radius_x, radius_y (each <= JMORPH_MAX_RADIUS).  clamp:
-// JH_MORPH_EDGE_CLAMP; straight: JH_MORPH_STRAIGHT.  tmp: device memory of jmorph_scratch_bytes(rect_w, rect_h, radius_y), the planes
-// H and P.  Three launches on `stream`.  Returns 0, -1 on arguments it refuses, -2 on a launch error.
-extern "C" int jh_morph_launch(hipStream_t stream, const void* src, void* dst, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
-                               uint32_t rect_w, uint32_t rect_h, int dilate, int clamp, int straight, uint32_t radius_x, uint32_t radius_y, void* tmp,
-                               int num_cus) {
-    if (!dst || !tmp || radius_x > JMORPH_MAX_RADIUS || radius_y > JMORPH_MAX_RADIUS) return -1;
-    if (!rect_inside(x, y, rect_w, rect_h, width, height)) return -1;
-    if (rect_w == 0u || rect_h == 0u) return 0;
-    const RowWindow rows = row_window(y, rect_h, radius_y, height);
-    const uint64_t nv = jmorph_plane_rows(rect_h, radius_y);
+// The rectangle r of the RGBA16F image dst = the erosion (dilate = 0) or dilation of the image src of the same size (null texels:
+// transparent black; may be dst) by the box of radius_x, radius_y (each <= JMORPH_MAX_RADIUS).  clamp: JH_MORPH_EDGE_CLAMP; straight:
+// JH_MORPH_STRAIGHT.  tmp: device memory of jmorph_scratch_bytes(r.w, r.h, radius_y), the planes H and P.  Three launches on
+// `stream`.  Returns 0, -1 on arguments it refuses, -2 on a launch error.
+extern "C" int jh_morph_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect r, int dilate, int clamp, int straight,
+                               uint32_t radius_x, uint32_t radius_y, void* tmp, int num_cus) {
+    if (!dst.texels || !tmp || radius_x > JMORPH_MAX_RADIUS || radius_y > JMORPH_MAX_RADIUS) return -1;
+    if (src.width != dst.width || src.height != dst.height || !jimage_rect_inside(r, dst.width, dst.height)) return -1;
+    if (jimage_rect_empty(r)) return 0;
+    const jimage_rows rows = jimage_row_window(r.y, r.h, radius_y, dst.height);
+    const uint64_t nv = jmorph_plane_rows(r.h, radius_y);
     if (nv > 0x7fffffffull) return -1;
     MorphPlanes m;
-    m.rw = rect_w;
+    m.rw = r.w;
     m.nv = (uint32_t)nv;
-    m.vlo = rows.row0 + radius_y - y;  // the plane row of image row rows.row0
+    m.vlo = rows.row0 + radius_y - r.y;  // the plane row of image row rows.row0
     m.vhi = m.vlo + rows.n_rows;
     m.L = 2u * radius_y + 1u;
     m.group = m.L >= kItemRows ? 1u : (kItemRows + m.L - 1u) / m.L;
-    m.strips = (rect_w + kColStrip - 1u) / kColStrip;
+    m.strips = (r.w + kColStrip - 1u) / kColStrip;
     m.pad = jmorph_pad(dilate, clamp);
-    const uint64_t blocks_all = (nv + m.L - 1u) / m.L, blocks_out = ((uint64_t)rect_h + m.L - 1u) / m.L;
-    const uint64_t items_rows = (uint64_t)rows.n_rows * ((rect_w + kRowSeg - 1u) / kRowSeg);
+    const uint64_t blocks_all = (nv + m.L - 1u) / m.L, blocks_out = ((uint64_t)r.h + m.L - 1u) / m.L;
+    const uint64_t items_rows = (uint64_t)rows.n_rows * ((r.w + kRowSeg - 1u) / kRowSeg);
     const uint64_t items_prefix = ((blocks_all + m.group - 1u) / m.group) * m.strips, items_final = ((blocks_out + m.group - 1u) / m.group) * m.strips;
     if (items_rows > 0x7fffffffull || items_prefix > 0x7fffffffull || items_final > 0x7fffffffull) return -1;
     int4* hp = (int4*)tmp;
-    int4* pp = (int4*)((char*)tmp + jmorph_plane_bytes(rect_w, rect_h, radius_y));
-    const uint32_t segs = (rect_w + kRowSeg - 1u) / kRowSeg, region = kRowSeg + 2u * radius_x;
+    int4* pp = (int4*)((char*)tmp + jmorph_plane_bytes(r.w, r.h, radius_y));
+    const uint32_t segs = (r.w + kRowSeg - 1u) / kRowSeg, region = kRowSeg + 2u * radius_x;
     const size_t lds = (size_t)kMorphWaves * region * sizeof(int4);
     const dim3 grid_rows(grid_blocks(items_rows, kMorphWaves, 8u, num_cus)), grid_prefix(grid_blocks(items_prefix, 1u, 32u, num_cus)),
         grid_final(grid_blocks(items_final, 1u, 32u, num_cus));
     with_flag(dilate != 0, [&](auto op) {
         with_flag(straight != 0, [&](auto flag) {
             constexpr bool DILATE = decltype(op)::value, STRAIGHT = decltype(flag)::value;
-            hipLaunchKernelGGL((k_morph_rows<DILATE, STRAIGHT>), grid_rows, dim3(kMorphThreads), lds, stream, (const uint2*)src, hp, width, x, rect_w, rows.row0, m.vlo,
+            hipLaunchKernelGGL((k_morph_rows<DILATE, STRAIGHT>), grid_rows, dim3(kMorphThreads), lds, stream, (const uint2*)src.texels, hp, dst.width, r.x, r.w, rows.row0, m.vlo,
                                radius_x, segs, region, (uint32_t)items_rows, m.pad);
             hipLaunchKernelGGL((k_morph_prefix<DILATE>), grid_prefix, dim3(kColThreads), 0, stream, (const int4*)hp, pp, m, (uint32_t)items_prefix);
-            hipLaunchKernelGGL((k_morph_final<DILATE, STRAIGHT>), grid_final, dim3(kColThreads), 0, stream, (const int4*)hp, (const int4*)pp, (uint2*)dst, width, x, y,
-                               rect_h, (uint32_t)blocks_out, m, (uint32_t)items_final);
+            hipLaunchKernelGGL((k_morph_final<DILATE, STRAIGHT>), grid_final, dim3(kColThreads), 0, stream, (const int4*)hp, (const int4*)pp, (uint2*)dst.texels, dst.width, r.x, r.y,
+                               r.h, (uint32_t)blocks_out, m, (uint32_t)items_final);
         });
     });
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -163,30 +163,29 @@ __global__ __launch_bounds__(kColThreads) void k_resample_cols(const float4* __r
 
 }  // namespace
 
-// The rectangle (dx, dy, dw, dh) of the dst_w x dst_h RGBA16F image at dst = the rectangle (sx, sy, sw, sh) of the src_w x src_h
-// image at src (null: transparent black; another image than dst) resized by the tables of this geometry, which are device memory
-// (the struct itself is read during the call).  tmp: device memory for sh x dw float4.  Two launches on `stream`.
-// Returns 0, -1 on arguments it refuses, -2 on a launch error.
-extern "C" int jh_resample_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw,
-                                  uint32_t sh, void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t dx, uint32_t dy, uint32_t dw, uint32_t dh,
-                                  int straight, const JhResampleTables* tables, void* tmp, int num_cus) {
-    if (!dst || !tmp || !tables || src == dst) return -1;
+// The rectangle d of the RGBA16F image dst = the rectangle s of the image src (null texels: transparent black; another image than
+// dst) resized by the tables of this geometry, which are device memory (the struct itself is read during the call).  tmp: device
+// memory of jresample_scratch_bytes(s, d), the rows jresample_scratch_rows names.  Two launches on `stream`.
+extern "C" int jh_resample_launch(hipStream_t stream, jimage_src src, jimage_rect s, jimage_dst dst, jimage_rect d, int straight,
+                                  const JhResampleTables* tables, void* tmp, int num_cus) {
+    if (!dst.texels || !tmp || !tables || src.texels == dst.texels) return -1;
     const JhResampleTables t = *tables;
     if (!t.win_x || !t.seg_x || !t.w_x || !t.win_y || !t.w_y) return -1;
-    if (!rect_inside(sx, sy, sw, sh, src_w, src_h) || !rect_inside(dx, dy, dw, dh, dst_w, dst_h)) return -1;
-    if (sw == 0u || sh == 0u || dw == 0u || dh == 0u) return -1;
+    if (!jimage_rect_inside(s, src.width, src.height) || !jimage_rect_inside(d, dst.width, dst.height)) return -1;
+    if (jimage_rect_empty(s) || jimage_rect_empty(d)) return -1;
+    const uint32_t dw = d.w, dh = d.h;
     if (t.taps_x == 0u || t.taps_x > JRESAMPLE_MAX_TAPS || t.stride_y == 0u || t.stride_y > JRESAMPLE_MAX_TAPS || t.region_x == 0u || t.region_x > kMaxRegion)
         return -1;
     const uint32_t segs = (dw + JH_RESAMPLE_ROW_SEG - 1u) / JH_RESAMPLE_ROW_SEG, strips = (dw + kColStrip - 1u) / kColStrip;
-    const uint64_t items_h = (uint64_t)sh * segs, items_v = (uint64_t)((dh + kColRows - 1u) / kColRows) * strips;
+    const uint64_t items_h = (uint64_t)jresample_scratch_rows(s) * segs, items_v = (uint64_t)((dh + kColRows - 1u) / kColRows) * strips;
     if (items_h > 0x7fffffffull || items_v > 0x7fffffffull) return -1;
     const size_t lds = (size_t)kRowWaves * t.region_x * sizeof(float4);
     const dim3 grid_h(grid_blocks(items_h, kRowWaves, 8u, num_cus)), grid_v(grid_blocks(items_v, kColWaves, 8u, num_cus));
     with_flag(straight != 0, [&](auto flag) {
         constexpr bool STRAIGHT = decltype(flag)::value;
-        hipLaunchKernelGGL(k_resample_rows<STRAIGHT>, grid_h, dim3(kRowThreads), lds, stream, (const uint2*)src, (float4*)tmp, src_w, sx, sy, dw, segs, t.region_x,
+        hipLaunchKernelGGL(k_resample_rows<STRAIGHT>, grid_h, dim3(kRowThreads), lds, stream, (const uint2*)src.texels, (float4*)tmp, src.width, s.x, s.y, dw, segs, t.region_x,
                            (uint32_t)items_h, t.win_x, t.seg_x, t.w_x);
-        hipLaunchKernelGGL(k_resample_cols<STRAIGHT>, grid_v, dim3(kColThreads), 0, stream, (const float4*)tmp, (uint2*)dst, dst_w, dx, dy, dw, dh, strips,
+        hipLaunchKernelGGL(k_resample_cols<STRAIGHT>, grid_v, dim3(kColThreads), 0, stream, (const float4*)tmp, (uint2*)dst.texels, dst.width, d.x, d.y, dw, dh, strips,
                            (uint32_t)items_v, t.win_y, t.w_y, t.stride_y);
     });
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -142,30 +142,29 @@ void launch_filter(hipStream_t stream, dim3 grid, int edge, bool straight, const
 
 }  // namespace
 
-// The rectangle (dx, dy, dw, dh) of the dst_w x dst_h RGBA16F image at dst = the rectangle (sx, sy, sw, sh) of the src_w x src_h
-// image at src (null: transparent black; another image than dst) under the plan (P, Q, R, S, T, W of include/jello_warp.h, host
+// The rectangle d of the RGBA16F image dst = the rectangle s of the image src (null texels: transparent black; another image than
+// dst) under the plan (P, Q, R, S, T, W of include/jello_warp.h, host
 // memory, read during the call).  One launch on `stream`: one of the 24 instantiations of k_warp, filter x edge x straight.
 // Returns 0, -1 on arguments it refuses (a plan outside a legal one's range among them: the kernel's indices are 32-bit), -2 on a
 // launch error.
-extern "C" int jh_warp_launch(hipStream_t stream, const void* src, uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh,
-                              void* dst, uint32_t dst_w, uint32_t dst_h, uint32_t dx, uint32_t dy, uint32_t dw, uint32_t dh, const int64_t* plan,
-                              int filter, int edge, int straight, int num_cus) {
-    if (!dst || !plan || src == dst || !jwarp_filter_ok(filter) || !jwarp_edge_ok(edge)) return -1;
-    if (src_w > JWARP_MAX_SIDE || src_h > JWARP_MAX_SIDE || dst_w > JWARP_MAX_SIDE || dst_h > JWARP_MAX_SIDE) return -1;
-    if (!rect_inside(sx, sy, sw, sh, src_w, src_h) || !rect_inside(dx, dy, dw, dh, dst_w, dst_h)) return -1;
-    if (sw == 0u || sh == 0u || dw == 0u || dh == 0u) return -1;
+extern "C" int jh_warp_launch(hipStream_t stream, jimage_src src, jimage_rect s, jimage_dst dst, jimage_rect d, const int64_t* plan, int filter,
+                              int edge, int straight, int num_cus) {
+    if (!dst.texels || !plan || src.texels == dst.texels || !jwarp_filter_ok(filter) || !jwarp_edge_ok(edge)) return -1;
+    if (src.width > JWARP_MAX_SIDE || src.height > JWARP_MAX_SIDE || dst.width > JWARP_MAX_SIDE || dst.height > JWARP_MAX_SIDE) return -1;
+    if (!jimage_rect_inside(s, src.width, src.height) || !jimage_rect_inside(d, dst.width, dst.height)) return -1;
+    if (jimage_rect_empty(s) || jimage_rect_empty(d)) return -1;
     for (int i = 0; i < 6; i++) {
         const int64_t lim = (i % 3) == 2 ? kMaxOffset : kMaxScale;
         if (plan[i] > lim || plan[i] < -lim) return -1;
     }
     WarpArgs a;
-    a.src = src ? (const uint2*)src + ((uint64_t)sy * src_w + sx) : nullptr;
-    a.dst = (uint2*)dst;
+    a.src = src.texels ? (const uint2*)src.texels + ((uint64_t)s.y * src.width + s.x) : nullptr;
+    a.dst = (uint2*)dst.texels;
     a.P = plan[0]; a.Q = plan[1]; a.R = plan[2]; a.S = plan[3]; a.T = plan[4]; a.W = plan[5];
-    a.src_w = src_w; a.sw = sw; a.sh = sh;
-    a.dst_w = dst_w; a.dx = dx; a.dy = dy; a.dw = dw; a.dh = dh;
-    a.tiles_x = (dw + 2u * (kTile - 1u)) / kTile;  // (+ 15: the grid of lines may start up to 15 texels before the row)
-    a.total = a.tiles_x * ((dh + kTile - 1u) / kTile);
+    a.src_w = src.width; a.sw = s.w; a.sh = s.h;
+    a.dst_w = dst.width; a.dx = d.x; a.dy = d.y; a.dw = d.w; a.dh = d.h;
+    a.tiles_x = (d.w + 2u * (kTile - 1u)) / kTile;  // (+ 15: the grid of lines may start up to 15 texels before the row)
+    a.total = a.tiles_x * ((d.h + kTile - 1u) / kTile);
     const dim3 grid(grid_blocks((uint64_t)a.total * kWaves, kWaves, 8u, num_cus));
     switch (filter) {
         case JWARP_NEAREST: launch_filter<JWARP_NEAREST>(stream, grid, edge, straight != 0, a); break;

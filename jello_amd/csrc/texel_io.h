@@ -1,5 +1,5 @@
 // texel_io.h -- what the image kernels share besides their rules: how an RGBA16F texel is widened and stored, the streaming pair
-// walk (kernels_composite.hip, kernels_color.hip), the grid rule and the launchers' preamble.  Tap loops, edge rules, LDS layouts and
+// walk (kernels_composite.hip, kernels_color.hip) and the grid rule.  Tap loops, edge rules, LDS layouts and
 // launch bounds stay in the kernel files.  Every function is internal to the file that includes it.
 // The helpers' signatures are part of the generated code, and three loops stay written out for that reason ("What is
 // shared"): the kernels' own __restrict__ parameters carry through the inlining, so the walk's pointer parameters have none (on src it
@@ -100,25 +100,13 @@ JD void pair_walk(const uint2* src, uint32_t src_w, uint32_t sx, uint32_t sy, ui
 }
 inline uint64_t walk_segs(uint32_t w, uint32_t threads) { return ((uint64_t)w + 1u + 2u * threads - 1u) / (2u * threads); }  // (+ 1: the pair grid may start one texel before the row)
 
-// ---- host side: the grid rule and the launchers' preamble ----
+// ---- host side: the grid rule (the rectangles, the views and the row window the launchers take: include/jello_image.h, through kcommon.h) ----
 
 // Workgroups to launch for `items` wave items, `waves` of them to a workgroup: at most per_cu workgroups per CU (256 CUs when the
 // count is unknown), the rest by grid stride.
 inline uint32_t grid_blocks(uint64_t items, uint32_t waves, uint32_t per_cu, int num_cus) {
     const uint64_t blocks = (items + waves - 1u) / waves, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * per_cu;
     return (uint32_t)(blocks < cap ? blocks : cap);
-}
-
-inline bool rect_inside(uint32_t x, uint32_t y, uint32_t w, uint32_t h, uint32_t img_w, uint32_t img_h) {
-    return (uint64_t)x + w <= img_w && (uint64_t)y + h <= img_h;
-}
-
-// The rows of an image of `height` rows within radius_y of the rows [y, y + rect_h): what a row pass prepares for its column pass.
-struct RowWindow { uint32_t row0, n_rows; };
-inline RowWindow row_window(uint32_t y, uint32_t rect_h, uint32_t radius_y, uint32_t height) {
-    const uint32_t row0 = y > radius_y ? y - radius_y : 0u;
-    const uint64_t row1 = (uint64_t)y + rect_h + radius_y < height ? (uint64_t)y + rect_h + radius_y : height;
-    return {row0, (uint32_t)(row1 - row0)};
 }
 
 // f(std::true_type) or f(std::false_type): a generic lambda launches the instantiation of a run-time flag, written once.

@@ -82,21 +82,24 @@ def blur_taps(sigma):
     return w, r.value
 
 
+def _rect(rect):  # (x, y, width, height) as a descriptor takes it: four ints, 0 x 0 -- the whole image -- for None
+    x, y, w, h = (0, 0, 0, 0) if rect is None else rect
+    return int(x), int(y), int(w), int(h)
+
+
 def _blur_desc(sigma, edge, rect):
     sx, sy = sigma if isinstance(sigma, (tuple, list)) else (sigma, sigma)
-    x, y, w, h = (0, 0, 0, 0) if rect is None else rect
-    return CBlurDesc(float(sx), float(sy), int(edge), int(x), int(y), int(w), int(h))
+    return CBlurDesc(float(sx), float(sy), int(edge), *_rect(rect))
 
 
 COMPOSITE_TINT = 1  # JH_COMPOSITE_TINT
 
 
 def _composite_desc(mix, compose, opacity, tint, src_rect, offset):
-    sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
     d = CCompositeDesc(int(mix), int(compose), float(opacity), 0 if tint is None else COMPOSITE_TINT)
     if tint is not None:
         d.tint[:] = [float(v) for v in tint]
-    d.sx, d.sy, d.sw, d.sh = int(sx), int(sy), int(sw), int(sh)
+    d.sx, d.sy, d.sw, d.sh = _rect(src_rect)
     d.dx, d.dy = int(offset[0]), int(offset[1])
     return d
 
@@ -129,9 +132,7 @@ def resample_taps(filter, n_in, n_out):
 
 
 def _resample_desc(filter, src_rect, dst_rect, premultiplied):
-    sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
-    dx, dy, dw, dh = (0, 0, 0, 0) if dst_rect is None else dst_rect
-    return CResampleDesc(int(filter), 0 if premultiplied else RESAMPLE_STRAIGHT, int(sx), int(sy), int(sw), int(sh), int(dx), int(dy), int(dw), int(dh))
+    return CResampleDesc(int(filter), 0 if premultiplied else RESAMPLE_STRAIGHT, *_rect(src_rect), *_rect(dst_rect))
 
 
 class MorphOp(enum.IntEnum):
@@ -152,10 +153,9 @@ MORPH_MAX_RADIUS = 255  # JH_MORPH_MAX_RADIUS
 
 def _morph_desc(op, radius, edge, rect, premultiplied):
     rx, ry = radius if isinstance(radius, (tuple, list)) else (radius, radius)
-    x, y, w, h = (0, 0, 0, 0) if rect is None else rect
     if not (0 <= int(rx) <= MORPH_MAX_RADIUS and 0 <= int(ry) <= MORPH_MAX_RADIUS):
         raise ValueError("jh_morphology: a radius above 255 or below 0")
-    return CMorphDesc(int(op), int(edge), 0 if premultiplied else MORPH_STRAIGHT, int(rx), int(ry), int(x), int(y), int(w), int(h))
+    return CMorphDesc(int(op), int(edge), 0 if premultiplied else MORPH_STRAIGHT, int(rx), int(ry), *_rect(rect))
 
 
 class WarpFilter(enum.IntEnum):
@@ -212,8 +212,8 @@ def _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
     d = CWarpDesc()
     d.matrix[:] = list(_matrix6(matrix))
     d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else WARP_STRAIGHT
-    d.src_x, d.src_y, d.src_width, d.src_height = (0, 0, 0, 0) if src_rect is None else [int(v) for v in src_rect]
-    d.dst_x, d.dst_y, d.dst_width, d.dst_height = (0, 0, 0, 0) if dst_rect is None else [int(v) for v in dst_rect]
+    d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
+    d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
     return d
 
 
@@ -245,7 +245,7 @@ def _color_desc(matrix, funcs, space, clamp, rect):
     colorfilter.linear / gamma / table / discrete return.  What the rule refuses is left for the call to refuse, except a value
     list that does not fit the struct."""
     d = CColorDesc()
-    d.x, d.y, d.width, d.height = (0, 0, 0, 0) if rect is None else [int(v) for v in rect]
+    d.x, d.y, d.width, d.height = _rect(rect)
     m = np.asarray(IDENTITY_MATRIX if matrix is None else matrix, np.float32).reshape(-1)
     if m.size != 20:
         raise ValueError("color_filter: the matrix has 20 entries (row-major 4 x 5)")
@@ -292,7 +292,7 @@ def composite_clip(src_size, dst_size, src_rect=None, offset=(0, 0)):
     (the geometry of DESIGN.md 5.8): (sx', sy', dx', dy', w, h), all zero when nothing is left.  No GPU needed.  ValueError for a
     source rectangle the rule refuses."""
     L = _lib.load_host()
-    sx, sy, sw, sh = (0, 0, 0, 0) if src_rect is None else src_rect
+    sx, sy, sw, sh = _rect(src_rect)
     out = (ctypes.c_uint32 * 6)()
     if L.jl_composite_clip(src_size[0], src_size[1], sx, sy, sw, sh, offset[0], offset[1], dst_size[0], dst_size[1], out) != 0:
         raise ValueError(L.jl_last_error().decode())

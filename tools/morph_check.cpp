@@ -3,8 +3,8 @@
 //     g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
 //         tools/morph_check.cpp -o /tmp/morph_check && /tmp/morph_check
 //
-// Three things.  (1) jmorph_desc_error over every legal (op, edge, flags, radius_x, radius_y) with a set of rectangles, and over a set
-// of illegal descriptors.  (2) The order key against a direct comparison of the values -- every f16 bit pattern widened to binary32,
+// Three things.  (1) jmorph_desc_error over every legal (op, edge, flags, radius_x, radius_y), with the sizes of the intermediate for a
+// set of rectangles, and over a set of illegal descriptors (the rectangles' own check: tools/image_rect_check.cpp).  (2) The order key against a direct comparison of the values -- every f16 bit pattern widened to binary32,
 // and the products of a few thousand pairs of them: sorted by key the values ascend in totalOrder, distinct values have distinct
 // keys, the inverse gives the value back, a NaN of either sign maps to the operator's extreme and nothing maps to the neutral key.
 // (3) The decomposition kernels_morph.hip uses -- rows by doubling in place, columns by block prefix and suffix over planes of
@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "jello_image.h"
 #include "jello_morph.h"
 
 static uint32_t f16_bits_to_f32_bits(uint16_t h) {
@@ -54,8 +55,8 @@ static int check_descriptors() {
                 for (uint32_t rx = 0; rx <= JMORPH_MAX_RADIUS; rx++)
                     for (uint32_t ry = 0; ry <= JMORPH_MAX_RADIUS; ry++)
                         for (const auto& r : rects) {
-                            if (jmorph_desc_error(op, edge, flags, rx, ry, r[0], r[1], r[2], r[3], W, H)) return 1;
-                            const jmorph_rect q = jmorph_resolve(r[0], r[1], r[2], r[3], W, H);
+                            if (jmorph_desc_error(op, edge, flags, rx, ry) || jimage_rect_check({r[0], r[1], r[2], r[3]}, W, H) != JIMAGE_RECT_OK) return 1;
+                            const jimage_rect q = jimage_resolve({r[0], r[1], r[2], r[3]}, W, H);
                             if (q.w == 0u || q.h == 0u || q.x + q.w > W || q.y + q.h > H) return 2;
                             if (jmorph_plane_rows(q.h, ry) != q.h + 2u * ry || jmorph_scratch_bytes(q.w, q.h, ry) != 32ull * q.w * (q.h + 2u * ry)) return 3;
                         }
@@ -67,8 +68,8 @@ static int check_descriptors() {
         {1, 0, 0, 1, 1, 0, 9, 4, H - 8}, {1, 0, 0, 1, 1, 0xffffffffu, 0, 2, 2}, {1, 0, 0, 1, 1, 0, 0xffffffffu, 2, 2}, {1, 0, 0, 1, 1, 0, 0, W + 1, H},
     };
     for (const Bad& b : bad)
-        if (!jmorph_desc_error(b.op, b.edge, b.flags, b.rx, b.ry, b.x, b.y, b.w, b.h, W, H)) return 4;
-    if (jmorph_desc_error(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)) return 5;  // an image without texels: its whole is legal
+        if (!jmorph_desc_error(b.op, b.edge, b.flags, b.rx, b.ry) && jimage_rect_check({b.x, b.y, b.w, b.h}, W, H) == JIMAGE_RECT_OK) return 4;
+    if (jmorph_desc_error(0, 0, 0, 0, 0) || jimage_rect_check({0, 0, 0, 0}, 0, 0) != JIMAGE_RECT_OK) return 5;  // an image without texels: its whole is legal
     return 0;
 }
 
