@@ -27,6 +27,7 @@
  *   jh_color_filter                   (no counterpart: colour matrix and transfer functions on an RGBA16F image)
  *   jh_morphology                     (no counterpart: erode / dilate of an RGBA16F image by a box on the device)
  *   jh_warp                           (no counterpart: an affine transform of an RGBA16F image on the device)
+ *   jh_convolve                       (no counterpart: feConvolveMatrix on an RGBA16F image on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -728,6 +729,77 @@ typedef struct jh_warp_desc {
 int jh_warp_plan(const double matrix[6], int64_t plan[6]);
 int jh_warp_bounds(const double matrix[6], uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t rect[4]);
 int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_warp_desc* desc);
+
+/* ---- Convolve: feConvolveMatrix, a small non-separable convolution with arbitrary weights (DESIGN.md 5.13 "Convolve rule") ----
+ * Sharpen, emboss, Sobel and Laplacian edge detection, a box or tent of the caller's choosing, any kernel up to 15 x 15 -- without the
+ * image leaving the device.  The result is defined on values, and every implementation produces these bits (include/jello_convolve.h
+ * states the host half, tests/convolve_ref.py restates all of it).
+ *   arguments   order_x, order_y: integers in [1, JH_CONVOLVE_MAX_ORDER = 15].  target_x < order_x, target_y < order_y.
+ *               weights[JH_CONVOLVE_MAX_TAPS = 225]: binary32, inline in the descriptor, row-major with stride order_x; only the first
+ *               order_x order_y are read.  edge: JH_CONVOLVE_EDGE_ZERO = 0 | _CLAMP = 1 | _REPEAT = 2 | _MIRROR = 3 (jh_warp_edge's
+ *               values: none, duplicate and wrap of the specification, plus mirror).  mode: JH_CONVOLVE_PREMULTIPLIED = 0 |
+ *               JH_CONVOLVE_STRAIGHT = 1 | JH_CONVOLVE_PRESERVE_ALPHA = 2.  bias: binary32.  The rectangle (x, y, width, height) of
+ *               dst is written; width == height == 0 means the whole image (x and y are then ignored).
+ *   legal       every weight that is read and the bias are finite.
+ *   weights     ARE IN THE ORDER THEY ARE APPLIED, a correlation: w[j][i] multiplies the operand at the image position (X - target_x
+ *               + i, Y - target_y + j).  The 180-degree flip and the divisor of feConvolveMatrix are the host's job
+ *               (jh_convolve_weights); the device never divides.
+ *   operand     the f16 texel widened to binary32.  PREMULTIPLIED: colour times alpha (exact; Inf x 0 is a NaN).  STRAIGHT: the four
+ *               channels as stored.  PRESERVE_ALPHA: the three colour channels as stored; the alpha channel is not convolved.
+ *   edge        the IMAGE is the edge, not the rectangle (as for blur and morphology).  A tap index is resolved per axis with exactly
+ *               jwarp_index(edge, i, n) of include/jello_warp.h against the image's extent n: ZERO: outside [0, n) the operand is
+ *               +0.0f in all channels and still takes part in the sum; CLAMP: min(max(i, 0), n - 1); REPEAT: i mod n, non-negative;
+ *               MIRROR: m = i mod 2 n; m if m < n, otherwise 2 n - 1 - m.  A source that was never written reads as transparent black.
+ *   sum         per channel ONE chain in binary32: acc = +0.0f; for j ascending, for i ascending: acc = fmaf(w[j][i], p(i, j), acc).
+ *               A zero weight still multiplies (0 x Inf is a NaN, as in Warp).  No per-row partial sums.
+ *   bias        if bias is +-0 this step does not exist and V = acc.  Otherwise STRAIGHT: V.c = acc.c + bias for all four channels;
+ *               PRESERVE_ALPHA: the same for the three colour channels; PREMULTIPLIED: V.a = acc.a + bias, then V.c = fmaf(bias, V.a,
+ *               acc.c) for colour (Filter Effects' bias ALPHA with the result's alpha).  Each operation is rounded once.
+ *   store       STRAIGHT: f16(V) per channel, round to nearest even.  PREMULTIPLIED: as fine, jh_composite and jh_resample store:
+ *               a_inv = 1.0f / max(V.a, 1e-6f); (f16(V.r a_inv + 0.0f), f16(V.g a_inv + 0.0f), f16(V.b a_inv + 0.0f), f16(V.a +
+ *               0.0f)).  PRESERVE_ALPHA: colour f16(V.c); alpha is the 16 bits of the source texel at (X, Y), copied (+0 for a
+ *               never-written source).
+ *   values      f16 subnormals are values, Inf and NaN follow IEEE, a NaN result is any NaN.  Nothing is clamped: jh_color_filter
+ *               with clamp comes after where [0, 1] is wanted.
+ * So under STRAIGHT the 1 x 1 kernel [1] copies every non-NaN value (a -0 comes out as +0: +0 + (-0)), and a kernel with a single 1
+ * at (i, j) and zeros elsewhere is the integer translation by (i - target_x, j - target_y) of every finite image under ZERO.  A
+ * constant image c under a kernel whose weights sum to 1 exactly stays c under CLAMP, REPEAT and MIRROR only up to the chain's
+ * rounding: |V - c| <= gamma_n |c| sum |w|, gamma_n = n u / (1 - n u), n = order_x order_y, u = 2^-24, before the store's half ULP
+ * -- a bound, not equality (weights whose partial sums are all exact, such as a box of 1/4, do give c).
+ * What the rule does not do: no call in place; no order above 15; zero weights are not skipped; no separable fast path; no
+ * kernelUnitLength.
+ *
+ * jh_convolve_weights: the weights of feConvolveMatrix's kernelMatrix (order_x order_y binary64, row-major) and divisor:
+ * weights[j ox + i] = (float)(kernel_matrix[(oy - 1 - j) ox + (ox - 1 - i)] / d), the quotient in binary64, rounded once to binary32;
+ * d = divisor if it is not 0, otherwise the sum of kernel_matrix in ascending index order in binary64, or 1.0 if that sum is 0.  Host
+ * only, no context.  JH_ERR_INVALID for an order outside [1, 15], a non-finite input or a weight that does not come out finite.
+ *
+ * jh_convolve: the rule applied to src_image_id, written to the rectangle of dst_image_id, another image of the same size (a tile
+ * of a call in place would read what another tile wrote).  Texels of dst outside the rectangle keep their bits; a dst that was never
+ * written is cleared to transparent black first and then counts as written.  Stream-ordered on the context's stream, never waits:
+ * ONE kernel launch, plus a fill when dst has to be cleared.  No scratch and no tables -- the weights travel in the kernel
+ * arguments: the call is always capturable.  With profiling on the call is a query "convolve" with stage = -1 in
+ * jh_profile_collect_tree.  Not in band mode (jh_set_band): the rows a window reads belong to another rank's context.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_convolve: ": a
+ * null desc; an unknown source or destination id; an image that is not RGBA16F; images of different size; src_image_id ==
+ * dst_image_id; an order outside 1..15; a target outside the order; an unknown edge or mode; a weight or a bias that is not finite;
+ * a rectangle that is not inside the image or that is empty in exactly one dimension; a band set with jh_set_band.  An image without
+ * texels returns JH_OK. */
+typedef enum jh_convolve_edge { JH_CONVOLVE_EDGE_ZERO = 0, JH_CONVOLVE_EDGE_CLAMP = 1, JH_CONVOLVE_EDGE_REPEAT = 2, JH_CONVOLVE_EDGE_MIRROR = 3 } jh_convolve_edge;
+typedef enum jh_convolve_mode { JH_CONVOLVE_PREMULTIPLIED = 0, JH_CONVOLVE_STRAIGHT = 1, JH_CONVOLVE_PRESERVE_ALPHA = 2 } jh_convolve_mode;
+#define JH_CONVOLVE_MAX_ORDER 15u
+#define JH_CONVOLVE_MAX_TAPS 225u
+typedef struct jh_convolve_desc {
+    uint32_t order_x, order_y;
+    uint32_t target_x, target_y;
+    int edge;                      /* jh_convolve_edge */
+    int mode;                      /* jh_convolve_mode */
+    float bias;
+    uint32_t x, y, width, height;  /* rectangle of dst that is written; 0 x 0: the whole image */
+    float weights[JH_CONVOLVE_MAX_TAPS];  /* row-major, stride order_x, in the order they are applied */
+} jh_convolve_desc;
+int jh_convolve_weights(uint32_t order_x, uint32_t order_y, const double* kernel_matrix, double divisor, float* weights);
+int jh_convolve(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_convolve_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -707,6 +707,68 @@ func (e *Engine) Warp(src, dst renderer.ImageProxy, desc WarpDesc) {
 	e.check(C.jh_warp(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "warp")
 }
 
+// ConvolveEdge is jh_convolve_edge: what a tap outside the image reads (WarpEdge's values: feConvolveMatrix's edgeMode none,
+// duplicate and wrap, and the image mirrored).
+type ConvolveEdge int32
+
+const (
+	ConvolveEdgeZero   ConvolveEdge = 0
+	ConvolveEdgeClamp  ConvolveEdge = 1
+	ConvolveEdgeRepeat ConvolveEdge = 2
+	ConvolveEdgeMirror ConvolveEdge = 3
+)
+
+// ConvolveMode is jh_convolve_mode: the operand -- colour times alpha, the four channels as stored, or the colour channels as stored
+// with the source's alpha copied (preserveAlpha).
+type ConvolveMode int32
+
+const (
+	ConvolvePremultiplied ConvolveMode = 0
+	ConvolveStraight      ConvolveMode = 1
+	ConvolvePreserveAlpha ConvolveMode = 2
+)
+
+// ConvolveDesc is jh_convolve_desc (include/jello_hip.h "Convolve"): the orders (1..15), the target, the edge mode, the operand mode,
+// the bias, the rectangle of dst that is written (Width == Height == 0: the whole image) and the weights, row-major with stride
+// OrderX, IN THE ORDER THEY ARE APPLIED (ConvolveWeights makes them of feConvolveMatrix's kernelMatrix and divisor).
+type ConvolveDesc struct {
+	OrderX, OrderY, TargetX, TargetY uint32
+	Edge                             ConvolveEdge
+	Mode                             ConvolveMode
+	Bias                             float32
+	X, Y, Width, Height              uint32
+	Weights                          []float32
+}
+
+// ConvolveWeights is jh_convolve_weights: feConvolveMatrix's kernelMatrix (orderX * orderY values, row-major) rotated by 180 degrees
+// and divided by divisor (0: the sum of the matrix, or 1 if that is 0), in binary64, rounded once to binary32.  Host only.
+func ConvolveWeights(orderX, orderY uint32, kernelMatrix []float64, divisor float64) ([]float32, error) {
+	if orderX < 1 || orderX > 15 || orderY < 1 || orderY > 15 || uint32(len(kernelMatrix)) != orderX*orderY {
+		return nil, fmt.Errorf("hip_engine: ConvolveWeights: an order outside 1..15, or a kernelMatrix of another length")
+	}
+	w := make([]float32, orderX*orderY)
+	if C.jh_convolve_weights(C.uint32_t(orderX), C.uint32_t(orderY), (*C.double)(unsafe.Pointer(&kernelMatrix[0])), C.double(divisor), (*C.float)(unsafe.Pointer(&w[0]))) != 0 {
+		return nil, fmt.Errorf("hip_engine: ConvolveWeights: a non-finite input, or a weight that does not come out finite")
+	}
+	return w, nil
+}
+
+// Convolve is jh_convolve: the RGBA16F image src under a small convolution kernel into the RGBA16F image dst (another image of the
+// same size) by the rule of DESIGN.md 5.13 (defined on values: every implementation gives the same bits) -- sharpen, emboss, edge
+// detection, any kernel up to 15 x 15.  Stream-ordered behind the frame, waits for nothing, one kernel launch, no scratch and no
+// tables: always capturable.
+func (e *Engine) Convolve(src, dst renderer.ImageProxy, desc ConvolveDesc) {
+	d := C.jh_convolve_desc{order_x: C.uint32_t(desc.OrderX), order_y: C.uint32_t(desc.OrderY), target_x: C.uint32_t(desc.TargetX),
+		target_y: C.uint32_t(desc.TargetY), edge: C.int(desc.Edge), mode: C.int(desc.Mode), bias: C.float(desc.Bias),
+		x: C.uint32_t(desc.X), y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height)}
+	for i, w := range desc.Weights {
+		if i < len(d.weights) {
+			d.weights[i] = C.float(w)
+		}
+	}
+	e.check(C.jh_convolve(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "convolve")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -179,6 +179,13 @@ class CWarpDesc(ctypes.Structure):
                 ("dst_x", ctypes.c_uint32), ("dst_y", ctypes.c_uint32), ("dst_width", ctypes.c_uint32), ("dst_height", ctypes.c_uint32)]
 
 
+class CConvolveDesc(ctypes.Structure):
+    """jh_convolve_desc (include/jello_hip.h)."""
+    _fields_ = [("order_x", ctypes.c_uint32), ("order_y", ctypes.c_uint32), ("target_x", ctypes.c_uint32), ("target_y", ctypes.c_uint32),
+                ("edge", ctypes.c_int32), ("mode", ctypes.c_int32), ("bias", ctypes.c_float), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("weights", ctypes.c_float * 225)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -251,6 +258,7 @@ def _declare(L):
     L.jl_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
     L.jl_warp_plan.argtypes = [dp, ctypes.POINTER(ctypes.c_int64)]
     L.jl_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
+    L.jl_convolve_weights.argtypes = [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -298,6 +306,8 @@ def _declare(L):
     hip.jh_warp.argtypes = [vp, u64, u64, ctypes.POINTER(CWarpDesc)]
     hip.jh_warp_plan.argtypes = [dp, ctypes.POINTER(ctypes.c_int64)]
     hip.jh_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
+    hip.jh_convolve.argtypes = [vp, u64, u64, ctypes.POINTER(CConvolveDesc)]
+    hip.jh_convolve_weights.argtypes = [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

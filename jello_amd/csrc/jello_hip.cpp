@@ -26,6 +26,7 @@
 #include "../../include/jello_color.h"
 #include "../../include/jello_morph.h"
 #include "../../include/jello_warp.h"
+#include "../../include/jello_convolve.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -1153,7 +1154,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1731,6 +1732,35 @@ int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_
         }
         return launch_status(ctx, "jh_warp",
                              jh_warp_launch(ctx->stream, v.from, s, v.to, d, plan, desc->filter, desc->edge, (desc->flags & JH_WARP_STRAIGHT) != 0u, ctx->num_cus));
+    });
+}
+
+// convolve (include/jello_hip.h "Convolve"; the descriptor and the weights: include/jello_convolve.h; kernels_convolve.hip)
+int jh_convolve_weights(uint32_t order_x, uint32_t order_y, const double* kernel_matrix, double divisor, float* weights) {
+    if (!kernel_matrix || !weights) return JH_ERR_INVALID;
+    return jconv_weights(order_x, order_y, kernel_matrix, divisor, weights) ? JH_ERR_INVALID : JH_OK;
+}
+int jh_convolve(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_convolve_desc* desc) {
+    static_assert(JH_CONVOLVE_EDGE_ZERO == JCONV_EDGE_ZERO && JH_CONVOLVE_EDGE_CLAMP == JCONV_EDGE_CLAMP && JH_CONVOLVE_EDGE_REPEAT == JCONV_EDGE_REPEAT &&
+                      JH_CONVOLVE_EDGE_MIRROR == JCONV_EDGE_MIRROR && JH_CONVOLVE_PREMULTIPLIED == JCONV_PREMULTIPLIED &&
+                      JH_CONVOLVE_STRAIGHT == JCONV_STRAIGHT && JH_CONVOLVE_PRESERVE_ALPHA == JCONV_PRESERVE_ALPHA &&
+                      JH_CONVOLVE_MAX_ORDER == JCONV_MAX_ORDER && JH_CONVOLVE_MAX_TAPS == JCONV_MAX_TAPS &&
+                      (int)JH_CONVOLVE_EDGE_ZERO == (int)JH_WARP_EDGE_ZERO && (int)JH_CONVOLVE_EDGE_MIRROR == (int)JH_WARP_EDGE_MIRROR,
+                  "the C ABI's values are the rule's");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = image_call_images(ctx, "jh_convolve", desc, src_image_id, dst_image_id, "a tile of a convolution in place reads what another tile wrote", "the rows a window reads belong to another rank", &src, &dst)) return rc;
+    if (src->width != dst->width || src->height != dst->height) return fail(ctx, JH_ERR_INVALID, "jh_convolve: the images differ in size");
+    if (const char* why = jconv_desc_error(desc->order_x, desc->order_y, desc->target_x, desc->target_y, desc->edge, desc->mode, desc->weights, desc->bias))
+        return fail(ctx, JH_ERR_INVALID, std::string("jh_convolve: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_convolve", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    return post_render_call(ctx, "convolve", [&] {
+        ImageViews v;
+        if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
+        return launch_status(ctx, "jh_convolve",
+                             jh_convolve_launch(ctx->stream, v.from, v.to, r, desc->order_x, desc->order_y, desc->target_x, desc->target_y, desc->weights,
+                                                desc->edge, desc->mode, desc->bias, ctx->num_cus));
     });
 }
 

@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CWarpDesc, CYuvDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CWarpDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -214,6 +214,68 @@ def _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
     d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else WARP_STRAIGHT
     d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
     d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
+    return d
+
+
+class ConvolveEdge(enum.IntEnum):
+    """jh_convolve_edge: what a tap outside the image reads -- feConvolveMatrix's edgeMode none, duplicate and wrap,
+    and the image mirrored; WarpEdge's values."""
+    ZERO = 0
+    CLAMP = 1
+    REPEAT = 2
+    MIRROR = 3
+
+
+class ConvolveMode(enum.IntEnum):
+    """jh_convolve_mode: the operand of jh_convolve -- colour times alpha (what feConvolveMatrix is defined on), the four channels as
+    stored, or the colour channels as stored with the source's alpha copied (preserveAlpha)."""
+    PREMULTIPLIED = 0
+    STRAIGHT = 1
+    PRESERVE_ALPHA = 2
+
+
+CONVOLVE_MAX_ORDER = 15  # JH_CONVOLVE_MAX_ORDER
+CONVOLVE_MAX_TAPS = 225  # JH_CONVOLVE_MAX_TAPS
+
+
+def _order2(order, what="order"):
+    ox, oy = order if isinstance(order, (tuple, list)) else (order, order)
+    if int(ox) != ox or int(oy) != oy or int(ox) < 0 or int(oy) < 0:
+        raise ValueError("jh_convolve: the %s is a non-negative integer or a pair of them" % what)
+    return int(ox), int(oy)
+
+
+def convolve_weights(order, kernel_matrix, divisor=0.0, twin=False):
+    """jh_convolve_weights (twin: jl_convolve_weights, the host twin): the float32 weights (order_y, order_x) jh_convolve applies for
+    feConvolveMatrix's `kernel_matrix` (order_x * order_y values, row-major) and `divisor` (0: the sum of the matrix, or 1 if that is
+    0) -- flipped by 180 degrees and divided.  `order` is a scalar or (order_x, order_y).  No GPU needed.  ValueError
+    for an order outside 1..15, a non-finite input or a weight that does not come out finite."""
+    L = _lib.load_host()
+    ox, oy = _order2(order)
+    km = [float(v) for v in np.asarray(kernel_matrix, np.float64).ravel()]
+    if not (1 <= ox <= CONVOLVE_MAX_ORDER and 1 <= oy <= CONVOLVE_MAX_ORDER) or len(km) != ox * oy:
+        raise ValueError("jh_convolve: an order outside 1..15, or a kernelMatrix that does not have order_x * order_y entries")
+    w = (ctypes.c_float * (ox * oy))()
+    if (L.jl_convolve_weights if twin else L.hip.jh_convolve_weights)(ox, oy, (ctypes.c_double * len(km))(*km), float(divisor), w) != 0:
+        raise ValueError("jh_convolve: illegal kernelMatrix or divisor (an entry not finite, or a weight that does not come out finite)")
+    return np.array(w, np.float32).reshape(oy, ox)
+
+
+def _convolve_desc(weights, order, target, edge, mode, bias, rect):
+    w = np.asarray(weights, np.float32)
+    if order is None:
+        if w.ndim != 2:
+            raise ValueError("jh_convolve: weights without an order are a two-dimensional array (order_y, order_x)")
+        order = (w.shape[1], w.shape[0])
+    ox, oy = _order2(order)
+    w = w.ravel()
+    if not (1 <= ox <= CONVOLVE_MAX_ORDER and 1 <= oy <= CONVOLVE_MAX_ORDER):
+        raise ValueError("jh_convolve: an order outside 1..15")
+    if w.size != ox * oy:
+        raise ValueError("jh_convolve: %d weights for an order of %d x %d" % (w.size, ox, oy))
+    tx, ty = (ox // 2, oy // 2) if target is None else _order2(target, "target")
+    d = CConvolveDesc(ox, oy, tx, ty, int(edge), int(mode), float(bias), *_rect(rect))
+    d.weights[:ox * oy] = [float(v) for v in w]
     return d
 
 
@@ -631,6 +693,20 @@ class Engine:
         d = _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied)
         self._check(self.hip.jh_warp(self.ctx, src_id, dst_id, ctypes.byref(d)), "warp", invalid=ValueError)
 
+    def convolve(self, src_id, dst_id, weights, order=None, target=None, edge=ConvolveEdge.CLAMP, mode=ConvolveMode.PREMULTIPLIED, bias=0.0, rect=None):
+        """jh_convolve: the RGBA16F image `src_id` under a small convolution kernel (the rule: DESIGN.md 5.13) into the RGBA16F image
+        `dst_id`, another image of the same size.  `weights` are float32 IN THE ORDER THEY ARE APPLIED (a correlation: weights[j][i]
+        multiplies the texel at (X - target_x + i, Y - target_y + j)); `order` is a scalar or (order_x, order_y), each in 1..15 (None:
+        the shape of a two-dimensional `weights`); `target` = (target_x, target_y) (None: the centre, order // 2, the
+        specification's default).  `edge`: what a tap outside the IMAGE reads (ConvolveEdge); `mode`: the operand (ConvolveMode);
+        `bias` is added after the sum (times the result's alpha under PREMULTIPLIED).  `rect` = (x, y, width, height) is the
+        rectangle of the destination that is written (None: the whole image); source texels outside it take part.  Nothing is
+        clamped: color_filter(clamp=True) comes after where [0, 1] is wanted.  jello_amd.convolution has feConvolveMatrix's
+        attributes (from_svg, which flips and divides) and the usual kernels, each the keywords of this call.  One launch, no
+        scratch: always capturable.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _convolve_desc(weights, order, target, edge, mode, bias, rect)
+        self._check(self.hip.jh_convolve(self.ctx, src_id, dst_id, ctypes.byref(d)), "convolve", invalid=ValueError)
+
     def place_layer(self, layer_id, target_id, matrix, scratch_image_id, layer_size, target_size, filter=WarpFilter.BILINEAR, **composite_keywords):
         """A cached layer onto a target under an affine transform, two calls: warp(layer -> scratch, edge ZERO, dst_rect =
         warp_bounds(...)): the layer in target space, written only where it can be other than transparent black;
@@ -781,7 +857,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None):
+                morphology=None, warp=None, convolve=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -808,8 +884,12 @@ class Engine:
         warp=dict(dst=image id, width=..., height=..., matrix=..., ...) (the other keywords of warp(), optional) transforms the
         frame's target into the RGBA16F image `dst` of width x height where resample= would resize it (one more launch, nothing to
         run eagerly first); the surface, YUV or pack conversion of the same capture then reads that image at its size.  It is
-        exclusive with resample=: giving both is a ValueError before anything is captured.  So the order of a capture is: render,
-        morphology, blur, composite, color, resample or warp, then the surface, YUV or pack conversion."""
+        exclusive with resample=: giving both is a ValueError before anything is captured.
+        convolve=dict(dst=image id, ...) (the other keywords of convolve(), `weights` among them) convolves the frame's target into
+        the RGBA16F image `dst` of the target's size after the color filter (one more launch, nothing to run eagerly first); the
+        later steps of the same capture -- resample or warp, the surface, YUV or pack conversion -- then read `dst`.  So the order
+        of a capture is: render, morphology, blur, composite, color, convolve, resample or warp, then the surface, YUV or pack
+        conversion."""
         if resample is not None and warp is not None:
             raise ValueError("capture: resample= and warp= are exclusive (both would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
@@ -824,6 +904,9 @@ class Engine:
                 self.composite(composite["src"], t["id"], **{k: v for k, v in composite.items() if k != "src"})
             if color is not None:
                 self.color_filter(t["id"], **color)
+            if convolve is not None:
+                self.convolve(t["id"], convolve["dst"], **{k: v for k, v in convolve.items() if k != "dst"})
+                t = {"id": convolve["dst"], "width": t["width"], "height": t["height"]}
             if resample is not None:
                 self.resample(t["id"], resample["dst"], **{k: v for k, v in resample.items() if k not in ("dst", "width", "height")})
                 t = {"id": resample["dst"], "width": resample["width"], "height": resample["height"]}

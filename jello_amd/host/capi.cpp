@@ -11,6 +11,7 @@
 #include "../../include/jello_resample.h"
 #include "../../include/jello_color.h"
 #include "../../include/jello_warp.h"
+#include "../../include/jello_convolve.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -471,6 +472,15 @@ int jl_warp_plan(const double* matrix, int64_t* plan) {
 int jl_warp_bounds(const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect) {
     const char* why = matrix && rect ? jwarp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect) : "null argument";
     if (why) { g_err = std::string("warp_bounds: ") + why; return -1; }
+    return 0;
+}
+
+// jl_convolve_weights is the host twin of jh_convolve_weights (the rule is in jello_hip.h and DESIGN.md 5.13): the same header,
+// compiled here by the host compiler -- feConvolveMatrix's kernelMatrix flipped and divided into the weights jh_convolve applies; -1
+// for what the rule refuses.
+int jl_convolve_weights(uint32_t order_x, uint32_t order_y, const double* kernel_matrix, double divisor, float* weights) {
+    const char* why = kernel_matrix && weights ? jconv_weights(order_x, order_y, kernel_matrix, divisor, weights) : "null argument";
+    if (why) { g_err = std::string("convolve_weights: ") + why; return -1; }
     return 0;
 }
 
