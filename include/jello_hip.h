@@ -28,6 +28,7 @@
  *   jh_morphology                     (no counterpart: erode / dilate of an RGBA16F image by a box on the device)
  *   jh_warp                           (no counterpart: an affine transform of an RGBA16F image on the device)
  *   jh_convolve                       (no counterpart: feConvolveMatrix on an RGBA16F image on the device)
+ *   jh_lighting                       (no counterpart: feDiffuseLighting / feSpecularLighting on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -800,6 +801,104 @@ typedef struct jh_convolve_desc {
 } jh_convolve_desc;
 int jh_convolve_weights(uint32_t order_x, uint32_t order_y, const double* kernel_matrix, double divisor, float* weights);
 int jh_convolve(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_convolve_desc* desc);
+
+/* ---- Lighting: feDiffuseLighting and feSpecularLighting with their three light sources (DESIGN.md 5.14 "Lighting rule") ----
+ * Bevels, embossed text, glossy buttons, a lit height map -- the alpha channel of src is the height, and the image never leaves the
+ * device.  The result is defined on values, and every implementation produces these bits (include/jello_lighting.h states the host
+ * half and the normal, tests/lighting_ref.py restates all of it).  Only the alpha channel of src is read.
+ *   arguments   kind: JH_LIGHTING_DIFFUSE = 0 | JH_LIGHTING_SPECULAR = 1.  light: JH_LIGHT_DISTANT = 0 | JH_LIGHT_POINT = 1 |
+ *               JH_LIGHT_SPOT = 2.  surface_scale: binary32, finite.  constant (kd or ks): binary32, finite, >= 0.
+ *               specular_exponent: binary32 in [1, 128], read only under SPECULAR.  color[3]: binary32, finite, >= 0, LINEAR (the
+ *               target is linear; decoding lighting-color from sRGB is the caller's job).  direction[3]: binary64, finite, TOWARDS the
+ *               light, its length in binary64 finite and not 0; DISTANT only (no azimuth and no elevation: no trigonometry is in the
+ *               rule).  position[3]: binary64, each finite as a binary32; POINT and SPOT.  points_at[3]: binary64, points_at - position
+ *               of finite non-zero length; SPOT only.  spot_exponent: binary32 in [1, 128]; SPOT only.  cone_cos: binary64 in [-1, 1],
+ *               the cosine of the limiting cone angle, -1: no cone; SPOT only.  The rectangle (x, y, width, height) of dst is written;
+ *               width == height == 0 means the whole image.  Fields the kind and the light do not use are not looked at.
+ *   space       coordinates are texels of the image; texel (X, Y) sits at (X + 0.5, Y + 0.5), the renderer's pixel centre.  An image
+ *               extent above 2^23 is refused, so that (float)X + 0.5f is exact.
+ *   plan        jh_lighting_plan (a jh_light_plan), on the host, the only place binary64 appears: s[span - 1][wsum - 2] = (float)(-(double)surface_scale
+ *               * 2.0 / (double)(span * wsum)) for span in {1, 2}, wsum in {2, 3, 4};  ldir = direction / |direction|, |d| = sqrt(x x +
+ *               y y + z z) in binary64 left to right, each quotient rounded once to binary32;  p = (float)position;  sdir = (points_at -
+ *               position) normalised the same way;  cone = (float)cone_cos.  What the light does not use is +0.
+ *   normal      A(i, j): the f16 alpha of src at column i, row j, widened to binary32 (a never-written src: +0).  x_lo = max(X - 1, 0),
+ *               x_hi = min(X + 1, W - 1), rows likewise -- the IMAGE is the edge, not the rectangle.  span_x = x_hi - x_lo; wsum_y = the
+ *               sum of the weights (1, 2, 1) over those of the rows Y - 1, Y, Y + 1 that exist.  c(col) = the sum over the existing rows,
+ *               ASCENDING, of w_j A(col, j), in binary32, the adds left to right (2 A is exact).  gx = c(x_hi) - c(x_lo); Nx =
+ *               s(span_x, wsum_y) gx.  Ny likewise with row sums r(row) over the existing columns ascending, gy = r(y_hi) - r(y_lo), Ny =
+ *               s(span_y, wsum_x) gy.  An axis with span 0 (an image one texel wide or high) gives +0 for its component.  These are the
+ *               specification's nine cases (interior, four edges, four corners: factors 1/4, 1/3, 1/2 and 2/3; DESIGN.md 5.14 lists
+ *               them).  nlen = sqrtf(fmaf(Nx, Nx, fmaf(Ny, Ny, 1.0f))); the normal is (Nx, Ny, 1) / nlen, never normalised by itself.
+ *   light       DISTANT: l = ldir, not renormalised.  POINT and SPOT: Z = surface_scale A(X, Y); v = (p.x - ((float)X + 0.5f), p.y -
+ *               ((float)Y + 0.5f), p.z - Z); len = sqrtf(fmaf(v.z, v.z, fmaf(v.y, v.y, v.x v.x))); l = v / len, three IEEE divisions.
+ *   colour      DISTANT and POINT: C = color.  SPOT: m = -fmaf(l.z, sdir.z, fmaf(l.y, sdir.y, l.x sdir.x)); if not (m > 0 and m >= cone)
+ *               C = +0 in all channels (a NaN lands here; the cone's edge is hard); otherwise C.c = color.c Pw(min(m, 1), spot_exponent).
+ *   power       Pw(t, 1.0f) = t.  Otherwise a table of JH_LIGHTING_TABLE_ENTRIES = 4097 binary32, T[i] = (float)pow((double)i / 4096.0,
+ *               (double)e) -- libm in binary64, rounded once;  u = t 4096.0f (exact); i = min((int)u, 4095); f = u - (float)i (exact);
+ *               Pw = fmaf(f, T[i + 1] - T[i], T[i]), the difference one binary32 subtraction.  |Pw - t^e| <= e (e - 1) / (8 4096^2) for e
+ *               >= 2, and <= 4096^-e for 1 < e < 2 (the first segment), before the rounding: DESIGN.md 5.14.
+ *   DIFFUSE     t = fmax(fmaf(Nx, l.x, fmaf(Ny, l.y, l.z)) / nlen, 0.0f) (maxNum: a NaN gives 0); k = constant t; V.c = fmin(k C.c,
+ *               1.0f); the texel is (f16(V.r), f16(V.g), f16(V.b), 0x3c00).
+ *   SPECULAR    h = (l.x, l.y, l.z + 1.0f); hlen = sqrtf(fmaf(h.z, h.z, fmaf(h.y, h.y, h.x h.x))); q = fmaf(Nx, h.x, fmaf(Ny, h.y, h.z)) /
+ *               (nlen hlen); t = Pw(fmin(fmax(q, 0.0f), 1.0f), specular_exponent); k = constant t; V.c = fmin(k C.c, 1.0f); a = max(V.r,
+ *               V.g, V.b); the store is fine's un-premultiplying one, as jh_convolve PREMULTIPLIED: a_inv = 1.0f / max(a, 1e-6f);
+ *               (f16(V.c a_inv + 0.0f), f16(a + 0.0f)).
+ *   values      no contraction beyond the fmaf written above; IEEE divide and sqrt; every operation rounded once; min and max are
+ *               minNum and maxNum; f16 subnormals are values; an Inf or NaN alpha follows these operations and nothing else; a NaN
+ *               result is any NaN.
+ * So a constant finite alpha gives N = (0, 0, 1) and DIFFUSE DISTANT is min(kd ldir.z color, 1) everywhere; a light below the
+ * surface gives black; a SPECULAR texel's alpha is the maximum of its premultiplied colour.
+ * What the rule does not do: no kernelUnitLength; no antialiased cone edge; no light in user units (a caller with a transform maps the
+ * light itself); no call in place; no second resident table set.
+ *
+ * jh_lighting_plan: the plan of desc.  jh_lighting_tables: the tables desc needs -- *which = JH_LIGHTING_TABLE_SPEC (SPECULAR with
+ * specular_exponent != 1) | JH_LIGHTING_TABLE_SPOT (SPOT with spot_exponent != 1); each that is needed is written where its pointer is
+ * not NULL.  Both host only, no context; JH_ERR_INVALID for a null or illegal desc (the rectangle is not looked at).
+ *
+ * jh_lighting: the rule applied to src_image_id, written to the rectangle of dst_image_id, another image of the same size (a tile of
+ * a call in place would read alpha that another tile overwrote).  Texels of dst outside the rectangle keep their bits; a dst that was
+ * never written is cleared to transparent black first and then counts as written.  Stream-ordered, never waits: ONE kernel launch,
+ * plus a fill when dst has to be cleared.  The context keeps the tables of ONE key -- the bit patterns of the two exponents where
+ * their table is needed, 0 otherwise -- in a scratch slot of their own, by the contract of jh_resample and jh_color_filter: repeating
+ * the key uploads nothing and is capturable; another key uploads its tables, bumps the generation and makes earlier graphs stale; a
+ * capture whose tables are not resident is refused (JH_ERR_OOM, "run this lighting once eagerly first"); a call that needs no table
+ * (DIFFUSE with DISTANT or POINT, any call whose exponents in use are 1) is always capturable and does not touch the slot;
+ * jh_scratch_trim forgets the key.  With profiling on the call is a query "lighting" with stage = -1 in jh_profile_collect_tree.  Not
+ * in band mode (jh_set_band).  JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that
+ * starts "jh_lighting: ": a null desc; an unknown source or destination id; an image that is not RGBA16F; images of different size;
+ * src_image_id == dst_image_id; an extent above 2^23; an unknown kind or light; an illegal field of the list above; a rectangle that
+ * is not inside the image or that is empty in exactly one dimension; a band set with jh_set_band.  An image without texels returns
+ * JH_OK. */
+typedef enum jh_lighting_kind { JH_LIGHTING_DIFFUSE = 0, JH_LIGHTING_SPECULAR = 1 } jh_lighting_kind;
+typedef enum jh_light_source { JH_LIGHT_DISTANT = 0, JH_LIGHT_POINT = 1, JH_LIGHT_SPOT = 2 } jh_light_source;
+#define JH_LIGHTING_TABLE_ENTRIES 4097u
+#define JH_LIGHTING_TABLE_SPEC 1u
+#define JH_LIGHTING_TABLE_SPOT 2u
+#define JH_LIGHTING_MAX_EXTENT 8388608u /* 2^23 */
+typedef struct jh_lighting_desc {
+    int kind;                      /* jh_lighting_kind */
+    int light;                     /* jh_light_source */
+    float surface_scale;
+    float constant;                /* kd or ks */
+    float specular_exponent;
+    float spot_exponent;
+    float color[3];                /* linear */
+    uint32_t x, y, width, height;  /* rectangle of dst that is written; 0 x 0: the whole image */
+    double direction[3];           /* towards the light */
+    double position[3];
+    double points_at[3];
+    double cone_cos;
+} jh_lighting_desc;
+typedef struct jh_light_plan {
+    float s[2][3];  /* [span - 1][wsum - 2] */
+    float ldir[3];
+    float p[3];
+    float sdir[3];
+    float cone;
+} jh_light_plan;
+int jh_lighting_plan(const jh_lighting_desc* desc, jh_light_plan* plan);
+int jh_lighting_tables(const jh_lighting_desc* desc, float* spec_table /* 4097 or NULL */, float* spot_table /* 4097 or NULL */, uint32_t* which);
+int jh_lighting(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_lighting_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

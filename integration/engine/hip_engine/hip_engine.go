@@ -769,6 +769,86 @@ func (e *Engine) Convolve(src, dst renderer.ImageProxy, desc ConvolveDesc) {
 	e.check(C.jh_convolve(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "convolve")
 }
 
+// LightKind is jh_lighting_kind: feDiffuseLighting or feSpecularLighting.
+type LightKind int32
+
+const (
+	LightingDiffuse  LightKind = 0
+	LightingSpecular LightKind = 1
+)
+
+// LightSource is jh_light_source: feDistantLight, fePointLight, feSpotLight.
+type LightSource int32
+
+const (
+	LightDistant LightSource = 0
+	LightPoint   LightSource = 1
+	LightSpot    LightSource = 2
+)
+
+// LightingDesc is jh_lighting_desc (include/jello_hip.h "Lighting"): the filter (SurfaceScale, Constant = kd or ks, SpecularExponent in
+// [1, 128], a LINEAR Color), the light (Direction towards a distant light; Position of a point or spot light, PointsAt, SpotExponent in
+// [1, 128] and ConeCos, the cosine of the limiting cone angle, -1: no cone) in texels of the image, texel (X, Y) at (X + 0.5, Y + 0.5),
+// and the rectangle of dst that is written (Width == Height == 0: the whole image).
+type LightingDesc struct {
+	Kind                                                  LightKind
+	Light                                                 LightSource
+	SurfaceScale, Constant, SpecularExponent, SpotExponent float32
+	Color                                                 [3]float32
+	X, Y, Width, Height                                   uint32
+	Direction, Position, PointsAt                         [3]float64
+	ConeCos                                               float64
+}
+
+// LightPlan is jh_light_plan: what the device is given of a LightingDesc, every value a binary32.
+type LightPlan struct {
+	S                [2][3]float32 // [span - 1][wsum - 2]
+	Ldir, P, Sdir    [3]float32
+	Cone             float32
+}
+
+func (desc LightingDesc) c() C.jh_lighting_desc {
+	d := C.jh_lighting_desc{kind: C.int(desc.Kind), light: C.int(desc.Light), surface_scale: C.float(desc.SurfaceScale), constant: C.float(desc.Constant),
+		specular_exponent: C.float(desc.SpecularExponent), spot_exponent: C.float(desc.SpotExponent), x: C.uint32_t(desc.X), y: C.uint32_t(desc.Y),
+		width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height), cone_cos: C.double(desc.ConeCos)}
+	for i := 0; i < 3; i++ {
+		d.color[i] = C.float(desc.Color[i])
+		d.direction[i] = C.double(desc.Direction[i])
+		d.position[i] = C.double(desc.Position[i])
+		d.points_at[i] = C.double(desc.PointsAt[i])
+	}
+	return d
+}
+
+// LightingPlan is jh_lighting_plan: the plan of desc -- the only place binary64 appears in the lighting rule.  Host only.
+func LightingPlan(desc LightingDesc) (LightPlan, error) {
+	d := desc.c()
+	var p C.jh_light_plan
+	if C.jh_lighting_plan(&d, &p) != 0 {
+		return LightPlan{}, fmt.Errorf("hip_engine: LightingPlan: a descriptor the rule refuses")
+	}
+	var out LightPlan
+	for i := 0; i < 2; i++ {
+		for j := 0; j < 3; j++ {
+			out.S[i][j] = float32(p.s[i][j])
+		}
+	}
+	for i := 0; i < 3; i++ {
+		out.Ldir[i], out.P[i], out.Sdir[i] = float32(p.ldir[i]), float32(p.p[i]), float32(p.sdir[i])
+	}
+	out.Cone = float32(p.cone)
+	return out, nil
+}
+
+// Lighting is jh_lighting: feDiffuseLighting or feSpecularLighting of the ALPHA channel of the RGBA16F image src into the RGBA16F
+// image dst (another image of the same size) by the rule of DESIGN.md 5.14 (defined on values: every implementation gives the same
+// bits).  Stream-ordered behind the frame, waits for nothing, one kernel launch.  The context holds the power tables of one pair of
+// exponents: a call with another uploads its own and makes graphs captured before it stale; exponents of 1 need none.
+func (e *Engine) Lighting(src, dst renderer.ImageProxy, desc LightingDesc) {
+	d := desc.c()
+	e.check(C.jh_lighting(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "lighting")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -186,6 +186,20 @@ class CConvolveDesc(ctypes.Structure):
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("weights", ctypes.c_float * 225)]
 
 
+class CLightingDesc(ctypes.Structure):
+    """jh_lighting_desc (include/jello_hip.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("light", ctypes.c_int32), ("surface_scale", ctypes.c_float), ("constant", ctypes.c_float),
+                ("specular_exponent", ctypes.c_float), ("spot_exponent", ctypes.c_float), ("color", ctypes.c_float * 3), ("x", ctypes.c_uint32),
+                ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("direction", ctypes.c_double * 3),
+                ("position", ctypes.c_double * 3), ("points_at", ctypes.c_double * 3), ("cone_cos", ctypes.c_double)]
+
+
+class CLightPlan(ctypes.Structure):
+    """jh_light_plan (include/jello_hip.h)."""
+    _fields_ = [("s", ctypes.c_float * 6), ("ldir", ctypes.c_float * 3), ("p", ctypes.c_float * 3), ("sdir", ctypes.c_float * 3),
+                ("cone", ctypes.c_float)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -259,6 +273,8 @@ def _declare(L):
     L.jl_warp_plan.argtypes = [dp, ctypes.POINTER(ctypes.c_int64)]
     L.jl_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
     L.jl_convolve_weights.argtypes = [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
+    L.jl_lighting_plan.argtypes = [ctypes.POINTER(CLightingDesc), ctypes.POINTER(CLightPlan)]
+    L.jl_lighting_tables.argtypes = [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -308,6 +324,9 @@ def _declare(L):
     hip.jh_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
     hip.jh_convolve.argtypes = [vp, u64, u64, ctypes.POINTER(CConvolveDesc)]
     hip.jh_convolve_weights.argtypes = [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
+    hip.jh_lighting.argtypes = [vp, u64, u64, ctypes.POINTER(CLightingDesc)]
+    hip.jh_lighting_plan.argtypes = [ctypes.POINTER(CLightingDesc), ctypes.POINTER(CLightPlan)]
+    hip.jh_lighting_tables.argtypes = [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -27,6 +27,7 @@
 #include "../../include/jello_morph.h"
 #include "../../include/jello_warp.h"
 #include "../../include/jello_convolve.h"
+#include "../../include/jello_lighting.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -145,6 +146,12 @@ struct jh_ctx {
         jcolor_key key = {};
         const char* dev = nullptr;
     } color;
+    // jh_lighting: the key whose tables the JH_SCR_LIGHT_TABLES slot holds, and where
+    struct {
+        bool valid = false;
+        jlight_key key = {};
+        const char* dev = nullptr;
+    } light;
 };
 
 static int flush_held(jh_ctx* ctx);
@@ -1154,7 +1161,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1764,6 +1771,57 @@ int jh_convolve(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const
     });
 }
 
+// lighting (include/jello_hip.h "Lighting"; the descriptor, the plan, the tables and the key: include/jello_lighting.h; kernels_lighting.hip)
+int jh_lighting_plan(const jh_lighting_desc* desc, jh_light_plan* plan) {
+    if (!desc || !plan) return JH_ERR_INVALID;
+    return jlight_plan(desc, plan) ? JH_ERR_INVALID : JH_OK;
+}
+int jh_lighting_tables(const jh_lighting_desc* desc, float* spec_table, float* spot_table, uint32_t* which) {
+    if (!desc || jlight_desc_error(desc)) return JH_ERR_INVALID;
+    const uint32_t w = jlight_tables(desc, spec_table, spot_table);
+    if (which) *which = w;
+    return JH_OK;
+}
+int jh_lighting(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_lighting_desc* desc) {
+    static_assert(JH_LIGHTING_DIFFUSE == JLIGHT_DIFFUSE && JH_LIGHTING_SPECULAR == JLIGHT_SPECULAR && JH_LIGHT_DISTANT == JLIGHT_DISTANT &&
+                      JH_LIGHT_POINT == JLIGHT_POINT && JH_LIGHT_SPOT == JLIGHT_SPOT && JH_LIGHTING_TABLE_ENTRIES == JLIGHT_ENTRIES &&
+                      JH_LIGHTING_TABLE_SPEC == JLIGHT_TABLE_SPEC && JH_LIGHTING_TABLE_SPOT == JLIGHT_TABLE_SPOT && JH_LIGHTING_MAX_EXTENT == JLIGHT_MAX_EXTENT,
+                  "the C ABI's values are the rule's");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = image_call_images(ctx, "jh_lighting", desc, src_image_id, dst_image_id, "a tile of a lighting in place reads alpha that another tile overwrote", "the rows a normal reads belong to another rank, the tables and their key to the context", &src, &dst)) return rc;
+    if (src->width != dst->width || src->height != dst->height) return fail(ctx, JH_ERR_INVALID, "jh_lighting: the images differ in size");
+    if (dst->width > JLIGHT_MAX_EXTENT || dst->height > JLIGHT_MAX_EXTENT) return fail(ctx, JH_ERR_INVALID, "jh_lighting: an image extent above 2^23");
+    jh_light_plan plan;
+    if (const char* why = jlight_plan(desc, &plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_lighting: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_lighting", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    const uint32_t which = jlight_which(desc);
+    jlight_key key;
+    jlight_key_of(desc, &key);
+    // (a call without tables does not touch the slot: nothing of it has to be resident)
+    ResidentTables tables = {which == 0u || (ctx->light.valid && jlight_key_equal(&ctx->light.key, &key)), {}};
+    const uint64_t table_bytes = (uint64_t)JLIGHT_ENTRIES * sizeof(float);
+    std::vector<char> blob;
+    if (tables.to_build(ctx)) {
+        blob.assign(2u * table_bytes, 0);
+        jlight_tables(desc, (float*)blob.data(), (float*)(blob.data() + table_bytes));
+    }
+    return post_render_call(
+        ctx, "lighting", [&] { return tables_take(ctx, "jh_lighting", "run this lighting once eagerly first", JH_SCR_LIGHT_TABLES, blob, &tables); },
+        [&] {
+            ImageViews v;
+            if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
+            if (int rc = tables_send(ctx, tables, &ctx->light.valid, [&](const char* dev) { ctx->light.key = key; ctx->light.dev = dev; })) return rc;
+            const char* dev = ctx->light.dev;
+            const float* spec = (which & JLIGHT_TABLE_SPEC) ? (const float*)dev : nullptr;
+            const float* spot = (which & JLIGHT_TABLE_SPOT) ? (const float*)(dev + table_bytes) : nullptr;
+            return launch_status(ctx, "jh_lighting",
+                                 jh_lighting_launch(ctx->stream, v.from, v.to, r, desc->kind, desc->light, &plan, desc->surface_scale, desc->constant, desc->color, spec,
+                                                    spot, ctx->num_cus));
+        });
+}
+
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.
 int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
@@ -1807,7 +1865,7 @@ int jh_debug_poison_scratch(jh_ctx* ctx, int byte) {
     JH_FLUSH(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int i = 0; i < JH_SCR_COUNT; i++) {
-        if (i == JH_SCR_RESAMPLE_TAPS || i == JH_SCR_COLOR_TABLES) continue;  // (uploaded content a captured jh_resample / jh_color_filter reads, not an array a frame fills before it reads it)
+        if (i == JH_SCR_RESAMPLE_TAPS || i == JH_SCR_COLOR_TABLES || i == JH_SCR_LIGHT_TABLES) continue;  // (uploaded content a captured jh_resample / jh_color_filter / jh_lighting reads, not an array a frame fills before it reads it)
         if (ctx->scratch.ptr[i] && ctx->scratch.cap[i]) HIP_TRY(ctx, hipMemsetAsync(ctx->scratch.ptr[i], byte, ctx->scratch.cap[i], ctx->stream));
     }
     ctx->scratch.clean_flags = 0u;
@@ -1874,6 +1932,7 @@ int jh_scratch_trim(jh_ctx* ctx) {
     ctx->scratch.clean_flags = 0;  // (new memory holds anything: every self-cleaned array is filled again on its next use)
     ctx->resample.valid = false;   // (jh_resample's tables went with their slot)
     ctx->color.valid = false;      // (jh_color_filter's likewise)
+    ctx->light.valid = false;      // (jh_lighting's likewise)
     ctx->generation++;
     return JH_OK;
 }

@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CWarpDesc, CYuvDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CLightingDesc, CLightPlan, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CWarpDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -277,6 +277,70 @@ def _convolve_desc(weights, order, target, edge, mode, bias, rect):
     d = CConvolveDesc(ox, oy, tx, ty, int(edge), int(mode), float(bias), *_rect(rect))
     d.weights[:ox * oy] = [float(v) for v in w]
     return d
+
+
+class LightKind(enum.IntEnum):
+    """jh_lighting_kind: feDiffuseLighting or feSpecularLighting."""
+    DIFFUSE = 0
+    SPECULAR = 1
+
+
+class LightSource(enum.IntEnum):
+    """jh_light_source: feDistantLight, fePointLight, feSpotLight."""
+    DISTANT = 0
+    POINT = 1
+    SPOT = 2
+
+
+LIGHTING_TABLE_ENTRIES = 4097  # JH_LIGHTING_TABLE_ENTRIES
+LIGHTING_TABLE_SPEC, LIGHTING_TABLE_SPOT = 1, 2  # jh_lighting_tables' `which`
+
+
+def _vec3(v, what):
+    v = tuple(float(c) for c in v)
+    if len(v) != 3:
+        raise ValueError("jh_lighting: %s has three components" % what)
+    return v
+
+
+def _lighting_desc(kind=LightKind.DIFFUSE, light=LightSource.DISTANT, surface_scale=1.0, constant=1.0, specular_exponent=1.0, color=(1.0, 1.0, 1.0),
+                   direction=(0.0, 0.0, 1.0), position=(0.0, 0.0, 0.0), points_at=(0.0, 0.0, 0.0), spot_exponent=1.0, cone_cos=-1.0, rect=None):
+    """jh_lighting_desc.  What the rule refuses is left for the call to refuse."""
+    d = CLightingDesc()
+    d.kind, d.light = int(kind), int(light)
+    d.surface_scale, d.constant, d.specular_exponent, d.spot_exponent = float(surface_scale), float(constant), float(specular_exponent), float(spot_exponent)
+    d.color[:] = _vec3(color, "color")
+    d.x, d.y, d.width, d.height = _rect(rect)
+    d.direction[:] = _vec3(direction, "direction")
+    d.position[:] = _vec3(position, "position")
+    d.points_at[:] = _vec3(points_at, "points_at")
+    d.cone_cos = float(cone_cos)
+    return d
+
+
+def lighting_plan(twin=False, **keywords):
+    """jh_lighting_plan (twin: jl_lighting_plan, the host twin): the plan of the lighting rule for the keywords of
+    Engine.lighting -- dict(s=float32 (2, 3) indexed [span - 1][wsum - 2], ldir, p, sdir = float32 (3,), cone = float32).  No GPU needed.
+    ValueError for a descriptor the rule refuses."""
+    L = _lib.load_host()
+    d, plan = _lighting_desc(**keywords), CLightPlan()
+    if (L.jl_lighting_plan if twin else L.hip.jh_lighting_plan)(ctypes.byref(d), ctypes.byref(plan)) != 0:
+        raise ValueError("jh_lighting: illegal descriptor")
+    return dict(s=np.array(plan.s, np.float32).reshape(2, 3), ldir=np.array(plan.ldir, np.float32), p=np.array(plan.p, np.float32),
+                sdir=np.array(plan.sdir, np.float32), cone=np.float32(plan.cone))
+
+
+def lighting_tables(twin=False, **keywords):
+    """jh_lighting_tables (twin: jl_lighting_tables): (spec, spot, which) -- the power tables the keywords of Engine.lighting need, float32
+    [4097] each or None where the exponent is 1 or is not in use, and the bit mask.  No GPU needed.  ValueError as lighting_plan."""
+    L = _lib.load_host()
+    d = _lighting_desc(**keywords)
+    spec, spot = np.zeros(LIGHTING_TABLE_ENTRIES, np.float32), np.zeros(LIGHTING_TABLE_ENTRIES, np.float32)
+    which = ctypes.c_uint32(0)
+    if (L.jl_lighting_tables if twin else L.hip.jh_lighting_tables)(ctypes.byref(d), spec.ctypes.data, spot.ctypes.data, ctypes.byref(which)) != 0:
+        raise ValueError("jh_lighting: illegal descriptor")
+    w = which.value
+    return (spec if w & LIGHTING_TABLE_SPEC else None, spot if w & LIGHTING_TABLE_SPOT else None, w)
 
 
 class ColorSpace(enum.IntEnum):
@@ -707,6 +771,32 @@ class Engine:
         d = _convolve_desc(weights, order, target, edge, mode, bias, rect)
         self._check(self.hip.jh_convolve(self.ctx, src_id, dst_id, ctypes.byref(d)), "convolve", invalid=ValueError)
 
+    def lighting(self, src_id, dst_id, **keywords):
+        """jh_lighting: feDiffuseLighting or feSpecularLighting (the rule: DESIGN.md 5.14) of the ALPHA channel of the RGBA16F image
+        `src_id`, the height map, into the RGBA16F image `dst_id`, another image of the same size.  Keywords: `kind` (LightKind),
+        `light` (LightSource), `surface_scale`, `constant` (kd or ks, >= 0), `specular_exponent` in [1, 128], `color` = (r, g, b) LINEAR and
+        >= 0, `direction` = (x, y, z) towards a DISTANT light, `position` of a POINT or SPOT light and `points_at`, `spot_exponent` in
+        [1, 128] and `cone_cos` in [-1, 1] (-1: no cone) of a SPOT light -- coordinates in texels of the image, texel (X, Y) at (X +
+        0.5, Y + 0.5) -- and `rect` = (x, y, width, height), the rectangle of the destination that is written (None: the whole image);
+        the alpha outside it takes part in the normals.  jello_amd.lighting has the specification's attributes (distant, point, spot,
+        diffuse, specular: azimuth and elevation, the cone angle, lighting-color in sRGB), each a part of these keywords.  DIFFUSE
+        gives an opaque image, SPECULAR one whose alpha is the largest of its premultiplied channels.  The context holds the power
+        tables of one pair of exponents: a call with another uploads its own and makes graphs captured before it stale; exponents
+        of 1 need none.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _lighting_desc(**keywords)
+        self._check(self.hip.jh_lighting(self.ctx, src_id, dst_id, ctypes.byref(d)), "lighting", invalid=ValueError)
+
+    def bevel(self, layer_id, target_id, scratch_a, scratch_b, sigma, light, size, surface_scale=5.0, ks=0.75, exponent=20.0, color=(1.0, 1.0, 1.0)):
+        """The specification's worked example (a lit bevel of a layer's alpha) as four calls on RGBA16F images of one `size` = (width,
+        height): blur(layer -> scratch_a, sigma); lighting(scratch_a -> scratch_b, SPECULAR, **light) -- `light` the keywords of
+        lighting.distant / point / spot, `color` linear; composite(layer onto scratch_b, DestIn): the highlight inside the layer;
+        composite(layer onto target), composite(scratch_b onto target, Plus).  The four images are distinct; the layer is only read."""
+        self.blur(layer_id, size[0], size[1], sigma, dst_image_id=scratch_a)
+        self.lighting(scratch_a, scratch_b, kind=LightKind.SPECULAR, surface_scale=surface_scale, constant=ks, specular_exponent=exponent, color=color, **light)
+        self.composite(layer_id, scratch_b, compose=Compose.DestIn)
+        self.composite(layer_id, target_id)
+        self.composite(scratch_b, target_id, compose=Compose.Plus)
+
     def place_layer(self, layer_id, target_id, matrix, scratch_image_id, layer_size, target_size, filter=WarpFilter.BILINEAR, **composite_keywords):
         """A cached layer onto a target under an affine transform, two calls: warp(layer -> scratch, edge ZERO, dst_rect =
         warp_bounds(...)): the layer in target space, written only where it can be other than transparent black;
@@ -857,7 +947,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None, convolve=None):
+                morphology=None, warp=None, convolve=None, lighting=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -887,9 +977,12 @@ class Engine:
         exclusive with resample=: giving both is a ValueError before anything is captured.
         convolve=dict(dst=image id, ...) (the other keywords of convolve(), `weights` among them) convolves the frame's target into
         the RGBA16F image `dst` of the target's size after the color filter (one more launch, nothing to run eagerly first); the
-        later steps of the same capture -- resample or warp, the surface, YUV or pack conversion -- then read `dst`.  So the order
-        of a capture is: render, morphology, blur, composite, color, convolve, resample or warp, then the surface, YUV or pack
-        conversion."""
+        later steps of the same capture -- resample or warp, the surface, YUV or pack conversion -- then read `dst`.
+        lighting=dict(dst=image id, ...) (the other keywords of lighting()) lights the alpha of the frame's target into the RGBA16F
+        image `dst` of the target's size after the color filter and BEFORE the convolve (one more launch); lighting whose exponents
+        need tables must have run once eagerly, and no other such since.  The later steps -- convolve, resample or warp, the
+        conversion -- then read `dst`.  So the order of a capture is: render, morphology, blur, composite, color, lighting, convolve,
+        resample or warp, then the surface, YUV or pack conversion."""
         if resample is not None and warp is not None:
             raise ValueError("capture: resample= and warp= are exclusive (both would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
@@ -904,6 +997,9 @@ class Engine:
                 self.composite(composite["src"], t["id"], **{k: v for k, v in composite.items() if k != "src"})
             if color is not None:
                 self.color_filter(t["id"], **color)
+            if lighting is not None:
+                self.lighting(t["id"], lighting["dst"], **{k: v for k, v in lighting.items() if k != "dst"})
+                t = {"id": lighting["dst"], "width": t["width"], "height": t["height"]}
             if convolve is not None:
                 self.convolve(t["id"], convolve["dst"], **{k: v for k, v in convolve.items() if k != "dst"})
                 t = {"id": convolve["dst"], "width": t["width"], "height": t["height"]}

@@ -12,6 +12,7 @@
 #include "../../include/jello_color.h"
 #include "../../include/jello_warp.h"
 #include "../../include/jello_convolve.h"
+#include "../../include/jello_lighting.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -492,6 +493,23 @@ int jl_color_tables(const jh_color_desc* desc, float* pre, uint16_t* post, uint3
     const char* why = desc ? jcolor_desc_error(desc) : "null descriptor";
     if (why) { g_err = std::string("color_tables: ") + why; return -1; }
     const uint32_t w = jcolor_tables(desc, pre, post);
+    if (which) *which = w;
+    return 0;
+}
+
+// jl_lighting_plan and jl_lighting_tables are the host twins of jh_lighting_plan and jh_lighting_tables (the rule is in jello_hip.h and
+// DESIGN.md 5.14): the same header, compiled here by the host compiler -- the plan of desc; its power tables (4097 floats each; or null),
+// only those it needs, and which they are into *which (bit 0: the specular exponent's, bit 1: the spot exponent's); -1 for a
+// descriptor the rule refuses.
+int jl_lighting_plan(const jh_lighting_desc* desc, jh_light_plan* plan) {
+    const char* why = desc && plan ? jlight_plan(desc, plan) : "null argument";
+    if (why) { g_err = std::string("lighting_plan: ") + why; return -1; }
+    return 0;
+}
+int jl_lighting_tables(const jh_lighting_desc* desc, float* spec_table, float* spot_table, uint32_t* which) {
+    const char* why = desc ? jlight_desc_error(desc) : "null descriptor";
+    if (why) { g_err = std::string("lighting_tables: ") + why; return -1; }
+    const uint32_t w = jlight_tables(desc, spec_table, spot_table);
     if (which) *which = w;
     return 0;
 }
