@@ -29,6 +29,7 @@
  *   jh_warp                           (no counterpart: an affine transform of an RGBA16F image on the device)
  *   jh_convolve                       (no counterpart: feConvolveMatrix on an RGBA16F image on the device)
  *   jh_lighting                       (no counterpart: feDiffuseLighting / feSpecularLighting on the device)
+ *   jh_turbulence                     (no counterpart: feTurbulence noise into an RGBA16F image on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -899,6 +900,98 @@ typedef struct jh_light_plan {
 int jh_lighting_plan(const jh_lighting_desc* desc, jh_light_plan* plan);
 int jh_lighting_tables(const jh_lighting_desc* desc, float* spec_table /* 4097 or NULL */, float* spot_table /* 4097 or NULL */, uint32_t* which);
 int jh_lighting(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_lighting_desc* desc);
+
+/* ---- Turbulence: feTurbulence, Perlin turbulence or fractal noise GENERATED into an image (DESIGN.md 5.15 "Turbulence rule") ----
+ * Grain, clouds, marble, the height map jh_lighting reads, a mask for jh_composite -- made where the other calls run, nothing is
+ * uploaded but 8.4 KB of tables per seed.  The algorithm is the reference code of Filter Effects Level 1 (the stitch comparison BEFORE
+ * the mask with 255).  The result is defined on values, and every implementation produces these bits (include/jello_turbulence.h states
+ * the host half and the device half's cases, tests/turbulence_ref.py restates all of it).  Binary64 appears in the plan and the tables
+ * only.  The image holds straight colour and so does the primitive's result: the four channels are stored as they come.
+ *   arguments   kind: JH_TURBULENCE_FRACTAL_NOISE = 0 | JH_TURBULENCE_TURBULENCE = 1.  base_frequency[2]: binary64, finite, >= 0, in
+ *               cells per texel.  octaves: 0 .. JH_TURBULENCE_MAX_OCTAVES = 16.  seed: int32.  stitch: 0 or 1.  tile[4]: binary64 x, y,
+ *               w, h, finite, w and h > 0; read only under stitch.  origin[2]: binary64, finite: the coordinate of the image's corner,
+ *               so that a caller can continue one noise field across images.  The rectangle (x, y, width, height) of dst is written;
+ *               width == height == 0 means the whole image.
+ *   space       the centre of texel (X, Y) of the IMAGE is at (origin.x + X + 0.5, origin.y + Y + 0.5).
+ *   seed        the specification's setup_seed, in integers, m = 2^31 - 1: s <= 0 becomes -(s mod (m - 1)) + 1 (C's remainder), s >
+ *               m - 1 becomes m - 1.  That value is the KEY of the tables.
+ *   tables      the specification's init with the Park-Miller generator (a = 16807, m = 2^31 - 1, Schrage's q = 127773, r = 2836;
+ *               from seed 1 the 10 000th number is 1043618065), the draws in its order: the gradients first, k = 0 .. 3 outermost, i =
+ *               0 .. 255, x then y, each ((r mod 512) - 256) / 256, which is exact; s = sqrt(x x + y y) in binary64 left to right;
+ *               G[k][i] = ((float)(x / s), (float)(y / s)), each quotient in binary64 rounded once.  A gradient whose components are
+ *               both 0 is 0 / 0 in the specification's code; here it stays (+0, +0).  Then the shuffle of P[i] = i: for i = 255 down to
+ *               1, swap P[i] and P[r mod 256].  The specification's duplicated upper halves are not stored: its P[i + by] with i + by up
+ *               to 510 is P[(i + by) & 255] by construction, which is what the rule reads (tools/turbulence_check.cpp compares them).
+ *   plan        jh_turbulence_plan (a jh_turb_plan), on the host.  Per axis f = base_frequency; under stitch and f != 0 the
+ *               specification's lo / hi rule in binary64: t = tile_w f, lo = floor(t) / tile_w, hi = ceil(t) / tile_w, f = lo if lo !=
+ *               0 and f / lo < hi / f, else hi.  Under stitch width = (int)(tile_w f + 0.5) and wrap = floor(tile_x f) + width, with
+ *               the adjusted f (the specification's + 4096 is dropped from both sides of its comparison); otherwise both are 0.
+ *               Positions are int64 in units of 2^-32 cell: step = nearbyint(f 2^32), start = nearbyint(((origin + 0.5) f) 2^32) --
+ *               the sum, the product and the (exact) scaling one binary64 operation each, ties to even --, pos(X) = start + X step.
+ *   legal       with L = (2^62 - 1) >> max(octaves - 1, 0): f 2^32 and |(origin + 0.5) f 2^32| below 2^62; |start| <= L; the image
+ *               extent at most max_extent = the largest W with start + (W - 1) step <= L -- so every position of the IMAGE shifted
+ *               left by octaves - 1 fits an int64 with a bit to spare --; under stitch tile_w f + 0.5 and |floor(tile_x f)| below 2^31
+ *               and |wrap|, width <= (2^31 - 1) >> max(octaves - 1, 0).  Anything else is refused with a message.
+ *   octave      for k = 0 .. octaves - 1, per axis: p = pos << k; cell i = p >> 32 (arithmetic: negative coordinates floor); r0 =
+ *               (float)((uint32)p >> 8) 2^-24 (exact), r1 = r0 - 1.0f (exact).  Under stitch wrap_k = wrap << k, width_k = width << k,
+ *               and each of i and i + 1 that is >= wrap_k has width_k subtracted; then the mask with 255: bx0, bx1, by0, by1.
+ *   lattice     b00 = P[(P[bx0] + by0) & 255], b10 = P[(P[bx1] + by0) & 255], b01 = P[(P[bx0] + by1) & 255], b11 = P[(P[bx1] + by1)
+ *               & 255].
+ *   noise       s(t) = (t t) fmaf(-2.0f, t, 3.0f); sx = s(rx0), sy = s(ry0).  For channel c (r, g, b, a = 0 .. 3) and corner b.. with
+ *               g = G[c][b..] and (rx, ry) the offset to that corner -- (rx0, ry0), (rx1, ry0), (rx0, ry1), (rx1, ry1) --: u.. =
+ *               fmaf(ry, g.y, rx g.x).  lerp(t, a, b) = fmaf(t, b - a, a); n = lerp(sy, lerp(sx, u00, u10), lerp(sx, u01, u11)).
+ *               sum = fmaf(n, 2^-k, sum) under FRACTAL_NOISE, fmaf(|n|, 2^-k, sum) under TURBULENCE, from +0.
+ *   result      v = fmaf(sum, 0.5f, 0.5f) under FRACTAL_NOISE, v = sum under TURBULENCE; fmin(fmax(v, 0.0f), 1.0f); the texel is
+ *               the four values rounded once to f16.  No contraction beyond the fmaf written here; every operation rounded once.
+ * So with 0 octaves FRACTAL_NOISE gives 0.5 in all four channels and TURBULENCE transparent black, and the noise is exactly 0 where
+ * the position is a lattice point in every octave.  The stored texel is within 2^-12 (half an f16 ULP below 1) + 10.5 (K (W + 2) 2^-33 +
+ * 2^-23) + (40 + 2 K) 2^-24 of the specification's binary64 code, K octaves on an image extent W, positions up to 2^20 cells: DESIGN.md
+ * 5.15 derives it.
+ * What the rule does not do: no colour-space conversion (the target is linear, as color-interpolation-filters defaults); no user-unit
+ * scale (the caller scales the frequency); stitched tiles repeat only to within the position grid -- the step is rounded to 2^-32
+ * cell, so after tile_w texels the position is off by at most tile_w 2^-33 cell per octave step, which is not bit-periodic (DESIGN.md
+ * 5.15 has the bound in f16 ULP) --; no second resident table set; no float seed.
+ *
+ * jh_turbulence_plan: the plan of desc (the rectangle is not looked at; the image extent is checked against max_extent by
+ * jh_turbulence).  jh_turbulence_tables: selector[256] = P and gradients[2048] = G[4][256][2] of desc's seed (either may be NULL).
+ * Both host only, no context; JH_ERR_INVALID for a null or illegal desc.
+ *
+ * jh_turbulence: the rule, written to the rectangle of dst_image_id.  Texels of dst outside the rectangle keep their bits; a dst that
+ * was never written is cleared to transparent black first and then counts as written.  Stream-ordered, never waits: ONE kernel
+ * launch, plus a fill when dst has to be cleared.  The context keeps the tables of ONE key (the seed after setup_seed) in a scratch
+ * slot of their own, by the contract of jh_lighting: repeating the key uploads nothing and is capturable; another key uploads its
+ * tables, bumps the generation and makes earlier graphs stale; a capture whose tables are not resident is refused (JH_ERR_OOM, "run
+ * this turbulence once eagerly first"); jh_scratch_trim forgets the key.  With profiling on the call is a query "turbulence" with
+ * stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band).  JH_ERR_INVALID, with nothing enqueued, no memory touched and
+ * nothing flushed, each with a message that starts "jh_turbulence: ": a null desc; an unknown destination id; an image that is not
+ * RGBA16F; an unknown kind; more than 16 octaves; a stitch that is neither 0 nor 1; an illegal field of the list above; an image
+ * beyond max_extent; a rectangle that is not inside the image or that is empty in exactly one dimension; a band set with jh_set_band.
+ * An image without texels returns JH_OK. */
+typedef enum jh_turbulence_kind { JH_TURBULENCE_FRACTAL_NOISE = 0, JH_TURBULENCE_TURBULENCE = 1 } jh_turbulence_kind;
+#define JH_TURBULENCE_MAX_OCTAVES 16u
+typedef struct jh_turbulence_desc {
+    int kind;                      /* jh_turbulence_kind */
+    uint32_t octaves;
+    int32_t seed;
+    int stitch;
+    uint32_t x, y, width, height;  /* rectangle of dst that is written; 0 x 0: the whole image */
+    double base_frequency[2];      /* cells per texel */
+    double tile[4];                /* x, y, w, h; under stitch */
+    double origin[2];              /* the coordinate of the image's corner */
+} jh_turbulence_desc;
+typedef struct jh_turb_plan {
+    double frequency[2];     /* after the stitch adjustment */
+    int64_t step[2];         /* 2^-32 cell per texel */
+    int64_t start[2];        /* the position of texel 0 */
+    int32_t wrap[2];         /* under stitch, else 0 */
+    int32_t width[2];
+    uint32_t max_extent[2];  /* the largest legal image extent */
+    uint32_t key;            /* the seed after setup_seed */
+    uint32_t stitched;
+} jh_turb_plan;
+int jh_turbulence_plan(const jh_turbulence_desc* desc, jh_turb_plan* plan);
+int jh_turbulence_tables(const jh_turbulence_desc* desc, uint8_t* selector /* 256 or NULL */, float* gradients /* 2048 or NULL */);
+int jh_turbulence(jh_ctx* ctx, uint64_t dst_image_id, const jh_turbulence_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -849,6 +849,82 @@ func (e *Engine) Lighting(src, dst renderer.ImageProxy, desc LightingDesc) {
 	e.check(C.jh_lighting(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "lighting")
 }
 
+// TurbulenceKind is jh_turbulence_kind: feTurbulence's type.
+type TurbulenceKind int32
+
+const (
+	TurbulenceFractalNoise TurbulenceKind = 0
+	TurbulenceTurbulence   TurbulenceKind = 1
+)
+
+// TurbulenceDesc is jh_turbulence_desc (include/jello_hip.h "Turbulence"): the kind, BaseFrequency in cells per texel (>= 0), Octaves
+// 0 .. 16, the Seed, Stitch with its Tile (x, y, w, h; read only under Stitch), Origin: the coordinate of the image's corner -- texel
+// (X, Y) is the noise at (Origin[0] + X + 0.5, Origin[1] + Y + 0.5) --, and the rectangle of dst that is written (Width == Height ==
+// 0: the whole image).
+type TurbulenceDesc struct {
+	Kind                TurbulenceKind
+	Octaves             uint32
+	Seed                int32
+	Stitch              bool
+	X, Y, Width, Height uint32
+	BaseFrequency       [2]float64
+	Tile                [4]float64
+	Origin              [2]float64
+}
+
+// TurbPlan is jh_turb_plan: what the device is given of a TurbulenceDesc -- the frequency after the stitch adjustment, the int64
+// positions in units of 2^-32 cell, the stitch pair, the largest legal image extent and the key of the tables.
+type TurbPlan struct {
+	Frequency   [2]float64
+	Step, Start [2]int64
+	Wrap, Width [2]int32
+	MaxExtent   [2]uint32
+	Key         uint32
+	Stitched    bool
+}
+
+func (desc TurbulenceDesc) c() C.jh_turbulence_desc {
+	d := C.jh_turbulence_desc{kind: C.int(desc.Kind), octaves: C.uint32_t(desc.Octaves), seed: C.int32_t(desc.Seed), x: C.uint32_t(desc.X),
+		y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height)}
+	if desc.Stitch {
+		d.stitch = 1
+	}
+	for i := 0; i < 2; i++ {
+		d.base_frequency[i] = C.double(desc.BaseFrequency[i])
+		d.origin[i] = C.double(desc.Origin[i])
+	}
+	for i := 0; i < 4; i++ {
+		d.tile[i] = C.double(desc.Tile[i])
+	}
+	return d
+}
+
+// TurbulencePlan is jh_turbulence_plan: the plan of desc -- with the tables the only place binary64 appears in the turbulence rule.
+// Host only.
+func TurbulencePlan(desc TurbulenceDesc) (TurbPlan, error) {
+	d := desc.c()
+	var p C.jh_turb_plan
+	if C.jh_turbulence_plan(&d, &p) != 0 {
+		return TurbPlan{}, fmt.Errorf("hip_engine: TurbulencePlan: a descriptor the rule refuses")
+	}
+	var out TurbPlan
+	for i := 0; i < 2; i++ {
+		out.Frequency[i], out.Step[i], out.Start[i] = float64(p.frequency[i]), int64(p.step[i]), int64(p.start[i])
+		out.Wrap[i], out.Width[i], out.MaxExtent[i] = int32(p.wrap[i]), int32(p.width[i]), uint32(p.max_extent[i])
+	}
+	out.Key, out.Stitched = uint32(p.key), p.stitched != 0
+	return out, nil
+}
+
+// Turbulence is jh_turbulence: feTurbulence -- Perlin turbulence or fractal noise, all four channels, straight colour -- GENERATED into
+// the RGBA16F image dst by the rule of DESIGN.md 5.15 (defined on values: every implementation gives the same bits).  Stream-ordered
+// behind the frame, waits for nothing, one kernel launch.  The context holds the tables of one seed: a call with another uploads its
+// own (8.4 KB) and makes graphs captured before it stale.
+func (e *Engine) Turbulence(dst renderer.ImageProxy, desc TurbulenceDesc) {
+	d := desc.c()
+	e.check(C.jh_turbulence(e.ctx, C.uint64_t(dst.ID), &d), "turbulence")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

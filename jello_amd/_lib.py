@@ -200,6 +200,19 @@ class CLightPlan(ctypes.Structure):
                 ("cone", ctypes.c_float)]
 
 
+class CTurbulenceDesc(ctypes.Structure):
+    """jh_turbulence_desc (include/jello_hip.h)."""
+    _fields_ = [("kind", ctypes.c_int32), ("octaves", ctypes.c_uint32), ("seed", ctypes.c_int32), ("stitch", ctypes.c_int32), ("x", ctypes.c_uint32),
+                ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("base_frequency", ctypes.c_double * 2),
+                ("tile", ctypes.c_double * 4), ("origin", ctypes.c_double * 2)]
+
+
+class CTurbPlan(ctypes.Structure):
+    """jh_turb_plan (include/jello_hip.h)."""
+    _fields_ = [("frequency", ctypes.c_double * 2), ("step", ctypes.c_int64 * 2), ("start", ctypes.c_int64 * 2), ("wrap", ctypes.c_int32 * 2),
+                ("width", ctypes.c_int32 * 2), ("max_extent", ctypes.c_uint32 * 2), ("key", ctypes.c_uint32), ("stitched", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -275,6 +288,8 @@ def _declare(L):
     L.jl_convolve_weights.argtypes = [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
     L.jl_lighting_plan.argtypes = [ctypes.POINTER(CLightingDesc), ctypes.POINTER(CLightPlan)]
     L.jl_lighting_tables.argtypes = [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)]
+    L.jl_turbulence_plan.argtypes = [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)]
+    L.jl_turbulence_tables.argtypes = [ctypes.POINTER(CTurbulenceDesc), vp, vp]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -327,6 +342,9 @@ def _declare(L):
     hip.jh_lighting.argtypes = [vp, u64, u64, ctypes.POINTER(CLightingDesc)]
     hip.jh_lighting_plan.argtypes = [ctypes.POINTER(CLightingDesc), ctypes.POINTER(CLightPlan)]
     hip.jh_lighting_tables.argtypes = [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)]
+    hip.jh_turbulence.argtypes = [vp, u64, ctypes.POINTER(CTurbulenceDesc)]
+    hip.jh_turbulence_plan.argtypes = [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)]
+    hip.jh_turbulence_tables.argtypes = [ctypes.POINTER(CTurbulenceDesc), vp, vp]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -28,6 +28,7 @@
 #include "../../include/jello_warp.h"
 #include "../../include/jello_convolve.h"
 #include "../../include/jello_lighting.h"
+#include "../../include/jello_turbulence.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -152,6 +153,12 @@ struct jh_ctx {
         jlight_key key = {};
         const char* dev = nullptr;
     } light;
+    // jh_turbulence: the key (the seed after setup_seed) whose tables the JH_SCR_TURB_TABLES slot holds, and where
+    struct {
+        bool valid = false;
+        uint32_t key = 0;
+        const char* dev = nullptr;
+    } turb;
 };
 
 static int flush_held(jh_ctx* ctx);
@@ -1161,7 +1168,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1257,6 +1264,14 @@ static int image_call_images(jh_ctx* ctx, const char* who, const void* desc, uin
     if (!desc) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": null descriptor");
     if (int rc = rgba16f_images(ctx, who, {{src_id, "source", src}, {dst_id, "destination", dst}}, size)) return rc;
     if (in_place && *src == *dst) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": the source is the destination (" + in_place + ")");
+    if (ctx->band_row0 == 0u && ctx->band_row1 == 0xffffffffu) return JH_OK;
+    return fail(ctx, JH_ERR_INVALID, std::string(who) + ": not in band mode (" + band_rows + ")");
+}
+// What a call that only writes one RGBA16F image (jh_turbulence generates) checks first: the same, for one image.
+static int image_call_image(jh_ctx* ctx, const char* who, const void* desc, uint64_t dst_id, const char* band_rows, Alloc** dst) {
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, std::string(who) + ": null descriptor");
+    if (int rc = rgba16f_images(ctx, who, {{dst_id, "destination", dst}})) return rc;
     if (ctx->band_row0 == 0u && ctx->band_row1 == 0xffffffffu) return JH_OK;
     return fail(ctx, JH_ERR_INVALID, std::string(who) + ": not in band mode (" + band_rows + ")");
 }
@@ -1822,6 +1837,47 @@ int jh_lighting(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const
         });
 }
 
+// turbulence (include/jello_hip.h "Turbulence"; the descriptor, the generator, the tables, the plan and the key: include/jello_turbulence.h; kernels_turbulence.hip)
+int jh_turbulence_plan(const jh_turbulence_desc* desc, jh_turb_plan* plan) {
+    if (!desc || !plan) return JH_ERR_INVALID;
+    return jturb_plan(desc, plan) ? JH_ERR_INVALID : JH_OK;
+}
+int jh_turbulence_tables(const jh_turbulence_desc* desc, uint8_t* selector, float* gradients) {
+    if (!desc || jturb_desc_error(desc)) return JH_ERR_INVALID;
+    jturb_tables(desc->seed, selector, gradients);
+    return JH_OK;
+}
+int jh_turbulence(jh_ctx* ctx, uint64_t dst_image_id, const jh_turbulence_desc* desc) {
+    static_assert(JH_TURBULENCE_FRACTAL_NOISE == JTURB_FRACTAL_NOISE && JH_TURBULENCE_TURBULENCE == JTURB_TURBULENCE && JH_TURBULENCE_MAX_OCTAVES == JTURB_MAX_OCTAVES,
+                  "the C ABI's values are the rule's");
+    Alloc* dst = nullptr;
+    if (int rc = image_call_image(ctx, "jh_turbulence", desc, dst_image_id, "a band's rows are one rank's, the tables and their key the context's", &dst)) return rc;
+    jh_turb_plan plan;
+    if (const char* why = jturb_plan(desc, &plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_turbulence: ") + why);
+    if (dst->width > plan.max_extent[0] || dst->height > plan.max_extent[1])
+        return fail(ctx, JH_ERR_INVALID, "jh_turbulence: the image reaches beyond the position range of this many octaves (max_extent of the plan)");
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_turbulence", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    ResidentTables tables = {ctx->turb.valid && ctx->turb.key == plan.key, {}};
+    std::vector<char> blob;
+    if (tables.to_build(ctx)) {
+        uint8_t P[256];
+        std::vector<float> G(JTURB_GRADIENT_FLOATS);
+        jturb_tables(desc->seed, P, G.data());
+        blob.assign(JTURB_DEVICE_BYTES, 0);
+        jturb_device_tables(P, G.data(), blob.data());
+    }
+    return post_render_call(
+        ctx, "turbulence", [&] { return tables_take(ctx, "jh_turbulence", "run this turbulence once eagerly first", JH_SCR_TURB_TABLES, blob, &tables); },
+        [&] {
+            if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
+            if (int rc = tables_send(ctx, tables, &ctx->turb.valid, [&](const char* dev) { ctx->turb.key = plan.key; ctx->turb.dev = dev; })) return rc;
+            return launch_status(ctx, "jh_turbulence",
+                                 jh_turbulence_launch(ctx->stream, {dst->ptr, dst->width, dst->height}, r, desc->kind, desc->octaves, &plan, ctx->turb.dev, ctx->num_cus));
+        });
+}
+
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.
 int jh_debug_unpack_rejects(jh_ctx* ctx, uint32_t* count, int reset) {
     if (!ctx || !ctx->hint_overflow) return JH_ERR_INVALID;
@@ -1865,7 +1921,7 @@ int jh_debug_poison_scratch(jh_ctx* ctx, int byte) {
     JH_FLUSH(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (int i = 0; i < JH_SCR_COUNT; i++) {
-        if (i == JH_SCR_RESAMPLE_TAPS || i == JH_SCR_COLOR_TABLES || i == JH_SCR_LIGHT_TABLES) continue;  // (uploaded content a captured jh_resample / jh_color_filter / jh_lighting reads, not an array a frame fills before it reads it)
+        if (i == JH_SCR_RESAMPLE_TAPS || i == JH_SCR_COLOR_TABLES || i == JH_SCR_LIGHT_TABLES || i == JH_SCR_TURB_TABLES) continue;  // (uploaded content a captured jh_resample / jh_color_filter / jh_lighting / jh_turbulence reads, not an array a frame fills before it reads it)
         if (ctx->scratch.ptr[i] && ctx->scratch.cap[i]) HIP_TRY(ctx, hipMemsetAsync(ctx->scratch.ptr[i], byte, ctx->scratch.cap[i], ctx->stream));
     }
     ctx->scratch.clean_flags = 0u;
@@ -1933,6 +1989,7 @@ int jh_scratch_trim(jh_ctx* ctx) {
     ctx->resample.valid = false;   // (jh_resample's tables went with their slot)
     ctx->color.valid = false;      // (jh_color_filter's likewise)
     ctx->light.valid = false;      // (jh_lighting's likewise)
+    ctx->turb.valid = false;       // (jh_turbulence's likewise)
     ctx->generation++;
     return JH_OK;
 }

@@ -237,6 +237,8 @@ struct JhImageDesc {
 //              4 x 65 536 f16 bit patterns, 1.25 MB; a call that needs no tables does not touch the slot)
 //   LIGHT_TABLES   (jh_lighting, the contract of COLOR_TABLES: the uploaded power tables of ONE key, 4097 floats for the specular
 //              exponent then 4097 for the spot exponent, 32.8 KB; a call that needs no table does not touch the slot)
+//   TURB_TABLES    (jh_turbulence, the same contract: the uploaded tables of ONE seed as the kernel reads them, 2048 floats of
+//              gradients laid out [lattice value][channel][2] then the 256 bytes of the selector, 8.25 KB)
 //   MORPH     (jh_morphology, as BLUR: the two planes of order keys between its three passes, each (rect height + 2 radius_y) x
 //              rect width x 16 B; it only grows and nothing else writes it, so a captured call stays valid)
 enum {
@@ -260,7 +262,8 @@ enum {
     JH_SCR_COLOR_TABLES = 17,   // jh_color_filter's tables
     JH_SCR_MORPH = 18,          // jh_morphology's intermediate planes
     JH_SCR_LIGHT_TABLES = 19,   // jh_lighting's tables
-    JH_SCR_COUNT = 20
+    JH_SCR_TURB_TABLES = 20,    // jh_turbulence's tables
+    JH_SCR_COUNT = 21
 };
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
@@ -358,7 +361,7 @@ struct JhResampleTables {
     uint32_t region_x;          // float4 slots of LDS a wave of the row pass needs: jh_resample_skew(longest span - 1) + 1
 };
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _turbulence, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses (an image launcher, which takes the views and resolved
 // rectangles of include/jello_image.h: a rectangle that is not inside its image), another negative value (-2) for a failed launch.
@@ -390,6 +393,9 @@ int jh_convolve_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimag
 struct jh_light_plan;  // include/jello_hip.h
 int jh_lighting_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect rect, int kind, int light, const jh_light_plan* plan,
                        float surface_scale, float constant, const float* color, const float* spec_table, const float* spot_table, int num_cus);
+struct jh_turb_plan;  // include/jello_hip.h
+int jh_turbulence_launch(hipStream_t stream, jimage_dst dst, jimage_rect rect, int kind, uint32_t octaves, const jh_turb_plan* plan, const void* tables,
+                         int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

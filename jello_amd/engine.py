@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CLightingDesc, CLightPlan, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CWarpDesc, CYuvDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CLightingDesc, CLightPlan, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CTurbPlan, CTurbulenceDesc, CWarpDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -341,6 +341,61 @@ def lighting_tables(twin=False, **keywords):
         raise ValueError("jh_lighting: illegal descriptor")
     w = which.value
     return (spec if w & LIGHTING_TABLE_SPEC else None, spot if w & LIGHTING_TABLE_SPOT else None, w)
+
+
+class TurbulenceKind(enum.IntEnum):
+    """jh_turbulence_kind: feTurbulence's type."""
+    FRACTAL_NOISE = 0
+    TURBULENCE = 1
+
+
+TURBULENCE_MAX_OCTAVES = 16  # JH_TURBULENCE_MAX_OCTAVES
+
+
+def _pair(v, what):
+    v = (v, v) if isinstance(v, (int, float)) else tuple(v)
+    if len(v) != 2:
+        raise ValueError("jh_turbulence: %s has two components" % what)
+    return float(v[0]), float(v[1])
+
+
+def _turbulence_desc(base_frequency=0.0, octaves=1, seed=0, kind=TurbulenceKind.TURBULENCE, stitch_tile=None, origin=(0.0, 0.0), rect=None):
+    """jh_turbulence_desc.  What the rule refuses is left for the call to refuse."""
+    d = CTurbulenceDesc()
+    d.kind, d.octaves, d.seed, d.stitch = int(kind), int(octaves), int(seed), 0 if stitch_tile is None else 1
+    d.x, d.y, d.width, d.height = _rect(rect)
+    d.base_frequency[:] = _pair(base_frequency, "base_frequency")
+    if stitch_tile is not None:
+        tile = tuple(float(c) for c in stitch_tile)
+        if len(tile) != 4:
+            raise ValueError("jh_turbulence: stitch_tile has four components (x, y, width, height)")
+        d.tile[:] = tile
+    d.origin[:] = _pair(origin, "origin")
+    return d
+
+
+def turbulence_plan(twin=False, **keywords):
+    """jh_turbulence_plan (twin: jl_turbulence_plan, the host twin): the plan of the turbulence rule for the keywords of
+    Engine.turbulence -- dict(frequency=float64 (2,), step, start = int64 (2,), wrap, width = int32 (2,), max_extent = uint32 (2,), key,
+    stitched).  No GPU needed.  ValueError for a descriptor the rule refuses."""
+    L = _lib.load_host()
+    d, plan = _turbulence_desc(**keywords), CTurbPlan()
+    if (L.jl_turbulence_plan if twin else L.hip.jh_turbulence_plan)(ctypes.byref(d), ctypes.byref(plan)) != 0:
+        raise ValueError("jh_turbulence: illegal descriptor")
+    return dict(frequency=np.array(plan.frequency, np.float64), step=np.array(plan.step, np.int64), start=np.array(plan.start, np.int64),
+                wrap=np.array(plan.wrap, np.int32), width=np.array(plan.width, np.int32), max_extent=np.array(plan.max_extent, np.uint32),
+                key=int(plan.key), stitched=int(plan.stitched))
+
+
+def turbulence_tables(twin=False, **keywords):
+    """jh_turbulence_tables (twin: jl_turbulence_tables): (selector, gradients) -- P, uint8 [256], and G, float32 [4][256][2], of the seed
+    among the keywords of Engine.turbulence.  No GPU needed.  ValueError as turbulence_plan."""
+    L = _lib.load_host()
+    d = _turbulence_desc(**keywords)
+    selector, gradients = np.zeros(256, np.uint8), np.zeros((4, 256, 2), np.float32)
+    if (L.jl_turbulence_tables if twin else L.hip.jh_turbulence_tables)(ctypes.byref(d), selector.ctypes.data, gradients.ctypes.data) != 0:
+        raise ValueError("jh_turbulence: illegal descriptor")
+    return selector, gradients
 
 
 class ColorSpace(enum.IntEnum):
@@ -797,6 +852,25 @@ class Engine:
         self.composite(layer_id, target_id)
         self.composite(scratch_b, target_id, compose=Compose.Plus)
 
+    def turbulence(self, dst_id, base_frequency, octaves=1, seed=0, kind=TurbulenceKind.TURBULENCE, stitch_tile=None, origin=(0.0, 0.0), rect=None):
+        """jh_turbulence: feTurbulence (the rule: DESIGN.md 5.15) GENERATED into the RGBA16F image `dst_id` -- Perlin turbulence or, with
+        `kind` = TurbulenceKind.FRACTAL_NOISE, fractal noise, all four channels, straight colour.  `base_frequency`: cells per texel, one
+        number or (x, y), >= 0; `octaves` 0 .. 16; `seed` an int32; `stitch_tile` = (x, y, width, height) turns stitchTiles on for
+        that tile (None: off); `origin` = (x, y): the coordinate of the image's corner -- texel (X, Y) is the noise at (origin.x + X +
+        0.5, origin.y + Y + 0.5), so images with adjoining origins continue one field; `rect` = (x, y, width, height), the rectangle
+        that is written (None: the whole image).  The context holds the tables of one seed: a call with another uploads its own (8.4
+        KB) and makes graphs captured before it stale.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _turbulence_desc(base_frequency, octaves, seed, kind, stitch_tile, origin, rect)
+        self._check(self.hip.jh_turbulence(self.ctx, dst_id, ctypes.byref(d)), "turbulence", invalid=ValueError)
+
+    def lit_noise(self, dst_id, scratch_id, light, base_frequency=0.05, octaves=4, seed=0, kind=TurbulenceKind.TURBULENCE, stitch_tile=None,
+                  origin=(0.0, 0.0), surface_scale=5.0, kd=1.0, color=(1.0, 1.0, 1.0)):
+        """The specification's textured surface (lit paper, stone, cloth) as two calls on RGBA16F images of one size: turbulence into
+        `scratch_id`, then lighting(scratch -> dst, DIFFUSE, **light) of the scratch's alpha -- `light` the keywords of lighting.distant /
+        point / spot, `color` linear.  The two images are distinct; `dst_id` ends opaque."""
+        self.turbulence(scratch_id, base_frequency, octaves, seed, kind, stitch_tile, origin)
+        self.lighting(scratch_id, dst_id, kind=LightKind.DIFFUSE, surface_scale=surface_scale, constant=kd, color=color, **light)
+
     def place_layer(self, layer_id, target_id, matrix, scratch_image_id, layer_size, target_size, filter=WarpFilter.BILINEAR, **composite_keywords):
         """A cached layer onto a target under an affine transform, two calls: warp(layer -> scratch, edge ZERO, dst_rect =
         warp_bounds(...)): the layer in target space, written only where it can be other than transparent black;
@@ -947,7 +1021,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None, convolve=None, lighting=None):
+                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -982,13 +1056,19 @@ class Engine:
         image `dst` of the target's size after the color filter and BEFORE the convolve (one more launch); lighting whose exponents
         need tables must have run once eagerly, and no other such since.  The later steps -- convolve, resample or warp, the
         conversion -- then read `dst`.  So the order of a capture is: render, morphology, blur, composite, color, lighting, convolve,
-        resample or warp, then the surface, YUV or pack conversion."""
+        resample or warp, then the surface, YUV or pack conversion.
+        turbulence=dict(dst=image id, ...) (the other keywords of turbulence(), `base_frequency` among them) generates noise into the
+        RGBA16F image `dst` right after the frame and before every other step (one more launch), so that composite=dict(src=dst, ...)
+        of the same capture can lay it over the frame; the frame's target stays what the later steps read.  Turbulence with this seed
+        must have run once eagerly, and none with another seed since."""
         if resample is not None and warp is not None:
             raise ValueError("capture: resample= and warp= are exclusive (both would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
             t = recording.target
+            if turbulence is not None:
+                self.turbulence(turbulence["dst"], **{k: v for k, v in turbulence.items() if k != "dst"})
             if morphology is not None:
                 self.morphology(t["id"], **morphology)
             if blur is not None:

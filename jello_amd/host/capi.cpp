@@ -13,6 +13,7 @@
 #include "../../include/jello_warp.h"
 #include "../../include/jello_convolve.h"
 #include "../../include/jello_lighting.h"
+#include "../../include/jello_turbulence.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -511,6 +512,21 @@ int jl_lighting_tables(const jh_lighting_desc* desc, float* spec_table, float* s
     if (why) { g_err = std::string("lighting_tables: ") + why; return -1; }
     const uint32_t w = jlight_tables(desc, spec_table, spot_table);
     if (which) *which = w;
+    return 0;
+}
+
+// jl_turbulence_plan and jl_turbulence_tables are the host twins of jh_turbulence_plan and jh_turbulence_tables (the rule is in
+// jello_hip.h and DESIGN.md 5.15): the same header, compiled here by the host compiler -- the plan of desc; the tables of its seed, the
+// selector (256 bytes; or null) and the gradients G[4][256][2] (2048 floats; or null); -1 for a descriptor the rule refuses.
+int jl_turbulence_plan(const jh_turbulence_desc* desc, jh_turb_plan* plan) {
+    const char* why = desc && plan ? jturb_plan(desc, plan) : "null argument";
+    if (why) { g_err = std::string("turbulence_plan: ") + why; return -1; }
+    return 0;
+}
+int jl_turbulence_tables(const jh_turbulence_desc* desc, uint8_t* selector, float* gradients) {
+    const char* why = desc ? jturb_desc_error(desc) : "null descriptor";
+    if (why) { g_err = std::string("turbulence_tables: ") + why; return -1; }
+    jturb_tables(desc->seed, selector, gradients);
     return 0;
 }
 
