@@ -201,7 +201,10 @@ RenderConfig new_render_config(const JlLayout& layout, uint32_t width, uint32_t 
 // ramp_cache.go.  color.Step (honnef.co/go/color, un-vendored) interpolates in sRGB and converts
 // to linear sRGB; its sampling positions are not visible from the reference tree.  Own definition:
 // n samples at t = i/(n-1), interpolated per channel in gamma-encoded sRGB (alpha linearly),
-// decoded to linear, premultiplied, stored as RTNE binary16.  PARITY UNPINNED for ramp texels.
+// decoded to linear, premultiplied, rounded to binary32 (RTNE) and stored as binary16 by jmath.Float16bits, as
+// gfx/color.go does: nearest, an exact tie AWAY from zero.  Held bit for bit, with the sample counts below (a stop
+// prepended at 0, round-half-away counts capped by what remains, the last segment the rest, none skipped, one = the
+// later stop), by tests/exact_paint.py's restatement in tests/test_paint_spec.py.
 // ------------------------------------------------------------------------------------------------
 static const uint32_t kNumSamples = 512, kRetainedCount = 64;
 
@@ -263,14 +266,18 @@ static std::vector<uint16_t> make_ramp(const ColorStop* stops_in, size_t n_in) {
     return out;
 }
 
-void Resolver::ramp_maintain() {  // ramp_cache.go:42-52
+// Deviation from ramp_cache.go:42-52, which trims only when the mapping holds more than kRetainedCount entries.  add
+// never lets it: with the cache full and no stale entry it appends a row WITHOUT a mapping entry (ramp_add's last
+// lines), so that test never held and the ramp image, and every frame's upload, kept the overflow rows of every frame.
+// Here the rows past the retained ones go at the start of each frame, whether or not the mapping overflowed: an
+// overflow row's id is valid within its frame only, which is all the frame's patches need.  No mapping entry has such
+// an id (an entry is made only while rows and entries are equal in number, below kRetainedCount, or takes over a
+// retained row), so there is nothing to erase there.  Ids and bytes are the reference's until a Host's cache first
+// overflows; after that only the ids of overflow rows differ: they start at kRetainedCount in every frame.
+void Resolver::ramp_maintain() {
     epoch_++;
-    if (mapping_.size() > kRetainedCount) {
-        for (auto it = mapping_.begin(); it != mapping_.end();) {
-            if (it->second.id >= kRetainedCount) it = mapping_.erase(it); else ++it;
-        }
-        ramp_data_.resize((size_t)kRetainedCount * kNumSamples * 4);
-    }
+    const size_t retained = (size_t)kRetainedCount * kNumSamples * 4;
+    if (ramp_data_.size() > retained) ramp_data_.resize(retained);
 }
 
 uint32_t Resolver::ramp_add(const ColorStop* stops, size_t n) {  // ramp_cache.go:54-109
