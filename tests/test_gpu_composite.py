@@ -6,25 +6,17 @@ import ctypes
 import numpy as np
 import pytest
 
-import jello_amd
-from jello_amd import BlurEdge, Brush, Cap, Compose, Fill, ImageFormat, Join, Mix, Path, RenderParams, Scene, Stroke, Surface
+from jello_amd import Compose, ImageFormat, Mix
 from jello_amd._lib import CCompositeDesc
-from jello_amd.engine import JH_ERR_INVALID, RUN_DISPATCHES, RUN_UPLOADS
 
 import blur_ref
 import composite_cases
 import composite_ref
-import surface_ref
-from devmem import CANARY, DevBuf, Image, _id, target_of
+from devmem import DevBuf, Image, _id, target_of
+from image_call import (assert_same_bits, canary_bits, captured_with_the_frame, check_refusals, common_refusals, images, one_query,
+                        run_case, scene)
 
 pytestmark = pytest.mark.gpu
-
-
-
-def _differences(got, want):
-    bad = np.argwhere(got != want)
-    return "%d of %d values differ, first at (y, x, ch) = %s: got %#06x, want %#06x" % (
-        len(bad), got.size, tuple(int(v) for v in bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
 
 
 @pytest.mark.parametrize("name", [c["name"] for c in composite_cases.CASES])
@@ -34,18 +26,9 @@ def test_battery(engine, name):
     in this rule the sign of a zero that min / max return cannot reach a stored value, so they hold the orderings of equal
     channels, not the device's ordering of zeros: test_the_devices_min_and_max_are_the_rules asks that directly.)"""
     c = composite_cases.BY_NAME[name]
-    src_bits, dst_bits = composite_cases.source(c), composite_cases.destination(c)
-    src, dst = Image(engine, src_bits), Image(engine, dst_bits)
-    try:
-        engine.composite(src.id, dst.id, Mix(c["mix"]), Compose(c["compose"]), c["opacity"], c["tint"], c["src_rect"], c["offset"])
-        got = dst.bits()
-        assert np.array_equal(src.bits(), src_bits)  # the source is only read
-    finally:
-        src.free()
-        dst.free()
-    want = composite_cases.expected(name)
-    if not composite_ref.same_bits(got, want):
-        pytest.fail("%s: %s" % (name, _differences(got, want)))
+    call = lambda src, dst: engine.composite(src.id, dst.id, Mix(c["mix"]), Compose(c["compose"]), c["opacity"], c["tint"], c["src_rect"], c["offset"])  # noqa: E731
+    got = run_case(engine, c, call, composite_cases.source(c), composite_cases.destination(c))
+    assert_same_bits(got, composite_cases.expected(name), name)
 
 
 def test_the_devices_min_and_max_are_the_rules(engine):
@@ -71,15 +54,11 @@ def test_a_never_written_destination_is_cleared_outside_the_rectangle(engine):
     """... and is the transparent backdrop inside it; placed over the whole of dst nothing has to be cleared first."""
     bits = composite_cases.unit(21, 9, seed=3)
     for size, offset in (((33, 21), (5, 4)), ((33, 21), (-3, 17)), ((21, 9), (0, 0)), ((20, 8), (-1, -1))):
-        src, dst = Image(engine, bits), Image(engine, None, size[0], size[1])
-        try:
+        with images(engine, bits, size) as (src, dst):
             engine.composite(src.id, dst.id, Mix.Multiply, Compose.SrcOver, 0.75, offset=offset)
             got = dst.bits()
-        finally:
-            src.free()
-            dst.free()
         want = composite_ref.composite(bits, None, Mix.Multiply, Compose.SrcOver, 0.75, offset=offset, dst_shape=(size[1], size[0]))
-        assert composite_ref.same_bits(got, want), (size, offset, _differences(got, want))
+        assert_same_bits(got, want, (size, offset))
 
 
 def test_a_never_written_source_is_transparent_black(engine):
@@ -87,173 +66,87 @@ def test_a_never_written_source_is_transparent_black(engine):
     erases the rectangle, and a tint colours nothing: the alpha it scales is 0."""
     bits = composite_cases.unit(40, 11, seed=4)
     for mix, compose, tint in ((Mix.Normal, Compose.SrcOver, None), (Mix.Normal, Compose.SrcIn, None), (Mix.Screen, Compose.Xor, (0.5, 0.25, 1.0, 1.0))):
-        src, dst = Image(engine, None, 17, 6), Image(engine, bits)
-        try:
+        with images(engine, (17, 6), bits) as (src, dst):
             engine.composite(src.id, dst.id, mix, compose, tint=tint, offset=(3, 2))
             got = dst.bits()
-        finally:
-            src.free()
-            dst.free()
         want = composite_ref.composite(np.zeros((6, 17, 4), np.uint16), bits, mix, compose, tint=tint, offset=(3, 2))
-        assert composite_ref.same_bits(got, want), (mix, compose, _differences(got, want))
-
-
-def _scene():
-    s = Scene()
-    s.fill(Fill.NonZero, None, Brush.solid((0.9, 0.4, 0.1, 1.0)), None, Path.circle(24, 20, 13))
-    curve = Path().move_to(6, 40).cubic_to(20, 2, 44, 46, 58, 8)
-    s.stroke(Stroke(3, Join.Round, 4, Cap.Round, Cap.Round), None, Brush.solid((0.1, 0.3, 0.9, 0.8)), None, curve)
-    return s, RenderParams(64, 48)
+        assert_same_bits(got, want, (mix, compose))
 
 
 def test_drop_shadow_of_a_rendered_frame(engine):
     """A rendered 64 x 48 frame (a circle and a stroked curve) as the layer: Engine.drop_shadow onto an 80 x 60 target =
     blur_ref, then composite_ref with the tint and the offset, then composite_ref of the layer itself."""
-    s, p = _scene()
-    rec, _, _ = engine.render(s, p)
+    rec, _, _ = engine.render(*scene((64, 48), 3))
     layer = target_of(engine, rec)
     assert layer.any()
     backdrop = composite_cases.unit(80, 60, seed=5)
     sigma, offset, color = (2.0, 3.5), (7, 5), (0.05, 0.0, 0.1, 0.6)
-    target, scratch = Image(engine, backdrop), Image(engine, None, 64, 48)
-    try:
+    with images(engine, backdrop, (64, 48)) as (target, scratch):
         engine.drop_shadow(rec.target["id"], target.id, 64, 48, sigma, offset, color, scratch.id)
         got, blurred = target.bits(), scratch.bits()
         assert np.array_equal(target_of(engine, rec), layer)
-    finally:
-        target.free()
-        scratch.free()
     shadow = blur_ref.blur(layer, sigma, blur_ref.ZERO)
     assert blur_ref.same_bits(blurred, shadow)
     want = composite_ref.composite(layer, composite_ref.composite(shadow, backdrop, tint=color, offset=offset))
-    assert composite_ref.same_bits(got, want), _differences(got, want)
+    assert_same_bits(got, want, "drop shadow")
     assert (want != composite_ref.composite(layer, backdrop)).any()  # (the shadow shows)
 
 
 def test_captured_with_the_frame(engine):
     """capture(composite=..., surface=...): render, composite an overlay onto the target, blit -- two more kernel launches than the
-    plain capture; replayed twice, the bytes of the eager calls."""
-    s, p = _scene()
-    fmt = Surface.RGBA8_SRGB
+    plain capture (the composite, the blit); replayed twice, the bytes of the eager calls."""
     what = dict(mix=Mix.Screen, compose=Compose.SrcAtop, opacity=0.625, src_rect=(3, 2, 30, 20), offset=(-5, 33))
-    rec = jello_amd.Host().record(s, p)
     overlay_bits = composite_cases.unit(41, 29, seed=6)
-    overlay, surf = Image(engine, overlay_bits), DevBuf(engine, 64 * 48 * 4)
-    g = None
-    try:
-        engine.run(rec, RUN_UPLOADS | RUN_DISPATCHES)
-        t = rec.target
-        plain = target_of(engine, rec)
-        engine.composite(overlay.id, t["id"], **what)
-        engine.blit(t["id"], 64, 48, fmt, out_device_ptr=surf.ptr)
-        eager = surf.bytes().reshape(48, 64, 4)
-        composed = composite_ref.composite(overlay_bits, plain, **what)
-        assert (composed != plain).any()
-        assert composite_ref.same_bits(target_of(engine, rec), composed)
-        assert np.array_equal(eager, surface_ref.convert(composed, int(fmt)))
-        g0 = engine.capture(rec)
-        g = engine.capture(rec, composite=dict(src=overlay.id, **what), surface=(surf.ptr, 64 * 4, fmt))
-        (k0, o0), (k1, o1) = engine.graph_node_counts(g0), engine.graph_node_counts(g)
-        engine.graph_destroy(g0)
-        assert (k1, o1) == (k0 + 2, o0)  # the composite, the blit
-        for _ in range(2):
-            engine.clear(surf.id)
-            engine.replay(g)
-            engine.sync()
-            assert np.array_equal(surf.bytes().reshape(48, 64, 4), eager)
-    finally:
-        if g is not None:
-            engine.graph_destroy(g)
-        overlay.free()
-        surf.free()
+    with images(engine, overlay_bits) as (overlay,):
+        captured_with_the_frame(engine, scene((64, 48), 3), lambda target, _: engine.composite(overlay.id, target, **what),
+                                lambda _: dict(composite=dict(src=overlay.id, **what)),
+                                lambda plain: composite_ref.composite(overlay_bits, plain, **what), extra_launches=2)
 
 
 def test_refusals(engine):
-    """Every refusal of the header's list: JH_ERR_INVALID, a message that starts "jh_composite: ", no texel of either image touched."""
+    """Every refusal of the header's list: JH_ERR_INVALID, a message that starts "jh_composite: ", no texel of either image and no
+    byte of a canary buffer touched."""
     hip, ctx = engine.hip, engine.ctx
     W, H = 16, 12
-    canary = np.full((H, W, 4), CANARY | (CANARY << 8), np.uint16)
-    src, dst = Image(engine, canary), Image(engine, canary)
-    rgba8 = Image(engine, np.full((H, W, 2), 0x1111, np.uint16), fmt=ImageFormat.RGBA8)  # (W x H texels of 4 bytes)
+    canary = canary_bits(W, H)
     nan, inf = float("nan"), float("inf")
+    with images(engine, canary, canary, (W, H, ImageFormat.RGBA8)) as (src, dst, rgba8):
+        def call(s=None, d=None, null=False, mix=0, compose=0, opacity=1.0, flags=0, tint=(0.0, 0.0, 0.0, 0.0), rect=(0, 0, 0, 0), at=(0, 0)):
+            desc = CCompositeDesc(mix, compose, opacity, flags, (ctypes.c_float * 4)(*tint), rect[0], rect[1], rect[2], rect[3], at[0], at[1])
+            return hip.jh_composite(ctx, src.id if s is None else s, dst.id if d is None else d, None if null else ctypes.byref(desc))
 
-    def call(s=None, d=None, null=False, mix=0, compose=0, opacity=1.0, flags=0, tint=(0.0, 0.0, 0.0, 0.0), rect=(0, 0, 0, 0), at=(0, 0)):
-        desc = CCompositeDesc(mix, compose, opacity, flags, (ctypes.c_float * 4)(*tint), rect[0], rect[1], rect[2], rect[3], at[0], at[1])
-        return hip.jh_composite(ctx, src.id if s is None else s, dst.id if d is None else d, None if null else ctypes.byref(desc))
-
-    refused = {
-        "null descriptor": lambda: call(null=True),
-        "unknown source": lambda: call(s=_id()),
-        "unknown destination": lambda: call(d=_id()),
-        "source not RGBA16F": lambda: call(s=rgba8.id),
-        "destination not RGBA16F": lambda: call(d=rgba8.id),
-        "source is the destination": lambda: call(d=src.id),
-        "mix 16": lambda: call(mix=16),
-        "Mix.Clip": lambda: call(mix=int(Mix.Clip)),
-        "compose 14": lambda: call(compose=14),
-        "opacity negative": lambda: call(opacity=-0.25),
-        "opacity above 1": lambda: call(opacity=1.5),
-        "opacity NaN": lambda: call(opacity=nan),
-        "tint alpha negative": lambda: call(flags=1, tint=(0.5, 0.5, 0.5, -0.5)),
-        "tint alpha above 1": lambda: call(flags=1, tint=(0.5, 0.5, 0.5, 1.25)),
-        "tint alpha NaN": lambda: call(flags=1, tint=(0.5, 0.5, 0.5, nan)),
-        "tint red infinite": lambda: call(flags=1, tint=(inf, 0.5, 0.5, 1.0)),
-        "tint green NaN": lambda: call(flags=1, tint=(0.5, nan, 0.5, 1.0)),
-        "tint blue -infinite": lambda: call(flags=1, tint=(0.5, 0.5, -inf, 1.0)),
-        "flag bit 1": lambda: call(flags=2),
-        "flag bit 31": lambda: call(flags=0x80000001, tint=(0.5, 0.5, 0.5, 1.0)),
-        "rectangle beyond the right edge": lambda: call(rect=(8, 0, 9, 4)),
-        "rectangle beyond the bottom edge": lambda: call(rect=(0, 9, 4, 4)),
-        "rectangle whose end wraps": lambda: call(rect=(0xFFFFFFFF, 0, 2, 2)),
-        "empty in x only": lambda: call(rect=(2, 2, 0, 4)),
-        "empty in y only": lambda: call(rect=(2, 2, 4, 0)),
-    }
-    try:
-        for what, f in refused.items():
-            assert f() == JH_ERR_INVALID, what
-            assert hip.jh_last_error(ctx).startswith(b"jh_composite: "), (what, hip.jh_last_error(ctx))
-        engine.set_band(0, 1)
-        try:
-            assert call() == JH_ERR_INVALID
-            assert hip.jh_last_error(ctx).startswith(b"jh_composite: ") and b"band" in hip.jh_last_error(ctx)
-        finally:
-            engine.set_band()
-        with pytest.raises(ValueError, match="jh_composite: "):
-            engine.composite(src.id, dst.id, opacity=2.0)
-        with pytest.raises(ValueError, match="jh_composite: "):
-            engine.composite(src.id, src.id)
-        assert np.array_equal(src.bits(), canary) and np.array_equal(dst.bits(), canary)  # no refusal touched a texel of either image
-        assert call(at=(W, 0)) == 0 and call(at=(0, -H)) == 0 and call(at=(-2 ** 31, 2 ** 31 - 1)) == 0  # placed outside: accepted, nothing to do
+        refused = dict(common_refusals(call, rgba8, rects=(("", "source ", "rect"),)), **{
+            "source is the destination": (lambda: call(d=src.id), b""),
+            "mix 16": (lambda: call(mix=16), b""),
+            "Mix.Clip": (lambda: call(mix=int(Mix.Clip)), b""),
+            "compose 14": (lambda: call(compose=14), b""),
+            "opacity negative": (lambda: call(opacity=-0.25), b""),
+            "opacity above 1": (lambda: call(opacity=1.5), b""),
+            "opacity NaN": (lambda: call(opacity=nan), b""),
+            "tint alpha negative": (lambda: call(flags=1, tint=(0.5, 0.5, 0.5, -0.5)), b""),
+            "tint alpha above 1": (lambda: call(flags=1, tint=(0.5, 0.5, 0.5, 1.25)), b""),
+            "tint alpha NaN": (lambda: call(flags=1, tint=(0.5, 0.5, 0.5, nan)), b""),
+            "tint red infinite": (lambda: call(flags=1, tint=(inf, 0.5, 0.5, 1.0)), b""),
+            "tint green NaN": (lambda: call(flags=1, tint=(0.5, nan, 0.5, 1.0)), b""),
+            "tint blue -infinite": (lambda: call(flags=1, tint=(0.5, 0.5, -inf, 1.0)), b""),
+            "flag bit 1": (lambda: call(flags=2), b""),
+            "flag bit 31": (lambda: call(flags=0x80000001, tint=(0.5, 0.5, 0.5, 1.0)), b""),
+        })
+        check_refusals(engine, "jh_composite", call, refused, untouched=((src, canary), (dst, canary)),
+                       raises=(lambda: engine.composite(src.id, dst.id, opacity=2.0), lambda: engine.composite(src.id, src.id)),
+                       accepted=(lambda: call(at=(W, 0)), lambda: call(at=(0, -H)), lambda: call(at=(-2 ** 31, 2 ** 31 - 1))))  # placed outside: accepted, nothing to do
         assert np.array_equal(src.bits(), canary) and np.array_equal(dst.bits(), canary)
         assert call(opacity=0.0, tint=(nan, inf, 0.0, 7.0)) == 0  # (the tint is read only with the flag)
         assert np.array_equal(src.bits(), canary)
         assert call(compose=int(Compose.Clear)) == 0  # (and a call with nothing wrong is accepted and does its work)
         assert np.array_equal(src.bits(), canary) and not dst.bits().any()
-    finally:
-        for im in (src, dst, rgba8):
-            im.free()
 
 
 def test_the_call_is_one_query_of_the_tree(engine):
     a, b = composite_cases.unit(48, 33, seed=7), composite_cases.unit(48, 33, seed=8)
-    src, dst = Image(engine, a), Image(engine, b)
-    try:
-        engine.profile(True)
-        try:
-            with engine.profile_group("post"):
-                engine.composite(src.id, dst.id, opacity=0.5)
-            tree = engine.profile_collect_tree()
-            engine.composite(src.id, dst.id, opacity=0.5)
-            flat = engine.profile_collect()
-        finally:
-            engine.profile(False)
+    with images(engine, a, b) as (src, dst):
+        one_query(engine, "composite", lambda: engine.composite(src.id, dst.id, opacity=0.5))
         got = dst.bits()
-    finally:
-        src.free()
-        dst.free()
-    assert [(n["kind"], n["label"], n["parent"], n["stage"]) for n in tree] == [("group", "post", -1, -1), ("query", "composite", 0, -1)]
-    assert tree[1]["gpu_end_ms"] >= tree[1]["gpu_start_ms"]
-    assert flat == []
     once = composite_ref.composite(a, b, opacity=0.5)
     assert composite_ref.same_bits(got, composite_ref.composite(a, once, opacity=0.5))
 

@@ -8,28 +8,26 @@ import numpy as np
 import pytest
 
 import jello_amd
-from jello_amd import Brush, Cap, Compose, Fill, ImageFormat, Join, LightKind, LightSource, Path, RenderParams, Scene, Stroke, Surface, lighting
+from jello_amd import Compose, ImageFormat, LightKind, LightSource, lighting
 from jello_amd._lib import CLightingDesc
-from jello_amd.engine import JH_ERR_INVALID, RUN_DISPATCHES, RUN_UPLOADS, _lighting_desc
+from jello_amd.engine import JH_ERR_INVALID, _lighting_desc
 
 import blur_ref
 import composite_ref
 import lighting_cases
 import lighting_ref
-import surface_ref
-from devmem import CANARY, DevBuf, Image, _id, target_of
+from devmem import target_of
+from image_call import (JH_ERR_OOM, assert_same_bits, canary_bits, captured_call, captured_with_the_frame, check_refusals, common_refusals, images,
+                        one_query, run_case, scene)
 
 pytestmark = pytest.mark.gpu
 
-JH_ERR_OOM = -5
 SLOT = 19  # JH_SCR_LIGHT_TABLES
 TABLE_BYTES = 4097 * 4
 
 
-def _differences(name, got, want):
-    bad = np.argwhere(got != want)
-    return "%s: %d of %d values differ, first at (y, x, ch) = %s: got %#06x, want %#06x" % (
-        name, len(bad), got.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
+def _ref_kw(k):
+    return {n: (int(v) if n in ("kind", "light") else v) for n, v in k.items()}
 
 
 @pytest.mark.parametrize("name", [c["name"] for c in lighting_cases.CASES])
@@ -37,20 +35,9 @@ def test_battery(engine, name):
     """Every case through Engine.lighting: dst is poisoned first (or never written), the whole of dst is compared -- the rectangle
     with the reference, the texels outside it with what they held (a never-written dst: transparent black)."""
     c = lighting_cases.BY_NAME[name]
-    src_bits, prior = lighting_cases.source(c), lighting_cases.before(c)
-    src = Image(engine, None, *c["size"]) if c["kind"] == "never" else Image(engine, src_bits)
-    dst = Image(engine, None, *c["size"]) if prior is None else Image(engine, prior)
-    try:
-        engine.lighting(src.id, dst.id, rect=c["rect"], **c["desc"])
-        got = dst.bits()
-        if c["kind"] != "never":  # (a never-written image reads as zero; its memory holds anything)
-            assert np.array_equal(src.bits(), src_bits)  # the source is only read
-    finally:
-        src.free()
-        dst.free()
-    want = lighting_cases.expected(name)
-    if not lighting_ref.same_bits(got, want):
-        pytest.fail(_differences(name, got, want))
+    call = lambda src, dst: engine.lighting(src.id, dst.id, rect=c["rect"], **c["desc"])  # noqa: E731
+    got = run_case(engine, c, call, lighting_cases.source(c), lighting_cases.before(c), dst_size=c["size"])
+    assert_same_bits(got, lighting_cases.expected(name), name)
 
 
 def test_the_battery_runs_every_instantiation():
@@ -59,58 +46,30 @@ def test_the_battery_runs_every_instantiation():
         "specular/point/1", "specular/spot/0", "specular/spot/1", "specular/spot/2", "specular/spot/3"}
 
 
-def _scene():
-    s = Scene()
-    s.fill(Fill.NonZero, None, Brush.solid((0.9, 0.4, 0.1, 1.0)), None, Path.circle(50, 44, 30))
-    curve = Path().move_to(10, 100).cubic_to(40, 4, 90, 120, 120, 16)
-    s.stroke(Stroke(9, Join.Round, 4, Cap.Round, Cap.Round), None, Brush.solid((0.1, 0.3, 0.9, 0.8)), None, curve)
-    return s, RenderParams(128, 128)
-
-
 @pytest.mark.parametrize("light", ["distant", "point", "spot"])
 def test_bevel_of_a_rendered_frame(engine, light):
     """Engine.bevel on a rendered 128 x 128 frame (a disc and a stroked curve) = blur_ref, lighting_ref and composite_ref composed on
     the download of the same render; the layer itself is untouched and the highlight is there."""
     lt = {"distant": lighting.distant(225, 35), "point": lighting.point(-50, -100, 200), "spot": lighting.spot(20, 10, 60, (64, 64, 0), 8, 40)}[light]
-    s, p = _scene()
-    rec, _, _ = engine.render(s, p)
+    rec, _, _ = engine.render(*scene(stroke=9))
     layer = target_of(engine, rec)
     assert layer.any()
     back = np.zeros((128, 128, 4), np.float16)
     back[...] = (0.1, 0.15, 0.2, 1.0)
     back = back.view(np.uint16)
-    target, a, b = Image(engine, back), Image(engine, None, 128, 128), Image(engine, None, 128, 128)
-    try:
+    with images(engine, back, (128, 128), (128, 128)) as (target, a, b):
         engine.bevel(rec.target["id"], target.id, a.id, b.id, 3.0, lt, (128, 128), surface_scale=5.0, ks=0.75, exponent=20.0)
         got, got_b = target.bits(), b.bits()
-    finally:
-        for im in (target, a, b):
-            im.free()
     blurred = blur_ref.blur(layer, 3.0)
     lit = lighting_ref.lighting(blurred, kind=lighting_ref.SPECULAR, surface_scale=5.0, constant=0.75, specular_exponent=20.0,
                                 **{k: (int(v) if k == "light" else v) for k, v in lt.items()})
     inside = composite_ref.composite(layer, lit, compose=int(Compose.DestIn))
     want = composite_ref.composite(inside, composite_ref.composite(layer, back), compose=int(Compose.Plus))
-    assert lighting_ref.same_bits(got_b, inside), _differences(light + " highlight", got_b, inside)
-    assert lighting_ref.same_bits(got, want), _differences(light, got, want)
+    assert_same_bits(got_b, inside, light + " highlight")
+    assert_same_bits(got, want, light)
     assert np.array_equal(target_of(engine, rec), layer)
     assert inside[..., 3].view(np.float16).max() > 0.05  # there is a highlight
     assert not np.array_equal(got, composite_ref.composite(layer, back))
-
-
-def _captured_call(engine, src, dst, desc, clear_first=None):
-    """jh_lighting between jh_graph_begin and jh_graph_end (after the clear of a buffer, if one is given): (rc, message, graph)."""
-    hip, ctx = engine.hip, engine.ctx
-    engine._check(hip.jh_graph_begin(ctx), "graph_begin")
-    try:
-        if clear_first is not None:
-            engine.clear(clear_first)
-        rc = hip.jh_lighting(ctx, src.id, dst.id, ctypes.byref(desc))
-        msg = hip.jh_last_error(ctx).decode()
-    finally:
-        g = ctypes.c_void_p()
-        engine._check(hip.jh_graph_end(ctx, ctypes.byref(g)), "graph_end")
-    return rc, msg, g
 
 
 def test_captures_and_the_resident_key():
@@ -122,105 +81,78 @@ def test_captures_and_the_resident_key():
     hip, ctx = engine.hip, engine.ctx
     bits = lighting_cases.content("disc", 37, 19, 8)
     poison = np.full((19, 37, 4), lighting_cases.POISON, np.uint16)
-    src, dst, buf = Image(engine, bits), Image(engine, poison), DevBuf(engine, 64)
     plain = dict(lighting.diffuse(4.0, 1.0), **lighting.point(10, 5, 20))
     plain_spot = dict(lighting.specular(4.0, 1.0, 1.0), **lighting.spot(10, 5, 20, (18, 9, 0), 1.0, 50))
     shiny = dict(lighting.specular(4.0, 1.0, 20.0), **lighting.point(10, 5, 20))
     shiny_moved = dict(lighting.specular(2.0, 0.5, 20.0, (1.0, 0.5, 0.25)), **lighting.distant(30, 60))
     both = dict(lighting.specular(4.0, 1.0, 20.0), **lighting.spot(10, 5, 20, (18, 9, 0), 8.0, 50))
-    ref = lambda kw: lighting_ref.lighting(bits, None, poison, **{k: (int(v) if k in ("kind", "light") else v) for k, v in kw.items()})  # noqa: E731
+    ref = lambda kw: lighting_ref.lighting(bits, None, poison, **_ref_kw(kw))  # noqa: E731
+    captured = lambda kw, **more: captured_call(  # noqa: E731
+        engine, lambda: hip.jh_lighting(ctx, src.id, dst.id, ctypes.byref(_lighting_desc(**kw))), **more)
     graphs = []
     try:
-        for kw in (plain, plain_spot):  # no tables: capturable on a fresh context, and the slot stays empty
-            rc, msg, g = _captured_call(engine, src, dst, _lighting_desc(**kw))
-            graphs.append(g)
-            assert rc == 0, msg
-            assert np.array_equal(dst.bits(), poison)  # a capture runs nothing
-            engine.replay(g)
-            assert lighting_ref.same_bits(dst.bits(), ref(kw))
-            assert hip.jh_debug_scratch_bytes(ctx, SLOT) == 0
-            engine.upload_image(dst.id, poison)
-        # a key that is not resident
-        rc, msg, refused = _captured_call(engine, src, dst, _lighting_desc(**shiny), clear_first=buf.id)
-        engine.graph_destroy(refused)
-        assert rc == JH_ERR_OOM and msg.startswith("jh_lighting: ") and "run this lighting once eagerly first" in msg, (rc, msg)
-        assert np.array_equal(dst.bits(), poison) and np.array_equal(src.bits(), bits)
-        engine.lighting(src.id, dst.id, **shiny)
-        assert lighting_ref.same_bits(dst.bits(), ref(shiny))
-        size = hip.jh_debug_scratch_bytes(ctx, SLOT)
-        assert size >= 2 * TABLE_BYTES
-        engine.upload_image(dst.id, poison)
-        rc, msg, g = _captured_call(engine, src, dst, _lighting_desc(**shiny))
-        graphs.append(g)
-        assert rc == 0, msg
-        assert np.array_equal(dst.bits(), poison)
-        engine.replay(g)
-        assert lighting_ref.same_bits(dst.bits(), ref(shiny))
-        # the same key with another light, scale, constant and colour, and calls without tables: nothing is uploaded, the graph stays valid
-        engine.lighting(src.id, dst.id, **shiny_moved)
-        assert lighting_ref.same_bits(dst.bits(), ref(shiny_moved))
-        engine.lighting(src.id, dst.id, **plain)
-        assert hip.jh_debug_scratch_bytes(ctx, SLOT) == size
-        engine.replay(g)
-        assert lighting_ref.same_bits(dst.bits(), ref(shiny))
-        # another key: its tables replace the ones the graph reads
-        engine.lighting(src.id, dst.id, **both)
-        assert hip.jh_graph_launch(ctx, g) == JH_ERR_INVALID
-        assert b"stale" in hip.jh_last_error(ctx)
-        assert lighting_ref.same_bits(dst.bits(), ref(both))
-        engine.lighting(src.id, dst.id, **shiny)  # (and back: the specular exponent alone is another key than both exponents)
-        assert lighting_ref.same_bits(dst.bits(), ref(shiny))
-        # a trim forgets the key: the same lighting is no longer capturable until it has run again
-        engine._check(hip.jh_scratch_trim(ctx), "scratch_trim")
-        rc, msg, refused = _captured_call(engine, src, dst, _lighting_desc(**shiny))
-        engine.graph_destroy(refused)
-        assert rc == JH_ERR_OOM and "run this lighting once eagerly first" in msg
-        engine.lighting(src.id, dst.id, **shiny)
-        assert lighting_ref.same_bits(dst.bits(), ref(shiny))
+        with images(engine, bits, poison, 64) as (src, dst, buf):
+            try:
+                for kw in (plain, plain_spot):  # no tables: capturable on a fresh context, and the slot stays empty
+                    rc, msg, g = captured(kw)
+                    graphs.append(g)
+                    assert rc == 0, msg
+                    assert np.array_equal(dst.bits(), poison)  # a capture runs nothing
+                    engine.replay(g)
+                    assert lighting_ref.same_bits(dst.bits(), ref(kw))
+                    assert hip.jh_debug_scratch_bytes(ctx, SLOT) == 0
+                    engine.upload_image(dst.id, poison)
+                # a key that is not resident
+                rc, msg, refused = captured(shiny, clear_first=buf.id)
+                engine.graph_destroy(refused)
+                assert rc == JH_ERR_OOM and msg.startswith("jh_lighting: ") and "run this lighting once eagerly first" in msg, (rc, msg)
+                assert np.array_equal(dst.bits(), poison) and np.array_equal(src.bits(), bits)
+                engine.lighting(src.id, dst.id, **shiny)
+                assert lighting_ref.same_bits(dst.bits(), ref(shiny))
+                size = hip.jh_debug_scratch_bytes(ctx, SLOT)
+                assert size >= 2 * TABLE_BYTES
+                engine.upload_image(dst.id, poison)
+                rc, msg, g = captured(shiny)
+                graphs.append(g)
+                assert rc == 0, msg
+                assert np.array_equal(dst.bits(), poison)
+                engine.replay(g)
+                assert lighting_ref.same_bits(dst.bits(), ref(shiny))
+                # the same key with another light, scale, constant and colour, and calls without tables: nothing is uploaded, the
+                # graph stays valid
+                engine.lighting(src.id, dst.id, **shiny_moved)
+                assert lighting_ref.same_bits(dst.bits(), ref(shiny_moved))
+                engine.lighting(src.id, dst.id, **plain)
+                assert hip.jh_debug_scratch_bytes(ctx, SLOT) == size
+                engine.replay(g)
+                assert lighting_ref.same_bits(dst.bits(), ref(shiny))
+                # another key: its tables replace the ones the graph reads
+                engine.lighting(src.id, dst.id, **both)
+                assert hip.jh_graph_launch(ctx, g) == JH_ERR_INVALID
+                assert b"stale" in hip.jh_last_error(ctx)
+                assert lighting_ref.same_bits(dst.bits(), ref(both))
+                engine.lighting(src.id, dst.id, **shiny)  # (and back: the specular exponent alone is another key than both exponents)
+                assert lighting_ref.same_bits(dst.bits(), ref(shiny))
+                # a trim forgets the key: the same lighting is no longer capturable until it has run again
+                engine._check(hip.jh_scratch_trim(ctx), "scratch_trim")
+                rc, msg, refused = captured(shiny)
+                engine.graph_destroy(refused)
+                assert rc == JH_ERR_OOM and "run this lighting once eagerly first" in msg
+                engine.lighting(src.id, dst.id, **shiny)
+                assert lighting_ref.same_bits(dst.bits(), ref(shiny))
+            finally:
+                for g in graphs:
+                    engine.graph_destroy(g)
     finally:
-        for g in graphs:
-            engine.graph_destroy(g)
-        for im in (src, dst, buf):
-            im.free()
         engine.close()
 
 
 def test_captured_with_the_frame(engine):
     """capture(lighting=..., surface=...): render, light the target's alpha into a second image, blit that image -- one launch more
-    than with the blit alone (the tables are resident), replayed twice, the bytes of the eager calls."""
-    s, p = _scene()
-    fmt = Surface.RGBA8_SRGB
+    than with the blit alone (the tables are resident, nothing is uploaded), replayed twice, the bytes of the eager calls."""
     k = dict(lighting.specular(6.0, 1.0, 20.0, (1.0, 0.9, 0.8)), **lighting.point(30, 20, 50))
-    rec = jello_amd.Host().record(s, p)
-    lit, surf, full = Image(engine, None, 128, 128), DevBuf(engine, 128 * 128 * 4), DevBuf(engine, 128 * 128 * 4)
-    g = None
-    try:
-        engine.run(rec, RUN_UPLOADS | RUN_DISPATCHES)
-        t = rec.target
-        plain = target_of(engine, rec)
-        engine.lighting(t["id"], lit.id, **k)
-        engine.blit(lit.id, 128, 128, fmt, out_device_ptr=surf.ptr)
-        eager = surf.bytes()[:128 * 128 * 4].reshape(128, 128, 4)
-        want = lighting_ref.lighting(plain, **{n: (int(v) if n in ("kind", "light") else v) for n, v in k.items()})
-        assert lighting_ref.same_bits(lit.bits(), want)
-        assert np.array_equal(eager, surface_ref.convert(want, int(fmt)))
-        g0 = engine.capture(rec, surface=(full.ptr, 128 * 4, fmt))  # (the frame and the blit of its own target)
-        g = engine.capture(rec, lighting=dict(dst=lit.id, **k), surface=(surf.ptr, 128 * 4, fmt))
-        (k0, o0), (k1, o1) = engine.graph_node_counts(g0), engine.graph_node_counts(g)
-        engine.graph_destroy(g0)
-        assert (k1, o1) == (k0 + 1, o0)  # one launch; the tables are resident, nothing is uploaded
-        for _ in range(2):
-            engine.clear(surf.id)
-            engine.replay(g)
-            engine.sync()
-            assert np.array_equal(surf.bytes()[:128 * 128 * 4].reshape(128, 128, 4), eager)
-        assert np.array_equal(target_of(engine, rec), plain)
-    finally:
-        if g is not None:
-            engine.graph_destroy(g)
-        lit.free()
-        surf.free()
-        full.free()
+    captured_with_the_frame(engine, scene(stroke=9), lambda target, dst: engine.lighting(target, dst, **k), lambda dst: dict(lighting=dict(dst=dst, **k)),
+                            lambda plain: lighting_ref.lighting(plain, **_ref_kw(k)), extra_launches=1, out_size=(128, 128), baseline_surface=True)
 
 
 def test_refusals(engine):
@@ -228,124 +160,72 @@ def test_refusals(engine):
     of a canary buffer touched; a valid call works afterwards."""
     hip, ctx = engine.hip, engine.ctx
     W, H = 16, 12
-    canary = np.full((H, W, 4), CANARY | (CANARY << 8), np.uint16)
-    src, dst = Image(engine, canary), Image(engine, canary)
-    rgba8 = Image(engine, np.full((H, W, 2), 0x1111, np.uint16), fmt=ImageFormat.RGBA8)  # (W x H texels of 4 bytes)
-    other = Image(engine, None, W + 1, H)
-    wide_a, wide_b = Image(engine, None, (1 << 23) + 1, 1), Image(engine, None, (1 << 23) + 1, 1)
-    guard = DevBuf(engine, 256)
+    canary = canary_bits(W, H)
     nan, inf = math.nan, math.inf
-
-    def call(s=None, d=None, null=False, **kw):
-        desc = _lighting_desc(**kw)
-        return hip.jh_lighting(ctx, src.id if s is None else s, dst.id if d is None else d, None if null else ctypes.byref(desc))
-
     point = dict(light=1, position=(1.0, 2.0, 3.0))
     spot = dict(light=2, position=(1.0, 2.0, 3.0), points_at=(4.0, 5.0, 0.0))
-    refused = {
-        "null descriptor": (lambda: call(null=True), b""),
-        "unknown source": (lambda: call(s=_id()), b"unknown source"),
-        "unknown destination": (lambda: call(d=_id()), b"unknown destination"),
-        "source not RGBA16F": (lambda: call(s=rgba8.id), b"RGBA16F"),
-        "destination not RGBA16F": (lambda: call(d=rgba8.id), b"RGBA16F"),
-        "images of different size": (lambda: call(d=other.id), b"size"),
-        "source is the destination": (lambda: call(d=src.id), b"source is the destination"),
-        "an extent above 2^23": (lambda: call(s=wide_a.id, d=wide_b.id), b"2^23"),
-        "kind 2": (lambda: call(kind=2), b"kind"),
-        "kind -1": (lambda: call(kind=-1), b"kind"),
-        "light 3": (lambda: call(light=3), b"light"),
-        "light -1": (lambda: call(light=-1), b"light"),
-        "a NaN surface_scale": (lambda: call(surface_scale=nan), b"surface_scale"),
-        "an infinite surface_scale": (lambda: call(surface_scale=-inf), b"surface_scale"),
-        "a negative constant": (lambda: call(constant=-1e-30), b"constant"),
-        "a NaN constant": (lambda: call(constant=nan), b"constant"),
-        "an infinite constant": (lambda: call(constant=inf), b"constant"),
-        "specular_exponent below 1": (lambda: call(kind=1, specular_exponent=0.99999994), b"specular_exponent"),
-        "specular_exponent above 128": (lambda: call(kind=1, specular_exponent=128.00002), b"specular_exponent"),
-        "a NaN specular_exponent": (lambda: call(kind=1, specular_exponent=nan), b"specular_exponent"),
-        "a negative color": (lambda: call(color=(1.0, -0.5, 1.0)), b"color"),
-        "a NaN color": (lambda: call(color=(1.0, 1.0, nan)), b"color"),
-        "an infinite color": (lambda: call(color=(inf, 1.0, 1.0)), b"color"),
-        "a zero direction": (lambda: call(direction=(0.0, 0.0, -0.0)), b"direction"),
-        "a NaN direction": (lambda: call(direction=(0.0, nan, 1.0)), b"direction"),
-        "a direction whose length overflows": (lambda: call(direction=(1e200, 0.0, 1.0)), b"direction"),
-        "a direction whose length underflows": (lambda: call(direction=(1e-200, 0.0, 0.0)), b"direction"),
-        "an infinite position": (lambda: call(light=1, position=(inf, 0.0, 0.0)), b"position"),
-        "a position beyond binary32": (lambda: call(light=1, position=(0.0, 1e39, 0.0)), b"position"),
-        "a NaN spot position": (lambda: call(**dict(spot, position=(0.0, 0.0, nan))), b"position"),
-        "points_at the position": (lambda: call(**dict(spot, points_at=(1.0, 2.0, 3.0))), b"points_at"),
-        "a NaN points_at": (lambda: call(**dict(spot, points_at=(nan, 2.0, 3.0))), b"points_at"),
-        "spot_exponent below 1": (lambda: call(spot_exponent=0.5, **spot), b"spot_exponent"),
-        "spot_exponent above 128": (lambda: call(spot_exponent=129.0, **spot), b"spot_exponent"),
-        "cone_cos above 1": (lambda: call(cone_cos=1.0000000000000002, **spot), b"cone_cos"),
-        "cone_cos below -1": (lambda: call(cone_cos=-1.5, **spot), b"cone_cos"),
-        "a NaN cone_cos": (lambda: call(cone_cos=nan, **spot), b"cone_cos"),
-        "rectangle beyond the right edge": (lambda: call(rect=(8, 0, 9, 4)), b"rectangle is not inside"),
-        "rectangle beyond the bottom edge": (lambda: call(rect=(0, 9, 4, 4)), b"rectangle is not inside"),
-        "rectangle whose end wraps": (lambda: call(rect=(0xFFFFFFFF, 0, 2, 2)), b"rectangle is not inside"),
-        "rectangle empty in x only": (lambda: call(rect=(2, 2, 0, 4)), b"empty in one dimension"),
-        "rectangle empty in y only": (lambda: call(rect=(2, 2, 4, 0)), b"empty in one dimension"),
-    }
-    try:
-        for what, (f, word) in refused.items():
-            assert f() == JH_ERR_INVALID, what
-            msg = hip.jh_last_error(ctx)
-            assert msg.startswith(b"jh_lighting: ") and word in msg, (what, msg)
-        engine.set_band(0, 1)
-        try:
-            assert call() == JH_ERR_INVALID
-            assert hip.jh_last_error(ctx).startswith(b"jh_lighting: ") and b"band" in hip.jh_last_error(ctx)
-        finally:
-            engine.set_band()
-        with pytest.raises(ValueError, match="jh_lighting: "):
-            engine.lighting(src.id, src.id)
-        with pytest.raises(ValueError, match="jh_lighting: "):
-            engine.lighting(src.id, dst.id, **dict(lighting.specular(exponent=200), **lighting.distant(0, 45)))
-        with pytest.raises(ValueError, match="jh_lighting: "):
-            engine.lighting(src.id, dst.id, color=(1.0, 1.0))
-        assert np.array_equal(src.bits(), canary) and np.array_equal(dst.bits(), canary)
-        assert np.all(guard.bytes() == CANARY)
-        # fields the kind and the light do not use are not looked at; the boundaries themselves are legal
-        assert call(specular_exponent=nan, spot_exponent=nan, position=(nan,) * 3, points_at=(nan,) * 3, cone_cos=nan, rect=(3, 3, 2, 2)) == 0
-        assert call(direction=(nan,) * 3, spot_exponent=0.0, rect=(3, 3, 2, 2), **point) == 0
-        assert call(specular_exponent=128.0, spot_exponent=1.0, cone_cos=1.0, rect=(3, 3, 2, 2), kind=1, **spot) == 0
-        assert call(specular_exponent=1.0, spot_exponent=128.0, cone_cos=-1.0, constant=0.0, rect=(3, 3, 2, 2), kind=1, **spot) == 0
+    with images(engine, canary, canary, (W, H, ImageFormat.RGBA8), (W + 1, H), ((1 << 23) + 1, 1), ((1 << 23) + 1, 1)) as (src, dst, rgba8, other, wide_a, wide_b):
+        def call(s=None, d=None, null=False, **kw):
+            desc = _lighting_desc(**kw)
+            return hip.jh_lighting(ctx, src.id if s is None else s, dst.id if d is None else d, None if null else ctypes.byref(desc))
+
+        refused = dict(common_refusals(call, rgba8), **{
+            "images of different size": (lambda: call(d=other.id), b"size"),
+            "source is the destination": (lambda: call(d=src.id), b"source is the destination"),
+            "an extent above 2^23": (lambda: call(s=wide_a.id, d=wide_b.id), b"2^23"),
+            "kind 2": (lambda: call(kind=2), b"kind"),
+            "kind -1": (lambda: call(kind=-1), b"kind"),
+            "light 3": (lambda: call(light=3), b"light"),
+            "light -1": (lambda: call(light=-1), b"light"),
+            "a NaN surface_scale": (lambda: call(surface_scale=nan), b"surface_scale"),
+            "an infinite surface_scale": (lambda: call(surface_scale=-inf), b"surface_scale"),
+            "a negative constant": (lambda: call(constant=-1e-30), b"constant"),
+            "a NaN constant": (lambda: call(constant=nan), b"constant"),
+            "an infinite constant": (lambda: call(constant=inf), b"constant"),
+            "specular_exponent below 1": (lambda: call(kind=1, specular_exponent=0.99999994), b"specular_exponent"),
+            "specular_exponent above 128": (lambda: call(kind=1, specular_exponent=128.00002), b"specular_exponent"),
+            "a NaN specular_exponent": (lambda: call(kind=1, specular_exponent=nan), b"specular_exponent"),
+            "a negative color": (lambda: call(color=(1.0, -0.5, 1.0)), b"color"),
+            "a NaN color": (lambda: call(color=(1.0, 1.0, nan)), b"color"),
+            "an infinite color": (lambda: call(color=(inf, 1.0, 1.0)), b"color"),
+            "a zero direction": (lambda: call(direction=(0.0, 0.0, -0.0)), b"direction"),
+            "a NaN direction": (lambda: call(direction=(0.0, nan, 1.0)), b"direction"),
+            "a direction whose length overflows": (lambda: call(direction=(1e200, 0.0, 1.0)), b"direction"),
+            "a direction whose length underflows": (lambda: call(direction=(1e-200, 0.0, 0.0)), b"direction"),
+            "an infinite position": (lambda: call(light=1, position=(inf, 0.0, 0.0)), b"position"),
+            "a position beyond binary32": (lambda: call(light=1, position=(0.0, 1e39, 0.0)), b"position"),
+            "a NaN spot position": (lambda: call(**dict(spot, position=(0.0, 0.0, nan))), b"position"),
+            "points_at the position": (lambda: call(**dict(spot, points_at=(1.0, 2.0, 3.0))), b"points_at"),
+            "a NaN points_at": (lambda: call(**dict(spot, points_at=(nan, 2.0, 3.0))), b"points_at"),
+            "spot_exponent below 1": (lambda: call(spot_exponent=0.5, **spot), b"spot_exponent"),
+            "spot_exponent above 128": (lambda: call(spot_exponent=129.0, **spot), b"spot_exponent"),
+            "cone_cos above 1": (lambda: call(cone_cos=1.0000000000000002, **spot), b"cone_cos"),
+            "cone_cos below -1": (lambda: call(cone_cos=-1.5, **spot), b"cone_cos"),
+            "a NaN cone_cos": (lambda: call(cone_cos=nan, **spot), b"cone_cos"),
+        })
+        # (accepted: fields the kind and the light do not use are not looked at; the boundaries themselves are legal)
+        check_refusals(engine, "jh_lighting", call, refused, untouched=((src, canary), (dst, canary)),
+                       raises=(lambda: engine.lighting(src.id, src.id),
+                               lambda: engine.lighting(src.id, dst.id, **dict(lighting.specular(exponent=200), **lighting.distant(0, 45))),
+                               lambda: engine.lighting(src.id, dst.id, color=(1.0, 1.0))),
+                       accepted=(lambda: call(specular_exponent=nan, spot_exponent=nan, position=(nan,) * 3, points_at=(nan,) * 3, cone_cos=nan, rect=(3, 3, 2, 2)),
+                                 lambda: call(direction=(nan,) * 3, spot_exponent=0.0, rect=(3, 3, 2, 2), **point),
+                                 lambda: call(specular_exponent=128.0, spot_exponent=1.0, cone_cos=1.0, rect=(3, 3, 2, 2), kind=1, **spot),
+                                 lambda: call(specular_exponent=1.0, spot_exponent=128.0, cone_cos=-1.0, constant=0.0, rect=(3, 3, 2, 2), kind=1, **spot)))
         want = canary.copy()
         want[3:5, 3:5] = 0  # (the last call: a constant of 0 gives transparent black under SPECULAR)
         assert np.array_equal(dst.bits(), want)
-        assert np.array_equal(src.bits(), canary) and np.all(guard.bytes() == CANARY)
-        empty_a, empty_b = Image(engine, None, 0, 5), Image(engine, None, 0, 5)
-        try:
+        assert np.array_equal(src.bits(), canary)
+        with images(engine, (0, 5), (0, 5)) as (empty_a, empty_b):
             assert hip.jh_lighting(ctx, empty_a.id, empty_b.id, ctypes.byref(CLightingDesc(0, 0, 1.0, 1.0, 1.0, 1.0, (ctypes.c_float * 3)(1, 1, 1), 0, 0, 0, 0,
                                                                                             (ctypes.c_double * 3)(0, 0, 1)))) == 0  # (an image without texels)
-        finally:
-            empty_a.free()
-            empty_b.free()
-    finally:
-        for im in (src, dst, rgba8, other, wide_a, wide_b, guard):
-            im.free()
     assert point["light"] == int(LightSource.POINT) and int(LightKind.SPECULAR) == 1
 
 
 def test_the_call_is_one_query_of_the_tree(engine):
     bits = lighting_cases.content("disc", 48, 33, 2)
     k = dict(lighting.diffuse(5.0, 1.2), **lighting.distant(45, 30))
-    src, dst = Image(engine, bits), Image(engine, None, 48, 33)
-    try:
-        engine.profile(True)
-        try:
-            with engine.profile_group("post"):
-                engine.lighting(src.id, dst.id, **k)
-            tree = engine.profile_collect_tree()
-            engine.lighting(src.id, dst.id, **k)
-            flat = engine.profile_collect()
-        finally:
-            engine.profile(False)
+    with images(engine, bits, (48, 33)) as (src, dst):
+        one_query(engine, "lighting", lambda: engine.lighting(src.id, dst.id, **k))
         got = dst.bits()
-    finally:
-        src.free()
-        dst.free()
-    assert [(n["kind"], n["label"], n["parent"], n["stage"]) for n in tree] == [("group", "post", -1, -1), ("query", "lighting", 0, -1)]
-    assert tree[1]["gpu_end_ms"] >= tree[1]["gpu_start_ms"]
-    assert flat == []
-    assert lighting_ref.same_bits(got, lighting_ref.lighting(bits, **{n: (int(v) if n in ("kind", "light") else v) for n, v in k.items()}))
+    assert lighting_ref.same_bits(got, lighting_ref.lighting(bits, **_ref_kw(k)))

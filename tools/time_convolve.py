@@ -9,14 +9,9 @@ kernels' own times run it under `rocprofv3 --kernel-trace --stats -d DIR -- pyth
 
     python tools/time_convolve.py [--blocks 5] [--per-block 5] [--out profiles/convolve_kernel_times.json]
 """
-import argparse
-import json
-import os
-import statistics
-
 import numpy as np
 
-from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_json
+from timing import Timer
 
 from jello_amd import BlurEdge, ConvolveEdge, ConvolveMode, WarpEdge, WarpFilter  # noqa: E402 (timing puts the root on sys.path)
 
@@ -26,47 +21,22 @@ ORDERS = (3, 5, 7, 15)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--per-block", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "convolve_kernel_times.json"))
-    a = ap.parse_args()
-    import torch
-    eng, stream = open_engine_on_stream()
+    t = Timer("tools/time_convolve.py", 5, 5, "convolve_kernel_times.json")
+    eng = t.eng
     rng = np.random.default_rng(1)
     # colours and alphas spread over [0, 1.25), as a fine stage leaves them
     img = (rng.random((SIZE, SIZE, 4), dtype=np.float32) * 1.25).astype(np.float16).view(np.uint16)
     src, dst = 0x71E0_0000, 0x71E2_0000
-    eng.upload_image(src, img)
-    eng.upload_image(dst, img)
-    with torch.cuda.stream(stream):
-        ta = torch.zeros((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-        tb = torch.ones((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-    results = []
-
-    def record(r, times, floor=None):
-        med = statistics.median(times)
-        r.update({"us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times], "us_spread": round(max(times) - min(times), 3)})
-        if floor is not None:
-            r.update({"copy_us_median": round(floor, 3), "ratio_to_copy": round(med / floor, 2)})
-        results.append(r)
-        print(json.dumps(r), flush=True)
-        return med
-
+    t.upload(img, src, dst)
+    t.tensors(SIZE, SIZE)
     for label, rect in (("whole", (0, 0, SIZE, SIZE)), ("rect1024", RECT)):
         x, y, w, h = rect
         call_rect = None if label == "whole" else rect
-
-        def copy():
-            with torch.cuda.stream(stream):
-                tb[y:y + h, x:x + w].copy_(ta[y:y + h, x:x + w])
-
-        floor = record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, timed_blocks(stream, copy, a.blocks, a.per_block))
-        record({"rect": label, "call": "jh_blur", "sigma": 1.0, "taps": "7 + 7"},
-               timed_blocks(stream, lambda: eng.blur(dst, SIZE, SIZE, 1.0, edge=BlurEdge.ZERO, rect=call_rect), a.blocks, a.per_block), floor)
-        record({"rect": label, "call": "jh_warp", "case": "identity", "filter": "BICUBIC", "taps": 16},
-               timed_blocks(stream, lambda: eng.warp(src, dst, (1.0, 0.0, 0.0, 1.0, 0.0, 0.0), filter=WarpFilter.BICUBIC, edge=WarpEdge.ZERO,
-                                                     dst_rect=call_rect), a.blocks, a.per_block), floor)
+        floor = t.record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, t.timed(t.copy(rect)))
+        t.record({"rect": label, "call": "jh_blur", "sigma": 1.0, "taps": "7 + 7"},
+                 t.timed(lambda: eng.blur(dst, SIZE, SIZE, 1.0, edge=BlurEdge.ZERO, rect=call_rect)), floor)
+        t.record({"rect": label, "call": "jh_warp", "case": "identity", "filter": "BICUBIC", "taps": 16},
+                 t.timed(lambda: eng.warp(src, dst, (1.0, 0.0, 0.0, 1.0, 0.0, 0.0), filter=WarpFilter.BICUBIC, edge=WarpEdge.ZERO, dst_rect=call_rect)), floor)
         for order in ORDERS:
             weights = (rng.random((order, order), dtype=np.float32) - 0.4) / np.float32(order * order)
             for mode in (ConvolveMode.PREMULTIPLIED, ConvolveMode.STRAIGHT):
@@ -74,19 +44,10 @@ def main():
                     launch = lambda: eng.convolve(src, dst, weights, edge=edge, mode=mode, rect=call_rect)  # noqa: E731
                     r = {"rect": label, "call": "jh_convolve", "order": order, "taps": order * order, "mode": mode.name, "edge": edge.name,
                          "instantiation": "%dx%d" % (order, order) if order in (3, 5) else "general"}
-                    med = record(r, timed_blocks(stream, launch, a.blocks, a.per_block), floor)
-                    r["ps_per_tap_and_texel"] = round(med * 1e6 / (order * order * w * h), 3)
-    for i in (src, dst):
-        eng.free_image(i)
-    eng.sync()
-    eng.set_stream(None)
-    eng.close()
-    out = {"tool": "tools/time_convolve.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block, "size": SIZE,
-           "note": "hipEvents around back-to-back jh_convolve calls (one kernel each) between two 4096^2 images; the copy is torch's copy_ of "
-                   "the same rectangle between two tensors of the image's shape; jh_blur at sigma 1 (two kernels, in place on the destination) "
-                   "and jh_warp BICUBIC under the identity (one kernel) at the same rectangle are timed in the same run",
-           "results": results}
-    write_json(a.out, out)
+                    t.record(r, t.timed(launch), floor, lambda med: {"ps_per_tap_and_texel": round(med * 1e6 / (order * order * w * h), 3)})
+    t.finish("hipEvents around back-to-back jh_convolve calls (one kernel each) between two 4096^2 images; the copy is torch's copy_ of "
+             "the same rectangle between two tensors of the image's shape; jh_blur at sigma 1 (two kernels, in place on the destination) "
+             "and jh_warp BICUBIC under the identity (one kernel) at the same rectangle are timed in the same run", SIZE)
 
 
 if __name__ == "__main__":

@@ -9,14 +9,9 @@ wrote down before the first run (ESTIMATE_US below, whole image).  Run on the GP
 
     python tools/time_lighting.py [--blocks 5] [--per-block 5] [--out profiles/lighting_kernel_times.json]
 """
-import argparse
-import json
-import os
-import statistics
-
 import numpy as np
 
-from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_json
+from timing import Timer
 
 from jello_amd import colorfilter, convolution, lighting  # noqa: E402 (timing puts the root on sys.path)
 
@@ -40,65 +35,32 @@ def configurations():
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--per-block", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lighting_kernel_times.json"))
-    a = ap.parse_args()
-    import torch
-    eng, stream = open_engine_on_stream()
+    t = Timer("tools/time_lighting.py", 5, 5, "lighting_kernel_times.json")
+    eng = t.eng
     rng = np.random.default_rng(1)
     # a height map with structure at every scale: random alpha in [0, 1), random colour
     img = rng.random((SIZE, SIZE, 4), dtype=np.float32).astype(np.float16).view(np.uint16)
     src, dst = 0x71E0_0000, 0x71E2_0000
-    eng.upload_image(src, img)
-    eng.upload_image(dst, img)
-    with torch.cuda.stream(stream):
-        ta = torch.zeros((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-        tb = torch.ones((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-    results = []
-
-    def record(r, times, floor=None):
-        med = statistics.median(times)
-        r.update({"us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times], "us_spread": round(max(times) - min(times), 3)})
-        if floor is not None:
-            r.update({"copy_us_median": round(floor, 3), "ratio_to_copy": round(med / floor, 2)})
-        results.append(r)
-        print(json.dumps(r), flush=True)
-        return med
-
+    t.upload(img, src, dst)
+    t.tensors(SIZE, SIZE)
     box = convolution.box(3)
     sepia = dict(matrix=colorfilter.sepia(1.0)["matrix"])  # (the matrix alone, in LINEAR space: no tables)
     for label, rect in (("whole", (0, 0, SIZE, SIZE)), ("rect1024", RECT)):
         x, y, w, h = rect
         call_rect = None if label == "whole" else rect
-
-        def copy():
-            with torch.cuda.stream(stream):
-                tb[y:y + h, x:x + w].copy_(ta[y:y + h, x:x + w])
-
-        floor = record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, timed_blocks(stream, copy, a.blocks, a.per_block))
-        record({"rect": label, "call": "jh_color_filter", "case": "sepia's matrix in LINEAR space: no tables"},
-               timed_blocks(stream, lambda: eng.color_filter(src, dst, rect=call_rect, **sepia), a.blocks, a.per_block), floor)
-        record({"rect": label, "call": "jh_convolve", "order": 3, "mode": "PREMULTIPLIED", "edge": "CLAMP"},
-               timed_blocks(stream, lambda: eng.convolve(src, dst, rect=call_rect, **box), a.blocks, a.per_block), floor)
+        floor = t.record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, t.timed(t.copy(rect)))
+        t.record({"rect": label, "call": "jh_color_filter", "case": "sepia's matrix in LINEAR space: no tables"},
+                 t.timed(lambda: eng.color_filter(src, dst, rect=call_rect, **sepia)), floor)
+        t.record({"rect": label, "call": "jh_convolve", "order": 3, "mode": "PREMULTIPLIED", "edge": "CLAMP"},
+                 t.timed(lambda: eng.convolve(src, dst, rect=call_rect, **box)), floor)
         for inst, kw in configurations():
             eng.lighting(src, dst, rect=call_rect, **kw)  # (uploads the key's tables outside the timed blocks)
             r = {"rect": label, "call": "jh_lighting", "instantiation": inst, "specular_exponent": kw.get("specular_exponent", 1.0), "spot_exponent": kw.get("spot_exponent", 1.0)}
-            med = record(r, timed_blocks(stream, lambda: eng.lighting(src, dst, rect=call_rect, **kw), a.blocks, a.per_block), floor)
-            if label == "whole":
-                r.update({"estimate_us": ESTIMATE_US[inst], "measured_over_estimate": round(med / ESTIMATE_US[inst], 2)})
-    for i in (src, dst):
-        eng.free_image(i)
-    eng.sync()
-    eng.set_stream(None)
-    eng.close()
-    out = {"tool": "tools/time_lighting.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block, "size": SIZE,
-           "note": "hipEvents around back-to-back jh_lighting calls (one kernel each) between two 4096^2 images of random alpha; the copy is torch's "
-                   "copy_ of the same rectangle between two tensors of the image's shape; jh_color_filter (a matrix, no tables) and jh_convolve 3 x 3 "
-                   "at the same rectangle are timed in the same run; estimate_us is what DESIGN 5.14 wrote down before the first timing run",
-           "results": results}
-    write_json(a.out, out)
+            t.record(r, t.timed(lambda: eng.lighting(src, dst, rect=call_rect, **kw)), floor, lambda med: {} if label != "whole" else {
+                "estimate_us": ESTIMATE_US[inst], "measured_over_estimate": round(med / ESTIMATE_US[inst], 2)})
+    t.finish("hipEvents around back-to-back jh_lighting calls (one kernel each) between two 4096^2 images of random alpha; the copy is torch's "
+             "copy_ of the same rectangle between two tensors of the image's shape; jh_color_filter (a matrix, no tables) and jh_convolve 3 x 3 "
+             "at the same rectangle are timed in the same run; estimate_us is what DESIGN 5.14 wrote down before the first timing run", SIZE)
 
 
 if __name__ == "__main__":

@@ -10,14 +10,11 @@ output does not grow with the window.  Run on the GPU box; for the kernels' own 
 
     python tools/time_morph.py [--blocks 5] [--per-block 5] [--out profiles/morph_kernel_times.json]
 """
-import argparse
 import json
-import os
-import statistics
 
 import numpy as np
 
-from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_json
+from timing import Timer
 
 from jello_amd import BlurEdge, MorphEdge, MorphOp  # noqa: E402 (timing puts the root on sys.path)
 
@@ -27,49 +24,25 @@ BLUR_MAX_RADIUS = 192
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--per-block", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "morph_kernel_times.json"))
-    a = ap.parse_args()
-    import torch
-    eng, stream = open_engine_on_stream()
+    t = Timer("tools/time_morph.py", 5, 5, "morph_kernel_times.json")
+    eng = t.eng
     rng = np.random.default_rng(1)
     # colours and alphas spread over [0, 1.25), as a fine stage leaves them
     img = (rng.random((SIZE, SIZE, 4), dtype=np.float32) * 1.25).astype(np.float16).view(np.uint16)
     src, dst = 0x71D0_0000, 0x71D1_0000
-    eng.upload_image(src, img)
-    eng.upload_image(dst, img)
-    with torch.cuda.stream(stream):
-        ta = torch.zeros((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-        tb = torch.ones((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-    results, ratios = [], []
-
-    def record(r, times, floor=None):
-        med = statistics.median(times)
-        r.update({"us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times], "us_spread": round(max(times) - min(times), 3)})
-        if floor is not None:
-            r.update({"copy_us_median": round(floor, 3), "ratio_to_copy": round(med / floor, 2)})
-        results.append(r)
-        print(json.dumps(r), flush=True)
-        return med
-
+    t.upload(img, src, dst)
+    t.tensors(SIZE, SIZE)
+    ratios = []
     for label, rect in (("whole", (0, 0, SIZE, SIZE)), ("rect1024", (1531, 1537, 1024, 1024))):
-        x, y, w, h = rect
-        texels = w * h
+        texels = rect[2] * rect[3]
         call_rect = None if label == "whole" else rect
-
-        def copy():
-            with torch.cuda.stream(stream):
-                tb[y:y + h, x:x + w].copy_(ta[y:y + h, x:x + w])
-
-        floor = record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * texels}, timed_blocks(stream, copy, a.blocks, a.per_block))
+        floor = t.record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * texels}, t.timed(t.copy(rect)))
         for r in RADII:
             if r > BLUR_MAX_RADIUS:
                 continue
             sigma = r / 3.0
             launch = lambda: eng.blur(src, SIZE, SIZE, sigma, dst_image_id=dst, edge=BlurEdge.ZERO, rect=call_rect)  # noqa: E731
-            record({"rect": label, "call": "jh_blur", "sigma": round(sigma, 4), "radius": r}, timed_blocks(stream, launch, a.blocks, a.per_block), floor)
+            t.record({"rect": label, "call": "jh_blur", "sigma": round(sigma, 4), "radius": r}, t.timed(launch), floor)
         for op in MorphOp:
             for premultiplied in (True, False):
                 both = {}
@@ -79,26 +52,18 @@ def main():
                                                         premultiplied=premultiplied)
                         # f16 in, plane H out; H in, plane P out; H and P in, f16 out (the rows above and below a rectangle, and
                         # the padding rows of P, not counted)
-                        med = record({"rect": label, "call": "jh_morphology", "op": op.name, "operands": "premultiplied" if premultiplied else "straight",
-                                      "radius": r, "axes": axes, "traffic_bytes": (8 + 16 + 16 + 16 + 32 + 8) * texels},
-                                     timed_blocks(stream, launch, a.blocks, a.per_block), floor)
+                        med = t.record({"rect": label, "call": "jh_morphology", "op": op.name, "operands": "premultiplied" if premultiplied else "straight",
+                                        "radius": r, "axes": axes, "traffic_bytes": (8 + 16 + 16 + 16 + 32 + 8) * texels}, t.timed(launch), floor)
                         if axes == "both":
                             both[r] = med
                 ratio = {"rect": label, "op": op.name, "operands": "premultiplied" if premultiplied else "straight",
                          "r255_over_r4": round(both[255] / both[4], 2), "r255_us": round(both[255], 3), "r4_us": round(both[4], 3)}
                 ratios.append(ratio)
                 print(json.dumps(ratio), flush=True)
-    eng.free_image(src)
-    eng.free_image(dst)
-    eng.sync()
-    eng.set_stream(None)
-    eng.close()
-    out = {"tool": "tools/time_morph.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block, "size": SIZE,
-           "note": "hipEvents around back-to-back jh_morphology calls (three kernels each) from one 4096^2 image into another, edge ZERO; the "
-                   "copy is torch's copy_ of the same rectangle between two tensors of the image's shape, and jh_blur (two kernels, "
-                   "sigma = r / 3) is timed in the same run; traffic_bytes = f16 in, keys out; keys in, prefix out; keys and prefix in, f16 out",
-           "r255_over_r4": ratios, "results": results}
-    write_json(a.out, out)
+    t.finish("hipEvents around back-to-back jh_morphology calls (three kernels each) from one 4096^2 image into another, edge ZERO; the "
+             "copy is torch's copy_ of the same rectangle between two tensors of the image's shape, and jh_blur (two kernels, "
+             "sigma = r / 3) is timed in the same run; traffic_bytes = f16 in, keys out; keys in, prefix out; keys and prefix in, f16 out",
+             SIZE, r255_over_r4=ratios)
 
 
 if __name__ == "__main__":

@@ -10,14 +10,9 @@ fmaf rate and the traffic rate.  Run on the GPU box; for the two kernels' own ti
 
     python tools/time_resample.py [--blocks 7] [--per-block 10] [--out profiles/resample_kernel_times.json]
 """
-import argparse
-import json
-import os
-import statistics
-
 import numpy as np
 
-from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_json
+from timing import Timer
 
 from jello_amd import ResampleFilter, resample_taps  # noqa: E402 (timing puts the root on sys.path)
 
@@ -25,65 +20,33 @@ GEOMETRIES = [((4096, 4096), (2048, 2048)), ((4096, 4096), (1920, 1080)), ((2048
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", type=int, default=7)
-    ap.add_argument("--per-block", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "resample_kernel_times.json"))
-    a = ap.parse_args()
-    import torch
-    eng, stream = open_engine_on_stream()
+    t = Timer("tools/time_resample.py", 7, 10, "resample_kernel_times.json")
+    eng = t.eng
     rng = np.random.default_rng(1)
     src, dst = 0x71C2_0000, 0x71C3_0000
-    results = []
     for (sw, sh), (dw, dh) in GEOMETRIES:
         # colours and alphas spread over [0, 1.25), as a fine stage leaves them
-        img = (rng.random((sh, sw, 4), dtype=np.float32) * 1.25).astype(np.float16).view(np.uint16)
-        eng.upload_image(src, img)
-        eng.upload_image(dst, np.zeros((dh, dw, 4), np.uint16))
-        with torch.cuda.stream(stream):
-            ta = torch.zeros((dh, dw, 4), dtype=torch.float16, device="cuda")
-            tb = torch.ones((dh, dw, 4), dtype=torch.float16, device="cuda")
+        t.upload((rng.random((sh, sw, 4), dtype=np.float32) * 1.25).astype(np.float16).view(np.uint16), src)
+        t.upload(np.zeros((dh, dw, 4), np.uint16), dst)
+        t.tensors(dw, dh)
         label = "%dx%d->%dx%d" % (sw, sh, dw, dh)
-
-        def copy():
-            with torch.cuda.stream(stream):
-                tb.copy_(ta)
-
-        times = timed_blocks(stream, copy, a.blocks, a.per_block)
-        floor = statistics.median(times)
-        r = {"geometry": label, "call": "device-to-device copy of dst", "us_median": round(floor, 3), "us_blocks": [round(t, 3) for t in times],
-             "us_spread": round(max(times) - min(times), 3), "algorithmic_bytes": 16 * dw * dh, "tb_per_s": round(16 * dw * dh / (floor * 1e-6) / 1e12, 3)}
-        results.append(r)
-        print(json.dumps(r), flush=True)
+        floor = t.record({"geometry": label, "call": "device-to-device copy of dst"}, t.timed(t.copy()), more=lambda med: {
+            "algorithmic_bytes": 16 * dw * dh, "tb_per_s": round(16 * dw * dh / (med * 1e-6) / 1e12, 3)})
         for filt in ResampleFilter:
             wins_y = resample_taps(filt, sh, dh)
             taps_x = sum(len(w) for _, w in resample_taps(filt, sw, dw))
             taps_y = sum(len(w) for _, w in wins_y)
             # the column pass loads a row of the intermediate once per item of four output rows whose windows hold it
             rows_in = sum(max(f + len(w) for f, w in wins_y[g:g + 4]) - min(f for f, _ in wins_y[g:g + 4]) for g in range(0, dh, 4))
-            launch = lambda: eng.resample(src, dst, filt)  # noqa: E731
-            times = timed_blocks(stream, launch, a.blocks, a.per_block)
-            med = statistics.median(times)
             fmas = 4 * (taps_x * sh + taps_y * dw)
             traffic = 8 * sw * sh + 16 * dw * sh + 16 * dw * rows_in + 8 * dw * dh  # f16 in, binary32 rows out, rows in per item, f16 out
-            r = {"geometry": label, "call": "jh_resample", "filter": filt.name, "taps_per_output_x": round(taps_x / dw, 2),
-                 "taps_per_output_y": round(taps_y / dh, 2), "us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times],
-                 "us_spread": round(max(times) - min(times), 3), "copy_us_median": round(floor, 3), "ratio_to_copy": round(med / floor, 2), "fmaf": fmas,
-                 "tfmaf_per_s": round(fmas / (med * 1e-6) / 1e12, 2), "traffic_bytes": traffic, "traffic_tb_per_s": round(traffic / (med * 1e-6) / 1e12, 3)}
-            results.append(r)
-            print(json.dumps(r), flush=True)
-        del ta, tb
-    eng.free_image(src)
-    eng.free_image(dst)
-    eng.sync()
-    eng.set_stream(None)
-    eng.close()
-    out = {"tool": "tools/time_resample.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block,
-           "note": "hipEvents around back-to-back jh_resample calls (two kernels each, tables resident) from one image into another; the copy is "
-                   "torch's copy_ between two tensors of the destination's shape in the same run; traffic_bytes = f16 source in, binary32 "
-                   "intermediate out, the intermediate in once per column item of four output rows (what the column pass asks of the caches), f16 out",
-           "results": results}
-    write_json(a.out, out)
+            t.record({"geometry": label, "call": "jh_resample", "filter": filt.name, "taps_per_output_x": round(taps_x / dw, 2),
+                      "taps_per_output_y": round(taps_y / dh, 2)}, t.timed(lambda: eng.resample(src, dst, filt)), floor, lambda med: {
+                "fmaf": fmas, "tfmaf_per_s": round(fmas / (med * 1e-6) / 1e12, 2), "traffic_bytes": traffic,
+                "traffic_tb_per_s": round(traffic / (med * 1e-6) / 1e12, 3)})
+    t.finish("hipEvents around back-to-back jh_resample calls (two kernels each, tables resident) from one image into another; the copy is "
+             "torch's copy_ between two tensors of the destination's shape in the same run; traffic_bytes = f16 source in, binary32 "
+             "intermediate out, the intermediate in once per column item of four output rows (what the column pass asks of the caches), f16 out")
 
 
 if __name__ == "__main__":

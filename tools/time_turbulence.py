@@ -9,14 +9,9 @@ before the first run (ESTIMATE_US below, whole image) first, then the times and 
 
     python tools/time_turbulence.py [--blocks 5] [--per-block 5] [--out profiles/turbulence_kernel_times.json]
 """
-import argparse
-import json
-import os
-import statistics
-
 import numpy as np
 
-from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_json
+from timing import Timer, median
 
 from jello_amd import TurbulenceKind, lighting  # noqa: E402 (timing puts the root on sys.path)
 
@@ -39,63 +34,31 @@ def configurations():
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--per-block", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "turbulence_kernel_times.json"))
-    a = ap.parse_args()
-    import torch
-    eng, stream = open_engine_on_stream()
+    t = Timer("tools/time_turbulence.py", 5, 5, "turbulence_kernel_times.json")
+    eng = t.eng
     rng = np.random.default_rng(1)
     img = rng.random((SIZE, SIZE, 4), dtype=np.float32).astype(np.float16).view(np.uint16)
     src, dst = 0x7B00_0000, 0x7B02_0000
-    eng.upload_image(src, img)
-    eng.upload_image(dst, img)
-    with torch.cuda.stream(stream):
-        ta = torch.zeros((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-        tb = torch.ones((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-    results = []
-
-    def record(r, times, floor=None):
-        med = statistics.median(times)
-        r.update({"us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times], "us_spread": round(max(times) - min(times), 3)})
-        if floor is not None:
-            r.update({"copy_us_median": round(floor, 3), "ratio_to_copy": round(med / floor, 2)})
-        results.append(r)
-        print(json.dumps(r), flush=True)
-        return med
-
+    t.upload(img, src, dst)
+    t.tensors(SIZE, SIZE)
     diffuse = dict(lighting.diffuse(5.0, 1.0), **lighting.distant(35, 40))
     for label, rect in (("whole", (0, 0, SIZE, SIZE)), ("rect1024", RECT)):
         x, y, w, h = rect
         call_rect = None if label == "whole" else rect
-
-        def copy():
-            with torch.cuda.stream(stream):
-                tb[y:y + h, x:x + w].copy_(ta[y:y + h, x:x + w])
-
-        floor = record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, timed_blocks(stream, copy, a.blocks, a.per_block))
-        record({"rect": label, "call": "jh_lighting", "instantiation": "diffuse/distant/0"},
-               timed_blocks(stream, lambda: eng.lighting(src, dst, rect=call_rect, **diffuse), a.blocks, a.per_block), floor)
+        floor = t.record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, t.timed(t.copy(rect)))
+        t.record({"rect": label, "call": "jh_lighting", "instantiation": "diffuse/distant/0"},
+                 t.timed(lambda: eng.lighting(src, dst, rect=call_rect, **diffuse)), floor)
         for inst, octaves, kw in configurations():
             eng.turbulence(dst, rect=call_rect, **kw)  # (uploads the seed's tables outside the timed blocks)
-            times = timed_blocks(stream, lambda: eng.turbulence(dst, rect=call_rect, **kw), a.blocks, a.per_block)
+            times = t.timed(lambda: eng.turbulence(dst, rect=call_rect, **kw))
             r = {"rect": label, "call": "jh_turbulence", "instantiation": inst, "octaves": octaves, "base_frequency": FREQUENCY}
-            if label == "whole":
+            if label == "whole":  # (in front of the times, where the committed profile has them: not record()'s more=, which comes behind)
                 est = ESTIMATE_US[(inst, octaves)]
-                r.update({"measured_over_estimate": round(statistics.median(times) / est, 2), "estimate_us": est})
-            record(r, times, floor)
-    for i in (src, dst):
-        eng.free_image(i)
-    eng.sync()
-    eng.set_stream(None)
-    eng.close()
-    out = {"tool": "tools/time_turbulence.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block, "size": SIZE,
-           "note": "hipEvents around back-to-back jh_turbulence calls (one kernel each) into a 4096^2 image at 0.02 cells per texel; the copy is "
-                   "torch's copy_ of the same rectangle between two tensors of the image's shape; jh_lighting DIFFUSE DISTANT at the same rectangle "
-                   "is timed in the same run; estimate_us is what DESIGN 5.15 wrote down before the first timing run",
-           "results": results}
-    write_json(a.out, out)
+                r.update({"measured_over_estimate": round(median(times) / est, 2), "estimate_us": est})
+            t.record(r, times, floor)
+    t.finish("hipEvents around back-to-back jh_turbulence calls (one kernel each) into a 4096^2 image at 0.02 cells per texel; the copy is "
+             "torch's copy_ of the same rectangle between two tensors of the image's shape; jh_lighting DIFFUSE DISTANT at the same rectangle "
+             "is timed in the same run; estimate_us is what DESIGN 5.15 wrote down before the first timing run", SIZE)
 
 
 if __name__ == "__main__":

@@ -9,15 +9,11 @@ run it under `rocprofv3 --kernel-trace --stats -d DIR -- python tools/time_warp.
 
     python tools/time_warp.py [--blocks 5] [--per-block 5] [--out profiles/warp_kernel_times.json]
 """
-import argparse
-import json
 import math
-import os
-import statistics
 
 import numpy as np
 
-from timing import ROOT, open_engine_on_stream, timed as timed_blocks, write_json
+from timing import Timer
 
 from jello_amd import ResampleFilter, WarpEdge, WarpFilter  # noqa: E402 (timing puts the root on sys.path)
 
@@ -33,51 +29,26 @@ def rotation(deg, size):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--blocks", type=int, default=5)
-    ap.add_argument("--per-block", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "warp_kernel_times.json"))
-    a = ap.parse_args()
-    import torch
-    eng, stream = open_engine_on_stream()
+    t = Timer("tools/time_warp.py", 5, 5, "warp_kernel_times.json")
+    eng = t.eng
     rng = np.random.default_rng(1)
     # colours and alphas spread over [0, 1.25), as a fine stage leaves them
     img = (rng.random((SIZE, SIZE, 4), dtype=np.float32) * 1.25).astype(np.float16).view(np.uint16)
     src, small, dst = 0x71E0_0000, 0x71E1_0000, 0x71E2_0000
-    eng.upload_image(src, img)
-    eng.upload_image(small, img[:HALF, :HALF])
-    eng.upload_image(dst, img)
-    with torch.cuda.stream(stream):
-        ta = torch.zeros((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-        tb = torch.ones((SIZE, SIZE, 4), dtype=torch.float16, device="cuda")
-    results = []
-
-    def record(r, times, floor=None):
-        med = statistics.median(times)
-        r.update({"us_median": round(med, 3), "us_blocks": [round(t, 3) for t in times], "us_spread": round(max(times) - min(times), 3)})
-        if floor is not None:
-            r.update({"copy_us_median": round(floor, 3), "ratio_to_copy": round(med / floor, 2)})
-        results.append(r)
-        print(json.dumps(r), flush=True)
-        return med
-
+    t.upload(img, src, dst)
+    t.upload(img[:HALF, :HALF], small)
+    t.tensors(SIZE, SIZE)
     cases = (("identity", src, (1.0, 0.0, 0.0, 1.0, 0.0, 0.0), None), ("rotate30", src, rotation(30, SIZE), None),
              ("up2", small, (2.0, 0.0, 0.0, 2.0, 0.0, 0.0), HALF))
     resample_of = {WarpFilter.BILINEAR: ResampleFilter.TRIANGLE, WarpFilter.BICUBIC: ResampleFilter.CATMULL_ROM}
     for label, rect in (("whole", (0, 0, SIZE, SIZE)), ("rect1024", RECT)):
         x, y, w, h = rect
         call_rect = None if label == "whole" else rect
-
-        def copy():
-            with torch.cuda.stream(stream):
-                tb[y:y + h, x:x + w].copy_(ta[y:y + h, x:x + w])
-
-        floor = record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, timed_blocks(stream, copy, a.blocks, a.per_block))
+        floor = t.record({"rect": label, "call": "device-to-device copy", "algorithmic_bytes": 16 * w * h}, t.timed(t.copy(rect)))
         for name, source, matrix, up_from in cases:
             for filt in WarpFilter:
                 launch = lambda: eng.warp(source, dst, matrix, filter=filt, edge=WarpEdge.ZERO, dst_rect=call_rect)  # noqa: E731
-                record({"rect": label, "call": "jh_warp", "case": name, "filter": filt.name, "taps": (1, 4, 16)[int(filt)]},
-                       timed_blocks(stream, launch, a.blocks, a.per_block), floor)
+                t.record({"rect": label, "call": "jh_warp", "case": name, "filter": filt.name, "taps": (1, 4, 16)[int(filt)]}, t.timed(launch), floor)
             if name == "rotate30":
                 continue
             # the same shape through jh_resample: the source rectangle the destination rectangle is the image of
@@ -85,20 +56,11 @@ def main():
             src_rect = None if label == "whole" else (x // k, y // k, w // k, h // k)
             for filt, rfilt in resample_of.items():
                 launch = lambda: eng.resample(source, dst, rfilt, src_rect=src_rect, dst_rect=call_rect)  # noqa: E731
-                record({"rect": label, "call": "jh_resample", "case": name, "filter": rfilt.name, "beside": filt.name},
-                       timed_blocks(stream, launch, a.blocks, a.per_block), floor)
-    for i in (src, small, dst):
-        eng.free_image(i)
-    eng.sync()
-    eng.set_stream(None)
-    eng.close()
-    out = {"tool": "tools/time_warp.py", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "per_block": a.per_block, "size": SIZE,
-           "note": "hipEvents around back-to-back jh_warp calls (one kernel each) into a 4096^2 image, premultiplied, edge ZERO; the copy is "
-                   "torch's copy_ of the same rectangle between two tensors of the image's shape, and jh_resample (two kernels) at the same "
-                   "shape is timed in the same run for the axis-aligned cases (its source rectangle is the destination rectangle's preimage, "
-                   "rounded down at the odd offset)",
-           "results": results}
-    write_json(a.out, out)
+                t.record({"rect": label, "call": "jh_resample", "case": name, "filter": rfilt.name, "beside": filt.name}, t.timed(launch), floor)
+    t.finish("hipEvents around back-to-back jh_warp calls (one kernel each) into a 4096^2 image, premultiplied, edge ZERO; the copy is "
+             "torch's copy_ of the same rectangle between two tensors of the image's shape, and jh_resample (two kernels) at the same "
+             "shape is timed in the same run for the axis-aligned cases (its source rectangle is the destination rectangle's preimage, "
+             "rounded down at the odd offset)", SIZE)
 
 
 if __name__ == "__main__":
