@@ -30,6 +30,7 @@
  *   jh_convolve                       (no counterpart: feConvolveMatrix on an RGBA16F image on the device)
  *   jh_lighting                       (no counterpart: feDiffuseLighting / feSpecularLighting on the device)
  *   jh_turbulence                     (no counterpart: feTurbulence noise into an RGBA16F image on the device)
+ *   jh_displace                       (no counterpart: feDisplacementMap on RGBA16F images on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -992,6 +993,64 @@ typedef struct jh_turb_plan {
 int jh_turbulence_plan(const jh_turbulence_desc* desc, jh_turb_plan* plan);
 int jh_turbulence_tables(const jh_turbulence_desc* desc, uint8_t* selector /* 256 or NULL */, float* gradients /* 2048 or NULL */);
 int jh_turbulence(jh_ctx* ctx, uint64_t dst_image_id, const jh_turbulence_desc* desc);
+
+/* ---- Displace: feDisplacementMap, a warp whose positions a second image moves texel by texel (DESIGN.md 5.17 "Displacement rule") ----
+ * Heat haze, ripples, a noise-roughened edge, frosted glass -- without the frame or the noise leaving the device.  The result is
+ * defined on values, and every implementation produces these bits (include/jello_displace.h states the host half,
+ * tests/displace_ref.py restates all of it).
+ *   arguments   matrix[6], filter, edge, flags (bit 0: JH_DISPLACE_STRAIGHT) and the source and destination rectangles: exactly
+ *               jh_warp_desc's, with the same meaning and the same legality -- the matrix takes continuous coordinates of the SOURCE
+ *               RECTANGLE to continuous coordinates of the DESTINATION IMAGE, and the identity is what feDisplacementMap needs.
+ *               scale_x, scale_y: binary32, finite, in texels of the source rectangle per unit of map value.  x_channel, y_channel:
+ *               JH_DISPLACE_R = 0 | _G = 1 | _B = 2 | _A = 3, which channel of the map moves which axis (they may be the same).
+ *   plan        jh_warp_plan's six integers P, Q, R, S, T, W, unchanged.
+ *   map         an RGBA16F image of the destination IMAGE's size.  For destination texel (X, Y) of the image the map value m is the
+ *               stored f16 of the chosen channel of the map's texel (X, Y), widened to binary32.  Stored texels are un-premultiplied,
+ *               which is what the specification asks of in2; JH_DISPLACE_STRAIGHT does not change how the map is read.  A map that
+ *               was never written reads 0 in every channel.  No colour-space conversion of the map.
+ *   offset      per axis: t = m - 0.5f (exact for every finite f16: at most 24 significant bits).  d = scale t, ONE binary32
+ *               product.  A NaN d (a NaN m, 0 x Inf) counts as +0; otherwise d is clamped to [-2^22, 2^22].  D = (int64) rint(d 2^32),
+ *               ties to even; the scaling and the conversion are exact after the clamp.
+ *   position    U = P (2 X + 1) + Q (2 Y + 1) + R + Dx, V = S (2 X + 1) + T (2 Y + 1) + W + Dy, int64, |U| < 2^56: the source position
+ *               in units of 2^-32 texel.  The displacement is in texels of the source rectangle and is added AFTER the affine map.
+ *               Under a translation (all the specification needs) that equals displacing in destination space; under a general
+ *               matrix it does not -- the rule does not apply the matrix's linear part to the displacement.
+ *   taps, edge, sum, store, values: jh_warp's, word for word, at (U, V): NEAREST is a floor, the fraction's low 16 bits are dropped,
+ *               BICUBIC's weights are jh_warp's; a tap index is resolved against the source RECTANGLE's extent; rows then columns
+ *               with single fmaf's; the operand is premultiplied unless JH_DISPLACE_STRAIGHT; the un-premultiplying store.
+ * So with scale = (0, 0), or with a map that is 0.5 in both chosen channels, the result is jh_warp's bit for bit; a constant map with
+ * scale t an integer is the integer translation by it; a call written in four quadrant rectangles equals the whole-image call.
+ *
+ * jh_displace_offset: D for one scale and one f16 bit pattern into *out.  Host only, no context; JH_ERR_INVALID for a null out (a
+ * non-finite scale is computed, by the rule's words; jh_displace refuses it).
+ *
+ * jh_displace: the rule from the rectangle (src_x, ...) of src_image_id into the rectangle (dst_x, ...) of dst_image_id, another
+ * image, moved by map_image_id.  THE MAP MAY BE THE DESTINATION: a texel's map value is read before that texel is written and by
+ * nothing else, so noise generated into an image (jh_turbulence) and then displaced over in place needs no third image.  The map may
+ * be the source too.  Only the destination rectangle is written; a dst that was never written is cleared to transparent black first
+ * (and, being the map as well, then reads 0) and then counts as written; a source that was never written reads as transparent black.
+ * Stream-ordered on the context's stream, never waits: ONE kernel launch, plus a fill when dst has to be cleared.  No scratch and
+ * no tables: the call is always capturable.  With profiling on the call is a query "displace" with stage = -1 in
+ * jh_profile_collect_tree.  Not in band mode (jh_set_band): the rows a tap reads belong to another rank's context.  JH_ERR_INVALID,
+ * with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_displace: ": everything jh_warp
+ * refuses (a null desc; an unknown source or destination id; an image that is not RGBA16F; an unknown filter, edge or flag bit; an
+ * illegal matrix; an image side above 32768; a rectangle that is not inside its image or that is empty in exactly one dimension;
+ * src_image_id == dst_image_id; a band); an unknown map id; a map that is not RGBA16F; a map whose size is not dst's; a channel
+ * outside 0..3; a scale that is not finite. */
+typedef enum jh_displace_channel { JH_DISPLACE_R = 0, JH_DISPLACE_G = 1, JH_DISPLACE_B = 2, JH_DISPLACE_A = 3 } jh_displace_channel;
+#define JH_DISPLACE_STRAIGHT 1u
+typedef struct jh_displace_desc {
+    double matrix[6];                                 /* (a, b, c, d, e, f): source rectangle -> destination image */
+    int filter;                                       /* jh_warp_filter */
+    int edge;                                         /* jh_warp_edge */
+    uint32_t flags;                                   /* bit 0: JH_DISPLACE_STRAIGHT */
+    uint32_t src_x, src_y, src_width, src_height;     /* source rectangle; width == height == 0: the whole image */
+    uint32_t dst_x, dst_y, dst_width, dst_height;     /* destination rectangle, likewise */
+    float scale_x, scale_y;                           /* texels of the source rectangle per unit of map value */
+    int x_channel, y_channel;                         /* jh_displace_channel */
+} jh_displace_desc;
+int jh_displace_offset(float scale, uint16_t f16_bits, int64_t* out);
+int jh_displace(jh_ctx* ctx, uint64_t src_image_id, uint64_t map_image_id, uint64_t dst_image_id, const jh_displace_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

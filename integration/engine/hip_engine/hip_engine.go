@@ -925,6 +925,57 @@ func (e *Engine) Turbulence(dst renderer.ImageProxy, desc TurbulenceDesc) {
 	e.check(C.jh_turbulence(e.ctx, C.uint64_t(dst.ID), &d), "turbulence")
 }
 
+// DisplaceChannel is jh_displace_channel: the channel of the map that moves an axis (feDisplacementMap's xChannelSelector and
+// yChannelSelector).
+type DisplaceChannel int32
+
+const (
+	DisplaceR DisplaceChannel = 0
+	DisplaceG DisplaceChannel = 1
+	DisplaceB DisplaceChannel = 2
+	DisplaceA DisplaceChannel = 3
+)
+
+// DisplaceStraight is JH_DISPLACE_STRAIGHT: the source's four channels are filtered as stored, not colour times alpha.
+const DisplaceStraight uint32 = 1
+
+// DisplaceDesc is jh_displace_desc (include/jello_hip.h "Displace"): WarpDesc's fields with WarpDesc's meaning -- the identity matrix
+// is what feDisplacementMap needs -- then the scales, in texels of the source rectangle per unit of map value, and the two channels.
+type DisplaceDesc struct {
+	Matrix                          [6]float64
+	Filter                          WarpFilter
+	Edge                            WarpEdge
+	Flags                           uint32
+	SrcX, SrcY, SrcWidth, SrcHeight uint32
+	DstX, DstY, DstWidth, DstHeight uint32
+	ScaleX, ScaleY                  float32
+	XChannel, YChannel              DisplaceChannel
+}
+
+// DisplaceOffset is jh_displace_offset: the displacement, in units of 2^-32 texel, that the map value with the f16 bit pattern bits
+// gives under scale -- rint(clamp(scale (m - 0.5), +-2^22) 2^32), a NaN product counting as 0 (DESIGN.md 5.17).  No context, no device.
+func DisplaceOffset(scale float32, bits uint16) int64 {
+	var out C.int64_t
+	C.jh_displace_offset(C.float(scale), C.uint16_t(bits), &out)
+	return int64(out)
+}
+
+// Displace is jh_displace: feDisplacementMap -- Warp of src into dst (another image) with every destination texel's source position
+// moved by scale x (m - 0.5), m the chosen channels of the texel at the same place of the RGBA16F image dmap, which has dst's size and
+// is read as stored -- by the rule of DESIGN.md 5.17 (defined on values: every implementation gives the same bits).  dmap may be dst
+// (noise generated into dst by Turbulence and displaced over in place) or src.  Stream-ordered behind the frame, waits for nothing,
+// one kernel launch, no scratch and no tables: always capturable.
+func (e *Engine) Displace(src, dmap, dst renderer.ImageProxy, desc DisplaceDesc) {
+	d := C.jh_displace_desc{filter: C.int(desc.Filter), edge: C.int(desc.Edge), flags: C.uint32_t(desc.Flags),
+		src_x: C.uint32_t(desc.SrcX), src_y: C.uint32_t(desc.SrcY), src_width: C.uint32_t(desc.SrcWidth), src_height: C.uint32_t(desc.SrcHeight),
+		dst_x: C.uint32_t(desc.DstX), dst_y: C.uint32_t(desc.DstY), dst_width: C.uint32_t(desc.DstWidth), dst_height: C.uint32_t(desc.DstHeight),
+		scale_x: C.float(desc.ScaleX), scale_y: C.float(desc.ScaleY), x_channel: C.int(desc.XChannel), y_channel: C.int(desc.YChannel)}
+	for i, m := range desc.Matrix {
+		d.matrix[i] = C.double(m)
+	}
+	e.check(C.jh_displace(e.ctx, C.uint64_t(src.ID), C.uint64_t(dmap.ID), C.uint64_t(dst.ID), &d), "displace")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -213,6 +213,14 @@ class CTurbPlan(ctypes.Structure):
                 ("width", ctypes.c_int32 * 2), ("max_extent", ctypes.c_uint32 * 2), ("key", ctypes.c_uint32), ("stitched", ctypes.c_uint32)]
 
 
+class CDisplaceDesc(ctypes.Structure):
+    """jh_displace_desc (include/jello_hip.h)."""
+    _fields_ = [("matrix", ctypes.c_double * 6), ("filter", ctypes.c_int32), ("edge", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("src_x", ctypes.c_uint32), ("src_y", ctypes.c_uint32), ("src_width", ctypes.c_uint32), ("src_height", ctypes.c_uint32),
+                ("dst_x", ctypes.c_uint32), ("dst_y", ctypes.c_uint32), ("dst_width", ctypes.c_uint32), ("dst_height", ctypes.c_uint32),
+                ("scale_x", ctypes.c_float), ("scale_y", ctypes.c_float), ("x_channel", ctypes.c_int32), ("y_channel", ctypes.c_int32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -290,6 +298,7 @@ def _declare(L):
     L.jl_lighting_tables.argtypes = [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)]
     L.jl_turbulence_plan.argtypes = [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)]
     L.jl_turbulence_tables.argtypes = [ctypes.POINTER(CTurbulenceDesc), vp, vp]
+    L.jl_displace_offset.argtypes = [ctypes.c_float, ctypes.c_uint16, ctypes.POINTER(ctypes.c_int64)]
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -345,6 +354,8 @@ def _declare(L):
     hip.jh_turbulence.argtypes = [vp, u64, ctypes.POINTER(CTurbulenceDesc)]
     hip.jh_turbulence_plan.argtypes = [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)]
     hip.jh_turbulence_tables.argtypes = [ctypes.POINTER(CTurbulenceDesc), vp, vp]
+    hip.jh_displace.argtypes = [vp, u64, u64, u64, ctypes.POINTER(CDisplaceDesc)]
+    hip.jh_displace_offset.argtypes = [ctypes.c_float, ctypes.c_uint16, ctypes.POINTER(ctypes.c_int64)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

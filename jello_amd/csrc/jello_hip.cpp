@@ -29,6 +29,7 @@
 #include "../../include/jello_convolve.h"
 #include "../../include/jello_lighting.h"
 #include "../../include/jello_turbulence.h"
+#include "../../include/jello_displace.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -1168,7 +1169,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1876,6 +1877,42 @@ int jh_turbulence(jh_ctx* ctx, uint64_t dst_image_id, const jh_turbulence_desc* 
             return launch_status(ctx, "jh_turbulence",
                                  jh_turbulence_launch(ctx->stream, {dst->ptr, dst->width, dst->height}, r, desc->kind, desc->octaves, &plan, ctx->turb.dev, ctx->num_cus));
         });
+}
+
+// displace (include/jello_hip.h "Displace"; the descriptor and the offset: include/jello_displace.h; the plan: include/jello_warp.h; kernels_displace.hip)
+int jh_displace_offset(float scale, uint16_t f16_bits, int64_t* out) {
+    if (!out) return JH_ERR_INVALID;
+    *out = jdisp_offset(scale, f16_bits);
+    return JH_OK;
+}
+int jh_displace(jh_ctx* ctx, uint64_t src_image_id, uint64_t map_image_id, uint64_t dst_image_id, const jh_displace_desc* desc) {
+    static_assert(JH_DISPLACE_R == JDISP_R && JH_DISPLACE_G == JDISP_G && JH_DISPLACE_B == JDISP_B && JH_DISPLACE_A == JDISP_A &&
+                      JH_DISPLACE_STRAIGHT == JDISP_STRAIGHT && JH_DISPLACE_STRAIGHT == JH_WARP_STRAIGHT,
+                  "the C ABI's values are the rule's");
+    Alloc *src = nullptr, *dst = nullptr, *map = nullptr;
+    if (int rc = image_call_images(ctx, "jh_displace", desc, src_image_id, dst_image_id, "a displacement in place reads what it writes", "the rows a tap reads belong to another rank", &src, &dst)) return rc;
+    if (int rc = rgba16f_images(ctx, "jh_displace", {{map_image_id, "map", &map}})) return rc;
+    if (const char* why = jdisp_desc_error(desc->filter, desc->edge, desc->flags, desc->scale_x, desc->scale_y, desc->x_channel, desc->y_channel, src->width,
+                                           src->height, map->width, map->height, dst->width, dst->height))
+        return fail(ctx, JH_ERR_INVALID, std::string("jh_displace: ") + why);
+    jimage_rect s, d;
+    if (int rc = image_call_rect(ctx, "jh_displace", {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, *src, "source ", &s)) return rc;
+    if (int rc = image_call_rect(ctx, "jh_displace", {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, *dst, "destination ", &d)) return rc;
+    int64_t plan[6];
+    if (const char* why = jwarp_plan(desc->matrix, plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_displace: illegal matrix: ") + why);
+    if (jimage_rect_empty(d)) return JH_OK;  // (an image without texels)
+    return post_render_call(ctx, "displace", [&] {
+        const jimage_src from_map = {content_or_null(*map), map->width, map->height};  // (taken first: the map may be dst, and a never-written one reads 0, not its memory)
+        ImageViews v;
+        if (int rc = image_call_views(ctx, src, dst, d, &v)) return rc;
+        if (jimage_rect_empty(s)) {  // a source without texels reads as transparent black: nothing is loaded, and the launcher gets a texel it can name
+            v.from = {nullptr, std::max(src->width, 1u), std::max(src->height, 1u)};
+            s = {s.x, s.y, std::max(s.w, 1u), std::max(s.h, 1u)};
+        }
+        return launch_status(ctx, "jh_displace",
+                             jh_displace_launch(ctx->stream, v.from, s, from_map, v.to, d, plan, desc->scale_x, desc->scale_y, desc->x_channel, desc->y_channel,
+                                                desc->filter, desc->edge, (desc->flags & JH_DISPLACE_STRAIGHT) != 0u, ctx->num_cus));
+    });
 }
 
 // Entries (or whole packs, counted once) jh_unpack_tiles has ignored since the last reset.  Synchronises the stream.

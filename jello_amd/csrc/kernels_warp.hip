@@ -15,6 +15,9 @@
 // direct 8-byte global loads, which assume no more alignment than a texel has.  The loads of a lane are unconditional (a tap ZERO
 // takes out reads the rectangle's nearest texel and is replaced by +0 afterwards), so all of them can be in flight together.
 // REPEAT and MIRROR divide once per axis and texel (the first tap's index) and step from there.
+// The taps of an axis (Taps, axis_taps) are warp_taps.h's, shared with kernels_displace.hip; that header's tap_sum is this kernel's load
+// and sum loop word for word, and the loop stays written out here because the helper's call changes this file's instructions (the
+// reason three loops of texel_io.h stay written out: DESIGN.md 5.8 and 5.17).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -22,6 +25,7 @@
 #include "../../include/jello_warp.h"
 #include "kcommon.h"
 #include "texel_io.h"
+#include "warp_taps.h"
 
 namespace {
 
@@ -36,51 +40,6 @@ struct WarpArgs {
     uint32_t dst_w, dx, dy, dw, dh;    // texels per row of the destination image; the destination rectangle
     uint32_t tiles_x, total;
 };
-
-template <int FILTER>
-struct Taps { static constexpr int N = FILTER == JWARP_NEAREST ? 1 : (FILTER == JWARP_BILINEAR ? 2 : 4); };
-
-// The taps of one axis at position U against the extent n: weights, the indices to load (always inside [0, n)) and whether the
-// operand is the loaded texel (false: ZERO's +0).
-template <int FILTER, int EDGE>
-JD void axis_taps(int64_t U, int32_t n, float (&w)[Taps<FILTER>::N], int32_t (&idx)[Taps<FILTER>::N], bool (&live)[Taps<FILTER>::N]) {
-    constexpr int N = Taps<FILTER>::N;
-    int32_t i0;
-    if (FILTER == JWARP_NEAREST) {
-        i0 = jwarp_nearest(U);
-        w[0] = 1.0f;
-    } else {
-        float f;
-        i0 = jwarp_split(U, &f);
-        if (FILTER == JWARP_BILINEAR) {
-            w[0] = 1.0f - f;
-            w[N - 1] = f;
-        } else {
-            float c[4];
-            jwarp_cubic_weights(f, c);
-#pragma unroll
-            for (int k = 0; k < N; k++) w[k] = c[k];
-            i0 -= 1;
-        }
-    }
-    if (EDGE == JWARP_EDGE_ZERO || EDGE == JWARP_EDGE_CLAMP) {
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            const int32_t i = i0 + k;
-            live[k] = EDGE == JWARP_EDGE_CLAMP || (i >= 0 && i < n);
-            idx[k] = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-        }
-    } else {
-        const int32_t period = EDGE == JWARP_EDGE_REPEAT ? n : 2 * n;
-        int32_t m = jwarp_mod(i0, period);
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            live[k] = true;
-            idx[k] = (EDGE == JWARP_EDGE_REPEAT || m < n) ? m : 2 * n - 1 - m;
-            m = m + 1 == period ? 0 : m + 1;
-        }
-    }
-}
 
 template <int FILTER, int EDGE, bool STRAIGHT>
 __global__ __launch_bounds__(kThreads) void k_warp(const WarpArgs a) {

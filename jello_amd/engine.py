@@ -9,7 +9,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CLightingDesc, CLightPlan, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CTurbPlan, CTurbulenceDesc, CWarpDesc, CYuvDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CDisplaceDesc, CLightingDesc, CLightPlan, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CTurbPlan, CTurbulenceDesc, CWarpDesc, CYuvDesc
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -396,6 +396,42 @@ def turbulence_tables(twin=False, **keywords):
     if (L.jl_turbulence_tables if twin else L.hip.jh_turbulence_tables)(ctypes.byref(d), selector.ctypes.data, gradients.ctypes.data) != 0:
         raise ValueError("jh_turbulence: illegal descriptor")
     return selector, gradients
+
+
+class DisplaceChannel(enum.IntEnum):
+    """jh_displace_channel: the channel of the map that moves an axis -- feDisplacementMap's xChannelSelector and
+    yChannelSelector."""
+    R = 0
+    G = 1
+    B = 2
+    A = 3
+
+
+DISPLACE_STRAIGHT = 1  # JH_DISPLACE_STRAIGHT
+AFFINE_IDENTITY = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)  # (a, b, c, d, e, f)
+
+
+def displace_offset(scale, bits, twin=False):
+    """jh_displace_offset (twin: jl_displace_offset, the host twin): D, the displacement in units of 2^-32 texel that the map value
+    with the f16 bit pattern `bits` gives under the binary32 `scale`, by the rule of DESIGN.md 5.17: rint(clamp(scale (m - 0.5)) 2^32), a
+    NaN product counting as 0.  No GPU needed."""
+    L = _lib.load_host()
+    out = ctypes.c_int64(0)
+    if (L.jl_displace_offset if twin else L.hip.jh_displace_offset)(float(np.float32(scale)), int(bits) & 0xFFFF, ctypes.byref(out)) != 0:
+        raise ValueError("jh_displace: null argument")
+    return int(out.value)
+
+
+def _displace_desc(scale, x_channel, y_channel, matrix, filter, edge, src_rect, dst_rect, premultiplied):
+    d = CDisplaceDesc()
+    d.matrix[:] = list(_matrix6(matrix))
+    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else DISPLACE_STRAIGHT
+    d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
+    d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
+    sx, sy = scale if isinstance(scale, (tuple, list)) else (scale, scale)
+    d.scale_x, d.scale_y = float(np.float32(sx)), float(np.float32(sy))
+    d.x_channel, d.y_channel = int(x_channel), int(y_channel)
+    return d
 
 
 class ColorSpace(enum.IntEnum):
@@ -871,6 +907,28 @@ class Engine:
         self.turbulence(scratch_id, base_frequency, octaves, seed, kind, stitch_tile, origin)
         self.lighting(scratch_id, dst_id, kind=LightKind.DIFFUSE, surface_scale=surface_scale, constant=kd, color=color, **light)
 
+    def displace(self, src_id, map_id, dst_id, scale, x_channel=DisplaceChannel.R, y_channel=DisplaceChannel.G, matrix=AFFINE_IDENTITY,
+                 filter=WarpFilter.BILINEAR, edge=WarpEdge.ZERO, src_rect=None, dst_rect=None, premultiplied=True):
+        """jh_displace: feDisplacementMap (the rule: DESIGN.md 5.17) -- warp() of the RGBA16F image `src_id` into the RGBA16F image
+        `dst_id` (another image) with every destination texel's source position moved by `scale` x (m - 0.5), m the `x_channel`
+        (`y_channel`) of the texel at the same place of the RGBA16F image `map_id`, which has dst's size; the map's channels are
+        read as stored (un-premultiplied).  `scale` is in texels of the source rectangle, one number or (x, y).  `matrix`, `filter`,
+        `edge`, `src_rect`, `dst_rect` and `premultiplied` are warp()'s; the identity is what the specification's primitive needs,
+        and under another matrix the displacement is added after the affine map, in source space.  `map_id` may be `dst_id`
+        (noise generated into dst and displaced over in place: distort()) or `src_id`.  One launch, no scratch: always
+        capturable.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _displace_desc(scale, x_channel, y_channel, matrix, filter, edge, src_rect, dst_rect, premultiplied)
+        self._check(self.hip.jh_displace(self.ctx, src_id, map_id, dst_id, ctypes.byref(d)), "displace", invalid=ValueError)
+
+    def distort(self, src_id, dst_id, scale, x_channel=DisplaceChannel.R, y_channel=DisplaceChannel.G, filter=WarpFilter.BILINEAR,
+                edge=WarpEdge.ZERO, premultiplied=True, **turbulence_keywords):
+        """The specification's usual pair (heat haze, ripples, a roughened edge) as two calls on RGBA16F images of one size:
+        turbulence(dst, **turbulence_keywords) -- `base_frequency` among them -- then displace(src, map = dst, dst, scale, ...): the
+        noise is the map and is overwritten texel by texel as it is used, so no third image is needed.  `src_id` is another image
+        than `dst_id`."""
+        self.turbulence(dst_id, **turbulence_keywords)
+        self.displace(src_id, dst_id, dst_id, scale, x_channel, y_channel, filter=filter, edge=edge, premultiplied=premultiplied)
+
     def place_layer(self, layer_id, target_id, matrix, scratch_image_id, layer_size, target_size, filter=WarpFilter.BILINEAR, **composite_keywords):
         """A cached layer onto a target under an affine transform, two calls: warp(layer -> scratch, edge ZERO, dst_rect =
         warp_bounds(...)): the layer in target space, written only where it can be other than transparent black;
@@ -1021,7 +1079,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None):
+                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -1060,9 +1118,14 @@ class Engine:
         turbulence=dict(dst=image id, ...) (the other keywords of turbulence(), `base_frequency` among them) generates noise into the
         RGBA16F image `dst` right after the frame and before every other step (one more launch), so that composite=dict(src=dst, ...)
         of the same capture can lay it over the frame; the frame's target stays what the later steps read.  Turbulence with this seed
-        must have run once eagerly, and none with another seed since."""
-        if resample is not None and warp is not None:
-            raise ValueError("capture: resample= and warp= are exclusive (both would feed the conversion)")
+        must have run once eagerly, and none with another seed since.
+        displace=dict(map=image id, dst=image id, width=..., height=..., scale=..., ...) (the other keywords of displace(),
+        optional) displaces the frame's target into the RGBA16F image `dst` of width x height by the RGBA16F image `map` of that
+        size where warp= would transform it (one more launch, nothing to run eagerly first); the conversion of the same capture
+        then reads `dst`.  It is exclusive with resample= and with warp=.  It runs after turbulence=, so one capture can make the
+        map (turbulence=dict(dst=m, ...)) and use it (displace=dict(map=m, ...)); `map` may be `dst`."""
+        if sum(step is not None for step in (resample, warp, displace)) > 1:
+            raise ValueError("capture: resample=, warp= and displace= are exclusive (each would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
@@ -1089,6 +1152,10 @@ class Engine:
             if warp is not None:
                 self.warp(t["id"], warp["dst"], warp["matrix"], **{k: v for k, v in warp.items() if k not in ("dst", "width", "height", "matrix")})
                 t = {"id": warp["dst"], "width": warp["width"], "height": warp["height"]}
+            if displace is not None:
+                self.displace(t["id"], displace["map"], displace["dst"], displace["scale"],
+                              **{k: v for k, v in displace.items() if k not in ("map", "dst", "width", "height", "scale")})
+                t = {"id": displace["dst"], "width": displace["width"], "height": displace["height"]}
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._blit(t["id"], ptr, pitch, t["width"], t["height"], fmt)

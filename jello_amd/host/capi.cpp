@@ -14,6 +14,7 @@
 #include "../../include/jello_convolve.h"
 #include "../../include/jello_lighting.h"
 #include "../../include/jello_turbulence.h"
+#include "../../include/jello_displace.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -527,6 +528,14 @@ int jl_turbulence_tables(const jh_turbulence_desc* desc, uint8_t* selector, floa
     const char* why = desc ? jturb_desc_error(desc) : "null descriptor";
     if (why) { g_err = std::string("turbulence_tables: ") + why; return -1; }
     jturb_tables(desc->seed, selector, gradients);
+    return 0;
+}
+
+// jl_displace_offset is the host twin of jh_displace_offset (the rule is in jello_hip.h and DESIGN.md 5.17): the same header, compiled
+// here by the host compiler -- D, the displacement in 2^-32 texel that one f16 map value gives under one scale; -1 for a null out.
+int jl_displace_offset(float scale, uint16_t f16_bits, int64_t* out) {
+    if (!out) { g_err = "displace_offset: null argument"; return -1; }
+    *out = jdisp_offset(scale, f16_bits);
     return 0;
 }
 
