@@ -1,6 +1,6 @@
 // jello_blur.h -- the host half of the blur rule (DESIGN.md 5.7 "Blur rule"): which sigma is legal, the radius, and the taps of
-// one axis, and the bytes of the intermediate.  Compiled by the library and the launcher (jello_amd/csrc/jello_hip.cpp: jh_blur_taps,
-// jh_blur; kernels_blur.hip: the intermediate), by the C++ host twin (jello_amd/host/capi.cpp: jl_blur_taps) and by tools/image_rect_check.cpp;
+// one axis, and the bytes of the intermediate.  Compiled by the library and the launcher (jello_amd/csrc/jello_hip.cpp:
+// jh_blur; kernels_blur.hip: the intermediate), by the query both libraries compile (include/jello_queries.h: jq_blur_taps) and by tools/image_rect_check.cpp;
 // tests/blur_ref.py restates it.  The device half -- the two fused-multiply-add sums over these taps -- is jello_amd/csrc/kernels_blur.hip.
 //
 //   sigma   given as binary32, used as binary64; legal: 0 <= sigma <= JBLUR_MAX_SIGMA (a NaN is not)

@@ -1,7 +1,7 @@
 // jello_color.h -- the host half of the colour-filter rule (DESIGN.md 5.10 "Colour-filter rule"): which descriptors are legal, which
 // tables a descriptor needs, and the tables themselves, one entry per f16 bit pattern.  Compiled by the library
-// (jello_amd/csrc/jello_hip.cpp: jh_color_tables, jh_color_filter) and by the C++ host twin (jello_amd/host/capi.cpp:
-// jl_color_tables) and by nothing else (tools/color_tables_check.cpp is its stand-alone check); tests/color_ref.py restates it.  The device half -- the table reads, the four fused steps of
+// (jello_amd/csrc/jello_hip.cpp: jh_color_filter), by the query both libraries compile (include/jello_queries.h: jq_color_tables, which
+// is jh_color_tables and its host twin jl_color_tables) and by nothing else (tools/color_tables_check.cpp is its stand-alone check); tests/color_ref.py restates it.  The device half -- the table reads, the four fused steps of
 // the matrix, the clamp and the one rounding to f16 -- is jello_amd/csrc/kernels_color.hip.
 //
 // binary64 throughout, nothing contracted; x is the value of the f16 bit pattern that indexes the entry:

@@ -1,6 +1,6 @@
 // jello_composite.h -- the host half of the composite rule (DESIGN.md 5.8 "Composite rule"): which source rectangle is legal and
-// where a placed rectangle lands in dst.  Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_composite), by the C++ host
-// twin (jello_amd/host/capi.cpp: jl_composite_clip), by tools/composite_clip_check.cpp, and by nothing else;
+// where a placed rectangle lands in dst.  Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_composite), by the host
+// library's query (include/jello_queries.h: jq_composite_clip, which is jl_composite_clip), by tools/composite_clip_check.cpp, and by nothing else;
 // tests/composite_ref.py restates it.  The device half -- the blend of the texels -- is jello_amd/csrc/kernels_composite.hip.
 //
 //   source rectangle   (sx, sy, sw, sh) inside the src_w x src_h image; sw == sh == 0: the whole image (sx, sy ignored);

@@ -1,8 +1,8 @@
 // jello_convolve.h -- the host half of the convolve rule (DESIGN.md 5.13 "Convolve rule"): which descriptor is legal (its rectangle
 // apart: jello_image.h), and the weights of an feConvolveMatrix: the 180-degree flip and the divisor, which the device never sees.
-// Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_convolve_weights, jh_convolve), by the kernels
+// Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_convolve), by the kernels
 // (jello_amd/csrc/kernels_convolve.hip: the limits; the index rules are jwarp_index of jello_warp.h, included here and not copied),
-// by the C++ host twin (jello_amd/host/capi.cpp: jl_convolve_weights) and by tools/convolve_check.cpp; tests/convolve_ref.py
+// by the query both libraries compile (include/jello_queries.h: jq_convolve_weights) and by tools/convolve_check.cpp; tests/convolve_ref.py
 // restates it.
 //
 //   weights   binary32, row-major with stride order_x, IN THE ORDER THEY ARE APPLIED: w[j][i] multiplies the operand at the image

@@ -1,7 +1,7 @@
 // jello_displace.h -- the host half of the displacement rule (DESIGN.md 5.17 "Displacement rule"): which descriptor is legal and the
-// offset one map value gives.  Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_displace, jh_displace_offset), by the kernels
+// offset one map value gives.  Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_displace), by the kernels
 // (jello_amd/csrc/kernels_displace.hip: jdisp_offset is the one text the device, the library and the stand-alone check compile), by
-// the C++ host twin (jello_amd/host/capi.cpp: jl_displace_offset) and by tools/displace_check.cpp; tests/displace_ref.py restates it.
+// the query both libraries compile (include/jello_queries.h: jq_displace_offset) and by tools/displace_check.cpp; tests/displace_ref.py restates it.
 // The matrix, the plan, the taps and the index rules are include/jello_warp.h's, unchanged.
 //
 //   map       m = the stored f16 of the chosen channel of the MAP's texel (X, Y), widened to binary32 (exact); un-premultiplied.

@@ -2,8 +2,8 @@
 // it): which descriptor is legal (its rectangle apart: jello_image.h), the plan -- the only place binary64 appears --, the power
 // tables, which of them a descriptor needs and the key they are resident under; and the part of the device half that has cases: the
 // surface normal's (span, wsum) selection, its side sums and the table's index rule, as functions the kernel compiles too.  Compiled by
-// the library (jello_amd/csrc/jello_hip.cpp: jh_lighting_plan, jh_lighting_tables, jh_lighting), by the kernel
-// (jello_amd/csrc/kernels_lighting.hip), by the C++ host twin (jello_amd/host/capi.cpp: jl_lighting_plan, jl_lighting_tables) and by
+// the library (jello_amd/csrc/jello_hip.cpp: jh_lighting), by the kernel
+// (jello_amd/csrc/kernels_lighting.hip), by the queries both libraries compile (include/jello_queries.h: jq_lighting_plan, jq_lighting_tables) and by
 // tools/lighting_check.cpp; tests/lighting_ref.py restates it.
 //
 //   s         s[span - 1][wsum - 2] = (float)(-(double)surface_scale * 2.0 / (double)(span * wsum)), span in {1, 2}, wsum in {2, 3, 4}:

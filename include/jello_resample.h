@@ -1,7 +1,7 @@
 // jello_resample.h -- the host half of the resample rule (DESIGN.md 5.9 "Resample rule"): which sizes are legal, and the window and
 // the taps of one output index of one axis, and the bytes of the intermediate.  Compiled by the library and the launcher
-// (jello_amd/csrc/jello_hip.cpp: jh_resample_taps, jh_resample; kernels_resample.hip: the intermediate), by the C++ host twin
-// (jello_amd/host/capi.cpp: jl_resample_taps) and by tools/image_rect_check.cpp; tests/resample_ref.py restates it.  The device half
+// (jello_amd/csrc/jello_hip.cpp: jh_resample; kernels_resample.hip: the intermediate), by the query both libraries compile
+// (include/jello_queries.h: jq_resample_taps) and by tools/image_rect_check.cpp; tests/resample_ref.py restates it.  The device half
 // -- the two fused-multiply-add sums over these taps -- is jello_amd/csrc/kernels_resample.hip.
 //
 // One axis, n_in source texels (the source RECTANGLE's extent) onto n_out; binary64 throughout, nothing contracted:

@@ -2,8 +2,8 @@
 // all of it): which descriptor is legal (its rectangle apart: jello_image.h), the generator, the tables and the key they are resident
 // under, the plan -- binary64 appears in the plan and the tables only --; and the part of the device half that has cases: the
 // cell / fraction split, the stitch step, the lattice walk, the s-curve, the dot and the lerp, as functions the kernel compiles too.
-// Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_turbulence_plan, jh_turbulence_tables, jh_turbulence), by the kernel
-// (jello_amd/csrc/kernels_turbulence.hip), by the C++ host twin (jello_amd/host/capi.cpp: jl_turbulence_plan, jl_turbulence_tables)
+// Compiled by the library (jello_amd/csrc/jello_hip.cpp: jh_turbulence), by the kernel
+// (jello_amd/csrc/kernels_turbulence.hip), by the queries both libraries compile (include/jello_queries.h: jq_turbulence_plan, jq_turbulence_tables)
 // and by tools/turbulence_check.cpp; tests/turbulence_ref.py restates it.
 //
 //   seed      the specification's setup_seed: s <= 0 becomes -(s mod (m - 1)) + 1 (the remainder C's, towards zero), s > m - 1 becomes

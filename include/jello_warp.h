@@ -1,8 +1,8 @@
 // jello_warp.h -- the host half of the warp rule (DESIGN.md 5.12 "Warp rule"): which matrix is legal, the six integers of the plan,
 // the per-axis taps and the four index rules, and the bounds rectangle.  Compiled by the library (jello_amd/csrc/jello_hip.cpp:
-// jh_warp_plan, jh_warp_bounds, jh_warp), by the kernels (jello_amd/csrc/kernels_warp.hip: the index rules, the fraction and the
-// cubic weights are the one text the device and the stand-alone check both compile), by the C++ host twin (jello_amd/host/capi.cpp:
-// jl_warp_plan, jl_warp_bounds) and by tools/warp_plan_check.cpp; tests/warp_ref.py restates it.
+// jh_warp), by the kernels (jello_amd/csrc/kernels_warp.hip: the index rules, the fraction and the
+// cubic weights are the one text the device and the stand-alone check both compile), by the queries both libraries compile
+// (include/jello_queries.h: jq_warp_plan, jq_warp_bounds) and by tools/warp_plan_check.cpp; tests/warp_ref.py restates it.
 //
 //   matrix    (a, b, c, d, e, f), binary64: x' = a x + c y + e, y' = b x + d y + f, from continuous coordinates of the source
 //             RECTANGLE (origin its top-left corner, texel (i, j) centred at (i + 0.5, j + 0.5)) to those of the destination IMAGE.

@@ -288,17 +288,22 @@ def _declare(L):
                                           ctypes.POINTER(ci)]
     u32, u64 = ctypes.c_uint32, ctypes.c_uint64
     L.jl_engine_read_pack.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(u64)]
-    L.jl_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
-    L.jl_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-    L.jl_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
-    L.jl_warp_plan.argtypes = [dp, ctypes.POINTER(ctypes.c_int64)]
-    L.jl_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
-    L.jl_convolve_weights.argtypes = [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
-    L.jl_lighting_plan.argtypes = [ctypes.POINTER(CLightingDesc), ctypes.POINTER(CLightPlan)]
-    L.jl_lighting_tables.argtypes = [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)]
-    L.jl_turbulence_plan.argtypes = [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)]
-    L.jl_turbulence_tables.argtypes = [ctypes.POINTER(CTurbulenceDesc), vp, vp]
-    L.jl_displace_offset.argtypes = [ctypes.c_float, ctypes.c_uint16, ctypes.POINTER(ctypes.c_int64)]
+    # the context-free queries of the image calls (include/jello_queries.h): jl_<name>, and below jh_<name>, take the same arguments
+    queries = {
+        "blur_taps": [ctypes.c_float, vp, ctypes.POINTER(u32)],
+        "resample_taps": [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)],
+        "color_tables": [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)],
+        "warp_plan": [dp, ctypes.POINTER(ctypes.c_int64)],
+        "warp_bounds": [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)],
+        "convolve_weights": [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)],
+        "lighting_plan": [ctypes.POINTER(CLightingDesc), ctypes.POINTER(CLightPlan)],
+        "lighting_tables": [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)],
+        "turbulence_plan": [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)],
+        "turbulence_tables": [ctypes.POINTER(CTurbulenceDesc), vp, vp],
+        "displace_offset": [ctypes.c_float, ctypes.c_uint16, ctypes.POINTER(ctypes.c_int64)],
+    }
+    for name, argtypes in queries.items():
+        getattr(L, "jl_" + name).argtypes = argtypes
     L.jl_composite_clip.argtypes = [u32, u32, u32, u32, u32, u32, ctypes.c_int32, ctypes.c_int32, u32, u32, ctypes.POINTER(u32)]
     # C ABI of libjello_hip.so (include/jello_hip.h), reachable through the same process image
     hip = ctypes.CDLL(lib_paths()["hip"])
@@ -335,27 +340,18 @@ def _declare(L):
     hip.jh_pack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u64]
     hip.jh_unpack_tiles.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32]
     hip.jh_dash.argtypes = [vp, ctypes.POINTER(PathEl), u64, ctypes.POINTER(CDashPath), u32, dp, u64, vp, u64, vp]
+    for name, argtypes in queries.items():
+        getattr(hip, "jh_" + name).argtypes = argtypes
     hip.jh_blur.argtypes = [vp, u64, u64, u32, u32, ctypes.POINTER(CBlurDesc)]
-    hip.jh_blur_taps.argtypes = [ctypes.c_float, vp, ctypes.POINTER(u32)]
     hip.jh_composite.argtypes = [vp, u64, u64, ctypes.POINTER(CCompositeDesc)]
     hip.jh_resample.argtypes = [vp, u64, u64, ctypes.POINTER(CResampleDesc)]
-    hip.jh_resample_taps.argtypes = [ci, u32, u32, u32, vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     hip.jh_color_filter.argtypes = [vp, u64, u64, ctypes.POINTER(CColorDesc)]
-    hip.jh_color_tables.argtypes = [ctypes.POINTER(CColorDesc), vp, vp, ctypes.POINTER(u32)]
     hip.jh_morphology.argtypes = [vp, u64, u64, ctypes.POINTER(CMorphDesc)]
     hip.jh_warp.argtypes = [vp, u64, u64, ctypes.POINTER(CWarpDesc)]
-    hip.jh_warp_plan.argtypes = [dp, ctypes.POINTER(ctypes.c_int64)]
-    hip.jh_warp_bounds.argtypes = [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)]
     hip.jh_convolve.argtypes = [vp, u64, u64, ctypes.POINTER(CConvolveDesc)]
-    hip.jh_convolve_weights.argtypes = [u32, u32, dp, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
     hip.jh_lighting.argtypes = [vp, u64, u64, ctypes.POINTER(CLightingDesc)]
-    hip.jh_lighting_plan.argtypes = [ctypes.POINTER(CLightingDesc), ctypes.POINTER(CLightPlan)]
-    hip.jh_lighting_tables.argtypes = [ctypes.POINTER(CLightingDesc), vp, vp, ctypes.POINTER(u32)]
     hip.jh_turbulence.argtypes = [vp, u64, ctypes.POINTER(CTurbulenceDesc)]
-    hip.jh_turbulence_plan.argtypes = [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)]
-    hip.jh_turbulence_tables.argtypes = [ctypes.POINTER(CTurbulenceDesc), vp, vp]
     hip.jh_displace.argtypes = [vp, u64, u64, u64, ctypes.POINTER(CDisplaceDesc)]
-    hip.jh_displace_offset.argtypes = [ctypes.c_float, ctypes.c_uint16, ctypes.POINTER(ctypes.c_int64)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -15,7 +15,7 @@ import math
 
 import numpy as np
 
-from .engine import ColorFunc, ColorSpace
+from .imagecalls import ColorFunc, ColorSpace
 
 
 def linear(slope, intercept=0.0):

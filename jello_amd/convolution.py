@@ -10,7 +10,7 @@ once to binary32.  The named kernels below are written in applied order; sobel_x
 with x and with y."""
 import numpy as np
 
-from .engine import ConvolveEdge, ConvolveMode, convolve_weights
+from .imagecalls import ConvolveEdge, ConvolveMode, convolve_weights
 
 EDGE_MODES = {"none": ConvolveEdge.ZERO, "duplicate": ConvolveEdge.CLAMP, "wrap": ConvolveEdge.REPEAT, "mirror": ConvolveEdge.MIRROR}
 

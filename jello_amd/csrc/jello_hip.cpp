@@ -30,6 +30,7 @@
 #include "../../include/jello_lighting.h"
 #include "../../include/jello_turbulence.h"
 #include "../../include/jello_displace.h"
+#include "../../include/jello_queries.h"
 #include "../../include/jello_dash_host.h"
 
 #ifndef JH_SCR_SKEW
@@ -1485,14 +1486,13 @@ int jh_dash(jh_ctx* ctx, const jh_dash_el* els, uint64_t n_els, const jh_dash_pa
         });
 }
 
-// blur (include/jello_hip.h "Gaussian blur", DESIGN 5.7; the taps: include/jello_blur.h; kernels_blur.hip)
-int jh_blur_taps(float sigma, float* weights, uint32_t* radius) {
-    if (!jblur_sigma_ok(sigma)) return JH_ERR_INVALID;
-    const uint32_t R = jblur_taps(sigma, weights);
-    if (radius) *radius = R;
-    return JH_OK;
-}
+// The context-free queries of the image calls (include/jello_hip.h, call by call): each is its one body in include/jello_queries.h,
+// which the host twin compiles too; the reason of a refusal stays there.
+#define JH_QUERY(name, params, args) int jh_##name params { return jq_##name args ? JH_ERR_INVALID : JH_OK; }
+JQ_QUERY_LIST(JH_QUERY)
+#undef JH_QUERY
 
+// blur (include/jello_hip.h "Gaussian blur", DESIGN 5.7; the taps: include/jello_blur.h; kernels_blur.hip)
 int jh_blur(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint32_t width, uint32_t height, const jh_blur_desc* desc) {
     Alloc *src = nullptr, *dst = nullptr;
     const uint32_t size[2] = {width, height};
@@ -1543,16 +1543,6 @@ int jh_composite(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, cons
 }
 
 // resample (include/jello_hip.h "Resample"; windows and taps: include/jello_resample.h; kernels_resample.hip)
-int jh_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, float* weights, uint32_t* first, uint32_t* count) {
-    if (!jresample_filter_ok(filter) || !jresample_sizes_ok(n_in, n_out) || i >= n_out) return JH_ERR_INVALID;
-    uint32_t f = 0u;
-    const uint32_t n = jresample_taps(filter, n_in, n_out, i, weights, &f, nullptr);
-    if (n == 0u) return JH_ERR_INVALID;
-    if (first) *first = f;
-    if (count) *count = n;
-    return JH_OK;
-}
-
 // The tables of one geometry as kernels_resample.hip reads them (JhResampleTables, kcommon.h), in one blob: [win_x][seg_x][w_x]
 // [win_y][w_y], each section on a 16-byte boundary.  false for a window without taps (the rule has none).
 struct ResampleBlob {
@@ -1651,13 +1641,6 @@ int jh_resample(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const
 }
 
 // colour filter (include/jello_hip.h "Colour filter"; the tables: include/jello_color.h; kernels_color.hip)
-int jh_color_tables(const jh_color_desc* desc, float* pre, uint16_t* post, uint32_t* which) {
-    if (!desc || jcolor_desc_error(desc)) return JH_ERR_INVALID;
-    const uint32_t w = jcolor_tables(desc, pre, post);
-    if (which) *which = w;
-    return JH_OK;
-}
-
 int jh_color_filter(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_color_desc* desc) {
     Alloc *src = nullptr, *dst = nullptr;
     if (int rc = image_call_images(ctx, "jh_color_filter", desc, src_image_id, dst_image_id, nullptr, "a band's rows are one rank's, the tables and their key the context's", &src, &dst)) return rc;
@@ -1723,14 +1706,6 @@ int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, con
 }
 
 // warp (include/jello_hip.h "Warp"; the plan, the bounds and the descriptor: include/jello_warp.h; kernels_warp.hip)
-int jh_warp_plan(const double matrix[6], int64_t plan[6]) {
-    if (!matrix || !plan) return JH_ERR_INVALID;
-    return jwarp_plan(matrix, plan) ? JH_ERR_INVALID : JH_OK;
-}
-int jh_warp_bounds(const double matrix[6], uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t rect[4]) {
-    if (!matrix || !rect) return JH_ERR_INVALID;
-    return jwarp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect) ? JH_ERR_INVALID : JH_OK;
-}
 int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_warp_desc* desc) {
     static_assert(JH_WARP_NEAREST == JWARP_NEAREST && JH_WARP_BILINEAR == JWARP_BILINEAR && JH_WARP_BICUBIC == JWARP_BICUBIC &&
                       JH_WARP_EDGE_ZERO == JWARP_EDGE_ZERO && JH_WARP_EDGE_CLAMP == JWARP_EDGE_CLAMP && JH_WARP_EDGE_REPEAT == JWARP_EDGE_REPEAT &&
@@ -1759,10 +1734,6 @@ int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_
 }
 
 // convolve (include/jello_hip.h "Convolve"; the descriptor and the weights: include/jello_convolve.h; kernels_convolve.hip)
-int jh_convolve_weights(uint32_t order_x, uint32_t order_y, const double* kernel_matrix, double divisor, float* weights) {
-    if (!kernel_matrix || !weights) return JH_ERR_INVALID;
-    return jconv_weights(order_x, order_y, kernel_matrix, divisor, weights) ? JH_ERR_INVALID : JH_OK;
-}
 int jh_convolve(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_convolve_desc* desc) {
     static_assert(JH_CONVOLVE_EDGE_ZERO == JCONV_EDGE_ZERO && JH_CONVOLVE_EDGE_CLAMP == JCONV_EDGE_CLAMP && JH_CONVOLVE_EDGE_REPEAT == JCONV_EDGE_REPEAT &&
                       JH_CONVOLVE_EDGE_MIRROR == JCONV_EDGE_MIRROR && JH_CONVOLVE_PREMULTIPLIED == JCONV_PREMULTIPLIED &&
@@ -1788,16 +1759,6 @@ int jh_convolve(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const
 }
 
 // lighting (include/jello_hip.h "Lighting"; the descriptor, the plan, the tables and the key: include/jello_lighting.h; kernels_lighting.hip)
-int jh_lighting_plan(const jh_lighting_desc* desc, jh_light_plan* plan) {
-    if (!desc || !plan) return JH_ERR_INVALID;
-    return jlight_plan(desc, plan) ? JH_ERR_INVALID : JH_OK;
-}
-int jh_lighting_tables(const jh_lighting_desc* desc, float* spec_table, float* spot_table, uint32_t* which) {
-    if (!desc || jlight_desc_error(desc)) return JH_ERR_INVALID;
-    const uint32_t w = jlight_tables(desc, spec_table, spot_table);
-    if (which) *which = w;
-    return JH_OK;
-}
 int jh_lighting(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_lighting_desc* desc) {
     static_assert(JH_LIGHTING_DIFFUSE == JLIGHT_DIFFUSE && JH_LIGHTING_SPECULAR == JLIGHT_SPECULAR && JH_LIGHT_DISTANT == JLIGHT_DISTANT &&
                       JH_LIGHT_POINT == JLIGHT_POINT && JH_LIGHT_SPOT == JLIGHT_SPOT && JH_LIGHTING_TABLE_ENTRIES == JLIGHT_ENTRIES &&
@@ -1839,15 +1800,6 @@ int jh_lighting(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const
 }
 
 // turbulence (include/jello_hip.h "Turbulence"; the descriptor, the generator, the tables, the plan and the key: include/jello_turbulence.h; kernels_turbulence.hip)
-int jh_turbulence_plan(const jh_turbulence_desc* desc, jh_turb_plan* plan) {
-    if (!desc || !plan) return JH_ERR_INVALID;
-    return jturb_plan(desc, plan) ? JH_ERR_INVALID : JH_OK;
-}
-int jh_turbulence_tables(const jh_turbulence_desc* desc, uint8_t* selector, float* gradients) {
-    if (!desc || jturb_desc_error(desc)) return JH_ERR_INVALID;
-    jturb_tables(desc->seed, selector, gradients);
-    return JH_OK;
-}
 int jh_turbulence(jh_ctx* ctx, uint64_t dst_image_id, const jh_turbulence_desc* desc) {
     static_assert(JH_TURBULENCE_FRACTAL_NOISE == JTURB_FRACTAL_NOISE && JH_TURBULENCE_TURBULENCE == JTURB_TURBULENCE && JH_TURBULENCE_MAX_OCTAVES == JTURB_MAX_OCTAVES,
                   "the C ABI's values are the rule's");
@@ -1880,11 +1832,6 @@ int jh_turbulence(jh_ctx* ctx, uint64_t dst_image_id, const jh_turbulence_desc* 
 }
 
 // displace (include/jello_hip.h "Displace"; the descriptor and the offset: include/jello_displace.h; the plan: include/jello_warp.h; kernels_displace.hip)
-int jh_displace_offset(float scale, uint16_t f16_bits, int64_t* out) {
-    if (!out) return JH_ERR_INVALID;
-    *out = jdisp_offset(scale, f16_bits);
-    return JH_OK;
-}
 int jh_displace(jh_ctx* ctx, uint64_t src_image_id, uint64_t map_image_id, uint64_t dst_image_id, const jh_displace_desc* desc) {
     static_assert(JH_DISPLACE_R == JDISP_R && JH_DISPLACE_G == JDISP_G && JH_DISPLACE_B == JDISP_B && JH_DISPLACE_A == JDISP_A &&
                       JH_DISPLACE_STRAIGHT == JDISP_STRAIGHT && JH_DISPLACE_STRAIGHT == JH_WARP_STRAIGHT,

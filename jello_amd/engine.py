@@ -9,7 +9,17 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConfig, CConvolveDesc, CDisplaceDesc, CLightingDesc, CLightPlan, CMorphDesc, CProfileNode, CProfileRecord, CResampleDesc, CTurbPlan, CTurbulenceDesc, CWarpDesc, CYuvDesc
+from ._lib import CConfig, CProfileNode, CProfileRecord, CYuvDesc
+# the image calls' enums, constants, descriptor builders and queries; imported whole, so that they stay reachable as engine.<name>
+from .imagecalls import (  # noqa: F401
+    BlurEdge, BLUR_MAX_SIGMA, blur_taps, _rect, _blur_desc, COMPOSITE_TINT, _composite_desc, ResampleFilter, RESAMPLE_STRAIGHT, RESAMPLE_MAX_TAPS,
+    resample_taps, _resample_desc, MorphOp, MorphEdge, MORPH_STRAIGHT, MORPH_MAX_RADIUS, _morph_desc, WarpFilter, WarpEdge, WARP_STRAIGHT, WARP_MAX_SIDE,
+    _matrix6, warp_plan, warp_bounds, _warp_desc, ConvolveEdge, ConvolveMode, CONVOLVE_MAX_ORDER, CONVOLVE_MAX_TAPS, _order2, convolve_weights,
+    _convolve_desc, LightKind, LightSource, LIGHTING_TABLE_ENTRIES, LIGHTING_TABLE_SPEC, LIGHTING_TABLE_SPOT, _vec3, _lighting_desc, lighting_plan,
+    lighting_tables, TurbulenceKind, TURBULENCE_MAX_OCTAVES, _pair, _turbulence_desc, turbulence_plan, turbulence_tables, DisplaceChannel,
+    DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
+    IDENTITY_MATRIX, _color_desc, color_tables, composite_clip,
+)
 from .scene import Compose, Mix
 
 STAGE_NAMES = ["pathtag_reduce", "pathtag_reduce2", "pathtag_scan1", "pathtag_scan_small", "pathtag_scan_large", "bbox_clear",
@@ -58,462 +68,6 @@ class YuvTransfer(enum.IntEnum):
     """jh_yuv_transfer: the R'G'B' codes are those of Surface.RGBA8_UNORM (NONE) or Surface.RGBA8_SRGB (SRGB)."""
     NONE = 0
     SRGB = 1
-
-
-class BlurEdge(enum.IntEnum):
-    """jh_blur_edge: what a tap outside the image reads -- nothing (ZERO), or the nearest texel of the image (CLAMP)."""
-    ZERO = 0
-    CLAMP = 1
-
-
-BLUR_MAX_SIGMA = 64.0
-
-
-def blur_taps(sigma):
-    """jh_blur_taps: (weights, R) of one axis of the blur rule -- the 2R + 1 float32 taps w[-R..R] of `sigma` and
-    R = ceil(3 sigma).  No GPU needed.  ValueError for a sigma that is negative, above 64 or NaN."""
-    hip = _lib.load_host().hip
-    sigma = float(np.float32(sigma))
-    r = ctypes.c_uint32(0)
-    if hip.jh_blur_taps(sigma, None, ctypes.byref(r)) != 0:
-        raise ValueError("blur_taps: sigma is negative, above 64 or NaN")
-    w = np.empty(2 * r.value + 1, dtype=np.float32)
-    hip.jh_blur_taps(sigma, w.ctypes.data, None)
-    return w, r.value
-
-
-def _rect(rect):  # (x, y, width, height) as a descriptor takes it: four ints, 0 x 0 -- the whole image -- for None
-    x, y, w, h = (0, 0, 0, 0) if rect is None else rect
-    return int(x), int(y), int(w), int(h)
-
-
-def _blur_desc(sigma, edge, rect):
-    sx, sy = sigma if isinstance(sigma, (tuple, list)) else (sigma, sigma)
-    return CBlurDesc(float(sx), float(sy), int(edge), *_rect(rect))
-
-
-COMPOSITE_TINT = 1  # JH_COMPOSITE_TINT
-
-
-def _composite_desc(mix, compose, opacity, tint, src_rect, offset):
-    d = CCompositeDesc(int(mix), int(compose), float(opacity), 0 if tint is None else COMPOSITE_TINT)
-    if tint is not None:
-        d.tint[:] = [float(v) for v in tint]
-    d.sx, d.sy, d.sw, d.sh = _rect(src_rect)
-    d.dx, d.dy = int(offset[0]), int(offset[1])
-    return d
-
-
-class ResampleFilter(enum.IntEnum):
-    """jh_resample_filter: the kernel of jh_resample, by its support at 1:1 -- 0.5, 1, 2 and 3 texels."""
-    BOX = 0
-    TRIANGLE = 1
-    CATMULL_ROM = 2
-    LANCZOS3 = 3
-
-
-RESAMPLE_STRAIGHT = 1  # JH_RESAMPLE_STRAIGHT
-RESAMPLE_MAX_TAPS = 96  # JH_RESAMPLE_MAX_TAPS
-
-
-def resample_taps(filter, n_in, n_out):
-    """jh_resample_taps for every output index of one axis of the resample rule, n_in source texels onto n_out: a
-    list of (first, weights) -- the window's first source index and its float32 taps.  No GPU needed.  ValueError for an unknown
-    filter or sizes outside 1 <= n_in <= 16 n_out."""
-    hip = _lib.load_host().hip
-    out = []
-    w = np.empty(RESAMPLE_MAX_TAPS, dtype=np.float32)
-    first, count = ctypes.c_uint32(0), ctypes.c_uint32(0)
-    for i in range(max(int(n_out), 1)):
-        if hip.jh_resample_taps(int(filter), int(n_in), int(n_out), i, w.ctypes.data, ctypes.byref(first), ctypes.byref(count)) != 0:
-            raise ValueError("resample_taps: unknown filter, or sizes outside 1 <= n_in <= 16 n_out")
-        out.append((first.value, w[:count.value].copy()))
-    return out
-
-
-def _resample_desc(filter, src_rect, dst_rect, premultiplied):
-    return CResampleDesc(int(filter), 0 if premultiplied else RESAMPLE_STRAIGHT, *_rect(src_rect), *_rect(dst_rect))
-
-
-class MorphOp(enum.IntEnum):
-    """jh_morph_op: the least (ERODE) or the greatest (DILATE) operand of the window."""
-    ERODE = 0
-    DILATE = 1
-
-
-class MorphEdge(enum.IntEnum):
-    """jh_morph_edge: a position outside the image takes part as transparent black (ZERO) or not at all (CLAMP)."""
-    ZERO = 0
-    CLAMP = 1
-
-
-MORPH_STRAIGHT = 1  # JH_MORPH_STRAIGHT
-MORPH_MAX_RADIUS = 255  # JH_MORPH_MAX_RADIUS
-
-
-def _morph_desc(op, radius, edge, rect, premultiplied):
-    rx, ry = radius if isinstance(radius, (tuple, list)) else (radius, radius)
-    if not (0 <= int(rx) <= MORPH_MAX_RADIUS and 0 <= int(ry) <= MORPH_MAX_RADIUS):
-        raise ValueError("jh_morphology: a radius above 255 or below 0")
-    return CMorphDesc(int(op), int(edge), 0 if premultiplied else MORPH_STRAIGHT, int(rx), int(ry), *_rect(rect))
-
-
-class WarpFilter(enum.IntEnum):
-    """jh_warp_filter: the taps of jh_warp -- 1, 2 x 2 and 4 x 4 (Catmull-Rom) source texels."""
-    NEAREST = 0
-    BILINEAR = 1
-    BICUBIC = 2
-
-
-class WarpEdge(enum.IntEnum):
-    """jh_warp_edge: what a tap outside the source rectangle reads -- transparent black, the nearest texel, the rectangle tiled, the
-    rectangle tiled with every other copy flipped."""
-    ZERO = 0
-    CLAMP = 1
-    REPEAT = 2
-    MIRROR = 3
-
-
-WARP_STRAIGHT = 1  # JH_WARP_STRAIGHT
-WARP_MAX_SIDE = 32768  # JH_WARP_MAX_SIDE
-
-
-def _matrix6(matrix):
-    m = [float(v) for v in matrix]
-    if len(m) != 6:
-        raise ValueError("jh_warp: the matrix has 6 entries (a, b, c, d, e, f)")
-    return (ctypes.c_double * 6)(*m)
-
-
-def warp_plan(matrix, twin=False):
-    """jh_warp_plan (twin: jl_warp_plan, the host twin): the six integers (P, Q, R, S, T, W) of the warp rule for
-    `matrix` = (a, b, c, d, e, f), source rectangle -> destination image.  No GPU needed.  ValueError for an illegal matrix."""
-    L = _lib.load_host()
-    plan = (ctypes.c_int64 * 6)()
-    if (L.jl_warp_plan if twin else L.hip.jh_warp_plan)(_matrix6(matrix), plan) != 0:
-        raise ValueError("jh_warp: illegal matrix (an entry not finite, a determinant that is 0 or not finite, an inverse coefficient "
-                         "above 64 or an inverse offset above 2^22)")
-    return tuple(int(v) for v in plan)
-
-
-def warp_bounds(matrix, src_size, filter, dst_size, twin=False):
-    """jh_warp_bounds (twin: jl_warp_bounds): the rectangle (x, y, width, height) of a destination of `dst_size` = (width, height)
-    outside which a warp of a source rectangle of `src_size` under WarpEdge.ZERO is transparent black; (0, 0, 0, 0) when nothing is
-    left.  No GPU needed.  ValueError for an illegal matrix, an unknown filter or a side above 32768."""
-    L = _lib.load_host()
-    rect = (ctypes.c_uint32 * 4)()
-    f = L.jl_warp_bounds if twin else L.hip.jh_warp_bounds
-    if f(_matrix6(matrix), int(src_size[0]), int(src_size[1]), int(filter), int(dst_size[0]), int(dst_size[1]), rect) != 0:
-        raise ValueError("jh_warp: illegal matrix, unknown filter or a side above 32768")
-    return tuple(int(v) for v in rect)
-
-
-def _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
-    d = CWarpDesc()
-    d.matrix[:] = list(_matrix6(matrix))
-    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else WARP_STRAIGHT
-    d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
-    d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
-    return d
-
-
-class ConvolveEdge(enum.IntEnum):
-    """jh_convolve_edge: what a tap outside the image reads -- feConvolveMatrix's edgeMode none, duplicate and wrap,
-    and the image mirrored; WarpEdge's values."""
-    ZERO = 0
-    CLAMP = 1
-    REPEAT = 2
-    MIRROR = 3
-
-
-class ConvolveMode(enum.IntEnum):
-    """jh_convolve_mode: the operand of jh_convolve -- colour times alpha (what feConvolveMatrix is defined on), the four channels as
-    stored, or the colour channels as stored with the source's alpha copied (preserveAlpha)."""
-    PREMULTIPLIED = 0
-    STRAIGHT = 1
-    PRESERVE_ALPHA = 2
-
-
-CONVOLVE_MAX_ORDER = 15  # JH_CONVOLVE_MAX_ORDER
-CONVOLVE_MAX_TAPS = 225  # JH_CONVOLVE_MAX_TAPS
-
-
-def _order2(order, what="order"):
-    ox, oy = order if isinstance(order, (tuple, list)) else (order, order)
-    if int(ox) != ox or int(oy) != oy or int(ox) < 0 or int(oy) < 0:
-        raise ValueError("jh_convolve: the %s is a non-negative integer or a pair of them" % what)
-    return int(ox), int(oy)
-
-
-def convolve_weights(order, kernel_matrix, divisor=0.0, twin=False):
-    """jh_convolve_weights (twin: jl_convolve_weights, the host twin): the float32 weights (order_y, order_x) jh_convolve applies for
-    feConvolveMatrix's `kernel_matrix` (order_x * order_y values, row-major) and `divisor` (0: the sum of the matrix, or 1 if that is
-    0) -- flipped by 180 degrees and divided.  `order` is a scalar or (order_x, order_y).  No GPU needed.  ValueError
-    for an order outside 1..15, a non-finite input or a weight that does not come out finite."""
-    L = _lib.load_host()
-    ox, oy = _order2(order)
-    km = [float(v) for v in np.asarray(kernel_matrix, np.float64).ravel()]
-    if not (1 <= ox <= CONVOLVE_MAX_ORDER and 1 <= oy <= CONVOLVE_MAX_ORDER) or len(km) != ox * oy:
-        raise ValueError("jh_convolve: an order outside 1..15, or a kernelMatrix that does not have order_x * order_y entries")
-    w = (ctypes.c_float * (ox * oy))()
-    if (L.jl_convolve_weights if twin else L.hip.jh_convolve_weights)(ox, oy, (ctypes.c_double * len(km))(*km), float(divisor), w) != 0:
-        raise ValueError("jh_convolve: illegal kernelMatrix or divisor (an entry not finite, or a weight that does not come out finite)")
-    return np.array(w, np.float32).reshape(oy, ox)
-
-
-def _convolve_desc(weights, order, target, edge, mode, bias, rect):
-    w = np.asarray(weights, np.float32)
-    if order is None:
-        if w.ndim != 2:
-            raise ValueError("jh_convolve: weights without an order are a two-dimensional array (order_y, order_x)")
-        order = (w.shape[1], w.shape[0])
-    ox, oy = _order2(order)
-    w = w.ravel()
-    if not (1 <= ox <= CONVOLVE_MAX_ORDER and 1 <= oy <= CONVOLVE_MAX_ORDER):
-        raise ValueError("jh_convolve: an order outside 1..15")
-    if w.size != ox * oy:
-        raise ValueError("jh_convolve: %d weights for an order of %d x %d" % (w.size, ox, oy))
-    tx, ty = (ox // 2, oy // 2) if target is None else _order2(target, "target")
-    d = CConvolveDesc(ox, oy, tx, ty, int(edge), int(mode), float(bias), *_rect(rect))
-    d.weights[:ox * oy] = [float(v) for v in w]
-    return d
-
-
-class LightKind(enum.IntEnum):
-    """jh_lighting_kind: feDiffuseLighting or feSpecularLighting."""
-    DIFFUSE = 0
-    SPECULAR = 1
-
-
-class LightSource(enum.IntEnum):
-    """jh_light_source: feDistantLight, fePointLight, feSpotLight."""
-    DISTANT = 0
-    POINT = 1
-    SPOT = 2
-
-
-LIGHTING_TABLE_ENTRIES = 4097  # JH_LIGHTING_TABLE_ENTRIES
-LIGHTING_TABLE_SPEC, LIGHTING_TABLE_SPOT = 1, 2  # jh_lighting_tables' `which`
-
-
-def _vec3(v, what):
-    v = tuple(float(c) for c in v)
-    if len(v) != 3:
-        raise ValueError("jh_lighting: %s has three components" % what)
-    return v
-
-
-def _lighting_desc(kind=LightKind.DIFFUSE, light=LightSource.DISTANT, surface_scale=1.0, constant=1.0, specular_exponent=1.0, color=(1.0, 1.0, 1.0),
-                   direction=(0.0, 0.0, 1.0), position=(0.0, 0.0, 0.0), points_at=(0.0, 0.0, 0.0), spot_exponent=1.0, cone_cos=-1.0, rect=None):
-    """jh_lighting_desc.  What the rule refuses is left for the call to refuse."""
-    d = CLightingDesc()
-    d.kind, d.light = int(kind), int(light)
-    d.surface_scale, d.constant, d.specular_exponent, d.spot_exponent = float(surface_scale), float(constant), float(specular_exponent), float(spot_exponent)
-    d.color[:] = _vec3(color, "color")
-    d.x, d.y, d.width, d.height = _rect(rect)
-    d.direction[:] = _vec3(direction, "direction")
-    d.position[:] = _vec3(position, "position")
-    d.points_at[:] = _vec3(points_at, "points_at")
-    d.cone_cos = float(cone_cos)
-    return d
-
-
-def lighting_plan(twin=False, **keywords):
-    """jh_lighting_plan (twin: jl_lighting_plan, the host twin): the plan of the lighting rule for the keywords of
-    Engine.lighting -- dict(s=float32 (2, 3) indexed [span - 1][wsum - 2], ldir, p, sdir = float32 (3,), cone = float32).  No GPU needed.
-    ValueError for a descriptor the rule refuses."""
-    L = _lib.load_host()
-    d, plan = _lighting_desc(**keywords), CLightPlan()
-    if (L.jl_lighting_plan if twin else L.hip.jh_lighting_plan)(ctypes.byref(d), ctypes.byref(plan)) != 0:
-        raise ValueError("jh_lighting: illegal descriptor")
-    return dict(s=np.array(plan.s, np.float32).reshape(2, 3), ldir=np.array(plan.ldir, np.float32), p=np.array(plan.p, np.float32),
-                sdir=np.array(plan.sdir, np.float32), cone=np.float32(plan.cone))
-
-
-def lighting_tables(twin=False, **keywords):
-    """jh_lighting_tables (twin: jl_lighting_tables): (spec, spot, which) -- the power tables the keywords of Engine.lighting need, float32
-    [4097] each or None where the exponent is 1 or is not in use, and the bit mask.  No GPU needed.  ValueError as lighting_plan."""
-    L = _lib.load_host()
-    d = _lighting_desc(**keywords)
-    spec, spot = np.zeros(LIGHTING_TABLE_ENTRIES, np.float32), np.zeros(LIGHTING_TABLE_ENTRIES, np.float32)
-    which = ctypes.c_uint32(0)
-    if (L.jl_lighting_tables if twin else L.hip.jh_lighting_tables)(ctypes.byref(d), spec.ctypes.data, spot.ctypes.data, ctypes.byref(which)) != 0:
-        raise ValueError("jh_lighting: illegal descriptor")
-    w = which.value
-    return (spec if w & LIGHTING_TABLE_SPEC else None, spot if w & LIGHTING_TABLE_SPOT else None, w)
-
-
-class TurbulenceKind(enum.IntEnum):
-    """jh_turbulence_kind: feTurbulence's type."""
-    FRACTAL_NOISE = 0
-    TURBULENCE = 1
-
-
-TURBULENCE_MAX_OCTAVES = 16  # JH_TURBULENCE_MAX_OCTAVES
-
-
-def _pair(v, what):
-    v = (v, v) if isinstance(v, (int, float)) else tuple(v)
-    if len(v) != 2:
-        raise ValueError("jh_turbulence: %s has two components" % what)
-    return float(v[0]), float(v[1])
-
-
-def _turbulence_desc(base_frequency=0.0, octaves=1, seed=0, kind=TurbulenceKind.TURBULENCE, stitch_tile=None, origin=(0.0, 0.0), rect=None):
-    """jh_turbulence_desc.  What the rule refuses is left for the call to refuse."""
-    d = CTurbulenceDesc()
-    d.kind, d.octaves, d.seed, d.stitch = int(kind), int(octaves), int(seed), 0 if stitch_tile is None else 1
-    d.x, d.y, d.width, d.height = _rect(rect)
-    d.base_frequency[:] = _pair(base_frequency, "base_frequency")
-    if stitch_tile is not None:
-        tile = tuple(float(c) for c in stitch_tile)
-        if len(tile) != 4:
-            raise ValueError("jh_turbulence: stitch_tile has four components (x, y, width, height)")
-        d.tile[:] = tile
-    d.origin[:] = _pair(origin, "origin")
-    return d
-
-
-def turbulence_plan(twin=False, **keywords):
-    """jh_turbulence_plan (twin: jl_turbulence_plan, the host twin): the plan of the turbulence rule for the keywords of
-    Engine.turbulence -- dict(frequency=float64 (2,), step, start = int64 (2,), wrap, width = int32 (2,), max_extent = uint32 (2,), key,
-    stitched).  No GPU needed.  ValueError for a descriptor the rule refuses."""
-    L = _lib.load_host()
-    d, plan = _turbulence_desc(**keywords), CTurbPlan()
-    if (L.jl_turbulence_plan if twin else L.hip.jh_turbulence_plan)(ctypes.byref(d), ctypes.byref(plan)) != 0:
-        raise ValueError("jh_turbulence: illegal descriptor")
-    return dict(frequency=np.array(plan.frequency, np.float64), step=np.array(plan.step, np.int64), start=np.array(plan.start, np.int64),
-                wrap=np.array(plan.wrap, np.int32), width=np.array(plan.width, np.int32), max_extent=np.array(plan.max_extent, np.uint32),
-                key=int(plan.key), stitched=int(plan.stitched))
-
-
-def turbulence_tables(twin=False, **keywords):
-    """jh_turbulence_tables (twin: jl_turbulence_tables): (selector, gradients) -- P, uint8 [256], and G, float32 [4][256][2], of the seed
-    among the keywords of Engine.turbulence.  No GPU needed.  ValueError as turbulence_plan."""
-    L = _lib.load_host()
-    d = _turbulence_desc(**keywords)
-    selector, gradients = np.zeros(256, np.uint8), np.zeros((4, 256, 2), np.float32)
-    if (L.jl_turbulence_tables if twin else L.hip.jh_turbulence_tables)(ctypes.byref(d), selector.ctypes.data, gradients.ctypes.data) != 0:
-        raise ValueError("jh_turbulence: illegal descriptor")
-    return selector, gradients
-
-
-class DisplaceChannel(enum.IntEnum):
-    """jh_displace_channel: the channel of the map that moves an axis -- feDisplacementMap's xChannelSelector and
-    yChannelSelector."""
-    R = 0
-    G = 1
-    B = 2
-    A = 3
-
-
-DISPLACE_STRAIGHT = 1  # JH_DISPLACE_STRAIGHT
-AFFINE_IDENTITY = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)  # (a, b, c, d, e, f)
-
-
-def displace_offset(scale, bits, twin=False):
-    """jh_displace_offset (twin: jl_displace_offset, the host twin): D, the displacement in units of 2^-32 texel that the map value
-    with the f16 bit pattern `bits` gives under the binary32 `scale`, by the rule of DESIGN.md 5.17: rint(clamp(scale (m - 0.5)) 2^32), a
-    NaN product counting as 0.  No GPU needed."""
-    L = _lib.load_host()
-    out = ctypes.c_int64(0)
-    if (L.jl_displace_offset if twin else L.hip.jh_displace_offset)(float(np.float32(scale)), int(bits) & 0xFFFF, ctypes.byref(out)) != 0:
-        raise ValueError("jh_displace: null argument")
-    return int(out.value)
-
-
-def _displace_desc(scale, x_channel, y_channel, matrix, filter, edge, src_rect, dst_rect, premultiplied):
-    d = CDisplaceDesc()
-    d.matrix[:] = list(_matrix6(matrix))
-    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else DISPLACE_STRAIGHT
-    d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
-    d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
-    sx, sy = scale if isinstance(scale, (tuple, list)) else (scale, scale)
-    d.scale_x, d.scale_y = float(np.float32(sx)), float(np.float32(sy))
-    d.x_channel, d.y_channel = int(x_channel), int(y_channel)
-    return d
-
-
-class ColorSpace(enum.IntEnum):
-    """jh_color_space: the values the matrix and the funcs of jh_color_filter act on -- the stored linear ones,
-    or the colour channels sRGB-encoded (what the CSS filter functions are defined on); alpha is never encoded."""
-    LINEAR = 0
-    SRGB = 1
-
-
-class ColorFunc(enum.IntEnum):
-    """jh_color_func_type: feComponentTransfer's function types."""
-    IDENTITY = 0
-    LINEAR = 1
-    GAMMA = 2
-    TABLE = 3
-    DISCRETE = 4
-
-
-COLOR_CLAMP = 1  # JH_COLOR_CLAMP
-COLOR_MAX_VALUES = 64  # JH_COLOR_MAX_VALUES
-COLOR_POST_SHIFT = 4  # jh_color_tables' `which`: bit c is PRE_c, bit 4 + i is POST_i
-IDENTITY_MATRIX = (1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
-
-
-def _color_desc(matrix, funcs, space, clamp, rect):
-    """jh_color_desc.  `funcs`: None or four entries, each None (IDENTITY) or (ColorFunc.LINEAR, slope, intercept),
-    (ColorFunc.GAMMA, amplitude, exponent, offset), (ColorFunc.TABLE, values), (ColorFunc.DISCRETE, values) -- what
-    colorfilter.linear / gamma / table / discrete return.  What the rule refuses is left for the call to refuse, except a value
-    list that does not fit the struct."""
-    d = CColorDesc()
-    d.x, d.y, d.width, d.height = _rect(rect)
-    m = np.asarray(IDENTITY_MATRIX if matrix is None else matrix, np.float32).reshape(-1)
-    if m.size != 20:
-        raise ValueError("color_filter: the matrix has 20 entries (row-major 4 x 5)")
-    d.matrix[:] = [float(v) for v in m]
-    d.space, d.flags = int(space), COLOR_CLAMP if clamp else 0
-    funcs = (None,) * 4 if funcs is None else tuple(funcs)
-    if len(funcs) != 4:
-        raise ValueError("color_filter: four funcs, one per output channel")
-    for i, f in enumerate(funcs):
-        if f is None:
-            continue
-        c, kind = d.func[i], int(f[0])
-        c.type = kind
-        if kind == ColorFunc.LINEAR:
-            c.slope, c.intercept = float(f[1]), float(f[2])
-        elif kind == ColorFunc.GAMMA:
-            c.amplitude, c.exponent, c.offset = float(f[1]), float(f[2]), float(f[3])
-        elif kind in (ColorFunc.TABLE, ColorFunc.DISCRETE):
-            values = [float(v) for v in f[1]]
-            c.n = len(values)  # (0 and more than 64 are the call's to refuse; only 64 fit the struct)
-            c.values[:min(len(values), COLOR_MAX_VALUES)] = values[:COLOR_MAX_VALUES]
-    return d
-
-
-def color_tables(funcs=None, space=ColorSpace.LINEAR, clamp=True, twin=False):
-    """jh_color_tables (twin: jl_color_tables, the host twin): the tables of the colour-filter rule for these
-    funcs, space and clamp setting, one entry per f16 bit pattern: (pre, post, which) -- pre a dict {channel: float32 [65536]},
-    post a dict {channel: uint16 [65536]} of the tables that exist, which the bit mask.  No GPU needed.  ValueError for what the
-    rule refuses."""
-    L = _lib.load_host()
-    d = _color_desc(None, funcs, space, clamp, None)
-    pre, post = np.zeros((3, 65536), np.float32), np.zeros((4, 65536), np.uint16)
-    which = ctypes.c_uint32(0)
-    f = L.jl_color_tables if twin else L.hip.jh_color_tables
-    if f(ctypes.byref(d), pre.ctypes.data, post.ctypes.data, ctypes.byref(which)) != 0:
-        raise ValueError("color_tables: unknown space or func type, n = 0 or n > 64 values, or a parameter that is not finite")
-    w = which.value
-    return ({c: pre[c] for c in range(3) if w >> c & 1}, {i: post[i] for i in range(4) if w >> (COLOR_POST_SHIFT + i) & 1}, w)
-
-
-def composite_clip(src_size, dst_size, src_rect=None, offset=(0, 0)):
-    """jl_composite_clip: where the rectangle `src_rect` = (sx, sy, sw, sh) (None: the whole image) of a source of `src_size` =
-    (width, height) lands when its top-left is placed at the signed `offset` of a destination of `dst_size` and clipped to it
-    (the geometry of DESIGN.md 5.8): (sx', sy', dx', dy', w, h), all zero when nothing is left.  No GPU needed.  ValueError for a
-    source rectangle the rule refuses."""
-    L = _lib.load_host()
-    sx, sy, sw, sh = _rect(src_rect)
-    out = (ctypes.c_uint32 * 6)()
-    if L.jl_composite_clip(src_size[0], src_size[1], sx, sy, sw, sh, offset[0], offset[1], dst_size[0], dst_size[1], out) != 0:
-        raise ValueError(L.jl_last_error().decode())
-    return tuple(out)
 
 
 # a context buffer that blit / render_to_surface convert into when the caller passes no device pointer (it only grows)

@@ -6,15 +6,7 @@
 #include <memory>
 #include <string>
 
-#include "../../include/jello_blur.h"
-#include "../../include/jello_composite.h"
-#include "../../include/jello_resample.h"
-#include "../../include/jello_color.h"
-#include "../../include/jello_warp.h"
-#include "../../include/jello_convolve.h"
-#include "../../include/jello_lighting.h"
-#include "../../include/jello_turbulence.h"
-#include "../../include/jello_displace.h"
+#include "../../include/jello_queries.h"
 #include "dash.h"
 #include "hip_engine.h"
 #include "scene.h"
@@ -437,119 +429,19 @@ void* jl_engine_render_to_yuv(void* e, void* scene, const jl_render_params* para
     return rec_handle_of(std::move(f), bump_out, attempts);
 }
 
-// jl_blur_taps is the host twin of jh_blur_taps (the rule is in jello_hip.h and DESIGN.md 5.7): the same header, compiled here by the
-// host compiler -- the 2R + 1 taps of sigma into weights (or null) and R into *radius; -1 for a sigma that is negative, above 64
-// or NaN.
-int jl_blur_taps(float sigma, float* weights, uint32_t* radius) {
-    if (!jblur_sigma_ok(sigma)) { g_err = "blur_taps: sigma is negative, above 64 or NaN"; return -1; }
-    const uint32_t R = jblur_taps(sigma, weights);
-    if (radius) *radius = R;
-    return 0;
-}
-
-// jl_resample_taps is the host twin of jh_resample_taps (the rule is in jello_hip.h and DESIGN.md 5.9): the same header, compiled here
-// by the host compiler -- the window of output i of an axis of n_in source texels onto n_out: its weights into weights (96 entries
-// are enough; or null), its first source index into *first, its tap count into *count; -1 for an unknown filter, illegal sizes or
-// i >= n_out.
-int jl_resample_taps(int filter, uint32_t n_in, uint32_t n_out, uint32_t i, float* weights, uint32_t* first, uint32_t* count) {
-    if (!jresample_filter_ok(filter) || !jresample_sizes_ok(n_in, n_out) || i >= n_out) {
-        g_err = "resample_taps: unknown filter, sizes outside 1 <= n_in <= 16 n_out, or an index outside the axis";
-        return -1;
+// The context-free queries of the image calls: jl_<name> is the host twin of jh_<name> (the rules are documented call by call in
+// jello_hip.h) -- the one body of include/jello_queries.h that the library compiles, compiled here by the host compiler, so that a
+// caller without a GPU gets the same bytes.  -1 with "<name>: <reason>" for what the rule refuses; nothing is written then.
+// jl_composite_clip, the geometry of jh_composite, has no jh_ form.
+#define JL_QUERY(name, params, args)                                      \
+    int jl_##name params {                                                \
+        const char* why = jq_##name args;                                 \
+        if (why) { g_err = std::string(#name ": ") + why; return -1; }    \
+        return 0;                                                         \
     }
-    uint32_t f = 0u;
-    const uint32_t n = jresample_taps(filter, n_in, n_out, i, weights, &f, nullptr);
-    if (n == 0u) { g_err = "resample_taps: a window without taps"; return -1; }
-    if (first) *first = f;
-    if (count) *count = n;
-    return 0;
-}
-
-// jl_warp_plan and jl_warp_bounds are the host twins of jh_warp_plan and jh_warp_bounds (the rule is in jello_hip.h and DESIGN.md
-// 5.12): the same header, compiled here by the host compiler -- the six integers of a matrix's plan, and the rectangle of the
-// destination outside which a ZERO warp is transparent black; -1 for what the rule refuses.
-int jl_warp_plan(const double* matrix, int64_t* plan) {
-    const char* why = matrix && plan ? jwarp_plan(matrix, plan) : "null argument";
-    if (why) { g_err = std::string("warp_plan: ") + why; return -1; }
-    return 0;
-}
-int jl_warp_bounds(const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect) {
-    const char* why = matrix && rect ? jwarp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect) : "null argument";
-    if (why) { g_err = std::string("warp_bounds: ") + why; return -1; }
-    return 0;
-}
-
-// jl_convolve_weights is the host twin of jh_convolve_weights (the rule is in jello_hip.h and DESIGN.md 5.13): the same header,
-// compiled here by the host compiler -- feConvolveMatrix's kernelMatrix flipped and divided into the weights jh_convolve applies; -1
-// for what the rule refuses.
-int jl_convolve_weights(uint32_t order_x, uint32_t order_y, const double* kernel_matrix, double divisor, float* weights) {
-    const char* why = kernel_matrix && weights ? jconv_weights(order_x, order_y, kernel_matrix, divisor, weights) : "null argument";
-    if (why) { g_err = std::string("convolve_weights: ") + why; return -1; }
-    return 0;
-}
-
-// jl_color_tables is the host twin of jh_color_tables (the rule is in jello_hip.h and DESIGN.md 5.10): the same header, compiled here
-// by the host compiler -- the PRE tables of desc into pre (3 x 65 536 floats; or null), its POST tables into post (4 x 65 536 f16 bit
-// patterns; or null), only those that exist, and which they are into *which (bit c: PRE_c, bit 4 + i: POST_i); -1 for a descriptor
-// the rule refuses.
-int jl_color_tables(const jh_color_desc* desc, float* pre, uint16_t* post, uint32_t* which) {
-    const char* why = desc ? jcolor_desc_error(desc) : "null descriptor";
-    if (why) { g_err = std::string("color_tables: ") + why; return -1; }
-    const uint32_t w = jcolor_tables(desc, pre, post);
-    if (which) *which = w;
-    return 0;
-}
-
-// jl_lighting_plan and jl_lighting_tables are the host twins of jh_lighting_plan and jh_lighting_tables (the rule is in jello_hip.h and
-// DESIGN.md 5.14): the same header, compiled here by the host compiler -- the plan of desc; its power tables (4097 floats each; or null),
-// only those it needs, and which they are into *which (bit 0: the specular exponent's, bit 1: the spot exponent's); -1 for a
-// descriptor the rule refuses.
-int jl_lighting_plan(const jh_lighting_desc* desc, jh_light_plan* plan) {
-    const char* why = desc && plan ? jlight_plan(desc, plan) : "null argument";
-    if (why) { g_err = std::string("lighting_plan: ") + why; return -1; }
-    return 0;
-}
-int jl_lighting_tables(const jh_lighting_desc* desc, float* spec_table, float* spot_table, uint32_t* which) {
-    const char* why = desc ? jlight_desc_error(desc) : "null descriptor";
-    if (why) { g_err = std::string("lighting_tables: ") + why; return -1; }
-    const uint32_t w = jlight_tables(desc, spec_table, spot_table);
-    if (which) *which = w;
-    return 0;
-}
-
-// jl_turbulence_plan and jl_turbulence_tables are the host twins of jh_turbulence_plan and jh_turbulence_tables (the rule is in
-// jello_hip.h and DESIGN.md 5.15): the same header, compiled here by the host compiler -- the plan of desc; the tables of its seed, the
-// selector (256 bytes; or null) and the gradients G[4][256][2] (2048 floats; or null); -1 for a descriptor the rule refuses.
-int jl_turbulence_plan(const jh_turbulence_desc* desc, jh_turb_plan* plan) {
-    const char* why = desc && plan ? jturb_plan(desc, plan) : "null argument";
-    if (why) { g_err = std::string("turbulence_plan: ") + why; return -1; }
-    return 0;
-}
-int jl_turbulence_tables(const jh_turbulence_desc* desc, uint8_t* selector, float* gradients) {
-    const char* why = desc ? jturb_desc_error(desc) : "null descriptor";
-    if (why) { g_err = std::string("turbulence_tables: ") + why; return -1; }
-    jturb_tables(desc->seed, selector, gradients);
-    return 0;
-}
-
-// jl_displace_offset is the host twin of jh_displace_offset (the rule is in jello_hip.h and DESIGN.md 5.17): the same header, compiled
-// here by the host compiler -- D, the displacement in 2^-32 texel that one f16 map value gives under one scale; -1 for a null out.
-int jl_displace_offset(float scale, uint16_t f16_bits, int64_t* out) {
-    if (!out) { g_err = "displace_offset: null argument"; return -1; }
-    *out = jdisp_offset(scale, f16_bits);
-    return 0;
-}
-
-// jl_composite_clip is the geometry of jh_composite (the rule is in jello_hip.h and DESIGN.md 5.8) without a GPU: the same header
-// the library compiles, compiled here by the host compiler -- the source rectangle (sx, sy, sw, sh) of a src_w x src_h image
-// placed at (dx, dy) of a dst_w x dst_h one, clipped, into out[6] = {sx', sy', dx', dy', w, h} (all zero when nothing is left);
-// -1 for a source rectangle the rule refuses.
-int jl_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w,
-                      uint32_t dst_h, uint32_t* out) {
-    jcomp_rect r;
-    if (!out || jcomp_clip(src_w, src_h, sx, sy, sw, sh, dx, dy, dst_w, dst_h, &r)) { g_err = "composite_clip: the source rectangle is not inside the source image or is empty in one dimension"; return -1; }
-    out[0] = r.sx; out[1] = r.sy; out[2] = r.dx; out[3] = r.dy; out[4] = r.w; out[5] = r.h;
-    return 0;
-}
+JQ_QUERY_LIST(JL_QUERY)
+JQ_HOST_QUERY_LIST(JL_QUERY)
+#undef JL_QUERY
 
 // The tile pack (jh_pack_tiles; the format is in jello_hip.h) at the device pointer device_ptr into `out`: the header first, then
 // exactly the size it states (written to *size).

@@ -10,7 +10,7 @@ limitingConeAngle and lighting-color (sRGB) are turned into those here, with Pyt
 the rule.  Coordinates are texels of the image, texel (X, Y) at (X + 0.5, Y + 0.5)."""
 import math
 
-from .engine import LightKind, LightSource
+from .imagecalls import LightKind, LightSource
 
 WHITE = (1.0, 1.0, 1.0)
 

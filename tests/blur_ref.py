@@ -7,16 +7,15 @@
   vertical    V = 0.0f; for k = -Ry..Ry ascending: V = fmaf(w_k, H[y + k], V); dst = f16(V)  (round to nearest even, once)
   edges       ZERO: a tap outside the image is not executed; CLAMP: it reads the nearest texel of the image.
 
-binary32 fmaf is emulated exactly (fmaf32): the product of two binary32 values is exact in binary64 (24 + 24 bits), its sum with
-the accumulator is rounded to odd in binary64 (TwoSum gives the error of the rounded sum; a sum that is inexact and even moves to
-its odd neighbour on the error's side), and one conversion to binary32 follows -- 53 >= 24 + 2 bits, so the double rounding is
-innocuous, subnormal results included.  A plain binary64 add in its place is not proven and is not used.
+binary32 fmaf is emulated exactly (image_ref.fmaf32).
 
 The keyword arguments of `blur` after `dst` build the four WRONG variants the battery has to tell from the rule
 (tests/test_blur_spec.py): unfused multiply then add, descending k, an f16 intermediate, taps normalised in binary32."""
 import math
 
 import numpy as np
+
+from image_ref import fmaf32, mul_add32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 
 ZERO, CLAMP = 0, 1
 MAX_SIGMA = 64.0
@@ -57,25 +56,6 @@ def exact_taps(sigma):
     return g / g.sum(), R
 
 
-def fmaf32(w, x, acc):
-    """fmaf(w, x, acc) in binary32, exactly, elementwise (w a scalar or an array)."""
-    with np.errstate(all="ignore"):
-        p = np.asarray(w, np.float32).astype(np.float64) * np.asarray(x, np.float32).astype(np.float64)  # exact
-        a = np.asarray(acc, np.float32).astype(np.float64)
-        s = p + a
-        bb = s - p  # TwoSum (Knuth): err = the exact p + a - s wherever s is finite
-        err = (p - (s - bb)) + (a - bb)
-        odd_wanted = np.isfinite(s) & (err != 0.0) & ((s.view(np.uint64) & np.uint64(1)) == 0)
-        toward = np.where(err > 0.0, np.inf, -np.inf)
-        s = np.where(odd_wanted, np.nextafter(s, toward), s)
-        return s.astype(np.float32)
-
-
-def _mul_add32(w, x, acc):  # (a wrong variant: the product rounded to binary32 before the add)
-    with np.errstate(all="ignore"):
-        return (np.float32(w) * np.asarray(x, np.float32) + np.asarray(acc, np.float32)).astype(np.float32)
-
-
 def _pass(src, w, R, edge, axis, step, descending):
     """One axis of the rule on a float32 array (H, W, 4): out = sum over k of w_k src[.. + k ..] by `step`, in order."""
     src = np.moveaxis(src, axis, 0)
@@ -105,7 +85,7 @@ def blur(src_bits, sigma, edge=ZERO, rect=None, dst_bits=None, fused=True, desce
     x, y, w, h = (0, 0, W, H) if rect is None or (rect[2] == 0 and rect[3] == 0) else rect
     wx, Rx = taps(sx, binary32_taps)
     wy, Ry = taps(sy, binary32_taps)
-    step = fmaf32 if fused else _mul_add32
+    step = fmaf32 if fused else mul_add32
     out = np.zeros_like(src_bits) if dst_bits is None else np.array(dst_bits, np.uint16)
     if w == 0 or h == 0:
         return out
@@ -139,10 +119,3 @@ def direct(src_bits, sigma, edge=ZERO):
                 if oy.any() and ox.any():
                     out[np.ix_(oy, ox)] += gy[ky + Ry] * gx[kx + Rx] * f[np.ix_(yy[oy], xx[ox])]
     return out
-
-
-def same_bits(a, b):
-    """Equal f16 bit patterns, a NaN equal to any NaN."""
-    a, b = np.asarray(a, np.uint16), np.asarray(b, np.uint16)
-    nan_a, nan_b = (a & 0x7FFF) > 0x7C00, (b & 0x7FFF) > 0x7C00
-    return bool(np.all((a == b) | (nan_a & nan_b)))

@@ -3,7 +3,7 @@ jh_color_tables are compared with bit for bit.  Nothing here reads include/jello
 
 Per texel, binary32 (h_c: the stored f16 bit pattern of channel c, un-premultiplied):
   input    t_c = PRE_c[h_c] for c = r, g, b in SRGB space; otherwise, and always for alpha, h_c widened
-  matrix   m = M[i][4]; m = fmaf(M[i][k], t_k, m) for k = 0, 1, 2, 3           (blur_ref.fmaf32: the exact binary32 fmaf)
+  matrix   m = M[i][4]; m = fmaf(M[i][k], t_k, m) for k = 0, 1, 2, 3           (image_ref.fmaf32: the exact binary32 fmaf)
   clamp    with the flag: m = m > 0 ? m : 0; m = m < 1 ? m : 1               (np.where on the comparison: NaN and -0 become +0)
   round    g = f16(m), round to nearest even; a NaN m gives 0x7e00
   output   POST_i[g] where channel i has a table, else g
@@ -24,7 +24,7 @@ import math
 
 import numpy as np
 
-from blur_ref import _mul_add32, fmaf32
+from image_ref import fmaf32, mul_add32
 
 LINEAR, SRGB = 0, 1
 F_IDENTITY, F_LINEAR, F_GAMMA, F_TABLE, F_DISCRETE = 0, 1, 2, 3, 4
@@ -155,7 +155,7 @@ def texels(bits, matrix=None, funcs=None, space=LINEAR, clamp=True, variant=None
     bits = np.ascontiguousarray(bits, np.uint16)
     M = np.asarray(IDENTITY if matrix is None else matrix, np.float32).reshape(4, 5)
     pre, post, _ = tables(funcs, space, clamp, func_after_dec=variant == "func_after_dec")
-    step = _mul_add32 if variant == "unfused" else fmaf32
+    step = mul_add32 if variant == "unfused" else fmaf32
     with np.errstate(all="ignore"):
         t = bits.view(np.float16).astype(np.float32)
         for c in range(4 if variant == "enc_alpha" and space == SRGB else 3):

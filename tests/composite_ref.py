@@ -16,7 +16,7 @@ The keyword arguments of `composite` after `dst_bits` build the four WRONG varia
 (tests/test_composite_spec.py)."""
 import numpy as np
 
-from blur_ref import fmaf32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
+from image_ref import fmaf32, fmax, fmin, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 
 F = np.float32
 ZERO, ONE, TWO, HALF = F(0.0), F(1.0), F(2.0), F(0.5)
@@ -31,22 +31,6 @@ COMPOSE_NAMES = ["SrcOver", "Copy", "Dest", "Clear", "DestOver", "SrcIn", "DestI
 
 def _f(a):
     return np.asarray(a, np.float32)
-
-
-def fmin(a, b):
-    """IEEE minNum with -0 below +0."""
-    a, b = np.broadcast_arrays(_f(a), _f(b))
-    both_zero = (a == 0) & (b == 0)
-    pick_a = np.isnan(b) | (a < b) | (both_zero & np.signbit(a))
-    return np.where(np.isnan(a), b, np.where(pick_a, a, b)).astype(np.float32)
-
-
-def fmax(a, b):
-    """IEEE maxNum with -0 below +0."""
-    a, b = np.broadcast_arrays(_f(a), _f(b))
-    both_zero = (a == 0) & (b == 0)
-    pick_a = np.isnan(b) | (a > b) | (both_zero & ~np.signbit(a))
-    return np.where(np.isnan(a), b, np.where(pick_a, a, b)).astype(np.float32)
 
 
 def _mix(a, b, t):

@@ -1,5 +1,5 @@
 """The convolve rule (include/jello_hip.h "Convolve") in numpy, written from the rule alone: what jh_convolve has to
-produce, bit for bit.  Sums are binary32 with the rule's fmaf (blur_ref.fmaf32), one chain per channel.
+produce, bit for bit.  Sums are binary32 with the rule's fmaf (image_ref.fmaf32), one chain per channel.
 
   weights(order, kernel_matrix, divisor)   jh_convolve_weights: feConvolveMatrix's matrix flipped and divided (ValueError when refused)
   convolve(...)                            the image jh_convolve leaves in dst
@@ -15,8 +15,8 @@ import math
 
 import numpy as np
 
-from blur_ref import fmaf32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
-from composite_ref import fmax
+import image_ref
+from image_ref import fmaf32, fmax, mul_add32, resolve, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 
 ZERO, CLAMP, REPEAT, MIRROR = 0, 1, 2, 3
 EDGES = (ZERO, CLAMP, REPEAT, MIRROR)
@@ -54,38 +54,12 @@ def weights(order, kernel_matrix, divisor=0.0):
 
 def index(edge, i, n, mirror_2n=True):
     """jwarp_index: the index in [0, n) a tap i reads, -1 where it reads +0 (ZERO outside); i an int64 array."""
-    i = np.asarray(i, np.int64)
-    if edge == ZERO:
-        return np.where((i >= 0) & (i < n), i, -1)
-    if edge == CLAMP:
-        return np.minimum(np.maximum(i, 0), n - 1)
-    if edge == REPEAT or not mirror_2n:  # (the wrong variant of MIRROR: period n)
-        return np.mod(i, n)
-    m = np.mod(i, 2 * n)
-    return np.where(m < n, m, 2 * n - 1 - m)
-
-
-def _mul_add32(w, x, acc):  # (a wrong variant: the product rounded to binary32 before the add)
-    with np.errstate(all="ignore"):
-        return (np.float32(w) * np.asarray(x, np.float32) + np.asarray(acc, np.float32)).astype(np.float32)
-
-
-def resolve(shape, rect):
-    """(x, y, w, h) of the rectangle `rect` names in an image of `shape` = (H, W, ...); ValueError for what the rule refuses."""
-    H, W = shape[:2]
-    x, y, w, h = (0, 0, W, H) if rect is None or (rect[2] == 0 and rect[3] == 0) else rect
-    if (w == 0) != (h == 0) or x + w > W or y + h > H:
-        raise ValueError("the rectangle is outside the image or empty in one dimension")
-    return x, y, w, h
+    return image_ref.index(edge if mirror_2n or edge != MIRROR else REPEAT, i, n)  # (the wrong variant of MIRROR: period n)
 
 
 def operands(src_bits, mode):
     """(H, W, 4) float32: what the sums take of every source texel (PRESERVE_ALPHA: the alpha channel is there and is not used)."""
-    with np.errstate(all="ignore"):
-        p = np.ascontiguousarray(src_bits, np.uint16).view(np.float16).astype(np.float32)
-        if mode == PREMULTIPLIED:
-            p = np.concatenate([p[..., :3] * p[..., 3:], p[..., 3:]], axis=-1).astype(np.float32)
-    return p
+    return image_ref.operands(src_bits, mode == PREMULTIPLIED)
 
 
 def check(w, target, edge, mode, bias):
@@ -119,7 +93,7 @@ def convolve(src_bits, w, target=None, edge=CLAMP, mode=PREMULTIPLIED, bias=0.0,
         w = w[::-1, ::-1]
     tx, ty = tx + target_shift, ty + target_shift
     p = operands(src_bits, mode)
-    step = fmaf32 if fused else _mul_add32
+    step = fmaf32 if fused else mul_add32
     X, Y = x + np.arange(rw, dtype=np.int64), y + np.arange(rh, dtype=np.int64)
 
     def operand(i, j):

@@ -17,8 +17,7 @@ texel)."""
 import numpy as np
 
 import warp_ref
-from blur_ref import fmaf32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
-from composite_ref import fmax
+from image_ref import fmaf32, fmax, operands, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 from warp_ref import BICUBIC, BILINEAR, CLAMP, EDGES, FILTERS, MIRROR, NEAREST, REPEAT, STRAIGHT, ZERO  # noqa: F401
 
 R, G, B, A = 0, 1, 2, 3
@@ -79,15 +78,6 @@ def _taps(filt, U, frac_unshifted):
     return [(i, w) for (i, _), (_, w) in zip(taps, warp_ref.axis_taps(filt, U + (1 << 31)))]  # (the wrong variant: the weights of the unshifted position)
 
 
-def _operands(src_bits, src_rect, straight, dtype):
-    sx, sy, sw, sh = src_rect
-    with np.errstate(all="ignore"):
-        p = src_bits[sy:sy + sh, sx:sx + sw].view(np.float16).astype(dtype)
-        if not straight:
-            p = np.concatenate([p[..., :3] * p[..., 3:], p[..., 3:]], axis=-1).astype(dtype)
-    return p
-
-
 def _arguments(src_bits, map_bits, dst_shape, scale, x_channel, y_channel, matrix, filt, edge, flags, src_rect, dst_rect):
     if filt not in FILTERS or edge not in EDGES or flags & ~STRAIGHT:
         raise ValueError("unknown filter, edge or flag bits")
@@ -118,7 +108,7 @@ def displace(src_bits, map_bits, dst_shape, scale, x_channel=R, y_channel=G, mat
         return out
     U, V = positions(map_bits, pl, drect, scale, x_channel, y_channel, **variant)
     straight = bool(flags & STRAIGHT)
-    p = _operands(src_bits, (sx, sy, sw, sh), straight, F)
+    p = operands(src_bits[sy:sy + sh, sx:sx + sw], not straight, F)
     with np.errstate(all="ignore"):
         ix = [(warp_ref.index(edge, i, sw), w[..., None]) for i, w in _taps(filt, U, frac_unshifted)]
         iy = [(warp_ref.index(edge, j, sh), w[..., None]) for j, w in _taps(filt, V, frac_unshifted)]
@@ -165,7 +155,7 @@ def direct(src_bits, map_bits, dst_shape, scale, x_channel=R, y_channel=G, matri
     src_bits, map_bits, (sx, sy, sw, sh), drect, pl = _arguments(src_bits, map_bits, dst_shape, scale, x_channel, y_channel, matrix, filt, edge, flags,
                                                                  src_rect, dst_rect)
     U, V = positions(map_bits, pl, drect, scale, x_channel, y_channel)
-    p = _operands(src_bits, (sx, sy, sw, sh), bool(flags & STRAIGHT), np.float64)
+    p = operands(src_bits[sy:sy + sh, sx:sx + sw], not flags & STRAIGHT, np.float64)
     acc = np.zeros(U.shape + (4,))
     for j, wy in _weights64(filt, V):
         jj = warp_ref.index(edge, j, sh)

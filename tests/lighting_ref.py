@@ -1,5 +1,5 @@
 """The lighting rule (include/jello_hip.h "Lighting") in numpy, written from the rule alone: what jh_lighting has to
-produce, bit for bit.  Every binary32 operation is one numpy float32 operation (correctly rounded), fmaf is blur_ref.fmaf32 (exact),
+produce, bit for bit.  Every binary32 operation is one numpy float32 operation (correctly rounded), fmaf is image_ref.fmaf32 (exact),
 min and max are composite_ref's minNum and maxNum; indices are int64; binary64 appears in plan() and table() only.
 
   check(**kw)      ValueError for a descriptor the rule refuses
@@ -18,8 +18,7 @@ import math
 
 import numpy as np
 
-from blur_ref import fmaf32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
-from composite_ref import fmax, fmin
+from image_ref import fmaf32, fmax, fmin, resolve, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 
 DIFFUSE, SPECULAR = 0, 1
 DISTANT, POINT, SPOT = 0, 1, 2
@@ -141,14 +140,6 @@ def power(t, e, entries=ENTRIES, index_rounded=False):
     i = np.minimum(i, steps - 1)
     f = (u - i.astype(F)).astype(F)
     return fmaf32(f, (T[i + 1] - T[i]).astype(F), T[i])
-
-
-def resolve(shape, rect):
-    H, W = shape[:2]
-    x, y, w, h = (0, 0, W, H) if rect is None or (rect[2] == 0 and rect[3] == 0) else rect
-    if (w == 0) != (h == 0) or x + w > W or y + h > H:
-        raise ValueError("the rectangle is outside the image or empty in one dimension")
-    return x, y, w, h
 
 
 def alpha_of(src_bits):

@@ -17,8 +17,8 @@ The keyword arguments of `morph` after `dst_bits` build the six near misses the 
 of the image, ZERO's padding left out, straight operands where premultiplied ones are asked for, a window of [-r, r)."""
 import numpy as np
 
-from blur_ref import same_bits  # noqa: F401 (part of this module's interface: equal f16 bit patterns, a NaN equal to any NaN)
-from composite_ref import fmax
+import image_ref
+from image_ref import fmax, same_bits  # noqa: F401 (part of this module's interface: equal f16 bit patterns, a NaN equal to any NaN)
 
 ERODE, DILATE = 0, 1
 ZERO, CLAMP = 0, 1
@@ -51,11 +51,7 @@ def _radii(radius):
 
 
 def resolve(shape, rect):
-    h, w = shape[:2]
-    x, y, rw, rh = (0, 0, w, h) if rect is None or (rect[2] == 0 and rect[3] == 0) else rect
-    if rw == 0 or rh == 0 or x + rw > w or y + rh > h:
-        raise ValueError("the rectangle is not inside the image or is empty in one dimension")
-    return x, y, rw, rh
+    return image_ref.resolve(shape, rect, "the rectangle is not inside the image or is empty in one dimension", texels=True)
 
 
 def legal(op, radius, edge, flags, shape, rect):
@@ -100,11 +96,7 @@ def store(v, straight):
 
 
 def operands(src_bits, straight):
-    with np.errstate(all="ignore"):
-        p = np.ascontiguousarray(src_bits, np.uint16).view(np.float16).astype(np.float32)
-        if not straight:
-            p = np.concatenate([p[..., :3] * p[..., 3:], p[..., 3:]], axis=-1).astype(np.float32)
-    return p
+    return image_ref.operands(src_bits, not straight)
 
 
 def morph(src_bits, op, radius, edge=ZERO, flags=0, rect=None, dst_bits=None, nan_sticky=True, signed_zero=True, window_image=True,

@@ -18,8 +18,7 @@ import math
 
 import numpy as np
 
-from blur_ref import fmaf32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
-from composite_ref import fmax
+from image_ref import fmaf32, fmax, mul_add32, resolve, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 
 BOX, TRIANGLE, CATMULL_ROM, LANCZOS3 = 0, 1, 2, 3
 FILTERS = (BOX, TRIANGLE, CATMULL_ROM, LANCZOS3)
@@ -95,11 +94,6 @@ def axis_taps(filt, n_in, n_out, **variant):
     return [window(filt, n_in, n_out, i, **variant)[:2] for i in range(n_out)]
 
 
-def _mul_add32(w, x, acc):  # (a wrong variant: the product rounded to binary32 before the add)
-    with np.errstate(all="ignore"):
-        return (np.float32(w) * np.asarray(x, np.float32) + np.asarray(acc, np.float32)).astype(np.float32)
-
-
 def _pass(src, taps, step, descending):
     """One axis of the rule along axis 0 of a float32 array (n_in, m, 4): out (n_out, m, 4), out[i] = the sum over the window of i."""
     out = np.zeros((len(taps),) + src.shape[1:], np.float32)
@@ -113,12 +107,8 @@ def _pass(src, taps, step, descending):
 
 
 def _rects(src_shape, dst_shape, src_rect, dst_rect):
-    sh_img, sw_img = src_shape[:2]
-    dh_img, dw_img = dst_shape[:2]
-    sx, sy, sw, sh = (0, 0, sw_img, sh_img) if src_rect is None or (src_rect[2] == 0 and src_rect[3] == 0) else src_rect
-    dx, dy, dw, dh = (0, 0, dw_img, dh_img) if dst_rect is None or (dst_rect[2] == 0 and dst_rect[3] == 0) else dst_rect
-    if sw == 0 or sh == 0 or dw == 0 or dh == 0 or sx + sw > sw_img or sy + sh > sh_img or dx + dw > dw_img or dy + dh > dh_img:
-        raise ValueError("a rectangle is outside its image or empty in one dimension")
+    why = "a rectangle is outside its image or empty in one dimension"
+    (sx, sy, sw, sh), (dx, dy, dw, dh) = resolve(src_shape, src_rect, why, texels=True), resolve(dst_shape, dst_rect, why, texels=True)
     if not sizes_ok(sw, dw) or not sizes_ok(sh, dh):
         raise ValueError("a ratio above 16:1")
     return (sx, sy, sw, sh), (dx, dy, dw, dh)
@@ -134,7 +124,7 @@ def resample(src_bits, dst_shape, filt, flags=0, src_rect=None, dst_rect=None, d
     (sx, sy, sw, sh), (dx, dy, dw, dh) = _rects(src_bits.shape, out.shape, src_rect, dst_rect)
     variant = dict(centre_half=centre_half, renormalise=renormalise)
     tx, ty = axis_taps(filt, sw, dw, **variant), axis_taps(filt, sh, dh, **variant)
-    step = fmaf32 if fused else _mul_add32
+    step = fmaf32 if fused else mul_add32
     straight = bool(flags & STRAIGHT)
     with np.errstate(all="ignore"):
         p = src_bits[sy:sy + sh, sx:sx + sw].view(np.float16).astype(np.float32)

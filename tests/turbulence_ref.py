@@ -9,8 +9,7 @@ import math
 
 import numpy as np
 
-from blur_ref import fmaf32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
-from composite_ref import fmax, fmin
+from image_ref import fmaf32, fmax, fmin, resolve, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 
 F = np.float32
 FRACTAL_NOISE, TURBULENCE = 0, 1
@@ -118,14 +117,6 @@ def plan(no_half=False, **kw):
                 raise ValueError("the stitch tile is beyond the lattice range of this many octaves")
             out["width"][a], out["wrap"][a] = width, wrap
     return out
-
-
-def resolve(shape, rect):
-    H, W = shape[:2]
-    x, y, w, h = (0, 0, W, H) if rect is None or (rect[2] == 0 and rect[3] == 0) else rect
-    if (w == 0) != (h == 0) or x + w > W or y + h > H:
-        raise ValueError("the rectangle is outside the image or empty in one dimension")
-    return x, y, w, h
 
 
 # ---- the texels ----

@@ -1,5 +1,5 @@
 """The warp rule (include/jello_hip.h "Warp") in numpy, written from the rule alone: what jh_warp has to produce, bit
-for bit.  Positions are int64 (exact), sums binary32 with the rule's fmaf (blur_ref.fmaf32).
+for bit.  Positions are int64 (exact), sums binary32 with the rule's fmaf (image_ref.fmaf32).
 
   plan(matrix)      the six integers P, Q, R, S, T, W (ValueError for an illegal matrix)
   bounds(...)       the rectangle of jh_warp_bounds
@@ -15,8 +15,8 @@ import math
 
 import numpy as np
 
-from blur_ref import fmaf32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
-from composite_ref import fmax
+import image_ref
+from image_ref import fmaf32, fmax, mul_add32, same_bits  # noqa: F401 (same_bits is part of this module's interface)
 
 NEAREST, BILINEAR, BICUBIC = 0, 1, 2
 FILTERS = (NEAREST, BILINEAR, BICUBIC)
@@ -96,16 +96,9 @@ def bounds(matrix, src_size, filt, dst_size):
 
 def index(edge, i, n, mirror_2n=True):
     """The index in [0, n) a tap i reads, -1 where it reads +0 (ZERO outside); i an int64 array."""
+    if mirror_2n or edge != MIRROR:
+        return image_ref.index(edge, i, n)
     i = np.asarray(i, np.int64)
-    if edge == ZERO:
-        return np.where((i >= 0) & (i < n), i, -1)
-    if edge == CLAMP:
-        return np.minimum(np.maximum(i, 0), n - 1)
-    if edge == REPEAT:
-        return np.mod(i, n)  # (numpy's mod of a positive modulus is non-negative)
-    if mirror_2n:
-        m = np.mod(i, 2 * n)
-        return np.where(m < n, m, 2 * n - 1 - m)
     if n == 1:  # (the wrong variant: period 2 n - 2)
         return np.zeros_like(i)
     m = np.mod(i, 2 * n - 2)
@@ -143,21 +136,13 @@ def axis_taps(filt, U, floor=True, frac_round=False):
     return [(i0 - 1 + k, w) for k, w in enumerate(cubic_weights(f))]
 
 
-def _mul_add32(w, x, acc):  # (a wrong variant: the product rounded to binary32 before the add)
-    with np.errstate(all="ignore"):
-        return (np.asarray(w, np.float32) * np.asarray(x, np.float32) + np.asarray(acc, np.float32)).astype(np.float32)
-
-
 def rects(src_shape, dst_shape, src_rect, dst_rect):
     """((sx, sy, sw, sh), (dx, dy, dw, dh)) resolved; ValueError for what the rule refuses."""
     out = []
     for (h, w), r in ((src_shape[:2], src_rect), (dst_shape[:2], dst_rect)):
         if w > MAX_SIDE or h > MAX_SIDE:
             raise ValueError("an image side above 32768")
-        x, y, rw, rh = (0, 0, w, h) if r is None or (r[2] == 0 and r[3] == 0) else r
-        if (rw == 0) != (rh == 0) or x + rw > w or y + rh > h:
-            raise ValueError("a rectangle is outside its image or empty in one dimension")
-        out.append((x, y, rw, rh))
+        out.append(image_ref.resolve((h, w), r, "a rectangle is outside its image or empty in one dimension"))
     return tuple(out)
 
 
@@ -186,7 +171,7 @@ def warp(src_bits, dst_shape, matrix, filt=BILINEAR, edge=ZERO, flags=0, src_rec
         return out
     U, V = positions(pl, drect)
     tx, ty = axis_taps(filt, U, floor, frac_round), axis_taps(filt, V, floor, frac_round)
-    step = fmaf32 if fused else _mul_add32
+    step = fmaf32 if fused else mul_add32
     straight = bool(flags & STRAIGHT)
     with np.errstate(all="ignore"):
         if edge_rect:
