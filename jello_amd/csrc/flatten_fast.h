@@ -1,5 +1,5 @@
 // flatten_fast.h -- a DECISION procedure for flatten's subdivision test (flatten.wgsl:94-133 + :401), shared by
-// k_flatten_items (device) and tools/flatten_fast_check.cpp (host, the same IEEE binary32 operations).
+// k_flatten_items (device) and tests/native/flatten_fast_check.cpp (host, the same IEEE binary32 operations).
 //
 // The subdivision test of flatten_euler accepts an interval iff  v = fl(fl(err * chord_len) * scale) <= tol,  where err
 // comes out of cubic_from_points_derivs: two atan2, two cos, two sin (pinned: binary64 sequences rounded once to
@@ -125,6 +125,22 @@ FF_INLINE int ff_decide(float h0x, float h0y, float len0, float h1x, float h1y, 
     if (v + guard < tol) return FF_ACCEPT;
     if (v - guard > tol) return FF_REJECT;
     return FF_UNSURE;
+}
+
+// ff_decide for an interval with a chord that is not tiny (chord_squared >= DERIV_THRESH^2; the tiny-chord branch has no
+// transcendentals and is decided exactly by the caller).  Prepares ff_decide's operands from what the walk has at hand:
+// the chord (end point - start point), the derivatives q0 / q1 at the two ends and actual_dt.  This is
+// cubic_from_points_derivs (flatten.wgsl:94-114) up to d0 / d1: h0 / h1 with the same operations on the same values, the
+// roots and the quotient through FF_SQRT / FF_RCP.  Over scalars: the device's and the host tool's vector types differ.
+FF_INLINE int ff_decide_interval(float chord_x, float chord_y, float q0x, float q0y, float q1x, float q1y, float actual_dt, float scale, float tol,
+                                 float* v_est, float* delta) {
+    const float chord_squared = chord_x * chord_x + chord_y * chord_y;
+    const float chord_len = FF_SQRT(chord_squared);
+    const float sc = actual_dt * FF_RCP(chord_squared);
+    const float h0x = q0x * chord_x + q0y * chord_y, h0y = q0y * chord_x - q0x * chord_y;
+    const float h1x = q1x * chord_x + q1y * chord_y, h1y = q1x * chord_y - q1y * chord_x;
+    const float len0 = FF_SQRT(h0x * h0x + h0y * h0y), len1 = FF_SQRT(h1x * h1x + h1y * h1y);
+    return ff_decide(h0x, h0y, len0, h1x, h1y, len1, len0 * sc, len1 * sc, chord_len, scale, tol, v_est, delta);
 }
 
 }  // namespace ffast

@@ -50,10 +50,6 @@ struct PathTagData { uint32_t tag_byte; MonoidK<5> monoid; };
 #define TANGENT_THRESH 1e-6f
 
 #define FL_INVALID 0xffffffffu
-// slot_info[t] = (record index, FL_INFO_* | lines of the piece << 8 | index of this line in the piece); every slot below the
-// slot cursor is written exactly once per frame (allocation is exact), so the array needs no clearing
-#define FL_INFO_PIECE 0x80000000u    // line i of an Euler piece (record: see "piece record" below)
-#define FL_INFO_DIRECT 0x40000000u   // complete line (record: {item, k, path_ix, -}, {p0, p1})
 #ifndef FL_REFILL_LANES
 #define FL_REFILL_LANES 32u  // idle lanes that trigger a refill of the wave
 #endif
@@ -75,6 +71,9 @@ struct FlTemp {
 };
 #define FL_CTR_CURSOR 512u    // word index of region 0's slot cursor; its record cursor 32 words on; next region FL_CUR_STRIDE on
 #define FL_CUR_STRIDE 64u
+template <class W>  // (W: uint32_t, or const uint32_t for k_flatten_lines, which only reads the counters)
+JD W* fl_cursor_in(W* ctr, uint32_t region, int kind) { return ctr + FL_CTR_CURSOR + FL_CUR_STRIDE * region + (kind ? 32u : 0u); }
+JD uint32_t* fl_cursor(const FlTemp& T, uint32_t region, int kind) { return fl_cursor_in(T.ctr, region, kind); }
 // n consecutive slots (KIND 0) or records (KIND 1): the position, or FL_INVALID when every region is full (the frame has
 // overflowed its line buffer).  `home` is the wave's region: WAVE-UNIFORM, so that the lanes that allocate in one instruction
 // can share one atomic (wave_bump; one atomic per lane means 400 000 per C3 frame instead of 8 000: +370 us).  `failed` is raised when home could not serve: the wave moves
@@ -83,7 +82,7 @@ struct FlTemp {
 template <int KIND>
 JD uint32_t fl_grab(const FlTemp& T, uint32_t home, uint32_t n, bool& failed) {
     // (the attempt on home stands apart from the loop over the other regions: inside the loop the region is a per-lane value)
-    uint32_t p = wave_bump(T.ctr + FL_CTR_CURSOR + FL_CUR_STRIDE * home + (KIND ? 32u : 0u), n);
+    uint32_t p = wave_bump(fl_cursor(T, home, KIND), n);
     if (__builtin_expect(p <= T.R && n <= T.R - p, 1)) return home * T.R + p;
     failed = true;
     uint32_t region = home;
@@ -92,10 +91,10 @@ JD uint32_t fl_grab(const FlTemp& T, uint32_t home, uint32_t n, bool& failed) {
             for (uint32_t i = p; i < T.R; i++) T.sinfo[(size_t)region * T.R + i] = make_uint2(0u, 0u);
         // (an add that found the region full already is taken back: the cursor of a full region stays within one allocation of R
         // however many waves still try it before they move on -- it can never wrap and reopen the region)
-        if (p >= T.R) atomicSub(T.ctr + FL_CTR_CURSOR + FL_CUR_STRIDE * region + (KIND ? 32u : 0u), n);
+        if (p >= T.R) atomicSub(fl_cursor(T, region, KIND), n);
         if (tries >= T.K) return FL_INVALID;
         region = region + 1u == T.K ? 0u : region + 1u;
-        p = atomicAdd(T.ctr + FL_CTR_CURSOR + FL_CUR_STRIDE * region + (KIND ? 32u : 0u), n);
+        p = atomicAdd(fl_cursor(T, region, KIND), n);
         if (p <= T.R && n <= T.R - p) return region * T.R + p;
     }
 }
@@ -103,18 +102,91 @@ JD uint32_t fl_grab(const FlTemp& T, uint32_t home, uint32_t n, bool& failed) {
 JD uint32_t fl_next_home(const FlTemp& T, uint32_t home, int kind) {
     uint32_t region = home;
     for (uint32_t tries = 0u; tries < T.K; tries++) {
-        const uint32_t cur = __hip_atomic_load(T.ctr + FL_CTR_CURSOR + FL_CUR_STRIDE * region + (kind ? 32u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t cur = __hip_atomic_load(fl_cursor(T, region, kind), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (cur < T.R) return region;
         region = region + 1u == T.K ? 0u : region + 1u;
     }
     return home;
 }
 
-// Line sink of the DIRECT items (caps, joins, straight segments) and of the sequential fall-back walk.  EMIT: an allocation
-// of n lines takes n temporary slots and n records (two returning atomics on different words; lanes that allocate in the same
-// instruction are combined by the compiler's atomic optimizer), a line leaves its record and its slot_info; k_flatten_lines
-// then moves it to lines[bases[item] + k], the canonical position.  !EMIT: only counts.
-template <bool EMIT>
+// ------------------------------------------------------------------------------------------------
+// What k_flatten_items leaves in the temporary for k_flatten_lines.  The layouts are stated HERE and nowhere else: nothing
+// outside this section indexes a record, shifts a slot_info word or spells a flag's value.
+// slot_info[t] = (record index, FL_INFO_* | lines of the piece << 8 | index of this line in the piece); every slot below the
+// slot cursor is written exactly once per frame (allocation is exact), so the array needs no clearing.  (0, 0) = empty.
+// A record is one 64-byte sector, 4 x uint4 at recs[4 * r]:
+//   direct (a complete line: caps, joins, straight segments)   0: item k path_ix -   1: p0.x p0.y p1.x p1.y   (k: line in item)
+//   piece (an accepted Euler piece; the number of its lines comes with slot_info)
+//     0: es_p0.x es_p0.y es_p1.x es_p1.y   1: th0 th1 int0 integral   2: noff item path_ix trans_ix << FL_PC_BITS | FL_PC_*
+//     3: (first piece of its item ? t_start.x : index of the piece's first line in the item) t_start.y t_end.x t_end.y
+//   t_start is read only by the item's first line, t_end only by its last.  Of the subdivision constants of
+//   flatten.wgsl:404-433, int0 and integral (two espc_int_approx evaluations) travel in the record; the Euler parameters k0,
+//   k1, ch are recomputed from the two angles (es_params_from_angles: 45 binary32 operations, no transcendentals), a and b
+//   by the same two products (piece_ab).
+// ------------------------------------------------------------------------------------------------
+#define FL_INFO_PIECE 0x80000000u    // line i of an Euler piece
+#define FL_INFO_DIRECT 0x40000000u   // complete line
+#define FL_PC_ROBUST 3u        // bits 0-1: the case of flatten.wgsl:413-433 that piece_params found:
+#define FL_ROBUST_NORMAL 0u
+#define FL_ROBUST_LOW_K1 1u    //   hardly any change of curvature
+#define FL_ROBUST_LOW_DIST 2u  //   hardly any offset
+#define FL_PC_ENDS_AT_ONE 4u   // the piece ends at t == 1: its last line ends in t_end
+#define FL_PC_FORWARD 8u       // offset >= 0: a line runs (start, end); else (end, start)
+#define FL_PC_NO_OFFSET 16u    // offset == 0: a fill, whose control points were transformed before the subdivision
+#define FL_PC_FIRST 32u        // first piece of its item
+#define FL_PC_BITS 6u
+JD uint32_t piece_flags(uint32_t robust, float t1, float offset, bool first) {
+    return robust | ((t1 == 1.0f) ? FL_PC_ENDS_AT_ONE : 0u) | ((offset >= 0.0f) ? FL_PC_FORWARD : 0u) | ((offset == 0.0f) ? FL_PC_NO_OFFSET : 0u) |
+           (first ? FL_PC_FIRST : 0u);
+}
+JD void direct_record_write(uint4* __restrict__ rec, uint32_t item, uint32_t k, uint32_t path_ix, V2 p0, V2 p1) {
+    rec[0] = make_uint4(item, k, path_ix, 0u);
+    rec[1] = make_uint4(f2u(p0.x), f2u(p0.y), f2u(p1.x), f2u(p1.y));
+}
+JD void piece_record_write(uint4* __restrict__ rec, V2 es_p0, V2 es_p1, float th0, float th1, float int0, float integral, float noff,
+                           uint32_t item, uint32_t path_ix, uint32_t trans_ix, uint32_t fl, uint32_t first, V2 t_start, V2 t_end) {
+    rec[0] = make_uint4(f2u(es_p0.x), f2u(es_p0.y), f2u(es_p1.x), f2u(es_p1.y));
+    rec[1] = make_uint4(f2u(th0), f2u(th1), f2u(int0), f2u(integral));
+    rec[2] = make_uint4(f2u(noff), item, path_ix, (trans_ix << FL_PC_BITS) | fl);
+    rec[3] = make_uint4((fl & FL_PC_FIRST) != 0u ? f2u(t_start.x) : first, f2u(t_start.y), f2u(t_end.x), f2u(t_end.y));
+}
+// the index of the piece's first line in its item, for a piece that was written before it was known (not the item's first piece)
+JD void piece_record_set_first(uint4* __restrict__ rec, uint32_t first) { ((uint32_t*)rec)[12] = first; }
+// slot_info of the n lines of a piece whose first line has slot tpos
+JD void piece_slots_write(uint2* __restrict__ sinfo, uint32_t tpos, uint32_t n_u, uint32_t r) {
+    for (uint32_t i = 0u; i < n_u; i++) sinfo[tpos + i] = make_uint2(r, FL_INFO_PIECE | (n_u << 8) | i);
+}
+// Readers.  k_flatten_lines holds the four words of a fetched record apart, in variables with a common name R and the digits
+// 0..3 (it requests words 0-1 for every line and 2-3 for piece lines only, one trip ahead).  Macros over R, not a view struct
+// or functions: through either the compiler slices and pairs the words differently and k_flatten_lines comes out 3 to 10
+// instructions longer; the kernel is held to the code that was measured.
+#define DREC_ITEM(R) ((R##0).x)
+#define DREC_K(R) ((R##0).y)
+#define DREC_PATH_IX(R) ((R##0).z)
+#define DREC_P0(R) make_uint2((R##1).x, (R##1).y)  // (copied, not interpreted)
+#define DREC_P1(R) make_uint2((R##1).z, (R##1).w)
+#define PREC_ES_P0(R) v2(u2f((R##0).x), u2f((R##0).y))
+#define PREC_ES_P1(R) v2(u2f((R##0).z), u2f((R##0).w))
+#define PREC_TH0(R) u2f((R##1).x)
+#define PREC_TH1(R) u2f((R##1).y)
+#define PREC_INT0(R) u2f((R##1).z)
+#define PREC_INTEGRAL(R) u2f((R##1).w)
+#define PREC_NOFF(R) u2f((R##2).x)
+#define PREC_ITEM(R) ((R##2).y)
+#define PREC_PATH_IX(R) ((R##2).z)
+#define PREC_FLAGS(R) ((R##2).w & ((1u << FL_PC_BITS) - 1u))
+#define PREC_TRANS_IX(R) ((R##2).w >> FL_PC_BITS)
+#define PREC_FIRST_LINE(R) (((R##2).w & FL_PC_FIRST) != 0u ? 0u : (R##3).x)
+#define PREC_T_START(R) v2(u2f((R##3).x), u2f((R##3).y))  // (of an item's first piece)
+#define PREC_T_END(R) v2(u2f((R##3).z), u2f((R##3).w))
+// slot_info.y of a piece line: the lines of its piece and its index among them
+#define SINFO_LINES(SI) (((SI).y >> 8) & 127u)
+#define SINFO_LINE(SI) ((SI).y & 127u)
+
+// Line sink of the DIRECT items (caps, joins, straight segments) and of the sequential fall-back walk.  An allocation of n
+// lines takes n temporary slots and n records (two returning atomics on different words; lanes that allocate in the same
+// instruction are combined by hand, wave_bump in kcommon.h -- the csrc Makefile says why not by the compiler's atomic
+// optimizer), a line leaves its record and its slot_info; k_flatten_lines then moves it to lines[bases[item] + k].
 struct Out {
     const JlConfig* cfg;
     FlTemp T;
@@ -127,27 +199,22 @@ struct Out {
     JD uint32_t alloc(uint32_t n) {
         uint32_t first = cursor;
         cursor += n;
-        if (EMIT) {
-            a_first = first;
-            a_spos = fl_grab<0>(T, home_s, n, failed_s);
-            a_rpos = fl_grab<1>(T, home_r, n, failed_r);
-        }
+        a_first = first;
+        a_spos = fl_grab<0>(T, home_s, n, failed_s);
+        a_rpos = fl_grab<1>(T, home_r, n, failed_r);
         return first;
     }
     JD void write_line(uint32_t line_ix, uint32_t path_ix, V2 p0, V2 p1) {  // flatten.wgsl:749-756
-        if (EMIT) {
-            if (a_spos != FL_INVALID && a_rpos != FL_INVALID) {
-                const uint32_t t = a_spos + (line_ix - a_first), r = a_rpos + (line_ix - a_first);
-                T.recs[(size_t)r * 4u] = make_uint4(slot, line_ix, path_ix, 0u);
-                T.recs[(size_t)r * 4u + 1u] = make_uint4(f2u(p0.x), f2u(p0.y), f2u(p1.x), f2u(p1.y));
-                T.sinfo[t] = make_uint2(r, FL_INFO_DIRECT);
-            } else if (a_spos != FL_INVALID) {
-                T.sinfo[a_spos + (line_ix - a_first)] = make_uint2(0u, 0u);  // (a slot without a record: empty)
-            }
+        if (a_spos != FL_INVALID && a_rpos != FL_INVALID) {
+            const uint32_t t = a_spos + (line_ix - a_first), r = a_rpos + (line_ix - a_first);
+            direct_record_write(T.recs + (size_t)r * 4u, slot, line_ix, path_ix, p0, p1);
+            T.sinfo[t] = make_uint2(r, FL_INFO_DIRECT);
+        } else if (a_spos != FL_INVALID) {
+            T.sinfo[a_spos + (line_ix - a_first)] = make_uint2(0u, 0u);  // (a slot without a record: empty)
         }
     }
     JD void write_line_t(uint32_t line_ix, uint32_t path_ix, V2 p0, V2 p1, const Xf& t) {
-        if (EMIT) write_line(line_ix, path_ix, xf_apply(t, p0), xf_apply(t, p1));
+        write_line(line_ix, path_ix, xf_apply(t, p0), xf_apply(t, p1));
     }
     JD void output_line_t(uint32_t path_ix, V2 p0, V2 p1, const Xf& t) {
         uint32_t ix = alloc(1);
@@ -369,24 +436,81 @@ struct Scene {
 // record.  Every point is computed once, with the same operations on the same values as in the sequential
 // formulation, hence the same bits.  Lines emitted directly (caps, joins) wait in records of their own and are copied.
 // ------------------------------------------------------------------------------------------------
-// piece record: one 64-byte sector, 4 x uint4 at recs[4 * r]:
-//   0: es_p0.x es_p0.y es_p1.x es_p1.y   1: th0 th1 int0 integral   2: noff item path_ix trans_ix<<6|flags
-//   3: (first piece of its item ? t_start.x : index of the piece's first line in the item) t_start.y t_end.x t_end.y
-// t_start is read only by the item's first line, t_end only by its last.  The number of lines n comes with slot_info.
-// flags: bits 0-1 robust case, 4 = ends at t == 1 (last line ends in t_end), 8 = offset >= 0, 16 = offset == 0,
-//        32 = first piece of its item.  Of the subdivision constants of flatten.wgsl:404-433, int0 and integral (two
-//        espc_int_approx evaluations) travel in the record; the Euler parameters k0, k1, ch are recomputed from the two angles
-//        (es_params_from_angles: 45 binary32 operations, no transcendentals), a and b by the same two products.
-JD void piece_record_write(uint4* __restrict__ rec, V2 es_p0, V2 es_p1, float th0, float th1, float int0, float integral, float noff,
-                           uint32_t item, uint32_t path_ix, uint32_t trans_ix, uint32_t fl, uint32_t first, V2 t_start, V2 t_end) {
-    rec[0] = make_uint4(f2u(es_p0.x), f2u(es_p0.y), f2u(es_p1.x), f2u(es_p1.y));
-    rec[1] = make_uint4(f2u(th0), f2u(th1), f2u(int0), f2u(integral));
-    rec[2] = make_uint4(f2u(noff), item, path_ix, (trans_ix << 6) | fl);
-    rec[3] = make_uint4((fl & 32u) != 0u ? f2u(t_start.x) : first, f2u(t_start.y), f2u(t_end.x), f2u(t_end.y));
+// The rules both formulations of the subdivision share -- the sequential walk (flatten_euler_wave) and the cooperative one
+// (node_ends ... piece_params) must get the same bits from them, or a batch that bails out to the walk writes other lines.
+//
+// The derivative the walk starts with (flatten.wgsl:355-358)
+JD V2 start_deriv(V2 p0, V2 p1, V2 p2, V2 p3) {
+    V2 q = p1 - p0;
+    if (dot(q, q) < DERIV_THRESH_SQUARED) q = eval_cubic_and_deriv(p0, p1, p2, p3, DERIV_EPS).deriv;
+    return q;
 }
-// slot_info of the n lines of a piece whose first line has slot tpos
-JD void piece_slots_write(uint2* __restrict__ sinfo, uint32_t tpos, uint32_t n_u, uint32_t r) {
-    for (uint32_t i = 0u; i < n_u; i++) sinfo[tpos + i] = make_uint2(r, FL_INFO_PIECE | (n_u << 8) | i);
+// Point and derivative at the end t1 of an interval (flatten.wgsl:366-383): where the derivative vanishes both are taken
+// DERIV_EPS earlier, and the interval ends there -- except at t1 == 1, which keeps its point
+struct IntervalEnd { PointDeriv pq; float t1; };
+JD IntervalEnd interval_end(V2 p0, V2 p1, V2 p2, V2 p3, float t1) {
+    IntervalEnd r;
+    r.pq = eval_cubic_and_deriv(p0, p1, p2, p3, t1);
+    if (dot(r.pq.deriv, r.pq.deriv) < DERIV_THRESH_SQUARED) {
+        PointDeriv new_pq1 = eval_cubic_and_deriv(p0, p1, p2, p3, t1 - DERIV_EPS);
+        r.pq.deriv = new_pq1.deriv;
+        if (t1 < 1.0f) { r.pq.point = new_pq1.point; t1 = t1 - DERIV_EPS; }
+    }
+    r.t1 = t1;
+    return r;
+}
+// a and b of the two cases of flatten.wgsl:413-433 that have them (robust != FL_ROBUST_LOW_K1)
+struct PieceAB { float a, b; };
+JD PieceAB piece_ab(const EulerParams& ep, float noff, uint32_t robust) {
+    const float k0 = ep.k0 - 0.5f * ep.k1, k1 = ep.k1;
+    const float dist_scaled = noff * ep.ch;
+    PieceAB r;
+    if (robust == FL_ROBUST_LOW_DIST) { r.a = k1; r.b = k0; }
+    else { r.a = -2.0f * dist_scaled * k1; r.b = -1.0f - 2.0f * dist_scaled * k0; }
+    return r;
+}
+// What flatten.wgsl:404-447 computes for an accepted interval besides the lines themselves: the Euler parameters and
+// the number of lines.
+struct PieceParams {
+    EulerParams ep;
+    float noff, int0, integral;
+    uint32_t n_u, robust;
+};
+JD PieceParams piece_params(const CubicParams& cp, float scale, float offset) {
+    const float tol = 0.25f;
+    PieceParams r;
+    r.ep = es_params_from_angles(cp.th0, cp.th1);
+    const EulerParams& ep = r.ep;
+    float k0 = ep.k0 - 0.5f * ep.k1;
+    float k1 = ep.k1;
+    float normalized_offset = offset / cp.chord_len;
+    float dist_scaled = normalized_offset * ep.ch;
+    float scale_multiplier = sqrt_(0.125f * scale * cp.chord_len / (ep.ch * tol));
+    float integral = 0.0f, int0 = 0.0f, n_frac;
+    uint32_t robust = FL_ROBUST_NORMAL;
+    if (abs_(k1) < K1_THRESH) {
+        float k = ep.k0;
+        n_frac = sqrt_(abs_(k * (k * dist_scaled + 1.0f)));
+        robust = FL_ROBUST_LOW_K1;
+    } else if (abs_(dist_scaled) < DIST_THRESH) {
+        robust = FL_ROBUST_LOW_DIST;
+        const PieceAB ab = piece_ab(ep, normalized_offset, robust);
+        int0 = pow_1_5_signed(ab.b);
+        float int1 = pow_1_5_signed(ab.a + ab.b);
+        integral = int1 - int0;
+        n_frac = (float)(2.0 / 3.0) * integral / ab.a;
+    } else {
+        const PieceAB ab = piece_ab(ep, normalized_offset, robust);
+        int0 = espc_int_approx(ab.b);
+        float int1 = espc_int_approx(ab.a + ab.b);
+        integral = int1 - int0;
+        float k_peak = k0 - k1 * ab.b / ab.a;
+        float integrand_peak = sqrt_(abs_(k_peak * (k_peak * dist_scaled + 1.0f)));
+        n_frac = integral * integrand_peak / ab.a;
+    }
+    r.n_u = to_u32(clamp_(ceil_(n_frac * scale_multiplier), 1.0f, 100.0f));
+    r.noff = normalized_offset; r.int0 = int0; r.integral = integral; r.robust = robust;
+    return r;
 }
 
 struct EulerJob {
@@ -444,7 +568,7 @@ JD void euler_begin(EulerLane& e, const EulerJob& job) {  // flatten.wgsl:328-36
     e.dt = 1.0f;
     e.last_p = e.p0;
     e.last_q = e.p1 - e.p0;
-    if (!e.done && dot(e.last_q, e.last_q) < DERIV_THRESH_SQUARED) e.last_q = eval_cubic_and_deriv(e.p0, e.p1, e.p2, e.p3, DERIV_EPS).deriv;
+    if (!e.done) e.last_q = start_deriv(e.p0, e.p1, e.p2, e.p3);
     e.last_t = 0.0f;
     e.t_start = t_start;
     e.first_piece = true;
@@ -453,17 +577,13 @@ JD void euler_begin(EulerLane& e, const EulerJob& job) {  // flatten.wgsl:328-36
 // `refill()` is called (by the whole wave) when enough lanes are idle; it finalises finished items, gives idle
 // lanes new ones (euler_begin) and returns false once no lane is active and the queue is empty.
 template <class Refill>
-JD void flatten_euler_wave(Out<true>& o, EulerLane& e, Refill&& refill) {
-    V2 &p0 = e.p0, &p1 = e.p1, &p2 = e.p2, &p3 = e.p3;
-    float& scale = e.scale;
-    const float& offset = e.offset;
-    V2& t_end = e.t_end;
-    bool& done = e.done;
-    const float tol = 0.25f;
-    uint32_t& t0_u = e.t0_u;
-    float& dt = e.dt;
+JD void flatten_euler_wave(Out& o, EulerLane& e, Refill&& refill) {
+    const V2 &p0 = e.p0, &p1 = e.p1, &p2 = e.p2, &p3 = e.p3;
+    const float &scale = e.scale, &offset = e.offset, tol = 0.25f;
     V2 &last_p = e.last_p, &last_q = e.last_q;
-    float& last_t = e.last_t;
+    float &last_t = e.last_t, &dt = e.dt;
+    uint32_t& t0_u = e.t0_u;
+    bool& done = e.done;
     for (;;) {
         {
             uint64_t idle = __builtin_amdgcn_ballot_w64(done);
@@ -473,9 +593,7 @@ JD void flatten_euler_wave(Out<true>& o, EulerLane& e, Refill&& refill) {
 
         bool accept = false;
         uint32_t n_u = 0u;
-        float pc_noff = 0.0f, pc_int0 = 0.0f, pc_integral = 0.0f;
-        EulerParams ep;
-        ep.th0 = ep.th1 = ep.k0 = ep.k1 = ep.ch = 0.0f;
+        float pc_noff = 0.0f, pc_int0 = 0.0f, pc_integral = 0.0f, pc_th0 = 0.0f, pc_th1 = 0.0f;
         V2 es_p0 = v2(0, 0), es_p1 = v2(0, 0);
         uint32_t pc_flags = 0u;
         if (!done) {
@@ -483,60 +601,19 @@ JD void flatten_euler_wave(Out<true>& o, EulerLane& e, Refill&& refill) {
             if (t0 == 1.0f) {
                 done = true;
             } else {
-                float t1 = t0 + dt;
-                V2 this_p0 = last_p;
-                V2 this_q0 = last_q;
-                PointDeriv this_pq1 = eval_cubic_and_deriv(p0, p1, p2, p3, t1);
-                if (dot(this_pq1.deriv, this_pq1.deriv) < DERIV_THRESH_SQUARED) {
-                    PointDeriv new_pq1 = eval_cubic_and_deriv(p0, p1, p2, p3, t1 - DERIV_EPS);
-                    this_pq1.deriv = new_pq1.deriv;
-                    if (t1 < 1.0f) {
-                        this_pq1.point = new_pq1.point;
-                        t1 = t1 - DERIV_EPS;
-                    }
-                }
-                float actual_dt = t1 - last_t;
-                CubicParams cp = cubic_from_points_derivs(this_p0, this_pq1.point, this_q0, this_pq1.deriv, actual_dt);
+                const IntervalEnd ie = interval_end(p0, p1, p2, p3, t0 + dt);
+                float actual_dt = ie.t1 - last_t;
+                CubicParams cp = cubic_from_points_derivs(last_p, ie.pq.point, last_q, ie.pq.deriv, actual_dt);
                 if (cp.err * scale <= tol || dt <= SUBDIV_LIMIT) {
-                    ep = es_params_from_angles(cp.th0, cp.th1);
-                    float k0 = ep.k0 - 0.5f * ep.k1;
-                    float k1 = ep.k1;
-                    float normalized_offset = offset / cp.chord_len;
-                    float dist_scaled = normalized_offset * ep.ch;
-                    float scale_multiplier = sqrt_(0.125f * scale * cp.chord_len / (ep.ch * tol));
-                    float a = 0.0f, b = 0.0f, integral = 0.0f, int0 = 0.0f, n_frac;
-                    uint32_t robust = 0u;
-                    if (abs_(k1) < K1_THRESH) {
-                        float k = ep.k0;
-                        n_frac = sqrt_(abs_(k * (k * dist_scaled + 1.0f)));
-                        robust = 1u;
-                    } else if (abs_(dist_scaled) < DIST_THRESH) {
-                        a = k1;
-                        b = k0;
-                        int0 = pow_1_5_signed(b);
-                        float int1 = pow_1_5_signed(a + b);
-                        integral = int1 - int0;
-                        n_frac = (float)(2.0 / 3.0) * integral / a;
-                        robust = 2u;
-                    } else {
-                        a = -2.0f * dist_scaled * k1;
-                        b = -1.0f - 2.0f * dist_scaled * k0;
-                        int0 = espc_int_approx(b);
-                        float int1 = espc_int_approx(a + b);
-                        integral = int1 - int0;
-                        float k_peak = k0 - k1 * b / a;
-                        float integrand_peak = sqrt_(abs_(k_peak * (k_peak * dist_scaled + 1.0f)));
-                        n_frac = integral * integrand_peak / a;
-                    }
-                    float n = clamp_(ceil_(n_frac * scale_multiplier), 1.0f, 100.0f);
-                    n_u = to_u32(n);
+                    const PieceParams pp = piece_params(cp, scale, offset);
+                    n_u = pp.n_u;
                     accept = true;
-                    pc_noff = normalized_offset; pc_int0 = int0; pc_integral = integral;  // (a, b: two products, recomputed)
-                    es_p0 = this_p0; es_p1 = this_pq1.point;
-                    pc_flags = robust | ((t1 == 1.0f) ? 4u : 0u) | ((offset >= 0.0f) ? 8u : 0u) | ((offset == 0.0f) ? 16u : 0u);
-                    last_p = this_pq1.point;
-                    last_q = this_pq1.deriv;
-                    last_t = t1;
+                    pc_noff = pp.noff; pc_int0 = pp.int0; pc_integral = pp.integral; pc_th0 = pp.ep.th0; pc_th1 = pp.ep.th1;
+                    es_p0 = last_p; es_p1 = ie.pq.point;
+                    pc_flags = piece_flags(pp.robust, ie.t1, offset, e.first_piece);
+                    last_p = ie.pq.point;
+                    last_q = ie.pq.deriv;
+                    last_t = ie.t1;
                     t0_u += 1u;
                     uint32_t shift = (t0_u == 0u) ? 32u : (uint32_t)__builtin_ctz(t0_u);
                     t0_u = (shift >= 32u) ? 0u : (t0_u >> shift);
@@ -550,11 +627,9 @@ JD void flatten_euler_wave(Out<true>& o, EulerLane& e, Refill&& refill) {
         if (accept) {  // (n slots and n records per piece, of which the piece uses the first: this walk is the rare fall-back)
             const uint32_t first = o.alloc(n_u);
             const uint32_t tpos = o.a_spos, r = o.a_rpos;
-            if (r != FL_INVALID) {
-                const uint32_t fl = pc_flags | (e.first_piece ? 32u : 0u);
-                piece_record_write(o.T.recs + (size_t)r * 4u, es_p0, es_p1, ep.th0, ep.th1, pc_int0, pc_integral, pc_noff, o.slot, e.path_ix,
-                                   e.trans_ix, fl, first, e.t_start, t_end);
-            }
+            if (r != FL_INVALID)
+                piece_record_write(o.T.recs + (size_t)r * 4u, es_p0, es_p1, pc_th0, pc_th1, pc_int0, pc_integral, pc_noff, o.slot, e.path_ix, e.trans_ix,
+                                   pc_flags, first, e.t_start, e.t_end);
             if (tpos != FL_INVALID) {
                 if (r != FL_INVALID) piece_slots_write(o.T.sinfo, tpos, n_u, r);
                 else for (uint32_t i = 0u; i < n_u; i++) o.T.sinfo[tpos + i] = make_uint2(0u, 0u);
@@ -565,8 +640,7 @@ JD void flatten_euler_wave(Out<true>& o, EulerLane& e, Refill&& refill) {
 }
 
 // flatten.wgsl:490-517
-template <bool EMIT>
-JD void flatten_arc(Out<EMIT>& o, uint32_t path_ix, V2 begin, V2 end, V2 center, float angle, const Xf& transform) {
+JD void flatten_arc(Out& o, uint32_t path_ix, V2 begin, V2 end, V2 center, float angle, const Xf& transform) {
     V2 p0 = xf_apply(transform, begin);
     V2 r = begin - center;
     const float MIN_THETA = 0.0001f;
@@ -575,24 +649,21 @@ JD void flatten_arc(Out<EMIT>& o, uint32_t path_ix, V2 begin, V2 end, V2 center,
     float theta = fmax_(MIN_THETA, 2.0f * acos_(1.0f - tol / radius));
     uint32_t n_lines = umax_(1u, to_u32(ceil_(angle / theta)));
     uint32_t line_ix = o.alloc(n_lines);
-    if (EMIT) {
-        float cs = cos_(theta);
-        float sn = sin_(theta);
-        for (uint32_t i = 0; i < n_lines - 1u; i++) {
-            r = v2(cs * r.x + sn * r.y, -sn * r.x + cs * r.y);
-            V2 p1 = xf_apply(transform, center + r);
-            o.write_line(line_ix + i, path_ix, p0, p1);
-            p0 = p1;
-        }
-        V2 p1 = xf_apply(transform, end);
-        o.write_line(line_ix + n_lines - 1u, path_ix, p0, p1);
+    float cs = cos_(theta);
+    float sn = sin_(theta);
+    for (uint32_t i = 0; i < n_lines - 1u; i++) {
+        r = v2(cs * r.x + sn * r.y, -sn * r.x + cs * r.y);
+        V2 p1 = xf_apply(transform, center + r);
+        o.write_line(line_ix + i, path_ix, p0, p1);
+        p0 = p1;
     }
+    V2 p1 = xf_apply(transform, end);
+    o.write_line(line_ix + n_lines - 1u, path_ix, p0, p1);
 }
 // flatten.wgsl:519-543
-template <bool EMIT>
-JD void draw_cap(Out<EMIT>& o, uint32_t path_ix, uint32_t cap_style, V2 point, V2 cap0, V2 cap1, V2 offset_tangent, const Xf& transform) {
+JD void draw_cap(Out& o, uint32_t path_ix, uint32_t cap_style, V2 point, V2 cap0, V2 cap1, V2 offset_tangent, const Xf& transform) {
     if (cap_style == JL_STYLE_FLAGS_CAP_ROUND) {
-        flatten_arc<EMIT>(o, path_ix, cap0, cap1, point, 3.1415927f, transform);
+        flatten_arc(o, path_ix, cap0, cap1, point, 3.1415927f, transform);
         return;
     }
     V2 start = cap0, end = cap1;
@@ -610,8 +681,7 @@ JD void draw_cap(Out<EMIT>& o, uint32_t path_ix, uint32_t cap_style, V2 point, V
     o.write_line_t(line_ix, path_ix, start, end, transform);
 }
 // flatten.wgsl:545-614
-template <bool EMIT>
-JD void draw_join(Out<EMIT>& o, uint32_t path_ix, uint32_t style_flags, V2 p0, V2 tan_prev, V2 tan_next, V2 n_prev, V2 n_next,
+JD void draw_join(Out& o, uint32_t path_ix, uint32_t style_flags, V2 p0, V2 tan_prev, V2 tan_next, V2 n_prev, V2 n_next,
                   const Xf& transform) {
     V2 front0 = p0 + n_prev;
     V2 front1 = p0 + n_next;
@@ -649,7 +719,7 @@ JD void draw_join(Out<EMIT>& o, uint32_t path_ix, uint32_t style_flags, V2 p0, V
         V2 arc0, arc1, other0, other1;
         if (cr > 0.0f) { arc0 = back0; arc1 = back1; other0 = front0; other1 = front1; }
         else { arc0 = front0; arc1 = front1; other0 = back0; other1 = back1; }
-        flatten_arc<EMIT>(o, path_ix, arc0, arc1, p0, abs_(atan2_(cr, d)), transform);
+        flatten_arc(o, path_ix, arc0, arc1, p0, abs_(atan2_(cr, d)), transform);
         o.output_line_t(path_ix, other0, other1, transform);
     }
 }
@@ -885,8 +955,7 @@ __global__ __launch_bounds__(JL_WG) void k_flatten_classify(const JlConfig* __re
 }
 
 // Everything of an item except Euler flattening, which is returned as a job for flatten_euler_wave.
-template <bool EMIT>
-JD void run_item(const JlConfig* cfg, const Scene& s, Out<EMIT>& o, uint32_t slot, EulerJob& job, uint32_t& path_ix_out) {
+JD void run_item(const JlConfig* cfg, const Scene& s, Out& o, uint32_t slot, EulerJob& job, uint32_t& path_ix_out) {
     uint32_t ix = slot / 3u, sub = slot - ix * 3u;
     Seg g = load_seg(s, ix);
     uint32_t path_ix = g.tag.monoid.v[4];
@@ -911,8 +980,7 @@ JD void run_item(const JlConfig* cfg, const Scene& s, Out<EMIT>& o, uint32_t slo
             V2 tangent = cubic_start_tangent(pts.p0, pts.p1, pts.p2, pts.p3);
             V2 offset_tangent = offset * normalize(tangent);
             V2 n = v2(offset_tangent.y * -1.0f, offset_tangent.x * 1.0f);
-            draw_cap<EMIT>(o, path_ix, (style_flags & JL_STYLE_FLAGS_START_CAP_MASK) >> 2, pts.p0, pts.p0 - n, pts.p0 + n, -offset_tangent,
-                           transform);
+            draw_cap(o, path_ix, (style_flags & JL_STYLE_FLAGS_START_CAP_MASK) >> 2, pts.p0, pts.p0 - n, pts.p0 + n, -offset_tangent, transform);
         } else {
             const float TT = TANGENT_THRESH * TANGENT_THRESH;
             V2 tan_prev = cubic_end_tangent(pts.p0, pts.p1, pts.p2, pts.p3);
@@ -937,10 +1005,9 @@ JD void run_item(const JlConfig* cfg, const Scene& s, Out<EMIT>& o, uint32_t slo
                     if (dot(tan_next, tan_next) < TT) tan_next = v2(TANGENT_THRESH, 0.0f);
                     V2 tnn = normalize(tan_next);
                     V2 n_next = v2((offset * tnn.y) * -1.0f, (offset * tnn.x) * 1.0f);
-                    draw_join<EMIT>(o, path_ix, style_flags, pts.p3, tan_prev, tan_next, n_prev, n_next, transform);
+                    draw_join(o, path_ix, style_flags, pts.p3, tan_prev, tan_next, n_prev, n_next, transform);
                 } else {
-                    draw_cap<EMIT>(o, path_ix, (style_flags & JL_STYLE_FLAGS_END_CAP_MASK), pts.p3, pts.p3 + n_prev, pts.p3 - n_prev, offset_tangent,
-                                   transform);
+                    draw_cap(o, path_ix, (style_flags & JL_STYLE_FLAGS_END_CAP_MASK), pts.p3, pts.p3 + n_prev, pts.p3 - n_prev, offset_tangent, transform);
                 }
             }
         }
@@ -994,8 +1061,6 @@ struct FlBatch {
 struct NodeResult {
     bool accept;
     CubicParams cp;
-    V2 es_p0, es_p1;
-    bool ends_at_one;
 };
 // The two ends of the interval [t0_u, t0_u + 1] * 2^-level as the sequential walk of flatten.wgsl:362-383 sees them: the
 // state it carries into the interval (the end of the piece that ended at t0) and the point / derivative at t1.
@@ -1011,8 +1076,7 @@ JD NodeEnds node_ends(V2 p0, V2 p1, V2 p2, V2 p3, uint32_t level, uint32_t t0_u)
     NodeEnds r;
     if (t0_u == 0u) {
         r.last_p = p0;
-        r.last_q = p1 - p0;
-        if (dot(r.last_q, r.last_q) < DERIV_THRESH_SQUARED) r.last_q = eval_cubic_and_deriv(p0, p1, p2, p3, DERIV_EPS).deriv;
+        r.last_q = start_deriv(p0, p1, p2, p3);
         r.last_t = 0.0f;
     } else {
         PointDeriv pq0 = eval_cubic_and_deriv(p0, p1, p2, p3, t0);
@@ -1026,19 +1090,10 @@ JD NodeEnds node_ends(V2 p0, V2 p1, V2 p2, V2 p3, uint32_t level, uint32_t t0_u)
         r.last_p = pq0.point;
         r.last_q = pq0.deriv;
     }
-    float t1 = t0 + dt;
-    PointDeriv this_pq1 = eval_cubic_and_deriv(p0, p1, p2, p3, t1);
-    if (dot(this_pq1.deriv, this_pq1.deriv) < DERIV_THRESH_SQUARED) {
-        PointDeriv new_pq1 = eval_cubic_and_deriv(p0, p1, p2, p3, t1 - DERIV_EPS);
-        this_pq1.deriv = new_pq1.deriv;
-        if (t1 < 1.0f) {
-            this_pq1.point = new_pq1.point;
-            t1 = t1 - DERIV_EPS;
-        }
-    }
-    r.point = this_pq1.point;
-    r.deriv = this_pq1.deriv;
-    r.t1 = t1;
+    const IntervalEnd ie = interval_end(p0, p1, p2, p3, t0 + dt);
+    r.point = ie.pq.point;
+    r.deriv = ie.pq.deriv;
+    r.t1 = ie.t1;
     return r;
 }
 // One attempt of flatten.wgsl:362-403 for the interval [t0_u, t0_u + 1] * 2^-level of the cubic (p0..p3): the pinned sequence.
@@ -1050,9 +1105,6 @@ JD NodeResult node_test(V2 p0, V2 p1, V2 p2, V2 p3, float scale, uint32_t level,
     NodeResult r;
     r.cp = cubic_from_points_derivs(ne.last_p, ne.point, ne.last_q, ne.deriv, actual_dt);
     r.accept = r.cp.err * scale <= tol || dt <= SUBDIV_LIMIT;
-    r.es_p0 = ne.last_p;
-    r.es_p1 = ne.point;
-    r.ends_at_one = ne.t1 == 1.0f;
     return r;
 }
 // The same attempt, DECIDED without transcendentals where that is provably safe (flatten_fast.h): FF_ACCEPT / FF_REJECT
@@ -1062,22 +1114,15 @@ JD int node_test_fast(V2 p0, V2 p1, V2 p2, V2 p3, float scale, uint32_t level, u
     const float tol = 0.25f;
     const NodeEnds ne = node_ends(p0, p1, p2, p3, level, t0_u);
     const float actual_dt = ne.t1 - ne.last_t;
-    // cubic_from_points_derivs (flatten.wgsl:94-114) up to d0 / d1: chord and h0 / h1 with the same operations on the same
-    // values, the roots and the quotient with the 1-ulp instructions (flatten_fast.h charges them)
     const V2 chord = ne.point - ne.last_p;
-    const float chord_squared = dot(chord, chord);
     const V2 q0 = ne.last_q, q1 = ne.deriv;
     *v_est = 0.0f; *delta = 0.0f;
-    if (chord_squared < DERIV_THRESH_SQUARED) {  // no transcendentals in this branch: decided exactly, by the pinned operations
+    if (dot(chord, chord) < DERIV_THRESH_SQUARED) {  // no transcendentals in this branch: decided exactly, by the pinned operations
         const float chord_err = sqrt_((float)(9.0 / 32.0) * (dot(q0, q0) + dot(q1, q1))) * actual_dt;
         return (chord_err * scale <= tol) ? ffast::FF_ACCEPT : ffast::FF_REJECT;
     }
-    const float chord_len = FF_SQRT(chord_squared);
-    const float sc = actual_dt * FF_RCP(chord_squared);
-    const V2 h0 = v2(q0.x * chord.x + q0.y * chord.y, q0.y * chord.x - q0.x * chord.y);
-    const V2 h1 = v2(q1.x * chord.x + q1.y * chord.y, q1.x * chord.y - q1.y * chord.x);
-    const float len0 = FF_SQRT(h0.x * h0.x + h0.y * h0.y), len1 = FF_SQRT(h1.x * h1.x + h1.y * h1.y);
-    return ffast::ff_decide(h0.x, h0.y, len0, h1.x, h1.y, len1, len0 * sc, len1 * sc, chord_len, scale, tol, v_est, delta);
+    // (the operands with the 1-ulp instructions: flatten_fast.h prepares and charges them)
+    return ffast::ff_decide_interval(chord.x, chord.y, q0.x, q0.y, q1.x, q1.y, actual_dt, scale, tol, v_est, delta);
 }
 // th0, th1 and chord_len of an ACCEPTED interval (the pinned atan2; err is not needed any more)
 JD CubicParams piece_angles(const NodeEnds& ne) {
@@ -1098,55 +1143,24 @@ JD CubicParams piece_angles(const NodeEnds& ne) {
     return r;
 }
 
-// What flatten.wgsl:404-447 computes for an accepted interval besides the lines themselves: the Euler parameters and
-// the number of lines.
-struct PieceParams {
-    EulerParams ep;
-    float n, noff, int0, integral;
-    uint32_t n_u, robust;
-};
-JD PieceParams piece_params(const CubicParams& cp, float scale, float offset) {
-    const float tol = 0.25f;
-    PieceParams r;
-    r.ep = es_params_from_angles(cp.th0, cp.th1);
-    const EulerParams& ep = r.ep;
-    float k0 = ep.k0 - 0.5f * ep.k1;
-    float k1 = ep.k1;
-    float normalized_offset = offset / cp.chord_len;
-    float dist_scaled = normalized_offset * ep.ch;
-    float scale_multiplier = sqrt_(0.125f * scale * cp.chord_len / (ep.ch * tol));
-    float a = 0.0f, b = 0.0f, integral = 0.0f, int0 = 0.0f, n_frac;
-    uint32_t robust = 0u;
-    if (abs_(k1) < K1_THRESH) {
-        float k = ep.k0;
-        n_frac = sqrt_(abs_(k * (k * dist_scaled + 1.0f)));
-        robust = 1u;
-    } else if (abs_(dist_scaled) < DIST_THRESH) {
-        a = k1;
-        b = k0;
-        int0 = pow_1_5_signed(b);
-        float int1 = pow_1_5_signed(a + b);
-        integral = int1 - int0;
-        n_frac = (float)(2.0 / 3.0) * integral / a;
-        robust = 2u;
-    } else {
-        a = -2.0f * dist_scaled * k1;
-        b = -1.0f - 2.0f * dist_scaled * k0;
-        int0 = espc_int_approx(b);
-        float int1 = espc_int_approx(a + b);
-        integral = int1 - int0;
-        float k_peak = k0 - k1 * b / a;
-        float integrand_peak = sqrt_(abs_(k_peak * (k_peak * dist_scaled + 1.0f)));
-        n_frac = integral * integrand_peak / a;
-    }
-    r.n = clamp_(ceil_(n_frac * scale_multiplier), 1.0f, 100.0f);
-    r.n_u = to_u32(r.n);
-    r.noff = normalized_offset;
-    r.int0 = int0;
-    r.integral = integral;
-    r.robust = robust;
-    return r;
-}
+
+// The state of job j of a batch.  It stays in the registers of the lane that set the job up -- no LDS storage: occupancy is
+// bound by registers only -- and is fetched from there (every lane takes part in the permutes).  A node needs the cubic and
+// the scale (FL_JOB_CURVE); a piece also the offset, the ids of its job and, if it is the item's first or last, the item's
+// end points (FL_JOB_PIECE).  Macros, not functions: through a function (by value, by reference, a lambda: all tried) the
+// compiler pairs the operations of the node test differently for its packed instructions and k_flatten_items spills two
+// registers more -- as with n_unsure below, the kernel is held to the code that was measured.
+struct JobState { V2 p0, p1, p2, p3; float scale, offset; uint32_t slot, path_ix, trans_ix; V2 t_start, t_end; };
+#define FL_JOB_CURVE(JB, E, J)                                                                                                      \
+    JobState JB;                                                                                                                    \
+    JB.p0 = v2(read_lane_var(E.p0.x, J), read_lane_var(E.p0.y, J)); JB.p1 = v2(read_lane_var(E.p1.x, J), read_lane_var(E.p1.y, J)); \
+    JB.p2 = v2(read_lane_var(E.p2.x, J), read_lane_var(E.p2.y, J)); JB.p3 = v2(read_lane_var(E.p3.x, J), read_lane_var(E.p3.y, J)); \
+    JB.scale = read_lane_var(E.scale, J)
+#define FL_JOB_PIECE(JB, E, SLOT, J)                                                                                                \
+    FL_JOB_CURVE(JB, E, J); JB.offset = read_lane_var(E.offset, J);                                                                 \
+    JB.slot = read_lane_var(SLOT, J); JB.path_ix = read_lane_var(E.path_ix, J); JB.trans_ix = read_lane_var(E.trans_ix, J);         \
+    JB.t_start = v2(read_lane_var(E.t_start.x, J), read_lane_var(E.t_start.y, J));                                                  \
+    JB.t_end = v2(read_lane_var(E.t_end.x, J), read_lane_var(E.t_end.y, J))
 
 #ifdef FL_FAST_CHECK
 __device__ uint32_t g_ff_stats[8];  // nodes tested, undecided, contradictions, bound violations
@@ -1196,7 +1210,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
     __syncthreads();
     const uint32_t lane = lane_id();
     FlBatch& B = sh_batch[threadIdx.x >> 6];
-    Out<true> o;
+    Out o;
     o.cfg = cfg; o.T = T; o.home_s = o.home_r = blockIdx.x % T.K; o.failed_s = o.failed_r = false; o.slot = 0u;
     if ((debug & 1u) != 0u) o.home_s = o.home_r = 0u;  // (jh_debug_flatten_regions: regions fill up and are left behind on ordinary scenes)
 #ifdef FL_SOAK_HOME0  // (tools/lab.py parity home0: the same for every frame of the build)
@@ -1242,7 +1256,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             slot = heavy ? list[t] : list[cap - 1u - (t - n_heavy)];
             o.slot = slot; o.cursor = 0u; o.a_first = 0u; o.a_spos = 0u; o.a_rpos = 0u;
             uint32_t path_ix;
-            run_item<true>(cfg, s, o, slot, job, path_ix);
+            run_item(cfg, s, o, slot, job, path_ix);
             if (!job.valid) counts[slot] = o.cursor;  // a direct item is complete
         }
         EulerLane e;
@@ -1280,26 +1294,22 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             const uint32_t node = has ? (exact_round ? B.unsure[nu - 1u - lane] : B.stack[ns - 1u - lane]) : 0u;
             wave_sync();
             const uint32_t j = node & 63u, level = (node >> 6) & 31u, t0_u = node >> 11;
-            // the job's state (control points, scale, offset, ids) stays in the registers of the lane that set the job up -- no LDS
-            // storage: occupancy is bound by registers only -- and is fetched from there (every lane takes part in the permutes)
-            const V2 jp0 = v2(read_lane_var(e.p0.x, j), read_lane_var(e.p0.y, j)), jp1 = v2(read_lane_var(e.p1.x, j), read_lane_var(e.p1.y, j));
-            const V2 jp2 = v2(read_lane_var(e.p2.x, j), read_lane_var(e.p2.y, j)), jp3 = v2(read_lane_var(e.p3.x, j), read_lane_var(e.p3.y, j));
-            const float scale = read_lane_var(e.scale, j);
+            FL_JOB_CURVE(jb, e, j);
             int kind = ffast::FF_UNSURE;
             if (exact_round) {
-                if (has) kind = node_test(jp0, jp1, jp2, jp3, scale, level, t0_u).accept ? ffast::FF_ACCEPT : ffast::FF_REJECT;
+                if (has) kind = node_test(jb.p0, jb.p1, jb.p2, jb.p3, jb.scale, level, t0_u).accept ? ffast::FF_ACCEPT : ffast::FF_REJECT;
             } else if (has) {
                 float v_est, delta;
-                kind = node_test_fast(jp0, jp1, jp2, jp3, scale, level, t0_u, &v_est, &delta);
+                kind = node_test_fast(jb.p0, jb.p1, jb.p2, jb.p3, jb.scale, level, t0_u, &v_est, &delta);
 #ifdef FL_FAST_CHECK  // (make VARIANT=ffcheck: both paths on every node; contradictions and bound violations are counted)
             }
             if (!exact_round) {  // (uniform; every lane takes part in the ballots: one atomic per wave and counter, not one per node)
                 bool c_unsure = false, c_contra = false, c_viol = false;
                 if (has) {
                     float v2_, d2_;
-                    const int k2 = node_test_fast(jp0, jp1, jp2, jp3, scale, level, t0_u, &v2_, &d2_);
-                    const NodeResult rx = node_test(jp0, jp1, jp2, jp3, scale, level, t0_u);
-                    const float vx = rx.cp.err * scale;
+                    const int k2 = node_test_fast(jb.p0, jb.p1, jb.p2, jb.p3, jb.scale, level, t0_u, &v2_, &d2_);
+                    const NodeResult rx = node_test(jb.p0, jb.p1, jb.p2, jb.p3, jb.scale, level, t0_u);
+                    const float vx = rx.cp.err * jb.scale;
                     c_unsure = k2 == ffast::FF_UNSURE;
                     c_contra = (k2 == ffast::FF_ACCEPT && !rx.accept) || (k2 == ffast::FF_REJECT && rx.accept);
                     c_viol = (d2_ > 0.0f && !(abs_(v2_ - vx) <= d2_)) || (d2_ == 0.0f && k2 != ffast::FF_UNSURE && v2_ != 0.0f);
@@ -1366,22 +1376,16 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             const bool has = li < nl;
             const uint32_t node = has ? B.l_tpos[li] : 0u;
             const uint32_t j = node & 63u, level = (node >> 6) & 31u, t0_u = node >> 11;
-            const V2 jp0 = v2(read_lane_var(e.p0.x, j), read_lane_var(e.p0.y, j)), jp1 = v2(read_lane_var(e.p1.x, j), read_lane_var(e.p1.y, j));
-            const V2 jp2 = v2(read_lane_var(e.p2.x, j), read_lane_var(e.p2.y, j)), jp3 = v2(read_lane_var(e.p3.x, j), read_lane_var(e.p3.y, j));
-            const float scale = read_lane_var(e.scale, j), offset = read_lane_var(e.offset, j);
-            // a piece needs the ids of its job and, if it is the item's first or last, the item's end points
-            const uint32_t j_slot = read_lane_var(slot, j), j_path = read_lane_var(e.path_ix, j), j_trans = read_lane_var(e.trans_ix, j);
-            const float j_tsx = read_lane_var(e.t_start.x, j), j_tsy = read_lane_var(e.t_start.y, j), j_tex = read_lane_var(e.t_end.x, j), j_tey = read_lane_var(e.t_end.y, j);
+            FL_JOB_PIECE(jb, e, slot, j);
             if (has) {
-                const NodeEnds ne = node_ends(jp0, jp1, jp2, jp3, level, t0_u);
+                const NodeEnds ne = node_ends(jb.p0, jb.p1, jb.p2, jb.p3, level, t0_u);
                 const CubicParams cp = piece_angles(ne);
-                const PieceParams pp = piece_params(cp, scale, offset);
-                const uint32_t fl = pp.robust | ((ne.t1 == 1.0f) ? 4u : 0u) | ((offset >= 0.0f) ? 8u : 0u) | ((offset == 0.0f) ? 16u : 0u) |
-                                    ((t0_u == 0u) ? 32u : 0u);
+                const PieceParams pp = piece_params(cp, jb.scale, jb.offset);
+                const uint32_t fl = piece_flags(pp.robust, ne.t1, jb.offset, t0_u == 0u);
                 const uint32_t r = rec_base + li;
-                if (rec_base != FL_INVALID)  // (word 12 of a piece that is not its item's first -- the index of its first line -- is written below)
-                    piece_record_write(T.recs + (size_t)r * 4u, ne.last_p, ne.point, pp.ep.th0, pp.ep.th1, pp.int0, pp.integral, pp.noff, j_slot, j_path,
-                                       j_trans, fl, 0u, v2(j_tsx, j_tsy), v2(j_tex, j_tey));
+                if (rec_base != FL_INVALID)  // (the first line of a piece that is not its item's first is filled in below: piece_record_set_first)
+                    piece_record_write(T.recs + (size_t)r * 4u, ne.last_p, ne.point, pp.ep.th0, pp.ep.th1, pp.int0, pp.integral, pp.noff, jb.slot,
+                                       jb.path_ix, jb.trans_ix, fl, 0u, jb.t_start, jb.t_end);
                 B.l_key[li] = (uint16_t)(B.l_key[li] | pp.n_u);
             }
         }
@@ -1422,7 +1426,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
             for (uint32_t li = lane; li < nl; li += 64u) {
                 const uint32_t j = B.l_link[li] >> 10, key = B.l_key[li], first = B.l_tpos[li];
                 const uint32_t r = rec_base + li, jb = B.unsure[j];
-                if (rec_base != FL_INVALID && (key >> 7) != 0u) ((uint32_t*)T.recs)[(size_t)r * 16u + 12u] = first;  // (t0 != 0: not the item's first piece)
+                if (rec_base != FL_INVALID && (key >> 7) != 0u) piece_record_set_first(T.recs + (size_t)r * 4u, first);  // (t0 != 0: not the item's first piece)
                 if (jb == FL_INVALID) continue;
                 if (rec_base != FL_INVALID) piece_slots_write(T.sinfo, jb + first, key & 127u, r);
                 else for (uint32_t i = 0u; i < (key & 127u); i++) T.sinfo[jb + first + i] = make_uint2(0u, 0u);  // (slots without a record: empty)
@@ -1450,6 +1454,8 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_WAVES_
     }
 #endif
 #undef FL_TL_END
+#undef FL_JOB_PIECE
+#undef FL_JOB_CURVE
 }
 
 // One thread per temporary slot: the Euler line (or the directly emitted line) that lives there, moved to
@@ -1472,7 +1478,7 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_LINES_
 #pragma unroll
     for (uint32_t c = 0u; c < FL_MAX_REGIONS; c++) {
         ru[c] = units;
-        used[c] = c < T.K ? umin_(counters[FL_CTR_CURSOR + FL_CUR_STRIDE * c], T.R) : 0u;
+        used[c] = c < T.K ? umin_(*fl_cursor_in(counters, c, 0), T.R) : 0u;
         units += (used[c] + JL_WG - 1u) / JL_WG;
     }
     auto fetch_info = [&](uint32_t u) -> uint2 {
@@ -1523,73 +1529,64 @@ __global__ __launch_bounds__(JL_WG) __attribute__((amdgpu_waves_per_eu(FL_LINES_
         uint32_t widx[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
         uint2 wdat[3] = {make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u)};
         if (st == 1u) {  // complete line: copy
-            const uint32_t item = r0.x, k = r0.y;
+            const uint32_t item = DREC_ITEM(r), k = DREC_K(r);
             if (item < n_slots) {
                 const uint32_t dst = bases[item] + k;
                 if (dst < lines_lim) {
-                    widx[0] = dst * 3u; wdat[0] = make_uint2(r0.z, 0u);
-                    widx[1] = dst * 3u + 1u; wdat[1] = make_uint2(r1.x, r1.y);
-                    widx[2] = dst * 3u + 2u; wdat[2] = make_uint2(r1.z, r1.w);
+                    widx[0] = dst * 3u; wdat[0] = make_uint2(DREC_PATH_IX(r), 0u);
+                    widx[1] = dst * 3u + 1u; wdat[1] = DREC_P0(r);
+                    widx[2] = dst * 3u + 2u; wdat[2] = DREC_P1(r);
                 }
             }
         } else if (st == 2u) {
-            const uint32_t n_u = (si.y >> 8) & 127u, i = si.y & 127u;
-            const uint32_t flags = r2.w & 63u;
-            const bool last_of_item = i + 1u == n_u && (flags & 4u) != 0u;
-            const uint32_t slot = r2.y, k = ((flags & 32u) != 0u ? 0u : r3.x) + i;
+            const uint32_t n_u = SINFO_LINES(si), i = SINFO_LINE(si);
+            const uint32_t flags = PREC_FLAGS(r);
+            const bool last_of_item = i + 1u == n_u && (flags & FL_PC_ENDS_AT_ONE) != 0u;
+            const uint32_t slot = PREC_ITEM(r), k = PREC_FIRST_LINE(r) + i;
             // (the transform and the line base only depend on the record: requested here, in front of the Euler evaluation, their
             // round trips pass under its ~500 instructions instead of following them)
             Xf tr;
-            if ((flags & 16u) != 0u) {
+            if ((flags & FL_PC_NO_OFFSET) != 0u) {
                 tr = xf_identity();
             } else {
-                uint32_t tb = cfg->layout.transform_base + (r2.w >> 6) * 6u;
+                uint32_t tb = cfg->layout.transform_base + PREC_TRANS_IX(r) * 6u;
                 tr.m0 = u2f(scene.rd(tb)); tr.m1 = u2f(scene.rd(tb + 1u)); tr.m2 = u2f(scene.rd(tb + 2u));
                 tr.m3 = u2f(scene.rd(tb + 3u)); tr.t0 = u2f(scene.rd(tb + 4u)); tr.t1 = u2f(scene.rd(tb + 5u));
             }
             const uint32_t slot_base = slot < n_slots ? bases[slot] : 0u;
             V2 lp1;
             if (last_of_item) {
-                lp1 = v2(u2f(r3.z), u2f(r3.w));
+                lp1 = PREC_T_END(r);
 #if defined(FL_LSPLIT) && FL_LSPLIT == 1  // (measurement builds only, tools/lab.py split lines: k_flatten_lines without the Euler evaluation -- results are wrong)
             } else if (true) {
-                lp1 = v2(u2f(r0.x) + (float)i, u2f(r0.w) + u2f(r1.x) + u2f(r1.y) + u2f(r1.z) + u2f(r1.w) + u2f(r2.x));
+                lp1 = v2(PREC_ES_P0(r).x + (float)i, PREC_ES_P1(r).y + PREC_TH0(r) + PREC_TH1(r) + PREC_INT0(r) + PREC_INTEGRAL(r) + PREC_NOFF(r));
 #endif
             } else {  // flatten.wgsl:404-461
-                const EulerParams ep = es_params_from_angles(u2f(r1.x), u2f(r1.y));
-                const float noff = u2f(r2.x), n = (float)n_u;
+                const EulerParams ep = es_params_from_angles(PREC_TH0(r), PREC_TH1(r));
+                const float noff = PREC_NOFF(r), n = (float)n_u;
                 const float tt = (float)(i + 1u) / n;
                 float sarg = tt;
-                const uint32_t robust = flags & 3u;
-                if (robust != 1u) {
-                    const float k0 = ep.k0 - 0.5f * ep.k1, k1 = ep.k1;
-                    const float dist_scaled = noff * ep.ch;
-                    const float int0 = u2f(r1.z), integral = u2f(r1.w);  // as k_flatten_items computed them
-                    float a, b;
-                    if (robust == 2u) {
-                        a = k1;
-                        b = k0;
-                    } else {
-                        a = -2.0f * dist_scaled * k1;
-                        b = -1.0f - 2.0f * dist_scaled * k0;
-                    }
+                const uint32_t robust = flags & FL_PC_ROBUST;
+                if (robust != FL_ROBUST_LOW_K1) {
+                    const PieceAB ab = piece_ab(ep, noff, robust);
+                    const float int0 = PREC_INT0(r), integral = PREC_INTEGRAL(r);  // as k_flatten_items computed them
                     float uu = integral * tt + int0;
                     float inv;
-                    if (robust == 2u) inv = pow23_abs_(uu) * sign_(uu); else inv = espc_int_inv_approx(uu);
-                    sarg = (inv - b) / a;
+                    if (robust == FL_ROBUST_LOW_DIST) inv = pow23_abs_(uu) * sign_(uu); else inv = espc_int_inv_approx(uu);
+                    sarg = (inv - ab.b) / ab.a;
                 }
-                lp1 = es_seg_eval_with_offset(v2(u2f(r0.x), u2f(r0.y)), v2(u2f(r0.z), u2f(r0.w)), ep, sarg, noff);
+                lp1 = es_seg_eval_with_offset(PREC_ES_P0(r), PREC_ES_P1(r), ep, sarg, noff);
             }
             const V2 q = xf_apply(tr, lp1);
             if (slot < n_slots) {
                 const uint32_t dst = slot_base + k;
-                const bool fwd = (flags & 8u) != 0u;  // offset >= 0: (start, end); else the line runs (end, start)
+                const bool fwd = (flags & FL_PC_FORWARD) != 0u;
                 const bool has_next = !last_of_item && dst + 1u < lines_lim;
-                const uint2 hdr = make_uint2(r2.z, 0u), pt = make_uint2(f2u(q.x), f2u(q.y));
+                const uint2 hdr = make_uint2(PREC_PATH_IX(r), 0u), pt = make_uint2(f2u(q.x), f2u(q.y));
                 if (dst < lines_lim) {
                     if (k == 0u) {  // the item's first line: header and start point (the job's start point), once per item
                         uint2* w = (uint2*)lines.p;
-                        const V2 qs = xf_apply(tr, v2(u2f(r3.x), u2f(r3.y)));
+                        const V2 qs = xf_apply(tr, PREC_T_START(r));
                         w[(size_t)dst * 3u] = hdr;
                         w[(size_t)dst * 3u + (fwd ? 1u : 2u)] = make_uint2(f2u(qs.x), f2u(qs.y));
                     }

@@ -45,15 +45,9 @@ static bool test_node(V2 lp, V2 p1, V2 q0, V2 q1, float dt, float scale, Stats& 
     V2 chord = p1 - lp;
     float chord_squared = dot(chord, chord);
     if (chord_squared < fl::DERIV_THRESH_SQUARED) { st.tiny_chord++; return accept; }  // (this branch has no transcendentals)
-    // (as k_flatten_items' node_test_fast computes them: the roots and the quotient through the 1-ulp operations)
-    float chord_len = FF_SQRT(chord_squared);
-    float sc = dt * FF_RCP(chord_squared);
-    V2 h0 = v2(q0.x * chord.x + q0.y * chord.y, q0.y * chord.x - q0.x * chord.y);
-    V2 h1 = v2(q1.x * chord.x + q1.y * chord.y, q1.x * chord.y - q1.y * chord.x);
-    float len0 = FF_SQRT(h0.x * h0.x + h0.y * h0.y), len1 = FF_SQRT(h1.x * h1.x + h1.y * h1.y);
-    float d0 = len0 * sc, d1 = len1 * sc;
+    // (the very function k_flatten_items' node_test_fast calls, operand preparation included)
     float ve, dl;
-    int k = ffast::ff_decide(h0.x, h0.y, len0, h1.x, h1.y, len1, d0, d1, chord_len, scale, tol, &ve, &dl);
+    int k = ffast::ff_decide_interval(chord.x, chord.y, q0.x, q0.y, q1.x, q1.y, dt, scale, tol, &ve, &dl);
     if (k == ffast::FF_UNSURE) st.unsure++;
     if (k == ffast::FF_ACCEPT) { st.acc++; if (!accept) st.contradictions++; }
     if (k == ffast::FF_REJECT) { st.rej++; if (accept) st.contradictions++; }
@@ -63,7 +57,7 @@ static bool test_node(V2 lp, V2 p1, V2 q0, V2 q1, float dt, float scale, Stats& 
         double r = diff / (double)dl;
         if (r > st.max_ratio) st.max_ratio = r;
         if (v > 0.05f && v < 1.25f && dl / v > st.max_rel_band) st.max_rel_band = dl / v;
-        if (ve == 2.0f * chord_len * scale) st.exact_sign++;  // (the err = 2 arm)
+        if (cp.err == 2.0f * cp.chord_len) st.exact_sign++;  // (the err = 2 arm: cosines of opposite signs, which both paths see alike)
     } else if (k != ffast::FF_UNSURE && ve != 0.0f) {
         st.bound_violations++;  // a decision without a bound
     }
