@@ -31,6 +31,7 @@
  *   jh_lighting                       (no counterpart: feDiffuseLighting / feSpecularLighting on the device)
  *   jh_turbulence                     (no counterpart: feTurbulence noise into an RGBA16F image on the device)
  *   jh_displace                       (no counterpart: feDisplacementMap on RGBA16F images on the device)
+ *   jh_shadow                         (no counterpart: a blurred rounded rectangle generated into an RGBA16F image)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -1051,6 +1052,82 @@ typedef struct jh_displace_desc {
 } jh_displace_desc;
 int jh_displace_offset(float scale, uint16_t f16_bits, int64_t* out);
 int jh_displace(jh_ctx* ctx, uint64_t src_image_id, uint64_t map_image_id, uint64_t dst_image_id, const jh_displace_desc* desc);
+
+/* ---- Shadow: the Gaussian blur of a rounded rectangle, GENERATED into an image or laid over it (DESIGN.md 5.18 "Shadow rule") ----
+ * The shadow under a card, a button, a window: the blur of this shape has a form that needs no source image, no intermediate and no
+ * blur pass, and its cost does not depend on sigma.  The result is defined on values, and every implementation produces these bits
+ * (include/jello_shadow.h states the host half and the device half's functions, tests/shadow_ref.py restates all of it).  Binary64
+ * appears in the plan and the bounds only.
+ *   arguments   the rectangle (x, y, width, height) of dst that is written (all zero: the whole image).  matrix[6]: binary64, (a, b,
+ *               c, d, e, f), x' = a x + c y + e, y' = b x + d y + f, from SHAPE space to continuous coordinates of the destination
+ *               IMAGE (texel (i, j) centred at (i + 0.5, j + 0.5)); legal as jh_warp's is.  box[4]: binary32 x0, y0, x1, y1 in shape
+ *               space.  radius, sigma: binary32, shape units.  color[4]: binary32, premultiplied, linear; any value.  flags:
+ *               JH_SHADOW_OVER = 1 | JH_SHADOW_INVERT = 2.
+ *   legal       the box finite with x1 >= x0 and y1 >= y0 (empty in a dimension is legal: S = 0) and every coordinate within
+ *               [-2^22, 2^22]; radius finite and >= 0; sigma finite and in [0, 2^16]; no other flag bit; image extents at most 2^23.
+ *   plan        jh_shadow_plan (a jh_shad_plan), on the host, binary64, every operation rounded once: m = jh_warp_plan's six integers of the matrix;
+ *               centre = (x0 + x1) / 2, a = (x1 - x0) / 2, likewise y and b; r = min(radius, a, b) (CSS's clamp); sigma' = max(sigma,
+ *               2^-8) (below it: the point-sampled shape); C = rint(centre 2^32); then, each rounded once to binary32: a, b, r, core =
+ *               a - r, straight = b - r, sigma', inv_s = 1 / (sigma' sqrt 2), window = K sigma' with K = 4.  N = 4 where r / sigma' <=
+ *               0.5, 8 where <= 1.5, else 16.
+ *   position    for destination texel (X, Y) of the image: U = m0 (2 X + 1) + m1 (2 Y + 1) + m2 - Cx, V = m3 (2 X + 1) + m4 (2 Y + 1) +
+ *               m5 - Cy, exact in int64 (below 2^63: |m0| <= 2^37, 2 X + 1 < 2^24), units of 2^-32.  x = (float)(int32)(U >> 32) +
+ *               (float)((uint32)U >> 8) 2^-24: the whole part converted (exact below 2^24), the fraction's low 8 bits dropped, the sum
+ *               rounded once; y of V.  The blur lives in shape space: a rotated box has a rotated shadow, and under a non-uniform
+ *               scale the blur is anisotropic on the device.
+ *   G(z)        the erf approximant, binary32: t = minNum(|z|, 4); u = t (a1 + t (a2 + t (a3 + t (a4 + t (a5 + t a6))))) by five fmaf
+ *               from the inside and one product, (a1 .. a6) = (0.0705230784, 0.0422820123, 0.0092705272, 0.0001520143, 0.0002765672,
+ *               0.0000430638) rounded to binary32; four times s = s (2 + s), from s = u; e = 1 - 1 / (1 + s), IEEE division; G =
+ *               copysign(e, z).  No table.  Monotone in binary32 and exactly 1 from |z| = 4 on; Phi(t) = (1 + G(t / sqrt 2)) / 2 within
+ *               2^-20 (measured 2.1e-7).
+ *   band        B(p, w) = G((p + w) inv_s) - G((p - w) inv_s), each sum, difference and product rounded once.
+ *   coverage    acc = B(y, straight) B(x, a).  With r > 0 the cap above, q = y - straight, then the cap below, q = -y - straight, add
+ *               to acc: lo = maxNum(q - window, 0), hi = minNum(q + window, r); nothing unless hi > lo; t0 = 1 - sqrt(1 - lo / r), t1 =
+ *               1 - sqrt(1 - hi / r), dt = (t1 - t0) (1 / N); m_0 = lo, m_N = hi and for 0 < i < N: t = fmaf(i, dt, t0), m_i =
+ *               minNum(maxNum((r t) (2 - t), m_(i-1)), hi); for i = 1 .. N: dG = G((m_i - q) inv_s) - G((m_(i-1) - q) inv_s), mm = 0.5
+ *               (m_(i-1) + m_i), w = core + sqrt((r - mm) (r + mm)), acc = fmaf(dG, B(x, w), acc).  S = minNum(0.25 acc, 1).
+ *   store       S' = S, or 1 - S under JH_SHADOW_INVERT.  p = color S', one product per channel.  The texel is p by the store rule
+ *               (a_inv = 1 / maxNum(p.a, 1e-6), f16(p.rgb a_inv + 0.0f), f16(p.a + 0.0f)).  Under JH_SHADOW_OVER that texel is the
+ *               SOURCE of jh_composite's rule, Normal + SrcOver, opacity 1, no tint, onto the texel dst holds (never written:
+ *               transparent black), word for word: so OVER equals the call without OVER into a second image followed by jh_composite,
+ *               bit for bit.
+ * So with r = 0 the coverage is the product of two bands, exact up to G; a box empty in a dimension gives transparent black (or
+ * color under INVERT); the result is symmetric under the box's two reflections wherever the positions are.
+ *
+ * jh_shadow_plan: the plan of desc (the rectangle and the flags' meaning are not looked at).  jh_shadow_bounds: rect[4] = {x, y, width,
+ * height} of a dst_w x dst_h destination outside which S is below 2^-12 -- the box grown by 3.625 sigma' on every side, its corners
+ * through the matrix in binary64, floor(min) - 1 and ceil(max) + 1, clipped to the image; all zero when nothing is left or the box is
+ * empty in a dimension.  It is how a caller restricts the call to the shadow; under INVERT it bounds S all the same, not 1 - S.  Both
+ * are host only, no context; JH_ERR_INVALID for a null argument or a descriptor the rule refuses, the outputs then untouched.
+ *
+ * jh_shadow: the rule, written to the rectangle of dst_image_id.  Texels of dst outside the rectangle keep their bits; a dst that was
+ * never written is cleared to transparent black first and then counts as written.  Stream-ordered on the context's stream, never
+ * waits: ONE kernel launch, plus a fill when dst has to be cleared.  No scratch, no tables, no resident key: always capturable.  With
+ * profiling on the call is a query "shadow" with stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band).
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_shadow: ": a null
+ * desc; an unknown destination id; an image that is not RGBA16F; an image extent above 2^23; what the list under `legal` refuses; an
+ * illegal matrix; a rectangle that is not inside the image or that is empty in exactly one dimension; a band. */
+#define JH_SHADOW_OVER 1u
+#define JH_SHADOW_INVERT 2u
+typedef struct jh_shadow_desc {
+    double matrix[6];               /* (a, b, c, d, e, f): shape space -> destination image */
+    uint32_t x, y, width, height;   /* the rectangle of dst that is written; width == height == 0: the whole image */
+    uint32_t flags;                 /* JH_SHADOW_OVER | JH_SHADOW_INVERT */
+    float radius, sigma;            /* shape units */
+    float box[4];                   /* x0, y0, x1, y1 in shape space */
+    float color[4];                 /* premultiplied, linear */
+} jh_shadow_desc;
+typedef struct jh_shad_plan {
+    int64_t m[6];        /* jh_warp_plan's P, Q, R, S, T, W */
+    int64_t centre[2];   /* the box's centre, 2^-32 shape units */
+    float a, b, radius;  /* the half sizes and the clamped radius */
+    float core, straight; /* a - r, b - r */
+    float sigma, inv_s, window; /* sigma', 1 / (sigma' sqrt 2), K sigma' */
+    uint32_t n, k;       /* N and K */
+} jh_shad_plan;
+int jh_shadow_plan(const jh_shadow_desc* desc, jh_shad_plan* plan);
+int jh_shadow_bounds(const jh_shadow_desc* desc, uint32_t dst_w, uint32_t dst_h, uint32_t* rect /* 4 */);
+int jh_shadow(jh_ctx* ctx, uint64_t dst_image_id, const jh_shadow_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

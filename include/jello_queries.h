@@ -15,6 +15,7 @@
 #include "jello_displace.h"
 #include "jello_lighting.h"
 #include "jello_resample.h"
+#include "jello_shadow.h"
 #include "jello_turbulence.h"
 #include "jello_warp.h"
 
@@ -90,6 +91,16 @@ static inline const char* jq_displace_offset(float scale, uint16_t f16_bits, int
     return nullptr;
 }
 
+static inline const char* jq_shadow_plan(const jh_shadow_desc* desc, jh_shad_plan* plan) {
+    if (!desc || !plan) return "null argument";
+    return jshadow_plan(desc, plan);
+}
+
+static inline const char* jq_shadow_bounds(const jh_shadow_desc* desc, uint32_t dst_w, uint32_t dst_h, uint32_t* rect) {
+    if (!desc || !rect) return "null argument";
+    return jshadow_bounds(desc, dst_w, dst_h, rect);
+}
+
 // (the geometry of jh_composite: out[6] = {sx', sy', dx', dy', w, h}, all zero when nothing is left)
 static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy,
                                             uint32_t dst_w, uint32_t dst_h, uint32_t* out) {
@@ -119,7 +130,9 @@ static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint
       (desc, spec_table, spot_table, which))                                                                                                \
     X(turbulence_plan, (const jh_turbulence_desc* desc, jh_turb_plan* plan), (desc, plan))                                                  \
     X(turbulence_tables, (const jh_turbulence_desc* desc, uint8_t* selector, float* gradients), (desc, selector, gradients))               \
-    X(displace_offset, (float scale, uint16_t f16_bits, int64_t* out), (scale, f16_bits, out))
+    X(displace_offset, (float scale, uint16_t f16_bits, int64_t* out), (scale, f16_bits, out))                                              \
+    X(shadow_plan, (const jh_shadow_desc* desc, jh_shad_plan* plan), (desc, plan))                                                        \
+    X(shadow_bounds, (const jh_shadow_desc* desc, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), (desc, dst_w, dst_h, rect))
 #define JQ_HOST_QUERY_LIST(X)                                                                                                               \
     X(composite_clip,                                                                                                                       \
       (uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w, uint32_t dst_h, \

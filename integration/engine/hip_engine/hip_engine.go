@@ -976,6 +976,82 @@ func (e *Engine) Displace(src, dmap, dst renderer.ImageProxy, desc DisplaceDesc)
 	e.check(C.jh_displace(e.ctx, C.uint64_t(src.ID), C.uint64_t(dmap.ID), C.uint64_t(dst.ID), &d), "displace")
 }
 
+// ShadowOver and ShadowInvert are JH_SHADOW_OVER and JH_SHADOW_INVERT: the shadow is laid over what dst holds (Normal + SrcOver, in
+// place); the coverage is 1 - S (inset shadows).
+const (
+	ShadowOver   uint32 = 1
+	ShadowInvert uint32 = 2
+)
+
+// ShadowDesc is jh_shadow_desc (include/jello_hip.h "Shadow"): Matrix takes shape space to dst's texel space, the rectangle of dst
+// that is written (Width == Height == 0: the whole image), the flags, Radius and Sigma in shape units, Box = x0, y0, x1, y1 in shape
+// space and Color, premultiplied and linear.
+type ShadowDesc struct {
+	Matrix              [6]float64
+	X, Y, Width, Height uint32
+	Flags               uint32
+	Radius, Sigma       float32
+	Box                 [4]float32
+	Color               [4]float32
+}
+
+// ShadPlan is jh_shad_plan: the six integers of the matrix, the box's centre in units of 2^-32, the half sizes, the clamped radius, A
+// - R and B - R, the floored sigma, 1 / (sigma sqrt 2), the cap window K sigma, and N and K.
+type ShadPlan struct {
+	M                                                [6]int64
+	Centre                                           [2]int64
+	A, B, Radius, Core, Straight, Sigma, InvS, Window float32
+	N, K                                             uint32
+}
+
+func (desc ShadowDesc) c() C.jh_shadow_desc {
+	d := C.jh_shadow_desc{x: C.uint32_t(desc.X), y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height),
+		flags: C.uint32_t(desc.Flags), radius: C.float(desc.Radius), sigma: C.float(desc.Sigma)}
+	for i, m := range desc.Matrix {
+		d.matrix[i] = C.double(m)
+	}
+	for i := 0; i < 4; i++ {
+		d.box[i], d.color[i] = C.float(desc.Box[i]), C.float(desc.Color[i])
+	}
+	return d
+}
+
+// ShadowPlan is jh_shadow_plan: the plan of desc -- with the bounds the only place binary64 appears in the shadow rule.  Host only.
+func ShadowPlan(desc ShadowDesc) (ShadPlan, error) {
+	d := desc.c()
+	var p C.jh_shad_plan
+	if C.jh_shadow_plan(&d, &p) != 0 {
+		return ShadPlan{}, fmt.Errorf("hip_engine: ShadowPlan: a descriptor the rule refuses")
+	}
+	out := ShadPlan{A: float32(p.a), B: float32(p.b), Radius: float32(p.radius), Core: float32(p.core), Straight: float32(p.straight),
+		Sigma: float32(p.sigma), InvS: float32(p.inv_s), Window: float32(p.window), N: uint32(p.n), K: uint32(p.k)}
+	for i := 0; i < 6; i++ {
+		out.M[i] = int64(p.m[i])
+	}
+	out.Centre[0], out.Centre[1] = int64(p.centre[0]), int64(p.centre[1])
+	return out, nil
+}
+
+// ShadowBounds is jh_shadow_bounds: the rectangle (x, y, width, height) of a dstW x dstH destination outside which the coverage is
+// below 2^-12 -- what the rectangle of a ShadowDesc is restricted to; all zero when nothing is left.  Host only.
+func ShadowBounds(desc ShadowDesc, dstW, dstH uint32) ([4]uint32, error) {
+	d := desc.c()
+	var r [4]C.uint32_t
+	if C.jh_shadow_bounds(&d, C.uint32_t(dstW), C.uint32_t(dstH), &r[0]) != 0 {
+		return [4]uint32{}, fmt.Errorf("hip_engine: ShadowBounds: a descriptor the rule refuses or an image extent above 2^23")
+	}
+	return [4]uint32{uint32(r[0]), uint32(r[1]), uint32(r[2]), uint32(r[3])}, nil
+}
+
+// Shadow is jh_shadow: the Gaussian blur of a rounded rectangle times a colour, GENERATED into the RGBA16F image dst or, with
+// ShadowOver, laid over what it holds, by the rule of DESIGN.md 5.18 (defined on values: every implementation gives the same bits).
+// Stream-ordered behind the frame, waits for nothing, one kernel launch whose cost does not depend on sigma, no scratch and no
+// tables: always capturable.
+func (e *Engine) Shadow(dst renderer.ImageProxy, desc ShadowDesc) {
+	d := desc.c()
+	e.check(C.jh_shadow(e.ctx, C.uint64_t(dst.ID), &d), "shadow")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

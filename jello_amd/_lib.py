@@ -221,6 +221,19 @@ class CDisplaceDesc(ctypes.Structure):
                 ("scale_x", ctypes.c_float), ("scale_y", ctypes.c_float), ("x_channel", ctypes.c_int32), ("y_channel", ctypes.c_int32)]
 
 
+class CShadowDesc(ctypes.Structure):
+    """jh_shadow_desc (include/jello_hip.h)."""
+    _fields_ = [("matrix", ctypes.c_double * 6), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("radius", ctypes.c_float), ("sigma", ctypes.c_float), ("box", ctypes.c_float * 4), ("color", ctypes.c_float * 4)]
+
+
+class CShadowPlan(ctypes.Structure):
+    """jh_shad_plan (include/jello_hip.h)."""
+    _fields_ = [("m", ctypes.c_int64 * 6), ("centre", ctypes.c_int64 * 2), ("a", ctypes.c_float), ("b", ctypes.c_float), ("radius", ctypes.c_float),
+                ("core", ctypes.c_float), ("straight", ctypes.c_float), ("sigma", ctypes.c_float), ("inv_s", ctypes.c_float), ("window", ctypes.c_float),
+                ("n", ctypes.c_uint32), ("k", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -301,6 +314,8 @@ def _declare(L):
         "turbulence_plan": [ctypes.POINTER(CTurbulenceDesc), ctypes.POINTER(CTurbPlan)],
         "turbulence_tables": [ctypes.POINTER(CTurbulenceDesc), vp, vp],
         "displace_offset": [ctypes.c_float, ctypes.c_uint16, ctypes.POINTER(ctypes.c_int64)],
+        "shadow_plan": [ctypes.POINTER(CShadowDesc), ctypes.POINTER(CShadowPlan)],
+        "shadow_bounds": [ctypes.POINTER(CShadowDesc), u32, u32, ctypes.POINTER(u32)],
     }
     for name, argtypes in queries.items():
         getattr(L, "jl_" + name).argtypes = argtypes
@@ -352,6 +367,7 @@ def _declare(L):
     hip.jh_lighting.argtypes = [vp, u64, u64, ctypes.POINTER(CLightingDesc)]
     hip.jh_turbulence.argtypes = [vp, u64, ctypes.POINTER(CTurbulenceDesc)]
     hip.jh_displace.argtypes = [vp, u64, u64, u64, ctypes.POINTER(CDisplaceDesc)]
+    hip.jh_shadow.argtypes = [vp, u64, ctypes.POINTER(CShadowDesc)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

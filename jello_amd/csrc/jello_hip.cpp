@@ -30,6 +30,7 @@
 #include "../../include/jello_lighting.h"
 #include "../../include/jello_turbulence.h"
 #include "../../include/jello_displace.h"
+#include "../../include/jello_shadow.h"
 #include "../../include/jello_queries.h"
 #include "../../include/jello_dash_host.h"
 
@@ -1170,7 +1171,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1859,6 +1860,26 @@ int jh_displace(jh_ctx* ctx, uint64_t src_image_id, uint64_t map_image_id, uint6
         return launch_status(ctx, "jh_displace",
                              jh_displace_launch(ctx->stream, v.from, s, from_map, v.to, d, plan, desc->scale_x, desc->scale_y, desc->x_channel, desc->y_channel,
                                                 desc->filter, desc->edge, (desc->flags & JH_DISPLACE_STRAIGHT) != 0u, ctx->num_cus));
+    });
+}
+
+// shadow (include/jello_hip.h "Shadow"; the descriptor, the plan and the coverage: include/jello_shadow.h; the matrix: include/jello_warp.h; kernels_shadow.hip)
+int jh_shadow(jh_ctx* ctx, uint64_t dst_image_id, const jh_shadow_desc* desc) {
+    static_assert(JH_SHADOW_OVER == JSHADOW_OVER && JH_SHADOW_INVERT == JSHADOW_INVERT, "the C ABI's values are the rule's");
+    Alloc* dst = nullptr;
+    if (int rc = image_call_image(ctx, "jh_shadow", desc, dst_image_id, "a band's rows are one rank's, the call writes its whole rectangle", &dst)) return rc;
+    if (const char* why = jshadow_extent_error(dst->width, dst->height)) return fail(ctx, JH_ERR_INVALID, std::string("jh_shadow: ") + why);
+    if (const char* why = jshadow_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_shadow: ") + why);
+    jh_shad_plan plan;
+    if (const char* why = jshadow_plan(desc, &plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_shadow: illegal matrix: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_shadow", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    return post_render_call(ctx, "shadow", [&] {
+        const bool backdrop = dst->written || dst->stored;  // (taken first: OVER onto a never-written image blends onto transparent black)
+        if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
+        return launch_status(ctx, "jh_shadow",
+                             jh_shadow_launch(ctx->stream, {dst->ptr, dst->width, dst->height}, backdrop, r, &plan, desc->color, desc->flags, ctx->num_cus));
     });
 }
 

@@ -17,7 +17,8 @@ from .imagecalls import (  # noqa: F401
     _matrix6, warp_plan, warp_bounds, _warp_desc, ConvolveEdge, ConvolveMode, CONVOLVE_MAX_ORDER, CONVOLVE_MAX_TAPS, _order2, convolve_weights,
     _convolve_desc, LightKind, LightSource, LIGHTING_TABLE_ENTRIES, LIGHTING_TABLE_SPEC, LIGHTING_TABLE_SPOT, _vec3, _lighting_desc, lighting_plan,
     lighting_tables, TurbulenceKind, TURBULENCE_MAX_OCTAVES, _pair, _turbulence_desc, turbulence_plan, turbulence_tables, DisplaceChannel,
-    DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
+    DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ShadowFlags, SHADOW_MAX_EXTENT, _shadow_desc, shadow_plan, shadow_bounds,
+    box_shadow_geometry, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
     IDENTITY_MATRIX, _color_desc, color_tables, composite_clip,
 )
 from .scene import Compose, Mix
@@ -483,6 +484,32 @@ class Engine:
         self.turbulence(dst_id, **turbulence_keywords)
         self.displace(src_id, dst_id, dst_id, scale, x_channel, y_channel, filter=filter, edge=edge, premultiplied=premultiplied)
 
+    def shadow(self, dst_id, box, radius, sigma, color, matrix=None, rect=None, over=False, invert=False):
+        """jh_shadow: the Gaussian blur of the rounded rectangle `box` = (x0, y0, x1, y1) with corner radius `radius` (clamped to
+        half the smaller side) by `sigma`, times `color` = (r, g, b, a), premultiplied and linear, GENERATED into the RGBA16F image
+        `dst_id` (the rule: DESIGN.md 5.18) -- no source image, no scratch, one launch whose cost does not depend on sigma.  `matrix`
+        = (a, b, c, d, e, f) takes the shape's space to dst's texel space (None: the identity); the blur lives in shape space, so
+        a rotated box has a rotated shadow and a non-uniform scale an anisotropic blur.  `rect` = (x, y, width, height) is the
+        rectangle of dst that is written (None: the whole image; shadow_bounds gives the one outside which there is no shadow).
+        `over`: the shadow is laid over what dst holds, in place (Normal + SrcOver, exactly composite()'s); `invert`: the coverage
+        is 1 - S (inset shadows).  Always capturable.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _shadow_desc(box, radius, sigma, color, matrix, rect, over, invert)
+        self._check(self.hip.jh_shadow(self.ctx, dst_id, ctypes.byref(d)), "shadow", invalid=ValueError)
+
+    def box_shadow(self, target, box, radius, sigma, offset, spread, color, matrix=None):
+        """CSS box-shadow of the border box `box` = (x0, y0, x1, y1) with corner radius `radius` onto `target` = (image id, width,
+        height) -- or the dict a Recording's .target is -- in ONE call: the box shifted by `offset` = (dx, dy) and grown by `spread`
+        (box_shadow_geometry), blurred by `sigma` (CSS's blur radius is 2 sigma), laid over the target (shadow(over=True)) inside
+        shadow_bounds' rectangle only.  Returns that rectangle; nothing is enqueued when it is empty.  It is drop_shadow() for the
+        shape whose blur has a closed form; a layer of any other shape goes through drop_shadow()."""
+        tid, width, height = (target["id"], target["width"], target["height"]) if isinstance(target, dict) else target
+        shape, r = box_shadow_geometry(box, radius, offset, spread)
+        rect = shadow_bounds(shape, r, sigma, (width, height), matrix)
+        if rect[2] == 0 or rect[3] == 0:
+            return rect
+        self.shadow(tid, shape, r, sigma, color, matrix, rect, over=True)
+        return rect
+
     def place_layer(self, layer_id, target_id, matrix, scratch_image_id, layer_size, target_size, filter=WarpFilter.BILINEAR, **composite_keywords):
         """A cached layer onto a target under an affine transform, two calls: warp(layer -> scratch, edge ZERO, dst_rect =
         warp_bounds(...)): the layer in target space, written only where it can be other than transparent black;
@@ -633,7 +660,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None):
+                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -677,7 +704,10 @@ class Engine:
         optional) displaces the frame's target into the RGBA16F image `dst` of width x height by the RGBA16F image `map` of that
         size where warp= would transform it (one more launch, nothing to run eagerly first); the conversion of the same capture
         then reads `dst`.  It is exclusive with resample= and with warp=.  It runs after turbulence=, so one capture can make the
-        map (turbulence=dict(dst=m, ...)) and use it (displace=dict(map=m, ...)); `map` may be `dst`."""
+        map (turbulence=dict(dst=m, ...)) and use it (displace=dict(map=m, ...)); `map` may be `dst`.
+        shadow=dict(box=..., radius=..., sigma=..., color=..., ...) (the other keywords of shadow(), optional; dst=image id: another
+        image than the frame's target) draws a blurred rounded rectangle right after turbulence= and before every other step (one
+        more launch, nothing to run eagerly first) -- with over=True onto the frame's target, which the later steps then read."""
         if sum(step is not None for step in (resample, warp, displace)) > 1:
             raise ValueError("capture: resample=, warp= and displace= are exclusive (each would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
@@ -686,6 +716,8 @@ class Engine:
             t = recording.target
             if turbulence is not None:
                 self.turbulence(turbulence["dst"], **{k: v for k, v in turbulence.items() if k != "dst"})
+            if shadow is not None:
+                self.shadow(shadow.get("dst", t["id"]), **{k: v for k, v in shadow.items() if k != "dst"})
             if morphology is not None:
                 self.morphology(t["id"], **morphology)
             if blur is not None:

@@ -8,7 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CLightingDesc, CLightPlan, CMorphDesc, CResampleDesc, CTurbPlan, CTurbulenceDesc, CWarpDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CLightingDesc, CLightPlan, CMorphDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
 
 
 def _query(name, twin=False):
@@ -380,6 +380,73 @@ def _displace_desc(scale, x_channel, y_channel, matrix, filter, edge, src_rect, 
     d.scale_x, d.scale_y = float(np.float32(sx)), float(np.float32(sy))
     d.x_channel, d.y_channel = int(x_channel), int(y_channel)
     return d
+
+
+class ShadowFlags(enum.IntFlag):
+    """jh_shadow's flags: OVER lays the shadow over what dst holds (Normal + SrcOver, in place), INVERT takes the
+    coverage 1 - S -- the raw material of CSS inset shadows."""
+    NONE = 0
+    OVER = 1
+    INVERT = 2
+
+
+SHADOW_MAX_EXTENT = 1 << 23  # JSHADOW_MAX_EXTENT
+
+
+def _shadow_desc(box, radius, sigma, color, matrix=None, rect=None, over=False, invert=False):
+    """jh_shadow_desc.  What the rule refuses is left for the call to refuse."""
+    d = CShadowDesc()
+    d.matrix[:] = list(_matrix6(AFFINE_IDENTITY if matrix is None else matrix))
+    d.x, d.y, d.width, d.height = _rect(rect)
+    d.flags = int((ShadowFlags.OVER if over else 0) | (ShadowFlags.INVERT if invert else 0))
+    d.radius, d.sigma = float(np.float32(radius)), float(np.float32(sigma))
+    box, color = [float(np.float32(v)) for v in box], [float(np.float32(v)) for v in color]
+    if len(box) != 4 or len(color) != 4:
+        raise ValueError("jh_shadow: the box has four entries (x0, y0, x1, y1) and the color four (r, g, b, a, premultiplied)")
+    d.box[:], d.color[:] = box, color
+    return d
+
+
+def shadow_plan(box, radius, sigma, matrix=None, twin=False):
+    """jh_shadow_plan (twin: jl_shadow_plan, the host twin): the plan of the shadow rule -- dict(m = the six integers of
+    the matrix, centre = int64 (2,), a, b, radius (clamped to the smaller half side), core, straight, sigma (floored at 2^-8), inv_s =
+    1 / (sigma sqrt 2), window = K sigma as float32, n, k).  No GPU needed.  ValueError for a descriptor the rule refuses."""
+    with np.errstate(over="ignore"):
+        d, plan = _shadow_desc(box, radius, sigma, (0.0, 0.0, 0.0, 1.0), matrix), CShadowPlan()
+    if _query("shadow_plan", twin)(ctypes.byref(d), ctypes.byref(plan)) != 0:
+        raise ValueError("jh_shadow: illegal descriptor")
+    out = dict(m=tuple(int(v) for v in plan.m), centre=np.array(plan.centre, np.int64), n=int(plan.n), k=int(plan.k))
+    out.update({name: np.float32(getattr(plan, name)) for name in ("a", "b", "radius", "core", "straight", "sigma", "inv_s", "window")})
+    return out
+
+
+def shadow_bounds(box, radius, sigma, dst_size, matrix=None, twin=False):
+    """jh_shadow_bounds (twin: jl_shadow_bounds): the rectangle (x, y, width, height) of a destination of `dst_size` = (width, height)
+    outside which the shadow's coverage S is below 2^-12; (0, 0, 0, 0) when nothing is left.  It is what `rect` of Engine.shadow is
+    restricted to: a 300 x 200 card in a 4096^2 frame costs a launch over the card's shadow, not over the frame.  No GPU needed.
+    ValueError for a descriptor the rule refuses or a side above 2^23."""
+    with np.errstate(over="ignore"):
+        d = _shadow_desc(box, radius, sigma, (0.0, 0.0, 0.0, 1.0), matrix)
+    rect = (ctypes.c_uint32 * 4)()
+    if not (0 <= int(dst_size[0]) < 1 << 32 and 0 <= int(dst_size[1]) < 1 << 32) or \
+            _query("shadow_bounds", twin)(ctypes.byref(d), int(dst_size[0]), int(dst_size[1]), rect) != 0:
+        raise ValueError("jh_shadow: illegal descriptor or an image extent above 2^23")
+    return tuple(int(v) for v in rect)
+
+
+def box_shadow_geometry(box, radius, offset, spread):
+    """CSS box-shadow's arithmetic on a border box (x0, y0, x1, y1) with corner radius `radius`: the offset shifts the box, the
+    spread grows it on every side (a negative one shrinks it, to nothing at most: the sides meet at the middle) and grows the radius
+    where there is one (a sharp corner stays sharp; never below 0).  Returns (box, radius) of the shape that is blurred."""
+    x0, y0, x1, y1 = (float(v) for v in box)
+    ox, oy = (float(v) for v in offset)
+    s, r = float(spread), float(radius)
+    x0, y0, x1, y1 = x0 + ox - s, y0 + oy - s, x1 + ox + s, y1 + oy + s
+    if x1 < x0:
+        x0 = x1 = 0.5 * (x0 + x1)
+    if y1 < y0:
+        y0 = y1 = 0.5 * (y0 + y1)
+    return (x0, y0, x1, y1), (max(r + s, 0.0) if r > 0.0 else 0.0)
 
 
 class ColorSpace(enum.IntEnum):

@@ -177,6 +177,30 @@ static void displace() {
     CHECK(is(jq_displace_offset(12.5f, 0x3A00u, nullptr), "null argument"));
 }
 
+static void shadow() {
+    Buf<jh_shadow_desc> d(1);
+    memset(d, 0, sizeof(jh_shadow_desc));
+    d[0].matrix[0] = d[0].matrix[3] = 1.0;
+    d[0].box[0] = 10.0f; d[0].box[1] = 8.0f; d[0].box[2] = 50.0f; d[0].box[3] = 30.0f;
+    d[0].radius = 6.0f;
+    d[0].sigma = 2.0f;
+    Buf<jh_shad_plan> plan(1);
+    Buf<uint32_t> rect(4);
+    CHECK(!jq_shadow_plan(d, plan) && !plan.untouched() && plan[0].n == 16u && plan[0].k == JSHADOW_K);
+    CHECK(!jq_shadow_bounds(d, 64u, 48u, rect) && rect[0] == 1u && rect[1] == 0u && rect[2] == 58u && rect[3] == 39u);  // grown by 7.25: 2.75 .. 57.25, 0.75 .. 37.25
+    Buf<jh_shad_plan> plan2(1);
+    Buf<uint32_t> rect2(4);
+    CHECK(is(jq_shadow_plan(nullptr, plan2), "null argument") && is(jq_shadow_plan(d, nullptr), "null argument"));
+    CHECK(is(jq_shadow_bounds(nullptr, 64u, 48u, rect2), "null argument") && is(jq_shadow_bounds(d, 64u, 48u, nullptr), "null argument"));
+    CHECK(is(jq_shadow_bounds(d, JSHADOW_MAX_EXTENT + 1u, 48u, rect2), "an image extent above 2^23"));
+    d[0].sigma = -1.0f;
+    CHECK(is(jq_shadow_plan(d, plan2), "sigma is outside [0, 2^16] or not finite") && is(jq_shadow_bounds(d, 64u, 48u, rect2), "sigma is outside [0, 2^16] or not finite"));
+    d[0].sigma = 2.0f;
+    d[0].matrix[0] = NAN;
+    CHECK(is(jq_shadow_plan(d, plan2), "a matrix entry is not finite") && is(jq_shadow_bounds(d, 64u, 48u, rect2), "a matrix entry is not finite"));
+    CHECK(plan2.untouched() && rect2.untouched());
+}
+
 static void composite() {
     static const char* const kWhy = "the source rectangle is not inside the source image or is empty in one dimension";
     Buf<uint32_t> out(6);
@@ -196,6 +220,7 @@ int main() {
     lighting();
     turbulence();
     displace();
+    shadow();
     composite();
     if (g_fail) return 1;
     printf("ok\n");
