@@ -32,6 +32,7 @@
  *   jh_turbulence                     (no counterpart: feTurbulence noise into an RGBA16F image on the device)
  *   jh_displace                       (no counterpart: feDisplacementMap on RGBA16F images on the device)
  *   jh_shadow                         (no counterpart: a blurred rounded rectangle generated into an RGBA16F image)
+ *   jh_perspective                    (no counterpart: a projective transform of RGBA16F images on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -699,7 +700,7 @@ int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, con
  * So under STRAIGHT the identity, an integer translation under ZERO and the eight flips and quarter turns are copies or permutations
  * of every finite value for every filter and edge (a -0 comes out as +0), and BILINEAR keeps a constant image constant.
  * What the rule does not do: no minification prefilter -- below about 1:2 the result aliases, jh_resample comes first for that, and
- * the limit of 64 is only there to bound the integers; no perspective; no call in place.
+ * the limit of 64 is only there to bound the integers; no perspective (that is jh_perspective, below); no call in place.
  *
  * jh_warp_plan: P, Q, R, S, T, W of a matrix into plan.  Host only, no context.  JH_ERR_INVALID for an illegal matrix.
  * jh_warp_bounds: a rectangle {x, y, width, height} of the dst_w x dst_h image into rect such that under EDGE_ZERO every destination
@@ -1128,6 +1129,68 @@ typedef struct jh_shad_plan {
 int jh_shadow_plan(const jh_shadow_desc* desc, jh_shad_plan* plan);
 int jh_shadow_bounds(const jh_shadow_desc* desc, uint32_t dst_w, uint32_t dst_h, uint32_t* rect /* 4 */);
 int jh_shadow(jh_ctx* ctx, uint64_t dst_image_id, const jh_shadow_desc* desc);
+
+/* ---- Perspective: a projective transform of a rectangle of one RGBA16F image into a rectangle of another ----
+ * A CSS perspective() / rotateX / rotateY / matrix3d card flip, a keystone correction, a layer mapped onto an arbitrary quad -- what
+ * Skia, Core Animation and every browser compositor do with one 3 x 3 matrix -- without the image leaving the device.  The result is
+ * defined on values, and every implementation produces these bits (include/jello_perspective.h states the plan and the position,
+ * tests/perspective_ref.py restates all of it).
+ *   arguments   matrix[9], binary64, column-major so that it extends jh_warp's order: (a, b, p, c, d, q, e, f, s),
+ *               x' w = a x + c y + e,  y' w = b x + d y + f,  w = p x + q y + s.  It maps continuous coordinates of the SOURCE
+ *               RECTANGLE (origin its top-left corner, texel (i, j) centred at (i + 0.5, j + 0.5)) to continuous coordinates of the
+ *               DESTINATION IMAGE.  With p = q = 0, s = 1 it is jh_warp's matrix.  filter, edge, flags (bit 0:
+ *               JH_PERSPECTIVE_STRAIGHT) and the rectangles: jh_warp_desc's, with the same meaning.
+ *   plan        host only, binary64, nothing contracted, each product, difference and quotient rounded once.  The adjugate is nine
+ *               two-product differences in this order:
+ *                 ( d s - f q,  e q - c s,  c f - e d )
+ *                 ( f p - b s,  a s - e p,  e b - a f )
+ *                 ( b q - d p,  c p - a q,  a d - c b )
+ *               det = ((a adj00) + (c adj10)) + (e adj20).  G = adj scaled by 2^-k, where 2^(k-1) < max |adj_ij| <= 2^k: an exact
+ *               ldexp, not a division, so a matrix whose inverse is dyadic stays exact.  G is negated when det < 0: every
+ *               |G_ij| <= 1, and den > 0 <=> w > 0 (in front of the viewer).
+ *   legal       nine finite entries; nine finite adjugate entries; det finite and not 0; both images at most 32768 on a side.
+ *   position    device, binary64, per destination texel (X, Y) of the image: x' = X + 0.5, y' = Y + 0.5 (exact);
+ *               n_u = ((G0 x') + (G1 y')) + G2, likewise n_v with G3..5 and den with G6..8; q = 1.0 / den (IEEE); u = n_u q,
+ *               v = n_v q.  The texel is VOID when !(den > 0) or when u or v is a NaN: it stores four +0.0 whatever the edge mode.
+ *               Otherwise u is clamped to [-2^22, 2^22] and U = (int64) rint(u 2^32), half to even; V likewise: the source
+ *               position in units of 2^-32 texel.
+ *   taps, edge, sum, store, values: jh_warp's, word for word, at (U, V).
+ * So under an affine matrix whose inverse is dyadic (the identity, integer and half-texel translations, the flips and quarter turns,
+ * a scale by a power of two) the result is jh_warp's bit for bit, and a call written in four quadrant rectangles equals the
+ * whole-image call.
+ * What the rule does not do: no minification prefilter -- toward the horizon the result aliases, and jh_resample first is the answer
+ * today; no call in place; under REPEAT / MIRROR a clamped position reads whatever the index rule gives there.
+ *
+ * jh_perspective_plan: the nine doubles of G into plan.  Host only, no context.  JH_ERR_INVALID for an illegal matrix.
+ * jh_perspective_bounds: a rectangle {x, y, width, height} of the dst_w x dst_h image into rect such that under EDGE_ZERO every
+ * destination texel outside it is transparent black: the forward images (binary64, uncontracted: xw = ((a x) + (c y)) + e,
+ * yw = ((b x) + (d y)) + f, w = ((p x) + (q y)) + s, then xw / w and yw / w) of the four corners of the src_w x src_h source
+ * rectangle grown by 0.5 NEAREST, 1 BILINEAR, 2 BICUBIC.  If a corner has w <= 0 the image of the rectangle is unbounded and the
+ * answer is the whole destination; otherwise floor(min) - 1 and ceil(max) + 1, clipped to the destination; an empty result is
+ * 0, 0, 0, 0.  Host only, no context.  JH_ERR_INVALID for an illegal matrix, an unknown filter or a side above 32768.
+ *
+ * jh_perspective: the rule from the rectangle (src_x, ...) of src_image_id into the rectangle (dst_x, ...) of dst_image_id, another
+ * image; the images carry their own sizes.  Only the destination rectangle is written; a dst that was never written is cleared to
+ * transparent black first and then counts as written; a source that was never written reads as transparent black.  Stream-ordered
+ * on the context's stream, never waits: ONE kernel launch, plus a fill when dst has to be cleared.  No scratch and no tables: the
+ * call is always capturable.  With profiling on the call is a query "perspective" with stage = -1 in jh_profile_collect_tree.  Not
+ * in band mode (jh_set_band): the rows a tap reads belong to another rank's context.  JH_ERR_INVALID, with nothing enqueued, no
+ * memory touched and nothing flushed, each with a message that starts "jh_perspective: ": a null desc; an unknown source or
+ * destination id; an image that is not RGBA16F; an unknown filter, edge or flag bit; an illegal matrix (the message names the
+ * condition that failed); an image side above 32768; a rectangle that is not inside its image or that is empty in exactly one
+ * dimension; src_image_id == dst_image_id; a band set with jh_set_band. */
+#define JH_PERSPECTIVE_STRAIGHT 1u
+typedef struct jh_perspective_desc {
+    double matrix[9];                                 /* (a, b, p, c, d, q, e, f, s): source rectangle -> destination image */
+    int filter;                                       /* jh_warp_filter */
+    int edge;                                         /* jh_warp_edge */
+    uint32_t flags;                                   /* bit 0: JH_PERSPECTIVE_STRAIGHT */
+    uint32_t src_x, src_y, src_width, src_height;     /* source rectangle; width == height == 0: the whole image */
+    uint32_t dst_x, dst_y, dst_width, dst_height;     /* destination rectangle, likewise */
+} jh_perspective_desc;
+int jh_perspective_plan(const double matrix[9], double plan[9]);
+int jh_perspective_bounds(const double matrix[9], uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t rect[4]);
+int jh_perspective(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_perspective_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -4,7 +4,8 @@
 // parameters and returns null for success or the reason of the refusal; on a refusal nothing is written.  Compiled by the library
 // (jello_amd/csrc/jello_hip.cpp expands JQ_QUERY_LIST to the jh_<name>, which answer JH_ERR_INVALID without the reason), by the C++
 // host twin (jello_amd/host/capi.cpp expands both lists to the jl_<name>, which answer -1 and keep "<name>: <reason>" for
-// jl_last_error) and by tools/queries_check.cpp; tests/test_queries.py holds the two libraries against each other.
+// jl_last_error) and by tools/queries_check.cpp; tests/test_queries.py holds the two libraries against each other (the perspective
+// queries: tests/test_perspective_spec.py).
 #pragma once
 #include <stdint.h>
 
@@ -14,6 +15,7 @@
 #include "jello_convolve.h"
 #include "jello_displace.h"
 #include "jello_lighting.h"
+#include "jello_perspective.h"
 #include "jello_resample.h"
 #include "jello_shadow.h"
 #include "jello_turbulence.h"
@@ -101,6 +103,16 @@ static inline const char* jq_shadow_bounds(const jh_shadow_desc* desc, uint32_t 
     return jshadow_bounds(desc, dst_w, dst_h, rect);
 }
 
+static inline const char* jq_perspective_plan(const double* matrix, double* plan) {
+    if (!matrix || !plan) return "null argument";
+    return jpersp_plan(matrix, plan);
+}
+
+static inline const char* jq_perspective_bounds(const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect) {
+    if (!matrix || !rect) return "null argument";
+    return jpersp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect);
+}
+
 // (the geometry of jh_composite: out[6] = {sx', sy', dx', dy', w, h}, all zero when nothing is left)
 static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy,
                                             uint32_t dst_w, uint32_t dst_h, uint32_t* out) {
@@ -132,7 +144,10 @@ static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint
     X(turbulence_tables, (const jh_turbulence_desc* desc, uint8_t* selector, float* gradients), (desc, selector, gradients))               \
     X(displace_offset, (float scale, uint16_t f16_bits, int64_t* out), (scale, f16_bits, out))                                              \
     X(shadow_plan, (const jh_shadow_desc* desc, jh_shad_plan* plan), (desc, plan))                                                        \
-    X(shadow_bounds, (const jh_shadow_desc* desc, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), (desc, dst_w, dst_h, rect))
+    X(shadow_bounds, (const jh_shadow_desc* desc, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), (desc, dst_w, dst_h, rect))        \
+    X(perspective_plan, (const double* matrix, double* plan), (matrix, plan))                                                               \
+    X(perspective_bounds, (const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), \
+      (matrix, src_w, src_h, filter, dst_w, dst_h, rect))
 #define JQ_HOST_QUERY_LIST(X)                                                                                                               \
     X(composite_clip,                                                                                                                       \
       (uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w, uint32_t dst_h, \

@@ -1052,6 +1052,68 @@ func (e *Engine) Shadow(dst renderer.ImageProxy, desc ShadowDesc) {
 	e.check(C.jh_shadow(e.ctx, C.uint64_t(dst.ID), &d), "shadow")
 }
 
+// PerspectiveStraight is JH_PERSPECTIVE_STRAIGHT: the source's four channels are filtered as stored, not colour times alpha.
+const PerspectiveStraight uint32 = 1
+
+// PerspectiveDesc is jh_perspective_desc (include/jello_hip.h "Perspective"): WarpDesc's fields with WarpDesc's meaning, the matrix
+// with nine entries, column-major: (a, b, p, c, d, q, e, f, s), x' w = a x + c y + e, y' w = b x + d y + f, w = p x + q y + s, from
+// the source rectangle to the destination image.
+type PerspectiveDesc struct {
+	Matrix                          [9]float64
+	Filter                          WarpFilter
+	Edge                            WarpEdge
+	Flags                           uint32
+	SrcX, SrcY, SrcWidth, SrcHeight uint32
+	DstX, DstY, DstWidth, DstHeight uint32
+}
+
+// PerspectivePlan is jh_perspective_plan: the nine doubles G of the perspective rule (DESIGN.md 5.19) -- the adjugate of the matrix
+// scaled by a power of two so that every |G| <= 1, negated when the determinant is negative.  Host only.
+func PerspectivePlan(matrix [9]float64) ([9]float64, error) {
+	var m, g [9]C.double
+	for i, v := range matrix {
+		m[i] = C.double(v)
+	}
+	if C.jh_perspective_plan(&m[0], &g[0]) != 0 {
+		return [9]float64{}, fmt.Errorf("hip_engine: PerspectivePlan: an illegal matrix")
+	}
+	var out [9]float64
+	for i, v := range g {
+		out[i] = float64(v)
+	}
+	return out, nil
+}
+
+// PerspectiveBounds is jh_perspective_bounds: the rectangle (x, y, width, height) of a dstW x dstH destination outside which
+// Perspective of a srcW x srcH source rectangle under WarpEdgeZero is transparent black -- the whole destination when the rectangle
+// reaches w <= 0; all zero when nothing is left.  Host only.
+func PerspectiveBounds(matrix [9]float64, srcW, srcH uint32, filter WarpFilter, dstW, dstH uint32) ([4]uint32, error) {
+	var m [9]C.double
+	for i, v := range matrix {
+		m[i] = C.double(v)
+	}
+	var r [4]C.uint32_t
+	if C.jh_perspective_bounds(&m[0], C.uint32_t(srcW), C.uint32_t(srcH), C.int(filter), C.uint32_t(dstW), C.uint32_t(dstH), &r[0]) != 0 {
+		return [4]uint32{}, fmt.Errorf("hip_engine: PerspectiveBounds: an illegal matrix, an unknown filter or a side above 32768")
+	}
+	return [4]uint32{uint32(r[0]), uint32(r[1]), uint32(r[2]), uint32(r[3])}, nil
+}
+
+// Perspective is jh_perspective: a rectangle of the RGBA16F image src under a projective map into a rectangle of the RGBA16F image dst
+// (another image) by the rule of DESIGN.md 5.19 (defined on values: every implementation gives the same bits).  A CSS perspective()
+// / rotateX / rotateY / matrix3d card flip, a keystone correction, a layer on an arbitrary quad.  A destination texel whose source
+// lies behind the viewer is transparent black.  No minification prefilter: toward the horizon the result aliases.  Stream-ordered
+// behind the frame, waits for nothing, one kernel launch, no scratch and no tables: always capturable.
+func (e *Engine) Perspective(src, dst renderer.ImageProxy, desc PerspectiveDesc) {
+	d := C.jh_perspective_desc{filter: C.int(desc.Filter), edge: C.int(desc.Edge), flags: C.uint32_t(desc.Flags),
+		src_x: C.uint32_t(desc.SrcX), src_y: C.uint32_t(desc.SrcY), src_width: C.uint32_t(desc.SrcWidth), src_height: C.uint32_t(desc.SrcHeight),
+		dst_x: C.uint32_t(desc.DstX), dst_y: C.uint32_t(desc.DstY), dst_width: C.uint32_t(desc.DstWidth), dst_height: C.uint32_t(desc.DstHeight)}
+	for i, m := range desc.Matrix {
+		d.matrix[i] = C.double(m)
+	}
+	e.check(C.jh_perspective(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "perspective")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -234,6 +234,13 @@ class CShadowPlan(ctypes.Structure):
                 ("n", ctypes.c_uint32), ("k", ctypes.c_uint32)]
 
 
+class CPerspectiveDesc(ctypes.Structure):
+    """jh_perspective_desc (include/jello_hip.h)."""
+    _fields_ = [("matrix", ctypes.c_double * 9), ("filter", ctypes.c_int32), ("edge", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("src_x", ctypes.c_uint32), ("src_y", ctypes.c_uint32), ("src_width", ctypes.c_uint32), ("src_height", ctypes.c_uint32),
+                ("dst_x", ctypes.c_uint32), ("dst_y", ctypes.c_uint32), ("dst_width", ctypes.c_uint32), ("dst_height", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -316,6 +323,8 @@ def _declare(L):
         "displace_offset": [ctypes.c_float, ctypes.c_uint16, ctypes.POINTER(ctypes.c_int64)],
         "shadow_plan": [ctypes.POINTER(CShadowDesc), ctypes.POINTER(CShadowPlan)],
         "shadow_bounds": [ctypes.POINTER(CShadowDesc), u32, u32, ctypes.POINTER(u32)],
+        "perspective_plan": [dp, dp],
+        "perspective_bounds": [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)],
     }
     for name, argtypes in queries.items():
         getattr(L, "jl_" + name).argtypes = argtypes
@@ -368,6 +377,7 @@ def _declare(L):
     hip.jh_turbulence.argtypes = [vp, u64, ctypes.POINTER(CTurbulenceDesc)]
     hip.jh_displace.argtypes = [vp, u64, u64, u64, ctypes.POINTER(CDisplaceDesc)]
     hip.jh_shadow.argtypes = [vp, u64, ctypes.POINTER(CShadowDesc)]
+    hip.jh_perspective.argtypes = [vp, u64, u64, ctypes.POINTER(CPerspectiveDesc)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

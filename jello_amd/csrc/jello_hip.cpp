@@ -31,6 +31,7 @@
 #include "../../include/jello_turbulence.h"
 #include "../../include/jello_displace.h"
 #include "../../include/jello_shadow.h"
+#include "../../include/jello_perspective.h"
 #include "../../include/jello_queries.h"
 #include "../../include/jello_dash_host.h"
 
@@ -1171,7 +1172,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow, perspective ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1880,6 +1881,31 @@ int jh_shadow(jh_ctx* ctx, uint64_t dst_image_id, const jh_shadow_desc* desc) {
         if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
         return launch_status(ctx, "jh_shadow",
                              jh_shadow_launch(ctx->stream, {dst->ptr, dst->width, dst->height}, backdrop, r, &plan, desc->color, desc->flags, ctx->num_cus));
+    });
+}
+
+// perspective (include/jello_hip.h "Perspective"; the plan, the position and the bounds: include/jello_perspective.h; kernels_perspective.hip)
+int jh_perspective(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_perspective_desc* desc) {
+    static_assert(JH_PERSPECTIVE_STRAIGHT == JPERSP_STRAIGHT && JH_PERSPECTIVE_STRAIGHT == JH_WARP_STRAIGHT, "the C ABI's values are the rule's");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = image_call_images(ctx, "jh_perspective", desc, src_image_id, dst_image_id, "a warp in place reads what it writes", "the rows a tap reads belong to another rank", &src, &dst)) return rc;
+    if (const char* why = jpersp_desc_error(desc->filter, desc->edge, desc->flags, src->width, src->height, dst->width, dst->height))
+        return fail(ctx, JH_ERR_INVALID, std::string("jh_perspective: ") + why);
+    jimage_rect s, d;
+    if (int rc = image_call_rect(ctx, "jh_perspective", {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, *src, "source ", &s)) return rc;
+    if (int rc = image_call_rect(ctx, "jh_perspective", {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, *dst, "destination ", &d)) return rc;
+    double plan[9];
+    if (const char* why = jpersp_plan(desc->matrix, plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_perspective: illegal matrix: ") + why);
+    if (jimage_rect_empty(d)) return JH_OK;  // (an image without texels)
+    return post_render_call(ctx, "perspective", [&] {
+        ImageViews v;
+        if (int rc = image_call_views(ctx, src, dst, d, &v)) return rc;
+        if (jimage_rect_empty(s)) {  // a source without texels reads as transparent black: nothing is loaded, and the launcher gets a texel it can name
+            v.from = {nullptr, std::max(src->width, 1u), std::max(src->height, 1u)};
+            s = {s.x, s.y, std::max(s.w, 1u), std::max(s.h, 1u)};
+        }
+        return launch_status(ctx, "jh_perspective",
+                             jh_perspective_launch(ctx->stream, v.from, s, v.to, d, plan, desc->filter, desc->edge, (desc->flags & JH_PERSPECTIVE_STRAIGHT) != 0u, ctx->num_cus));
     });
 }
 

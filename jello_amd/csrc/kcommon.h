@@ -361,7 +361,7 @@ struct JhResampleTables {
     uint32_t region_x;          // float4 slots of LDS a wave of the row pass needs: jh_resample_skew(longest span - 1) + 1
 };
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _turbulence, _displace, _shadow, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _turbulence, _displace, _shadow, _perspective, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses (an image launcher, which takes the views and resolved
 // rectangles of include/jello_image.h: a rectangle that is not inside its image), another negative value (-2) for a failed launch.
@@ -401,6 +401,8 @@ int jh_displace_launch(hipStream_t stream, jimage_src src, jimage_rect src_rect,
 struct jh_shad_plan;  // include/jello_hip.h
 int jh_shadow_launch(hipStream_t stream, jimage_dst dst, int dst_has_content, jimage_rect rect, const jh_shad_plan* plan, const float* color,
                      uint32_t flags, int num_cus);
+int jh_perspective_launch(hipStream_t stream, jimage_src src, jimage_rect src_rect, jimage_dst dst, jimage_rect dst_rect, const double* plan, int filter,
+                          int edge, int straight, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

@@ -18,7 +18,7 @@ from .imagecalls import (  # noqa: F401
     _convolve_desc, LightKind, LightSource, LIGHTING_TABLE_ENTRIES, LIGHTING_TABLE_SPEC, LIGHTING_TABLE_SPOT, _vec3, _lighting_desc, lighting_plan,
     lighting_tables, TurbulenceKind, TURBULENCE_MAX_OCTAVES, _pair, _turbulence_desc, turbulence_plan, turbulence_tables, DisplaceChannel,
     DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ShadowFlags, SHADOW_MAX_EXTENT, _shadow_desc, shadow_plan, shadow_bounds,
-    box_shadow_geometry, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
+    box_shadow_geometry, PERSPECTIVE_STRAIGHT, PROJECTIVE_IDENTITY, _matrix9, perspective_plan, perspective_bounds, _perspective_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
     IDENTITY_MATRIX, _color_desc, color_tables, composite_clip,
 )
 from .scene import Compose, Mix
@@ -526,6 +526,32 @@ class Engine:
         self.composite(scratch_image_id, target_id, src_rect=rect, offset=(rect[0], rect[1]), **composite_keywords)
         return rect
 
+    def perspective(self, src_id, dst_id, matrix, filter=WarpFilter.BILINEAR, edge=WarpEdge.ZERO, src_rect=None, dst_rect=None, premultiplied=True):
+        """jh_perspective: warp() under a projective map (the rule: DESIGN.md 5.19).  `matrix` = (a, b, p, c, d, q, e, f, s), x' w =
+        a x + c y + e, y' w = b x + d y + f, w = p x + q y + s, takes continuous coordinates of the source rectangle `src_rect` of the
+        RGBA16F image `src_id` to continuous coordinates of the destination IMAGE `dst_id` (another RGBA16F image); `dst_rect` is
+        only what gets written.  jello_amd.perspective has the constructors: affine, from_quad, from_matrix3d, rotate_x, rotate_y,
+        compose.  A destination texel whose source lies behind the viewer (w <= 0) is transparent black whatever `edge` says.  The
+        other arguments are warp()'s.  There is no minification prefilter: toward the horizon the result aliases.  One launch, no
+        scratch: always capturable.  Stream-ordered, returns nothing; ValueError for a call the rule refuses."""
+        d = _perspective_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied)
+        self._check(self.hip.jh_perspective(self.ctx, src_id, dst_id, ctypes.byref(d)), "perspective", invalid=ValueError)
+
+    def project_layer(self, layer_id, target_id, matrix, scratch_image_id, layer_size, target_size, filter=WarpFilter.BILINEAR, **composite_keywords):
+        """place_layer() under a projective transform, two calls: perspective(layer -> scratch, edge ZERO, dst_rect =
+        perspective_bounds(...)): the layer in target space, written only where it can be other than transparent black (the whole
+        target when the layer reaches w <= 0); composite(scratch -> target, src_rect = that rectangle, offset = its corner,
+        **composite_keywords).  `matrix` has nine entries; the other arguments and the result are place_layer()'s."""
+        for k in ("src_rect", "offset"):
+            if k in composite_keywords:
+                raise ValueError("project_layer: %s is the placed rectangle's" % k)
+        rect = perspective_bounds(matrix, layer_size, filter, target_size)
+        if rect[2] == 0 or rect[3] == 0:
+            return rect
+        self.perspective(layer_id, scratch_image_id, matrix, filter=filter, edge=WarpEdge.ZERO, dst_rect=rect)
+        self.composite(scratch_image_id, target_id, src_rect=rect, offset=(rect[0], rect[1]), **composite_keywords)
+        return rect
+
     def outline(self, layer_id, target_id, radius, color, scratch_image_id):
         """A layer with an outline (a halo) of `radius` texels onto a target, three calls: morphology(layer -> scratch, DILATE, edge
         ZERO); composite(scratch -> target, tint=color): the grown alpha in the outline's colour; composite(layer -> target).
@@ -660,7 +686,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None):
+                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None, perspective=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -707,9 +733,13 @@ class Engine:
         map (turbulence=dict(dst=m, ...)) and use it (displace=dict(map=m, ...)); `map` may be `dst`.
         shadow=dict(box=..., radius=..., sigma=..., color=..., ...) (the other keywords of shadow(), optional; dst=image id: another
         image than the frame's target) draws a blurred rounded rectangle right after turbulence= and before every other step (one
-        more launch, nothing to run eagerly first) -- with over=True onto the frame's target, which the later steps then read."""
-        if sum(step is not None for step in (resample, warp, displace)) > 1:
-            raise ValueError("capture: resample=, warp= and displace= are exclusive (each would feed the conversion)")
+        more launch, nothing to run eagerly first) -- with over=True onto the frame's target, which the later steps then read.
+        perspective=dict(dst=image id, width=..., height=..., matrix=..., ...) (the other keywords of perspective(), optional; the
+        matrix has nine entries) transforms the frame's target into the RGBA16F image `dst` of width x height where warp= would (one
+        more launch, nothing to run eagerly first); the conversion of the same capture then reads `dst`.  It is exclusive with
+        resample=, warp= and displace=."""
+        if sum(step is not None for step in (resample, warp, displace, perspective)) > 1:
+            raise ValueError("capture: resample=, warp=, displace= and perspective= are exclusive (each would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
@@ -742,6 +772,10 @@ class Engine:
                 self.displace(t["id"], displace["map"], displace["dst"], displace["scale"],
                               **{k: v for k, v in displace.items() if k not in ("map", "dst", "width", "height", "scale")})
                 t = {"id": displace["dst"], "width": displace["width"], "height": displace["height"]}
+            if perspective is not None:
+                self.perspective(t["id"], perspective["dst"], perspective["matrix"],
+                                 **{k: v for k, v in perspective.items() if k not in ("dst", "width", "height", "matrix")})
+                t = {"id": perspective["dst"], "width": perspective["width"], "height": perspective["height"]}
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._blit(t["id"], ptr, pitch, t["width"], t["height"], fmt)

@@ -8,7 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CLightingDesc, CLightPlan, CMorphDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CLightingDesc, CLightPlan, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
 
 
 def _query(name, twin=False):
@@ -447,6 +447,47 @@ def box_shadow_geometry(box, radius, offset, spread):
     if y1 < y0:
         y0 = y1 = 0.5 * (y0 + y1)
     return (x0, y0, x1, y1), (max(r + s, 0.0) if r > 0.0 else 0.0)
+
+
+PERSPECTIVE_STRAIGHT = 1  # JH_PERSPECTIVE_STRAIGHT
+PROJECTIVE_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)  # (a, b, p, c, d, q, e, f, s)
+
+
+def _matrix9(matrix):
+    m = [float(v) for v in matrix]
+    if len(m) != 9:
+        raise ValueError("jh_perspective: the matrix has 9 entries (a, b, p, c, d, q, e, f, s)")
+    return (ctypes.c_double * 9)(*m)
+
+
+def perspective_plan(matrix, twin=False):
+    """jh_perspective_plan (twin: jl_perspective_plan, the host twin): the nine doubles G of the perspective rule for
+    `matrix` = (a, b, p, c, d, q, e, f, s), source rectangle -> destination image: the adjugate scaled by a power of two so that
+    every |G| <= 1, negated when the determinant is negative.  No GPU needed.  ValueError for an illegal matrix."""
+    plan = (ctypes.c_double * 9)()
+    if _query("perspective_plan", twin)(_matrix9(matrix), plan) != 0:
+        raise ValueError("jh_perspective: illegal matrix (an entry or an adjugate entry not finite, a determinant that is 0 or not finite)")
+    return tuple(float(v) for v in plan)
+
+
+def perspective_bounds(matrix, src_size, filter, dst_size, twin=False):
+    """jh_perspective_bounds (twin: jl_perspective_bounds): the rectangle (x, y, width, height) of a destination of `dst_size` =
+    (width, height) outside which jh_perspective of a source rectangle of `src_size` under WarpEdge.ZERO is transparent black -- the
+    whole destination when the rectangle reaches w <= 0; (0, 0, 0, 0) when nothing is left.  No GPU needed.  ValueError for an illegal
+    matrix, an unknown filter or a side above 32768."""
+    rect = (ctypes.c_uint32 * 4)()
+    if _query("perspective_bounds", twin)(_matrix9(matrix), int(src_size[0]), int(src_size[1]), int(filter), int(dst_size[0]), int(dst_size[1]), rect) != 0:
+        raise ValueError("jh_perspective: illegal matrix, unknown filter or a side above 32768")
+    return tuple(int(v) for v in rect)
+
+
+def _perspective_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
+    d = CPerspectiveDesc()
+    d.matrix[:] = list(_matrix9(matrix))
+    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else PERSPECTIVE_STRAIGHT
+    d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
+    d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
+    return d
 
 
 class ColorSpace(enum.IntEnum):

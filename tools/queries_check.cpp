@@ -201,6 +201,27 @@ static void shadow() {
     CHECK(plan2.untouched() && rect2.untouched());
 }
 
+static void perspective() {
+    Buf<double> m(9);
+    const double keystone[9] = {1.0, 0.0, 0.25, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};  // w = 1 + x / 4
+    memcpy(m, keystone, sizeof keystone);
+    Buf<double> plan(9);
+    Buf<uint32_t> rect(4);
+    CHECK(!jq_perspective_plan(m, plan) && !plan.untouched() && plan[0] == 1.0 && plan[6] == -0.25 && plan[8] == 1.0);
+    CHECK(!jq_perspective_bounds(m, 4u, 2u, JWARP_NEAREST, 16u, 8u, rect) && rect[0] == 0u && rect[1] == 0u && rect[2] == 4u && rect[3] == 4u);  // x: -4/7 .. 36/17, y: -4/7 .. 20/7
+    Buf<double> plan2(9);
+    Buf<uint32_t> rect2(4);
+    CHECK(is(jq_perspective_plan(nullptr, plan2), "null argument") && is(jq_perspective_plan(m, nullptr), "null argument"));
+    CHECK(is(jq_perspective_bounds(nullptr, 4u, 2u, 0, 16u, 8u, rect2), "null argument") && is(jq_perspective_bounds(m, 4u, 2u, 0, 16u, 8u, nullptr), "null argument"));
+    CHECK(is(jq_perspective_bounds(m, 4u, 2u, 3, 16u, 8u, rect2), "unknown filter") && is(jq_perspective_bounds(m, 4u, 2u, 0, 32769u, 8u, rect2), "an image side above 32768"));
+    m[8] = NAN;
+    CHECK(is(jq_perspective_plan(m, plan2), "a matrix entry is not finite") && is(jq_perspective_bounds(m, 4u, 2u, 0, 16u, 8u, rect2), "a matrix entry is not finite"));
+    m[8] = 0.0;
+    m[2] = 0.0;
+    CHECK(is(jq_perspective_plan(m, plan2), "the determinant is 0"));
+    CHECK(plan2.untouched() && rect2.untouched());
+}
+
 static void composite() {
     static const char* const kWhy = "the source rectangle is not inside the source image or is empty in one dimension";
     Buf<uint32_t> out(6);
@@ -221,6 +242,7 @@ int main() {
     turbulence();
     displace();
     shadow();
+    perspective();
     composite();
     if (g_fail) return 1;
     printf("ok\n");
