@@ -1,6 +1,6 @@
 // jello_warp.h -- the host half of the warp rule (DESIGN.md 5.12 "Warp rule"): which matrix is legal, the six integers of the plan,
 // the per-axis taps and the four index rules, and the bounds rectangle.  Compiled by the library (jello_amd/csrc/jello_hip.cpp:
-// jh_warp), by the kernels (jello_amd/csrc/kernels_warp.hip: the index rules, the fraction and the
+// jh_warp), by the kernels (jello_amd/csrc/warp_taps.h and kernels_warp.hip: the index rules, the fraction and the
 // cubic weights are the one text the device and the stand-alone check both compile), by the queries both libraries compile
 // (include/jello_queries.h: jq_warp_plan, jq_warp_bounds) and by tools/warp_plan_check.cpp; tests/warp_ref.py restates it.
 //
@@ -72,6 +72,16 @@ static inline const char* jwarp_plan(const double m[6], int64_t plan[6]) {
     if (const char* why = jwarp_inverse(m, inv)) return why;
     for (int i = 0; i < 6; i++) plan[i] = (int64_t)rint(inv[i] * ((i % 3) == 2 ? 4294967296.0 : 2147483648.0));  // (the scalings are exact)
     return nullptr;
+}
+// Whether the six integers lie where a legal matrix's do: |P|, |Q|, |S|, |T| <= 64 x 2^31, |R|, |W| <= 2^22 x 2^32 (the limits above,
+// scaled as jwarp_plan scales; both products are exact).  What a launcher asks of a plan it did not make: the positions then fit
+// int64 and the taps' indices 32 bits.
+static inline bool jwarp_plan_in_range(const int64_t plan[6]) {
+    for (int i = 0; i < 6; i++) {
+        const int64_t lim = (int64_t)((i % 3) == 2 ? JWARP_MAX_OFFSET * 4294967296.0 : JWARP_MAX_SCALE * 2147483648.0);
+        if (plan[i] > lim || plan[i] < -lim) return false;
+    }
+    return true;
 }
 
 // The source position of destination texel (X, Y), one axis: the row (P, Q, R) or (S, T, W) of the plan.

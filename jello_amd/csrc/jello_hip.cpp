@@ -1707,7 +1707,27 @@ int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, con
         });
 }
 
-// warp (include/jello_hip.h "Warp"; the plan, the bounds and the descriptor: include/jello_warp.h; kernels_warp.hip)
+extern "C++" {  // (a template cannot have C linkage)
+// What jh_warp, jh_displace and jh_perspective do alike between their own checks.  warp_family_rects: the source and the destination
+// rectangle the descriptor names, resolved into *s and *d, or the refusal.  warp_family_views: image_call_views for the destination
+// rectangle d, and a source rectangle without texels reads as transparent black: nothing is loaded, and the launcher gets a texel it
+// can name.
+template <class Desc>
+static int warp_family_rects(jh_ctx* ctx, const char* who, const Desc* desc, const Alloc& src, const Alloc& dst, jimage_rect* s, jimage_rect* d) {
+    if (int rc = image_call_rect(ctx, who, {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, src, "source ", s)) return rc;
+    return image_call_rect(ctx, who, {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, dst, "destination ", d);
+}
+}
+static int warp_family_views(jh_ctx* ctx, const Alloc* src, Alloc* dst, jimage_rect* s, jimage_rect d, ImageViews* v) {
+    if (int rc = image_call_views(ctx, src, dst, d, v)) return rc;
+    if (jimage_rect_empty(*s)) {
+        v->from = {nullptr, std::max(src->width, 1u), std::max(src->height, 1u)};
+        *s = {s->x, s->y, std::max(s->w, 1u), std::max(s->h, 1u)};
+    }
+    return JH_OK;
+}
+
+// warp (include/jello_hip.h "Warp"; the plan, the bounds and the descriptor: include/jello_warp.h; kernels_warp.hip, warp_taps.h)
 int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_warp_desc* desc) {
     static_assert(JH_WARP_NEAREST == JWARP_NEAREST && JH_WARP_BILINEAR == JWARP_BILINEAR && JH_WARP_BICUBIC == JWARP_BICUBIC &&
                       JH_WARP_EDGE_ZERO == JWARP_EDGE_ZERO && JH_WARP_EDGE_CLAMP == JWARP_EDGE_CLAMP && JH_WARP_EDGE_REPEAT == JWARP_EDGE_REPEAT &&
@@ -1718,18 +1738,13 @@ int jh_warp(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_
     if (const char* why = jwarp_desc_error(desc->filter, desc->edge, desc->flags, src->width, src->height, dst->width, dst->height))
         return fail(ctx, JH_ERR_INVALID, std::string("jh_warp: ") + why);
     jimage_rect s, d;
-    if (int rc = image_call_rect(ctx, "jh_warp", {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, *src, "source ", &s)) return rc;
-    if (int rc = image_call_rect(ctx, "jh_warp", {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, *dst, "destination ", &d)) return rc;
+    if (int rc = warp_family_rects(ctx, "jh_warp", desc, *src, *dst, &s, &d)) return rc;
     int64_t plan[6];
     if (const char* why = jwarp_plan(desc->matrix, plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_warp: illegal matrix: ") + why);
     if (jimage_rect_empty(d)) return JH_OK;  // (an image without texels)
     return post_render_call(ctx, "warp", [&] {
         ImageViews v;
-        if (int rc = image_call_views(ctx, src, dst, d, &v)) return rc;
-        if (jimage_rect_empty(s)) {  // a source without texels reads as transparent black: nothing is loaded, and the launcher gets a texel it can name
-            v.from = {nullptr, std::max(src->width, 1u), std::max(src->height, 1u)};
-            s = {s.x, s.y, std::max(s.w, 1u), std::max(s.h, 1u)};
-        }
+        if (int rc = warp_family_views(ctx, src, dst, &s, d, &v)) return rc;
         return launch_status(ctx, "jh_warp",
                              jh_warp_launch(ctx->stream, v.from, s, v.to, d, plan, desc->filter, desc->edge, (desc->flags & JH_WARP_STRAIGHT) != 0u, ctx->num_cus));
     });
@@ -1833,7 +1848,7 @@ int jh_turbulence(jh_ctx* ctx, uint64_t dst_image_id, const jh_turbulence_desc* 
         });
 }
 
-// displace (include/jello_hip.h "Displace"; the descriptor and the offset: include/jello_displace.h; the plan: include/jello_warp.h; kernels_displace.hip)
+// displace (include/jello_hip.h "Displace"; the descriptor and the offset: include/jello_displace.h; the plan: include/jello_warp.h; kernels_displace.hip, warp_taps.h)
 int jh_displace(jh_ctx* ctx, uint64_t src_image_id, uint64_t map_image_id, uint64_t dst_image_id, const jh_displace_desc* desc) {
     static_assert(JH_DISPLACE_R == JDISP_R && JH_DISPLACE_G == JDISP_G && JH_DISPLACE_B == JDISP_B && JH_DISPLACE_A == JDISP_A &&
                       JH_DISPLACE_STRAIGHT == JDISP_STRAIGHT && JH_DISPLACE_STRAIGHT == JH_WARP_STRAIGHT,
@@ -1845,19 +1860,14 @@ int jh_displace(jh_ctx* ctx, uint64_t src_image_id, uint64_t map_image_id, uint6
                                            src->height, map->width, map->height, dst->width, dst->height))
         return fail(ctx, JH_ERR_INVALID, std::string("jh_displace: ") + why);
     jimage_rect s, d;
-    if (int rc = image_call_rect(ctx, "jh_displace", {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, *src, "source ", &s)) return rc;
-    if (int rc = image_call_rect(ctx, "jh_displace", {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, *dst, "destination ", &d)) return rc;
+    if (int rc = warp_family_rects(ctx, "jh_displace", desc, *src, *dst, &s, &d)) return rc;
     int64_t plan[6];
     if (const char* why = jwarp_plan(desc->matrix, plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_displace: illegal matrix: ") + why);
     if (jimage_rect_empty(d)) return JH_OK;  // (an image without texels)
     return post_render_call(ctx, "displace", [&] {
         const jimage_src from_map = {content_or_null(*map), map->width, map->height};  // (taken first: the map may be dst, and a never-written one reads 0, not its memory)
         ImageViews v;
-        if (int rc = image_call_views(ctx, src, dst, d, &v)) return rc;
-        if (jimage_rect_empty(s)) {  // a source without texels reads as transparent black: nothing is loaded, and the launcher gets a texel it can name
-            v.from = {nullptr, std::max(src->width, 1u), std::max(src->height, 1u)};
-            s = {s.x, s.y, std::max(s.w, 1u), std::max(s.h, 1u)};
-        }
+        if (int rc = warp_family_views(ctx, src, dst, &s, d, &v)) return rc;
         return launch_status(ctx, "jh_displace",
                              jh_displace_launch(ctx->stream, v.from, s, from_map, v.to, d, plan, desc->scale_x, desc->scale_y, desc->x_channel, desc->y_channel,
                                                 desc->filter, desc->edge, (desc->flags & JH_DISPLACE_STRAIGHT) != 0u, ctx->num_cus));
@@ -1884,7 +1894,7 @@ int jh_shadow(jh_ctx* ctx, uint64_t dst_image_id, const jh_shadow_desc* desc) {
     });
 }
 
-// perspective (include/jello_hip.h "Perspective"; the plan, the position and the bounds: include/jello_perspective.h; kernels_perspective.hip)
+// perspective (include/jello_hip.h "Perspective"; the plan, the position and the bounds: include/jello_perspective.h; kernels_perspective.hip, warp_taps.h)
 int jh_perspective(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_perspective_desc* desc) {
     static_assert(JH_PERSPECTIVE_STRAIGHT == JPERSP_STRAIGHT && JH_PERSPECTIVE_STRAIGHT == JH_WARP_STRAIGHT, "the C ABI's values are the rule's");
     Alloc *src = nullptr, *dst = nullptr;
@@ -1892,18 +1902,13 @@ int jh_perspective(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, co
     if (const char* why = jpersp_desc_error(desc->filter, desc->edge, desc->flags, src->width, src->height, dst->width, dst->height))
         return fail(ctx, JH_ERR_INVALID, std::string("jh_perspective: ") + why);
     jimage_rect s, d;
-    if (int rc = image_call_rect(ctx, "jh_perspective", {desc->src_x, desc->src_y, desc->src_width, desc->src_height}, *src, "source ", &s)) return rc;
-    if (int rc = image_call_rect(ctx, "jh_perspective", {desc->dst_x, desc->dst_y, desc->dst_width, desc->dst_height}, *dst, "destination ", &d)) return rc;
+    if (int rc = warp_family_rects(ctx, "jh_perspective", desc, *src, *dst, &s, &d)) return rc;
     double plan[9];
     if (const char* why = jpersp_plan(desc->matrix, plan)) return fail(ctx, JH_ERR_INVALID, std::string("jh_perspective: illegal matrix: ") + why);
     if (jimage_rect_empty(d)) return JH_OK;  // (an image without texels)
     return post_render_call(ctx, "perspective", [&] {
         ImageViews v;
-        if (int rc = image_call_views(ctx, src, dst, d, &v)) return rc;
-        if (jimage_rect_empty(s)) {  // a source without texels reads as transparent black: nothing is loaded, and the launcher gets a texel it can name
-            v.from = {nullptr, std::max(src->width, 1u), std::max(src->height, 1u)};
-            s = {s.x, s.y, std::max(s.w, 1u), std::max(s.h, 1u)};
-        }
+        if (int rc = warp_family_views(ctx, src, dst, &s, d, &v)) return rc;
         return launch_status(ctx, "jh_perspective",
                              jh_perspective_launch(ctx->stream, v.from, s, v.to, d, plan, desc->filter, desc->edge, (desc->flags & JH_PERSPECTIVE_STRAIGHT) != 0u, ctx->num_cus));
     });

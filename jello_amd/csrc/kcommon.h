@@ -365,6 +365,7 @@ struct JhResampleTables {
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses (an image launcher, which takes the views and resolved
 // rectangles of include/jello_image.h: a rectangle that is not inside its image), another negative value (-2) for a failed launch.
+// jh_warp_launch, jh_displace_launch and jh_perspective_launch share warp_taps.h: one argument block, one ladder, each its own position rule.
 extern "C" {
 int jh_blit_launch(hipStream_t stream, const void* src, void* dst, uint64_t pitch, uint32_t width, uint32_t row0, uint32_t row1, int format,
                    int num_cus);

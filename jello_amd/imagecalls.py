@@ -162,13 +162,19 @@ def warp_bounds(matrix, src_size, filter, dst_size, twin=False):
     return tuple(int(v) for v in rect)
 
 
-def _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
-    d = CWarpDesc()
-    d.matrix[:] = list(_matrix6(matrix))
-    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else WARP_STRAIGHT
+def _warp_family_desc(ctype, matrix, straight, filter, edge, src_rect, dst_rect, premultiplied):
+    """What jh_warp_desc, jh_displace_desc and jh_perspective_desc share: the matrix (in the descriptor's layout), filter, edge, the
+    call's `straight` flag and the two rectangles."""
+    d = ctype()
+    d.matrix[:] = list(matrix)
+    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else straight
     d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
     d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
     return d
+
+
+def _warp_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
+    return _warp_family_desc(CWarpDesc, _matrix6(matrix), WARP_STRAIGHT, filter, edge, src_rect, dst_rect, premultiplied)
 
 
 class ConvolveEdge(enum.IntEnum):
@@ -371,11 +377,7 @@ def displace_offset(scale, bits, twin=False):
 
 
 def _displace_desc(scale, x_channel, y_channel, matrix, filter, edge, src_rect, dst_rect, premultiplied):
-    d = CDisplaceDesc()
-    d.matrix[:] = list(_matrix6(matrix))
-    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else DISPLACE_STRAIGHT
-    d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
-    d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
+    d = _warp_family_desc(CDisplaceDesc, _matrix6(matrix), DISPLACE_STRAIGHT, filter, edge, src_rect, dst_rect, premultiplied)
     sx, sy = scale if isinstance(scale, (tuple, list)) else (scale, scale)
     d.scale_x, d.scale_y = float(np.float32(sx)), float(np.float32(sy))
     d.x_channel, d.y_channel = int(x_channel), int(y_channel)
@@ -482,12 +484,7 @@ def perspective_bounds(matrix, src_size, filter, dst_size, twin=False):
 
 
 def _perspective_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
-    d = CPerspectiveDesc()
-    d.matrix[:] = list(_matrix9(matrix))
-    d.filter, d.edge, d.flags = int(filter), int(edge), 0 if premultiplied else PERSPECTIVE_STRAIGHT
-    d.src_x, d.src_y, d.src_width, d.src_height = _rect(src_rect)
-    d.dst_x, d.dst_y, d.dst_width, d.dst_height = _rect(dst_rect)
-    return d
+    return _warp_family_desc(CPerspectiveDesc, _matrix9(matrix), PERSPECTIVE_STRAIGHT, filter, edge, src_rect, dst_rect, premultiplied)
 
 
 class ColorSpace(enum.IntEnum):

@@ -5,7 +5,7 @@ source's content kind, what dst held before ('poison' or 'never'), the scale pai
 the map is: 'own' (a third image), 'dst', 'src', or 'never' (a third image that was never written).  Every image but the grid-stride
 case's is at most 64 x 48.
 
-Sizes on each side of every boundary of the kernel (jello_amd/csrc/kernels_displace.hip; they are k_warp's, tests/warp_cases.py):
+Sizes on each side of every boundary of the kernel (jello_amd/csrc/warp_taps.h; they are jh_warp's, tests/warp_cases.py):
 widths 1, 15, 16, 17, 31, 33 against the tile row of 16 texels, heights 1, 3, 4, 5, 15, 16, 17 against the wave's 4 and the workgroup's
 16 rows, rectangles at odd offsets (the phase of the tile grid differs from row to row), and 1040 x 520 = 2 178 tiles against the
 launcher's cap of 2 048 workgroups.  The source image outside its rectangle is NaN, which a tap that left the rectangle would carry into

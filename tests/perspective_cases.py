@@ -1,11 +1,11 @@
 """The battery jh_perspective is held to (tests/test_gpu_perspective.py) and the reference's sensitivity is measured on
 (tests/test_perspective_spec.py).  A case: name, the source image's size and rectangle, the destination image's size and rectangle,
 the matrix (nine entries, source rectangle -> destination image), filter, edge, flags, the content kind, what dst held before
-('poison' or 'never'), `inst` = (filter, edge, straight), the instantiation of k_perspective it runs, and for the affine cases whose
+('poison' or 'never'), `inst` = (filter, edge, straight), the instantiation of jh_perspective's kernel it runs, and for the affine cases whose
 inverse is dyadic `affine`, the six entries Engine.warp takes.  Every image but the one of the grid-stride case is at most 128 on a
 side.
 
-Sizes on each side of every boundary of the kernel (jello_amd/csrc/kernels_perspective.hip): a tile's row of 16 texels (widths 15, 16,
+Sizes on each side of every boundary of the kernel (jello_amd/csrc/warp_taps.h): a tile's row of 16 texels (widths 15, 16,
 17, 31, 32, 33), a wave's 4 rows and a workgroup's 16 (heights 3, 4, 5, 15, 16, 17), 1 x 1, 1 x 5 and 5 x 1, rectangles at odd offsets
 (the tile grid lies on dst's 128-byte lines, so the phase differs from row to row), and warp_cases.BIG's 1040 x 520 = 2 178 tiles,
 above the launcher's cap of 8 per CU x 256 CUs.  The source outside its rectangle is NaN and dst outside its rectangle POISON.

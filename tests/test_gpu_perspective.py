@@ -36,7 +36,7 @@ INSTANTIATIONS = sorted({c["inst"] for c in perspective_cases.CASES})
 
 @pytest.mark.parametrize("inst", INSTANTIATIONS, ids=lambda i: "%s_%s_%s" % (WarpFilter(i[0]).name, WarpEdge(i[1]).name, "straight" if i[2] else "premul"))
 def test_battery(engine, inst):
-    """Every case of one instantiation of k_perspective through Engine.perspective: dst is poisoned first (or never written), the
+    """Every case of one instantiation of jh_perspective's kernel through Engine.perspective: dst is poisoned first (or never written), the
     whole of dst is compared -- the rectangle with the reference, the texels outside it with what they held (a never-written dst:
     transparent black).  A failure names the case."""
     names = [c["name"] for c in perspective_cases.CASES if c["inst"] == inst]

@@ -3,7 +3,7 @@ A case: name, the source image's size and rectangle, the destination image's siz
 destination image), filter, edge, flags, the content kind, and what dst held before ('poison' or 'never').  Every image but the one of
 the grid-stride case is at most 64 x 48.
 
-Sizes on each side of every boundary of the kernel (jello_amd/csrc/kernels_warp.hip):
+Sizes on each side of every boundary of the kernel (jello_amd/csrc/kernels_warp.hip, on the tile constants of warp_taps.h):
   a tile's row, 16 texels = one 128-byte line of dst     destination widths 1, 15, 16, 17, 31, 33
   a wave's tile, 4 rows; a workgroup's, 16               destination heights 1, 3, 4, 5, 15, 16, 17, 31, 33
   the tile grid lies on dst's 128-byte lines             widths that are no multiple of 16 and rectangles at odd offsets: the phase

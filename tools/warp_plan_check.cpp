@@ -3,7 +3,8 @@
 //     g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
 //         tools/warp_plan_check.cpp -o /tmp/warp_plan_check && /tmp/warp_plan_check
 //
-// Four things.  (1) Legal and illegal matrices: each condition of the rule from both sides, the reason named.  (2) The plan against
+// Four things.  (1) Legal and illegal matrices: each condition of the rule from both sides, the reason named; every plan jwarp_plan
+// makes is inside jwarp_plan_in_range, a plan one unit beyond either limit is not.  (2) The plan against
 // __int128 arithmetic: every coefficient is the binary64 inverse coefficient times 2^31 (offsets: 2^32) rounded half to even, worked
 // on the double's own integer mantissa; the positions U, V of the corner texels of a 32768 x 32768 destination in __int128 equal the
 // int64 ones and stay below 2^58.  (3) The four index rules against a brute-force definition (a walk, no division) for n = 1 .. 5
@@ -56,7 +57,7 @@ static int check_matrices() {
         {{1, 0, 0, 1, 4194305.0, 0}, "above 2^22"}, {{1, 0, 0, 1, 0, -4194304.5}, "above 2^22"}, {{1e-300, 0, 0, 1e-300, 0, 0}, "determinant is 0"}};
     int64_t plan[6];
     for (const auto& m : legal)
-        if (jwarp_plan(m, plan)) return 1;
+        if (jwarp_plan(m, plan) || !jwarp_plan_in_range(plan)) return 1;
     for (const auto& c : illegal) {
         plan[0] = 77;
         const char* why = jwarp_plan(c.m, plan);
@@ -64,6 +65,19 @@ static int check_matrices() {
     }
     const double id[6] = {1, 0, 0, 1, 0, 0};
     if (jwarp_plan(id, plan) || plan[0] != ((int64_t)1 << 31) || plan[1] != 0 || plan[2] != 0 || plan[3] != 0 || plan[4] != ((int64_t)1 << 31) || plan[5] != 0) return 3;
+    // the range a launcher asks of a plan: the legal matrices at each limit are inside it (2^37 = 64 x 2^31, 2^54 = 2^22 x 2^32), a
+    // coefficient one unit beyond its limit is not
+    const double at_scale[6] = {1.0 / 64, 0, 0, -1.0 / 64, 0, 0}, at_offset[6] = {1, 0, 0, 1, 4194304.0, -4194304.0};
+    if (jwarp_plan(at_scale, plan) || plan[0] != ((int64_t)1 << 37) || plan[4] != -((int64_t)1 << 37) || !jwarp_plan_in_range(plan)) return 4;
+    if (jwarp_plan(at_offset, plan) || plan[2] != -((int64_t)1 << 54) || plan[5] != ((int64_t)1 << 54) || !jwarp_plan_in_range(plan)) return 5;
+    for (int i = 0; i < 6; i++)
+        for (int64_t sign : {1, -1}) {
+            int64_t edge[6] = {0, 0, 0, 0, 0, 0};
+            edge[i] = sign * ((int64_t)1 << (i % 3 == 2 ? 54 : 37));
+            if (!jwarp_plan_in_range(edge)) return 6;
+            edge[i] += sign;
+            if (jwarp_plan_in_range(edge)) return 7;
+        }
     return 0;
 }
 
@@ -80,6 +94,7 @@ static int check_plans(unsigned* count) {
         const char* why = jwarp_inverse(m, inv);
         if ((why != nullptr) != (jwarp_plan(m, plan) != nullptr)) return 1;
         if (why) continue;
+        if (!jwarp_plan_in_range(plan)) return 7;
         n++;
         for (int i = 0; i < 6; i++)
             if ((i128)plan[i] != scaled_rint(inv[i], i % 3 == 2 ? 32 : 31)) return 2;
