@@ -33,6 +33,7 @@
  *   jh_displace                       (no counterpart: feDisplacementMap on RGBA16F images on the device)
  *   jh_shadow                         (no counterpart: a blurred rounded rectangle generated into an RGBA16F image)
  *   jh_perspective                    (no counterpart: a projective transform of RGBA16F images on the device)
+ *   jh_distance                       (no counterpart: the capped Euclidean distance to a shape, through a ramp)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -1191,6 +1192,87 @@ typedef struct jh_perspective_desc {
 int jh_perspective_plan(const double matrix[9], double plan[9]);
 int jh_perspective_bounds(const double matrix[9], uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t rect[4]);
 int jh_perspective(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_perspective_desc* desc);
+
+/* ---- Distance: the Euclidean distance to a shape, capped at a radius, through a linear ramp (DESIGN.md 5.20 "Distance rule") ----
+ * Round outlines, inner and outer strokes of fractional width, dilate and erode by a DISC, glows with a defined falloff, signed
+ * distance fields of a cached layer -- one function of one quantity, without the image leaving the device.  The squared distance is
+ * an integer, so the result is defined on values, and every implementation produces these bits (include/jello_distance.h states the
+ * host half and the per-axis pieces, tests/distance_ref.py restates all of it from the set definition).
+ *   arguments   channel: 0..3, which of R, G, B, A of the source is read.  threshold: binary32, finite.  which: JH_DISTANCE_OUTER = 0 |
+ *               JH_DISTANCE_INNER = 1 | JH_DISTANCE_SIGNED = 2.  edge: JH_DISTANCE_EDGE_ZERO = 0 | JH_DISTANCE_EDGE_CLAMP = 1.
+ *               max_distance: R, an integer in [1, JH_DISTANCE_MAX_RADIUS = 255].  scale, offset: binary32, finite.  color[4]:
+ *               binary32, premultiplied, linear; any value (as jh_shadow's).  flags: bit 0, JH_DISTANCE_STRAIGHT.  The rectangle (x,
+ *               y, width, height) of dst is written; width == height == 0 means the whole image (x and y are then ignored).
+ *   seed        a texel of the image is a SEED iff its chosen channel, the f16 widened to binary32, is >= threshold.  The comparison
+ *               is IEEE: a NaN is not a seed, and -0 >= +0 holds.  A source that was never written reads as transparent black.
+ *   distance^2  integers.  CAP = (R + 1)^2.  Dout(X, Y) = min(CAP, min of (x - X)^2 + (y - Y)^2 over the seeds (x, y) of the image);
+ *               Din(X, Y) the same over the non-seeds.  Under EDGE_ZERO every integer position outside the image is a non-seed, so
+ *               an inner distance ends at the image's border (as an erode under JH_MORPH_EDGE_ZERO does); under EDGE_CLAMP the
+ *               positions outside the image do not exist.  The IMAGE is the edge, not the rectangle: seeds outside the rectangle
+ *               but inside the image count.  A feature farther than R in x or in y is at least CAP away, so a window of +-R and the
+ *               whole plane give the same D.  THE RESULT IS DEFINED ON THE SET, NOT ON PASSES: columns then rows, a lower envelope
+ *               and a brute-force window all give these bits, and the implementation is free to choose.
+ *   distance    binary32; sqrtf is the correctly rounded IEEE square root.  OUTER: s = sqrtf((float)Dout).  INNER: s =
+ *               sqrtf((float)Din).  SIGNED: a non-seed texel has s = sqrtf((float)Dout) - 0.5f, a seed texel s = 0.5f -
+ *               sqrtf((float)Din): the zero crossing lies on the texel edge between the two classes.  Where D = CAP, s is 256 in
+ *               OUTER and INNER and +255.5 (non-seed) or -255.5 (seed) in SIGNED for R = 255, R + 1 and +-(R + 0.5) in general:
+ *               "farther than R".
+ *   value       v = minNum(maxNum(fmaf(s, scale, offset), 0), 1).  An overflow to +-Inf is clamped.  No NaN can arise: s, scale and
+ *               offset are finite, so the fused product-sum is a finite real rounded once.
+ *   store       p = color v, one product per channel.  STRAIGHT: f16(p) per channel, round to nearest even.  Otherwise as fine,
+ *               jh_composite and jh_shadow store: a_inv = 1.0f / maxNum(p.a, 1e-6f); (f16(p.r a_inv + 0.0f), f16(p.g a_inv + 0.0f),
+ *               f16(p.b a_inv + 0.0f), f16(p.a + 0.0f)).
+ * So OUTER with scale = -1, offset = w + 0.5 is the coverage of the shape dilated by a DISC of radius w -- w may be fractional, and
+ * the edge has a ramp one texel wide; INNER with scale = 1, offset = 0.5 - w is the erode by that disc; SIGNED with scale =
+ * 1 / (2 R), offset = 0.5 is the usual SDF texture.  A call written in four quadrant rectangles equals the whole-image call.  OUTER is
+ * monotone in the seed set: more seeds never make a distance longer.  On an image of height 1 or width 1 the disc is the box, and
+ * the step ramp (scale -1, offset R + 1) on a 0 / 1 mask is jh_morphology's STRAIGHT dilate of it, bit for bit.
+ *
+ * jh_distance_plan: what the call will do with desc on an image_w x image_h image -- the resolved rectangle, R, CAP, the number of
+ * planes (2 for SIGNED, else 1), their columns (rectangle width + 2 R) and rows (rectangle height), and the bytes of scratch they
+ * take (0 for an image without texels).  Host only, no context.  It is what a caller needs to know which eager call must precede a
+ * capture.  JH_ERR_INVALID for a null argument, a descriptor the rule refuses or a rectangle the image refuses, plan then untouched.
+ *
+ * jh_distance: the rule applied to src_image_id, written to the rectangle of dst_image_id.  The images carry their own sizes and
+ * must be JL_RGBA16_FLOAT and of equal size.  dst_image_id may equal src_image_id: the source is read once into the intermediate and
+ * no pass reads what the call has written.  Texels of dst outside the rectangle keep their bits; a dst that was never written is
+ * cleared to transparent black first and then counts as written.
+ * Stream-ordered on the context's stream, never waits: TWO kernel launches (the columns' run lengths into planes of uint16_t; the
+ * rows' lower envelope over them from LDS, the square root, the ramp and the store), plus a fill when dst has to be cleared.  The
+ * row pass's walk stops as soon as dx^2 reaches the best squared distance so far, so its cost follows the distance found, not R.
+ * The planes live in a scratch array of the context, planes x rect height x (rect width + 2 R) x 2 bytes, which only grows: the call
+ * may be captured between jh_graph_begin and jh_graph_end once a call needing no more has run eagerly (a capture that would have to
+ * grow it is refused with JH_ERR_OOM and that advice).  With profiling on the call is a query "distance" with stage = -1 in
+ * jh_profile_collect_tree.  Not in band mode (jh_set_band): the rows next to a band belong to another rank's context.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_distance: ": a
+ * null desc; an unknown source or destination id; an image that is not RGBA16F; images of different size; an unknown channel,
+ * which, edge or flag bit; max_distance 0 or above 255; a threshold, scale or offset that is not finite; a rectangle that is not
+ * inside the image or that is empty in exactly one dimension; a band set with jh_set_band. */
+typedef enum jh_distance_which { JH_DISTANCE_OUTER = 0, JH_DISTANCE_INNER = 1, JH_DISTANCE_SIGNED = 2 } jh_distance_which;
+typedef enum jh_distance_edge { JH_DISTANCE_EDGE_ZERO = 0, JH_DISTANCE_EDGE_CLAMP = 1 } jh_distance_edge;
+#define JH_DISTANCE_STRAIGHT 1u
+#define JH_DISTANCE_MAX_RADIUS 255u
+typedef struct jh_distance_desc {
+    int channel;                   /* 0..3: R, G, B, A of the source */
+    float threshold;               /* a texel is a seed iff its channel >= threshold */
+    int which;                     /* jh_distance_which */
+    int edge;                      /* jh_distance_edge */
+    uint32_t max_distance;         /* R, 1..255 */
+    float scale, offset;           /* v = clamp(fmaf(s, scale, offset), 0, 1) */
+    float color[4];                /* premultiplied, linear */
+    uint32_t flags;                /* bit 0: JH_DISTANCE_STRAIGHT */
+    uint32_t x, y, width, height;  /* rectangle of dst that is written; 0 x 0: the whole image */
+} jh_distance_desc;
+typedef struct jh_dist_plan {
+    uint32_t x, y, width, height;  /* the resolved rectangle */
+    uint32_t radius, cap;          /* R and (R + 1)^2 */
+    uint32_t planes;               /* 1, or 2 for SIGNED */
+    uint32_t plane_columns, plane_rows; /* width + 2 R, height */
+    uint32_t reserved;             /* 0 */
+    uint64_t scratch_bytes;        /* planes x plane_rows x plane_columns x 2; 0 for an image without texels */
+} jh_dist_plan;
+int jh_distance_plan(const jh_distance_desc* desc, uint32_t image_w, uint32_t image_h, jh_dist_plan* plan);
+int jh_distance(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_distance_desc* desc);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -14,6 +14,7 @@
 #include "jello_composite.h"
 #include "jello_convolve.h"
 #include "jello_displace.h"
+#include "jello_distance.h"
 #include "jello_lighting.h"
 #include "jello_perspective.h"
 #include "jello_resample.h"
@@ -113,6 +114,11 @@ static inline const char* jq_perspective_bounds(const double* matrix, uint32_t s
     return jpersp_bounds(matrix, src_w, src_h, filter, dst_w, dst_h, rect);
 }
 
+static inline const char* jq_distance_plan(const jh_distance_desc* desc, uint32_t image_w, uint32_t image_h, jh_dist_plan* plan) {
+    if (!desc || !plan) return "null argument";
+    return jdist_plan(desc, image_w, image_h, plan);
+}
+
 // (the geometry of jh_composite: out[6] = {sx', sy', dx', dy', w, h}, all zero when nothing is left)
 static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy,
                                             uint32_t dst_w, uint32_t dst_h, uint32_t* out) {
@@ -147,7 +153,8 @@ static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint
     X(shadow_bounds, (const jh_shadow_desc* desc, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), (desc, dst_w, dst_h, rect))        \
     X(perspective_plan, (const double* matrix, double* plan), (matrix, plan))                                                               \
     X(perspective_bounds, (const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), \
-      (matrix, src_w, src_h, filter, dst_w, dst_h, rect))
+      (matrix, src_w, src_h, filter, dst_w, dst_h, rect))                                                                                   \
+    X(distance_plan, (const jh_distance_desc* desc, uint32_t image_w, uint32_t image_h, jh_dist_plan* plan), (desc, image_w, image_h, plan))
 #define JQ_HOST_QUERY_LIST(X)                                                                                                               \
     X(composite_clip,                                                                                                                       \
       (uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w, uint32_t dst_h, \

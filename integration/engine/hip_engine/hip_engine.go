@@ -1114,6 +1114,82 @@ func (e *Engine) Perspective(src, dst renderer.ImageProxy, desc PerspectiveDesc)
 	e.check(C.jh_perspective(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "perspective")
 }
 
+// DistanceWhich is jh_distance_which: the distance to the nearest seed, to the nearest non-seed, or signed (negative inside).
+type DistanceWhich int32
+
+const (
+	DistanceOuter  DistanceWhich = 0
+	DistanceInner  DistanceWhich = 1
+	DistanceSigned DistanceWhich = 2
+)
+
+// DistanceEdge is jh_distance_edge: every position outside the image is a non-seed, or none exists.
+type DistanceEdge int32
+
+const (
+	DistanceEdgeZero  DistanceEdge = 0
+	DistanceEdgeClamp DistanceEdge = 1
+)
+
+// DistanceStraight is JH_DISTANCE_STRAIGHT: f16(color v) is stored as it is, not by the store rule.
+const DistanceStraight uint32 = 1
+
+// DistanceDesc is jh_distance_desc (include/jello_hip.h "Distance"): the channel (0..3) and threshold that make a texel a seed, which
+// distance, the edge mode, R = MaxDistance (1..255), the ramp v = clamp(s Scale + Offset, 0, 1), the premultiplied colour, the flags and
+// the rectangle of dst that is written (0 x 0: the whole image).
+type DistanceDesc struct {
+	Channel             int32
+	Threshold           float32
+	Which               DistanceWhich
+	Edge                DistanceEdge
+	MaxDistance         uint32
+	Scale, Offset       float32
+	Color               [4]float32
+	Flags               uint32
+	X, Y, Width, Height uint32
+}
+
+func (desc DistanceDesc) c() C.jh_distance_desc {
+	d := C.jh_distance_desc{channel: C.int(desc.Channel), threshold: C.float(desc.Threshold), which: C.int(desc.Which), edge: C.int(desc.Edge),
+		max_distance: C.uint32_t(desc.MaxDistance), scale: C.float(desc.Scale), offset: C.float(desc.Offset), flags: C.uint32_t(desc.Flags),
+		x: C.uint32_t(desc.X), y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height)}
+	for i, v := range desc.Color {
+		d.color[i] = C.float(v)
+	}
+	return d
+}
+
+// DistPlan is jh_dist_plan: the resolved rectangle, R, CAP = (R + 1)^2, the planes of the intermediate and the scratch they take.
+type DistPlan struct {
+	X, Y, Width, Height     uint32
+	Radius, Cap             uint32
+	Planes                  uint32
+	PlaneColumns, PlaneRows uint32
+	ScratchBytes            uint64
+}
+
+// DistancePlan is jh_distance_plan: what Distance does with desc on an imageW x imageH image -- in particular the scratch bytes, which
+// say which eager call has to precede a capture (one that needs no less).  Host only.
+func DistancePlan(desc DistanceDesc, imageW, imageH uint32) (DistPlan, error) {
+	d := desc.c()
+	var p C.jh_dist_plan
+	if C.jh_distance_plan(&d, C.uint32_t(imageW), C.uint32_t(imageH), &p) != 0 {
+		return DistPlan{}, fmt.Errorf("hip_engine: DistancePlan: a descriptor the rule refuses or a rectangle the image refuses")
+	}
+	return DistPlan{X: uint32(p.x), Y: uint32(p.y), Width: uint32(p.width), Height: uint32(p.height), Radius: uint32(p.radius), Cap: uint32(p.cap),
+		Planes: uint32(p.planes), PlaneColumns: uint32(p.plane_columns), PlaneRows: uint32(p.plane_rows), ScratchBytes: uint64(p.scratch_bytes)}, nil
+}
+
+// Distance is jh_distance: the Euclidean distance to the shape in the RGBA16F image src -- the texels whose channel is >= the threshold
+// -- capped at MaxDistance, through a linear ramp, times a colour, into the image dst of the same size (dst may be src) by the rule of
+// DESIGN.md 5.20 (defined on integers and on values: every implementation gives the same bits).  Round outlines, strokes of fractional
+// width, disc dilate and erode, glows, SDF textures.  Stream-ordered behind the frame, waits for nothing, two kernel launches; the
+// intermediate planes live in a scratch array that only grows, so the call is capturable once a call needing no less has run eagerly.
+func (e *Engine) Distance(src, dst renderer.ImageProxy, desc DistanceDesc) {
+	d := desc.c()
+	e.check(C.jh_distance(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "distance")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -241,6 +241,20 @@ class CPerspectiveDesc(ctypes.Structure):
                 ("dst_x", ctypes.c_uint32), ("dst_y", ctypes.c_uint32), ("dst_width", ctypes.c_uint32), ("dst_height", ctypes.c_uint32)]
 
 
+class CDistanceDesc(ctypes.Structure):
+    """jh_distance_desc (include/jello_hip.h)."""
+    _fields_ = [("channel", ctypes.c_int32), ("threshold", ctypes.c_float), ("which", ctypes.c_int32), ("edge", ctypes.c_int32),
+                ("max_distance", ctypes.c_uint32), ("scale", ctypes.c_float), ("offset", ctypes.c_float), ("color", ctypes.c_float * 4),
+                ("flags", ctypes.c_uint32), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
+
+
+class CDistPlan(ctypes.Structure):
+    """jh_dist_plan (include/jello_hip.h)."""
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("radius", ctypes.c_uint32),
+                ("cap", ctypes.c_uint32), ("planes", ctypes.c_uint32), ("plane_columns", ctypes.c_uint32), ("plane_rows", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("scratch_bytes", ctypes.c_uint64)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -325,6 +339,7 @@ def _declare(L):
         "shadow_bounds": [ctypes.POINTER(CShadowDesc), u32, u32, ctypes.POINTER(u32)],
         "perspective_plan": [dp, dp],
         "perspective_bounds": [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)],
+        "distance_plan": [ctypes.POINTER(CDistanceDesc), u32, u32, ctypes.POINTER(CDistPlan)],
     }
     for name, argtypes in queries.items():
         getattr(L, "jl_" + name).argtypes = argtypes
@@ -378,6 +393,7 @@ def _declare(L):
     hip.jh_displace.argtypes = [vp, u64, u64, u64, ctypes.POINTER(CDisplaceDesc)]
     hip.jh_shadow.argtypes = [vp, u64, ctypes.POINTER(CShadowDesc)]
     hip.jh_perspective.argtypes = [vp, u64, u64, ctypes.POINTER(CPerspectiveDesc)]
+    hip.jh_distance.argtypes = [vp, u64, u64, ctypes.POINTER(CDistanceDesc)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -24,6 +24,7 @@
 #include "../../include/jello_composite.h"
 #include "../../include/jello_resample.h"
 #include "../../include/jello_color.h"
+#include "../../include/jello_distance.h"
 #include "../../include/jello_morph.h"
 #include "../../include/jello_warp.h"
 #include "../../include/jello_convolve.h"
@@ -1172,7 +1173,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow, perspective ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow, perspective, distance ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1704,6 +1705,33 @@ int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, con
             return launch_status(ctx, "jh_morphology",
                                  jh_morph_launch(ctx->stream, v.from, v.to, r, desc->op == JH_MORPH_DILATE, desc->edge == JH_MORPH_EDGE_CLAMP,
                                                  (desc->flags & JH_MORPH_STRAIGHT) != 0u, desc->radius_x, desc->radius_y, tmp, ctx->num_cus));
+        });
+}
+
+// distance (include/jello_hip.h "Distance"; the descriptor, the planes and the per-axis pieces: include/jello_distance.h; kernels_distance.hip)
+int jh_distance(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_distance_desc* desc) {
+    static_assert(JH_DISTANCE_OUTER == JDIST_OUTER && JH_DISTANCE_INNER == JDIST_INNER && JH_DISTANCE_SIGNED == JDIST_SIGNED &&
+                      JH_DISTANCE_EDGE_ZERO == JDIST_EDGE_ZERO && JH_DISTANCE_EDGE_CLAMP == JDIST_EDGE_CLAMP && JH_DISTANCE_STRAIGHT == JDIST_STRAIGHT &&
+                      JH_DISTANCE_MAX_RADIUS == JDIST_MAX_RADIUS,
+                  "the C ABI's values are the rule's");
+    Alloc *src = nullptr, *dst = nullptr;
+    if (int rc = image_call_images(ctx, "jh_distance", desc, src_image_id, dst_image_id, nullptr, "the rows next to a band belong to another rank", &src, &dst)) return rc;
+    if (src->width != dst->width || src->height != dst->height) return fail(ctx, JH_ERR_INVALID, "jh_distance: the images differ in size");
+    if (const char* why = jdist_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_distance: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_distance", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    void* tmp = nullptr;
+    return post_render_call(
+        ctx, "distance",
+        [&] {
+            return scratch_take(ctx, "jh_distance", "run a call needing no less scratch (jh_distance_plan) once eagerly first", JH_SCR_DISTANCE,
+                                jdist_scratch_bytes(r.w, r.h, desc->max_distance, desc->which), &tmp);
+        },
+        [&] {
+            ImageViews v;
+            if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
+            return launch_status(ctx, "jh_distance", jh_distance_launch(ctx->stream, v.from, v.to, r, desc, tmp, ctx->num_cus));
         });
 }
 

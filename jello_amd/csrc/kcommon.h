@@ -241,6 +241,8 @@ struct JhImageDesc {
 //              gradients laid out [lattice value][channel][2] then the 256 bytes of the selector, 8.25 KB)
 //   MORPH     (jh_morphology, as BLUR: the two planes of order keys between its three passes, each (rect height + 2 radius_y) x
 //              rect width x 16 B; it only grows and nothing else writes it, so a captured call stays valid)
+//   DISTANCE  (jh_distance, as MORPH: the one or two planes of uint16_t run lengths between its two passes, each rect height x
+//              (rect width + 2 max_distance) x 2 B; it only grows and nothing else writes it, so a captured call stays valid)
 enum {
     JH_SCR_SCAN_TMP = 0,
     JH_SCR_A = 1,
@@ -263,7 +265,8 @@ enum {
     JH_SCR_MORPH = 18,          // jh_morphology's intermediate planes
     JH_SCR_LIGHT_TABLES = 19,   // jh_lighting's tables
     JH_SCR_TURB_TABLES = 20,    // jh_turbulence's tables
-    JH_SCR_COUNT = 21
+    JH_SCR_DISTANCE = 21,       // jh_distance's intermediate planes
+    JH_SCR_COUNT = 22
 };
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
@@ -361,7 +364,7 @@ struct JhResampleTables {
     uint32_t region_x;          // float4 slots of LDS a wave of the row pass needs: jh_resample_skew(longest span - 1) + 1
 };
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _turbulence, _displace, _shadow, _perspective, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _turbulence, _displace, _shadow, _perspective, _distance, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses (an image launcher, which takes the views and resolved
 // rectangles of include/jello_image.h: a rectangle that is not inside its image), another negative value (-2) for a failed launch.
@@ -404,6 +407,8 @@ int jh_shadow_launch(hipStream_t stream, jimage_dst dst, int dst_has_content, ji
                      uint32_t flags, int num_cus);
 int jh_perspective_launch(hipStream_t stream, jimage_src src, jimage_rect src_rect, jimage_dst dst, jimage_rect dst_rect, const double* plan, int filter,
                           int edge, int straight, int num_cus);
+struct jh_distance_desc;  // include/jello_hip.h
+int jh_distance_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect rect, const jh_distance_desc* desc, void* tmp, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

@@ -19,7 +19,8 @@ from .imagecalls import (  # noqa: F401
     lighting_tables, TurbulenceKind, TURBULENCE_MAX_OCTAVES, _pair, _turbulence_desc, turbulence_plan, turbulence_tables, DisplaceChannel,
     DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ShadowFlags, SHADOW_MAX_EXTENT, _shadow_desc, shadow_plan, shadow_bounds,
     box_shadow_geometry, PERSPECTIVE_STRAIGHT, PROJECTIVE_IDENTITY, _matrix9, perspective_plan, perspective_bounds, _perspective_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
-    IDENTITY_MATRIX, _color_desc, color_tables, composite_clip,
+    IDENTITY_MATRIX, _color_desc, color_tables, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, DISTANCE_MAX_RADIUS, _distance_desc,
+    distance_plan,
 )
 from .scene import Compose, Mix
 
@@ -391,6 +392,44 @@ class Engine:
         dst = src_id if dst_id is None else dst_id
         self._check(self.hip.jh_morphology(self.ctx, src_id, dst, ctypes.byref(d)), "morphology", invalid=ValueError)
 
+    def distance(self, src_id, dst_id=None, channel=3, threshold=0.5, which=DistanceWhich.OUTER, edge=DistanceEdge.ZERO, max_distance=1, scale=1.0,
+                 offset=0.0, color=(1.0, 1.0, 1.0, 1.0), rect=None, straight=False):
+        """jh_distance: the Euclidean distance to the shape in the RGBA16F image `src_id`, capped at `max_distance` and put through a
+        linear ramp (the rule: DESIGN.md 5.20), into the image `dst_id` of the same size -- None: in place.  A texel is a seed iff its
+        `channel` (0..3; 3: alpha) is >= `threshold`.  `which`: the distance s to the nearest seed (OUTER), to the nearest non-seed
+        (INNER), or signed, negative inside, zero on the texel edge between the classes (SIGNED).  `edge`: under ZERO every position
+        outside the image is a non-seed, under CLAMP there is none.  `max_distance`: R, an integer in [1, 255]; s is R + 1 where
+        nothing lies within R.  The texel is `color` (premultiplied) times v = clamp(s scale + offset, 0, 1), stored by the store
+        rule, or as it is with `straight` (masks, SDF textures).  jello_amd.distance has the ramps -- outline, inset, glow, sdf --
+        each the keywords of this call.  `rect` = (x, y, width, height) is the rectangle of the destination that is written (None:
+        the whole image); texels outside it keep their bits, seeds outside it count.  Stream-ordered, returns nothing; ValueError
+        for a call the rule refuses."""
+        d = _distance_desc(channel, threshold, which, edge, max_distance, scale, offset, color, rect, straight)
+        dst = src_id if dst_id is None else dst_id
+        self._check(self.hip.jh_distance(self.ctx, src_id, dst, ctypes.byref(d)), "distance", invalid=ValueError)
+
+    def round_outline(self, layer_id, target_id, width, color, scratch_image_id):
+        """outline() with a disc instead of a box, and a width that may be fractional, three calls: distance(layer -> scratch, OUTER,
+        the ramp distance.outline(width), the colour in the descriptor): the coverage of the layer's alpha >= 0.5 grown by a disc of
+        radius `width`, in the outline's colour; composite(scratch -> target); composite(layer -> target).  `layer_id` and
+        `scratch_image_id` are RGBA16F images of one size (the scratch's content is overwritten), `color` = (r, g, b, a), not
+        premultiplied, as outline()'s tint."""
+        from . import distance as ramps
+        r, g, b, a = (float(c) for c in color)
+        self.distance(layer_id, scratch_image_id, color=(r * a, g * a, b * a, a), **ramps.outline(width))
+        self.composite(scratch_image_id, target_id)
+        self.composite(layer_id, target_id)
+
+    def glow(self, layer_id, target_id, radius, color, scratch_image_id, inner=False):
+        """A glow of `radius` texels around a layer (inner: inside it) onto a target, two calls: distance(layer -> scratch, the ramp
+        distance.glow(radius, inner), the colour in the descriptor): `color` at the shape's edge, falling linearly to nothing
+        `radius` away; composite(scratch -> target, Plus) -- or SrcAtop for an inner glow, onto a target that holds the layer.
+        `color` = (r, g, b, a), not premultiplied."""
+        from . import distance as ramps
+        r, g, b, a = (float(c) for c in color)
+        self.distance(layer_id, scratch_image_id, color=(r * a, g * a, b * a, a), **ramps.glow(radius, inner))
+        self.composite(scratch_image_id, target_id, compose=Compose.SrcAtop if inner else Compose.Plus)
+
     def warp(self, src_id, dst_id, matrix, filter=WarpFilter.BILINEAR, edge=WarpEdge.ZERO, src_rect=None, dst_rect=None, premultiplied=True):
         """jh_warp: the rectangle `src_rect` = (x, y, width, height) of the RGBA16F image `src_id` (None: the whole image) under the
         affine map `matrix` = (a, b, c, d, e, f), x' = a x + c y + e, y' = b x + d y + f, into the RGBA16F image `dst_id` (another
@@ -686,7 +725,7 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None, perspective=None):
+                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None, perspective=None, distance=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -737,7 +776,10 @@ class Engine:
         perspective=dict(dst=image id, width=..., height=..., matrix=..., ...) (the other keywords of perspective(), optional; the
         matrix has nine entries) transforms the frame's target into the RGBA16F image `dst` of width x height where warp= would (one
         more launch, nothing to run eagerly first); the conversion of the same capture then reads `dst`.  It is exclusive with
-        resample=, warp= and displace=."""
+        resample=, warp= and displace=.
+        distance=dict(...) (the keywords of distance() but the ids) turns the frame's target into its distance field in place, after
+        the morphology and before the blur (two more launches); a call whose planes are no smaller (distance_plan's scratch_bytes)
+        must have run once eagerly."""
         if sum(step is not None for step in (resample, warp, displace, perspective)) > 1:
             raise ValueError("capture: resample=, warp=, displace= and perspective= are exclusive (each would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
@@ -750,6 +792,8 @@ class Engine:
                 self.shadow(shadow.get("dst", t["id"]), **{k: v for k, v in shadow.items() if k != "dst"})
             if morphology is not None:
                 self.morphology(t["id"], **morphology)
+            if distance is not None:
+                self.distance(t["id"], **distance)
             if blur is not None:
                 self.blur(t["id"], t["width"], t["height"], blur["sigma"], edge=blur.get("edge", BlurEdge.ZERO), rect=blur.get("rect"))
             if composite is not None:

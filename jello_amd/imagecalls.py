@@ -8,7 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CLightingDesc, CLightPlan, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CDistanceDesc, CDistPlan, CLightingDesc, CLightPlan, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
 
 
 def _query(name, twin=False):
@@ -485,6 +485,60 @@ def perspective_bounds(matrix, src_size, filter, dst_size, twin=False):
 
 def _perspective_desc(matrix, filter, edge, src_rect, dst_rect, premultiplied):
     return _warp_family_desc(CPerspectiveDesc, _matrix9(matrix), PERSPECTIVE_STRAIGHT, filter, edge, src_rect, dst_rect, premultiplied)
+
+
+class DistanceWhich(enum.IntEnum):
+    """jh_distance_which: the distance to the nearest seed (OUTER), to the nearest non-seed (INNER), or the signed distance to the
+    texel edge between the two classes, negative inside (SIGNED) -- DESIGN.md 5.20."""
+    OUTER = 0
+    INNER = 1
+    SIGNED = 2
+
+
+class DistanceEdge(enum.IntEnum):
+    """jh_distance_edge: every position outside the image is a non-seed (ZERO: an inner distance ends at the image's border), or no
+    position outside the image exists (CLAMP)."""
+    ZERO = 0
+    CLAMP = 1
+
+
+class DistanceFlags(enum.IntFlag):
+    """jh_distance's flags: STRAIGHT stores f16(color v) as it is -- data images, masks, SDF textures -- instead of by the store rule."""
+    NONE = 0
+    STRAIGHT = 1
+
+
+DISTANCE_MAX_RADIUS = 255  # JH_DISTANCE_MAX_RADIUS
+
+
+def _distance_desc(channel=3, threshold=0.5, which=DistanceWhich.OUTER, edge=DistanceEdge.ZERO, max_distance=1, scale=1.0, offset=0.0,
+                   color=(1.0, 1.0, 1.0, 1.0), rect=None, straight=False):
+    """jh_distance_desc.  What the rule refuses is left for the call to refuse, except a max_distance that does not fit the field."""
+    if int(max_distance) != max_distance or not 0 <= int(max_distance) < 1 << 32:
+        raise ValueError("jh_distance: max_distance is an integer in [1, 255]")
+    with np.errstate(over="ignore"):
+        color = [float(np.float32(v)) for v in color]
+        if len(color) != 4:
+            raise ValueError("jh_distance: the color has four entries (r, g, b, a, premultiplied)")
+        d = CDistanceDesc(int(channel), float(np.float32(threshold)), int(which), int(edge), int(max_distance), float(np.float32(scale)),
+                          float(np.float32(offset)))
+    d.color[:] = color
+    d.flags = int(DistanceFlags.STRAIGHT if straight else DistanceFlags.NONE)
+    d.x, d.y, d.width, d.height = _rect(rect)
+    return d
+
+
+def distance_plan(image_size, twin=False, **keywords):
+    """jh_distance_plan (twin: jl_distance_plan, the host twin): what Engine.distance with these keywords does on an image of
+    `image_size` = (width, height) -- dict(rect = the resolved (x, y, width, height), radius, cap = (radius + 1)^2, planes,
+    plane_columns, plane_rows, scratch_bytes).  It says which eager call has to precede a capture: one whose scratch_bytes are no
+    less.  No GPU needed.  ValueError for a descriptor the rule refuses or a rectangle the image refuses."""
+    d, plan = _distance_desc(**keywords), CDistPlan()
+    if not (0 <= int(image_size[0]) < 1 << 32 and 0 <= int(image_size[1]) < 1 << 32) or \
+            _query("distance_plan", twin)(ctypes.byref(d), int(image_size[0]), int(image_size[1]), ctypes.byref(plan)) != 0:
+        raise ValueError("jh_distance: illegal descriptor or rectangle")
+    return dict(rect=(plan.x, plan.y, plan.width, plan.height), radius=plan.radius, cap=plan.cap, planes=plan.planes,
+                plane_columns=plan.plane_columns, plane_rows=plan.plane_rows, scratch_bytes=int(plan.scratch_bytes))
 
 
 class ColorSpace(enum.IntEnum):

@@ -222,6 +222,25 @@ static void perspective() {
     CHECK(plan2.untouched() && rect2.untouched());
 }
 
+static void distance() {
+    Buf<jh_distance_desc> d(1);
+    memset(d, 0, sizeof(jh_distance_desc));
+    d[0].channel = 3; d[0].threshold = 0.5f; d[0].which = JDIST_SIGNED; d[0].max_distance = 7u; d[0].scale = 1.0f;
+    d[0].x = 3u; d[0].y = 5u; d[0].width = 40u; d[0].height = 20u;
+    Buf<jh_dist_plan> plan(1);
+    CHECK(!jq_distance_plan(d, 100u, 50u, plan) && plan[0].x == 3u && plan[0].y == 5u && plan[0].width == 40u && plan[0].height == 20u && plan[0].radius == 7u &&
+          plan[0].cap == 64u && plan[0].planes == 2u && plan[0].plane_columns == 54u && plan[0].plane_rows == 20u && plan[0].scratch_bytes == 4320u);
+    Buf<jh_dist_plan> plan2(1);
+    CHECK(is(jq_distance_plan(nullptr, 100u, 50u, plan2), "null argument") && is(jq_distance_plan(d, 100u, 50u, nullptr), "null argument"));
+    CHECK(is(jq_distance_plan(d, 42u, 50u, plan2), "the rectangle is not inside the image"));
+    d[0].max_distance = 256u;
+    CHECK(is(jq_distance_plan(d, 100u, 50u, plan2), "max_distance outside [1, 255]"));
+    d[0].max_distance = 7u;
+    d[0].scale = INFINITY;
+    CHECK(is(jq_distance_plan(d, 100u, 50u, plan2), "scale or offset is not finite"));
+    CHECK(plan2.untouched());
+}
+
 static void composite() {
     static const char* const kWhy = "the source rectangle is not inside the source image or is empty in one dimension";
     Buf<uint32_t> out(6);
@@ -243,6 +262,7 @@ int main() {
     displace();
     shadow();
     perspective();
+    distance();
     composite();
     if (g_fail) return 1;
     printf("ok\n");
