@@ -1274,6 +1274,74 @@ typedef struct jh_dist_plan {
 int jh_distance_plan(const jh_distance_desc* desc, uint32_t image_w, uint32_t image_h, jh_dist_plan* plan);
 int jh_distance(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_distance_desc* desc);
 
+/* ---- load: 8-bit surfaces and 8-bit Y'CbCr 4:2:0 frames INTO RGBA16F images (DESIGN.md 5.21 "Load rule") ----
+ * The inverses of jh_blit and jh_blit_yuv: a decoded picture or video frame in device memory becomes an image every image call
+ * takes.  The result is defined byte for byte (include/jello_load.h is the rule's text for the kernels, the queries and their host
+ * twin; tests/load_ref.py restates it in numpy):
+ *   texel     from four 8-bit codes (r, g, b, a) and a transfer:  U(c) = the binary32 nearest to c / 255 (= (float)c / 255.0f);
+ *             L(c) = kSrgbToLinear[c], the decode table of the fine kernel.  Colour = L(c) under an sRGB format or transfer, U(c)
+ *             otherwise; alpha is always U(a).
+ *               JH_LOAD_ALPHA_STRAIGHT        texel_pack(colour, U(a)): RGBA16F images hold straight colour
+ *               JH_LOAD_ALPHA_PREMULTIPLIED   texel_unpremultiply(colour, U(a)), the store rule of DESIGN.md 5.8 (what jh_blit
+ *                                             writes is premultiplied); a = 0 under a non-zero colour gives large values or Inf
+ *               JH_LOAD_ALPHA_OPAQUE          byte 3 is ignored, alpha is 1.0 (BGRX surfaces)
+ *             BGRA formats swap bytes 0 and 2.
+ *   chroma    planes are ceil(w / 2) x ceil(h / 2), laid out as jh_blit_yuv writes them, sample (cx, cy) at luma position
+ *             (2 cx + 1/2, 2 cy + 1/2).  For the texel (x, y) of the frame: cx0 = x >> 1, cx1 = clamp(cx0 + (x odd ? 1 : -1), 0,
+ *             ceil(w / 2) - 1), cy0 and cy1 the same in y.  The sum S is 16 x a code:
+ *               JH_CHROMA_REPLICATE  S = 16 C[cy0][cx0]   (the adjoint of jh_blit_yuv's box)
+ *               JH_CHROMA_BILINEAR   S = 9 C[cy0][cx0] + 3 C[cy0][cx1] + 3 C[cy1][cx0] + C[cy1][cx1]   (the edge sample repeated)
+ *   codes     in integers, with Y' = Y - o (o = 16 limited, 0 full), u = S_cb - 2048, v = S_cr - 2048, the shift arithmetic:
+ *               R = clamp8((16 Ky Y' + Krv v         + 2^19) >> 20)
+ *               G = clamp8((16 Ky Y' + Kgu u + Kgv v + 2^19) >> 20)
+ *               B = clamp8((16 Ky Y' + Kbu u         + 2^19) >> 20)
+ *   tables    round-half-even(exact * 2^16) of 255/219 or 1, 2 (1 - Kr) s, -2 Kb (1 - Kb) / Kg s, -2 Kr (1 - Kr) / Kg s, 2 (1 - Kb) s,
+ *             s = 255/224 or 1 (jello_amd/csrc/load_decode_lut.h, tools/gen_load_tables.py).   (Ky | Krv | Kgu, Kgv | Kbu)
+ *               BT.601 limited   76309 | 104597 | -25675, -53279 | 132201
+ *               BT.601 full      65536 |  91881 | -22553, -46802 | 116130
+ *               BT.709 limited   76309 | 117489 | -13975, -34925 | 138438
+ *               BT.709 full      65536 | 103206 | -12276, -30679 | 121609
+ *             The codes are within 0.51 of the real-valued inverse matrix, clamped; every grey gives R = G = B.
+ *   yuv texel the texel rule on (R, G, B, 255) with the transfer, straight: what jh_load_surface (OPAQUE) makes of those codes.
+ *
+ * jh_load_texel and jh_load_yuv_codes: the rule on batches, host only, no context.  jh_load_texel: format_or_transfer is a
+ * jh_surface_format, or 4 + a jh_yuv_transfer for RGBA-ordered codes under that transfer; rgba holds n pixels of 4 bytes, out gets
+ * 4 n f16 bit patterns (r, g, b, a).  jh_load_yuv_codes: y holds n codes, s_cb and s_cr n sums in [0, 4080], rgb gets 3 n codes.
+ * JH_ERR_INVALID for a null argument or an unknown enum value (or a sum above 4080), the outputs then untouched.
+ *
+ * jh_load_surface: the frame at desc->src -- height rows of 4 * width bytes, desc->pitch apart, in desc->format -- into the rectangle
+ * (x, y, width, height) of dst_image_id; 0 x 0 names the whole image, and the frame has the rectangle's size.  jh_load_yuv: the same
+ * for the planes of a width x height 4:2:0 frame.  dst must be JL_RGBA16_FLOAT.  Texels outside the rectangle keep their bits; a dst
+ * that was never written is cleared to transparent black first (where the rectangle is not the whole image) and then counts as
+ * written.  The source is only read, and never between a row's bytes and its pitch; any pointer and any pitch >= the row's bytes is
+ * legal.  Source memory that overlaps the destination image's is undefined.
+ * Stream-ordered on the context's stream, never waits: ONE kernel launch (plus the fill), no scratch, no resident tables: always
+ * capturable between jh_graph_begin and jh_graph_end (the graph then holds the pointers).  With profiling on each call is one
+ * query, "load_surface" or "load_yuv", with stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band).
+ * JH_ERR_INVALID, with nothing enqueued, each with a message that starts "jh_load_surface: " or "jh_load_yuv: ": a null desc; an
+ * unknown destination id or one that is not RGBA16F; a rectangle that is not inside the image or empty in exactly one dimension; an
+ * unknown format, alpha, layout, matrix, range, transfer or chroma; a null src or required plane; a pitch below the row's bytes; a
+ * band set with jh_set_band. */
+typedef enum jh_load_alpha { JH_LOAD_ALPHA_STRAIGHT = 0, JH_LOAD_ALPHA_PREMULTIPLIED = 1, JH_LOAD_ALPHA_OPAQUE = 2 } jh_load_alpha;
+typedef enum jh_chroma_filter { JH_CHROMA_REPLICATE = 0, JH_CHROMA_BILINEAR = 1 } jh_chroma_filter;
+typedef struct jh_load_surface_desc {
+    int32_t format, alpha;         /* jh_surface_format, jh_load_alpha */
+    const void* src;               /* caller-owned device memory */
+    uint64_t pitch;                /* bytes between the rows */
+    uint32_t x, y, width, height;  /* rectangle of dst that is written = the frame's size; 0 x 0: the whole image */
+} jh_load_surface_desc;
+typedef struct jh_load_yuv_desc {
+    int32_t layout, matrix, range, transfer; /* jh_yuv_layout, jh_yuv_matrix, jh_yuv_range, jh_yuv_transfer */
+    int32_t chroma, reserved;                /* jh_chroma_filter; 0 */
+    const void* plane[3];                    /* caller-owned device memory, as jh_yuv_desc's */
+    uint64_t pitch[3];                       /* bytes between the rows of each plane */
+    uint32_t x, y, width, height;            /* rectangle of dst that is written = the frame's size; 0 x 0: the whole image */
+} jh_load_yuv_desc;
+int jh_load_texel(int format_or_transfer, int alpha, uint64_t n, const uint8_t* rgba, uint16_t* out);
+int jh_load_yuv_codes(int matrix, int range, uint64_t n, const uint8_t* y, const uint16_t* s_cb, const uint16_t* s_cr, uint8_t* rgb);
+int jh_load_surface(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_surface_desc* desc);
+int jh_load_yuv(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_yuv_desc* desc);
+
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);
 /* Waits for the device, writes up to max records (one per dispatch since the last collect), returns the count. */

@@ -16,6 +16,7 @@
 #include "jello_displace.h"
 #include "jello_distance.h"
 #include "jello_lighting.h"
+#include "jello_load.h"
 #include "jello_perspective.h"
 #include "jello_resample.h"
 #include "jello_shadow.h"
@@ -119,6 +120,16 @@ static inline const char* jq_distance_plan(const jh_distance_desc* desc, uint32_
     return jdist_plan(desc, image_w, image_h, plan);
 }
 
+static inline const char* jq_load_texel(int format_or_transfer, int alpha, uint64_t n, const uint8_t* rgba, uint16_t* out) {
+    if (n != 0u && (!rgba || !out)) return "null argument";
+    return jload_texels(format_or_transfer, alpha, n, rgba, out);
+}
+
+static inline const char* jq_load_yuv_codes(int matrix, int range, uint64_t n, const uint8_t* y, const uint16_t* s_cb, const uint16_t* s_cr, uint8_t* rgb) {
+    if (n != 0u && (!y || !s_cb || !s_cr || !rgb)) return "null argument";
+    return jload_yuv_codes(matrix, range, n, y, s_cb, s_cr, rgb);
+}
+
 // (the geometry of jh_composite: out[6] = {sx', sy', dx', dy', w, h}, all zero when nothing is left)
 static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy,
                                             uint32_t dst_w, uint32_t dst_h, uint32_t* out) {
@@ -154,7 +165,10 @@ static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint
     X(perspective_plan, (const double* matrix, double* plan), (matrix, plan))                                                               \
     X(perspective_bounds, (const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), \
       (matrix, src_w, src_h, filter, dst_w, dst_h, rect))                                                                                   \
-    X(distance_plan, (const jh_distance_desc* desc, uint32_t image_w, uint32_t image_h, jh_dist_plan* plan), (desc, image_w, image_h, plan))
+    X(distance_plan, (const jh_distance_desc* desc, uint32_t image_w, uint32_t image_h, jh_dist_plan* plan), (desc, image_w, image_h, plan)) \
+    X(load_texel, (int format_or_transfer, int alpha, uint64_t n, const uint8_t* rgba, uint16_t* out), (format_or_transfer, alpha, n, rgba, out)) \
+    X(load_yuv_codes, (int matrix, int range, uint64_t n, const uint8_t* y, const uint16_t* s_cb, const uint16_t* s_cr, uint8_t* rgb),     \
+      (matrix, range, n, y, s_cb, s_cr, rgb))
 #define JQ_HOST_QUERY_LIST(X)                                                                                                               \
     X(composite_clip,                                                                                                                       \
       (uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w, uint32_t dst_h, \

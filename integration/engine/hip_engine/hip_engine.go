@@ -1190,6 +1190,49 @@ func (e *Engine) Distance(src, dst renderer.ImageProxy, desc DistanceDesc) {
 	e.check(C.jh_distance(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), &d), "distance")
 }
 
+// LoadAlpha is jh_load_alpha: byte 3 of a loaded surface pixel is straight alpha, the alpha the colour has been multiplied by (what
+// RenderToSurface writes), or ignored (BGRX: the texel is opaque).
+type LoadAlpha int32
+
+const (
+	LoadAlphaStraight      LoadAlpha = C.JH_LOAD_ALPHA_STRAIGHT
+	LoadAlphaPremultiplied LoadAlpha = C.JH_LOAD_ALPHA_PREMULTIPLIED
+	LoadAlphaOpaque        LoadAlpha = C.JH_LOAD_ALPHA_OPAQUE
+)
+
+// ChromaFilter is jh_chroma_filter: the chroma sample that covers the texel, or the 9 / 3 / 3 / 1 blend of the four nearest.
+type ChromaFilter int32
+
+const (
+	ChromaReplicate ChromaFilter = C.JH_CHROMA_REPLICATE
+	ChromaBilinear  ChromaFilter = C.JH_CHROMA_BILINEAR
+)
+
+// LoadSurface is jh_load_surface: the 8-bit frame at src (device memory, rows pitch bytes apart, in format) INTO the rectangle
+// (x, y, width, height) of the RGBA16F image dst -- 0 x 0: the whole image; the frame has the rectangle's size -- by the rule of
+// DESIGN.md 5.21 (defined on values: every implementation gives the same bits).  A decoded picture or a screen capture becomes the
+// source of Composite, Warp, Perspective.  Stream-ordered behind the frame, waits for nothing, one kernel launch, no scratch and no
+// tables: always capturable.
+func (e *Engine) LoadSurface(dst renderer.ImageProxy, src unsafe.Pointer, pitch uint64, format SurfaceFormat, alpha LoadAlpha, x, y, width, height uint32) {
+	d := C.jh_load_surface_desc{format: C.int32_t(format), alpha: C.int32_t(alpha), src: src, pitch: C.uint64_t(pitch), x: C.uint32_t(x), y: C.uint32_t(y),
+		width: C.uint32_t(width), height: C.uint32_t(height)}
+	e.check(C.jh_load_surface(e.ctx, C.uint64_t(dst.ID), &d), "load_surface")
+}
+
+// LoadYUV is jh_load_yuv: the 8-bit Y'CbCr 4:2:0 frame in planes (device memory, laid out as RenderToYUV writes them; the third is
+// unused for NV12) INTO the rectangle of the RGBA16F image dst, opaque, by the rule of DESIGN.md 5.21: a decoded video frame becomes
+// the source of Composite, Warp, Perspective.  format.Transfer says whether the R'G'B' codes are sRGB-encoded (decoded to linear)
+// or linear.  Stream-ordered behind the frame, waits for nothing, one kernel launch, no scratch and no tables: always capturable.
+func (e *Engine) LoadYUV(dst renderer.ImageProxy, planes [3]unsafe.Pointer, pitches [3]uint64, format YUVFormat, chroma ChromaFilter, x, y, width, height uint32) {
+	d := C.jh_load_yuv_desc{layout: C.int32_t(format.Layout), matrix: C.int32_t(format.Matrix), _range: C.int32_t(format.Range),
+		transfer: C.int32_t(format.Transfer), chroma: C.int32_t(chroma), x: C.uint32_t(x), y: C.uint32_t(y), width: C.uint32_t(width), height: C.uint32_t(height)}
+	for i := 0; i < 3; i++ {
+		d.plane[i] = planes[i]
+		d.pitch[i] = C.uint64_t(pitches[i])
+	}
+	e.check(C.jh_load_yuv(e.ctx, C.uint64_t(dst.ID), &d), "load_yuv")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

@@ -9,7 +9,7 @@ from .scene import (  # noqa: F401
     Scene, Path, Brush, Stroke, dash, Color, ColorStop, RenderParams, BumpSizes, Fill, Join, Cap, Mix, Compose, Extend, Aa,
 )
 from .engine import (  # noqa: F401
-    Host, Recording, Engine, ImageFormat, Surface, YuvLayout, YuvMatrix, YuvRange, YuvTransfer, BlurEdge, blur_taps, ResampleFilter, resample_taps, MorphOp, MorphEdge, WarpFilter, WarpEdge, warp_plan, warp_bounds, ConvolveEdge, ConvolveMode, convolve_weights, LightKind, LightSource, lighting_plan, lighting_tables, TurbulenceKind, turbulence_plan, turbulence_tables, DisplaceChannel, displace_offset, ShadowFlags, shadow_plan, shadow_bounds, box_shadow_geometry, perspective_plan, perspective_bounds, ColorSpace, ColorFunc, color_tables, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, distance_plan, STAGE_NAMES, CMD,
+    Host, Recording, Engine, ImageFormat, Surface, YuvLayout, YuvMatrix, YuvRange, YuvTransfer, BlurEdge, blur_taps, ResampleFilter, resample_taps, MorphOp, MorphEdge, WarpFilter, WarpEdge, warp_plan, warp_bounds, ConvolveEdge, ConvolveMode, convolve_weights, LightKind, LightSource, lighting_plan, lighting_tables, TurbulenceKind, turbulence_plan, turbulence_tables, DisplaceChannel, displace_offset, ShadowFlags, shadow_plan, shadow_bounds, box_shadow_geometry, perspective_plan, perspective_bounds, ColorSpace, ColorFunc, color_tables, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, distance_plan, LoadAlpha, ChromaFilter, load_texels, load_yuv_codes, STAGE_NAMES, CMD,
 )
 from . import colorfilter  # noqa: F401,E402
 from . import convolution  # noqa: F401,E402

@@ -255,6 +255,19 @@ class CDistPlan(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("scratch_bytes", ctypes.c_uint64)]
 
 
+class CLoadSurfaceDesc(ctypes.Structure):
+    """jh_load_surface_desc (include/jello_hip.h)."""
+    _fields_ = [("format", ctypes.c_int32), ("alpha", ctypes.c_int32), ("src", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("x", ctypes.c_uint32),
+                ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
+
+
+class CLoadYuvDesc(ctypes.Structure):
+    """jh_load_yuv_desc (include/jello_hip.h)."""
+    _fields_ = [("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32), ("transfer", ctypes.c_int32),
+                ("chroma", ctypes.c_int32), ("reserved", ctypes.c_int32), ("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_uint64 * 3),
+                ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -340,6 +353,8 @@ def _declare(L):
         "perspective_plan": [dp, dp],
         "perspective_bounds": [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)],
         "distance_plan": [ctypes.POINTER(CDistanceDesc), u32, u32, ctypes.POINTER(CDistPlan)],
+        "load_texel": [ci, ci, u64, vp, vp],
+        "load_yuv_codes": [ci, ci, u64, vp, vp, vp, vp],
     }
     for name, argtypes in queries.items():
         getattr(L, "jl_" + name).argtypes = argtypes
@@ -394,6 +409,8 @@ def _declare(L):
     hip.jh_shadow.argtypes = [vp, u64, ctypes.POINTER(CShadowDesc)]
     hip.jh_perspective.argtypes = [vp, u64, u64, ctypes.POINTER(CPerspectiveDesc)]
     hip.jh_distance.argtypes = [vp, u64, u64, ctypes.POINTER(CDistanceDesc)]
+    hip.jh_load_surface.argtypes = [vp, u64, ctypes.POINTER(CLoadSurfaceDesc)]
+    hip.jh_load_yuv.argtypes = [vp, u64, ctypes.POINTER(CLoadYuvDesc)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

@@ -1173,7 +1173,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow, perspective, distance ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow, perspective, distance, load ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1939,6 +1939,40 @@ int jh_perspective(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, co
         if (int rc = warp_family_views(ctx, src, dst, &s, d, &v)) return rc;
         return launch_status(ctx, "jh_perspective",
                              jh_perspective_launch(ctx->stream, v.from, s, v.to, d, plan, desc->filter, desc->edge, (desc->flags & JH_PERSPECTIVE_STRAIGHT) != 0u, ctx->num_cus));
+    });
+}
+
+// load (include/jello_hip.h "load"; the descriptors' legality, the tables and the texel: include/jello_load.h; kernels_load.hip)
+int jh_load_surface(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_surface_desc* desc) {
+    static_assert(JH_LOAD_ALPHA_STRAIGHT == JLOAD_ALPHA_STRAIGHT && JH_LOAD_ALPHA_PREMULTIPLIED == JLOAD_ALPHA_PREMULTIPLIED &&
+                      JH_LOAD_ALPHA_OPAQUE == JLOAD_ALPHA_OPAQUE && JH_CHROMA_REPLICATE == JLOAD_CHROMA_REPLICATE && JH_CHROMA_BILINEAR == JLOAD_CHROMA_BILINEAR,
+                  "the C ABI's values are the rule's");
+    Alloc* dst = nullptr;
+    if (int rc = image_call_image(ctx, "jh_load_surface", desc, dst_image_id, "a band's rows are one rank's, the frame is the whole rectangle's", &dst)) return rc;
+    if (const char* why = jload_surface_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_surface: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_load_surface", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (const char* why = jload_surface_pitch_error(desc, r.w)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_surface: ") + why);
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    return post_render_call(ctx, "load_surface", [&] {
+        if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
+        return launch_status(ctx, "jh_load_surface",
+                             jh_load_surface_launch(ctx->stream, desc->src, desc->pitch, {dst->ptr, dst->width, dst->height}, r, desc->format, desc->alpha, ctx->num_cus));
+    });
+}
+
+int jh_load_yuv(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_yuv_desc* desc) {
+    Alloc* dst = nullptr;
+    if (int rc = image_call_image(ctx, "jh_load_yuv", desc, dst_image_id, "a band's rows are one rank's, the frame is the whole rectangle's", &dst)) return rc;
+    if (const char* why = jload_yuv_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_yuv: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_load_yuv", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
+    if (const char* why = jload_yuv_pitch_error(desc, r.w)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_yuv: ") + why);
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    return post_render_call(ctx, "load_yuv", [&] {
+        if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
+        return launch_status(ctx, "jh_load_yuv", jh_load_yuv_launch(ctx->stream, desc->plane, desc->pitch, {dst->ptr, dst->width, dst->height}, r, desc->layout,
+                                                                    desc->matrix, desc->range, desc->transfer, desc->chroma, ctx->num_cus));
     });
 }
 

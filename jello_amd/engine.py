@@ -20,7 +20,7 @@ from .imagecalls import (  # noqa: F401
     DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ShadowFlags, SHADOW_MAX_EXTENT, _shadow_desc, shadow_plan, shadow_bounds,
     box_shadow_geometry, PERSPECTIVE_STRAIGHT, PROJECTIVE_IDENTITY, _matrix9, perspective_plan, perspective_bounds, _perspective_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
     IDENTITY_MATRIX, _color_desc, color_tables, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, DISTANCE_MAX_RADIUS, _distance_desc,
-    distance_plan,
+    distance_plan, LoadAlpha, ChromaFilter, LOAD_TRANSFER, _load_surface_desc, _load_yuv_desc, _surface_array_source, _yuv_array_source, load_texels, load_yuv_codes,
 )
 from .scene import Compose, Mix
 
@@ -82,6 +82,9 @@ _DASH_INDEX_BUFFER_ID = 0x44415348494E4400
 DASH_EL = np.dtype([("kind", "<u4"), ("p", "<f4", 6)])  # jh_dash_out_el, 28 bytes
 # a context buffer that blit_yuv / render_to_yuv convert into when the caller passes no planes (it only grows)
 _YUV_BUFFER_ID = 0x5955565F4F555400
+# context buffers that load_surface / load_yuv upload host arrays into before they convert them (they only grow)
+_LOAD_SURFACE_BUFFER_ID = 0x4C4F41445F535200
+_LOAD_YUV_BUFFER_ID = 0x4C4F41445F595500
 
 
 class CMD:
@@ -335,6 +338,58 @@ class Engine:
                                             ctypes.byref(attempts))
         frame = self._frame(h, bump, attempts, "render_to_yuv")
         return (None if own is None else self._download_yuv(params.width, params.height, layout, own),) + frame
+
+    def _upload_own(self, buffer_id, host):
+        """`host` (uint8, contiguous) into the engine's own buffer `buffer_id`; returns its device pointer."""
+        self._check(self.hip.jh_upload(self.ctx, buffer_id, host.ctypes.data, host.size), "upload")
+        return self.hip.jh_buffer_device_ptr(self.ctx, buffer_id)
+
+    def load_surface(self, dst_id, pixels, fmt, alpha=LoadAlpha.STRAIGHT, rect=None, pitch=None):
+        """jh_load_surface: an 8-bit frame in the Surface format `fmt` INTO the RGBA16F image `dst_id` (the rule: DESIGN.md 5.21) --
+        a decoded picture or a screen capture as the source of composite(), warp(), place_layer() ...  `pixels` is an (H, W, 4)
+        uint8 array, uploaded to a buffer of the engine's own first, or a device pointer to rows `pitch` bytes apart (None: 4 x
+        the rectangle's width).  `alpha`: byte 3 is straight alpha, the alpha the colour is premultiplied by (what blit() writes),
+        or ignored (LoadAlpha.OPAQUE).  `rect` = (x, y, width, height) is the rectangle of dst the frame fills and has the size of
+        (None: for an array (0, 0, W, H) of the array's own size -- the call never reads more than was uploaded, and an array
+        larger than the image is refused; for a device pointer the whole image, with a pitch given).  Texels outside it keep
+        their bits.  One launch, no scratch: always capturable.  Stream-ordered, returns nothing; ValueError for a call the rule
+        refuses."""
+        if isinstance(pixels, np.ndarray):
+            source = _surface_array_source(pixels, rect)
+            if source is None:
+                return
+            host, pitch, rect = source
+            src = self._upload_own(_LOAD_SURFACE_BUFFER_ID, host)
+        else:
+            src = pixels
+            if pitch is None:
+                if rect is None:
+                    raise ValueError("jh_load_surface: a device pointer needs a pitch or a rectangle")
+                pitch = 4 * int(rect[2])
+        d = _load_surface_desc(fmt, alpha, src, pitch, rect)
+        self._check(self.hip.jh_load_surface(self.ctx, dst_id, ctypes.byref(d)), "load_surface", invalid=ValueError)
+
+    def load_yuv(self, dst_id, planes, layout=YuvLayout.NV12, matrix=YuvMatrix.BT709, range=YuvRange.LIMITED, transfer=YuvTransfer.NONE,
+                 chroma=ChromaFilter.BILINEAR, rect=None):
+        """jh_load_yuv: an 8-bit Y'CbCr 4:2:0 frame INTO the RGBA16F image `dst_id`, opaque (the rule: DESIGN.md 5.21) -- a decoded
+        video frame as the source of composite(), warp(), project_layer() ...  `planes` is either the uint8 arrays as blit_yuv()
+        returns them -- (Y (H, W), CbCr (ceil(H/2), ceil(W/2), 2)) for NV12, (Y, Cb, Cr) for I420 -- uploaded to a buffer of the
+        engine's own first, or [(device pointer, pitch)] per plane.  `matrix` and `range` name the coefficients, `transfer` whether
+        the R'G'B' codes are sRGB-encoded (YuvTransfer.SRGB: decoded to linear) or linear; `chroma` how the half-resolution planes
+        are read.  `rect` = (x, y, width, height) is the rectangle of dst the frame fills and has the size of (None: for arrays
+        (0, 0, W, H) of the luma plane's own size -- the call never reads more than was uploaded, and a frame larger than the image
+        is refused; for device pointers the whole image).  One launch, no scratch: always capturable.  Stream-ordered, returns
+        nothing; ValueError for a call the rule refuses."""
+        planes = list(planes)
+        if any(isinstance(p, np.ndarray) for p in planes):
+            source = _yuv_array_source(planes, layout, rect)
+            if source is None:
+                return
+            host, placed, rect = source
+            base = self._upload_own(_LOAD_YUV_BUFFER_ID, host)
+            planes = [(base + o, pitch) for o, pitch in placed]
+        d = _load_yuv_desc(layout, matrix, range, transfer, chroma, planes, rect)
+        self._check(self.hip.jh_load_yuv(self.ctx, dst_id, ctypes.byref(d)), "load_yuv", invalid=ValueError)
 
     def blur(self, image_id, width, height, sigma, dst_image_id=None, edge=BlurEdge.ZERO, rect=None):
         """jh_blur: the Gaussian blur (the rule: DESIGN.md 5.7) of the RGBA16F image `image_id` into `dst_image_id` -- None: in
@@ -725,7 +780,8 @@ class Engine:
         return out
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
-                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None, perspective=None, distance=None):
+                morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None, perspective=None, distance=None,
+                load_surface=None, load_yuv=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -779,13 +835,29 @@ class Engine:
         resample=, warp= and displace=.
         distance=dict(...) (the keywords of distance() but the ids) turns the frame's target into its distance field in place, after
         the morphology and before the blur (two more launches); a call whose planes are no smaller (distance_plan's scratch_bytes)
-        must have run once eagerly."""
+        must have run once eagerly.
+        load_surface=dict(dst=image id, pixels=device pointer, fmt=..., ...) and load_yuv=dict(dst=image id, planes=[(device pointer,
+        pitch)], ...) (the other keywords of load_surface() and load_yuv(), optional; device memory only: a capture cannot upload)
+        convert a frame into the RGBA16F image `dst` right after the frame and before turbulence= (one more launch each, nothing to
+        run eagerly first), so that composite=dict(src=dst, ...) of the same capture lays the loaded frame over the rendered one.  The
+        graph holds the pointers: a replay converts what they hold then."""
+        for name, step, key in (("load_surface", load_surface, "pixels"), ("load_yuv", load_yuv, "planes")):
+            if step is None:
+                continue
+            if "dst" not in step or key not in step:
+                raise ValueError("capture: %s= needs dst= and %s=" % (name, key))
+            if isinstance(step[key], np.ndarray) or (key == "planes" and any(isinstance(p, np.ndarray) for p in step[key])):
+                raise ValueError("capture: %s= takes device memory, not arrays (a capture cannot upload)" % name)
         if sum(step is not None for step in (resample, warp, displace, perspective)) > 1:
             raise ValueError("capture: resample=, warp=, displace= and perspective= are exclusive (each would feed the conversion)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
             t = recording.target
+            if load_surface is not None:
+                self.load_surface(load_surface["dst"], **{k: v for k, v in load_surface.items() if k != "dst"})
+            if load_yuv is not None:
+                self.load_yuv(load_yuv["dst"], **{k: v for k, v in load_yuv.items() if k != "dst"})
             if turbulence is not None:
                 self.turbulence(turbulence["dst"], **{k: v for k, v in turbulence.items() if k != "dst"})
             if shadow is not None:

@@ -8,7 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CDistanceDesc, CDistPlan, CLightingDesc, CLightPlan, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CDistanceDesc, CDistPlan, CLightingDesc, CLightPlan, CLoadSurfaceDesc, CLoadYuvDesc, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
 
 
 def _query(name, twin=False):
@@ -539,6 +539,123 @@ def distance_plan(image_size, twin=False, **keywords):
         raise ValueError("jh_distance: illegal descriptor or rectangle")
     return dict(rect=(plan.x, plan.y, plan.width, plan.height), radius=plan.radius, cap=plan.cap, planes=plan.planes,
                 plane_columns=plan.plane_columns, plane_rows=plan.plane_rows, scratch_bytes=int(plan.scratch_bytes))
+
+
+class LoadAlpha(enum.IntEnum):
+    """jh_load_alpha: what byte 3 of a loaded surface pixel is -- straight alpha beside straight colour, the alpha
+    the colour has been multiplied by (what blit() writes), or nothing (BGRX: the texel is opaque)."""
+    STRAIGHT = 0
+    PREMULTIPLIED = 1
+    OPAQUE = 2
+
+
+class ChromaFilter(enum.IntEnum):
+    """jh_chroma_filter: how load_yuv reads the half-resolution chroma planes -- the sample that covers the texel (REPLICATE, the
+    adjoint of blit_yuv's box), or the 9 / 3 / 3 / 1 blend of the four nearest, centre-sited, the edge sample repeated (BILINEAR)."""
+    REPLICATE = 0
+    BILINEAR = 1
+
+
+LOAD_TRANSFER = 4  # jh_load_texel's format_or_transfer: 4 + a YuvTransfer names RGBA codes under that transfer
+
+
+def _load_surface_desc(fmt, alpha, src, pitch, rect):
+    x, y, w, h = _rect(rect)
+    return CLoadSurfaceDesc(int(fmt), int(alpha), src, int(pitch), x, y, w, h)
+
+
+def _load_yuv_desc(layout, matrix, rng, transfer, chroma, planes, rect):
+    """jh_load_yuv_desc; `planes` = [(device pointer, pitch)] per plane."""
+    d = CLoadYuvDesc(int(layout), int(matrix), int(rng), int(transfer), int(chroma), 0)
+    if len(planes) > 3:
+        raise ValueError("jh_load_yuv: at most three planes")
+    for i, (ptr, pitch) in enumerate(planes):
+        d.plane[i], d.pitch[i] = ptr, int(pitch)
+    d.x, d.y, d.width, d.height = _rect(rect)
+    return d
+
+
+def _frame_rect(rect, w, h, who):
+    """The rectangle of a frame given as host arrays of w x h texels: `rect` where it has the frame's size, (0, 0, w, h) for None --
+    never 0 x 0, which would name the whole image and let the call read more than was uploaded."""
+    if rect is None:
+        return (0, 0, w, h)
+    if len(rect) != 4 or (int(rect[2]), int(rect[3])) != (w, h):
+        raise ValueError("%s: the rectangle has the size of the frame" % who)
+    return tuple(int(v) for v in rect)
+
+
+def _surface_array_source(pixels, rect):
+    """What Engine.load_surface uploads and describes for an (H, W, 4) uint8 array: (bytes uint8 [H * W * 4], pitch, rect), rect
+    always of the array's size; None for an array without texels."""
+    px = np.ascontiguousarray(pixels, np.uint8)
+    if px.ndim != 3 or px.shape[2] != 4:
+        raise ValueError("jh_load_surface: pixels is an (H, W, 4) uint8 array or a device pointer")
+    h, w = px.shape[:2]
+    rect = _frame_rect(rect, w, h, "jh_load_surface")
+    return None if w * h == 0 else (px.reshape(-1), 4 * w, rect)
+
+
+def _yuv_plane_shapes(width, height, layout):
+    """[(rows, bytes per row)] of the planes of a width x height frame: Y, then CbCr (NV12: layout 0) or Cb and Cr (I420)."""
+    cw, ch = (width + 1) // 2, (height + 1) // 2
+    return [(height, width), (ch, 2 * cw)] if int(layout) == 0 else [(height, width), (ch, cw), (ch, cw)]
+
+
+def _yuv_array_source(planes, layout, rect):
+    """What Engine.load_yuv uploads and describes for planes given as uint8 arrays: (bytes uint8, [(offset, pitch)] per plane, rect),
+    the planes one after the other with tightly packed rows, each starting at a multiple of 16, rect always of the luma plane's size;
+    None for a frame without texels."""
+    if not all(isinstance(a, np.ndarray) for a in planes):
+        raise ValueError("jh_load_yuv: the planes are all arrays or all (device pointer, pitch)")
+    arrays = [np.ascontiguousarray(a, np.uint8) for a in planes]
+    if not arrays or arrays[0].ndim != 2 or any(a.ndim not in (2, 3) for a in arrays) or int(layout) not in (0, 1):
+        raise ValueError("jh_load_yuv: the planes are two-dimensional uint8 arrays (NV12's chroma may be (rows, samples, 2)) of layout NV12 or I420")
+    h, w = arrays[0].shape
+    if w * h and [a.reshape(a.shape[0], -1).shape for a in arrays] != _yuv_plane_shapes(w, h, layout):
+        raise ValueError("jh_load_yuv: the planes do not have the shapes of a frame of the luma plane's size in this layout")
+    rect = _frame_rect(rect, w, h, "jh_load_yuv")
+    if w * h == 0:
+        return None
+    offs, off = [], 0
+    for a in arrays:
+        offs.append(off)
+        off += (a.size + 15) & ~15
+    host = np.zeros(off, np.uint8)
+    for a, o in zip(arrays, offs):
+        host[o:o + a.size] = a.reshape(-1)
+    return host, [(o, b) for o, (_, b) in zip(offs, _yuv_plane_shapes(w, h, layout))], rect
+
+
+def load_texels(pixels, fmt=None, alpha=LoadAlpha.STRAIGHT, transfer=None, twin=False):
+    """jh_load_texel (twin: jl_load_texel, the host twin): the RGBA16F texels of the load rule for `pixels`, a uint8
+    array (..., 4) -- in the byte order of the Surface format `fmt`, or, with `transfer` (a YuvTransfer) in its place, RGBA codes
+    under that transfer.  Returns the f16 bit patterns, uint16 of the same shape.  No GPU needed.  ValueError for an unknown
+    format, transfer or alpha."""
+    if (fmt is None) == (transfer is None):
+        raise ValueError("jh_load_texel: one of fmt and transfer")
+    if not 0 <= int(transfer if fmt is None else fmt) < (2 if fmt is None else LOAD_TRANSFER):
+        raise ValueError("jh_load_texel: unknown surface format or transfer")
+    px = np.ascontiguousarray(pixels, np.uint8)
+    if px.ndim < 1 or px.shape[-1] != 4:
+        raise ValueError("jh_load_texel: pixels of four bytes")
+    out = np.zeros(px.shape, np.uint16)
+    if _query("load_texel", twin)(int(fmt) if transfer is None else LOAD_TRANSFER + int(transfer), int(alpha), px.size // 4, px.ctypes.data, out.ctypes.data) != 0:
+        raise ValueError("jh_load_texel: unknown surface format, transfer or alpha mode")
+    return out
+
+
+def load_yuv_codes(y, s_cb, s_cr, matrix, range, twin=False):
+    """jh_load_yuv_codes (twin: jl_load_yuv_codes): the R'G'B' codes of the load rule for luma codes `y` and chroma sums `s_cb`,
+    `s_cr` (16 x a code, 0 .. 4080), arrays of one shape, under a YuvMatrix and YuvRange: uint8 of shape (..., 3).  No GPU needed.
+    ValueError for an unknown matrix or range or a sum above 4080."""
+    yy, cb, cr = np.ascontiguousarray(y, np.uint8), np.ascontiguousarray(s_cb, np.uint16), np.ascontiguousarray(s_cr, np.uint16)
+    if not (yy.shape == cb.shape == cr.shape):
+        raise ValueError("jh_load_yuv_codes: y, s_cb and s_cr have one shape")
+    out = np.zeros(yy.shape + (3,), np.uint8)
+    if _query("load_yuv_codes", twin)(int(matrix), int(range), yy.size, yy.ctypes.data, cb.ctypes.data, cr.ctypes.data, out.ctypes.data) != 0:
+        raise ValueError("jh_load_yuv_codes: unknown matrix or range, or a chroma sum above 4080")
+    return out
 
 
 class ColorSpace(enum.IntEnum):

@@ -251,7 +251,34 @@ static void composite() {
     CHECK(out2.untouched());
 }
 
+static void load() {
+    Buf<uint8_t> px(8);
+    for (int i = 0; i < 8; i++) px[i] = (uint8_t)(31 * i + 7);
+    Buf<uint16_t> out(8);
+    CHECK(!jq_load_texel(JH_SURFACE_BGRA8_SRGB, JH_LOAD_ALPHA_PREMULTIPLIED, 2u, px, out) && !out.untouched());
+    CHECK(!jq_load_texel(4 + JH_YUV_TRANSFER_SRGB, JH_LOAD_ALPHA_OPAQUE, 2u, px, out) && out[3] == 0x3c00u && out[7] == 0x3c00u);
+    CHECK(!jq_load_texel(0, 0, 0u, nullptr, nullptr));
+    Buf<uint16_t> out2(8);
+    CHECK(is(jq_load_texel(0, 0, 2u, nullptr, out2), "null argument") && is(jq_load_texel(0, 0, 2u, px, nullptr), "null argument"));
+    CHECK(is(jq_load_texel(6, 0, 2u, px, out2), "unknown surface format or transfer") && is(jq_load_texel(0, 3, 2u, px, out2), "unknown alpha mode"));
+    CHECK(out2.untouched());
+    Buf<uint8_t> y(3), rgb(9);
+    Buf<uint16_t> s_cb(3), s_cr(3);
+    y[0] = 235; y[1] = 63; y[2] = 16;
+    s_cb[0] = 2048; s_cb[1] = 16 * 102; s_cb[2] = 4080;
+    s_cr[0] = 2048; s_cr[1] = 16 * 240; s_cr[2] = 0;
+    CHECK(!jq_load_yuv_codes(JH_YUV_BT709, JH_YUV_LIMITED, 3u, y, s_cb, s_cr, rgb) && rgb[0] == 255 && rgb[1] == 255 && rgb[2] == 255 && rgb[3] == 255 &&
+          rgb[4] == 1 && rgb[5] == 0);
+    Buf<uint8_t> rgb2(9);
+    CHECK(is(jq_load_yuv_codes(2, 0, 3u, y, s_cb, s_cr, rgb2), "unknown matrix or range") && is(jq_load_yuv_codes(0, 0, 3u, y, s_cb, s_cr, nullptr), "null argument") &&
+          is(jq_load_yuv_codes(0, 0, 3u, nullptr, s_cb, s_cr, rgb2), "null argument"));
+    s_cr[2] = 4081;
+    CHECK(is(jq_load_yuv_codes(0, 0, 3u, y, s_cb, s_cr, rgb2), "a chroma sum above 16 * 255"));
+    CHECK(rgb2.untouched());
+}
+
 int main() {
+    load();
     blur();
     resample();
     color();
