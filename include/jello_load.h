@@ -1,5 +1,5 @@
 // jello_load.h -- the load rule (DESIGN.md 5.21 "Load rule"): 8-bit surfaces and 8-bit Y'CbCr 4:2:0 frames into RGBA16F images, the
-// inverse of jh_blit and jh_blit_yuv.  Which descriptor is legal (its rectangle apart: jello_image.h), the coefficient rows, and -- the
+// inverse of jh_blit and jh_blit_yuv.  Which descriptor is legal (rectangle: jello_image.h; frame: jello_frame.h), the coefficient rows, and -- the
 // one text the kernels (jello_amd/csrc/kernels_load.hip), the library's queries and their host twin (include/jello_queries.h) and the
 // stand-alone check (tools/load_check.cpp) all compile -- the chroma sum, the codes and the texel.  tests/load_ref.py restates the
 // rule from the text below and includes nothing of this file.
@@ -28,7 +28,7 @@
 #include <string.h>
 
 #include "jello_color.h"  // jcolor_f16_bits: binary64 to f16 on the host
-#include "jello_hip.h"
+#include "jello_frame.h"  // what a surface and a 4:2:0 frame are: formats, enums, planes, pitches, clamp8
 #include "jello_image.h"
 
 #if defined(__HIPCC__)
@@ -38,12 +38,6 @@
 #endif
 #define JLOAD_TABLE static constexpr
 #include "../jello_amd/csrc/load_decode_lut.h"
-
-#define JLOAD_ALPHA_STRAIGHT 0
-#define JLOAD_ALPHA_PREMULTIPLIED 1
-#define JLOAD_ALPHA_OPAQUE 2
-#define JLOAD_CHROMA_REPLICATE 0
-#define JLOAD_CHROMA_BILINEAR 1
 
 // ---- the pieces ----
 
@@ -69,8 +63,6 @@ JLOAD_HD uint16_t jload_f16(float v) {
 }
 JLOAD_HD float jload_unorm(uint32_t c) { return (float)c / 255.0f; }                 // U(c)
 JLOAD_HD float jload_linear(uint32_t c) { return jload_bits_f32(kLoadSrgbF32[c]); }  // L(c)
-JLOAD_HD bool jload_format_srgb(int format) { return format == JH_SURFACE_RGBA8_SRGB || format == JH_SURFACE_BGRA8_SRGB; }
-JLOAD_HD bool jload_format_bgra(int format) { return format == JH_SURFACE_BGRA8_UNORM || format == JH_SURFACE_BGRA8_SRGB; }
 
 // A texel is the two words of an RGBA16F texel: x = g << 16 | r, y = a << 16 | b.  The codes (r, g, b, a) are in RGBA order: the
 // caller has swapped a BGRA pixel's bytes 0 and 2.
@@ -92,8 +84,8 @@ JLOAD_HD void jload_texel_premultiplied(float rv, float gv, float bv, float av, 
 }
 // The texel rule whole, from the committed tables.
 JLOAD_HD void jload_texel(bool srgb, int alpha, uint32_t r, uint32_t g, uint32_t b, uint32_t a, uint32_t* x, uint32_t* y) {
-    if (alpha != JLOAD_ALPHA_PREMULTIPLIED)
-        jload_texel_tables(srgb ? kLoadSrgbF16 : kLoadUnormF16, kLoadUnormF16, alpha == JLOAD_ALPHA_OPAQUE, r, g, b, a, x, y);
+    if (alpha != JH_LOAD_ALPHA_PREMULTIPLIED)
+        jload_texel_tables(srgb ? kLoadSrgbF16 : kLoadUnormF16, kLoadUnormF16, alpha == JH_LOAD_ALPHA_OPAQUE, r, g, b, a, x, y);
     else if (srgb)
         jload_texel_premultiplied(jload_linear(r), jload_linear(g), jload_linear(b), jload_unorm(a), x, y);
     else
@@ -109,7 +101,7 @@ JLOAD_HD uint32_t jload_chroma_other(uint32_t x, uint32_t n) {
 }
 // S of the four samples c00 = C[cy0][cx0], c01 = C[cy0][cx1], c10 = C[cy1][cx0], c11 = C[cy1][cx1].
 JLOAD_HD int32_t jload_chroma_sum(int chroma, int32_t c00, int32_t c01, int32_t c10, int32_t c11) {
-    return chroma == JLOAD_CHROMA_BILINEAR ? 9 * c00 + 3 * c01 + 3 * c10 + c11 : 16 * c00;
+    return chroma == JH_CHROMA_BILINEAR ? 9 * c00 + 3 * c01 + 3 * c10 + c11 : 16 * c00;
 }
 JLOAD_HD int32_t jload_mul(int32_t a, int32_t b) {  // both operands within 24 bits with their sign, the product within 32
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -118,65 +110,40 @@ JLOAD_HD int32_t jload_mul(int32_t a, int32_t b) {  // both operands within 24 b
     return a * b;
 #endif
 }
-JLOAD_HD uint32_t jload_clamp8(int32_t v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 // The codes of (Y, S_cb, S_cr) under the row k = {Ky, Krv, Kgu, Kgv, Kbu} and the luma offset `off`, as r | g << 8 | b << 16.
 JLOAD_HD uint32_t jload_codes(const int32_t* k, int32_t off, int32_t y, int32_t s_cb, int32_t s_cr) {
     const int32_t u = s_cb - 2048, v = s_cr - 2048;
     const int32_t luma = jload_mul(k[0], 16 * (y - off)) + (1 << 19);
-    const uint32_t r = jload_clamp8((luma + jload_mul(k[1], v)) >> 20);
-    const uint32_t g = jload_clamp8((luma + jload_mul(k[2], u) + jload_mul(k[3], v)) >> 20);
-    const uint32_t b = jload_clamp8((luma + jload_mul(k[4], u)) >> 20);
+    const uint32_t r = jframe_clamp8((luma + jload_mul(k[1], v)) >> 20);
+    const uint32_t g = jframe_clamp8((luma + jload_mul(k[2], u) + jload_mul(k[3], v)) >> 20);
+    const uint32_t b = jframe_clamp8((luma + jload_mul(k[4], u)) >> 20);
     return r | (g << 8) | (b << 16);
 }
 
 // ---- the host half ----
 
-static inline bool jload_yuv_enums_ok(int matrix, int range) {
-    return (matrix == JH_YUV_BT601 || matrix == JH_YUV_BT709) && (range == JH_YUV_LIMITED || range == JH_YUV_FULL);
-}
-static inline bool jload_alpha_ok(int alpha) { return alpha == JLOAD_ALPHA_STRAIGHT || alpha == JLOAD_ALPHA_PREMULTIPLIED || alpha == JLOAD_ALPHA_OPAQUE; }
-static inline bool jload_format_ok(int format) { return format >= JH_SURFACE_RGBA8_UNORM && format <= JH_SURFACE_BGRA8_SRGB; }
-
-// nullptr for a legal descriptor (its rectangle apart: jimage_rect_check; the pitch: jload_surface_pitch_error), else what is wrong with it.
+static inline bool jload_alpha_ok(int alpha) { return alpha == JH_LOAD_ALPHA_STRAIGHT || alpha == JH_LOAD_ALPHA_PREMULTIPLIED || alpha == JH_LOAD_ALPHA_OPAQUE; }
+// nullptr for a legal descriptor, else what is wrong with it -- its rectangle apart (jimage_rect_check) and its pitches, which are judged against that rectangle's width (jello_frame.h).
 static inline const char* jload_surface_desc_error(const jh_load_surface_desc* d) {
-    if (!jload_format_ok(d->format)) return "unknown surface format";
+    if (const char* why = jframe_surface_format_error(d->format)) return why;
     if (!jload_alpha_ok(d->alpha)) return "unknown alpha mode";
     if (!d->src) return "null src";
     return nullptr;
 }
-static inline const char* jload_surface_pitch_error(const jh_load_surface_desc* d, uint32_t rect_w) {
-    return d->pitch < 4ull * rect_w ? "pitch below 4 * width" : nullptr;
-}
-static inline int jload_yuv_planes(int layout) { return layout == JH_YUV_NV12 ? 2 : 3; }
-// The bytes of a row of plane i of a frame w texels wide.
-static inline uint64_t jload_yuv_row_bytes(int layout, int i, uint32_t w) {
-    const uint64_t cw = ((uint64_t)w + 1u) / 2u;
-    return i == 0 ? w : (layout == JH_YUV_NV12 ? 2u * cw : cw);
-}
 static inline const char* jload_yuv_desc_error(const jh_load_yuv_desc* d) {
-    if (d->layout != JH_YUV_NV12 && d->layout != JH_YUV_I420) return "unknown layout";
-    if (d->matrix != JH_YUV_BT601 && d->matrix != JH_YUV_BT709) return "unknown matrix";
-    if (d->range != JH_YUV_LIMITED && d->range != JH_YUV_FULL) return "unknown range";
-    if (d->transfer != JH_YUV_TRANSFER_NONE && d->transfer != JH_YUV_TRANSFER_SRGB) return "unknown transfer";
-    if (d->chroma != JLOAD_CHROMA_REPLICATE && d->chroma != JLOAD_CHROMA_BILINEAR) return "unknown chroma filter";
-    for (int i = 0; i < jload_yuv_planes(d->layout); i++)
-        if (!d->plane[i]) return "null plane";
-    return nullptr;
-}
-static inline const char* jload_yuv_pitch_error(const jh_load_yuv_desc* d, uint32_t rect_w) {
-    for (int i = 0; i < jload_yuv_planes(d->layout); i++)
-        if (d->pitch[i] < jload_yuv_row_bytes(d->layout, i, rect_w)) return "pitch below the row's bytes";
-    return nullptr;
+    if (const char* why = jframe_yuv_enums_error(d->layout, d->matrix, d->range, d->transfer)) return why;
+    if (d->chroma != JH_CHROMA_REPLICATE && d->chroma != JH_CHROMA_BILINEAR) return "unknown chroma filter";
+    return jframe_yuv_planes_error(d->layout, d->plane, d->pitch, 0u, JFRAME_NULL_PLANE);
 }
 
 // The batch queries' bodies.  texels: `format_or_transfer` is a jh_surface_format, or 4 + a jh_yuv_transfer for RGBA codes under
 // that transfer (what jh_load_yuv does with its codes); rgba: n pixels of 4 bytes in the format's order; out: 4 n f16 bit patterns.
 static inline const char* jload_texels(int format_or_transfer, int alpha, uint64_t n, const uint8_t* rgba, uint16_t* out) {
     const bool transfer = format_or_transfer == 4 + JH_YUV_TRANSFER_NONE || format_or_transfer == 4 + JH_YUV_TRANSFER_SRGB;
-    if (!transfer && !jload_format_ok(format_or_transfer)) return "unknown surface format or transfer";
+    if (!transfer && !jframe_surface_format_ok(format_or_transfer)) return "unknown surface format or transfer";
     if (!jload_alpha_ok(alpha)) return "unknown alpha mode";
-    const bool srgb = transfer ? format_or_transfer == 4 + JH_YUV_TRANSFER_SRGB : jload_format_srgb(format_or_transfer);
-    const bool bgra = !transfer && jload_format_bgra(format_or_transfer);
+    const bool srgb = transfer ? format_or_transfer == 4 + JH_YUV_TRANSFER_SRGB : jframe_surface_srgb(format_or_transfer);
+    const bool bgra = !transfer && jframe_surface_bgra(format_or_transfer);
     for (uint64_t i = 0; i < n; i++) {
         const uint8_t* p = rgba + 4u * i;
         uint32_t x, y;
@@ -188,7 +155,7 @@ static inline const char* jload_texels(int format_or_transfer, int alpha, uint64
 }
 // y: n codes; s_cb, s_cr: n sums in [0, 4080]; rgb: 3 n codes out.
 static inline const char* jload_yuv_codes(int matrix, int range, uint64_t n, const uint8_t* y, const uint16_t* s_cb, const uint16_t* s_cr, uint8_t* rgb) {
-    if (!jload_yuv_enums_ok(matrix, range)) return "unknown matrix or range";
+    if (jframe_yuv_enums_error(JH_YUV_NV12, matrix, range, JH_YUV_TRANSFER_NONE)) return "unknown matrix or range";
     for (uint64_t i = 0; i < n; i++)
         if (s_cb[i] > 4080u || s_cr[i] > 4080u) return "a chroma sum above 16 * 255";
     for (uint64_t i = 0; i < n; i++) {

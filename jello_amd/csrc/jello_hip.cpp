@@ -1352,9 +1352,8 @@ int jh_blit(jh_ctx* ctx, uint64_t src_image_id, void* dst_device_ptr, uint64_t d
     Alloc* a = nullptr;
     if (int rc = rgba16f_images(ctx, "jh_blit", {{src_image_id, "source", &a}}, size)) return rc;
     if (!dst_device_ptr) return fail(ctx, JH_ERR_INVALID, "jh_blit: null destination");
-    if (dst_pitch_bytes < 4ull * width) return fail(ctx, JH_ERR_INVALID, "jh_blit: pitch below 4 * width");
-    if (surface_format < JH_SURFACE_RGBA8_UNORM || surface_format > JH_SURFACE_BGRA8_SRGB)
-        return fail(ctx, JH_ERR_INVALID, "jh_blit: unknown surface format");
+    if (const char* why = jframe_surface_pitch_error(dst_pitch_bytes, width)) return fail(ctx, JH_ERR_INVALID, std::string("jh_blit: ") + why);
+    if (const char* why = jframe_surface_format_error(surface_format)) return fail(ctx, JH_ERR_INVALID, std::string("jh_blit: ") + why);
     return post_render_call(ctx, "blit", [&] {
         uint32_t row0, row1;
         band_pixel_rows(ctx, height, &row0, &row1);
@@ -1370,17 +1369,9 @@ int jh_blit_yuv(jh_ctx* ctx, uint64_t src_image_id, uint32_t width, uint32_t hei
     const uint32_t size[2] = {width, height};
     Alloc* a = nullptr;
     if (int rc = rgba16f_images(ctx, "jh_blit_yuv", {{src_image_id, "source", &a}}, size)) return rc;
-    if (desc->layout != JH_YUV_NV12 && desc->layout != JH_YUV_I420) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown layout");
-    if (desc->matrix != JH_YUV_BT601 && desc->matrix != JH_YUV_BT709) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown matrix");
-    if (desc->range != JH_YUV_LIMITED && desc->range != JH_YUV_FULL) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown range");
-    if (desc->transfer != JH_YUV_TRANSFER_NONE && desc->transfer != JH_YUV_TRANSFER_SRGB)
-        return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: unknown transfer");
-    const uint64_t cw = (width + 1ull) / 2u;
-    const uint64_t row_bytes[3] = {width, desc->layout == JH_YUV_NV12 ? 2u * cw : cw, cw};
-    for (int i = 0; i < (desc->layout == JH_YUV_NV12 ? 2 : 3); i++) {
-        if (!desc->plane[i]) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: null plane");
-        if (desc->pitch[i] < row_bytes[i]) return fail(ctx, JH_ERR_INVALID, "jh_blit_yuv: pitch below the row's bytes");
-    }
+    const char* why = jframe_yuv_enums_error(desc->layout, desc->matrix, desc->range, desc->transfer);
+    if (!why) why = jframe_yuv_planes_error(desc->layout, desc->plane, desc->pitch, width, JFRAME_NULL_PLANE | JFRAME_SHORT_PITCH);  // (plane by plane)
+    if (why) return fail(ctx, JH_ERR_INVALID, std::string("jh_blit_yuv: ") + why);
     return post_render_call(ctx, "blit_yuv", [&] {
         uint32_t row0, row1;  // the luma rows of the band, and the chroma rows under them
         band_pixel_rows(ctx, height, &row0, &row1);
@@ -1942,17 +1933,14 @@ int jh_perspective(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, co
     });
 }
 
-// load (include/jello_hip.h "load"; the descriptors' legality, the tables and the texel: include/jello_load.h; kernels_load.hip)
+// load (include/jello_hip.h "load"; legality, tables, texel: include/jello_load.h and jello_frame.h; kernels_load.hip): null planes before the rectangle, pitches after it
 int jh_load_surface(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_surface_desc* desc) {
-    static_assert(JH_LOAD_ALPHA_STRAIGHT == JLOAD_ALPHA_STRAIGHT && JH_LOAD_ALPHA_PREMULTIPLIED == JLOAD_ALPHA_PREMULTIPLIED &&
-                      JH_LOAD_ALPHA_OPAQUE == JLOAD_ALPHA_OPAQUE && JH_CHROMA_REPLICATE == JLOAD_CHROMA_REPLICATE && JH_CHROMA_BILINEAR == JLOAD_CHROMA_BILINEAR,
-                  "the C ABI's values are the rule's");
     Alloc* dst = nullptr;
     if (int rc = image_call_image(ctx, "jh_load_surface", desc, dst_image_id, "a band's rows are one rank's, the frame is the whole rectangle's", &dst)) return rc;
     if (const char* why = jload_surface_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_surface: ") + why);
     jimage_rect r;
     if (int rc = image_call_rect(ctx, "jh_load_surface", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
-    if (const char* why = jload_surface_pitch_error(desc, r.w)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_surface: ") + why);
+    if (const char* why = jframe_surface_pitch_error(desc->pitch, r.w)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_surface: ") + why);
     if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
     return post_render_call(ctx, "load_surface", [&] {
         if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;
@@ -1967,7 +1955,7 @@ int jh_load_yuv(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_yuv_desc* desc
     if (const char* why = jload_yuv_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_yuv: ") + why);
     jimage_rect r;
     if (int rc = image_call_rect(ctx, "jh_load_yuv", {desc->x, desc->y, desc->width, desc->height}, *dst, "", &r)) return rc;
-    if (const char* why = jload_yuv_pitch_error(desc, r.w)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_yuv: ") + why);
+    if (const char* why = jframe_yuv_planes_error(desc->layout, desc->plane, desc->pitch, r.w, JFRAME_SHORT_PITCH)) return fail(ctx, JH_ERR_INVALID, std::string("jh_load_yuv: ") + why);
     if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
     return post_render_call(ctx, "load_yuv", [&] {
         if (int rc = first_content(ctx, dst, r.w, r.h)) return rc;

@@ -51,25 +51,25 @@ __device__ __forceinline__ uint32_t load_px_bytes(const uint8_t* s) {
     return (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
 }
 
-// ALPHA: JLOAD_ALPHA_*.  STRAIGHT and OPAQUE look every channel up in f16 tables; PREMULTIPLIED takes the binary32 values from
+// ALPHA: JH_LOAD_ALPHA_*.  STRAIGHT and OPAQUE look every channel up in f16 tables; PREMULTIPLIED takes the binary32 values from
 // tables of its own through the store rule.
 template <bool SRGB, int ALPHA>
 __global__ __launch_bounds__(kLoadThreads) void k_load_surface(const uint8_t* __restrict__ src, uint64_t pitch, uint2* __restrict__ dst, uint32_t dst_w,
                                                                uint32_t dx, uint32_t dy, uint32_t w, uint32_t bgra, uint32_t segs, uint32_t total_items) {
-    constexpr bool PREMUL = ALPHA == JLOAD_ALPHA_PREMULTIPLIED;
+    constexpr bool PREMUL = ALPHA == JH_LOAD_ALPHA_PREMULTIPLIED;
     __shared__ uint16_t colour16[PREMUL ? 1 : 256];
-    __shared__ uint16_t unorm16[(PREMUL || ALPHA == JLOAD_ALPHA_OPAQUE || !SRGB) ? 1 : 256];  // (STRAIGHT's alpha, where colour16 is not it)
+    __shared__ uint16_t unorm16[(PREMUL || ALPHA == JH_LOAD_ALPHA_OPAQUE || !SRGB) ? 1 : 256];  // (STRAIGHT's alpha, where colour16 is not it)
     __shared__ float colour32[PREMUL ? 256 : 1];
     __shared__ float unorm32[(PREMUL && SRGB) ? 256 : 1];
     {  // (kLoadThreads = 256 entries)
         const uint32_t t = threadIdx.x;
         if (!PREMUL) colour16[t] = SRGB ? kLoadSrgbF16[t] : kLoadUnormF16[t];
-        if (!PREMUL && ALPHA == JLOAD_ALPHA_STRAIGHT && SRGB) unorm16[t] = kLoadUnormF16[t];
+        if (!PREMUL && ALPHA == JH_LOAD_ALPHA_STRAIGHT && SRGB) unorm16[t] = kLoadUnormF16[t];
         if (PREMUL) colour32[t] = SRGB ? jload_linear(t) : jload_unorm(t);
         if (PREMUL && SRGB) unorm32[t] = jload_unorm(t);
         __syncthreads();
     }
-    const uint16_t* a16 = (ALPHA == JLOAD_ALPHA_STRAIGHT && SRGB) ? unorm16 : colour16;
+    const uint16_t* a16 = (ALPHA == JH_LOAD_ALPHA_STRAIGHT && SRGB) ? unorm16 : colour16;
     const float* a32 = SRGB ? unorm32 : colour32;
     for (uint32_t it = blockIdx.x; it < total_items; it += gridDim.x) {
         LoadPair p;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kLoadThreads) void k_load_surface(const uint8_t* __
             // (the store rule itself; jello_load.h's jload_texel_premultiplied is its host copy for the queries, and
             // tests/test_gpu_load.py holds this kernel to that query over every code x alpha pair)
             if (PREMUL) t[j] = texel_unpremultiply(make_float4(colour32[r], colour32[g], colour32[b], a32[a]));
-            else jload_texel_tables(colour16, a16, ALPHA == JLOAD_ALPHA_OPAQUE, r, g, b, a, &t[j].x, &t[j].y);
+            else jload_texel_tables(colour16, a16, ALPHA == JH_LOAD_ALPHA_OPAQUE, r, g, b, a, &t[j].x, &t[j].y);
         }
         store_pair(p, t[0], t[1]);
     }
@@ -141,11 +141,11 @@ __device__ __forceinline__ uint2 load_yuv_texel(const LoadYuvPlanes& pl, const L
         load_chroma<NV12>(pl, cx1, cy0, &cb01, &cr01);
         load_chroma<NV12>(pl, cx0, cy1, &cb10, &cr10);
         load_chroma<NV12>(pl, cx1, cy1, &cb11, &cr11);
-        s_cb = jload_chroma_sum(JLOAD_CHROMA_BILINEAR, cb00, cb01, cb10, cb11);
-        s_cr = jload_chroma_sum(JLOAD_CHROMA_BILINEAR, cr00, cr01, cr10, cr11);
+        s_cb = jload_chroma_sum(JH_CHROMA_BILINEAR, cb00, cb01, cb10, cb11);
+        s_cr = jload_chroma_sum(JH_CHROMA_BILINEAR, cr00, cr01, cr10, cr11);
     } else {
-        s_cb = jload_chroma_sum(JLOAD_CHROMA_REPLICATE, cb00, 0, 0, 0);
-        s_cr = jload_chroma_sum(JLOAD_CHROMA_REPLICATE, cr00, 0, 0, 0);
+        s_cb = jload_chroma_sum(JH_CHROMA_REPLICATE, cb00, 0, 0, 0);
+        s_cr = jload_chroma_sum(JH_CHROMA_REPLICATE, cr00, 0, 0, 0);
     }
     const uint32_t c = jload_codes(k.k, k.off, luma, s_cb, s_cr);
     uint2 t;
@@ -185,23 +185,23 @@ bool load_items(jimage_rect rect, uint32_t* segs, uint32_t* total) {
 // not empty).  alpha: jh_load_alpha.  Returns 0, -1 on bad arguments, -2 on a launch error.
 extern "C" int jh_load_surface_launch(hipStream_t stream, const void* src, uint64_t pitch, jimage_dst dst, jimage_rect rect, int format, int alpha,
                                       int num_cus) {
-    if (!src || !dst.texels || !jload_format_ok(format) || !jload_alpha_ok(alpha) || pitch < 4ull * rect.w) return -1;
+    if (!src || !dst.texels || !jframe_surface_format_ok(format) || !jload_alpha_ok(alpha) || jframe_surface_pitch_error(pitch, rect.w)) return -1;
     if (jimage_rect_empty(rect) || !jimage_rect_inside(rect, dst.width, dst.height)) return -1;
     uint32_t segs, total;
     if (!load_items(rect, &segs, &total)) return -1;
     const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kLoadThreads);
-    const uint32_t bgra = jload_format_bgra(format) ? 1u : 0u;
+    const uint32_t bgra = jframe_surface_bgra(format) ? 1u : 0u;
     const uint8_t* s = (const uint8_t*)src;
     uint2* d = (uint2*)dst.texels;
 #define JH_LOAD_SURFACE(SRGB, ALPHA) \
     hipLaunchKernelGGL((k_load_surface<SRGB, ALPHA>), grid, block, 0, stream, s, pitch, d, dst.width, rect.x, rect.y, rect.w, bgra, segs, total)
-    switch ((jload_format_srgb(format) ? 3 : 0) + alpha) {
-        case 0: JH_LOAD_SURFACE(false, JLOAD_ALPHA_STRAIGHT); break;
-        case 1: JH_LOAD_SURFACE(false, JLOAD_ALPHA_PREMULTIPLIED); break;
-        case 2: JH_LOAD_SURFACE(false, JLOAD_ALPHA_OPAQUE); break;
-        case 3: JH_LOAD_SURFACE(true, JLOAD_ALPHA_STRAIGHT); break;
-        case 4: JH_LOAD_SURFACE(true, JLOAD_ALPHA_PREMULTIPLIED); break;
-        default: JH_LOAD_SURFACE(true, JLOAD_ALPHA_OPAQUE); break;
+    switch ((jframe_surface_srgb(format) ? 3 : 0) + alpha) {
+        case 0: JH_LOAD_SURFACE(false, JH_LOAD_ALPHA_STRAIGHT); break;
+        case 1: JH_LOAD_SURFACE(false, JH_LOAD_ALPHA_PREMULTIPLIED); break;
+        case 2: JH_LOAD_SURFACE(false, JH_LOAD_ALPHA_OPAQUE); break;
+        case 3: JH_LOAD_SURFACE(true, JH_LOAD_ALPHA_STRAIGHT); break;
+        case 4: JH_LOAD_SURFACE(true, JH_LOAD_ALPHA_PREMULTIPLIED); break;
+        default: JH_LOAD_SURFACE(true, JH_LOAD_ALPHA_OPAQUE); break;
     }
 #undef JH_LOAD_SURFACE
     return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -212,11 +212,11 @@ extern "C" int jh_load_surface_launch(hipStream_t stream, const void* src, uint6
 // jh_chroma_filter.  Returns 0, -1 on bad arguments, -2 on a launch error.
 extern "C" int jh_load_yuv_launch(hipStream_t stream, const void* const* planes, const uint64_t* pitches, jimage_dst dst, jimage_rect rect, int layout,
                                   int matrix, int range, int transfer, int chroma, int num_cus) {
-    if (layout < 0 || layout > 1 || !jload_yuv_enums_ok(matrix, range) || transfer < 0 || transfer > 1 || chroma < 0 || chroma > 1) return -1;
+    if (jframe_yuv_enums_error(layout, matrix, range, transfer) || (chroma != JH_CHROMA_REPLICATE && chroma != JH_CHROMA_BILINEAR)) return -1;
     if (!dst.texels || jimage_rect_empty(rect) || !jimage_rect_inside(rect, dst.width, dst.height)) return -1;
+    if (jframe_yuv_planes_error(layout, planes, pitches, rect.w, JFRAME_NULL_PLANE | JFRAME_SHORT_PITCH)) return -1;
     LoadYuvPlanes pl = {};
-    for (int i = 0; i < jload_yuv_planes(layout); i++) {
-        if (!planes[i] || pitches[i] < jload_yuv_row_bytes(layout, i, rect.w)) return -1;
+    for (int i = 0; i < jframe_yuv_planes(layout); i++) {
         pl.p[i] = (const uint8_t*)planes[i];
         pl.pitch[i] = pitches[i];
     }
@@ -227,10 +227,10 @@ extern "C" int jh_load_yuv_launch(hipStream_t stream, const void* const* planes,
     k.off = kLoadYuvOffset[range];
     const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kLoadThreads);
     uint2* d = (uint2*)dst.texels;
-    const uint32_t srgb = (uint32_t)transfer;
+    const uint32_t srgb = transfer == JH_YUV_TRANSFER_SRGB ? 1u : 0u;
 #define JH_LOAD_YUV(NV12, BILINEAR) \
     hipLaunchKernelGGL((k_load_yuv<NV12, BILINEAR>), grid, block, 0, stream, pl, k, d, dst.width, rect.x, rect.y, rect.w, rect.h, srgb, segs, total)
-    switch (chroma * 2 + layout) {
+    switch ((chroma == JH_CHROMA_BILINEAR ? 2 : 0) + (layout == JH_YUV_I420 ? 1 : 0)) {
         case 0: JH_LOAD_YUV(true, false); break;
         case 1: JH_LOAD_YUV(false, false); break;
         case 2: JH_LOAD_YUV(true, true); break;

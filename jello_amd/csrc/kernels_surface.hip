@@ -12,6 +12,7 @@
 
 #include <stdint.h>
 
+#include "../../include/jello_frame.h"
 #include "blit_convert.h"
 #include "kcommon.h"
 #include "texel_io.h"
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(kBlitThreads) void k_blit(const uint2* __restrict__
 // format: jh_surface_format.  Returns 0, -1 on bad arguments, -2 on a launch error.
 extern "C" int jh_blit_launch(hipStream_t stream, const void* src, void* dst, uint64_t pitch, uint32_t width, uint32_t row0,
                               uint32_t row1, int format, int num_cus) {
-    if (!dst || format < 0 || format > 3 || pitch < 4ull * width || row1 < row0) return -1;
+    if (!dst || !jframe_surface_format_ok(format) || jframe_surface_pitch_error(pitch, width) || row1 < row0) return -1;
     if (width == 0u || row1 == row0) return 0;
     // widest work list of any row: the head length depends on (dst + y * pitch) % 16, which repeats after at most 4 rows
     uint32_t items = 0u;
@@ -100,9 +101,9 @@ extern "C" int jh_blit_launch(hipStream_t stream, const void* src, void* dst, ui
     uint8_t* d = (uint8_t*)dst;
     const uint32_t bpr = (uint32_t)blocks_per_row, tb = (uint32_t)total;
     switch (format) {
-        case 0: hipLaunchKernelGGL((k_blit<false, false>), grid, block, 0, stream, s, d, pitch, width, row0, bpr, tb); break;
-        case 1: hipLaunchKernelGGL((k_blit<false, true>), grid, block, 0, stream, s, d, pitch, width, row0, bpr, tb); break;
-        case 2: hipLaunchKernelGGL((k_blit<true, false>), grid, block, 0, stream, s, d, pitch, width, row0, bpr, tb); break;
+        case JH_SURFACE_RGBA8_UNORM: hipLaunchKernelGGL((k_blit<false, false>), grid, block, 0, stream, s, d, pitch, width, row0, bpr, tb); break;
+        case JH_SURFACE_BGRA8_UNORM: hipLaunchKernelGGL((k_blit<false, true>), grid, block, 0, stream, s, d, pitch, width, row0, bpr, tb); break;
+        case JH_SURFACE_RGBA8_SRGB: hipLaunchKernelGGL((k_blit<true, false>), grid, block, 0, stream, s, d, pitch, width, row0, bpr, tb); break;
         default: hipLaunchKernelGGL((k_blit<true, true>), grid, block, 0, stream, s, d, pitch, width, row0, bpr, tb); break;
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;

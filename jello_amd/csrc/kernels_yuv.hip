@@ -14,6 +14,7 @@
 
 #include <stdint.h>
 
+#include "../../include/jello_frame.h"
 #include "blit_convert.h"
 #include "kcommon.h"
 #include "texel_io.h"
@@ -30,8 +31,6 @@ struct YuvPlanes {
     uint8_t* p[3];  // Y, CbCr interleaved (NV12) or Cb, - or Cr
     uint64_t pitch[3];
 };
-
-__device__ __forceinline__ uint32_t yuv_clamp8(int32_t v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
 // row . (r, g, b) + bias with 24-bit multiplies (full rate; a 32-bit v_mul_lo is a quarter of it): the coefficients need 17 bits
 // with their sign, the codes 8 and their sums over four pixels 10, and every result fits int32
@@ -102,11 +101,11 @@ __global__ __launch_bounds__(kYuvThreads) void k_blit_yuv(const uint2* __restric
             for (uint32_t j = 0; j < 4u; j++) {
                 const uint32_t px = blit_pixel<SRGB, false>(t[j], lut);
                 const int32_t r = (int32_t)(px & 0xffu), g = (int32_t)((px >> 8) & 0xffu), b = (int32_t)((px >> 16) & 0xffu);
-                yy[j] = yuv_clamp8(k.off + (yuv_dot(k.y, r, g, b, 1 << 15) >> 16));
+                yy[j] = jframe_clamp8(k.off + (yuv_dot(k.y, r, g, b, 1 << 15) >> 16));
                 sr += r; sg += g; sb += b;
             }
-            const uint32_t cb = yuv_clamp8(128 + (yuv_dot(k.cb, sr, sg, sb, 1 << 17) >> 18));
-            const uint32_t cr = yuv_clamp8(128 + (yuv_dot(k.cr, sr, sg, sb, 1 << 17) >> 18));
+            const uint32_t cb = jframe_clamp8(128 + (yuv_dot(k.cb, sr, sg, sb, 1 << 17) >> 18));
+            const uint32_t cr = jframe_clamp8(128 + (yuv_dot(k.cr, sr, sg, sb, 1 << 17) >> 18));
             *(uint16_t*)(st + 2u * i) = (uint16_t)(yy[0] | (yy[1] << 8));
             *(uint16_t*)(st + 2u * T + 2u * i) = (uint16_t)(yy[2] | (yy[3] << 8));
             if (NV12) {
@@ -154,21 +153,19 @@ __global__ __launch_bounds__(kYuvThreads) void k_blit_yuv(const uint2* __restric
 extern "C" int jh_blit_yuv_launch(hipStream_t stream, const void* src, void* const* planes, const uint64_t* pitches, uint32_t width,
                                   uint32_t height, uint32_t row0, uint32_t row1, int layout, int matrix, int range, int transfer,
                                   int num_cus) {
-    if (layout < 0 || layout > 1 || matrix < 0 || matrix > 1 || range < 0 || range > 1 || transfer < 0 || transfer > 1) return -1;
+    if (jframe_yuv_enums_error(layout, matrix, range, transfer)) return -1;
     if ((row0 & 1u) || row1 > height || row1 < row0 || ((row1 & 1u) && row1 != height)) return -1;
-    const uint64_t cw = (width + 1ull) / 2u;
-    const uint64_t need[3] = {width, layout == 0 ? 2u * cw : cw, cw};
-    const int n_planes = layout == 0 ? 2 : 3;
+    if (jframe_yuv_planes_error(layout, planes, pitches, width, JFRAME_NULL_PLANE | JFRAME_SHORT_PITCH)) return -1;
+    const uint64_t cw = jframe_chroma_extent(width);
     YuvPlanes pl = {};
     uint32_t wide = 1u;
-    for (int i = 0; i < n_planes; i++) {
-        if (!planes[i] || pitches[i] < need[i]) return -1;
+    for (int i = 0; i < jframe_yuv_planes(layout); i++) {
         pl.p[i] = (uint8_t*)planes[i];
         pl.pitch[i] = pitches[i];
         if (((uintptr_t)planes[i] | pitches[i]) & 15u) wide = 0u;
     }
     if (width == 0u || row1 == row0) return 0;
-    const uint32_t pair0 = row0 / 2u, pair1 = (row1 + 1u) / 2u;
+    const uint32_t pair0 = row0 / 2u, pair1 = (uint32_t)jframe_chroma_extent(row1);
     const uint64_t tiles_per_pair = (cw + kYuvTile - 1u) / kYuvTile;
     const uint64_t total = tiles_per_pair * (pair1 - pair0);
     if (total > 0x7fffffffull) return -1;
@@ -179,7 +176,7 @@ extern "C" int jh_blit_yuv_launch(hipStream_t stream, const void* src, void* con
     const dim3 grid(grid_blocks(total, 1u, 8u, num_cus)), block(kYuvThreads);
     const uint2* s = (const uint2*)src;
     const uint32_t tpp = (uint32_t)tiles_per_pair, tt = (uint32_t)total;
-    switch (transfer * 2 + layout) {
+    switch ((transfer == JH_YUV_TRANSFER_SRGB ? 2 : 0) + (layout == JH_YUV_I420 ? 1 : 0)) {
         case 0: hipLaunchKernelGGL((k_blit_yuv<false, true>), grid, block, 0, stream, s, pl, k, width, height, pair0, tpp, tt, wide); break;
         case 1: hipLaunchKernelGGL((k_blit_yuv<false, false>), grid, block, 0, stream, s, pl, k, width, height, pair0, tpp, tt, wide); break;
         case 2: hipLaunchKernelGGL((k_blit_yuv<true, true>), grid, block, 0, stream, s, pl, k, width, height, pair0, tpp, tt, wide); break;

@@ -20,7 +20,7 @@ from .imagecalls import (  # noqa: F401
     DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ShadowFlags, SHADOW_MAX_EXTENT, _shadow_desc, shadow_plan, shadow_bounds,
     box_shadow_geometry, PERSPECTIVE_STRAIGHT, PROJECTIVE_IDENTITY, _matrix9, perspective_plan, perspective_bounds, _perspective_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
     IDENTITY_MATRIX, _color_desc, color_tables, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, DISTANCE_MAX_RADIUS, _distance_desc,
-    distance_plan, LoadAlpha, ChromaFilter, LOAD_TRANSFER, _load_surface_desc, _load_yuv_desc, _surface_array_source, _yuv_array_source, load_texels, load_yuv_codes,
+    distance_plan, LoadAlpha, ChromaFilter, LOAD_TRANSFER, _load_surface_desc, _load_yuv_desc, _surface_array_source, yuv_plane_shapes, packed_plane_offsets, _yuv_array_source, load_texels, load_yuv_codes,
 )
 from .scene import Compose, Mix
 
@@ -277,24 +277,17 @@ class Engine:
         frame = self._frame(h, bump, attempts, "render_to_surface")
         return (None if out_device_ptr is not None else self._download_surface(params.width, params.height),) + frame
 
-    @staticmethod
-    def yuv_plane_shapes(width, height, layout):
-        """[(rows, bytes per row)] of the planes of a width x height frame: Y, then CbCr (NV12) or Cb and Cr (I420)."""
-        cw, ch = (width + 1) // 2, (height + 1) // 2
-        return [(height, width), (ch, 2 * cw)] if int(layout) == YuvLayout.NV12 else [(height, width), (ch, cw), (ch, cw)]
+    yuv_plane_shapes = staticmethod(yuv_plane_shapes)  # [(rows, bytes per row)] of a frame's planes: imagecalls.yuv_plane_shapes
 
     def _yuv_desc(self, width, height, layout, matrix, rng, transfer, planes):
         """(CYuvDesc, own) for `planes` = [(device pointer, pitch or None)] per plane, or None: the engine's own buffer, the
-        planes one after the other with tightly packed rows, each starting at a multiple of 16 (own = their offsets)."""
-        shapes = self.yuv_plane_shapes(width, height, layout)
+        planes as packed_plane_offsets lays them out (own = their offsets)."""
+        shapes = yuv_plane_shapes(width, height, layout)
         d = CYuvDesc(int(layout), int(matrix), int(rng), int(transfer))
         own = None
         if planes is None:
-            own, off = [], 0
-            for rows, rb in shapes:
-                own.append(off)
-                off += (rows * rb + 15) & ~15
-            base = self._own_buffer(_YUV_BUFFER_ID, max(off, 16))
+            own, total = packed_plane_offsets(shapes)
+            base = self._own_buffer(_YUV_BUFFER_ID, max(total, 16))
             planes = [(base + o, None) for o in own]
         for i, pl in enumerate(planes):
             ptr, pitch = pl if isinstance(pl, (tuple, list)) else (pl, None)
@@ -304,7 +297,7 @@ class Engine:
 
     def _download_yuv(self, width, height, layout, own):
         out = []
-        for (rows, rb), off in zip(self.yuv_plane_shapes(width, height, layout), own):
+        for (rows, rb), off in zip(yuv_plane_shapes(width, height, layout), own):
             a = np.empty((rows, rb), dtype=np.uint8)
             if a.nbytes:
                 self._check(self.hip.jh_download(self.ctx, _YUV_BUFFER_ID, a.ctypes.data, off, a.nbytes), "download")

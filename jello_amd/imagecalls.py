@@ -596,10 +596,16 @@ def _surface_array_source(pixels, rect):
     return None if w * h == 0 else (px.reshape(-1), 4 * w, rect)
 
 
-def _yuv_plane_shapes(width, height, layout):
-    """[(rows, bytes per row)] of the planes of a width x height frame: Y, then CbCr (NV12: layout 0) or Cb and Cr (I420)."""
+def yuv_plane_shapes(width, height, layout):
+    """[(rows, bytes per row)] of the planes of a width x height frame (include/jello_frame.h): Y, then CbCr (NV12: layout 0) or Cb and Cr (I420)."""
     cw, ch = (width + 1) // 2, (height + 1) // 2
     return [(height, width), (ch, 2 * cw)] if int(layout) == 0 else [(height, width), (ch, cw), (ch, cw)]
+
+
+def packed_plane_offsets(shapes):
+    """(offsets, total bytes) of planes [(rows, bytes per row)] in a buffer of the engine's own: one after the other, tight rows, each start a multiple of 16."""
+    sizes = [(rows * row_bytes + 15) & ~15 for rows, row_bytes in shapes]
+    return [sum(sizes[:i]) for i in range(len(sizes))], sum(sizes)
 
 
 def _yuv_array_source(planes, layout, rect):
@@ -612,19 +618,17 @@ def _yuv_array_source(planes, layout, rect):
     if not arrays or arrays[0].ndim != 2 or any(a.ndim not in (2, 3) for a in arrays) or int(layout) not in (0, 1):
         raise ValueError("jh_load_yuv: the planes are two-dimensional uint8 arrays (NV12's chroma may be (rows, samples, 2)) of layout NV12 or I420")
     h, w = arrays[0].shape
-    if w * h and [a.reshape(a.shape[0], -1).shape for a in arrays] != _yuv_plane_shapes(w, h, layout):
+    shapes = yuv_plane_shapes(w, h, layout)
+    if w * h and [a.reshape(a.shape[0], -1).shape for a in arrays] != shapes:
         raise ValueError("jh_load_yuv: the planes do not have the shapes of a frame of the luma plane's size in this layout")
     rect = _frame_rect(rect, w, h, "jh_load_yuv")
     if w * h == 0:
         return None
-    offs, off = [], 0
-    for a in arrays:
-        offs.append(off)
-        off += (a.size + 15) & ~15
-    host = np.zeros(off, np.uint8)
+    offs, total = packed_plane_offsets(shapes)
+    host = np.zeros(total, np.uint8)
     for a, o in zip(arrays, offs):
         host[o:o + a.size] = a.reshape(-1)
-    return host, [(o, b) for o, (_, b) in zip(offs, _yuv_plane_shapes(w, h, layout))], rect
+    return host, [(o, b) for o, (_, b) in zip(offs, shapes)], rect
 
 
 def load_texels(pixels, fmt=None, alpha=LoadAlpha.STRAIGHT, transfer=None, twin=False):

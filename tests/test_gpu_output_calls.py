@@ -129,6 +129,62 @@ def test_messages_keep_their_prefixes(engine):
         mem.free()
 
 
+def test_the_way_out_and_the_way_in_refuse_the_same_frame_faults_in_the_same_words(engine):
+    """include/jello_frame.h from both sides, on a 5 x 3 image with the planes in one canary buffer: a null pointer or a pitch one
+    below the row's bytes at every plane index the layout uses, given to jh_blit_yuv and -- the same planes as a jh_load_yuv_desc -- to
+    jh_load_yuv; a pitch one below 4 * width and the formats -1 and 4, given to jh_blit and jh_load_surface.  Every one is
+    JH_ERR_INVALID with the same words behind the call's own prefix, and nothing is written.  Only after that, the pitches that
+    are exactly the rows' bytes are accepted (the only launches of this test) and write nothing outside the planes' rows."""
+    from jello_amd.engine import _load_surface_desc, _load_yuv_desc
+    hip, ctx = engine.hip, engine.ctx
+    w, h = 5, 3
+    bits = np.random.default_rng(53).random((h, w, 4), dtype=np.float32).astype(np.float16).view(np.uint16)
+    src, dst, mem = Image(engine, bits), Image(engine, bits), DevBuf(engine, 1024)
+
+    def both_yuv(layout, planes):
+        out, _ = engine._yuv_desc(w, h, layout, 1, 0, 0, planes)
+        into = _load_yuv_desc(layout, 1, 0, 0, 1, planes, None)
+        return [("jh_blit_yuv", hip.jh_blit_yuv(ctx, src.id, w, h, ctypes.byref(out)), hip.jh_last_error(ctx)),
+                ("jh_load_yuv", hip.jh_load_yuv(ctx, dst.id, ctypes.byref(into)), hip.jh_last_error(ctx))]
+
+    def both_surface(fmt, pitch):
+        into = _load_surface_desc(fmt, 0, mem.ptr, pitch, None)
+        return [("jh_blit", hip.jh_blit(ctx, src.id, mem.ptr, pitch, w, h, fmt), hip.jh_last_error(ctx)),
+                ("jh_load_surface", hip.jh_load_surface(ctx, dst.id, ctypes.byref(into)), hip.jh_last_error(ctx))]
+
+    def refused(answers, words):
+        for name, rc, message in answers:
+            assert rc == JH_ERR_INVALID and message == name.encode() + b": " + words, (name, rc, message, words)
+
+    try:
+        legal = {}
+        for layout in (YuvLayout.NV12, YuvLayout.I420):
+            shapes = engine.yuv_plane_shapes(w, h, layout)
+            assert [rb for _, rb in shapes] == ([5, 6] if layout == YuvLayout.NV12 else [5, 3, 3])
+            legal[layout] = [(mem.ptr + 256 * i, rb) for i, (_, rb) in enumerate(shapes)]
+            for i, (ptr, rb) in enumerate(legal[layout]):
+                refused(both_yuv(layout, legal[layout][:i] + [(None, rb)] + legal[layout][i + 1:]), b"null plane")
+                refused(both_yuv(layout, legal[layout][:i] + [(ptr, rb - 1)] + legal[layout][i + 1:]), b"pitch below the row's bytes")
+        refused(both_surface(int(Surface.BGRA8_SRGB), 4 * w - 1), b"pitch below 4 * width")
+        for fmt in (-1, 4):
+            refused(both_surface(fmt, 4 * w), b"unknown surface format")
+        assert np.all(mem.bytes() == CANARY) and np.array_equal(src.bits(), bits) and np.array_equal(dst.bits(), bits)
+        # the boundary's other side: exactly the rows' bytes (NV12 without a third plane)
+        outside = np.ones(mem.n, bool)  # (of the rows written so far; I420 first: its chroma rows lie inside NV12's, so each is checked exactly)
+        for layout in (YuvLayout.I420, YuvLayout.NV12):
+            assert [rc for _, rc, _ in both_yuv(layout, legal[layout])] == [0, 0], layout
+            for (rows, rb), i in zip(engine.yuv_plane_shapes(w, h, layout), range(3)):
+                outside[256 * i:256 * i + rows * rb] = False
+            assert np.all(mem.bytes()[outside] == CANARY), layout
+        assert [rc for _, rc, _ in both_surface(int(Surface.BGRA8_SRGB), 4 * w)] == [0, 0]
+        after = mem.bytes()  # (the surface's 4 w h bytes lie inside plane 0's 256; the chroma planes still hold I420's bytes)
+        assert np.all(after[4 * w * h:256] == CANARY) and np.all(after[256 * 2 + 2 * 3:] == CANARY) and np.array_equal(src.bits(), bits)
+    finally:
+        src.free()
+        dst.free()
+        mem.free()
+
+
 def test_engine_methods_raise_for_a_refused_call(engine):
     """One refused call per Engine method on a 16 x 16 image (one tile): the exception class the method documents -- ValueError
     for what the rule of blur and composite refuses, RuntimeError elsewhere -- with the entry point's own text in it, and the

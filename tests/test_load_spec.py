@@ -299,7 +299,7 @@ def check_program(tmp_path_factory):
 
 def test_the_stand_alone_check_passes_under_the_sanitizers(check_program):
     out = subprocess.check_output([check_program]).decode()
-    assert out.startswith("ok: 4 tables, 16777216 triples, 25 frames"), out
+    assert out.startswith("ok: 4 tables, 16777216 triples, 25 frames, 18 layout widths"), out  # (both layouts x widths 1..9: jello_frame.h)
 
 
 @pytest.mark.parametrize("w,h", [(1, 1), (2, 2), (3, 3), (5, 4), (4, 5)])

@@ -9,7 +9,8 @@
 // division in place of the shift: no sum overflows, and the shift is arithmetic.  (3) jload_chroma_other and jload_chroma_sum on every
 // texel of frames up to 5 x 5 against a written-out walk over the chroma samples with the tent weights of their positions, from exactly
 // sized arrays (a read past an end is an AddressSanitizer report).  (4) The descriptors' legality from both sides of every boundary.
-// Prints "ok" and returns 0.
+// (5) include/jello_frame.h, the frame rule the loads share with jh_blit and jh_blit_yuv: plane counts and row bytes of both layouts at
+// widths 1..9 against a walk over the pixels, every predicate from both sides, the enum words, clamp8.  Prints "ok" and returns 0.
 //
 // With arguments -- W H LAYOUT CHROMA MATRIX RANGE TRANSFER HEX, HEX the bytes of the Y, Cb and Cr planes one after the other (W H,
 // then twice ceil(W/2) ceil(H/2)), two hex digits each -- it prints the texels of the frame, H lines of W texels "rrrr gggg bbbb aaaa"
@@ -116,34 +117,97 @@ static uint32_t check_chroma() {
             for (auto& b : plane) { seed = seed * 1664525u + 1013904223u; b = (uint8_t)(seed >> 24); }
             for (uint32_t y = 0; y < h; y++)
                 for (uint32_t x = 0; x < w; x++) {
-                    CHECK(rule_sum(plane, cw, ch, x, y, JLOAD_CHROMA_BILINEAR) == walk_sum(plane, cw, ch, x, y, true));
-                    CHECK(rule_sum(plane, cw, ch, x, y, JLOAD_CHROMA_REPLICATE) == walk_sum(plane, cw, ch, x, y, false));
+                    CHECK(rule_sum(plane, cw, ch, x, y, JH_CHROMA_BILINEAR) == walk_sum(plane, cw, ch, x, y, true));
+                    CHECK(rule_sum(plane, cw, ch, x, y, JH_CHROMA_REPLICATE) == walk_sum(plane, cw, ch, x, y, false));
                 }
         }
     return frames;
 }
 
+static bool same(const char* got, const char* want) { return want ? got && !strcmp(got, want) : !got; }
+
+// include/jello_frame.h: what the way out (jh_blit, jh_blit_yuv) and the way in share.  The plane count and the rows' bytes against a
+// count made by walking the pixels, two per chroma sample; every predicate from both sides of its boundary; the words.
+static uint32_t check_frame() {
+    uint32_t widths = 0;
+    for (int layout = JH_YUV_NV12; layout <= JH_YUV_I420; layout++)
+        for (uint32_t w = 1; w <= 9u; w++, widths++) {
+            uint64_t luma = 0, samples = 0;
+            for (uint32_t x = 0; x < w; x++) { luma++; if (x % 2u == 0u) samples++; }  // (a sample per pair of pixels begun)
+            CHECK(jframe_chroma_extent(w) == samples);
+            std::vector<uint64_t> need = {luma, layout == JH_YUV_NV12 ? 2u * samples : samples};  // NV12: a (Cb, Cr) pair per sample
+            if (layout == JH_YUV_I420) need.push_back(samples);
+            CHECK(jframe_yuv_planes(layout) == (int)need.size());
+            uint8_t byte = 0;
+            const void* planes[3] = {&byte, &byte, &byte};
+            uint64_t pitches[3] = {need[0], need[1], need.size() > 2u ? need[2] : 0u};
+            const int both = JFRAME_NULL_PLANE | JFRAME_SHORT_PITCH;
+            CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, both), nullptr));
+            for (int i = 0; i < 3; i++) {
+                const bool used = i < (int)need.size();
+                if (used) {
+                    CHECK(jframe_yuv_row_bytes(layout, i, w) == need[(size_t)i]);
+                    CHECK(!jframe_pitch_short(layout, i, need[(size_t)i], w) && jframe_pitch_short(layout, i, need[(size_t)i] - 1u, w));
+                }
+                planes[i] = nullptr;  // a null plane: refused where the layout uses it, under NULL_PLANE only; index 2 of NV12 is ignored
+                CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, both), used ? "null plane" : nullptr));
+                CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, JFRAME_NULL_PLANE), used ? "null plane" : nullptr));
+                CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, JFRAME_SHORT_PITCH), nullptr));
+                planes[i] = &byte;
+                pitches[i]--;  // a pitch one short (of NV12's index 2: 2^64 - 1, ignored)
+                CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, both), used ? "pitch below the row's bytes" : nullptr));
+                CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, JFRAME_SHORT_PITCH), used ? "pitch below the row's bytes" : nullptr));
+                CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, JFRAME_NULL_PLANE), nullptr));
+                if (used && i + 1 < (int)need.size()) {  // plane by plane, null before pitch: a later null plane comes second, an own one first
+                    planes[i + 1] = nullptr;
+                    CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, both), "pitch below the row's bytes"));
+                    planes[i + 1] = &byte; planes[i] = nullptr;
+                    CHECK(same(jframe_yuv_planes_error(layout, planes, pitches, w, both), "null plane"));
+                    planes[i] = &byte;
+                }
+                pitches[i]++;
+            }
+            CHECK(same(jframe_surface_pitch_error(4u * (uint64_t)w, w), nullptr) && same(jframe_surface_pitch_error(4u * (uint64_t)w - 1u, w), "pitch below 4 * width"));
+        }
+    CHECK(jframe_plane_null(nullptr) && !jframe_plane_null(&widths));
+    CHECK(jframe_chroma_extent(0u) == 0u && jframe_chroma_extent(0xffffffffu) == 0x80000000ull);
+    CHECK(same(jframe_surface_pitch_error(0u, 0u), nullptr) && same(jframe_surface_pitch_error(0x3fffffffcull - 1u, 0xffffffffu), "pitch below 4 * width"));
+    const char* words[4] = {"unknown layout", "unknown matrix", "unknown range", "unknown transfer"};
+    for (int field = 0; field < 4; field++)
+        for (int v = -1; v <= 2; v++) {
+            int e[4] = {JH_YUV_I420, JH_YUV_BT709, JH_YUV_FULL, JH_YUV_TRANSFER_SRGB};
+            e[field] = v;
+            CHECK(same(jframe_yuv_enums_error(e[0], e[1], e[2], e[3]), v == 0 || v == 1 ? nullptr : words[field]));
+            for (int later = field + 1; later < 4; later++) {  // the first illegal value is the one named
+                e[later] = 2;
+                CHECK(same(jframe_yuv_enums_error(e[0], e[1], e[2], e[3]), v == 0 || v == 1 ? words[field + 1] : words[field]));
+            }
+        }
+    for (int f = -1; f <= 4; f++) {
+        CHECK(jframe_surface_format_ok(f) == (f >= 0 && f <= 3) && same(jframe_surface_format_error(f), f >= 0 && f <= 3 ? nullptr : "unknown surface format"));
+        CHECK(jframe_surface_srgb(f) == (f == 2 || f == 3) && jframe_surface_bgra(f) == (f == 1 || f == 3));
+    }
+    for (int32_t v = -300; v <= 600; v++) CHECK(jframe_clamp8(v) == (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)));
+    CHECK(jframe_clamp8(INT32_MIN) == 0u && jframe_clamp8(INT32_MAX) == 255u);
+    return widths;
+}
+
 static void check_legality() {
     uint8_t byte = 0;
     jh_load_surface_desc s = {JH_SURFACE_RGBA8_UNORM, JH_LOAD_ALPHA_STRAIGHT, &byte, 40, 0, 0, 10, 2};
-    CHECK(!jload_surface_desc_error(&s) && !jload_surface_pitch_error(&s, 10));
-    CHECK(jload_surface_pitch_error(&s, 11) != nullptr);
+    CHECK(!jload_surface_desc_error(&s));
     for (int f = -1; f <= 4; f++) { s.format = f; CHECK((jload_surface_desc_error(&s) == nullptr) == (f >= 0 && f <= 3)); }
     s.format = 0;
     for (int a = -1; a <= 3; a++) { s.alpha = a; CHECK((jload_surface_desc_error(&s) == nullptr) == (a >= 0 && a <= 2)); }
     s.alpha = 0; s.src = nullptr;
     CHECK(jload_surface_desc_error(&s) != nullptr);
-    jh_load_yuv_desc y = {JH_YUV_NV12, JH_YUV_BT709, JH_YUV_LIMITED, JH_YUV_TRANSFER_NONE, JH_CHROMA_BILINEAR, 0, {&byte, &byte, nullptr}, {9, 10, 0}, 0, 0, 9, 3};
-    CHECK(!jload_yuv_desc_error(&y) && !jload_yuv_pitch_error(&y, 9));
-    CHECK(jload_yuv_pitch_error(&y, 10) != nullptr);  // (luma)
-    y.pitch[0] = 11;
-    CHECK(jload_yuv_pitch_error(&y, 11) != nullptr);  // (NV12 chroma: 12 bytes)
+    // (a descriptor's pitches are not the descriptor check's: short ones pass it, and jframe_yuv_planes_error finds them)
+    jh_load_yuv_desc y = {JH_YUV_NV12, JH_YUV_BT709, JH_YUV_LIMITED, JH_YUV_TRANSFER_NONE, JH_CHROMA_BILINEAR, 0, {&byte, &byte, nullptr}, {0, 0, 0}, 0, 0, 9, 3};
+    CHECK(!jload_yuv_desc_error(&y) && same(jframe_yuv_planes_error(y.layout, y.plane, y.pitch, 9, JFRAME_SHORT_PITCH), "pitch below the row's bytes"));
     y.layout = JH_YUV_I420;
-    CHECK(jload_yuv_desc_error(&y) != nullptr);  // (the third plane)
-    y.plane[2] = &byte; y.pitch[1] = 6; y.pitch[2] = 5;
-    CHECK(!jload_yuv_desc_error(&y) && jload_yuv_pitch_error(&y, 11) != nullptr);
-    y.pitch[2] = 6;
-    CHECK(!jload_yuv_pitch_error(&y, 11));
+    CHECK(same(jload_yuv_desc_error(&y), "null plane"));  // (the third plane)
+    y.plane[2] = &byte;
+    CHECK(!jload_yuv_desc_error(&y));
     int32_t* fields[5] = {&y.layout, &y.matrix, &y.range, &y.transfer, &y.chroma};
     for (int32_t* f : fields) {
         const int32_t keep = *f;
@@ -164,8 +228,7 @@ static int print_frame(char** a) {
     const int layout = atoi(a[2]), chroma = atoi(a[3]), matrix = atoi(a[4]), range = atoi(a[5]), transfer = atoi(a[6]);
     const uint32_t cw = (w + 1u) / 2u, ch = (h + 1u) / 2u;
     const size_t n = (size_t)w * h + 2u * (size_t)cw * ch;
-    if (w == 0u || h == 0u || w > 64u || h > 64u || strlen(a[7]) != 2u * n || !jload_yuv_enums_ok(matrix, range) || (unsigned)layout > 1u || (unsigned)chroma > 1u ||
-        (unsigned)transfer > 1u)
+    if (w == 0u || h == 0u || w > 64u || h > 64u || strlen(a[7]) != 2u * n || jframe_yuv_enums_error(layout, matrix, range, transfer) || (unsigned)chroma > 1u)
         return 2;
     std::vector<uint8_t> bytes(n);
     for (size_t i = 0; i < n; i++) {
@@ -179,7 +242,7 @@ static int print_frame(char** a) {
         for (uint32_t x = 0; x < w; x++) {
             const uint32_t c = jload_codes(kLoadYuv[matrix][range], kLoadYuvOffset[range], Y[(size_t)y * w + x], rule_sum(Cb, cw, ch, x, y, chroma), rule_sum(Cr, cw, ch, x, y, chroma));
             uint32_t tx, ty;
-            jload_texel(transfer == JH_YUV_TRANSFER_SRGB, JLOAD_ALPHA_STRAIGHT, c & 0xffu, (c >> 8) & 0xffu, c >> 16, 255u, &tx, &ty);
+            jload_texel(transfer == JH_YUV_TRANSFER_SRGB, JH_LOAD_ALPHA_STRAIGHT, c & 0xffu, (c >> 8) & 0xffu, c >> 16, 255u, &tx, &ty);
             printf("%s%04x %04x %04x %04x", x ? " | " : "", tx & 0xffffu, tx >> 16, ty & 0xffffu, ty >> 16);
         }
         printf("\n");
@@ -193,11 +256,12 @@ int main(int argc, char** argv) {
     check_tables();
     const uint64_t triples = check_codes();
     const uint32_t frames = check_chroma();
+    const uint32_t widths = check_frame();
     check_legality();
     if (failures) {
         printf("FAILED: %d checks\n", failures);
         return 1;
     }
-    printf("ok: 4 tables, %llu triples, %u frames\n", (unsigned long long)triples, frames);
+    printf("ok: 4 tables, %llu triples, %u frames, %u layout widths\n", (unsigned long long)triples, frames, widths);
     return 0;
 }
