@@ -34,6 +34,7 @@
  *   jh_shadow                         (no counterpart: a blurred rounded rectangle generated into an RGBA16F image)
  *   jh_perspective                    (no counterpart: a projective transform of RGBA16F images on the device)
  *   jh_distance                       (no counterpart: the capped Euclidean distance to a shape, through a ramp)
+ *   jh_stats                          (no counterpart: content bounds, channel extremes and histograms of an RGBA16F image)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -1341,6 +1342,94 @@ int jh_load_texel(int format_or_transfer, int alpha, uint64_t n, const uint8_t* 
 int jh_load_yuv_codes(int matrix, int range, uint64_t n, const uint8_t* y, const uint16_t* s_cb, const uint16_t* s_cr, uint8_t* rgb);
 int jh_load_surface(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_surface_desc* desc);
 int jh_load_yuv(jh_ctx* ctx, uint64_t dst_image_id, const jh_load_yuv_desc* desc);
+
+/* ---- Stats: content bounds, channel extremes and histograms of an RGBA16F image (DESIGN.md 5.22 "Stats rule") ----
+ * The one image call that brings a fact about an image OUT: the box of a layer's content (the rectangle every other image call
+ * takes), the channel extremes and four 256-bin histograms (what chooses jh_color_filter's LINEAR / TABLE parameters: auto-levels,
+ * normalisation, equalisation), as a fixed-size record in caller-owned device memory.  Everything in the record is an integer count
+ * or an integer min / max over the SET of texels of the rectangle, so it is defined byte for byte whatever the decomposition
+ * (include/jello_stats.h is the rule's text for the kernels, the library, the host twin and the stand-alone check;
+ * tests/stats_ref.py restates it in numpy):
+ *   content     a texel is CONTENT iff its chosen channel (0..3), the f16 widened to binary32, is >= threshold -- jh_distance's seed
+ *               test: IEEE, a NaN is not content, -0 >= +0 holds; the threshold is finite.  A source that was never written reads
+ *               as transparent black.  content_count: the content texels of the rectangle; always written.
+ *   bounds      (JH_STATS_BOUNDS) x0, y0, x1, y1: the smallest box of the content texels INSIDE the rectangle -- texels outside it
+ *               do not exist for this call -- in IMAGE coordinates, x1 and y1 exclusive; 0, 0, 0, 0 without content.
+ *   population  the texels the extremes and the histogram are taken over: JH_STATS_ALL: every texel of the rectangle;
+ *               JH_STATS_CONTENT: the content texels only (a layer on a transparent background).  population_count and nan_count
+ *               are written when EXTREMES or HISTOGRAM is asked for.
+ *   extremes    (JH_STATS_EXTREMES) per channel, over the population's non-NaN values, under the order of jh_morphology
+ *               (totalOrder: -Inf < ... < -0 < +0 < ... < +Inf), as f16 bit patterns.  A channel without a non-NaN value has
+ *               min_bits = 0x7C00 and max_bits = 0xFC00, the neutral elements.  nan_count[c]: the NaNs of channel c in the
+ *               population; they take no other part in the extremes.
+ *   histogram   (JH_STATS_HISTOGRAM) the code of a value v (straight colour: nothing is multiplied by alpha): q = the clamp of
+ *               jh_blit (NaN -> 0, -0 -> +0, +Inf -> 1);  JH_STATS_LINEAR: rintf(q * 255.0f) -- the product is exact for an f16, so
+ *               this is round-half-even of 255 q;  JH_STATS_SRGB: the code u with t[u] <= q < t[u + 1] of jh_blit's threshold table
+ *               (jello_amd/csrc/srgb_encode_lut.h), code 0 from 0 and code 255 up to 1.  `transfer` is the code of R, G, B; alpha is
+ *               always LINEAR.  A NaN counts in bin 0 AND in nan_count.  Each channel's 256 bins sum to population_count.
+ *   parts       a part that `what` does not ask for is written as zeros (min_bits and max_bits too: zeros, not the neutral
+ *               elements).  An image without texels (the 0 x 0 rectangle of an image of no width or height) writes a record of
+ *               zeros with the eight header words filled in: there is no texel to be an extreme.
+ * The record of a rectangle is the merge -- integer sums, mins, maxes, the union of the boxes -- of the records of any disjoint
+ * rectangles that tile it: four quadrant calls merged equal one call (jello_amd.stats.merge).
+ *
+ * jh_stats_plan: what the call will do with desc on an image_w x image_h image -- the resolved rectangle, the kernel launches (2; 1
+ * for an image without texels), the bytes of the record (sizeof(jh_stats_record)) and the bytes of scratch the call keeps (0 for an
+ * image without texels; otherwise JH_STATS_MAX_PARTIALS partial records, the same for every image: what a device of 256 compute
+ * units uses).  Host only, no context.  JH_ERR_INVALID for a null argument, a descriptor the rule refuses or a rectangle the image
+ * refuses, plan then untouched.
+ * jh_stats_codes: the histogram code of n f16 bit patterns under `transfer`, host only, no context.  JH_ERR_INVALID for a null
+ * argument (with n > 0) or an unknown transfer, codes then untouched.
+ *
+ * jh_stats: the record of the rectangle of src_image_id into out_device_ptr, sizeof(jh_stats_record) bytes of caller-owned device
+ * memory on an 8-byte boundary.  The source is only read: the call never clears an image or marks it as written.
+ * Stream-ordered on the context's stream, never waits: TWO kernel launches with the kernel boundary as the only hand-off -- every
+ * workgroup of the first streams its share of the rectangle and writes one partial record (box, extremes and counts reduced in
+ * registers, across the wave and through LDS; the bins in LDS) to its own slot of a scratch array; the second combines the
+ * partials in a fixed order and writes every byte of the record.  No global atomics, no fill.  The scratch array has one size for
+ * every image and only grows: the call may be captured between jh_graph_begin and jh_graph_end once one call has run eagerly (a
+ * capture that would have to allocate it is refused with JH_ERR_OOM and that advice).  With profiling on the call is a query
+ * "stats" with stage = -1 in jh_profile_collect_tree.  Not in band mode (jh_set_band): the rows outside a band belong to another
+ * rank's context.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_stats: ": a null
+ * desc or out pointer; an out pointer that is not 8-byte aligned; an unknown image id; an image that is not RGBA16F; `what` 0 or
+ * with an unknown bit; an unknown channel, population or transfer; a threshold that is not finite; a rectangle that is not inside
+ * the image or that is empty in exactly one dimension; a rectangle of more than JH_STATS_MAX_TEXELS = 2^31 texels (every count then
+ * fits a uint32_t); a band set with jh_set_band. */
+typedef enum jh_stats_population { JH_STATS_ALL = 0, JH_STATS_CONTENT = 1 } jh_stats_population;
+typedef enum jh_stats_transfer { JH_STATS_LINEAR = 0, JH_STATS_SRGB = 1 } jh_stats_transfer;
+#define JH_STATS_BOUNDS 1u
+#define JH_STATS_EXTREMES 2u
+#define JH_STATS_HISTOGRAM 4u
+#define JH_STATS_MAX_TEXELS 2147483648u /* 2^31: every count fits a uint32_t */
+#define JH_STATS_MAX_PARTIALS 1024u     /* partial records of the scratch array: 4 workgroups to each of 256 compute units */
+typedef struct jh_stats_desc {
+    uint32_t what;                 /* any non-empty subset of JH_STATS_BOUNDS | JH_STATS_EXTREMES | JH_STATS_HISTOGRAM */
+    int channel;                   /* 0..3: the channel of the content test */
+    float threshold;               /* content: the texels whose channel is >= threshold */
+    int population;                /* jh_stats_population: which texels the extremes and the histogram are taken over */
+    int transfer;                  /* jh_stats_transfer: the histogram's code for R, G, B; alpha is always LINEAR */
+    uint32_t x, y, width, height;  /* rectangle of src that is read; 0 x 0: the whole image */
+} jh_stats_desc;
+typedef struct jh_stats_record {
+    uint32_t x, y, width, height;                  /* the resolved rectangle */
+    uint32_t what, population, transfer, reserved; /* of the descriptor; 0 */
+    uint32_t content_count;                        /* content texels in the rectangle */
+    uint32_t bounds[4];                            /* x0, y0, x1, y1 in IMAGE coordinates, x1 / y1 exclusive; 0, 0, 0, 0 when content_count == 0 */
+    uint32_t population_count;                     /* texels that took part in extremes and histogram */
+    uint32_t nan_count[4];                         /* per channel, over the population */
+    uint16_t min_bits[4], max_bits[4];             /* f16 bit patterns */
+    uint32_t histogram[4][256];
+} jh_stats_record;
+typedef struct jh_stats_plan_t {
+    uint32_t x, y, width, height;  /* the resolved rectangle */
+    uint32_t launches, reserved;   /* 2, or 1 for an image without texels; 0 */
+    uint64_t record_bytes;         /* sizeof(jh_stats_record) */
+    uint64_t scratch_bytes;        /* 0 for an image without texels, else JH_STATS_MAX_PARTIALS partial records */
+} jh_stats_plan_t;
+int jh_stats_plan(const jh_stats_desc* desc, uint32_t image_w, uint32_t image_h, jh_stats_plan_t* plan);
+int jh_stats_codes(int transfer, uint64_t n, const uint16_t* f16_bits, uint8_t* codes);
+int jh_stats(jh_ctx* ctx, uint64_t src_image_id, const jh_stats_desc* desc, void* out_device_ptr);
 
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);

@@ -20,8 +20,15 @@
 #include "jello_perspective.h"
 #include "jello_resample.h"
 #include "jello_shadow.h"
+#include "jello_stats.h"
 #include "jello_turbulence.h"
 #include "jello_warp.h"
+
+// jh_blit's sRGB thresholds as a host constant, for jq_stats_codes (a file that includes this one does not include the kernels'
+// blit_convert.h, which takes the table as a device constant).
+#define JSRGB_ENCODE_TABLE static const
+#include "../jello_amd/csrc/srgb_encode_lut.h"
+#undef JSRGB_ENCODE_TABLE
 
 static inline const char* jq_blur_taps(float sigma, float* weights, uint32_t* radius) {
     if (!jblur_sigma_ok(sigma)) return "sigma is negative, above 64 or NaN";
@@ -120,6 +127,16 @@ static inline const char* jq_distance_plan(const jh_distance_desc* desc, uint32_
     return jdist_plan(desc, image_w, image_h, plan);
 }
 
+static inline const char* jq_stats_plan(const jh_stats_desc* desc, uint32_t image_w, uint32_t image_h, jh_stats_plan_t* plan) {
+    if (!desc || !plan) return "null argument";
+    return jstats_plan(desc, image_w, image_h, plan);
+}
+
+static inline const char* jq_stats_codes(int transfer, uint64_t n, const uint16_t* f16_bits, uint8_t* codes) {
+    if (n != 0u && (!f16_bits || !codes)) return "null argument";
+    return jstats_codes(transfer, n, f16_bits, codes, kSrgbEncodeThreshold);
+}
+
 static inline const char* jq_load_texel(int format_or_transfer, int alpha, uint64_t n, const uint8_t* rgba, uint16_t* out) {
     if (n != 0u && (!rgba || !out)) return "null argument";
     return jload_texels(format_or_transfer, alpha, n, rgba, out);
@@ -166,6 +183,8 @@ static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint
     X(perspective_bounds, (const double* matrix, uint32_t src_w, uint32_t src_h, int filter, uint32_t dst_w, uint32_t dst_h, uint32_t* rect), \
       (matrix, src_w, src_h, filter, dst_w, dst_h, rect))                                                                                   \
     X(distance_plan, (const jh_distance_desc* desc, uint32_t image_w, uint32_t image_h, jh_dist_plan* plan), (desc, image_w, image_h, plan)) \
+    X(stats_plan, (const jh_stats_desc* desc, uint32_t image_w, uint32_t image_h, jh_stats_plan_t* plan), (desc, image_w, image_h, plan))   \
+    X(stats_codes, (int transfer, uint64_t n, const uint16_t* f16_bits, uint8_t* codes), (transfer, n, f16_bits, codes))                    \
     X(load_texel, (int format_or_transfer, int alpha, uint64_t n, const uint8_t* rgba, uint16_t* out), (format_or_transfer, alpha, n, rgba, out)) \
     X(load_yuv_codes, (int matrix, int range, uint64_t n, const uint8_t* y, const uint16_t* s_cb, const uint16_t* s_cr, uint8_t* rgb),     \
       (matrix, range, n, y, s_cb, s_cr, rgb))

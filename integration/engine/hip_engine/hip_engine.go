@@ -1233,6 +1233,91 @@ func (e *Engine) LoadYUV(dst renderer.ImageProxy, planes [3]unsafe.Pointer, pitc
 	e.check(C.jh_load_yuv(e.ctx, C.uint64_t(dst.ID), &d), "load_yuv")
 }
 
+// StatsPopulation is jh_stats_population: the extremes and the histogram are taken over every texel of the rectangle, or over the
+// content texels only.
+type StatsPopulation int32
+
+const (
+	StatsAll     StatsPopulation = C.JH_STATS_ALL
+	StatsContent StatsPopulation = C.JH_STATS_CONTENT
+)
+
+// StatsTransfer is jh_stats_transfer: the histogram's code for R, G, B (alpha is always linear).
+type StatsTransfer int32
+
+const (
+	StatsLinear StatsTransfer = C.JH_STATS_LINEAR
+	StatsSRGB   StatsTransfer = C.JH_STATS_SRGB
+)
+
+// The parts of the record (jh_stats_desc.what): any non-empty subset.
+const (
+	StatsBounds    uint32 = C.JH_STATS_BOUNDS
+	StatsExtremes  uint32 = C.JH_STATS_EXTREMES
+	StatsHistogram uint32 = C.JH_STATS_HISTOGRAM
+)
+
+// StatsRecordBytes is sizeof(jh_stats_record): what Stats writes at its out pointer.
+const StatsRecordBytes = C.sizeof_jh_stats_record
+
+// StatsDesc is jh_stats_desc (include/jello_hip.h "Stats"): the parts asked for, the channel (0..3) and threshold that make a texel
+// content, the population, the histogram's transfer, and the rectangle of the image that is read (0 x 0: the whole image).
+type StatsDesc struct {
+	What                uint32
+	Channel             int32
+	Threshold           float32
+	Population          StatsPopulation
+	Transfer            StatsTransfer
+	X, Y, Width, Height uint32
+}
+
+func (desc StatsDesc) c() C.jh_stats_desc {
+	return C.jh_stats_desc{what: C.uint32_t(desc.What), channel: C.int(desc.Channel), threshold: C.float(desc.Threshold), population: C.int(desc.Population),
+		transfer: C.int(desc.Transfer), x: C.uint32_t(desc.X), y: C.uint32_t(desc.Y), width: C.uint32_t(desc.Width), height: C.uint32_t(desc.Height)}
+}
+
+// StatsPlanResult is jh_stats_plan_t: the resolved rectangle, the kernel launches, the bytes of the record and of the scratch.
+type StatsPlanResult struct {
+	X, Y, Width, Height uint32
+	Launches            uint32
+	RecordBytes         uint64
+	ScratchBytes        uint64
+}
+
+// StatsPlan is jh_stats_plan: what Stats does with desc on an imageW x imageH image.  Host only.
+func StatsPlan(desc StatsDesc, imageW, imageH uint32) (StatsPlanResult, error) {
+	d := desc.c()
+	var p C.jh_stats_plan_t
+	if C.jh_stats_plan(&d, C.uint32_t(imageW), C.uint32_t(imageH), &p) != 0 {
+		return StatsPlanResult{}, fmt.Errorf("hip_engine: StatsPlan: a descriptor the rule refuses or a rectangle the image refuses")
+	}
+	return StatsPlanResult{X: uint32(p.x), Y: uint32(p.y), Width: uint32(p.width), Height: uint32(p.height), Launches: uint32(p.launches),
+		RecordBytes: uint64(p.record_bytes), ScratchBytes: uint64(p.scratch_bytes)}, nil
+}
+
+// StatsCodes is jh_stats_codes: the histogram code of every f16 bit pattern of bits under transfer, as a colour channel's.  Host only.
+func StatsCodes(transfer StatsTransfer, bits []uint16) ([]uint8, error) {
+	codes := make([]uint8, len(bits))
+	if len(bits) == 0 {
+		return codes, nil
+	}
+	if C.jh_stats_codes(C.int(transfer), C.uint64_t(len(bits)), (*C.uint16_t)(unsafe.Pointer(&bits[0])), (*C.uint8_t)(unsafe.Pointer(&codes[0]))) != 0 {
+		return nil, fmt.Errorf("hip_engine: StatsCodes: unknown transfer")
+	}
+	return codes, nil
+}
+
+// Stats is jh_stats: the content box, the channel extremes and four 256-bin histograms of a rectangle of the RGBA16F image src, as a
+// jh_stats_record at out -- StatsRecordBytes of caller-owned device memory on an 8-byte boundary -- by the rule of DESIGN.md 5.22
+// (integer counts, mins and maxes over the set of texels: every implementation gives the same bytes).  The box is the rectangle the
+// other image calls take for a layer; the histogram chooses ColorFilter's functions.  The image is only read.  Stream-ordered behind
+// the frame, waits for nothing, two kernel launches; the partial records live in a scratch array of one size for every image, so
+// the call is capturable once one call has run eagerly.
+func (e *Engine) Stats(src renderer.ImageProxy, desc StatsDesc, out unsafe.Pointer) {
+	d := desc.c()
+	e.check(C.jh_stats(e.ctx, C.uint64_t(src.ID), &d, out), "stats")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

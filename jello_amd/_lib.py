@@ -255,6 +255,26 @@ class CDistPlan(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("scratch_bytes", ctypes.c_uint64)]
 
 
+class CStatsDesc(ctypes.Structure):
+    """jh_stats_desc (include/jello_hip.h)."""
+    _fields_ = [("what", ctypes.c_uint32), ("channel", ctypes.c_int32), ("threshold", ctypes.c_float), ("population", ctypes.c_int32),
+                ("transfer", ctypes.c_int32), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
+
+
+class CStatsRecord(ctypes.Structure):
+    """jh_stats_record (include/jello_hip.h)."""
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("what", ctypes.c_uint32),
+                ("population", ctypes.c_uint32), ("transfer", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("content_count", ctypes.c_uint32),
+                ("bounds", ctypes.c_uint32 * 4), ("population_count", ctypes.c_uint32), ("nan_count", ctypes.c_uint32 * 4),
+                ("min_bits", ctypes.c_uint16 * 4), ("max_bits", ctypes.c_uint16 * 4), ("histogram", (ctypes.c_uint32 * 256) * 4)]
+
+
+class CStatsPlan(ctypes.Structure):
+    """jh_stats_plan_t (include/jello_hip.h)."""
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("launches", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("record_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64)]
+
+
 class CLoadSurfaceDesc(ctypes.Structure):
     """jh_load_surface_desc (include/jello_hip.h)."""
     _fields_ = [("format", ctypes.c_int32), ("alpha", ctypes.c_int32), ("src", ctypes.c_void_p), ("pitch", ctypes.c_uint64), ("x", ctypes.c_uint32),
@@ -353,6 +373,8 @@ def _declare(L):
         "perspective_plan": [dp, dp],
         "perspective_bounds": [dp, u32, u32, ci, u32, u32, ctypes.POINTER(u32)],
         "distance_plan": [ctypes.POINTER(CDistanceDesc), u32, u32, ctypes.POINTER(CDistPlan)],
+        "stats_plan": [ctypes.POINTER(CStatsDesc), u32, u32, ctypes.POINTER(CStatsPlan)],
+        "stats_codes": [ci, u64, vp, vp],
         "load_texel": [ci, ci, u64, vp, vp],
         "load_yuv_codes": [ci, ci, u64, vp, vp, vp, vp],
     }
@@ -409,6 +431,7 @@ def _declare(L):
     hip.jh_shadow.argtypes = [vp, u64, ctypes.POINTER(CShadowDesc)]
     hip.jh_perspective.argtypes = [vp, u64, u64, ctypes.POINTER(CPerspectiveDesc)]
     hip.jh_distance.argtypes = [vp, u64, u64, ctypes.POINTER(CDistanceDesc)]
+    hip.jh_stats.argtypes = [vp, u64, ctypes.POINTER(CStatsDesc), vp]
     hip.jh_load_surface.argtypes = [vp, u64, ctypes.POINTER(CLoadSurfaceDesc)]
     hip.jh_load_yuv.argtypes = [vp, u64, ctypes.POINTER(CLoadYuvDesc)]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]

@@ -25,6 +25,7 @@
 #include "../../include/jello_resample.h"
 #include "../../include/jello_color.h"
 #include "../../include/jello_distance.h"
+#include "../../include/jello_stats.h"
 #include "../../include/jello_morph.h"
 #include "../../include/jello_warp.h"
 #include "../../include/jello_convolve.h"
@@ -1173,7 +1174,7 @@ int jh_profile_collect_tree(jh_ctx* ctx, jh_profile_node* out, int max) {
     return n;
 }
 
-// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow, perspective, distance, load ----
+// ---- post-render calls: the surface and YUV blits, the tile pack, dashing, blur, composite, resample, colour filter, morphology, warp, convolve, lighting, turbulence, displace, shadow, perspective, distance, load, stats ----
 // The words of the context's counter block (hint_overflow: 64 words, zeroed at creation) and who counts in them.
 enum {
     kHintOverflowWord = 0,   // fine: blend-stack saves dropped because the clip-depth hint was too small (L.hint_overflow)
@@ -1723,6 +1724,38 @@ int jh_distance(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const
             ImageViews v;
             if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
             return launch_status(ctx, "jh_distance", jh_distance_launch(ctx->stream, v.from, v.to, r, desc, tmp, ctx->num_cus));
+        });
+}
+
+// stats (include/jello_hip.h "Stats"; the descriptor, the plan, the partial and the record: include/jello_stats.h; kernels_stats.hip)
+int jh_stats(jh_ctx* ctx, uint64_t src_image_id, const jh_stats_desc* desc, void* out_device_ptr) {
+    static_assert(JH_STATS_ALL == JSTATS_ALL && JH_STATS_CONTENT == JSTATS_CONTENT && JH_STATS_LINEAR == JSTATS_LINEAR && JH_STATS_SRGB == JSTATS_SRGB &&
+                      JH_STATS_BOUNDS == JSTATS_BOUNDS && JH_STATS_EXTREMES == JSTATS_EXTREMES && JH_STATS_HISTOGRAM == JSTATS_HISTOGRAM &&
+                      JH_STATS_MAX_TEXELS == JSTATS_MAX_TEXELS && JH_STATS_MAX_PARTIALS == JSTATS_MAX_PARTIALS,
+                  "the C ABI's values are the rule's");
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_stats: null descriptor");
+    if (!out_device_ptr) return fail(ctx, JH_ERR_INVALID, "jh_stats: null out pointer");
+    if (((uintptr_t)out_device_ptr & 7u) != 0u) return fail(ctx, JH_ERR_INVALID, "jh_stats: the out pointer is not 8-byte aligned");
+    Alloc* src = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_stats", {{src_image_id, "source", &src}})) return rc;
+    if (const char* why = jstats_desc_error(desc)) return fail(ctx, JH_ERR_INVALID, std::string("jh_stats: ") + why);
+    jimage_rect r;
+    if (int rc = image_call_rect(ctx, "jh_stats", {desc->x, desc->y, desc->width, desc->height}, *src, "", &r)) return rc;
+    if (const char* why = jstats_rect_error(desc, src->width, src->height, &r)) return fail(ctx, JH_ERR_INVALID, std::string("jh_stats: ") + why);
+    if (!(ctx->band_row0 == 0u && ctx->band_row1 == 0xffffffffu))
+        return fail(ctx, JH_ERR_INVALID, "jh_stats: not in band mode (the rows outside a band belong to another rank)");
+    void* tmp = nullptr;
+    return post_render_call(
+        ctx, "stats",
+        [&] {
+            if (jimage_rect_empty(r)) return (int)JH_OK;  // (an image without texels: the record's header and zeros, no partials)
+            return scratch_take(ctx, "jh_stats", "run one jh_stats call once eagerly first", JH_SCR_STATS, jstats_scratch_bytes(r), &tmp);
+        },
+        [&] {
+            // (the source is only read: nothing is cleared and nothing counts as written)
+            const jimage_src from = {content_or_null(*src), src->width, src->height};
+            return launch_status(ctx, "jh_stats", jh_stats_launch(ctx->stream, from, r, desc, out_device_ptr, tmp, ctx->num_cus));
         });
 }
 

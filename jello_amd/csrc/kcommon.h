@@ -243,6 +243,9 @@ struct JhImageDesc {
 //              rect width x 16 B; it only grows and nothing else writes it, so a captured call stays valid)
 //   DISTANCE  (jh_distance, as MORPH: the one or two planes of uint16_t run lengths between its two passes, each rect height x
 //              (rect width + 2 max_distance) x 2 B; it only grows and nothing else writes it, so a captured call stays valid)
+//   STATS     (jh_stats: the partial records between its two launches, JSTATS_MAX_PARTIALS x JSTATS_PARTIAL_BYTES = 4.07 MiB whatever
+//              the image -- the grid cap of the largest device -- so one eager call makes every later call capturable; every word that
+//              is read was written by the same call's first launch)
 enum {
     JH_SCR_SCAN_TMP = 0,
     JH_SCR_A = 1,
@@ -266,7 +269,8 @@ enum {
     JH_SCR_LIGHT_TABLES = 19,   // jh_lighting's tables
     JH_SCR_TURB_TABLES = 20,    // jh_turbulence's tables
     JH_SCR_DISTANCE = 21,       // jh_distance's intermediate planes
-    JH_SCR_COUNT = 22
+    JH_SCR_STATS = 22,          // jh_stats's partial records
+    JH_SCR_COUNT = 23
 };
 struct JhScratch;  // per-context scratch allocator, defined in jello_hip.cpp
 void* jh_scratch_get(JhScratch* s, int slot, uint64_t bytes);  // grows on demand, returns device pointer (nullptr on OOM)
@@ -364,7 +368,7 @@ struct JhResampleTables {
     uint32_t region_x;          // float4 slots of LDS a wave of the row pass needs: jh_resample_skew(longest span - 1) + 1
 };
 
-// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _turbulence, _displace, _shadow, _perspective, _distance, _selftest .hip).  Declared
+// The launchers outside the stage table, each documented at its definition (kernels_surface, _yuv, _pack, _blur, _composite, _resample, _color, _morph, _warp, _convolve, _lighting, _turbulence, _displace, _shadow, _perspective, _distance, _stats, _selftest .hip).  Declared
 // here and nowhere else: the file that defines one and the file that calls it both include this, so a signature that changes on one
 // side only does not compile.  int results: 0, -1 for arguments the launcher refuses (an image launcher, which takes the views and resolved
 // rectangles of include/jello_image.h: a rectangle that is not inside its image), another negative value (-2) for a failed launch.
@@ -409,6 +413,8 @@ int jh_perspective_launch(hipStream_t stream, jimage_src src, jimage_rect src_re
                           int edge, int straight, int num_cus);
 struct jh_distance_desc;  // include/jello_hip.h
 int jh_distance_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect rect, const jh_distance_desc* desc, void* tmp, int num_cus);
+struct jh_stats_desc;  // include/jello_hip.h
+int jh_stats_launch(hipStream_t stream, jimage_src src, jimage_rect rect, const jh_stats_desc* desc, void* out, void* tmp, int num_cus);
 int jh_load_surface_launch(hipStream_t stream, const void* src, uint64_t pitch, jimage_dst dst, jimage_rect rect, int format, int alpha, int num_cus);
 int jh_load_yuv_launch(hipStream_t stream, const void* const* planes, const uint64_t* pitches, jimage_dst dst, jimage_rect rect, int layout, int matrix,
                        int range, int transfer, int chroma, int num_cus);

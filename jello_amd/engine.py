@@ -21,6 +21,7 @@ from .imagecalls import (  # noqa: F401
     box_shadow_geometry, PERSPECTIVE_STRAIGHT, PROJECTIVE_IDENTITY, _matrix9, perspective_plan, perspective_bounds, _perspective_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
     IDENTITY_MATRIX, _color_desc, color_tables, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, DISTANCE_MAX_RADIUS, _distance_desc,
     distance_plan, LoadAlpha, ChromaFilter, LOAD_TRANSFER, _load_surface_desc, _load_yuv_desc, _surface_array_source, yuv_plane_shapes, packed_plane_offsets, _yuv_array_source, load_texels, load_yuv_codes,
+    StatsWhat, StatsPopulation, StatsTransfer, STATS_MAX_TEXELS, STATS_MAX_PARTIALS, STATS_RECORD_BYTES, _stats_desc, stats_plan, stats_codes,
 )
 from .scene import Compose, Mix
 
@@ -85,6 +86,8 @@ _YUV_BUFFER_ID = 0x5955565F4F555400
 # context buffers that load_surface / load_yuv upload host arrays into before they convert them (they only grow)
 _LOAD_SURFACE_BUFFER_ID = 0x4C4F41445F535200
 _LOAD_YUV_BUFFER_ID = 0x4C4F41445F595500
+# a context buffer that stats writes its record into when the caller passes no device pointer
+_STATS_BUFFER_ID = 0x53544154535F5200
 
 
 class CMD:
@@ -456,6 +459,41 @@ class Engine:
         dst = src_id if dst_id is None else dst_id
         self._check(self.hip.jh_distance(self.ctx, src_id, dst, ctypes.byref(d)), "distance", invalid=ValueError)
 
+    def stats(self, image_id, rect=None, what=StatsWhat.ALL, channel=3, threshold=2.0 ** -24, population=StatsPopulation.ALL,
+              transfer=StatsTransfer.LINEAR, out_device_ptr=None):
+        """jh_stats: the content box, the channel extremes and four 256-bin histograms (the parts `what` names; the rule: DESIGN.md
+        5.22) of the rectangle `rect` = (x, y, width, height) of the RGBA16F image `image_id` (None: the whole image), which is only
+        read.  A texel is content iff its `channel` (0..3; 3: alpha) is >= `threshold` (the default: the smallest positive f16 --
+        what is not transparent).  `population`: the extremes and the histogram are taken over every texel of the rectangle (ALL) or
+        over the content texels (CONTENT).  `transfer`: the histogram's code for R, G, B.  With `out_device_ptr` --
+        STATS_RECORD_BYTES of device memory on an 8-byte boundary -- the call is stream-ordered and returns None; without one the
+        record goes into a buffer of the engine's own, the call waits, and a jello_amd.stats.Stats is returned.  ValueError for a
+        call the rule refuses."""
+        from . import stats as _stats
+        d = _stats_desc(what, channel, threshold, population, transfer, rect)
+        ptr = out_device_ptr if out_device_ptr is not None else self._own_buffer(_STATS_BUFFER_ID, STATS_RECORD_BYTES)
+        self._check(self.hip.jh_stats(self.ctx, image_id, ctypes.byref(d), ptr), "stats", invalid=ValueError)
+        if out_device_ptr is not None:
+            return None
+        return _stats.Stats(self.download(_STATS_BUFFER_ID, STATS_RECORD_BYTES))
+
+    def content_bounds(self, image_id, channel=3, threshold=2.0 ** -24, rect=None):
+        """The box (x, y, width, height), in image coordinates, of the texels of `rect` (None: the whole image) whose `channel` is >=
+        `threshold`, or None when there is none: stats(what=BOUNDS) -- the rectangle the other image calls take for a layer."""
+        return self.stats(image_id, rect, StatsWhat.BOUNDS, channel, threshold).bounds
+
+    def auto_levels(self, src_id, dst_id=None, clip=(0.0, 0.0), population=StatsPopulation.CONTENT, transfer=StatsTransfer.LINEAR, channel=3,
+                    threshold=2.0 ** -24, rect=None):
+        """Stretches the colour channels of `src_id` to the full range, two calls with the host in between: stats(HISTOGRAM) over the
+        `population`, then color_filter(src -> dst; None: in place) with the LINEAR functions stats.levels(record, clip) computes for R,
+        G and B -- alpha keeps its values -- in ColorSpace.SRGB when the codes are `transfer` SRGB's.  `clip` = (dark, bright)
+        fractions of the population that may saturate.  Returns the record."""
+        from . import stats as _stats
+        record = self.stats(src_id, rect, StatsWhat.HISTOGRAM, channel, threshold, population, transfer)
+        funcs = _stats.levels(record, clip)[:3] + [None]
+        self.color_filter(src_id, dst_id, funcs=funcs, space=ColorSpace.SRGB if int(transfer) == StatsTransfer.SRGB else ColorSpace.LINEAR, clamp=True, rect=rect)
+        return record
+
     def round_outline(self, layer_id, target_id, width, color, scratch_image_id):
         """outline() with a disc instead of a box, and a width that may be fractional, three calls: distance(layer -> scratch, OUTER,
         the ramp distance.outline(width), the colour in the descriptor): the coverage of the layer's alpha >= 0.5 grown by a disc of
@@ -774,7 +812,7 @@ class Engine:
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
                 morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None, perspective=None, distance=None,
-                load_surface=None, load_yuv=None):
+                load_surface=None, load_yuv=None, stats=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -833,7 +871,11 @@ class Engine:
         pitch)], ...) (the other keywords of load_surface() and load_yuv(), optional; device memory only: a capture cannot upload)
         convert a frame into the RGBA16F image `dst` right after the frame and before turbulence= (one more launch each, nothing to
         run eagerly first), so that composite=dict(src=dst, ...) of the same capture lays the loaded frame over the rendered one.  The
-        graph holds the pointers: a replay converts what they hold then."""
+        graph holds the pointers: a replay converts what they hold then.
+        stats=dict(out=device pointer, ...) (the other keywords of stats() but the id, optional) writes the record of the frame's
+        target -- as it is after the render and after the other image keywords of the same capture that work on it in place; the
+        target itself, not the image a lighting=, convolve=, resample=, warp=, displace= or perspective= wrote -- into `out` on every
+        replay, before the surface, YUV or pack conversion (two more launches); one stats() call must have run once eagerly."""
         for name, step, key in (("load_surface", load_surface, "pixels"), ("load_yuv", load_yuv, "planes")):
             if step is None:
                 continue
@@ -843,6 +885,8 @@ class Engine:
                 raise ValueError("capture: %s= takes device memory, not arrays (a capture cannot upload)" % name)
         if sum(step is not None for step in (resample, warp, displace, perspective)) > 1:
             raise ValueError("capture: resample=, warp=, displace= and perspective= are exclusive (each would feed the conversion)")
+        if stats is not None and stats.get("out") is None:
+            raise ValueError("capture: stats= needs out=, a device pointer (a capture cannot wait for a record)")
         self._check(self.hip.jh_graph_begin(self.ctx), "graph_begin")
         try:
             self.run(recording, RUN_DISPATCHES, out_device_ptr)
@@ -885,6 +929,8 @@ class Engine:
                 self.perspective(t["id"], perspective["dst"], perspective["matrix"],
                                  **{k: v for k, v in perspective.items() if k not in ("dst", "width", "height", "matrix")})
                 t = {"id": perspective["dst"], "width": perspective["width"], "height": perspective["height"]}
+            if stats is not None:
+                self.stats(recording.target["id"], out_device_ptr=stats["out"], **{k: v for k, v in stats.items() if k != "out"})
             if surface is not None:
                 ptr, pitch, fmt = surface
                 self._blit(t["id"], ptr, pitch, t["width"], t["height"], fmt)

@@ -8,7 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CDistanceDesc, CDistPlan, CLightingDesc, CLightPlan, CLoadSurfaceDesc, CLoadYuvDesc, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CTurbPlan, CTurbulenceDesc, CWarpDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CDistanceDesc, CDistPlan, CLightingDesc, CLightPlan, CLoadSurfaceDesc, CLoadYuvDesc, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CStatsDesc, CStatsPlan, CStatsRecord, CTurbPlan, CTurbulenceDesc, CWarpDesc
 
 
 def _query(name, twin=False):
@@ -539,6 +539,67 @@ def distance_plan(image_size, twin=False, **keywords):
         raise ValueError("jh_distance: illegal descriptor or rectangle")
     return dict(rect=(plan.x, plan.y, plan.width, plan.height), radius=plan.radius, cap=plan.cap, planes=plan.planes,
                 plane_columns=plan.plane_columns, plane_rows=plan.plane_rows, scratch_bytes=int(plan.scratch_bytes))
+
+
+class StatsWhat(enum.IntFlag):
+    """The parts of jh_stats's record (JH_STATS_BOUNDS | JH_STATS_EXTREMES | JH_STATS_HISTOGRAM); a part not asked for is zeros."""
+    BOUNDS = 1
+    EXTREMES = 2
+    HISTOGRAM = 4
+    ALL = 7
+
+
+class StatsPopulation(enum.IntEnum):
+    """jh_stats_population: the texels the extremes and the histogram are taken over -- every texel of the rectangle (ALL) or the
+    content texels only (CONTENT: a layer on a transparent background, whose bin 0 would otherwise hold the background)."""
+    ALL = 0
+    CONTENT = 1
+
+
+class StatsTransfer(enum.IntEnum):
+    """jh_stats_transfer: the histogram's code for R, G, B -- round-half-even of 255 clamp(v) (LINEAR) or jh_blit's sRGB code (SRGB);
+    alpha is always LINEAR."""
+    LINEAR = 0
+    SRGB = 1
+
+
+STATS_MAX_TEXELS = 1 << 31  # JH_STATS_MAX_TEXELS
+STATS_MAX_PARTIALS = 1024  # JH_STATS_MAX_PARTIALS
+STATS_RECORD_BYTES = ctypes.sizeof(CStatsRecord)
+
+
+def _stats_desc(what=StatsWhat.ALL, channel=3, threshold=2.0 ** -24, population=StatsPopulation.ALL, transfer=StatsTransfer.LINEAR, rect=None):
+    """jh_stats_desc.  What the rule refuses is left for the call to refuse, except a `what` that does not fit the field.  The default
+    threshold is the smallest positive f16: content is what is not transparent."""
+    if int(what) != what or not 0 <= int(what) < 1 << 32:
+        raise ValueError("jh_stats: what is a subset of StatsWhat")
+    with np.errstate(over="ignore"):
+        d = CStatsDesc(int(what), int(channel), float(np.float32(threshold)), int(population), int(transfer))
+    d.x, d.y, d.width, d.height = _rect(rect)
+    return d
+
+
+def stats_plan(image_size, twin=False, **keywords):
+    """jh_stats_plan (twin: jl_stats_plan, the host twin): what Engine.stats with these keywords does on an image of `image_size` =
+    (width, height) -- dict(rect = the resolved (x, y, width, height), launches, record_bytes, scratch_bytes).  The scratch is the
+    same for every image with texels: one eager call makes every later one capturable.  No GPU needed.  ValueError for a descriptor
+    the rule refuses or a rectangle the image refuses."""
+    d, plan = _stats_desc(**keywords), CStatsPlan()
+    if not (0 <= int(image_size[0]) < 1 << 32 and 0 <= int(image_size[1]) < 1 << 32) or \
+            _query("stats_plan", twin)(ctypes.byref(d), int(image_size[0]), int(image_size[1]), ctypes.byref(plan)) != 0:
+        raise ValueError("jh_stats: illegal descriptor or rectangle")
+    return dict(rect=(plan.x, plan.y, plan.width, plan.height), launches=plan.launches, record_bytes=int(plan.record_bytes),
+                scratch_bytes=int(plan.scratch_bytes))
+
+
+def stats_codes(f16_bits, transfer=StatsTransfer.LINEAR, twin=False):
+    """jh_stats_codes (twin: jl_stats_codes): the histogram code (uint8, the shape of the input) of every f16 bit pattern of `f16_bits`
+    under `transfer`, as a colour channel's.  No GPU needed.  ValueError for an unknown transfer."""
+    bits = np.ascontiguousarray(f16_bits, np.uint16)
+    codes = np.empty(bits.shape, np.uint8)
+    if _query("stats_codes", twin)(int(transfer), bits.size, bits.ctypes.data, codes.ctypes.data) != 0:
+        raise ValueError("jh_stats: unknown transfer")
+    return codes
 
 
 class LoadAlpha(enum.IntEnum):

@@ -52,8 +52,13 @@ def render(t):
         "// otherwise; code = rint(255 enc(v)), all in binary64, ties to even.  kSrgbEncodeThreshold[k - 1] is the smallest f32",
         "// whose code is >= k (k = 1..255), so code(v) = #{k : threshold[k - 1] <= v}.  Generated -- do not edit:",
         "//     python tools/gen_srgb_encode_table.py",
+        "// JSRGB_ENCODE_TABLE is the including file's storage for the table: a device constant unless it says otherwise (the host",
+        "// half of the stats rule, include/jello_queries.h and tools/stats_check.cpp, reads the same numbers as a host constant).",
         "#pragma once",
-        "static __device__ __constant__ const float kSrgbEncodeThreshold[255] = {",
+        "#ifndef JSRGB_ENCODE_TABLE",
+        "#define JSRGB_ENCODE_TABLE static __device__ __constant__ const",
+        "#endif",
+        "JSRGB_ENCODE_TABLE float kSrgbEncodeThreshold[255] = {",
     ]
     vals = [float(x).hex() + "f" for x in t]
     for i in range(0, len(vals), 4):

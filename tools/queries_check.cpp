@@ -241,6 +241,35 @@ static void distance() {
     CHECK(plan2.untouched());
 }
 
+static void stats() {
+    Buf<jh_stats_desc> d(1);
+    memset(d, 0, sizeof(jh_stats_desc));
+    d[0].what = JSTATS_BOUNDS | JSTATS_HISTOGRAM; d[0].channel = 3; d[0].threshold = 0.5f; d[0].population = JSTATS_CONTENT; d[0].transfer = JSTATS_SRGB;
+    d[0].x = 3u; d[0].y = 5u; d[0].width = 40u; d[0].height = 20u;
+    Buf<jh_stats_plan_t> plan(1);
+    CHECK(!jq_stats_plan(d, 100u, 50u, plan) && plan[0].x == 3u && plan[0].y == 5u && plan[0].width == 40u && plan[0].height == 20u && plan[0].launches == 2u &&
+          plan[0].reserved == 0u && plan[0].record_bytes == sizeof(jh_stats_record) && plan[0].scratch_bytes == 1024u * 4168u);
+    Buf<jh_stats_plan_t> plan2(1);
+    CHECK(is(jq_stats_plan(nullptr, 100u, 50u, plan2), "null argument") && is(jq_stats_plan(d, 100u, 50u, nullptr), "null argument"));
+    CHECK(is(jq_stats_plan(d, 42u, 50u, plan2), "the rectangle is not inside the image"));
+    d[0].what = 8u;
+    CHECK(is(jq_stats_plan(d, 100u, 50u, plan2), "unknown bits in what"));
+    d[0].what = 1u;
+    d[0].threshold = INFINITY;
+    CHECK(is(jq_stats_plan(d, 100u, 50u, plan2), "threshold is not finite"));
+    CHECK(plan2.untouched());
+    Buf<uint16_t> bits(5);
+    bits[0] = 0x0000; bits[1] = 0x3c00; bits[2] = 0x3800; bits[3] = 0x7e00; bits[4] = 0xfc00;
+    Buf<uint8_t> codes(5);
+    CHECK(!jq_stats_codes(JSTATS_LINEAR, 5u, bits, codes) && codes[0] == 0 && codes[1] == 255 && codes[2] == 128 && codes[3] == 0 && codes[4] == 0);
+    CHECK(!jq_stats_codes(JSTATS_SRGB, 5u, bits, codes) && codes[0] == 0 && codes[1] == 255 && codes[2] == 188 && codes[3] == 0 && codes[4] == 0);
+    CHECK(!jq_stats_codes(JSTATS_SRGB, 0u, nullptr, nullptr));
+    Buf<uint8_t> codes2(5);
+    CHECK(is(jq_stats_codes(0, 5u, nullptr, codes2), "null argument") && is(jq_stats_codes(0, 5u, bits, nullptr), "null argument"));
+    CHECK(is(jq_stats_codes(2, 5u, bits, codes2), "unknown transfer") && is(jq_stats_codes(-1, 5u, bits, codes2), "unknown transfer"));
+    CHECK(codes2.untouched());
+}
+
 static void composite() {
     static const char* const kWhy = "the source rectangle is not inside the source image or is empty in one dimension";
     Buf<uint32_t> out(6);
@@ -290,6 +319,7 @@ int main() {
     shadow();
     perspective();
     distance();
+    stats();
     composite();
     if (g_fail) return 1;
     printf("ok\n");
