@@ -35,6 +35,7 @@
  *   jh_perspective                    (no counterpart: a projective transform of RGBA16F images on the device)
  *   jh_distance                       (no counterpart: the capped Euclidean distance to a shape, through a ramp)
  *   jh_stats                          (no counterpart: content bounds, channel extremes and histograms of an RGBA16F image)
+ *   jh_lut3d                          (no counterpart: a 3D colour lookup table applied to an RGBA16F image on the device)
  * Binding order for every stage is the WGSL @binding order = renderer/render.go dispatch order.
  *
  * Conventions: plain pointers and sizes only; every call returns 0 on success or a negative
@@ -176,6 +177,8 @@ int jh_image_write(jh_ctx* ctx, uint64_t id, uint32_t x, uint32_t y, uint32_t wi
 int jh_image_download(jh_ctx* ctx, uint64_t id, void* dst, uint64_t size);
 int jh_image_free(jh_ctx* ctx, uint64_t id);
 void* jh_image_device_ptr(jh_ctx* ctx, uint64_t id);
+/* The size an image was created, uploaded or imported with (either pointer may be null); JH_ERR_INVALID for an unknown id, with no message. */
+int jh_image_size(jh_ctx* ctx, uint64_t id, uint32_t* width, uint32_t* height);
 
 /* ---- dispatch ----
  * One call per recorded Dispatch: `stage` is a jh_stage (= the field order of renderer.FullShaders), (gx, gy, gz) the
@@ -1431,6 +1434,61 @@ int jh_stats_plan(const jh_stats_desc* desc, uint32_t image_w, uint32_t image_h,
 int jh_stats_codes(int transfer, uint64_t n, const uint16_t* f16_bits, uint8_t* codes);
 int jh_stats(jh_ctx* ctx, uint64_t src_image_id, const jh_stats_desc* desc, void* out_device_ptr);
 
+/* ---- 3D LUT: a colour lookup table applied to an RGBA16F image by tetrahedral interpolation (DESIGN.md 5.23 "LUT rule") ----
+ * What jh_color_filter cannot say -- a .cube grade, a gamut map, a film look, anything that mixes the channels non-linearly -- and a
+ * way to BAKE a chain of colour calls into one pass: the table is an ordinary RGBA16F image of the context, so every image call can
+ * write it; a sequence of jh_color_filter calls over an identity table leaves a table that applies the whole chain, per texel, in
+ * one launch.  The reference project has no counterpart; the result is defined here on values, byte for byte
+ * (include/jello_lut3d.h is the rule's text for the kernel, the library, the host twin and the stand-alone check;
+ * tests/lut3d_ref.py restates it in numpy):
+ *   the LUT   an RGBA16F image of the context, N texels wide and N^2 high, 2 <= N <= 65.  Entry (i, j, k) indexes (red, green, blue)
+ *             and is the texel (x = i, y = j + N k): red varies fastest, the .cube order.  Its r, g, b are the output colour for
+ *             the input (i, j, k) / (N - 1); its alpha is ignored.  A never-written LUT reads as zeros, like every never-written
+ *             source.  There is no scratch slot, no resident key and no staleness rule: the call is always capturable.
+ *   per texel binary32, nothing contracted but the stated fmaf; h_c is the stored (un-premultiplied) f16 of channel c, widened.
+ *     1 clamp     c = h > 0 ? h : 0; c = c < 1 ? c : 1 -- compare and select, so NaN and -0 become +0, as in the colour filter.
+ *     2 position  p = c (N - 1), k = min((int)p, N - 2), f = p - (float)k.  Every one of these operations is exact for every f16
+ *                 input and every legal N: p, f, 1 - f and the differences of two fractions are representable in binary32.  The
+ *                 position carries no rounding, and the weights below sum to exactly 1.
+ *     3 walk      start at the vertex V0 = (k_r, k_g, k_b) and step +1 along one axis at a time in descending order of the
+ *                 fractions: V1, V2 and V3 = (k_r + 1, k_g + 1, k_b + 1).  Ties go r before g before b: the order is the stable
+ *                 sort decided by f_r >= f_g, f_r >= f_b, f_g >= f_b.  With the fractions f1 >= f2 >= f3 in that order the weights
+ *                 are w0 = 1 - f1, w1 = f1 - f2, w2 = f2 - f3, w3 = f3, all exact.
+ *     4 sum       per colour channel: m = w0 V0.c, then m = fmaf(w1, V1.c, m), m = fmaf(w2, V2.c, m), m = fmaf(w3, V3.c, m) -- one
+ *                 multiply and three fmaf, in this order.  Zero weights are multiplied, not skipped: 0 x Inf is NaN, as for
+ *                 jh_convolve.  The tie rule therefore decides which vertex a zero weight touches, which non-finite entries show
+ *                 and nothing else does.
+ *     5 store     f16(m), round to nearest even; a NaN result is any NaN.  Alpha is the source's bit pattern, copied.
+ * So: an identity table whose N - 1 is a power of two returns every finite f16 in [0, 1] bit for bit (-0 becomes +0, values
+ * outside are clamped, NaN becomes 0); exactly four entries are read per texel; alpha never changes.
+ *
+ * jh_lut3d_identity: the identity table of n into out_texels, n^3 entries of four f16 bit patterns in the image's order: entry
+ * value f16(i / (n - 1)), rounded once from binary64, alpha 1.0.  jh_lut3d_texels: the rule on `count` texels (in_texels, four f16
+ * bit patterns each) over a host table lut_texels of n^3 entries, into out_texels.  Host only, no context.  JH_ERR_INVALID for a
+ * null argument (jh_lut3d_texels: with count > 0, the table always) or an n outside 2..65, the outputs then untouched.
+ *
+ * jh_lut3d: the rule applied to the rectangle (x, y, width, height) of src_image_id through the table lut_image_id, written to the
+ * same rectangle of dst_image_id; one rectangle for both, 0 x 0: the whole source.  src == dst is legal (the rule is per texel) and
+ * so is lut == src.  A never-written source reads as transparent black; a never-written destination is cleared outside the
+ * rectangle and the context's generation moves, as for jh_color_filter.  Stream-ordered on the context's stream, never waits: one
+ * kernel launch (tables of N <= 17 are copied into LDS by every workgroup, larger ones are gathered from memory).  May be captured
+ * between jh_graph_begin and jh_graph_end at any time.  With profiling on the call is a query "lut3d" with stage = -1 in
+ * jh_profile_collect_tree.  Not in band mode (jh_set_band): a band's rows are one rank's, the table the context's.
+ * JH_ERR_INVALID, with nothing enqueued, no memory touched and nothing flushed, each with a message that starts "jh_lut3d: ": a null
+ * desc; an unknown source, destination or LUT id; an image that is not RGBA16F; a size outside 2..65; flags that are not 0; a LUT
+ * image that is not exactly size x size^2; the LUT being the destination; a rectangle that is not inside the source or the
+ * destination or that is empty in exactly one dimension; a band set with jh_set_band. */
+#define JH_LUT3D_MIN_SIZE 2u
+#define JH_LUT3D_MAX_SIZE 65u
+typedef struct jh_lut3d_desc {
+    uint32_t size;                 /* N: the LUT image is N x N^2 */
+    uint32_t flags;                /* must be 0 */
+    uint32_t x, y, width, height;  /* rectangle of src that is read and of dst that is written; 0 x 0: the whole source */
+} jh_lut3d_desc;
+int jh_lut3d_identity(uint32_t n, uint16_t* out_texels);
+int jh_lut3d_texels(uint32_t n, const uint16_t* lut_texels, const uint16_t* in_texels, uint64_t count, uint16_t* out_texels);
+int jh_lut3d(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint64_t lut_image_id, const jh_lut3d_desc* desc);
+
 /* ---- profiling ---- */
 int jh_profile_enable(jh_ctx* ctx, int on);
 /* Waits for the device, writes up to max records (one per dispatch since the last collect), returns the count. */
@@ -1473,6 +1531,9 @@ int jh_scratch_trim(jh_ctx* ctx);
 int jh_debug_flatten_regions(jh_ctx* ctx, uint32_t flags);
 uint64_t jh_debug_graph_self_cleans(jh_ctx* ctx);  /* replays that had to zero an internal counter first (tests) */
 int jh_debug_poison_scratch(jh_ctx* ctx, int byte);
+/* tests and timing: which instantiation jh_lut3d launches -- 0 the launcher's choice (tables of N <= 17 in LDS), 1 always gathered
+   from memory, 2 always from LDS (a call with a larger table is then refused).  The results do not depend on it. */
+int jh_debug_lut3d_variant(jh_ctx* ctx, int variant);
 
 /* ---- introspection ---- */
 int jh_device_info(jh_ctx* ctx, char* name, int name_len, int* compute_units, uint64_t* total_mem);

@@ -17,6 +17,7 @@
 #include "jello_distance.h"
 #include "jello_lighting.h"
 #include "jello_load.h"
+#include "jello_lut3d.h"
 #include "jello_perspective.h"
 #include "jello_resample.h"
 #include "jello_shadow.h"
@@ -147,6 +148,16 @@ static inline const char* jq_load_yuv_codes(int matrix, int range, uint64_t n, c
     return jload_yuv_codes(matrix, range, n, y, s_cb, s_cr, rgb);
 }
 
+static inline const char* jq_lut3d_identity(uint32_t n, uint16_t* out_texels) {
+    if (!out_texels) return "null argument";
+    return jlut_identity_query(n, out_texels);
+}
+
+static inline const char* jq_lut3d_texels(uint32_t n, const uint16_t* lut_texels, const uint16_t* in_texels, uint64_t count, uint16_t* out_texels) {
+    if (!lut_texels || (count != 0u && (!in_texels || !out_texels))) return "null argument";
+    return jlut_texels(n, lut_texels, in_texels, count, out_texels);
+}
+
 // (the geometry of jh_composite: out[6] = {sx', sy', dx', dy', w, h}, all zero when nothing is left)
 static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy,
                                             uint32_t dst_w, uint32_t dst_h, uint32_t* out) {
@@ -187,7 +198,10 @@ static inline const char* jq_composite_clip(uint32_t src_w, uint32_t src_h, uint
     X(stats_codes, (int transfer, uint64_t n, const uint16_t* f16_bits, uint8_t* codes), (transfer, n, f16_bits, codes))                    \
     X(load_texel, (int format_or_transfer, int alpha, uint64_t n, const uint8_t* rgba, uint16_t* out), (format_or_transfer, alpha, n, rgba, out)) \
     X(load_yuv_codes, (int matrix, int range, uint64_t n, const uint8_t* y, const uint16_t* s_cb, const uint16_t* s_cr, uint8_t* rgb),     \
-      (matrix, range, n, y, s_cb, s_cr, rgb))
+      (matrix, range, n, y, s_cb, s_cr, rgb))                                                                                               \
+    X(lut3d_identity, (uint32_t n, uint16_t* out_texels), (n, out_texels))                                                                  \
+    X(lut3d_texels, (uint32_t n, const uint16_t* lut_texels, const uint16_t* in_texels, uint64_t count, uint16_t* out_texels),             \
+      (n, lut_texels, in_texels, count, out_texels))
 #define JQ_HOST_QUERY_LIST(X)                                                                                                               \
     X(composite_clip,                                                                                                                       \
       (uint32_t src_w, uint32_t src_h, uint32_t sx, uint32_t sy, uint32_t sw, uint32_t sh, int32_t dx, int32_t dy, uint32_t dst_w, uint32_t dst_h, \

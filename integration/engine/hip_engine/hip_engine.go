@@ -1318,6 +1318,36 @@ func (e *Engine) Stats(src renderer.ImageProxy, desc StatsDesc, out unsafe.Point
 	e.check(C.jh_stats(e.ctx, C.uint64_t(src.ID), &d, out), "stats")
 }
 
+// Lut3DMinSize and Lut3DMaxSize are JH_LUT3D_MIN_SIZE and JH_LUT3D_MAX_SIZE: the sizes N of a 3D lookup table.
+const (
+	Lut3DMinSize = 2
+	Lut3DMaxSize = 65
+)
+
+// Lut3DIdentity is jh_lut3d_identity: the identity table of n as the texels of its image -- n wide, n*n high, four f16 bit patterns
+// per texel, entry (r, g, b) at (x = r, y = g + n b), value f16(index / (n - 1)), alpha 1.0.  Host only.
+func Lut3DIdentity(n uint32) ([]uint16, error) {
+	if n < Lut3DMinSize || n > Lut3DMaxSize {
+		return nil, fmt.Errorf("hip_engine: Lut3DIdentity: size outside 2..65")
+	}
+	texels := make([]uint16, 4*int(n)*int(n)*int(n))
+	if C.jh_lut3d_identity(C.uint32_t(n), (*C.uint16_t)(unsafe.Pointer(&texels[0]))) != 0 {
+		return nil, fmt.Errorf("hip_engine: Lut3DIdentity: size outside 2..65")
+	}
+	return texels, nil
+}
+
+// Lut3D is jh_lut3d: the 3D colour lookup table held by the RGBA16F image lut -- size wide and size*size high, Lut3DIdentity's layout,
+// the order of a .cube file -- applied by tetrahedral interpolation to the rectangle of the RGBA16F image src (0 x 0: the whole image)
+// and written to the same rectangle of dst, by the rule of DESIGN.md 5.23: the colour clamped to [0, 1], four entries read per texel,
+// alpha copied.  src may be dst and lut may be src; lut is never dst.  The table is an image like any other: UploadImage writes it, and
+// ColorFilter calls over an identity table bake their chain into it.  Stream-ordered behind the frame, waits for nothing, one kernel
+// launch, no scratch and no tables: always capturable.
+func (e *Engine) Lut3D(src, dst, lut renderer.ImageProxy, size, x, y, width, height uint32) {
+	d := C.jh_lut3d_desc{size: C.uint32_t(size), flags: 0, x: C.uint32_t(x), y: C.uint32_t(y), width: C.uint32_t(width), height: C.uint32_t(height)}
+	e.check(C.jh_lut3d(e.ctx, C.uint64_t(src.ID), C.uint64_t(dst.ID), C.uint64_t(lut.ID), &d), "lut3d")
+}
+
 // UnpackTiles is jh_unpack_tiles: writes the SOLID and RAW tiles of the pack (device memory, packBytes long; untrusted: what
 // fails the checks is ignored) into the frame at dst and touches nothing else.  Stream-ordered.
 func (e *Engine) UnpackTiles(pack unsafe.Pointer, packBytes uint64, dst unsafe.Pointer, dstPitch uint64, width, height, texelBytes uint32) {

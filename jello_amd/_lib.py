@@ -288,6 +288,12 @@ class CLoadYuvDesc(ctypes.Structure):
                 ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
 
 
+class CLut3dDesc(ctypes.Structure):
+    """jh_lut3d_desc (include/jello_hip.h)."""
+    _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32)]
+
+
 class CProfileRecord(ctypes.Structure):
     """jh_profile_record (include/jello_hip.h)."""
     _fields_ = [("stage", ctypes.c_int32), ("pad", ctypes.c_uint32), ("ms", ctypes.c_float)]
@@ -377,6 +383,8 @@ def _declare(L):
         "stats_codes": [ci, u64, vp, vp],
         "load_texel": [ci, ci, u64, vp, vp],
         "load_yuv_codes": [ci, ci, u64, vp, vp, vp, vp],
+        "lut3d_identity": [u32, vp],
+        "lut3d_texels": [u32, vp, vp, u64, vp],
     }
     for name, argtypes in queries.items():
         getattr(L, "jl_" + name).argtypes = argtypes
@@ -397,6 +405,7 @@ def _declare(L):
     hip.jh_image_download.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]
     hip.jh_image_device_ptr.restype = vp
     hip.jh_image_device_ptr.argtypes = [vp, ctypes.c_uint64]
+    hip.jh_image_size.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     hip.jh_sync.argtypes = [vp]
     hip.jh_set_stream.argtypes = [vp, vp]
     hip.jh_set_band.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
@@ -434,6 +443,8 @@ def _declare(L):
     hip.jh_stats.argtypes = [vp, u64, ctypes.POINTER(CStatsDesc), vp]
     hip.jh_load_surface.argtypes = [vp, u64, ctypes.POINTER(CLoadSurfaceDesc)]
     hip.jh_load_yuv.argtypes = [vp, u64, ctypes.POINTER(CLoadYuvDesc)]
+    hip.jh_lut3d.argtypes = [vp, u64, u64, u64, ctypes.POINTER(CLut3dDesc)]
+    hip.jh_debug_lut3d_variant.argtypes = [vp, ci]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]

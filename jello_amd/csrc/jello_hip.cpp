@@ -165,6 +165,7 @@ struct jh_ctx {
         uint32_t key = 0;
         const char* dev = nullptr;
     } turb;
+    int debug_lut3d = 0;  // jh_debug_lut3d_variant (last: the members above stay where they were)
 };
 
 static int flush_held(jh_ctx* ctx);
@@ -798,6 +799,13 @@ int jh_image_free(jh_ctx* ctx, uint64_t id) {
 void* jh_image_device_ptr(jh_ctx* ctx, uint64_t id) {
     const Alloc* a = ctx ? find_alloc(ctx->images, id) : nullptr;
     return a ? a->ptr : nullptr;
+}
+int jh_image_size(jh_ctx* ctx, uint64_t id, uint32_t* width, uint32_t* height) {
+    const Alloc* a = ctx ? find_alloc(ctx->images, id) : nullptr;
+    if (!a) return JH_ERR_INVALID;
+    if (width) *width = a->width;
+    if (height) *height = a->height;
+    return JH_OK;
 }
 
 // ---- dispatch ----
@@ -1672,6 +1680,31 @@ int jh_color_filter(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, c
         });
 }
 
+// 3D LUT (include/jello_hip.h "3D LUT"; the rule: include/jello_lut3d.h; kernels_lut3d.hip)
+int jh_lut3d(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, uint64_t lut_image_id, const jh_lut3d_desc* desc) {
+    static_assert(JH_LUT3D_MIN_SIZE == JLUT_MIN_SIZE && JH_LUT3D_MAX_SIZE == JLUT_MAX_SIZE, "the C ABI's values are the rule's");
+    if (!ctx) return JH_ERR_INVALID;
+    if (!desc) return fail(ctx, JH_ERR_INVALID, "jh_lut3d: null descriptor");
+    Alloc *src = nullptr, *dst = nullptr, *lut = nullptr;
+    if (int rc = rgba16f_images(ctx, "jh_lut3d", {{src_image_id, "source", &src}, {dst_image_id, "destination", &dst}, {lut_image_id, "LUT", &lut}})) return rc;
+    if (const char* why = jlut_check(desc->size, desc->flags)) return fail(ctx, JH_ERR_INVALID, std::string("jh_lut3d: ") + why);
+    if (const char* why = jlut_image_error(desc->size, lut->width, lut->height)) return fail(ctx, JH_ERR_INVALID, std::string("jh_lut3d: ") + why);
+    if (lut == dst) return fail(ctx, JH_ERR_INVALID, "jh_lut3d: the LUT is the destination (the call would read entries it has written)");
+    if (!(ctx->band_row0 == 0u && ctx->band_row1 == 0xffffffffu))
+        return fail(ctx, JH_ERR_INVALID, "jh_lut3d: not in band mode (a band's rows are one rank's, the table the context's)");
+    jimage_rect r;  // (named in the source, where 0 x 0 is the whole of it, and the same texels of the destination)
+    if (int rc = image_call_rect(ctx, "jh_lut3d", {desc->x, desc->y, desc->width, desc->height}, *src, "source ", &r)) return rc;
+    if (!jimage_rect_inside(r, dst->width, dst->height)) return refuse_rect(ctx, "jh_lut3d", JIMAGE_RECT_OUTSIDE, "destination ");
+    if (jimage_rect_empty(r)) return JH_OK;  // (an image without texels)
+    if (ctx->debug_lut3d == 2 && desc->size > JLUT_STAGED_MAX_SIZE) return fail(ctx, JH_ERR_INVALID, "jh_lut3d: jh_debug_lut3d_variant asks for a table in LDS, and this one does not fit");
+    return post_render_call(ctx, "lut3d", [&] {
+        const void* table = content_or_null(*lut);  // (taken first: the table may be the source, never the destination)
+        ImageViews v;
+        if (int rc = image_call_views(ctx, src, dst, r, &v)) return rc;
+        return launch_status(ctx, "jh_lut3d", jh_lut3d_launch(ctx->stream, v.from, v.to, r, table, desc->size, ctx->debug_lut3d, ctx->num_cus));
+    });
+}
+
 // morphology (include/jello_hip.h "Morphology"; the descriptor, the planes and the key: include/jello_morph.h; kernels_morph.hip)
 int jh_morphology(jh_ctx* ctx, uint64_t src_image_id, uint64_t dst_image_id, const jh_morph_desc* desc) {
     static_assert(JH_MORPH_ERODE == JMORPH_ERODE && JH_MORPH_DILATE == JMORPH_DILATE && JH_MORPH_EDGE_ZERO == JMORPH_EDGE_ZERO &&
@@ -2063,6 +2096,12 @@ int jh_debug_flatten_regions(jh_ctx* ctx, uint32_t flags) {
     if (!ctx) return JH_ERR_INVALID;
     ctx->debug_flatten = flags;
     ctx->generation++;  // (a captured graph holds the old kernel arguments)
+    return JH_OK;
+}
+// Tests and timing: the instantiation jh_lut3d launches (0: the launcher's choice, 1: gathers from memory, 2: the table in LDS).
+int jh_debug_lut3d_variant(jh_ctx* ctx, int variant) {
+    if (!ctx || variant < 0 || variant > 2) return JH_ERR_INVALID;
+    ctx->debug_lut3d = variant;
     return JH_OK;
 }
 // Blend-stack saves the fine stage dropped since the last reset because jh_set_clip_depth_hint promised a shallower scene than

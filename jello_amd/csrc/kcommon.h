@@ -418,6 +418,7 @@ int jh_stats_launch(hipStream_t stream, jimage_src src, jimage_rect rect, const 
 int jh_load_surface_launch(hipStream_t stream, const void* src, uint64_t pitch, jimage_dst dst, jimage_rect rect, int format, int alpha, int num_cus);
 int jh_load_yuv_launch(hipStream_t stream, const void* const* planes, const uint64_t* pitches, jimage_dst dst, jimage_rect rect, int layout, int matrix,
                        int range, int transfer, int chroma, int num_cus);
+int jh_lut3d_launch(hipStream_t stream, jimage_src src, jimage_dst dst, jimage_rect rect, const void* lut, uint32_t n, int variant, int num_cus);
 int jh_selftest_math_launch(hipStream_t stream, int op, const float* a, const float* b, float* out, uint32_t n);
 int jh_selftest_atomics_launch(hipStream_t stream, int form, uint32_t seed, uint32_t n_waves);
 }

@@ -19,7 +19,7 @@ from .imagecalls import (  # noqa: F401
     lighting_tables, TurbulenceKind, TURBULENCE_MAX_OCTAVES, _pair, _turbulence_desc, turbulence_plan, turbulence_tables, DisplaceChannel,
     DISPLACE_STRAIGHT, AFFINE_IDENTITY, displace_offset, _displace_desc, ShadowFlags, SHADOW_MAX_EXTENT, _shadow_desc, shadow_plan, shadow_bounds,
     box_shadow_geometry, PERSPECTIVE_STRAIGHT, PROJECTIVE_IDENTITY, _matrix9, perspective_plan, perspective_bounds, _perspective_desc, ColorSpace, ColorFunc, COLOR_CLAMP, COLOR_MAX_VALUES, COLOR_POST_SHIFT,
-    IDENTITY_MATRIX, _color_desc, color_tables, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, DISTANCE_MAX_RADIUS, _distance_desc,
+    IDENTITY_MATRIX, _color_desc, color_tables, _lut3d_desc, LUT3D_MIN_SIZE, LUT3D_MAX_SIZE, composite_clip, DistanceWhich, DistanceEdge, DistanceFlags, DISTANCE_MAX_RADIUS, _distance_desc,
     distance_plan, LoadAlpha, ChromaFilter, LOAD_TRANSFER, _load_surface_desc, _load_yuv_desc, _surface_array_source, yuv_plane_shapes, packed_plane_offsets, _yuv_array_source, load_texels, load_yuv_codes,
     StatsWhat, StatsPopulation, StatsTransfer, STATS_MAX_TEXELS, STATS_MAX_PARTIALS, STATS_RECORD_BYTES, _stats_desc, stats_plan, stats_codes,
 )
@@ -431,6 +431,30 @@ class Engine:
         dst = src_id if dst_id is None else dst_id
         self._check(self.hip.jh_color_filter(self.ctx, src_id, dst, ctypes.byref(d)), "color_filter", invalid=ValueError)
 
+    def lut3d(self, src_id, lut_id, dst_id=None, rect=None):
+        """jh_lut3d: the 3D colour lookup table held by the RGBA16F image `lut_id` -- N texels wide and N * N high, 2 <= N <= 65,
+        entry (r, g, b) at (x = r, y = g + N b), as jello_amd.lut3d.as_image lays a table out -- applied by tetrahedral
+        interpolation (the rule: DESIGN.md 5.23) to the rectangle `rect` = (x, y, width, height) of the RGBA16F image `src_id` (None:
+        the whole image), written to the same rectangle of `dst_id` -- None: in place.  The colour is clamped to [0, 1] before the
+        lookup, alpha is copied.  N is read from the LUT image's width.  The table is an image like any other: upload_image writes
+        it, every image call can (bake_lut), it may be the source, never the destination.  Stream-ordered, capturable at any time,
+        returns nothing; ValueError for a call the rule refuses."""
+        n = ctypes.c_uint32(0)  # (an unknown id leaves 0, and the call refuses the id before it looks at the size)
+        self.hip.jh_image_size(self.ctx, lut_id, ctypes.byref(n), None)
+        d = _lut3d_desc(n.value, rect)
+        dst = src_id if dst_id is None else dst_id
+        self._check(self.hip.jh_lut3d(self.ctx, src_id, dst, lut_id, ctypes.byref(d)), "lut3d", invalid=ValueError)
+
+    def bake_lut(self, lut_id, n, steps):
+        """A chain of colour calls as ONE table: uploads lut3d.identity(n) as the RGBA16F image `lut_id` (n x n * n), then runs each
+        of `steps` -- a dict of color_filter's keywords but the ids, e.g. colorfilter.sepia(1) -- over it in place.  lut3d(image,
+        lut_id) then applies the whole chain in one launch, up to the table's resolution: exactly for chains that are affine per
+        cell, by tetrahedral interpolation between the entries otherwise."""
+        from . import lut3d as _lut3d
+        self.upload_image(lut_id, _lut3d.as_image(_lut3d.identity(n)))
+        for step in steps:
+            self.color_filter(lut_id, **step)
+
     def morphology(self, src_id, dst_id=None, op=MorphOp.DILATE, radius=1, edge=MorphEdge.ZERO, rect=None, premultiplied=True):
         """jh_morphology: the RGBA16F image `src_id` eroded or dilated by a box (the rule: DESIGN.md 5.11) into the image `dst_id`
         of the same size -- None: in place.  `radius` is a scalar or (rx, ry), integers in [0, 255]: the window of a texel is
@@ -812,7 +836,7 @@ class Engine:
 
     def capture(self, recording, out_device_ptr=None, surface=None, pack=None, yuv=None, blur=None, composite=None, resample=None, color=None,
                 morphology=None, warp=None, convolve=None, lighting=None, turbulence=None, displace=None, shadow=None, perspective=None, distance=None,
-                load_surface=None, load_yuv=None, stats=None):
+                load_surface=None, load_yuv=None, stats=None, lut3d=None):
         """Capture one dispatch-only replay of `recording` into a hipGraph; returns an opaque handle for replay().
         The recording must have been run once (buffers + scratch exist).  surface=(device pointer, pitch, Surface format)
         appends the blit of the frame's target into that surface (one more kernel launch).
@@ -875,7 +899,9 @@ class Engine:
         stats=dict(out=device pointer, ...) (the other keywords of stats() but the id, optional) writes the record of the frame's
         target -- as it is after the render and after the other image keywords of the same capture that work on it in place; the
         target itself, not the image a lighting=, convolve=, resample=, warp=, displace= or perspective= wrote -- into `out` on every
-        replay, before the surface, YUV or pack conversion (two more launches); one stats() call must have run once eagerly."""
+        replay, before the surface, YUV or pack conversion (two more launches); one stats() call must have run once eagerly.
+        lut3d=dict(lut=image id, ...) (the other keywords of lut3d() but the ids, optional) puts the frame's target through that
+        table in place, right after color= and before lighting= (one more launch, nothing to run eagerly first)."""
         for name, step, key in (("load_surface", load_surface, "pixels"), ("load_yuv", load_yuv, "planes")):
             if step is None:
                 continue
@@ -909,6 +935,8 @@ class Engine:
                 self.composite(composite["src"], t["id"], **{k: v for k, v in composite.items() if k != "src"})
             if color is not None:
                 self.color_filter(t["id"], **color)
+            if lut3d is not None:
+                self.lut3d(t["id"], lut3d["lut"], **{k: v for k, v in lut3d.items() if k != "lut"})
             if lighting is not None:
                 self.lighting(t["id"], lighting["dst"], **{k: v for k, v in lighting.items() if k != "dst"})
                 t = {"id": lighting["dst"], "width": t["width"], "height": t["height"]}

@@ -8,7 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
-from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CDistanceDesc, CDistPlan, CLightingDesc, CLightPlan, CLoadSurfaceDesc, CLoadYuvDesc, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CStatsDesc, CStatsPlan, CStatsRecord, CTurbPlan, CTurbulenceDesc, CWarpDesc
+from ._lib import CBlurDesc, CColorDesc, CCompositeDesc, CConvolveDesc, CDisplaceDesc, CDistanceDesc, CDistPlan, CLightingDesc, CLightPlan, CLoadSurfaceDesc, CLoadYuvDesc, CLut3dDesc, CMorphDesc, CPerspectiveDesc, CResampleDesc, CShadowDesc, CShadowPlan, CStatsDesc, CStatsPlan, CStatsRecord, CTurbPlan, CTurbulenceDesc, CWarpDesc
 
 
 def _query(name, twin=False):
@@ -788,6 +788,45 @@ def color_tables(funcs=None, space=ColorSpace.LINEAR, clamp=True, twin=False):
         raise ValueError("color_tables: unknown space or func type, n = 0 or n > 64 values, or a parameter that is not finite")
     w = which.value
     return ({c: pre[c] for c in range(3) if w >> c & 1}, {i: post[i] for i in range(4) if w >> (COLOR_POST_SHIFT + i) & 1}, w)
+
+
+LUT3D_MIN_SIZE = 2  # JH_LUT3D_MIN_SIZE
+LUT3D_MAX_SIZE = 65  # JH_LUT3D_MAX_SIZE
+
+
+def _lut3d_desc(size, rect):
+    """jh_lut3d_desc: the table's N and the rectangle; what the rule refuses is left for the call to refuse."""
+    return CLut3dDesc(int(size), 0, *_rect(rect))
+
+
+def lut3d_identity(n, twin=False):
+    """jh_lut3d_identity (twin: jl_lut3d_identity, the host twin): the identity table of the LUT rule as the
+    (n * n, n, 4) uint16 image of f16 bit patterns jh_lut3d takes -- entry (r, g, b) at [g + n * b, r], value f16(index / (n - 1)),
+    alpha 1.0.  No GPU needed.  ValueError for an n outside 2..65."""
+    n = int(n)
+    if not LUT3D_MIN_SIZE <= n <= LUT3D_MAX_SIZE:
+        raise ValueError("jh_lut3d_identity: size outside 2..65")
+    out = np.empty((n * n, n, 4), np.uint16)
+    if _query("lut3d_identity", twin)(n, out.ctypes.data) != 0:
+        raise ValueError("jh_lut3d_identity: size outside 2..65")
+    return out
+
+
+def lut3d_texels(lut_image, texels, twin=False):
+    """jh_lut3d_texels (twin: jl_lut3d_texels): the LUT rule on the host -- `texels`, (..., 4) uint16 f16 bit
+    patterns, through the table `lut_image`, the (n * n, n, 4) uint16 image; returns the same shape.  No GPU needed.  ValueError for
+    a table that is not (n * n, n, 4) with n in 2..65."""
+    lut = np.ascontiguousarray(lut_image, np.uint16)
+    n = lut.shape[1] if lut.ndim == 3 else 0
+    if lut.ndim != 3 or lut.shape != (n * n, n, 4) or not LUT3D_MIN_SIZE <= n <= LUT3D_MAX_SIZE:
+        raise ValueError("jh_lut3d_texels: the table is not an (n * n, n, 4) image with n in 2..65")
+    t = np.ascontiguousarray(texels, np.uint16)
+    if t.shape[-1:] != (4,):
+        raise ValueError("jh_lut3d_texels: texels of four channels")
+    out = np.empty_like(t)
+    if _query("lut3d_texels", twin)(n, lut.ctypes.data, t.ctypes.data, t.size // 4, out.ctypes.data) != 0:
+        raise ValueError("jh_lut3d_texels: size outside 2..65")
+    return out
 
 
 def composite_clip(src_size, dst_size, src_rect=None, offset=(0, 0)):

@@ -306,8 +306,27 @@ static void load() {
     CHECK(rgb2.untouched());
 }
 
+static void lut3d() {
+    const uint32_t n = 3u;
+    Buf<uint16_t> table(4u * n * n * n);
+    CHECK(!jq_lut3d_identity(n, table) && !table.untouched() && table[0] == 0u && table[3] == 0x3c00u && table[4u * 26u] == 0x3c00u && table[4u] == 0x3800u);
+    Buf<uint16_t> in(4u * 5u), out(4u * 5u);
+    for (uint32_t i = 0; i < 20u; i++) in[i] = (uint16_t)(0x3000u + 97u * i);
+    CHECK(!jq_lut3d_texels(n, table, in, 5u, out) && !out.untouched());
+    CHECK(!jq_lut3d_texels(n, table, nullptr, 0u, nullptr));  // (no texels: only the table is needed)
+    Buf<uint16_t> most(4u * JLUT_MAX_SIZE * JLUT_MAX_SIZE * JLUT_MAX_SIZE), least(4u * 8u);
+    CHECK(!jq_lut3d_identity(JLUT_MAX_SIZE, most) && !jq_lut3d_identity(JLUT_MIN_SIZE, least) && !jq_lut3d_texels(JLUT_MAX_SIZE, most, in, 5u, out));
+    Buf<uint16_t> t2(4u * 8u), o2(4u * 5u);
+    CHECK(is(jq_lut3d_identity(n, nullptr), "null argument") && is(jq_lut3d_identity(1u, t2), "size outside 2..65") && jq_lut3d_identity(66u, t2) && jq_lut3d_identity(0u, t2));
+    CHECK(is(jq_lut3d_texels(n, nullptr, in, 5u, o2), "null argument") && is(jq_lut3d_texels(n, table, nullptr, 5u, o2), "null argument") &&
+          is(jq_lut3d_texels(n, table, in, 5u, nullptr), "null argument") && is(jq_lut3d_texels(1u, table, in, 5u, o2), "size outside 2..65") &&
+          jq_lut3d_texels(66u, table, in, 5u, o2));
+    CHECK(t2.untouched() && o2.untouched());
+}
+
 int main() {
     load();
+    lut3d();
     blur();
     resample();
     color();
