@@ -1642,6 +1642,14 @@ __global__ __launch_bounds__(64 * FINE_WG_WAVES(CLIPS)) __attribute__((amdgpu_wa
             for (int k = 0; k < 4; k++) rgba[k] = FINE_SKIP == 5 ? v4(rgba[k].x + area[k], rgba[k].y + fg.x, rgba[k].z + fg.y, rgba[k].w + fg.z * fg.w) : over(rgba[k], fg, area[k]);
         }
     }
+    if constexpr (CLIPS) {
+        // A list that ends with layers still pending (BEGIN_CLIPs that nothing was drawn behind and no END_CLIP closed): in the WGSL
+        // the innermost of them started from zero and that is what is stored.  The saves themselves have no reader any more.
+        if (pushed_depth < clip_depth) {  // uniform
+#pragma unroll
+            for (int k = 0; k < 4; k++) rgba[k] = v4(0, 0, 0, 0);
+        }
+    }
 #ifdef FINE_TIMING
     if (hint_overflow != nullptr && lane == 0u) {
         unsigned long long* t = (unsigned long long*)(hint_overflow + 8);
