@@ -1534,6 +1534,14 @@ int jh_debug_poison_scratch(jh_ctx* ctx, int byte);
 /* tests and timing: which instantiation jh_lut3d launches -- 0 the launcher's choice (tables of N <= 17 in LDS), 1 always gathered
    from memory, 2 always from LDS (a call with a larger table is then refused).  The results do not depend on it. */
 int jh_debug_lut3d_variant(jh_ctx* ctx, int variant);
+/* tests: one launch of the single-pass exclusive u32 scan that flatten, path_count and jh_dash allocate through, on the context's
+   stream and scratch: out[i] = in[0] + in[stride] + ... + in[(i - 1) stride] mod 2^32 for i < n.  `in_id` and `out_id` are context
+   buffers of at least n_max * stride and n_max words.  n = n_max, or min(n_max, word `count_word` of the buffer `count_id`) when
+   count_id != 0: the count is read on the device.  With total_id != 0 the sum of the n inputs goes to word `total_word` of that
+   buffer.  Words of `out` from n on are not written.  Stream-ordered and capturable (after one eager call of at least this n_max);
+   JH_ERR_INVALID for an unknown id, a buffer that is too small or a stride of 0. */
+int jh_debug_scan_u32(jh_ctx* ctx, uint64_t in_id, uint64_t out_id, uint32_t stride, uint32_t n_max, uint64_t count_id, uint32_t count_word,
+                      uint64_t total_id, uint32_t total_word);
 
 /* ---- introspection ---- */
 int jh_device_info(jh_ctx* ctx, char* name, int name_len, int* compute_units, uint64_t* total_mem);

@@ -446,6 +446,7 @@ def _declare(L):
     hip.jh_lut3d.argtypes = [vp, u64, u64, u64, ctypes.POINTER(CLut3dDesc)]
     hip.jh_debug_lut3d_variant.argtypes = [vp, ci]
     hip.jh_debug_unpack_rejects.argtypes = [vp, ctypes.POINTER(u32), ci]
+    hip.jh_debug_scan_u32.argtypes = [vp, u64, u64, u32, u32, u64, u32, u64, u32]
     hip.jh_image_write.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint64]
     hip.jh_buffer_import.argtypes = [vp, ctypes.c_uint64, vp, ctypes.c_uint64]
     hip.jh_graph_begin.argtypes = [vp]

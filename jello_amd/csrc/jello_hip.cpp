@@ -2104,6 +2104,28 @@ int jh_debug_lut3d_variant(jh_ctx* ctx, int variant) {
     ctx->debug_lut3d = variant;
     return JH_OK;
 }
+// Tests: jh_scan_u32 -- the look-back scan has no stage id -- on the context's stream and scratch, on context buffers.  The checks
+// are what keeps the kernel inside them: it reads in[(n - 1) * stride] and writes out[n - 1] at most, n <= n_max.
+int jh_debug_scan_u32(jh_ctx* ctx, uint64_t in_id, uint64_t out_id, uint32_t stride, uint32_t n_max, uint64_t count_id, uint32_t count_word,
+                      uint64_t total_id, uint32_t total_word) {
+    if (!ctx) return JH_ERR_INVALID;
+    JH_FLUSH(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const Alloc* in = find_alloc(ctx->buffers, in_id);
+    const Alloc* out = find_alloc(ctx->buffers, out_id);
+    const Alloc* count = count_id ? find_alloc(ctx->buffers, count_id) : nullptr;
+    const Alloc* total = total_id ? find_alloc(ctx->buffers, total_id) : nullptr;
+    if (!in || !out || (count_id && !count) || (total_id && !total)) return fail(ctx, JH_ERR_INVALID, "jh_debug_scan_u32: unknown buffer");
+    if (stride == 0u || in->size < (uint64_t)n_max * stride * 4u || out->size < (uint64_t)n_max * 4u || in == out ||
+        (count && count->size < ((uint64_t)count_word + 1u) * 4u) || (total && total->size < ((uint64_t)total_word + 1u) * 4u))
+        return fail(ctx, JH_ERR_INVALID, "jh_debug_scan_u32: stride 0 or a buffer too small for n_max");
+    static const std::vector<JhBound> none;
+    const JhResult r = jh_scan_u32(make_launch(ctx, 0, 0, 0, none), (const uint32_t*)in->ptr, stride, (uint32_t*)out->ptr, n_max,
+                                   count ? (const uint32_t*)count->ptr + count_word : nullptr, total ? (uint32_t*)total->ptr + total_word : nullptr);
+    if (r != JH_L_OK) return launch_result(ctx, -1, r);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? hip_fail(ctx, e, "jh_debug_scan_u32") : (int)JH_OK;
+}
 // Blend-stack saves the fine stage dropped since the last reset because jh_set_clip_depth_hint promised a shallower scene than
 // it got (every one of them is a wrong pixel colour): 0 for every correct hint.  Synchronises the stream.
 int jh_debug_clip_hint_overflows(jh_ctx* ctx, uint32_t* count, int reset) {
