@@ -215,8 +215,11 @@ struct JhImageDesc {
 //             (jh_dash, a call outside the frame's stages, uses A: the uploaded job, B: lengths / segment, C: counts and relocation
 //              flags / segment, D: their scans, E: whole / merged / subpath, and SCAN_TMP through jh_scan_u32)
 //   SCAN_TMP  (jh_scan_u32's control words and tile descriptors, whichever stage scans: flatten, path_count)   self-cleaned
-//   A         counts / slot     wg totals   counts      wide list     counts / line              counts + wg totals
-//   B         bases / slot                  wg totals                 bases / line               scratch PTCL (clips)
+//   A         counts / slot     wg totals   counts      wide list     sums / wave of 64 lines    counts + wg totals
+//                                                                     + the number of such waves
+//   B         bases / slot                  wg totals                 bases / wave of 64 lines   scratch PTCL (clips)
+//             (path_count kept a count and a base per LINE here until its scan went over the wave sums: 2 x 4 B x the line buffer's
+//              capacity; A and B are now as large as flatten's tag slots or coarse make them)
 //   C         FlTemp.sinfo                                            tile_of / crossing         relocation side arrays
 //   D         FlTemp.recs                                             list / crossing                                 clip levels
 //   E                                                                 list_base / tile

@@ -362,9 +362,30 @@ JD LineSetup line_setup(const JlLineSoup& line, const Buf<JlPath>& paths) {
     return r;
 }
 
-// pass 1: crossings per line
+// Which lines path_count counts, and with how many crossings: ONE rule for k_pc_count and k_pc_emit.  k_pc_emit places a line's
+// crossings at (the scanned sum of the waves in front) + (the wave prefix of the counts it derives ITSELF), so a line that one
+// kernel counted and the other did not would shift every crossing behind it.  Both kernels take their line limit from
+// pc_line_limit (0 when an earlier stage failed: the indirect count is 0 then) and every line's count from pc_line_count.
+JD uint32_t pc_line_limit(const JlBump* __restrict__ bump, uint32_t ind_x, uint32_t lines_cap) {
+    return umin_(umin_(bump->lines, lines_cap), ind_x * JL_WG);
+}
+JD uint32_t pc_waves(uint32_t n_lines) { return (n_lines >> 6) + ((n_lines & 63u) != 0u ? 1u : 0u); }  // waves of 64 lines that hold lines
+// -> crossings of line gid (0: past the limit, outside the buffer, or nothing to emit); s.valid and pix (~0u) say which
+JD uint32_t pc_line_count(const Buf<JlLineSoup>& lines, const Buf<JlPath>& paths, uint32_t gid, uint32_t n_lines, LineSetup& s, uint32_t& pix) {
+    s.valid = false;
+    pix = 0xffffffffu;
+    if (gid < n_lines && lines.ok(gid)) {
+        pix = lines.p[gid].path_ix;
+        s = line_setup(lines.p[gid], paths);
+    }
+    return s.valid ? s.imax - s.imin : 0u;
+}
+
+// pass 1: crossings per WAVE of 64 consecutive lines (wave w of the line order = lines [64 w, 64 w + 64)), and per path.
+// The scan behind it runs over the wave sums only (1/64 of the words a scan of per-line counts moved); k_pc_emit, which has the
+// same wave = 64 lines mapping and derives every line's count again anyway, adds the prefix inside the wave itself.
 __global__ __launch_bounds__(JL_WG) void k_pc_count(const JlBump* __restrict__ bump, const JlIndirectCount* __restrict__ ind, Buf<JlLineSoup> lines,
-                                                    Buf<JlPath> paths, uint32_t* __restrict__ counts, uint32_t counts_n,
+                                                    Buf<JlPath> paths, uint32_t* __restrict__ wsum, uint32_t lines_cap, uint32_t* __restrict__ n_waves_out,
                                                     uint32_t* __restrict__ zero, uint32_t zero_n, uint32_t* __restrict__ ptotal, uint32_t ptotal_n,
                                                     unsigned long long* __restrict__ bd_ctr,
                                                     JlIndirectCount* __restrict__ setup_out) {  // != nullptr: path_count_setup was held back (jello_hip.cpp,
@@ -374,7 +395,6 @@ __global__ __launch_bounds__(JL_WG) void k_pc_count(const JlBump* __restrict__ b
     // stage that follows: kcommon.h, JH_CLEAN_*)
     for (uint32_t i = blockIdx.x * JL_WG + threadIdx.x; i < zero_n; i += gridDim.x * JL_WG) zero[i] = 0u;
     if (blockIdx.x == 0u && threadIdx.x == 0u) *bd_ctr = 0ull;
-    uint32_t n_lines = umin_(bump->lines, counts_n);
     uint32_t ind_x;
     if (setup_out) {  // (every thread derives the count itself; one of them also stores it for the kernels that follow)
         ind_x = bump->failed != 0u ? 0u : (bump->lines + (JL_WG - 1u)) / JL_WG;
@@ -382,22 +402,21 @@ __global__ __launch_bounds__(JL_WG) void k_pc_count(const JlBump* __restrict__ b
     } else {
         ind_x = ind->x;
     }
-    uint32_t n_threads = umin_(ind_x * JL_WG, counts_n);
+    const uint32_t n_lines = pc_line_limit(bump, ind_x, lines_cap);
+    // (the scan's element count: written every frame before the scan reads it, so there is nothing to clean)
+    if (blockIdx.x == 0u && threadIdx.x == 0u) *n_waves_out = pc_waves(n_lines);
     const uint32_t lane = lane_id();
     for (uint32_t g0 = blockIdx.x * JL_WG + (threadIdx.x & ~63u); g0 < n_lines; g0 += gridDim.x * JL_WG) {  // uniform per wave
         const uint32_t gid = g0 + lane;
-        uint32_t c = 0u, pix = 0xffffffffu;
-        if (gid < n_lines && gid < n_threads && lines.ok(gid)) {
-            pix = lines.p[gid].path_ix;
-            LineSetup s = line_setup(lines.p[gid], paths);
-            if (s.valid) c = s.imax - s.imin;
-        }
-        if (gid < n_lines) counts[gid] = c;
+        LineSetup s;
+        uint32_t pix;
+        const uint32_t c = pc_line_count(lines, paths, gid, n_lines, s, pix);
         // Crossings per PATH (k_pc_emit: a path of more than PC_BIG_PATH crossings takes the list route).  Lines are in path order,
         // so a wave's lines are a few runs of equal path index: the run's sum comes out of one wave prefix sum, its last lane
         // sends ONE atomic.  (Round 5: the sums used to be derived from first / last line of every path by a launch of its own,
         // k_pc_paths, behind the scan; the ranges it also produced are written by k_pc_emit in passing now.)
         const uint32_t incl = wave_incl_scan_u32(c);
+        if (lane == 63u) wsum[g0 >> 6] = incl;  // (every wave that holds lines writes its word: g0 < n_lines <= lines_cap)
         const uint32_t prev = lane_prev(pix, ~pix);  // (lane 0: a head)
         const uint64_t heads = __builtin_amdgcn_ballot_w64(lane == 0u || pix != prev);
         const uint32_t leader = 63u - (uint32_t)__builtin_clzll(heads & ((2ull << lane) - 1ull));  // nearest head at or before the lane
@@ -411,8 +430,7 @@ __global__ __launch_bounds__(JL_WG) void k_pc_count(const JlBump* __restrict__ b
 // the contiguous range [pstart[P], pend[P]) of seg_counts.  Both arrays are zeroed before (paths without lines); k_pc_emit
 // writes them at the first and the last line of every path.
 // crossings [ps, pe) of path P (empty if it has no line)
-JD void path_range(uint32_t P, const uint32_t* __restrict__ pstart, const uint32_t* __restrict__ pend, const uint32_t*, const uint32_t*,
-                   uint32_t& ps, uint32_t& pe) {
+JD void path_range(uint32_t P, const uint32_t* __restrict__ pstart, const uint32_t* __restrict__ pend, uint32_t& ps, uint32_t& pe) {
     ps = pstart[P];
     pe = pend[P];
 }
@@ -493,33 +511,30 @@ JD void emit_crossing(const EmitCtx& c, const LineSetup& s, uint32_t i, uint32_t
 
 __global__ __launch_bounds__(JL_WG) void k_pc_emit(const JlConfig* __restrict__ cfg, const JlBump* __restrict__ bump,
                                                    const JlIndirectCount* __restrict__ ind, Buf<JlLineSoup> lines, Buf<JlPath> paths, Buf<JlTile> tile,
-                                                   Buf<JlSegmentCount> seg_counts, const uint32_t* __restrict__ seg_bases, uint32_t bases_n,
+                                                   Buf<JlSegmentCount> seg_counts, const uint32_t* __restrict__ wbase, uint32_t lines_cap,
                                                    uint2* __restrict__ tile_of, uint32_t* __restrict__ keys, uint32_t* __restrict__ kbig,
                                                    uint32_t tile_of_n, uint32_t* __restrict__ pfirst, uint32_t* __restrict__ plast,
                                                    const uint32_t* __restrict__ ptotal, uint32_t n_paths, uint32_t* __restrict__ gate) {
     EmitCtx c;
     c.cfg = cfg; c.bump = bump; c.tile = tile; c.seg_counts = seg_counts; c.tile_of = tile_of; c.keys = keys; c.kbig = kbig;
     c.tile_of_n = tile_of_n;
-    const uint32_t n_lines = umin_(umin_(bump->lines, bases_n), ind->x * JL_WG);
+    const uint32_t n_lines = pc_line_limit(bump, ind->x, lines_cap);  // (k_pc_count's limit: see pc_line_limit)
     const uint32_t lane = lane_id();
     for (uint32_t g0 = blockIdx.x * JL_WG + (threadIdx.x & ~63u); g0 < n_lines; g0 += gridDim.x * JL_WG) {  // uniform per wave
         const uint32_t gid = g0 + lane;
-        LineSetup s;
-        s.valid = false;
-        uint32_t P = 0xffffffffu;  // (a line outside the buffer)
+        const uint32_t wave_base = wbase[g0 >> 6];  // crossings of all the waves of lines in front (uniform; g0 < n_lines <= lines_cap)
         // (the path indices of the lines next door -- lanes 0 and 63 need them for the path ranges below -- are requested with the
         // wave's own lines, not behind line_setup's dependent loads: a round trip less)
         uint32_t edgeP = 0xffffffffu;
         if (lane == 0u && gid > 0u && gid - 1u < n_lines && lines.ok(gid - 1u)) edgeP = lines.p[gid - 1u].path_ix;
         if (lane == 63u && gid + 1u < n_lines && lines.ok(gid + 1u)) edgeP = lines.p[gid + 1u].path_ix;
-        if (gid < n_lines && lines.ok(gid)) {
-            P = lines.p[gid].path_ix;
-            s = line_setup(lines.p[gid], paths);
-        }
+        LineSetup s;
+        uint32_t P;  // (~0u: a line outside the buffer)
+        const uint32_t cnt = pc_line_count(lines, paths, gid, n_lines, s, P);
+        // the line's first crossing: the wave's base + the crossings of the lanes below (the counts k_pc_count summed, by the same rule)
+        const uint32_t seg_base = wave_base + (wave_incl_scan_u32(cnt) - cnt);
         // big path (or a path index outside the table): arrival slots by atomics, as the scatter pass / k_pc_rank expect
         bool big = true;
-        uint32_t seg_base = 0u;
-        if (gid < n_lines) seg_base = seg_bases[gid];
         if (s.valid) {
             if (P < n_paths) big = ptotal[P] > PC_BIG_PATH;  // (= pend - pstart: the crossings of all of the path's lines)
         } else {
@@ -531,7 +546,7 @@ __global__ __launch_bounds__(JL_WG) void k_pc_emit(const JlConfig* __restrict__ 
             if (lane == 63u) nextP = edgeP;
             if (gid < n_lines && P < n_paths) {
                 if (P != prevP) pfirst[P] = seg_base;
-                if (P != nextP) plast[P] = seg_base + (s.valid ? s.imax - s.imin : 0u);
+                if (P != nextP) plast[P] = seg_base + cnt;
             }
         }
         // open the gate of the list route: the number of tiles its list-base scan has to cover (one lane per wave, and
@@ -616,8 +631,7 @@ JD void pc_scatter_part(const JlConfig* __restrict__ cfg, const JlBump* __restri
                         uint32_t* __restrict__ gate, uint32_t* __restrict__ dense, uint32_t dense_cap, uint32_t block, uint32_t blocks);
 __global__ __launch_bounds__(JL_WG) void k_pc_rank_small(const JlConfig* __restrict__ cfg, const JlBump* __restrict__ bump, Buf<JlTile> tile,
                                                          const uint32_t* __restrict__ keys, uint32_t n_cap, const uint32_t* __restrict__ pfirst,
-                                                         const uint32_t* __restrict__ plast, const uint32_t* __restrict__ counts,
-                                                         const uint32_t* __restrict__ seg_bases, uint32_t n_paths,
+                                                         const uint32_t* __restrict__ plast, uint32_t n_paths,
                                                          Buf<JlSegmentCount> seg_counts, PcScatterArgs sc, uint32_t* __restrict__ ptotal_zero,
                                                          uint32_t ptotal_words) {
     // (the crossings-per-path sums have served k_pc_emit: back to zero for the next frame's atomics -- kcommon.h, JH_CLEAN_*)
@@ -643,7 +657,7 @@ __global__ __launch_bounds__(JL_WG) void k_pc_rank_small(const JlConfig* __restr
     auto load_ranges = [&](uint32_t task, uint32_t& ps, uint32_t& pe) {
         ps = 0u; pe = 0u;
         const uint32_t P = task * PCR_K + lane;
-        if (task < n_tasks && lane < PCR_K && P < n_paths) path_range(P, pfirst, plast, counts, seg_bases, ps, pe);
+        if (task < n_tasks && lane < PCR_K && P < n_paths) path_range(P, pfirst, plast, ps, pe);
     };
     uint32_t t_ps = 0u, t_pe = 0u;   // lane i < PCR_K: crossings [t_ps, t_pe) of path task * PCR_K + i (t_pe cut to the buffer)
     uint64_t todo = 0ull;            // paths of the task still to rank (small, non-empty)
@@ -1136,8 +1150,10 @@ JhResult jh_launch_path_count(const JhLaunch& L) {
     auto segc = L.buf<JlSegmentCount>(PC_SEGC);
     auto ind = (const JlIndirectCount*)L.indirect;
     uint32_t lines_cap = lines.n, seg_cap = segc.n, tiles_cap = tile.n;
-    uint32_t* counts = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_A, (uint64_t)lines_cap * 4);
-    uint32_t* bases = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_B, (uint64_t)lines_cap * 4);
+    // one crossing sum per wave of 64 lines, their scan, and behind the sums (on a 64-byte boundary) the number of waves that hold lines
+    const uint32_t waves_cap = (uint32_t)(((uint64_t)lines_cap + 63u) / 64u), waves_pad = (waves_cap + 15u) & ~15u;
+    uint32_t* wsum = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_A, ((uint64_t)waves_pad + 16u) * 4);
+    uint32_t* wbase = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_B, (uint64_t)waves_pad * 4);
     uint2* tile_of = (uint2*)jh_scratch_get(L.scratch, JH_SCR_C, (uint64_t)seg_cap * 8);
     uint32_t* list = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_D, (uint64_t)seg_cap * 4);
     uint32_t* list_base = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_E, (uint64_t)tiles_cap * 4);
@@ -1150,7 +1166,8 @@ JhResult jh_launch_path_count(const JhLaunch& L) {
     // [pstart | pend | gate, number of dense tiles ... | crossings per path]: zeroed every frame (by the launch in front of k_pc_count's atomics
     // on the last part, see below) (the variables below keep the names of the path_range parameters)
     uint32_t* prange = (uint32_t*)jh_scratch_get(L.scratch, JH_SCR_I, ((uint64_t)n_paths * 3 + 64) * 4);
-    if (!counts || !bases || !tile_of || !list || !list_base || !keys || !kbig || !prange) return JH_L_SCRATCH;
+    if (!wsum || !wbase || !tile_of || !list || !list_base || !keys || !kbig || !prange) return JH_L_SCRATCH;
+    uint32_t* n_waves_dev = wsum + waves_pad;  // written by k_pc_count, the scan's element count
     uint32_t *pfirst = prange, *plast = prange + n_paths, *gate = prange + 2 * (size_t)n_paths;
     uint32_t gl = stride_grid(L, lines_cap), gs = stride_grid(L, seg_cap);
     unsigned long long* bd_ctr = (unsigned long long*)jh_scratch_get(L.scratch, JH_SCR_BD_CTR, 64);
@@ -1161,12 +1178,12 @@ JhResult jh_launch_path_count(const JhLaunch& L) {
     uint32_t* ptotal = (uint32_t*)jh_scratch_acquire(L.scratch, JH_SCR_PC_TOT, (uint64_t)n_paths * 4, 0xffffffffull * 4, L.stream);
     if (!ptotal) return JH_L_SCRATCH;
     const uint32_t ptotal_words = (uint32_t)std::min<uint64_t>(jh_scratch_cap(L.scratch, JH_SCR_PC_TOT) / 4, 0xffffffffull);
-    hipLaunchKernelGGL(k_pc_count, dim3(gl), dim3(JL_WG), 0, L.stream, (const JlBump*)bump, ind, lines, paths, counts, lines_cap, prange,
+    hipLaunchKernelGGL(k_pc_count, dim3(gl), dim3(JL_WG), 0, L.stream, (const JlBump*)bump, ind, lines, paths, wsum, lines_cap, n_waves_dev, prange,
                        n_paths * 2u + 64u, ptotal, n_paths, bd_ctr, L.absorbed.write_indirect ? (JlIndirectCount*)L.indirect : (JlIndirectCount*)nullptr);
     jh_scratch_left_clean(L.scratch, JH_SCR_BD_CTR);  // (k_pc_count zeroes backdrop's counter for the stage that follows)
-    JhResult rc = jh_scan_u32(L, counts, 1, bases, lines_cap, &bump->lines, &bump->seg_counts);
+    JhResult rc = jh_scan_u32(L, wsum, 1, wbase, waves_cap, n_waves_dev, &bump->seg_counts);
     if (rc) return rc;
-    const uint32_t *cpf = pfirst, *cpl = plast, *cc = counts, *cb = bases;
+    const uint32_t *cpf = pfirst, *cpl = plast, *cb = wbase;
     hipLaunchKernelGGL(k_pc_emit, dim3(stride_grid(L, lines_cap, PC_EMIT_GRID_PER_CU)), dim3(JL_WG), 0, L.stream, cfg, (const JlBump*)bump, ind, lines, paths, tile, segc, cb, lines_cap,
                        tile_of, keys, kbig, seg_cap, pfirst, plast, (const uint32_t*)ptotal, n_paths, gate);
     // Big paths only (`gate` = number of tiles if there is one, else 0: the scan then covers 0 elements and the kernels
@@ -1179,7 +1196,7 @@ JhResult jh_launch_path_count(const JhLaunch& L) {
     sc.tile_of = tile_of; sc.list_base = list_base; sc.tiles_cap = tiles_cap; sc.list = list; sc.kbig = kbig; sc.gate = gate; sc.dense = dense;
     sc.dense_cap = dense_cap; sc.blocks = gs;
     hipLaunchKernelGGL(k_pc_rank_small, dim3(gs + stride_grid(L, (uint64_t)n_paths * 64u)), dim3(JL_WG), 0, L.stream, cfg, (const JlBump*)bump, tile,
-                       (const uint32_t*)keys, seg_cap, cpf, cpl, cc, cb, n_paths, segc, sc, ptotal, ptotal_words);
+                       (const uint32_t*)keys, seg_cap, cpf, cpl, n_paths, segc, sc, ptotal, ptotal_words);
     jh_scratch_left_clean(L.scratch, JH_SCR_PC_TOT);
     hipLaunchKernelGGL(k_pc_rank, dim3(gs), dim3(JL_WG), 0, L.stream, cfg, (const JlBump*)bump, tile, (const uint2*)tile_of, seg_cap,
                        (const uint32_t*)list_base, tiles_cap, (const uint32_t*)list, segc, (const uint32_t*)kbig, (const uint32_t*)gate,
